@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoised joint-trajectories/s, 50-step DDIM, H=100, J=20.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|train] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|train] [--batch B] [--full] [--dump-outputs DIR]
 
 ``--mode sample`` (default, BASELINE.json configs[2]): one "step" = one complete 50-step DDIM rollout of a batch of
 B = 4096 trajectories per GPU through ``sd_ddim_sample`` (d=256, L=4, 4 heads, T=100, J=20, M=11 memory tokens),
@@ -15,9 +15,16 @@ N > 1: one process per GPU.  Under ``torch.distributed.run`` (WORLD_SIZE set) th
 plainly as ``python bench.py --gpus N`` the parent launches N fresh ranks itself BEFORE it touches the GPU and exits
 with their exit code.  A world size that disagrees with ``--gpus`` is an error, never a silent 1-GPU run.
 
-Prints ONE JSON line (rank 0) with the contract keys plus ``roofline`` and ``cpu_baseline``; at N = 1 in sample mode
-the line also carries the hipGraph replay of the same rollout, north_star's B = 256 sampling shape and the C2
-training step (each timed after the headline region).
+Prints ONE JSON line (rank 0) with the contract keys.  A plain run does only what that line needs: set-up, warm-up, the
+timed steps.  ``--full`` adds everything else: ``roofline`` (a HIP-event pair around every launch of the timed steps) and
+``cpu_baseline``; at N = 1 in sample mode the hipGraph replay of the same rollout, north_star's B = 256 sampling shape,
+the C2 training step and the image backbone (each timed after the headline region); at N > 1 in train mode the
+all-reduce figures.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as float32 / float64 ``.npy`` files (rank 0;
+the inputs are seeded, so two builds can be compared output for output): sample mode ``trajectories.npy`` (B, T, J), a
+fixed seeded subset of the trajectories when B exceeds DUMP_MAX_BYTES; train mode ``loss.npy`` and ``params.npy`` (the
+flat fp32 parameters after the step).
 """
 
 from __future__ import annotations
@@ -43,6 +50,7 @@ PEAK_F16_MFMA_TFLOPS = 2516.8  # MI355X_MICROARCH.md: BF16/F16 MFMA dense (~2.5 
 PEAK_HBM_GBS = 8000.0
 FUSED_BYTES_PER_TRAJ_STEP = 2 * T * J * 4 + M * D * 4   # x in + eps out + memory = 27 264 B
 TRAIN_B = 256
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: all files together stay under 64 MB
 
 
 def flops_per_traj_step():
@@ -348,6 +356,17 @@ def time_train(leg: TrainLeg, steps: int, warmup: int, dist):
     return elapsed, float(loss)
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 as computed."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def train_chain_roofline(leg: "TrainLeg", step_ms: float, n=4):
     """Roofline of the training step's dominant kernel class - the layer chains: since round 4 the trajectory-owning forward launches
     (sd_train_head_fwd, sd_train_layer_fwd: embedding, both attention cores and every row GEMM of a layer's forward) and the backward
@@ -412,7 +431,7 @@ def train_record(elapsed, steps, world, B, loss, allreduce_ms, dropout, n_params
         "algorithmic_tflops_per_gpu": round(tf / world, 2),
         "frac_of_f16_mfma_peak": round(tf / world / PEAK_F16_MFMA_TFLOPS, 4),
         "frac_of_f32_mfma_peak": round(tf / world / PEAK_F32_MFMA_TFLOPS, 4),
-        "allreduce_ms": round(allreduce_ms, 4), "allreduce_bytes": 4 * n_params,
+        "allreduce_ms": None if allreduce_ms is None else round(allreduce_ms, 4), "allreduce_bytes": 4 * n_params,
         "dropout_p": dropout, "final_loss": round(loss, 6),
     }
 
@@ -432,9 +451,15 @@ def main():
                          "weights); 4 = the opt-in two-product Q|K|V site (max_mode=4 / SD_SAMPLER_MODE=4), its SD_STATUS_SHARP_LOGITS guard "
                          "read after the timed region")
     ap.add_argument("--no-graph", action="store_true", help="train mode: issue the step's launches eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="sample mode: skip the hipGraph / B=256 / training sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: per-launch HIP-event timing of the timed steps and the roofline record, the CPU "
+                         "baseline, at N = 1 in sample mode the sub-records (other_traj_mode, hipgraph, b256, loop_form, train, "
+                         "image_backbone, image_backbone_train), at N > 1 in train mode the all-reduce figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-launch HIP-event timing and the roofline record")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, sample mode: skip the hipGraph / B=256 / training sub-records")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -501,10 +526,14 @@ def run_train(args, rank, world, dev, dist):
     B = args.batch or TRAIN_B
     leg = TrainLeg(dev, rank, world, B, steps + warmup, dropout=args.dropout, graph=not args.no_graph)
     elapsed, loss = time_train(leg, steps, max(warmup, 3 if leg.graphed is not None else 0), dist)   # capture happens on call 3
-    ar = leg.allreduce_ms()
-    ar_exposed = leg.exposed_allreduce_ms() if world > 1 else 0.0
+    if args.dump_outputs and rank == 0:   # before the all-reduce figures below, which step the optimizer further
+        import numpy as np
+
+        dump_outputs(args.dump_outputs, {"loss": np.array([loss], dtype=np.float64), "params": leg.opt.flat_param.detach().cpu().numpy()})
+    ar = leg.allreduce_ms() if args.full or world == 1 else None   # (0.0 at N = 1: nothing to exchange)
+    ar_exposed = (leg.exposed_allreduce_ms() if world > 1 else 0.0) if args.full or world == 1 else None
     chain = None
-    if world == 1 and not args.no_kernel_timing:
+    if world == 1 and args.full and not args.no_kernel_timing:
         try:
             chain = train_chain_roofline(leg, elapsed / steps * 1e3)
         except Exception as e:  # noqa: BLE001 - a sub-record must not take the line down
@@ -514,8 +543,8 @@ def run_train(args, rank, world, dev, dist):
     if rank != 0:
         return
     rec = train_record(elapsed, steps, world, B, loss, ar, leg.dropout, leg.opt.flat_param.numel())
-    rec["allreduce_exposed_ms"] = round(ar_exposed, 4)
-    if world > 1 and ar > 0:   # bus bandwidth of the flat-gradient exchange as RCCL's tests define it: bytes x 2 (N - 1) / N / time
+    rec["allreduce_exposed_ms"] = None if ar_exposed is None else round(ar_exposed, 4)
+    if world > 1 and ar:   # bus bandwidth of the flat-gradient exchange as RCCL's tests define it: bytes x 2 (N - 1) / N / time
         rec["allreduce_busbw_gbs"] = round(rec["allreduce_bytes"] * 2 * (world - 1) / world / (ar * 1e-3) / 1e9, 2)
     if world > 1:
         rec["allreduce_form"] = ("per-layer buckets started from gradient hooks and overlapped with the rest of the backward (training.BucketedAllReduce; "
@@ -545,7 +574,7 @@ def run_train(args, rank, world, dev, dist):
         "world": inventory,
         "cpu_baseline": None,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from soccerdiffusion_amd.synthetic import synthetic_state_dict
 
         line["cpu_baseline"] = cpu_baseline_train(synthetic_state_dict(D, J, L, seed=7))
@@ -553,7 +582,7 @@ def run_train(args, rank, world, dev, dist):
 
 
 def run_sample(args, rank, world, dev, dist):
-    import numpy as np  # noqa: F401
+    import numpy as np
     import torch
 
     from soccerdiffusion_amd import _lib, ops
@@ -586,7 +615,7 @@ def run_sample(args, rank, world, dev, dist):
 
     for _ in range(warmup):
         rollout()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -608,6 +637,13 @@ def run_sample(args, rank, world, dev, dist):
         elapsed = float(tt.item())
     assert torch.isfinite(x).all(), "sampler produced non-finite values"
     assert int(guard.item()) == 0, "sampler range guard tripped (non-finite sample, or mode 4 outside its validated logit range)"
+    if args.dump_outputs and rank == 0:
+        out = x
+        if x.numel() * x.element_size() > DUMP_MAX_BYTES:   # a fixed, seeded subset of the trajectories
+            keep = DUMP_MAX_BYTES // (x[0].numel() * x.element_size())
+            rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+            out = x[torch.from_numpy(rows).to(dev)]
+        dump_outputs(args.dump_outputs, {"trajectories": out.cpu().numpy()})
 
     roofline = None
     if timing:
@@ -621,7 +657,7 @@ def run_sample(args, rank, world, dev, dist):
     if rank != 0:
         return
     extras = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         extras = sample_extras(ops, packed, toks, coef, x_T, ctx, x, sd, dev, mode, guard)
     value = world * B * steps / elapsed
     line = {
@@ -641,16 +677,17 @@ def run_sample(args, rank, world, dev, dist):
             "workload": "BASELINE.json configs[2]: 50-step DDIM sampling, B=%d parallel rollouts per GPU, "
                         "transformer denoiser d=256 L=4 heads=4, horizon T=100, J=20, memory M=11 "
                         "(10 context tokens + step token); one step = one full rollout; the timed region issues the rollout's "
-                        "launches eagerly with a HIP-event pair around each (the roofline leg); the hipGraph replay of the same "
-                        "rollout is timed right after it (`hipgraph`).  Kernel selection: sampler mode %d (--sampler-mode; "
-                        "`other_traj_mode` holds the same rollout in the other trajectory-kernel mode)" % (B, mode),
+                        "launches eagerly%s%s.  Kernel selection: sampler mode %d (--sampler-mode%s)"
+                        % (B, " with a HIP-event pair around each (the roofline leg)" if timing else "",
+                           "; the hipGraph replay of the same rollout is timed right after it (`hipgraph`)" if extras else "", mode,
+                           "; `other_traj_mode` holds the same rollout in the other trajectory-kernel mode" if "other_traj_mode" in extras else ""),
             "batch_per_gpu": B, "ddim_steps": N_DDIM, "horizon": T, "joints": J, "hidden_dim": D,
             "decoder_layers": L, "memory_tokens": M, "parallelism": f"dp{world} (independent rollouts, no collective)",
         },
         "roofline": roofline,
         "world": inventory,
         **extras,
-        "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(sd),
+        "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(sd),
     }
     print(json.dumps(line), flush=True)
 

@@ -133,7 +133,8 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(mode):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SD_BENCH_SHARE_GPU"] = "1"
-    args = ["--gpus", "2", "--mode", mode, "--steps", "2", "--warmup", "1", "--batch", "64" if mode == "sample" else "16", "--no-cpu-baseline"]
+    args = ["--gpus", "2", "--mode", mode, "--steps", "2", "--warmup", "1", "--batch", "64" if mode == "sample" else "16", "--full",
+            "--no-cpu-baseline"]
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), *args], env=env, capture_output=True, text=True, timeout=580)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

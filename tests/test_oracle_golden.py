@@ -20,8 +20,14 @@ def test_step_token_int_and_float(g1):
 
 
 def test_positional_table(g1):
+    """Element by element, to the last bits torch's CPU exp / sin / cos can move: they go through MKL's vector math, whose code
+    path depends on the host CPU (the golden table was recorded on one; on another the same code differs by up to 4 ulp of 1.0).
+    A 1-ulp change of a frequency moves pos * div (< 16 here) by at most 1 ulp, 9.5e-7; a base off by 1e-4 already moves the table
+    by 6e-5, a position offset or swapped sin / cos by O(1)."""
     c = g1["config"]
-    assert torch.equal(ref.positional_table(c["d"], c["T"]), g1["pe"])
+    got, want = ref.positional_table(c["d"], c["T"]), g1["pe"]
+    assert got.dtype == want.dtype and got.shape == want.shape
+    assert float((got - want).abs().max()) <= 1e-6
 
 
 def test_decoder_forward(g1):

@@ -569,6 +569,43 @@ size_t sd_conv_wgrad_scratch_floats(int N, int H, int W, int Cin, int Cout, int 
 int sd_conv_wgrad(const float *dy, const float *x, const uint32_t *dy_amax, const uint32_t *x_amax, float *dw, float *scratch, int N, int H, int W,
                   int Cin, int Cout, int ksize, int stride, void *stream);
 
+/* ---- Swin-T / Swin-S image encoder, inference (reference option image_encoder_type "swin_transformer_tiny" / "swin_transformer_small":
+ * soccer_diffusion/ml/model/encoder/image.py:11-20, 86-100; torchvision.models.swin_transformer V1 as restated in
+ * soccerdiffusion_amd/ml/model/encoder/image.py, _ShiftedWindowAttention / _SwinBlock / _PatchMerging / _SwinTransformer).  Tokens are NHWC fp32
+ * rows (N * H * W, C).  Products on split fp16 operands (three v_mfma_f32_16x16x32_f16, fp32 accumulation; csrc/sd_swin.hip), LayerNorm /
+ * erf-GELU / softmax in fp32.
+ *   sd_token_pack: W (N, K) fp32 (nn.Linear.weight), K a multiple of 32 -> sd_token_packed_halfs(N, K) fp16 values in fragment order and
+ *     w_inv (sd_token_pad_cols(N) floats): the inverse power-of-two scale of each weight row.  Once per weight update.
+ *   sd_token_linear: out (R, N) = epi(pro(A) W^T + bias); A (R, K) 16-byte aligned, any R.  pro: LayerNorm over K with ln_w / ln_b (both NULL:
+ *     none; K <= 1536 with it); epi: erf-GELU if gelu, then + res (R, N) (NULL: none; res may equal out: the residual add in place).
+ *   sd_token_merge_linear: the same GEMM (no bias, no epilogue) on torchvision PatchMerging's A operand, gathered in the load: x (Nimg, H, W, C)
+ *     -> rows of cat(x[0::2, 0::2], x[1::2, 0::2], x[0::2, 1::2], x[1::2, 1::2]) (zero padding for an odd H or W), K = 4 C <= 1536, LayerNorm
+ *     over K -> out (Nimg, ceil(H/2), ceil(W/2), N).
+ *   sd_swin_window_plan: plan6 = (pH, pW, sh, sw, nWy, nWx) of _ShiftedWindowAttention.forward: the map padded to whole windows, the shift
+ *     per dimension (0 where the window covers the padded map), the window counts.
+ *   sd_swin_window_attention: qkv (Nimg * H * W, 3 C) = the qkv Linear's output on the un-padded, un-rolled map -> out (Nimg * H * W, C): the
+ *     shifted-window attention before proj, heads = C / 32 (head dimension 32), window <= 8.  Window token (i, j) of window (wy, wx) is position
+ *     ((wy w + i + sh) mod pH, (wx w + j + sw) mod pW); a position past H / W is padding: its q / k / v are qkv_bias (3 C), it is NOT masked as a
+ *     key, its output is dropped.  Adds table[rpi[q w^2 + k]][head] (relative_position_bias_table ((2w-1)^2, heads), relative_position_index
+ *     (w^2 * w^2) int64) and, when a shift is nonzero, -100 between tokens of different regions of the rolled map.
+ *   sd_swin_patch_embed: x (Nimg, 3, H, W) NCHW frames -> out (Nimg, H/4, W/4, 96): conv 4 x 4 / stride 4 (w (96, 3, 4, 4), bias (96)) and
+ *     LayerNorm(96) in one launch (fp32 FMA: K = 48).
+ *   sd_swin_head_pool: x (Nimg, T, C) -> pooled (Nimg, C) = mean over the T tokens of LayerNorm(x); C a multiple of 64, <= 1024.  The head
+ *     Linear follows as sd_token_linear. */
+size_t sd_token_packed_halfs(int N, int K);
+int sd_token_pad_cols(int N);
+int sd_token_pack(const float *w, int N, int K, void *planes, float *w_inv, void *stream);
+int sd_token_linear(const float *A, const void *planes, const float *w_inv, const float *bias, const float *ln_w, const float *ln_b, float ln_eps,
+                    const float *res, float *out, int64_t R, int N, int K, int gelu, void *stream);
+int sd_token_merge_linear(const float *x, int Nimg, int H, int W, int C, const void *planes, const float *w_inv, const float *ln_w, const float *ln_b,
+                          float ln_eps, float *out, int N, void *stream);
+int sd_swin_window_plan(int H, int W, int window, int shift, int *plan6);
+int sd_swin_window_attention(const float *qkv, const float *qkv_bias, const float *table, const int64_t *rpi, float *out, int Nimg, int H, int W,
+                             int C, int heads, int window, int shift, void *stream);
+int sd_swin_patch_embed(const float *x, const float *w, const float *bias, const float *ln_w, const float *ln_b, float ln_eps, float *out, int Nimg,
+                        int H, int W, void *stream);
+int sd_swin_head_pool(const float *x, const float *ln_w, const float *ln_b, float ln_eps, float *pooled, int Nimg, int T, int C, void *stream);
+
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair
  * on the launch stream.  sd_profile_collect waits for them, returns the summed device

@@ -177,6 +177,15 @@ SIGNATURES = {
     "sd_stem_packed_halfs": (C.c_size_t, []),
     "sd_stem_pack": (C.c_int, [C.c_void_p] * 5),
     "sd_stem_conv_bn_relu_pool": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_void_p]),
+    "sd_token_packed_halfs": (C.c_size_t, [C.c_int, C.c_int]),
+    "sd_token_pad_cols": (C.c_int, [C.c_int]),
+    "sd_token_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sd_token_linear": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sd_token_merge_linear": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_swin_window_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
+    "sd_swin_window_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]),
+    "sd_swin_patch_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "sd_swin_head_pool": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

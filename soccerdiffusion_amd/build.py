@@ -17,7 +17,7 @@ REPO = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", "sd_kernels.hip"), os.path.join(PKG, "csrc", "sd_train.hip"),
        os.path.join(PKG, "csrc", "sd_train_chain.hip"), os.path.join(PKG, "csrc", "sd_conv.hip"),
        os.path.join(PKG, "csrc", "sd_train_traj.hip"), os.path.join(PKG, "csrc", "sd_trajg.hip"),
-       os.path.join(PKG, "csrc", "sd_conv_train.hip")]
+       os.path.join(PKG, "csrc", "sd_conv_train.hip"), os.path.join(PKG, "csrc", "sd_swin.hip")]
 HDR = [os.path.join(REPO, "include", "soccerdiffusion_hip.h"), os.path.join(PKG, "csrc", "sd_common.h"),
        os.path.join(PKG, "csrc", "sd_panel.h"), os.path.join(PKG, "csrc", "sd_f16x3.h"), os.path.join(PKG, "csrc", "sd_traj.h"),
        os.path.join(PKG, "csrc", "sd_trajg.h")]
@@ -43,12 +43,12 @@ def _obj(src: str) -> str:
 
 
 def _deps(src: str) -> list:
-    """sd_f16x3.h and sd_traj.h are included by sd_kernels.hip only, sd_panel.h not by sd_train.hip."""
+    """sd_f16x3.h and sd_traj.h are included by sd_kernels.hip only, sd_panel.h not by sd_train.hip (nor by the image-path units)."""
     hdr = [h for h in HDR if not (h.endswith("sd_f16x3.h") and not src.endswith("sd_kernels.hip"))
            and not (h.endswith("sd_trajg.h") and not (src.endswith("sd_kernels.hip") or src.endswith("sd_trajg.hip")))
            and not (h.endswith("sd_traj.h") and not (src.endswith("sd_kernels.hip") or src.endswith("sd_train_traj.hip")))
            and not (h.endswith("sd_panel.h") and (src.endswith("sd_train.hip") or src.endswith("sd_conv.hip") or src.endswith("sd_conv_train.hip")
-                                                 or src.endswith("sd_trajg.hip")))]
+                                                 or src.endswith("sd_trajg.hip") or src.endswith("sd_swin.hip")))]
     return [src] + hdr
 
 

@@ -13,8 +13,15 @@ convolution (``sd_conv3x3_bn_act``), the stride-2 stage entries and 1 x 1 shortc
 epilogues (``SD_CONV=torch`` in the environment keeps ``torch.nn``).
 TRAINING (a tape, or ``train()`` mode): see ``_ResNet.forward``.
 Pretrained ImageNet weights cannot be fetched offline (``weights=...DEFAULT`` in the
-reference): load them from a reference checkpoint.  The Swin-T/S encoders are restated with
-torch ops (shifted-window attention); every shipped YAML uses resnet18.
+reference): load them from a reference checkpoint.  The Swin-T/S encoders are torchvision's
+Swin V1 restated attribute for attribute (shifted-window attention in torch ops).  INFERENCE (the
+same gate as the ResNets: eval mode, no tape, fp32 CUDA tensors; ``SD_SWIN=torch`` keeps the torch
+ops) runs the whole Swin backbone on csrc/sd_swin.hip with NHWC tokens: patch embedding + LayerNorm
+in one launch (``sd_swin_patch_embed``), per block qkv with norm1 in the GEMM prologue, the
+shifted-window attention on the un-padded, un-rolled map (``sd_swin_window_attention``), proj +
+residual, fc1 with norm2 and GELU, fc2 + residual (``sd_token_linear``), patch merging's gather and
+LayerNorm inside its GEMM (``sd_token_merge_linear``), the final LayerNorm + mean over the tokens
+(``sd_swin_head_pool``) and the head.  Training keeps the torch ops.  Every shipped YAML uses resnet18.
 """
 
 from __future__ import annotations
@@ -333,6 +340,16 @@ class _ShiftedWindowAttention(nn.Module):
         return x[:, :H, :W, :].contiguous()
 
 
+def _token_packed(lin: nn.Linear) -> "ops.PackedTokenLinear":
+    """The split fp16 planes of a Linear for sd_token_linear, cached off-module and repacked when the weight's version or
+    ops.weights_generation() (FusedAdamW's version-less updates) moves."""
+    store = _derived(lin)
+    pk = store.get("tok")
+    if pk is None or pk.device != lin.weight.device:
+        pk = store["tok"] = ops.PackedTokenLinear(lin.weight)
+    return pk.refresh(lin.weight)
+
+
 class _StochasticDepth(nn.Module):       # torchvision.ops.StochasticDepth(p, "row")
     def __init__(self, p: float):
         super().__init__()
@@ -359,6 +376,18 @@ class _SwinBlock(nn.Module):
         x = x + self.stochastic_depth(self.attn(self.norm1(x)))
         return x + self.stochastic_depth(self.mlp(self.norm2(x)))
 
+    def forward_hip(self, h: torch.Tensor) -> torch.Tensor:
+        """Inference on the hand-written kernels (csrc/sd_swin.hip), five launches: qkv (norm1 in its prologue), the shifted-window
+        attention (no padded or rolled tensor), proj + residual and fc2 + residual IN PLACE on h (N, H, W, C) - a token tensor of the
+        backbone's own forward - and fc1 (norm2 in its prologue, erf-GELU in its epilogue)."""
+        a, fc1, fc2 = self.attn, self.mlp[0], self.mlp[3]
+        qkv = ops.token_linear(h, _token_packed(a.qkv), a.qkv.bias, ln=(self.norm1.weight, self.norm1.bias, self.norm1.eps))
+        qkv_bias = a.qkv.bias if a.qkv.bias is not None else torch.zeros(a.qkv.out_features, device=h.device)
+        o = ops.swin_window_attention(qkv, a.heads, a.window, a.shift, qkv_bias, a.relative_position_bias_table, a.relative_position_index)
+        ops.token_linear(o, _token_packed(a.proj), a.proj.bias, res=h, out=h)
+        u = ops.token_linear(h, _token_packed(fc1), fc1.bias, ln=(self.norm2.weight, self.norm2.bias, self.norm2.eps), gelu=True)
+        return ops.token_linear(u, _token_packed(fc2), fc2.bias, res=h, out=h)
+
 
 class _PatchMerging(nn.Module):
     def __init__(self, dim):
@@ -371,6 +400,10 @@ class _PatchMerging(nn.Module):
         x = nn.functional.pad(x, (0, 0, 0, W % 2, 0, H % 2))
         x = torch.cat([x[..., 0::2, 0::2, :], x[..., 1::2, 0::2, :], x[..., 0::2, 1::2, :], x[..., 1::2, 1::2, :]], -1)
         return self.reduction(self.norm(x))
+
+    def forward_hip(self, h: torch.Tensor) -> torch.Tensor:
+        """Inference: the 2 x 2 gather and the LayerNorm inside the operand load of the reduction GEMM (sd_token_merge_linear), one launch."""
+        return ops.token_merge_linear(h, _token_packed(self.reduction), (self.norm.weight, self.norm.bias, self.norm.eps))
 
 
 class _Permute(nn.Module):
@@ -412,7 +445,26 @@ class _SwinTransformer(nn.Module):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
+    def _hip_inference(self, x: torch.Tensor) -> bool:
+        # fp32 only, as _ResNet._hip_inference; no autograd tape (training / fine-tuning keeps torch ops); SD_SWIN=torch keeps them too
+        stem = self.features[0][0]
+        return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and stem.weight.dtype == torch.float32
+                and self.head.weight.dtype == torch.float32 and not self.training and not torch.is_grad_enabled()
+                and os.environ.get("SD_SWIN", "hip") != "torch")
+
     def forward(self, x):
+        if self._hip_inference(x):
+            # the whole backbone on the hand-written kernels (csrc/sd_swin.hip), NHWC tokens end to end: patch embedding + LayerNorm (one
+            # launch), five launches per block, one per patch merging, LayerNorm + mean over the tokens and the head (two)
+            stem, ln = self.features[0][0], self.features[0][2]
+            h = ops.swin_patch_embed(x.contiguous(), stem.weight, stem.bias, (ln.weight, ln.bias, ln.eps))
+            for m in self.features[1:]:
+                if isinstance(m, _PatchMerging):
+                    h = m.forward_hip(h)
+                else:
+                    for blk in m:
+                        h = blk.forward_hip(h)
+            return ops.swin_head(h, (self.norm.weight, self.norm.bias, self.norm.eps), _token_packed(self.head), self.head.bias)
         return self.head(self.flatten(self.avgpool(self.permute(self.norm(self.features(x))))))
 
 

@@ -1101,3 +1101,186 @@ def stem_conv_bn_relu_pool(x: Tensor, x_amax: Tensor, w: PackedStem, bn_scale: T
                                                 bn_shift.data_ptr(), y.data_ptr(), _ptr(y_amax), N, H, W, _stream()),
           "sd_stem_conv_bn_relu_pool")
     return y
+
+
+# ---- image path: Swin-T / Swin-S inference (csrc/sd_swin.hip) -------------------------------------------
+def swin_window_plan(H: int, W: int, window: int, shift: int) -> tuple:
+    """(pH, pW, sh, sw, nWy, nWx) of torchvision's shifted-window attention on an H x W map (ml/model/encoder/image.py,
+    _ShiftedWindowAttention.forward): the map padded at the bottom / right to whole windows, the shift per dimension (0 where one window covers
+    the padded map) and the window counts.  The same rule as the C host code of sd_swin_window_attention (sd_swin_window_plan)."""
+    if H <= 0 or W <= 0 or window <= 0 or shift < 0:
+        raise ValueError("positive map and window, non-negative shift")
+    pH, pW = H + (window - H % window) % window, W + (window - W % window) % window
+    return pH, pW, 0 if window >= pH else shift, 0 if window >= pW else shift, pH // window, pW // window
+
+
+def _swin_req(t: Tensor, name: str, device=None, dtype=torch.float32, aligned: bool = False) -> Tensor:
+    """Argument check of the Swin entry points: ValueError (never a launch) for a CPU tensor, another dtype or device, a strided view; ``aligned``:
+    a 16-byte aligned start (the activation operands the kernels read 16 bytes at a time - parameters are read element-wise: an optimizer's flat
+    buffer places them anywhere)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a tensor on the MI355X (cuda) device")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: on {t.device}, expected {device}")
+    if aligned and t.data_ptr() % 16:
+        raise ValueError(f"{name}: expected a 16-byte aligned tensor")
+    return t
+
+
+def _version_key(t: Tensor):
+    """t._version, or None for a tensor without a version counter (an inference tensor): such a weight is repacked on every call."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
+
+
+def _swin_ln(ln, K: int, device, name: str):
+    if ln is None:
+        return None, None, 1e-5
+    g, b, eps = ln
+    for t, n in ((g, f"{name} weight"), (b, f"{name} bias")):
+        _swin_req(t, n, device)
+        if t.numel() != K:
+            raise ValueError(f"{n}: {t.numel()} values, expected {K}")
+    return g.data_ptr(), b.data_ptr(), float(eps)
+
+
+class PackedTokenLinear:
+    """An nn.Linear weight (N, K), K a multiple of 32, in the fragment order of ``sd_token_linear`` (split fp16 planes) plus the inverse
+    power-of-two scale of each row; repacked when the weight's version counter or ``weights_generation()`` moves."""
+
+    def __init__(self, weight: Tensor):
+        lib = _lib.load()
+        w = weight.detach()
+        _swin_req(w, "weight")
+        if w.dim() != 2 or w.shape[1] % 32 or w.shape[0] <= 0:
+            raise ValueError(f"weight (N, K) with K a multiple of 32, got {tuple(w.shape)}")
+        self.N, self.K = int(w.shape[0]), int(w.shape[1])
+        self.device = w.device
+        self.planes = torch.empty(lib.sd_token_packed_halfs(self.N, self.K), dtype=torch.float16, device=w.device)
+        self.w_inv = torch.empty(lib.sd_token_pad_cols(self.N), dtype=torch.float32, device=w.device)
+        self.version = None
+        self.refresh(weight)
+
+    def refresh(self, weight: Tensor) -> "PackedTokenLinear":
+        key = (_version_key(weight), weight.data_ptr(), _weights_generation)
+        if self.version != key or key[0] is None:
+            w = weight.detach()
+            _swin_req(w, "weight", self.device)
+            if tuple(w.shape) != (self.N, self.K):
+                raise ValueError("weight shape changed")
+            check(_lib.load().sd_token_pack(w.data_ptr(), self.N, self.K, self.planes.data_ptr(), self.w_inv.data_ptr(), _stream()),
+                  "sd_token_pack")
+            self.version = key
+        return self
+
+
+def token_linear(A: Tensor, w: PackedTokenLinear, bias: Optional[Tensor] = None, ln: Optional[tuple] = None, gelu: bool = False,
+                 res: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """out (..., N) = [+ res] [gelu] (LayerNorm?(A) W^T + bias) for token rows A (..., K): the Swin block's qkv (``ln`` = (norm1.weight,
+    norm1.bias, eps)), proj (+ residual), fc1 (norm2, ``gelu``: erf-GELU), fc2 (+ residual) and the head, one launch.  ``res`` may be ``out``
+    itself (the residual add in place)."""
+    dev = w.device
+    _swin_req(A, "A", dev, aligned=True)
+    if A.dim() < 1 or A.shape[-1] != w.K:
+        raise ValueError(f"A: last dimension {A.shape[-1] if A.dim() else None}, expected K = {w.K}")
+    R = A.numel() // w.K
+    if R <= 0:
+        raise ValueError("A: no rows")
+    if ln is not None and w.K > 1536:
+        raise ValueError("the LayerNorm prologue takes K <= 1536")
+    shape = (*A.shape[:-1], w.N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(_swin_req(out, "out", dev).shape) != shape:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected {shape}")
+    if bias is not None and _swin_req(bias, "bias", dev).numel() != w.N:
+        raise ValueError(f"bias: {bias.numel()} values, expected {w.N}")
+    if res is not None:
+        if tuple(_swin_req(res, "res", dev).shape) != shape:
+            raise ValueError(f"res: shape {tuple(res.shape)}, expected {shape}")
+        if res.data_ptr() != out.data_ptr() and res.data_ptr() < out.data_ptr() + out.numel() * 4 and out.data_ptr() < res.data_ptr() + res.numel() * 4:
+            raise ValueError("res overlaps out without being out")
+    if A.data_ptr() < out.data_ptr() + out.numel() * 4 and out.data_ptr() < A.data_ptr() + A.numel() * 4:
+        raise ValueError("A overlaps out")
+    g, b, eps = _swin_ln(ln, w.K, dev, "ln")
+    check(_lib.load().sd_token_linear(A.data_ptr(), w.planes.data_ptr(), w.w_inv.data_ptr(), _ptr(bias), g, b, eps, _ptr(res), out.data_ptr(),
+                                      R, w.N, w.K, int(bool(gelu)), _stream()), "sd_token_linear")
+    return out
+
+
+def token_merge_linear(x: Tensor, w: PackedTokenLinear, ln: tuple) -> Tensor:
+    """torchvision PatchMerging on NHWC tokens: x (N, H, W, C) -> reduction(norm(cat(x[0::2, 0::2], x[1::2, 0::2], x[0::2, 1::2],
+    x[1::2, 1::2]))) (N, ceil(H/2), ceil(W/2), w.N), the 2 x 2 gather (zero padding for an odd H / W) inside the GEMM's operand load."""
+    dev = w.device
+    _swin_req(x, "x", dev, aligned=True)
+    if x.dim() != 4 or 4 * x.shape[3] != w.K or x.shape[3] % 32:
+        raise ValueError(f"x (N, H, W, C) with 4 C = {w.K}, C a multiple of 32; got {tuple(x.shape)}")
+    if w.K > 1536:
+        raise ValueError("the LayerNorm prologue takes 4 C <= 1536")
+    N, H, W, Cc = x.shape
+    g, b, eps = _swin_ln(ln, w.K, dev, "ln")
+    out = torch.empty(N, (H + 1) // 2, (W + 1) // 2, w.N, dtype=torch.float32, device=dev)
+    check(_lib.load().sd_token_merge_linear(x.data_ptr(), N, H, W, Cc, w.planes.data_ptr(), w.w_inv.data_ptr(), g, b, eps, out.data_ptr(), w.N,
+                                            _stream()), "sd_token_merge_linear")
+    return out
+
+
+def swin_window_attention(qkv: Tensor, heads: int, window: int, shift: int, qkv_bias: Tensor, table: Tensor, index: Tensor) -> Tensor:
+    """torchvision's shifted-window attention before proj, with no rolled or padded tensor: qkv (N, H, W, 3 C) - the qkv Linear of the
+    un-padded map - -> (N, H, W, C); head dimension 32 (C = 32 heads), window <= 8.  ``table`` / ``index``: the module's
+    relative_position_bias_table ((2 window - 1)^2, heads) and relative_position_index (window^4,) int64."""
+    dev = qkv.device
+    _swin_req(qkv, "qkv", aligned=True)
+    if qkv.dim() != 4 or qkv.shape[3] % 3:
+        raise ValueError(f"qkv (N, H, W, 3 C), got {tuple(qkv.shape)}")
+    N, H, W, C3 = qkv.shape
+    C = C3 // 3
+    if C != 32 * heads:
+        raise ValueError(f"head dimension 32: C = {C} for {heads} heads")
+    if not 1 <= window <= 8 or not 0 <= shift < window:
+        raise ValueError("window 1 .. 8, 0 <= shift < window")
+    if _swin_req(qkv_bias, "qkv_bias", dev).numel() != C3:
+        raise ValueError("qkv_bias: 3 C values")
+    if tuple(_swin_req(table, "table", dev).shape) != ((2 * window - 1) ** 2, heads):
+        raise ValueError(f"table: shape {tuple(table.shape)}, expected {((2 * window - 1) ** 2, heads)}")
+    if _swin_req(index, "index", dev, torch.int64).numel() != window ** 4:
+        raise ValueError("index: window^4 entries")
+    out = torch.empty(N, H, W, C, dtype=torch.float32, device=dev)
+    check(_lib.load().sd_swin_window_attention(qkv.data_ptr(), qkv_bias.data_ptr(), table.data_ptr(), index.data_ptr(), out.data_ptr(), N, H, W, C,
+                                               heads, window, shift, _stream()), "sd_swin_window_attention")
+    return out
+
+
+def swin_patch_embed(x: Tensor, weight: Tensor, bias: Tensor, ln: tuple) -> Tensor:
+    """Swin's stem: LayerNorm(conv4x4/s4(x) + bias) from NCHW frames x (N, 3, H, W) to NHWC tokens (N, H // 4, W // 4, 96), one launch."""
+    dev = x.device
+    _swin_req(x, "x")   # (element-wise loads: any view of the frames)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] < 4 or x.shape[3] < 4:
+        raise ValueError(f"x (N, 3, H, W) with H, W >= 4, got {tuple(x.shape)}")
+    if tuple(_swin_req(weight, "weight", dev).shape) != (96, 3, 4, 4) or _swin_req(bias, "bias", dev).numel() != 96:
+        raise ValueError("the patch embedding is Conv2d(3, 96, 4, stride 4) with bias")
+    g, b, eps = _swin_ln(ln, 96, dev, "ln")
+    N, _, H, W = x.shape
+    out = torch.empty(N, H // 4, W // 4, 96, dtype=torch.float32, device=dev)
+    check(_lib.load().sd_swin_patch_embed(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), g, b, eps, out.data_ptr(), N, H, W, _stream()),
+          "sd_swin_patch_embed")
+    return out
+
+
+def swin_head(x: Tensor, ln: tuple, w: PackedTokenLinear, bias: Optional[Tensor]) -> Tensor:
+    """Swin's head on NHWC tokens x (N, H, W, C): head(mean over H W of norm(x)) -> (N, w.N); two launches (LayerNorm + mean, the Linear)."""
+    dev = w.device
+    _swin_req(x, "x", dev)
+    if x.dim() != 4 or x.shape[3] != w.K or x.shape[3] % 64 or x.shape[3] > 1024:
+        raise ValueError(f"x (N, H, W, C) with C = {w.K} a multiple of 64 up to 1024, got {tuple(x.shape)}")
+    N, H, W, Cc = x.shape
+    g, b, eps = _swin_ln(ln, Cc, dev, "ln")
+    pooled = torch.empty(N, Cc, dtype=torch.float32, device=dev)
+    check(_lib.load().sd_swin_head_pool(x.data_ptr(), g, b, eps, pooled.data_ptr(), N, H * W, Cc, _stream()), "sd_swin_head_pool")
+    return token_linear(pooled, w, bias)

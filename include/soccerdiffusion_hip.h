@@ -606,6 +606,41 @@ int sd_swin_patch_embed(const float *x, const float *w, const float *bias, const
                         int H, int W, void *stream);
 int sd_swin_head_pool(const float *x, const float *ln_w, const float *ln_b, float ln_eps, float *pooled, int Nimg, int T, int C, void *stream);
 
+/* ---- image feed: the reference's frame preprocessing (soccer_diffusion/dataset/pytorch.py:209-211: cv2.resize(frame, (R, R),
+ * interpolation=cv2.INTER_AREA), then torchvision's ToDtype(float32, scale=True) and Normalize(ImageNet mean, std)), csrc/sd_frames.hip.
+ *   sd_frames_area: store (n_frames, 480, 480, 3) uint8 (the recordings' frames), 16-byte aligned; index (n_slots) int64 into it, -1 (any
+ *     index outside [0, n_frames)) = a zero frame -> out (n_slots, 3, R, R) fp32, 1 <= R <= 480, one launch.  An integer factor 480 / R
+ *     takes OpenCV's resizeAreaFast (taps / weights unused, may be NULL); any other R takes resizeArea with computeResizeAreaTab's table
+ *     of one axis (both axes are 480 -> R): taps (3 R) int32 = first source index, tap count, offset into weights per output index;
+ *     weights (n_weights <= 1440) fp32.  fp32 without FMA contraction, round half to even. */
+/* ---- the ResNet encoder heads (soccer_diffusion/ml/model/encoder/image.py:61-83), csrc/sd_head.hip: avgpool -> fc, or the no-avgpool
+ * head's Conv2d(C, 32, 1) + bias flattened in NCHW order -> fc, forward and backward, from the last block's NHWC map.
+ *   sd_head_gemm: C (M x N) = A (M x K) B (K x N) (+ bias (N)), or C += that with accumulate; fp32 FMA.  Element (i, j) of an operand is
+ *     ptr[off(i, row_div, row_s1, row_s0) + off(j, col_div, col_s1, col_s0)], off(i, d, s1, s0) = (i / d) s1 + (i % d) s0, or i s0 for d = 0
+ *     (s0 = 0: a broadcast scalar, e.g. a single 1.0f for a column sum).  scratch: sd_head_gemm_scratch_floats(M, N, K) floats (0: none
+ *     needed; NULL: one pass) - a long reduction with few output tiles is split over workgroups into it and summed by a second launch in a
+ *     fixed order: deterministic, no atomics.
+ *   sd_head_pool: pooled (N, C) = mean over the HW pixels of x (N, HW, C);  sd_head_pool_bwd: dx (N, HW, C) = dpooled (N, C) / HW. */
+typedef struct sd_strided_operand {
+    float *ptr;
+    int64_t row_div, row_s1, row_s0;
+    int64_t col_div, col_s1, col_s0;
+} sd_strided_operand;
+typedef struct sd_head_gemm_args {
+    int64_t M, N, K;
+    sd_strided_operand A, B, C;
+    const float *bias;
+    float *scratch;
+    int32_t accumulate, _pad;
+} sd_head_gemm_args;
+size_t sd_head_gemm_scratch_floats(int64_t M, int64_t N, int64_t K);
+int sd_head_gemm(const sd_head_gemm_args *args, void *stream);
+int sd_head_pool(const float *x, float *pooled, int N, int HW, int C, void *stream);
+int sd_head_pool_bwd(const float *dpooled, float *dx, int N, int HW, int C, void *stream);
+
+int sd_frames_area(const uint8_t *store, int64_t n_frames, const int64_t *index, int64_t n_slots, int R, const int32_t *taps, const float *weights,
+                   int n_weights, float *out, void *stream);
+
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair
  * on the launch stream.  sd_profile_collect waits for them, returns the summed device

@@ -91,6 +91,19 @@ class GemmTnProblem(C.Structure):
                 + [("R", C.c_int64), ("N", C.c_int32), ("K", C.c_int32), ("ldy", C.c_int32), ("ldx", C.c_int32), ("ldw", C.c_int32)])
 
 
+class StridedOperand(C.Structure):
+    """sd_strided_operand (field order = header order)."""
+
+    _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int64) for n in ("row_div", "row_s1", "row_s0", "col_div", "col_s1", "col_s0")]
+
+
+class HeadGemmArgs(C.Structure):
+    """sd_head_gemm_args (field order = header order)."""
+
+    _fields_ = ([(n, C.c_int64) for n in ("M", "N", "K")] + [(n, StridedOperand) for n in ("A", "B", "C")]
+                + [("bias", C.c_void_p), ("scratch", C.c_void_p), ("accumulate", C.c_int32), ("_pad", C.c_int32)])
+
+
 # name -> (restype, argtypes); mirrors the header one to one (tests check the export list)
 SIGNATURES = {
     "sd_abi_version": (C.c_int, []),
@@ -186,6 +199,11 @@ SIGNATURES = {
     "sd_swin_window_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]),
     "sd_swin_patch_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "sd_swin_head_pool": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "sd_head_gemm_scratch_floats": (C.c_size_t, [C.c_int64] * 3),
+    "sd_head_gemm": (C.c_int, [C.POINTER(HeadGemmArgs), C.c_void_p]),
+    "sd_head_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sd_head_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sd_frames_area": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

@@ -17,7 +17,8 @@ REPO = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", "sd_kernels.hip"), os.path.join(PKG, "csrc", "sd_train.hip"),
        os.path.join(PKG, "csrc", "sd_train_chain.hip"), os.path.join(PKG, "csrc", "sd_conv.hip"),
        os.path.join(PKG, "csrc", "sd_train_traj.hip"), os.path.join(PKG, "csrc", "sd_trajg.hip"),
-       os.path.join(PKG, "csrc", "sd_conv_train.hip"), os.path.join(PKG, "csrc", "sd_swin.hip")]
+       os.path.join(PKG, "csrc", "sd_conv_train.hip"), os.path.join(PKG, "csrc", "sd_swin.hip"), os.path.join(PKG, "csrc", "sd_frames.hip"),
+       os.path.join(PKG, "csrc", "sd_head.hip")]
 HDR = [os.path.join(REPO, "include", "soccerdiffusion_hip.h"), os.path.join(PKG, "csrc", "sd_common.h"),
        os.path.join(PKG, "csrc", "sd_panel.h"), os.path.join(PKG, "csrc", "sd_f16x3.h"), os.path.join(PKG, "csrc", "sd_traj.h"),
        os.path.join(PKG, "csrc", "sd_trajg.h")]
@@ -48,7 +49,8 @@ def _deps(src: str) -> list:
            and not (h.endswith("sd_trajg.h") and not (src.endswith("sd_kernels.hip") or src.endswith("sd_trajg.hip")))
            and not (h.endswith("sd_traj.h") and not (src.endswith("sd_kernels.hip") or src.endswith("sd_train_traj.hip")))
            and not (h.endswith("sd_panel.h") and (src.endswith("sd_train.hip") or src.endswith("sd_conv.hip") or src.endswith("sd_conv_train.hip")
-                                                 or src.endswith("sd_trajg.hip") or src.endswith("sd_swin.hip")))]
+                                                 or src.endswith("sd_trajg.hip") or src.endswith("sd_swin.hip") or src.endswith("sd_frames.hip")
+                                                 or src.endswith("sd_head.hip")))]
     return [src] + hdr
 
 

@@ -110,8 +110,9 @@ class DataSource:
         return {k: v[idx.to(dev)] for k, v in self.tensors.items()}
 
 
-def open_database(path: str, params: dict):
-    """The reference's SQLite database (dataset/models.py schema) through the pre-extracting feed."""
+def open_database(path: str, params: dict, device=None):
+    """The reference's SQLite database (dataset/models.py schema) through the pre-extracting feed; ``device``: the run's GPU (the frames
+    go there at construction and every image_resolution in 1 .. 480 is resampled by the feed's kernel)."""
     from .dataset import SoccerDiffusionDataset
 
     return SoccerDiffusionDataset(
@@ -121,7 +122,7 @@ def open_database(path: str, params: dict):
         num_samples_joint_states=params["joint_state_context_length"],
         imu_representation=params["imu_orientation_embedding_method"], use_action_history=params["use_action_history"],
         use_imu=params["use_imu"], use_joint_states=params["use_joint_states"], use_images=params["use_images"],
-        use_game_state=params["use_gamestate"], image_resolution=params.get("image_resolution", 480))
+        use_game_state=params["use_gamestate"], image_resolution=params.get("image_resolution", 480), device=device)
 
 
 def data_source(args, params: dict, device) -> DataSource:
@@ -130,7 +131,7 @@ def data_source(args, params: dict, device) -> DataSource:
         raise SystemExit("give exactly one data source: --db FILE (the reference's SQLite database), --data FILE.pt "
                          f"or --synthetic N (got: {', '.join('--' + c for c in chosen) or 'none'})")
     if getattr(args, "db", None):
-        return DataSource(dataset=open_database(args.db, params), device=device)
+        return DataSource(dataset=open_database(args.db, params, device), device=device)
     return DataSource(tensors=load_data(args, params), device=device)
 
 

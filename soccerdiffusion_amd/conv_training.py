@@ -329,3 +329,34 @@ def supported(conv: torch.nn.Conv2d) -> bool:
     ok = (k in (1, 3) and s in (1, 2) and conv.padding[0] == k // 2 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
           and conv.bias is None and conv.groups == 1 and conv.dilation[0] == 1)
     return ok and (s == 1 or conv.out_channels % 128 == 0)
+
+
+# ---- the encoder head (avgpool -> fc, or the no-avgpool head's Conv2d(C, 32, 1) + bias -> fc) on csrc/sd_head.hip -----------------------
+class ResNetHead(torch.autograd.Function):
+    """y = fc(pool(x)) from the last block's NHWC map x (N, H, W, C); conv_w / conv_b None: the avgpool head.  The backward adds the
+    parameter gradients into their .grad buffers (FusedAdamW's flat buffer) when they all exist, and hands the NHWC map gradient back."""
+
+    @staticmethod
+    def forward(ctx, x, conv_w, conv_b, fc_w, fc_b):
+        y, feat = ops.resnet_head(x, conv_w, conv_b, fc_w, fc_b)
+        ctx.save_for_backward(x, feat)
+        ctx.params = (conv_w, conv_b, fc_w, fc_b)     # leaves: their .grad buffers are the targets
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .training import _grad_targets
+
+        x, feat = ctx.saved_tensors
+        conv_w, conv_b, fc_w, fc_b = ctx.params
+        if conv_w is None:
+            (dfw, dfb), back = _grad_targets(fc_w, fc_b)
+            grads, back = (None, None, dfw, dfb), [None, None] + back
+        else:
+            grads, back = _grad_targets(conv_w, conv_b, fc_w, fc_b)
+        dx = ops.resnet_head_backward(dy.contiguous(), x, feat, conv_w, fc_w, tuple(grads), want_dx=ctx.needs_input_grad[0])
+        return (dx, *back)
+
+
+def resnet_head(x: Tensor, conv: Optional[torch.nn.Conv2d], fc: torch.nn.Linear) -> Tensor:
+    return ResNetHead.apply(x, None if conv is None else conv.weight, None if conv is None else conv.bias, fc.weight, fc.bias)

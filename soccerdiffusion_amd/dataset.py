@@ -8,7 +8,8 @@ into dense tensors, and a whole batch is assembled with a few vectorised gathers
 host or, after ``.to(device)``, directly in HBM (a 50 Hz recording is ~10 KB/s: days of data
 fit).  Sample indexing, windows, front padding (zeros / identity quaternion), the game-state
 lookup and the field names of ``Result`` are the reference's.  Image frames are kept as the
-stored uint8 blobs (691 KB per frame: an hour at 10 fps is 25 GB of the 288 GB) and preprocessed per batch.
+stored uint8 blobs (691 KB per frame: an hour at 10 fps is 25 GB of the 288 GB), all recordings in one store, and
+preprocessed per batch: on a GPU by one launch of the area-resampling kernel (ops.frames_area), on the host by torch.
 """
 
 from __future__ import annotations
@@ -20,6 +21,8 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 import torch
+
+from . import ops
 
 # JointStates.get_ordered_joint_names() — soccer_diffusion/dataset/models.py:222-247 (alphabetical)
 JOINT_NAMES_22 = [
@@ -66,14 +69,20 @@ def quats_to_5d(quats: np.ndarray) -> np.ndarray:
 
 
 IMAGE_SIZE = 480  # the recordings store 480 x 480 rgb8 frames (dataset/models.py:111-113, pytorch.py:209)
+_HOST_RESOLUTION = ("image_resolution {R}: on the host, image_resolution must divide 480 (cv2.INTER_AREA is restated there for integer "
+                    "factors only); pass device= (a GPU) for any 1 <= image_resolution <= 480")
 
 
 class SoccerDiffusionDataset(torch.utils.data.Dataset):
     """Same constructor keywords as the reference class.  Images (``use_images``): the 480x480 rgb8 blobs of a
     recording are read once and kept as uint8; a batch gathers each sample's last ``num_frames_video`` frames of
     the preceding ``(num_frames_video + 1) / max_fps_video`` seconds, front-padded with zeros, and applies the
-    reference's preprocessing (dataset/pytorch.py:173-229): area down-scaling (integer factors of 480 only),
-    [0, 1] scaling, ImageNet mean/std, channels first."""
+    reference's preprocessing (dataset/pytorch.py:173-229): cv2.INTER_AREA down-scaling, [0, 1] scaling, ImageNet
+    mean/std, channels first.
+
+    ``device``: where the recordings live.  A GPU takes the frames there at construction, one recording at a time,
+    and assembles every item and batch with the area-resampling kernel: any ``1 <= image_resolution <= 480``.  The
+    host (no ``device``) handles the integer factors of 480 only."""
 
     Result = Result
 
@@ -98,9 +107,15 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
         use_game_state: bool = True,
         db_path: Optional[str] = None,
         joint_names: Optional[Sequence[str]] = None,
+        device=None,
     ):
-        if use_images and (image_resolution <= 0 or IMAGE_SIZE % image_resolution != 0):
-            raise NotImplementedError(f"image_resolution must divide {IMAGE_SIZE} (cv2.INTER_AREA is restated for integer factors only)")
+        device = torch.device(device) if device is not None else None
+        if use_images:
+            if device is not None and device.type == "cuda":
+                if isinstance(image_resolution, bool) or not isinstance(image_resolution, int) or not 1 <= image_resolution <= IMAGE_SIZE:
+                    raise NotImplementedError(f"image_resolution must be an int in 1 .. {IMAGE_SIZE} (INTER_AREA down-scaling), got {image_resolution!r}")
+            elif image_resolution <= 0 or IMAGE_SIZE % image_resolution != 0:
+                raise NotImplementedError(_HOST_RESOLUTION.format(R=image_resolution))
         if db_connection is None:
             if db_path is None:
                 raise ValueError("pass db_connection or db_path")
@@ -130,6 +145,12 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
         self.num_samples = 0
         self.sample_boundaries: list[tuple[int, int, int]] = []
         self._rec: dict[int, dict] = {}
+        self._frames: Optional[torch.Tensor] = None     # every recording's frames, (total, 480, 480, 3) uint8
+        self._img_off: dict[int, int] = {}              # recording -> its first frame in the store
+        if use_images:
+            n_img = {rid: cur.execute("SELECT COUNT(*) FROM Image WHERE recording_id = ?", (rid,)).fetchone()[0] for rid, _ in counts}
+            self._frames = torch.empty((sum(n_img.values()), IMAGE_SIZE, IMAGE_SIZE, 3), dtype=torch.uint8, device=device or "cpu")
+            filled = 0
         for recording_id, n in counts:
             assert n > 0, "Recording length is negative or zero"
             before = self.num_samples
@@ -153,23 +174,35 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
             if use_images:
                 rows = cur.execute("SELECT stamp, data FROM Image WHERE recording_id = ? ORDER BY stamp ASC", (recording_id,)).fetchall()
                 rec["img_stamp"] = torch.tensor([r[0] for r in rows], dtype=torch.float64)
-                frames = np.stack([np.frombuffer(r[1], dtype=np.uint8).reshape(IMAGE_SIZE, IMAGE_SIZE, 3) for r in rows]) if rows else \
-                    np.zeros((0, IMAGE_SIZE, IMAGE_SIZE, 3), np.uint8)
-                rec["img"] = torch.from_numpy(frames.copy())
+                assert len(rows) == n_img[recording_id], "the Image table changed while it was read"
+                self._img_off[recording_id] = filled
+                if rows:   # one recording at a time on the host
+                    frames = np.stack([np.frombuffer(r[1], dtype=np.uint8).reshape(IMAGE_SIZE, IMAGE_SIZE, 3) for r in rows])
+                    self._frames[filled : filled + len(rows)].copy_(torch.from_numpy(frames))
+                rec["img"] = self._frames[filled : filled + len(rows)]
+                filled += len(rows)
             self._rec[recording_id] = rec
         self._starts = torch.tensor([b[0] for b in self.sample_boundaries], dtype=torch.int64)
         feat = 4 if self.imu_representation == "quaternion" else 5
         pad = torch.tensor([0.0, 0.0, 0.0, 1.0])  # identity quaternion, converted like the data
         self._imu_pad = pad if feat == 4 else torch.tensor(quats_to_5d(pad[None].numpy())[0]).float()
+        if device is not None:
+            self.to(device)
 
     def __len__(self) -> int:
         return self.num_samples
 
     def to(self, device) -> "SoccerDiffusionDataset":
         """Moves the pre-extracted recordings (e.g. into HBM); batches are then assembled there."""
-        for rec in self._rec.values():
+        if self._frames is not None:
+            self._frames = self._frames.to(device)
+        for recording_id, rec in self._rec.items():
             for k, v in rec.items():
-                rec[k] = v.to(device)
+                if k != "img":
+                    rec[k] = v.to(device)
+            if "img" in rec:   # a view of the store
+                off = self._img_off[recording_id]
+                rec["img"] = self._frames[off : off + rec["img_stamp"].shape[0]]
         self._imu_pad = self._imu_pad.to(device)
         return self
 
@@ -231,6 +264,10 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
     def _images(self, rec, stamps: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         idx, st = self._image_frames(rec, stamps)
         R = self.image_resolution
+        if rec["img"].is_cuda:   # gather + INTER_AREA + normalisation + layout + zero padding: one launch
+            return st.to(torch.float32), ops.frames_area(rec["img"], idx, R)
+        if IMAGE_SIZE % R:
+            raise NotImplementedError(_HOST_RESOLUTION.format(R=R))
         out = torch.zeros(idx.shape + (3, R, R), dtype=torch.float32, device=rec["img"].device)
         live = idx >= 0
         if live.any():
@@ -279,6 +316,7 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
         indices = indices.to(torch.int64).cpu()
         which = torch.searchsorted(self._starts, indices, right=True) - 1
         out: dict[str, list] = {}
+        frames: list = []   # on a GPU: (sel, indices into the store) per recording, then ONE launch for the whole batch
         for r in which.unique().tolist():
             start, _, recording_id = self.sample_boundaries[r]
             rec = self._rec[recording_id]
@@ -306,7 +344,13 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
                 unknown = torch.full_like(k, ROBOT_STATES.index("UNKNOWN"))
                 parts["game_state"] = torch.where(k >= 0, rec["gs_state"][k.clamp(min=0)], unknown) if len(rec["gs_state"]) else unknown
             if self.use_images:
-                parts["image_stamps"], parts["image_data"] = self._images(rec, i.to(torch.float64) / self.sampling_rate)
+                stamps = i.to(torch.float64) / self.sampling_rate
+                if rec["img"].is_cuda:
+                    idx, st = self._image_frames(rec, stamps)
+                    parts["image_stamps"] = st.to(torch.float32)
+                    frames.append((sel, torch.where(idx >= 0, idx + self._img_off[recording_id], idx)))
+                else:
+                    parts["image_stamps"], parts["image_data"] = self._images(rec, stamps)
             for name, t in parts.items():
                 out.setdefault(name, []).append((sel, t))
         result = {}
@@ -316,6 +360,12 @@ class SoccerDiffusionDataset(torch.utils.data.Dataset):
             for sel, t in chunks:
                 full[sel.to(first.device)] = t
             result[name] = full
+        if frames:
+            dev = frames[0][1].device
+            index = torch.empty((len(indices), self.num_frames_video), dtype=torch.int64, device=dev)
+            for sel, t in frames:
+                index[sel.to(dev)] = t
+            result["image_data"] = ops.frames_area(self._frames, index, self.image_resolution)
         return result
 
     def tensors(self) -> dict[str, torch.Tensor]:

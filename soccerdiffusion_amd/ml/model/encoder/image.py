@@ -233,6 +233,26 @@ class _ResNet(nn.Module):
             ok = self.__dict__["_train_ok"] = all(_train_ok(b) for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer)
         return ok
 
+    def _hip_head(self, h: torch.Tensor):
+        """(conv or None, fc) when the head is exactly AdaptiveAvgPool2d((1, 1)) or Conv2d(C, 32, 1, bias=True), then an nn.Linear (with bias)
+        whose in_features matches the last block's NHWC map h (N, H, W, C): it runs on ops.resnet_head (csrc/sd_head.hip).  Anything else
+        keeps torch's head - and a mismatch raises torch's own shape error, as the reference does."""
+        pool, fc = self.avgpool, self.fc
+        if not h.is_contiguous() or type(fc) is not nn.Linear or fc.bias is None:
+            return None
+        _, H, W, C = h.shape
+        if type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1)):
+            conv, J = None, C
+        elif (type(pool) is nn.Conv2d and pool.bias is not None and pool.padding_mode == "zeros" and pool.groups == 1
+              and (pool.in_channels, pool.out_channels, pool.kernel_size, pool.stride, pool.padding, pool.dilation) == (C, 32, (1, 1), (1, 1), (0, 0), (1, 1))):
+            conv, J = pool, 32 * H * W
+        else:
+            return None
+        params = (fc.weight, fc.bias) + (() if conv is None else (conv.weight, conv.bias))
+        if fc.in_features != J or not all(p.device == h.device and p.dtype == torch.float32 and p.is_contiguous() for p in params):
+            return None
+        return conv, fc
+
     def forward(self, x):
         if self._hip_training(x):
             # Training: every convolution and BatchNorm of the backbone on this package's kernels (convolution forward / data gradient / weight
@@ -254,6 +274,9 @@ class _ResNet(nn.Module):
             for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
                 for blk in layer:
                     h, amax = blk.forward_train_nhwc(h, amax)
+            head = self._hip_head(h)
+            if head is not None:   # the head's forward and backward on csrc/sd_head.hip
+                return ct.resnet_head(h, *head)
             x = h.permute(0, 3, 1, 2)
             return self.fc(torch.flatten(self.avgpool(x), 1))
         if self._hip_inference(x):
@@ -275,6 +298,10 @@ class _ResNet(nn.Module):
                 for blk in layer:
                     h, amax = blk.forward_nhwc(h, amax, words[at:at + 3])
                     at += 3
+            head = self._hip_head(h)
+            if head is not None:
+                conv, fc = head
+                return ops.resnet_head(h, None if conv is None else conv.weight, None if conv is None else conv.bias, fc.weight, fc.bias)[0]
             x = h.permute(0, 3, 1, 2)
         else:
             x = self.layer4(self.layer3(self.layer2(self.layer1(self.maxpool(self.relu(self.bn1(self.conv1(x))))))))

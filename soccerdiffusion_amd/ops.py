@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import sys
 from typing import Mapping, Optional, Sequence
 
 import numpy as np
@@ -1284,3 +1285,177 @@ def swin_head(x: Tensor, ln: tuple, w: PackedTokenLinear, bias: Optional[Tensor]
     pooled = torch.empty(N, Cc, dtype=torch.float32, device=dev)
     check(_lib.load().sd_swin_head_pool(x.data_ptr(), g, b, eps, pooled.data_ptr(), N, H * W, Cc, _stream()), "sd_swin_head_pool")
     return token_linear(pooled, w, bias)
+
+
+# ---- image feed: OpenCV INTER_AREA down-scaling of the stored frames + the reference's normalisation (csrc/sd_frames.hip) ----------------
+FRAME_SIZE = 480   # the recordings store 480 x 480 rgb8 frames (dataset/models.py:111-113)
+
+
+def area_is_integer(R: int, src: int = FRAME_SIZE) -> bool:
+    """cv::resize's choice of resizeAreaFast for src -> R (imgproc/src/resize.cpp): scale = 1 / (R / src) within DBL_EPSILON of an integer
+    (saturate_cast<int> rounds half to even, as Python's round)."""
+    scale = 1.0 / (R / src)
+    return abs(scale - round(scale)) < sys.float_info.epsilon
+
+
+def area_taps(R: int, src: int = FRAME_SIZE) -> tuple:
+    """computeResizeAreaTab (imgproc/src/resize.cpp) of one axis src -> R, in Python doubles (no contraction), each weight rounded to fp32
+    once: (first, count, woff) int32 (R,) - output index d reads source indices first[d] .. first[d] + count[d] - 1 with the weights
+    weights[woff[d] ...] in that order (the left partial tap, the full ones, the right partial one) - and weights float32."""
+    if not 1 <= R <= src:
+        raise ValueError(f"1 <= R <= {src}, got {R}")
+    scale = 1.0 / (R / src)
+    first, count, woff, w = [], [], [], []
+    for d in range(R):
+        fsx1 = d * scale
+        fsx2 = fsx1 + scale
+        cell = min(scale, src - fsx1)
+        sx1, sx2 = math.ceil(fsx1), math.floor(fsx2)
+        sx2 = min(sx2, src - 1)
+        sx1 = min(sx1, sx2)
+        taps = []
+        if sx1 - fsx1 > 1e-3:
+            taps.append((sx1 - 1, (sx1 - fsx1) / cell))
+        taps += [(sx, 1.0 / cell) for sx in range(sx1, sx2)]
+        if fsx2 - sx2 > 1e-3:
+            taps.append((sx2, min(min(fsx2 - sx2, 1.0), cell) / cell))
+        first.append(taps[0][0])
+        count.append(len(taps))
+        woff.append(len(w))
+        w += [t[1] for t in taps]
+        # the kernel's row streaming relies on it: consecutive outputs share at most their boundary source index
+        if d and first[d] < first[d - 1] + count[d - 1] - 1:
+            raise AssertionError(f"area taps of {src} -> {R}: outputs {d - 1} and {d} overlap by more than one source index")
+    return (np.asarray(first, np.int32), np.asarray(count, np.int32), np.asarray(woff, np.int32), np.asarray(w, np.float64).astype(np.float32))
+
+
+_area_tables: dict = {}
+
+
+def _area_table(R: int, device) -> tuple:
+    key = (R, str(device))
+    if key not in _area_tables:
+        first, count, woff, w = area_taps(R)
+        _area_tables[key] = (torch.from_numpy(np.concatenate([first, count, woff])).to(device), torch.from_numpy(w).to(device))
+    return _area_tables[key]
+
+
+def frames_area(store: Tensor, index: Tensor, R: int, out: Optional[Tensor] = None) -> Tensor:
+    """The reference's frame preprocessing (dataset/pytorch.py:209-211 + its transforms) on gathered frames, one launch:
+    cv2.resize(frame, (R, R), interpolation=cv2.INTER_AREA) of store[index] - OpenCV's integer-factor path or its generic area path, bit
+    for bit as restated in DESIGN.md section 2 - then x / 255, (x - ImageNet mean) / std, channels first.  store (N, 480, 480, 3) uint8 on
+    the device, index (...) int64 into it, -1 (or any index outside [0, N)) = a zero frame -> (..., 3, R, R) float32, 1 <= R <= 480."""
+    _swin_req(store, "store", dtype=torch.uint8, aligned=True)
+    if store.dim() != 4 or tuple(store.shape[1:]) != (FRAME_SIZE, FRAME_SIZE, 3):
+        raise ValueError(f"store: (N, {FRAME_SIZE}, {FRAME_SIZE}, 3) rgb8 frames, got {tuple(store.shape)}")
+    dev = store.device
+    _swin_req(index, "index", dev, torch.int64)
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= FRAME_SIZE:
+        raise ValueError(f"R: an int in 1 .. {FRAME_SIZE} (down-scaling only), got {R!r}")
+    R = int(R)
+    shape = (*index.shape, 3, R, R)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(_swin_req(out, "out", dev).shape) != shape:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected {shape}")
+    tab = w = None
+    if not area_is_integer(R):
+        tab, w = _area_table(R, dev)
+    check(_lib.load().sd_frames_area(store.data_ptr(), store.shape[0], index.data_ptr(), index.numel(), R, _ptr(tab), _ptr(w),
+                                     0 if w is None else w.numel(), out.data_ptr(), _stream()), "sd_frames_area")
+    return out
+
+
+# ---- the ResNet encoder heads (csrc/sd_head.hip): avgpool -> fc, or Conv2d(C, 32, 1) + bias flattened NCHW -> fc ------------------------
+def _operand(t: Tensor, row=(0, 0, 0), col=(0, 0, 0)):
+    """sd_strided_operand: element (i, j) at ((i / d) s1 + (i % d) s0) + ((j / d') s1' + (j % d') s0') floats from t's start (d = 0: i s0)."""
+    return _lib.StridedOperand(t.data_ptr(), *row, *col)
+
+
+_ones: dict = {}
+
+
+def _one(device) -> Tensor:
+    key = str(device)
+    if key not in _ones:
+        _ones[key] = torch.ones(1, dtype=torch.float32, device=device)
+    return _ones[key]
+
+
+def head_gemm(M: int, N: int, K: int, A, B, Cop, bias: Optional[Tensor] = None, accumulate: bool = False, device=None) -> None:
+    """C (M x N) [+]= A (M x K) B (K x N) [+ bias], operands given as ``_operand`` descriptors (sd_head_gemm): deterministic split
+    reductions through a scratch buffer, fp32 FMA."""
+    lib = _lib.load()
+    n_scr = lib.sd_head_gemm_scratch_floats(M, N, K)
+    scratch = torch.empty(n_scr, dtype=torch.float32, device=device) if n_scr else None
+    args = _lib.HeadGemmArgs(M, N, K, A, B, Cop, _ptr(bias), _ptr(scratch), int(bool(accumulate)), 0)
+    check(lib.sd_head_gemm(C.byref(args), _stream()), "sd_head_gemm")
+
+
+def _head_check(x: Tensor, conv_w: Optional[Tensor], conv_b: Optional[Tensor], fc_w: Tensor, fc_b: Tensor) -> tuple:
+    dev = x.device
+    _swin_req(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"x: the NHWC map (N, H, W, C), got {tuple(x.shape)}")
+    N, H, W, Cc = x.shape
+    if conv_w is not None:
+        if tuple(_swin_req(conv_w, "conv_w", dev).shape) not in ((32, Cc, 1, 1), (32, Cc)) or _swin_req(conv_b, "conv_b", dev).numel() != 32:
+            raise ValueError(f"the no-avgpool head is Conv2d({Cc}, 32, 1) with bias")
+    J = 32 * H * W if conv_w is not None else Cc
+    if _swin_req(fc_w, "fc_w", dev).dim() != 2 or fc_w.shape[1] != J or _swin_req(fc_b, "fc_b", dev).numel() != fc_w.shape[0]:
+        raise ValueError(f"fc: Linear({J}, d) with bias expected, got weight {tuple(fc_w.shape)}")
+    return N, H * W, Cc, J, fc_w.shape[0]
+
+
+def resnet_head(x: Tensor, conv_w: Optional[Tensor], conv_b: Optional[Tensor], fc_w: Tensor, fc_b: Tensor) -> tuple:
+    """The ResNet encoder head on the last block's NHWC map x (N, H, W, C): ``conv_w is None`` -> fc(mean over H W) (AdaptiveAvgPool2d((1, 1))),
+    else fc(flatten_NCHW(Conv2d(C, 32, 1)(x))).  Returns (y (N, d), the fc input (N, J)) - the latter is what the backward needs."""
+    N, HW, Cc, J, d = _head_check(x, conv_w, conv_b, fc_w, fc_b)
+    dev = x.device
+    feat = torch.empty(N, J, dtype=torch.float32, device=dev)
+    if conv_w is None:
+        check(_lib.load().sd_head_pool(x.data_ptr(), feat.data_ptr(), N, HW, Cc, _stream()), "sd_head_pool")
+    else:   # feat[n, o HW + p] = cb[o] + sum_c x[n, p, c] cw[o, c]: rows m = n HW + p
+        head_gemm(N * HW, 32, Cc, _operand(x, (0, 0, Cc), (0, 0, 1)), _operand(conv_w, (0, 0, 1), (0, 0, Cc)),
+                  _operand(feat, (HW, 32 * HW, 1), (0, 0, HW)), bias=conv_b, device=dev)
+    y = torch.empty(N, d, dtype=torch.float32, device=dev)
+    head_gemm(N, d, J, _operand(feat, (0, 0, J), (0, 0, 1)), _operand(fc_w, (0, 0, 1), (0, 0, J)), _operand(y, (0, 0, d), (0, 0, 1)),
+              bias=fc_b, device=dev)
+    return y, feat
+
+
+def resnet_head_backward(dy: Tensor, x: Tensor, feat: Tensor, conv_w: Optional[Tensor], fc_w: Tensor, grads: tuple, want_dx: bool = True):
+    """The head's backward for dy (N, d): accumulates into grads = (d conv_w, d conv_b, d fc_w, d fc_b) (None for the avgpool head's conv
+    pair; the buffers are added to, as the optimizer's flat gradient is) and returns the NHWC gradient of x (or None)."""
+    dev = x.device
+    N, H, W, Cc = x.shape
+    HW, d = H * W, fc_w.shape[0]
+    J = feat.shape[1]
+    _swin_req(dy, "dy", dev)
+    if tuple(dy.shape) != (N, d) or tuple(feat.shape) != (N, J):
+        raise ValueError("dy (N, d) and the saved fc input (N, J) expected")
+    dcw, dcb, dfw, dfb = grads
+    one = _one(dev)
+    # fc: d fc_w += dy^T feat, d fc_b += 1^T dy
+    head_gemm(d, J, N, _operand(dy, (0, 0, 1), (0, 0, d)), _operand(feat, (0, 0, J), (0, 0, 1)), _operand(dfw, (0, 0, J), (0, 0, 1)),
+              accumulate=True, device=dev)
+    head_gemm(1, d, N, _operand(one), _operand(dy, (0, 0, d), (0, 0, 1)), _operand(dfb, (0, 0, 0), (0, 0, 1)), accumulate=True, device=dev)
+    if conv_w is None and not want_dx:
+        return None
+    dfeat = torch.empty(N, J, dtype=torch.float32, device=dev)          # dy fc_w
+    head_gemm(N, J, d, _operand(dy, (0, 0, d), (0, 0, 1)), _operand(fc_w, (0, 0, J), (0, 0, 1)), _operand(dfeat, (0, 0, J), (0, 0, 1)), device=dev)
+    if conv_w is None:
+        dx = torch.empty_like(x)
+        check(_lib.load().sd_head_pool_bwd(dfeat.data_ptr(), dx.data_ptr(), N, HW, Cc, _stream()), "sd_head_pool_bwd")
+        return dx
+    # dz[n][p][o] = dfeat[n, o HW + p]; reduction index k = n HW + p
+    dz_k = (HW, 32 * HW, 1)
+    head_gemm(32, Cc, N * HW, _operand(dfeat, (0, 0, HW), dz_k), _operand(x, (0, 0, Cc), (0, 0, 1)), _operand(dcw, (0, 0, Cc), (0, 0, 1)),
+              accumulate=True, device=dev)
+    head_gemm(1, 32, N * HW, _operand(one), _operand(dfeat, dz_k, (0, 0, HW)), _operand(dcb, (0, 0, 0), (0, 0, 1)), accumulate=True, device=dev)
+    if not want_dx:
+        return None
+    dx = torch.empty_like(x)                                              # dz conv_w
+    head_gemm(N * HW, Cc, 32, _operand(dfeat, dz_k, (0, 0, HW)), _operand(conv_w, (0, 0, Cc), (0, 0, 1)), _operand(dx, (0, 0, Cc), (0, 0, 1)),
+              device=dev)
+    return dx

@@ -299,4 +299,24 @@ static inline unsigned grid_for(long n, int block = 256) {
 int linear(const float *A, const float *W, const float *bias, const float *ln_w, const float *ln_b, const float *res,
            float *out, int R, int N, int d, int act, hipStream_t s, int lda = 0);
 
+// the sampler's fp16 kernels are on (SD_SAMPLER_GEMM=f32 in the environment keeps the fp32-MFMA kernels: A/B runs); sd_kernels.hip
+bool f16_env_ok();
+
+// split weights of layer l inside the sampler's wf region (mode 2 and the tuned trajectory kernels, each in its own fragment order):
+// [Wo | W1 | W2 | in_proj (3 passes)], 12 d^2 halfs
+static inline f16 *f16_wf(f16 *wf, int l, int d, int which) {   // which: 0 Wo, 1 W1, 2 W2, 3 in_proj
+    return wf + ((size_t)l * 6 + (which < 3 ? which : 3)) * 2 * d * d;
+}
+
+// small launches of sd_kernels.hip that the trajectory units share with the row-panel sampler:
+// zero `bytes` (a multiple of 4) of device memory
+int zero_async(void *ptr, size_t bytes, hipStream_t st);
+// atomicMax of the bits of max |x[0 .. n)| into *out (f16_absmax_kernel)
+int f16_absmax(const float *x, long n, unsigned *out, hipStream_t st);
+// fold of the cross-attention projections into n_rows projected memory rows, 4 heads of d / 4 (xattn_fold_kernel)
+int xattn_fold(const float *kv, long n_rows, int keys_per_item, const float *wq, const float *bq, const float *wo, float *gv, float *cb,
+               long item_rows, int head_rows, int d, unsigned *maxG, unsigned *maxV, hipStream_t st);
+// map[b] = 0 where step token b equals token 0 bit for bit, else b (step_map_kernel)
+int step_map(const float *tokens, int n_tok, int d, int *map, hipStream_t st);
+
 #endif

@@ -1293,7 +1293,7 @@ static int chain_b(const ChainBArgs &g, int d, hipStream_t s) {
 }
 
 #include "sd_f16x3.h"
-#include "sd_traj.h"
+#include "sd_traj_host.h"
 #include "sd_trajg.h"
 
 template <int D>
@@ -2483,7 +2483,7 @@ __global__ void zero_words_kernel(unsigned *__restrict__ p, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0u;
 }
 // bytes: a multiple of 4; 16-byte aligned regions go through the wide kernel
-static int zero_async(void *ptr, size_t bytes, hipStream_t st) {
+int zero_async(void *ptr, size_t bytes, hipStream_t st) {
     if (bytes == 0) return 0;
     if ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && bytes % 16 == 0) {
         SD_LAUNCH(zero_fill_kernel, dim3(grid_for((long)(bytes / 16))), dim3(256), 0, st, reinterpret_cast<f32x4 *>(ptr), (long)(bytes / 16));
@@ -2491,6 +2491,19 @@ static int zero_async(void *ptr, size_t bytes, hipStream_t st) {
         SD_LAUNCH(zero_words_kernel, dim3(grid_for((long)(bytes / 4))), dim3(256), 0, st, reinterpret_cast<unsigned *>(ptr), (long)(bytes / 4));
     }
     SD_CHECK_LAUNCH("zero_fill_kernel");
+    return 0;
+}
+int f16_absmax(const float *x, long n, unsigned *out, hipStream_t st) {
+    SD_LAUNCH(f16_absmax_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, out);
+    SD_CHECK_LAUNCH("f16_absmax_kernel");
+    return 0;
+}
+int xattn_fold(const float *kv, long n_rows, int keys_per_item, const float *wq, const float *bq, const float *wo, float *gv, float *cb,
+               long item_rows, int head_rows, int d, unsigned *maxG, unsigned *maxV, hipStream_t st) {
+    const int hd = d / 4;
+    SD_LAUNCH(xattn_fold_kernel, dim3((unsigned)((n_rows + FOLD_RB - 1) / FOLD_RB), 4), dim3(256), 2 * (size_t)FOLD_RB * hd * sizeof(float), st, kv, n_rows,
+              keys_per_item, wq, bq, wo, gv, cb, item_rows, head_rows, 0, d, hd, maxG, maxV);
+    SD_CHECK_LAUNCH("xattn_fold_kernel");
     return 0;
 }
 
@@ -2515,7 +2528,7 @@ struct Scratch {  // carve-up of the caller's workspace (floats)
     float *gv, *cb, *gvstep, *cstep;   // folded cross-attention (sampler only)
     // fp16x3 operands of the sampler (sd_f16x3.h): split weights, folded blocks, scales
     f16 *wf, *g16, *v16, *gstep16, *vstep16;
-    f16 *wio;   // sampler mode 3 (sd_traj.h): embedding (256 x 32) and fc_out (32 x 256) planes
+    f16 *wio;   // sampler mode 3 (sd_traj.hip): embedding (256 x 32) and fc_out (32 x 256) planes
     float *scales;
     unsigned *maxbits;
     // split weights of the unfused row chains (chain_f16_kernel, hidden_dim 128 / 256 / 512): per layer
@@ -2529,7 +2542,7 @@ struct Scratch {  // carve-up of the caller's workspace (floats)
 
 // the fp16x3 kernels are instantiated for hidden_dim 256 (the folded fp32 kernels serve the other sizes);
 // SD_SAMPLER_GEMM=f32 keeps the fp32-MFMA kernels (A/B runs)
-static bool f16_env_ok() {
+bool f16_env_ok() {
     static const char *env = getenv("SD_SAMPLER_GEMM");
     return !(env && strcmp(env, "f32") == 0);
 }
@@ -2540,67 +2553,56 @@ static bool fold_ok(int d, int heads, int T, int Mk) { return heads == 4 && d >=
 
 static size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
-static Scratch carve(float *ws, long R, long RM, int d, int L, int n_steps, long B = 0) {
-    Scratch s;
+// The one description of the workspace: walks the regions and assigns them from `ws`; *end (if given) receives the floats they take.
+// With ws == NULL nothing is assigned (every pointer NULL) and only the count is made: sd_workspace_floats.
+static Scratch carve(float *ws, long R, long RM, int d, int L, int n_steps, long B = 0, size_t *end = nullptr) {
+    Scratch s{};
     size_t off = 0;
+    auto take = [&](size_t n) { float *p = ws ? ws + off : nullptr; off += align64(n); return p; };
+    auto take16 = [&](size_t n) { return reinterpret_cast<f16 *>(take(n)); };   // sizes in floats (2 halfs each)
     const size_t kt = B > 0 ? (size_t)((RM / B + 15) / 16) : 1;   // key tiles of the folded blocks (memory rows per trajectory / 16)
-    s.h = ws + off; off += align64((size_t)((R + 63) / 64 * 64) * d);   // whole panels (accumulator-order layout)
-    s.qkv = ws + off; off += align64((size_t)R * 3 * d);
-    s.a = ws + off; off += align64((size_t)R * d);
-    s.u = ws + off; off += align64((size_t)R * d);
-    s.kv = ws + off; off += align64((size_t)L * RM * 2 * d);
-    s.kvstep = ws + off; off += align64((size_t)L * (n_steps > 0 ? n_steps : 1) * 2 * d);
-    s.kvtmp = ws + off; off += align64((size_t)L * RM * 2 * d);
-    s.gv = s.cb = s.gvstep = s.cstep = nullptr;
-    if (n_steps > 0) {
-        s.gv = ws + off; off += align64((size_t)L * B * kt * 64 * 2 * d);
-        s.cb = ws + off; off += align64((size_t)L * B * kt * 64);
-        s.gvstep = ws + off; off += align64((size_t)L * n_steps * 4 * 2 * d);
-        s.cstep = ws + off; off += align64((size_t)L * n_steps * 4);
+    s.h = take((size_t)((R + 63) / 64 * 64) * d);   // whole panels (accumulator-order layout)
+    s.qkv = take((size_t)R * 3 * d);
+    s.a = take((size_t)R * d);
+    s.u = take((size_t)R * d);
+    s.kv = take((size_t)L * RM * 2 * d);
+    s.kvstep = take((size_t)L * (n_steps > 0 ? n_steps : 1) * 2 * d);
+    s.kvtmp = take((size_t)L * RM * 2 * d);
+    if (n_steps > 0) {   // folded cross-attention blocks of the sampler: 64 rows of 2d (+ 1 bias) per trajectory, key tile and layer
+        s.gv = take((size_t)L * B * kt * 64 * 2 * d);
+        s.cb = take((size_t)L * B * kt * 64);
+        s.gvstep = take((size_t)L * n_steps * 4 * 2 * d);
+        s.cstep = take((size_t)L * n_steps * 4);
     }
-    s.wf = s.g16 = s.v16 = s.gstep16 = s.vstep16 = s.wio = nullptr;
-    s.scales = nullptr;
-    s.maxbits = nullptr;
-    if (n_steps > 0 && d == 256) {   // sizes in floats (2 halfs each)
-        s.wf = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * 6 * d * d);
-        s.g16 = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * B * kt * 4 * 16 * d);
-        s.v16 = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * B * kt * 4 * 16 * d);
-        s.gstep16 = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * n_steps * 4 * 16 * d);
-        s.vstep16 = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * n_steps * 16 * d);
-        s.scales = ws + off; off += align64((size_t)(L + 1) * 8);
-        s.maxbits = reinterpret_cast<unsigned *>(ws + off); off += align64((size_t)(L + 1) * 8);
-        s.wio = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)2 * 32 * d);
+    if (n_steps > 0 && d == 256) {   // fp16x3 operands (sd_f16x3.h; sd_traj.hip keeps its own in the same regions)
+        s.wf = take16((size_t)L * 6 * d * d);
+        s.g16 = take16((size_t)L * B * kt * 4 * 16 * d);
+        s.v16 = take16((size_t)L * B * kt * 4 * 16 * d);
+        s.gstep16 = take16((size_t)L * n_steps * 4 * 16 * d);
+        s.vstep16 = take16((size_t)L * n_steps * 16 * d);
+        s.scales = take((size_t)(L + 1) * 8);
+        s.maxbits = reinterpret_cast<unsigned *>(take((size_t)(L + 1) * 8));
+        s.wio = take16((size_t)2 * 32 * d);
     }
-    s.wfc = nullptr;
-    s.scc = nullptr;
-    s.mbc = nullptr;
     if (n_steps > 0 && (d == 128 || d == 256 || d == 512)) {
-        s.wfc = reinterpret_cast<f16 *>(ws + off); off += align64((size_t)L * 8 * d * d);
-        s.scc = ws + off; off += align64((size_t)L * 8);
-        s.mbc = reinterpret_cast<unsigned *>(ws + off); off += align64((size_t)L * 8);
+        s.wfc = take16((size_t)L * 8 * d * d);
+        s.scc = take((size_t)L * 8);
+        s.mbc = reinterpret_cast<unsigned *>(take((size_t)L * 8));
     }
-    s.stepmap = nullptr;
-    if (n_steps > 0) { s.stepmap = reinterpret_cast<int *>(ws + off); off += align64((size_t)n_steps); }
-    s.gws = nullptr;
-    if (n_steps > 0 && B > 0 && (d == 128 || d == 256 || d == 512)) s.gws = ws + off;   // trajg_workspace_floats(B, Mc, d, L, n_steps) floats
+    if (n_steps > 0) s.stepmap = reinterpret_cast<int *>(take((size_t)n_steps));
+    // behind everything else: trajg_workspace_floats(B, Mc, d, L, n_steps) floats (sd_workspace_floats adds them)
+    if (ws && n_steps > 0 && B > 0 && (d == 128 || d == 256 || d == 512)) s.gws = ws + off;
+    if (end) *end = off;
     return s;
 }
 
 extern "C" size_t sd_workspace_floats(int B, int T, int M, int d, int L, int n_steps) {
     // M memory rows per trajectory (+1: the sampler adds the step row to the context rows)
-    const size_t R = (size_t)B * T, RM = (size_t)B * ((M > 0 ? M : 0) + 1);
-    const size_t kt = (size_t)(((M > 0 ? M : 0) + 1 + 15) / 16);   // as carve()
-    size_t n = align64(R * d) * 2 + align64((R + 63) / 64 * 64 * d) + align64(R * 3 * d) + 2 * align64((size_t)L * RM * 2 * d) +
-               align64((size_t)L * (n_steps > 0 ? n_steps : 1) * 2 * d) + 1024;
-    if (n_steps > 0)   // folded cross-attention blocks of the sampler: 64 rows of 2d (+ 1 bias) per trajectory and layer
-        n += align64((size_t)L * B * kt * 64 * 2 * d) + align64((size_t)L * B * kt * 64) + align64((size_t)L * n_steps * 4 * 2 * d) +
-             align64((size_t)L * n_steps * 4);
-    if (n_steps > 0 && d == 256)   // fp16x3 operands (sd_f16x3.h)
-        n += align64((size_t)L * 6 * d * d) + 2 * align64((size_t)L * B * kt * 4 * 16 * d) + align64((size_t)L * n_steps * 4 * 16 * d) +
-             align64((size_t)L * n_steps * 16 * d) + 2 * align64((size_t)(L + 1) * 8) + align64((size_t)2 * 32 * d);
-    if (n_steps > 0 && (d == 128 || d == 256 || d == 512)) n += align64((size_t)L * 8 * d * d) + 2 * align64((size_t)L * 8);
-    if (n_steps > 0) n += align64((size_t)n_steps);   // step map
-    if (n_steps > 0 && (d == 128 || d == 256 || d == 512)) n += trajg_workspace_floats(B, M > 0 ? M : 0, d, L, n_steps);
+    const int Mc = M > 0 ? M : 0;
+    size_t n = 0;
+    carve(nullptr, (long)B * T, (long)B * (Mc + 1), d, L, n_steps, B, &n);
+    n += 1024;
+    if (n_steps > 0 && (d == 128 || d == 256 || d == 512)) n += trajg_workspace_floats(B, Mc, d, L, n_steps);
     return n;
 }
 
@@ -2634,8 +2636,7 @@ static int f16_prepare_chain_d(const sd_denoiser_weights *w, const Scratch &s, h
             const int rows[6] = {d, d, d, d, d, 3 * d};
             for (int m = 0; m < 6; ++m) {
                 if (pass == 0) {
-                    SD_LAUNCH(f16_absmax_kernel, dim3(grid_for((long)rows[m] * d)), dim3(256), 0, st, mats[m], (long)rows[m] * d, s.mbc + l * 8 + m);
-                    SD_CHECK_LAUNCH("f16_absmax_kernel");
+                    if (int ra = f16_absmax(mats[m], (long)rows[m] * d, s.mbc + l * 8 + m, st)) return ra;
                 } else {
                     SD_LAUNCH((f16_pack_weight_kernel<D>), dim3(grid_for((long)rows[m] * d / 8)), dim3(256), 0, st, mats[m], rows[m],
                               s.mbc + l * 8 + m, f16_wfc(s, l, d, m), s.scc + l * 8 + m);
@@ -2652,9 +2653,7 @@ static int f16_prepare_chain(const sd_denoiser_weights *w, const Scratch &s, hip
 // the unfused row chains run on the fp16 pipe when their split weights were prepared (sampler, hidden_dim 128 / 256 / 512;
 // SD_SAMPLER_GEMM=f32 keeps the fp32 kernels)
 static bool chain16_ok(int d, int J) {
-    static const char *env = getenv("SD_SAMPLER_GEMM");
-    if (env && strcmp(env, "f32") == 0) return false;
-    return (d == 128 || d == 256 || d == 512) && J % 4 == 0;
+    return f16_env_ok() && (d == 128 || d == 256 || d == 512) && J % 4 == 0;
 }
 
 template <typename KV>
@@ -2726,10 +2725,7 @@ static int decoder_stack(const sd_denoiser_weights *w, const float *x, const Scr
 }
 
 // ---- fp16x3 sampler path (sd_f16x3.h) --------------------------------------------------------------
-// split weights of layer l: [Wo | W1 | W2 | in_proj (3 passes)] in fragment-major planes, 12 d^2 halfs
-static f16 *f16_wf(const Scratch &s, int l, int d, int which) {   // which: 0 Wo, 1 W1, 2 W2, 3 in_proj
-    return s.wf + ((size_t)l * 6 + (which < 3 ? which : 3)) * 2 * d * d;
-}
+// split weights of layer l: f16_wf(s.wf, l, d, which) (sd_common.h: the tuned trajectory kernels keep their planes in the same region)
 
 // once per rollout, after the fp32 fold (gv, gvstep): scales, split weights, split folded blocks
 static int f16_prepare(const sd_denoiser_weights *w, const Scratch &s, int B, int Mc, int n_steps, hipStream_t st) {
@@ -2742,8 +2738,7 @@ static int f16_prepare(const sd_denoiser_weights *w, const Scratch &s, int B, in
         const int rows[4] = {d, d, d, 3 * d};
         unsigned *mb = s.maxbits + l * 8;
         for (int m = 0; m < 4; ++m) {
-            SD_LAUNCH(f16_absmax_kernel, dim3(grid_for((long)rows[m] * d)), dim3(256), 0, st, mats[m], (long)rows[m] * d, mb + m);
-            SD_CHECK_LAUNCH("f16_absmax_kernel");
+            if (int ra = f16_absmax(mats[m], (long)rows[m] * d, mb + m, st)) return ra;
         }
     }
     for (int l = 0; l < L; ++l) {
@@ -2754,7 +2749,7 @@ static int f16_prepare(const sd_denoiser_weights *w, const Scratch &s, int B, in
         float *sc = s.scales + l * 8;
         for (int m = 0; m < 4; ++m) {
             SD_LAUNCH((f16_pack_weight_kernel<256>), dim3(grid_for((long)rows[m] * d / 8)), dim3(256), 0, st, mats[m], rows[m], mb + m,
-                      f16_wf(s, l, d, m), sc + m);
+                      f16_wf(s.wf, l, d, m), sc + m);
             SD_CHECK_LAUNCH("f16_pack_weight_kernel");
         }
         const size_t blk = (size_t)32 * d;
@@ -2797,7 +2792,7 @@ static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scrat
     static const char *henv = getenv("SD_H");   // "rows": h stays row-major (A/B runs)
     const int hfrag = !(henv && strcmp(henv, "rows") == 0);
     F16HeadArgs fh{DecoderHeadArgs{x, w->emb_w, w->emb_b, w->pe, l0.n1_w, l0.n1_b, l0.sa_in_w, l0.sa_in_b, s.h, s.qkv, R, T, w->J},
-                   f16_wf(s, 0, d, 3), s.scales, hm ? 1 : 0, hfrag};
+                   f16_wf(s.wf, 0, d, 3), s.scales, hm ? 1 : 0, hfrag};
     // the head of steps 1.. runs inside the previous step's last layer kernel (SD_MERGE_HEAD=0: always its own launch; A/B runs)
     static const char *menv = getenv("SD_MERGE_HEAD");
     const bool merge = !(menv && strcmp(menv, "0") == 0) && T >= 64 && w->J <= 64;
@@ -2830,10 +2825,10 @@ static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scrat
             if (merge && !fa.next_head && n_steps > 1) fa.g.slot = L + 2;   // keep the stamps of the merged launch before it
 #endif
         }
-        fa.wf_o = f16_wf(s, l, d, 0);
-        fa.wf_1 = f16_wf(s, l, d, 1);
-        fa.wf_2 = f16_wf(s, l, d, 2);
-        fa.wf_qkv = last ? nullptr : f16_wf(s, l + 1, d, 3);
+        fa.wf_o = f16_wf(s.wf, l, d, 0);
+        fa.wf_1 = f16_wf(s.wf, l, d, 1);
+        fa.wf_2 = f16_wf(s.wf, l, d, 2);
+        fa.wf_qkv = last ? nullptr : f16_wf(s.wf, l + 1, d, 3);
         fa.sc_own = s.scales + l * 8;
         fa.sc_next = s.scales + (l + 1) * 8;
         fa.g16 = s.g16 + (size_t)l * B * 4 * blk;
@@ -2848,139 +2843,7 @@ static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scrat
     return 0;
 }
 
-
-// ---- sampler mode 3: the trajectory-owning step kernel (sd_traj.h) ---------------------------------------
-// One launch per DDIM step: embedding, all layers (self-attention inside), fc_out and the DDIM update for one trajectory per
-// workgroup.  Same folded cross-attention blocks (gv, cb) and abs-max words as mode 2; the split planes are written in the
-// 16x16x32 fragment order of sd_traj.h into the same workspace regions.  SD_SAMPLER_TRAJ=0 in the environment keeps mode 2.
-static bool traj_ok(int d, int heads, int T, int Mk, int J, int L) {
-    static const char *env = getenv("SD_SAMPLER_TRAJ");
-    if (env && strcmp(env, "0") == 0) return false;
-    // any joint count up to 32 (the embedding's K and fc_out's N are zero-padded to 32 in the packed planes; the reference's database
-    // has 22 joints: soccer_diffusion/dataset/models.py:222-247)
-    static const char *mr = getenv("SD_TRAJ_MAXROWS");   // A/B runs: memory rows beyond this go to the generic kernels (sd_trajg.hip) instead of the wide instantiation
-    const int max_rows = mr ? atoi(mr) : 64;
-    return f16_env_ok() && d == 256 && heads == 4 && T >= 1 && T <= tj::TMAX && Mk >= 1 && Mk <= (max_rows < 64 ? max_rows : 64) && J >= 1 && J <= 32 && L >= 1 &&
-           L <= tj::MAX_L;
-}
-// key tiles of 16 memory slots in the folded blocks: 1 for the trajectory kernels proper, 2 .. 4 for traj_step_wide_kernel (17 .. 64 rows)
-static int key_tiles(int Mk) { return Mk <= 16 ? 1 : (Mk + 15) / 16; }
-
-// the instantiation for ceil(T / 16) token tiles; precise = three fp16 products at the Q | K | V site too (sampler mode 3), else two (mode 4)
-typedef void (*TrajStepFn)(tj::StepArgs);
-static TrajStepFn traj_step_wide_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tj::traj_step_wide_kernel<1>;
-        case 2: return tj::traj_step_wide_kernel<2>;
-        case 3: return tj::traj_step_wide_kernel<3>;
-        case 4: return tj::traj_step_wide_kernel<4>;
-        case 5: return tj::traj_step_wide_kernel<5>;
-        case 6: return tj::traj_step_wide_kernel<6>;
-        case 7: return tj::traj_step_wide_kernel<7>;
-        default: return nullptr;
-    }
-}
-template <bool PRECISE>
-static TrajStepFn traj_step_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tj::traj_step_kernel<1, PRECISE>;
-        case 2: return tj::traj_step_kernel<2, PRECISE>;
-        case 3: return tj::traj_step_kernel<3, PRECISE>;
-        case 4: return tj::traj_step_kernel<4, PRECISE>;
-        case 5: return tj::traj_step_kernel<5, PRECISE>;
-        case 6: return tj::traj_step_kernel<6, PRECISE>;
-        case 7: return tj::traj_step_kernel<7, PRECISE>;
-        default: return nullptr;
-    }
-}
-
-// zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
-__global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < rows * ncols) mb[(i / ncols) * 8 + col0 + i % ncols] = 0u;
-}
-static int zero_word_cols(unsigned *mb, int rows, int col0, int ncols, hipStream_t st) {
-    SD_LAUNCH(zero_word_cols_kernel, dim3((unsigned)((rows * ncols + 63) / 64)), dim3(64), 0, st, mb, rows, col0, ncols);
-    SD_CHECK_LAUNCH("zero_word_cols_kernel");
-    return 0;
-}
-
-// The trajectory path prepares its operands in three independent stages (sd_ddim_sample_eps runs all three per call;
-// sd_sampler_prepare / sd_sampler_eps let a caller that evaluates the denoiser step by step - the reference's own loop,
-// soccer_diffusion/ml/inference/plot.py:122-131 - keep the first two across calls):
-//   weights: abs-max + split planes of every matrix (words 0 .. 3 of a layer's row of the abs-max table, 6 / 7 of row L)
-//   context: K / V of the context rows, the fold, its split blocks g16 / v16 (words 4 / 5, scales sc[4] / sc[5])
-//   steps:   K / V of the n_tok step tokens, their fold, the split step blocks (words 6 / 7, scales sc[6] / sc[7])
-static int traj_prepare_weights(const sd_denoiser_weights *w, const Scratch &s, hipStream_t st) {
-    const int d = w->d, L = w->L;
-    int rc = zero_word_cols(s.maxbits, L, 0, 4, st);
-    if (!rc) rc = zero_word_cols(s.maxbits + L * 8, 1, 6, 2, st);
-    if (rc) return rc;
-    for (int l = 0; l < L; ++l) {
-        const sd_layer_weights &lw = w->layers[l];
-        const float *mats[4] = {lw.sa_out_w, lw.lin1_w, lw.lin2_w, lw.sa_in_w};
-        const int rows[4] = {d, d, d, 3 * d};
-        for (int m = 0; m < 4; ++m) {
-            SD_LAUNCH(f16_absmax_kernel, dim3(grid_for((long)rows[m] * d)), dim3(256), 0, st, mats[m], (long)rows[m] * d, s.maxbits + l * 8 + m);
-            SD_CHECK_LAUNCH("f16_absmax_kernel");
-        }
-    }
-    SD_LAUNCH(f16_absmax_kernel, dim3(grid_for((long)d * w->J)), dim3(256), 0, st, w->emb_w, (long)d * w->J, s.maxbits + L * 8 + 6);
-    SD_CHECK_LAUNCH("f16_absmax_kernel");
-    SD_LAUNCH(f16_absmax_kernel, dim3(grid_for((long)d * w->J)), dim3(256), 0, st, w->out_w, (long)d * w->J, s.maxbits + L * 8 + 7);
-    SD_CHECK_LAUNCH("f16_absmax_kernel");
-    SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)d * 4)), dim3(256), 0, st, w->emb_w, d, w->J, d, 32, s.maxbits + L * 8 + 6, 0.f, s.wio,
-              s.scales + L * 8 + 6);
-    SD_CHECK_LAUNCH("pack_w16_kernel");
-    SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)32 * d / 8)), dim3(256), 0, st, w->out_w, w->J, d, 32, d, s.maxbits + L * 8 + 7, 0.f,
-              s.wio + (size_t)2 * 32 * d, s.scales + L * 8 + 7);
-    SD_CHECK_LAUNCH("pack_w16_kernel");
-    for (int l = 0; l < L; ++l) {
-        const sd_layer_weights &lw = w->layers[l];
-        const float *mats[4] = {lw.sa_out_w, lw.lin1_w, lw.lin2_w, lw.sa_in_w};
-        const int rows[4] = {d, d, d, 3 * d};
-        for (int m = 0; m < 4; ++m) {
-            SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)rows[m] * d / 8)), dim3(256), 0, st, mats[m], rows[m], d, rows[m], d, s.maxbits + l * 8 + m, 0.f,
-                      f16_wf(s, l, d, m), s.scales + l * 8 + m);
-            SD_CHECK_LAUNCH("pack_w16_kernel");
-        }
-    }
-    return 0;
-}
-
-static int traj_prepare_ctx(const sd_denoiser_weights *w, const Scratch &s, const float *ctx, int B, int Mc, hipStream_t st) {
-    const int d = w->d, L = w->L, hd = d / 4, nkt = key_tiles(Mc + 1);
-    const size_t gvstride = (size_t)B * nkt * 64 * 2 * d, cbstride = (size_t)B * nkt * 64;
-    const size_t lds = 2 * (size_t)FOLD_RB * hd * sizeof(float);
-    int rc = zero_async(s.gv, L * gvstride * sizeof(float), st);   // unused key slots must be finite
-    if (!rc) rc = zero_async(s.cb, L * cbstride * sizeof(float), st);
-    if (!rc) rc = zero_word_cols(s.maxbits, L, 4, 2, st);
-    if (rc) return rc;
-    const size_t blk = (size_t)32 * d;   // halfs per (trajectory, head)
-    for (int l = 0; l < L; ++l) {
-        const sd_layer_weights &lw = w->layers[l];
-        unsigned *mb = s.maxbits + l * 8;
-        if (Mc > 0) {
-            const long rows = (long)B * Mc;
-            float *kvl = s.kvtmp + (size_t)l * B * Mc * 2 * d;
-            rc = linear(ctx, lw.ca_in_w + (size_t)d * d, lw.ca_in_b + d, nullptr, nullptr, nullptr, kvl, B * Mc, 2 * d, d, 0, st, 0);
-            if (rc) return rc;
-            SD_LAUNCH(xattn_fold_kernel, dim3((unsigned)((rows + FOLD_RB - 1) / FOLD_RB), 4), dim3(256), lds, st, kvl, rows, Mc, lw.ca_in_w, lw.ca_in_b,
-                      lw.ca_out_w, s.gv + l * gvstride, s.cb + l * cbstride, 64L * nkt, 16, 0, d, hd, mb + 4, mb + 5);
-            SD_CHECK_LAUNCH("xattn_fold_kernel");
-        }
-        SD_LAUNCH(tj::pack_g16_kernel, dim3(grid_for((long)B * nkt * 4 * 16 * d / 8)), dim3(256), 0, st, s.gv + l * gvstride, (long)B * nkt, Mc, mb + 4,
-                  s.g16 + (size_t)l * B * nkt * 4 * blk, s.scales + l * 8 + 4, nkt);
-        SD_CHECK_LAUNCH("pack_g16_kernel");
-        SD_LAUNCH(tj::pack_v16_kernel, dim3(grid_for((long)B * nkt * 16 * 2 * 64)), dim3(256), 0, st, s.gv + l * gvstride, (long)B * nkt, Mc, mb + 5,
-                  s.v16 + (size_t)l * B * nkt * 4 * blk, s.scales + l * 8 + 5, nkt);
-        SD_CHECK_LAUNCH("pack_v16_kernel");
-    }
-    return 0;
-}
-
-// ---- the step tokens' part of the preparation, all layers in one launch each (a forward_with_context call of the reference's loop pays
-// it once per call: four launches instead of four per layer)
+// Per-trajectory step tokens of the trajectory kernels (sd_traj.hip, sd_trajg.hip):
 // map[b] = 0 where step token b equals token 0 bit for bit (the usual call of the reference's loop: one timestep for the whole batch, passed
 // as a (B,) tensor), else b: trajectory b reads the folded blocks of token map[b], and only tokens with map[b] == b are folded and packed
 __global__ void step_map_kernel(const float *__restrict__ tokens, int n_tok, int d, int *map) {
@@ -2991,216 +2854,9 @@ __global__ void step_map_kernel(const float *__restrict__ tokens, int n_tok, int
     same = __syncthreads_and(same);
     if (threadIdx.x == 0) map[b] = same ? 0 : b;
 }
-struct StepFoldArgs { const float *wkv[tj::MAX_L], *bkv[tj::MAX_L], *wq[tj::MAX_L], *bq[tj::MAX_L], *woc[tj::MAX_L]; };
-// hidden_dim 256.  step_kv_kernel, grid (n_tok, L, 8), 256 threads: rows 64 z .. 64 z + 63 of K | V = Wkv tok + bkv (memory rows are not
-// layer-normed) -> kvstep[l][tok][2 D].  step_fold_all_kernel, grid (n_tok, L, 4 heads): the fold of xattn_fold_kernel for this one row and head:
-// G_h = Wq_h^T K_h, V'_h = Woc_h V_h, c_h = bq_h . K_h -> gvstep row [tok * 4 + h][2 D], cstep [tok * 4 + h]; abs-max of G / V' -> words 6 / 7 of
-// the layer's row.  (One workgroup per (token, layer) did all of it as a chain of dependent weight loads: 130 us for ONE token - what every
-// forward_with_context call of the reference's loop pays, 27 % of a B = 256 rollout; 16 rows in flight per wave: 100 us; the work of a token
-// and layer spread over 8 + 4 workgroups: see NOTEBOOK round 5.)
-__global__ __launch_bounds__(256) void step_kv_kernel(StepFoldArgs a, const float *__restrict__ tokens, float *__restrict__ kvstep, long n_tok,
-                                                      const int *__restrict__ map) {
-    constexpr int D = tj::D;
-    const int l = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long tok = blockIdx.x;
-    if (map && map[tok] != (int)tok) return;   // a duplicate of token 0: nobody reads its blocks
-    const f32x4 t4 = *reinterpret_cast<const f32x4 *>(tokens + tok * D + 4 * lane);
-    const float *wkv = a.wkv[l], *bkv = a.bkv[l];
-    const int o0 = blockIdx.z * 64 + wv * 16;
-    f32x4 w4[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) w4[u] = *reinterpret_cast<const f32x4 *>(wkv + (long)(o0 + u) * D + 4 * lane);
-    float *out = kvstep + ((long)l * n_tok + tok) * 2 * D;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const float s = wave_sum((w4[u][0] * t4[0] + w4[u][1] * t4[1]) + (w4[u][2] * t4[2] + w4[u][3] * t4[3]));
-        if (lane == 0) out[o0 + u] = s + bkv[o0 + u];
-    }
-}
-__global__ __launch_bounds__(256) void step_fold_all_kernel(StepFoldArgs a, const float *__restrict__ kvstep, long n_tok, float *__restrict__ gvstep,
-                                                            long gv_layer_stride, float *__restrict__ cstep, long c_layer_stride,
-                                                            unsigned *maxbits, const int *__restrict__ map) {
-    constexpr int D = tj::D, HD = tj::HD;
-    __shared__ __attribute__((aligned(16))) float sk[HD], sv[HD];
-    const int l = blockIdx.y, h = blockIdx.z, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long tok = blockIdx.x;
-    if (map && map[tok] != (int)tok) return;
-    const int n = threadIdx.x;
-    const float *wq = a.wq[l], *woc = a.woc[l] + (long)n * D;
-    // the head's weights first (64 + 16 loads per thread in flight), then its K / V slice
-    float wqv[HD];
-    f32x4 wov[HD / 4];
-#pragma unroll
-    for (int j = 0; j < HD; ++j) wqv[j] = wq[(long)(h * HD + j) * D + n];
-#pragma unroll
-    for (int j = 0; j < HD / 4; ++j) wov[j] = *reinterpret_cast<const f32x4 *>(woc + h * HD + 4 * j);
-    const float *kv = kvstep + ((long)l * n_tok + tok) * 2 * D;
-    if (threadIdx.x < HD) sk[threadIdx.x] = kv[h * HD + threadIdx.x];
-    else if (threadIdx.x < 2 * HD) sv[threadIdx.x - HD] = kv[D + h * HD + threadIdx.x - HD];
-    __syncthreads();
-    if (wv == 0) {   // the score bias of head h
-        const float c = wave_sum(a.bq[l][h * HD + lane] * sk[lane]);
-        if (lane == 0) cstep[l * c_layer_stride + tok * 4 + h] = c;
-    }
-    float g = 0.f, v = 0.f;
-#pragma unroll
-    for (int j = 0; j < HD; ++j) g += wqv[j] * sk[j];
-#pragma unroll
-    for (int j = 0; j < HD / 4; ++j) {
-        const f32x4 v4 = *reinterpret_cast<const f32x4 *>(sv + 4 * j);
-        v += (wov[j][0] * v4[0] + wov[j][1] * v4[1]) + (wov[j][2] * v4[2] + wov[j][3] * v4[3]);
-    }
-    float *out = gvstep + l * gv_layer_stride + tok * 4 * 2 * D;
-    out[(long)h * 2 * D + n] = g;
-    out[(long)h * 2 * D + D + n] = v;
-    float mg = fabsf(g), mv = fabsf(v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        mv = fmaxf(mv, __shfl_xor(mv, o, 64));
-    }
-    if (lane == 0) {
-        const unsigned bg = __builtin_bit_cast(unsigned, mg), bv = __builtin_bit_cast(unsigned, mv);
-        if (bg > __atomic_load_n(maxbits + l * 8 + 6, __ATOMIC_RELAXED)) atomicMax(maxbits + l * 8 + 6, bg);
-        if (bv > __atomic_load_n(maxbits + l * 8 + 7, __ATOMIC_RELAXED)) atomicMax(maxbits + l * 8 + 7, bv);
-    }
-}
-// grid (blocks, L): tj::pack_gstep16_kernel + tj::pack_vstep16_kernel of every layer (scales from words 6 / 7 -> sc[6], sc[7]); with
-// no_ctx also sc[4] = sc[6], sc[5] = sc[7] (no context rows: the all-zero context blocks carry no scale of their own - a scale of 1 from an
-// abs-max of 0 would drag the common value scale of tj::step_scale down to 1)
-__global__ void pack_step16_all_kernel(const float *__restrict__ gvstep, long gv_layer_stride, long n_tok, const unsigned *maxbits,
-                                       f16 *__restrict__ gdst, long g_layer_stride, f16 *__restrict__ vdst, long v_layer_stride, float *scales,
-                                       int no_ctx, const int *__restrict__ map) {
-    constexpr int D = tj::D;
-    const int l = blockIdx.y;
-    const float sg = f16_scale_from_bits(maxbits[l * 8 + 6]), sv = f16_scale_from_bits(maxbits[l * 8 + 7]);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scales[l * 8 + 6] = sg;
-        scales[l * 8 + 7] = sv;
-        if (no_ctx) {
-            scales[l * 8 + 4] = sg;
-            scales[l * 8 + 5] = sv;
-        }
-    }
-    const float *src = gvstep + l * gv_layer_stride;
-    f16 *gd = gdst + l * g_layer_stride, *vd = vdst + l * v_layer_stride;
-    const long ng = n_tok * 4 * (D / 8), nv = n_tok * 4 * D;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < ng + nv; i += (long)gridDim.x * blockDim.x) {
-        if (i < ng) {
-            const int k8 = (int)(i % (D / 8));
-            const long ih = i / (D / 8);
-            if (map && map[ih >> 2] != (int)(ih >> 2)) continue;
-            f16x4 h0, l0, h1, l1;
-            const float *row = src + ih * 2 * D + tj::kperm(k8, 0);
-            f16_split4(*reinterpret_cast<const f32x4 *>(row), sg, h0, l0);
-            f16_split4(*reinterpret_cast<const f32x4 *>(row + 16), sg, h1, l1);
-            f16 *o = gd + ih * (8 * 2 * 32) + ((k8 >> 2) * 2) * 32 + (k8 & 3) * 8;
-            *reinterpret_cast<f16x4 *>(o) = h0;
-            *reinterpret_cast<f16x4 *>(o + 4) = h1;
-            *reinterpret_cast<f16x4 *>(o + 32) = l0;
-            *reinterpret_cast<f16x4 *>(o + 36) = l1;
-        } else {
-            const long j = i - ng;
-            const int n = (int)(j % D), head = (int)((j / D) & 3);
-            const long item = j / D / 4;
-            if (map && map[item] != (int)item) continue;
-            const float v = src[(item * 4 + head) * 2 * D + D + n] * sv;
-            const f16 h = (f16)v;
-            vd[(item * 2 + 0) * 4 * D + head * D + n] = h;
-            vd[(item * 2 + 1) * 4 * D + head * D + n] = (f16)(v - (float)h);
-        }
-    }
-}
-
-// n_tok step tokens (rows of `tokens`): one per DDIM step of a rollout, or one per trajectory of a single evaluation
-static int traj_prepare_steps(const sd_denoiser_weights *w, const Scratch &s, const float *tokens, int n_tok, int Mc, hipStream_t st,
-                              bool per_traj = false) {
-    const int d = w->d, L = w->L;
-    const size_t gvsstride = (size_t)n_tok * 4 * 2 * d, cssstride = (size_t)n_tok * 4;
-    const size_t blk = (size_t)32 * d;
-    int rc = zero_word_cols(s.maxbits, L, 6, 2, st);
-    if (rc) return rc;
-    const int *map = nullptr;
-    if (per_traj) {   // one token per trajectory: fold the distinct ones only (see step_map_kernel)
-        SD_LAUNCH(step_map_kernel, dim3((unsigned)n_tok), dim3(64), 0, st, tokens, n_tok, d, s.stepmap);
-        SD_CHECK_LAUNCH("step_map_kernel");
-        map = s.stepmap;
-    }
-    StepFoldArgs fa{};
-    for (int l = 0; l < L; ++l) {
-        const sd_layer_weights &lw = w->layers[l];
-        fa.wkv[l] = lw.ca_in_w + (size_t)d * d; fa.bkv[l] = lw.ca_in_b + d;
-        fa.wq[l] = lw.ca_in_w; fa.bq[l] = lw.ca_in_b; fa.woc[l] = lw.ca_out_w;
-    }
-    SD_LAUNCH(step_kv_kernel, dim3((unsigned)n_tok, (unsigned)L, 8), dim3(256), 0, st, fa, tokens, s.kvstep, (long)n_tok, map);
-    SD_CHECK_LAUNCH("step_kv_kernel");
-    SD_LAUNCH(step_fold_all_kernel, dim3((unsigned)n_tok, (unsigned)L, 4), dim3(256), 0, st, fa, s.kvstep, (long)n_tok, s.gvstep, (long)gvsstride, s.cstep,
-              (long)cssstride, s.maxbits, map);
-    SD_CHECK_LAUNCH("step_fold_all_kernel");
-    // per-layer regions as carved for mode 2 (n_tok * 4 * blk / n_tok * blk halfs), the step blocks packed densely inside
-    unsigned gx = grid_for((long)n_tok * 4 * (d / 8 + d));
-    SD_LAUNCH(pack_step16_all_kernel, dim3(gx, (unsigned)L), dim3(256), 0, st, s.gvstep, (long)gvsstride, (long)n_tok, s.maxbits, s.gstep16,
-              (long)((size_t)n_tok * 4 * blk), s.vstep16, (long)((size_t)n_tok * blk), s.scales, Mc == 0 ? 1 : 0, map);
-    SD_CHECK_LAUNCH("pack_step16_all_kernel");
-    return 0;
-}
-
-// one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
-// coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
-static int decoder_step_traj(const sd_denoiser_weights *w, float *x, const Scratch &s, int B, int T, int Mc, int i, int n_steps,
-                             const float *coef, hipStream_t st, bool precise, float *eps = nullptr, int32_t *status = nullptr,
-                             bool per_traj = false) {
-    const int d = w->d, L = w->L, nkt = key_tiles(Mc + 1);
-    const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
-    tj::StepArgs a{};
-    a.nkt = nkt;
-    a.status = status;
-    a.x = x;
-    a.eps_out = eps;
-    a.w_emb = s.wio;
-    a.b_emb = w->emb_b;
-    a.pe = w->pe;
-    a.n1_w = w->layers[0].n1_w;
-    a.n1_b = w->layers[0].n1_b;
-    a.w_out = s.wio + (size_t)2 * 32 * d;
-    a.b_out = w->out_b;
-    a.sc_io = s.scales + L * 8 + 6;
-    if (coef) { a.c0 = coef[0]; a.c1 = coef[1]; a.c2 = coef[2]; a.c3 = coef[3]; }
-    a.scale_log2e = (1.0f / sqrtf((float)(d / w->heads))) * 1.44269504088896340736f;
-    a.T = T; a.B = B; a.J = w->J; a.L = L; a.Mk = Mc + 1; a.update_x = coef ? 1 : 0;
-    a.step_per_traj = per_traj ? 1 : 0;
-    a.step_map = per_traj ? s.stepmap : nullptr;
-    for (int l = 0; l < L; ++l) {
-        const sd_layer_weights &lw = w->layers[l];
-        tj::LayerW &q = a.layer[l];
-        q.n2_w = lw.n2_w; q.n2_b = lw.n2_b; q.n3_w = lw.n3_w; q.n3_b = lw.n3_b;
-        q.w_o = f16_wf(s, l, d, 0); q.w_1 = f16_wf(s, l, d, 1); q.w_2 = f16_wf(s, l, d, 2); q.w_in = f16_wf(s, l, d, 3);
-        q.b_in = lw.sa_in_b; q.b_o = lw.sa_out_b; q.b_1 = lw.lin1_b; q.b_2 = lw.lin2_b; q.b_oc = lw.ca_out_b;
-        q.sc = s.scales + l * 8;
-        q.g16 = s.g16 + (size_t)l * B * nkt * 4 * blk;
-        q.v16 = s.v16 + (size_t)l * B * nkt * 4 * blk;
-        q.cb = s.cb + l * cbstride;
-        // per-layer regions as carved for mode 2 (n_steps * 4 * blk / n_steps * blk halfs), the step blocks packed densely inside
-        q.gstep = s.gstep16 + (size_t)l * n_steps * 4 * blk + (size_t)i * (4 * 8 * 2 * 32);
-        q.vstep = s.vstep16 + (size_t)l * n_steps * blk + (size_t)i * (2 * 4 * d);
-        q.cstep = s.cstep + ((size_t)l * n_steps + i) * 4;
-        q.nln_w = l + 1 < L ? w->layers[l + 1].n1_w : nullptr;
-        q.nln_b = l + 1 < L ? w->layers[l + 1].n1_b : nullptr;
-    }
-    const int ntt = (T + 15) / 16;
-    // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
-    const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
-    const TrajStepFn fn = variant == 2 ? traj_step_wide_fn(ntt) : (precise ? traj_step_fn<true>(ntt) : traj_step_fn<false>(ntt));
-    if (!fn) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
-    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-    static DevFlag attr_set[3][8];
-    if (!attr_set[variant][ntt]) {
-        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
-        if (e != hipSuccess) return fail((int)e, "traj_step_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        attr_set[variant][ntt] = true;
-    }
-    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a);
-    SD_CHECK_LAUNCH("traj_step_kernel");
+int step_map(const float *tokens, int n_tok, int d, int *map, hipStream_t st) {
+    SD_LAUNCH(step_map_kernel, dim3((unsigned)n_tok), dim3(64), 0, st, tokens, n_tok, d, map);
+    SD_CHECK_LAUNCH("step_map_kernel");
     return 0;
 }
 
@@ -3296,69 +2952,97 @@ extern "C" int sd_ddim_sample_ex(const sd_denoiser_weights *w, const float *ctx,
     return sd_ddim_sample_eps(w, ctx, step_tokens, coef, x, trace, nullptr, workspace, B, T, Mc, n_steps, status, max_mode, stream);
 }
 
-extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
-                                  const float *coef, float *x, float *trace, float *eps_trace, float *workspace, int B, int T, int Mc,
-                                  int n_steps, int32_t *status, int max_mode, void *stream) {
-    int rc = check_denoiser(w);
-    if (rc) return rc;
-    if (!step_tokens || !coef || !x || !workspace || B <= 0 || T <= 0 || Mc < 0 || n_steps <= 0 || (Mc > 0 && !ctx))
-        return fail(SD_E_BADARG, "sd_ddim_sample: null pointer or empty shape");
-    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, "sd_ddim_sample_ex: max_mode must be -1, 0, 1, 2, 3 or 4");
-    // automatic = the highest mode that is valid for ANY weights: 3.  Mode 4's two-product Q | K | V site is opt-in (max_mode = 4):
-    // it is validated up to SD_SHARP_LOGIT_LIMIT and reports through `status` when a logit leaves that range
-    if (max_mode < 0) max_mode = 3;
-    if (max_mode == 4 && !status) return fail(SD_E_BADARG, "sd_ddim_sample_ex: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
-    if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
-    hipStream_t st = (hipStream_t)stream;
+// ---- the trajectory kernels (sampler modes 3 / 4): two families behind the same four stages ---------------------------------
+// tuned: sd_traj.hip (hidden_dim 256, <= 64 memory rows; its operands live in mode 2's workspace regions), generic: sd_trajg.hip (every
+// other hidden_dim 128 / 256 / 512 shape, whatever its memory length; its own region s.gws)
+enum TrajFamily { TRAJ_NONE, TRAJ_TUNED, TRAJ_GENERIC };
+static TrajFamily traj_family(const sd_denoiser_weights *w, const Scratch &s, int B, int T, int Mc, int max_mode) {
+    const int d = w->d, Mk = Mc + 1;
+    if (max_mode < 3) return TRAJ_NONE;
+    // the tuned kernel takes any horizon <= 100: it needs the folded blocks, not the row-panel kernels' T >= 64
+    if ((long)B * Mk * 2 * d < (1L << 30) && traj_ok(d, w->heads, T, Mk, w->J, w->L) && s.wf != nullptr && s.wio != nullptr) return TRAJ_TUNED;
+    if (trajg_ok(d, w->heads, T, Mk, w->J, w->L) && s.gws != nullptr) return TRAJ_GENERIC;
+    return TRAJ_NONE;
+}
+
+// One sampler call on the trajectory kernels.  The three preparation stages are independent (sd_ddim_sample_eps runs all three per call;
+// sd_sampler_prepare / sd_sampler_eps let a caller that evaluates the denoiser step by step - the reference's own loop,
+// soccer_diffusion/ml/inference/plot.py:122-131 - keep the first two across calls).
+struct TrajCall {
+    TrajFamily fam;
+    const sd_denoiser_weights *w;
+    const Scratch &s;
+    int B, T, Mc, n_tok;
+    hipStream_t st;
+    TrajWs ws() const { return TrajWs{s.kvtmp, s.kvstep, s.gv, s.cb, s.gvstep, s.cstep, s.wf, s.g16, s.v16, s.gstep16, s.vstep16, s.wio, s.scales, s.maxbits, s.stepmap}; }
+    int prepare_weights() const {
+        return fam == TRAJ_GENERIC ? trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st) : traj_prepare_weights(w, ws(), st);
+    }
+    int prepare_ctx(const float *ctx) const {
+        return fam == TRAJ_GENERIC ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st) : traj_prepare_ctx(w, ws(), ctx, B, Mc, st);
+    }
+    // per_traj: one token per trajectory (only the distinct ones are prepared: step_map_kernel), else one per DDIM step
+    int prepare_steps(const float *tokens, bool per_traj) const {
+        if (fam != TRAJ_GENERIC) return traj_prepare_steps(w, ws(), tokens, n_tok, Mc, st, per_traj);
+        if (per_traj)
+            if (int rc = step_map(tokens, n_tok, w->d, s.stepmap, st)) return rc;
+        return trajg_prepare_steps(w, s.gws, tokens, s.kvstep, B, Mc, n_tok, st, per_traj ? s.stepmap : nullptr);
+    }
+    // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
+    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int max_mode, int32_t *status) const {
+        if (fam == TRAJ_GENERIC) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr);
+        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, max_mode == 3, max_mode == 3 ? nullptr : status);
+    }
+};
+
+static int trace_copy(const float *x, float *trace, int i, long n, hipStream_t st) {
+    SD_LAUNCH(copy_rows_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, trace + (size_t)i * n, n, 1L, (int)n);
+    SD_CHECK_LAUNCH("copy_rows_kernel");
+    return 0;
+}
+static int finite_check(const float *x, long n, int32_t *status, hipStream_t st) {
+    SD_LAUNCH(finite_check_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, status, SD_STATUS_NONFINITE);
+    SD_CHECK_LAUNCH("finite_check_kernel");
+    return 0;
+}
+
+// the rollout on the trajectory kernels: one launch per DDIM step
+static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
+                        int32_t *status, int max_mode) {
+    const long n = (long)c.B * c.T * c.w->J;
+    int rc;
+    if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
+    if ((rc = c.prepare_weights())) return rc;
+    if ((rc = c.prepare_ctx(ctx))) return rc;
+    if ((rc = c.prepare_steps(step_tokens, false))) return rc;
+    for (int i = 0; i < c.n_tok; ++i) {
+        // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
+        float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, max_mode, status))) return rc;
+        if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
+    }
+    return status ? finite_check(x, n, status, c.st) : 0;
+}
+
+// the rollout on the row-panel kernels (sampler modes 0 - 2)
+static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                         float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, hipStream_t st) {
     const int d = w->d, R = B * T, L = w->L;
-    Scratch s = carve(workspace, R, (long)B * (Mc + 1), d, L, n_steps, B);
+    int rc;
     // once per rollout: K/V of the context rows (placed as rows 0..Mc-1 of each trajectory's
     // [Mk][2d] block, Mk = Mc + 1) and of all n_steps step tokens, per layer
     const int Mk = Mc + 1;
     const size_t kvstride = (size_t)B * Mk * 2 * d, kvsstride = (size_t)n_steps * 2 * d;
     const bool small = (long)B * Mk * 2 * d < (1L << 30);
-    // the trajectory kernel (modes 3 / 4) takes any horizon <= 100: it needs the folded blocks, not the row-panel kernels' T >= 64
-    const bool traj = max_mode >= 3 && small && traj_ok(d, w->heads, T, Mk, w->J, L) && s.wf != nullptr && s.wio != nullptr;
-    // ... and the generic trajectory kernels (sd_trajg.hip) every other hidden_dim 128 / 256 / 512 shape, whatever its memory length
-    const bool trajg = !traj && max_mode >= 3 && trajg_ok(d, w->heads, T, Mk, w->J, L) && s.gws != nullptr;
-    if (trajg) {
-        if (status) {
-            if (int rz = zero_async(status, sizeof(int32_t), st)) return rz;
-        }
-        if ((rc = trajg_prepare_weights(w, s.gws, B, Mc, n_steps, st))) return rc;
-        if ((rc = trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_steps, st))) return rc;
-        if ((rc = trajg_prepare_steps(w, s.gws, step_tokens, s.kvstep, B, Mc, n_steps, st))) return rc;
-        for (int i = 0; i < n_steps; ++i) {
-            float *eps_i = eps_trace ? eps_trace + (size_t)i * R * w->J : nullptr;
-            if ((rc = trajg_step(w, s.gws, x, eps_i, B, T, Mc, i, n_steps, coef + 4 * i, false, st))) return rc;
-            if (trace) {
-                const long n = (long)R * w->J;
-                SD_LAUNCH(copy_rows_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, trace + (size_t)i * n, n, 1L, (int)n);
-                SD_CHECK_LAUNCH("copy_rows_kernel");
-            }
-        }
-        if (status) {
-            const long n = (long)R * w->J;
-            SD_LAUNCH(finite_check_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, status, SD_STATUS_NONFINITE);
-            SD_CHECK_LAUNCH("finite_check_kernel");
-        }
-        return 0;
-    }
-    const bool fold = traj || (max_mode >= 1 && fold_ok(d, w->heads, T, Mk) && fused_layer_ok(d, w->heads, T, Mk) && small);
-    const int nkt = traj ? key_tiles(Mk) : 1;   // (the row-panel fold: Mk <= 16)
-    const size_t gvstride = (size_t)B * nkt * 64 * 2 * d, cbstride = (size_t)B * nkt * 64;
+    const bool fold = max_mode >= 1 && fold_ok(d, w->heads, T, Mk) && fused_layer_ok(d, w->heads, T, Mk) && small;
+    const size_t gvstride = (size_t)B * 64 * 2 * d, cbstride = (size_t)B * 64;   // (the row-panel fold: Mk <= 16, one key tile)
     const size_t gvsstride = (size_t)n_steps * 4 * 2 * d, cssstride = (size_t)n_steps * 4;
-    const bool f16 = traj || (max_mode >= 2 && fold && f16_ok(d, w->J) && s.wf != nullptr);
+    const bool f16 = max_mode >= 2 && fold && f16_ok(d, w->J) && s.wf != nullptr;
     const bool chain16 = max_mode >= 2 && !fold && chain16_ok(d, w->J) && s.wfc != nullptr && !fused_layer_ok(d, w->heads, T, Mk);
     if (status) {
         if (int rz = zero_async(status, sizeof(int32_t), st)) return rz;
     }
-    if (traj) {
-        if ((rc = traj_prepare_weights(w, s, st))) return rc;
-        if ((rc = traj_prepare_ctx(w, s, ctx, B, Mc, st))) return rc;
-        if ((rc = traj_prepare_steps(w, s, step_tokens, n_steps, Mc, st))) return rc;
-    }
-    for (int l = 0; l < L && !traj; ++l) {
+    for (int l = 0; l < L; ++l) {
         const sd_layer_weights &lw = w->layers[l];
         const float *wkv = lw.ca_in_w + (size_t)d * d, *bkv = lw.ca_in_b + d;
         auto lin = max_mode >= 2 ? linear : linear32;
@@ -3370,30 +3054,23 @@ extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx
         if (rc) return rc;
     }
     if (chain16 && (rc = f16_prepare_chain(w, s, st))) return rc;
-    if (traj) {
-    } else if (fold) {
+    if (fold) {
         // the memory is fixed over the rollout: fold Wq into its keys and Woc into its values once
-        const int hd = d / 4;
-        const size_t lds = 2 * (size_t)FOLD_RB * hd * sizeof(float);
         int rz = zero_async(s.gv, L * gvstride * sizeof(float), st);   // unused key slots must be finite
         if (!rz && f16) rz = zero_async(s.maxbits, (size_t)(L + 1) * 8 * sizeof(unsigned), st);   // abs-max words
         if (!rz) rz = zero_async(s.cb, L * cbstride * sizeof(float), st);
         if (rz) return rz;
         for (int l = 0; l < L; ++l) {
             const sd_layer_weights &lw = w->layers[l];
+            unsigned *maxG = f16 ? s.maxbits + l * 8 + 4 : nullptr, *maxV = f16 ? s.maxbits + l * 8 + 5 : nullptr;
             if (Mc > 0) {
-                const long rows = (long)B * Mc;
-                SD_LAUNCH(xattn_fold_kernel, dim3((unsigned)((rows + FOLD_RB - 1) / FOLD_RB), 4), dim3(256), lds, st,
-                          s.kvtmp + (size_t)l * B * Mc * 2 * d, rows, Mc, lw.ca_in_w, lw.ca_in_b, lw.ca_out_w,
-                          s.gv + l * gvstride, s.cb + l * cbstride, 64L * nkt, 16, 0, d, hd, f16 ? s.maxbits + l * 8 + 4 : (unsigned *)nullptr,
-                          f16 ? s.maxbits + l * 8 + 5 : (unsigned *)nullptr);
-                SD_CHECK_LAUNCH("xattn_fold_kernel");
+                rc = xattn_fold(s.kvtmp + (size_t)l * B * Mc * 2 * d, (long)B * Mc, Mc, lw.ca_in_w, lw.ca_in_b, lw.ca_out_w, s.gv + l * gvstride,
+                                s.cb + l * cbstride, 64L, 16, d, maxG, maxV, st);
+                if (rc) return rc;
             }
-            SD_LAUNCH(xattn_fold_kernel, dim3((unsigned)((n_steps + FOLD_RB - 1) / FOLD_RB), 4), dim3(256), lds, st,
-                      s.kvstep + (size_t)l * kvsstride, (long)n_steps, 1, lw.ca_in_w, lw.ca_in_b, lw.ca_out_w,
-                      s.gvstep + l * gvsstride, s.cstep + l * cssstride, 4L, 1, 0, d, hd, f16 ? s.maxbits + l * 8 + 4 : (unsigned *)nullptr,
-                      f16 ? s.maxbits + l * 8 + 5 : (unsigned *)nullptr);
-            SD_CHECK_LAUNCH("xattn_fold_kernel");
+            rc = xattn_fold(s.kvstep + (size_t)l * kvsstride, (long)n_steps, 1, lw.ca_in_w, lw.ca_in_b, lw.ca_out_w, s.gvstep + l * gvsstride,
+                            s.cstep + l * cssstride, 4L, 1, d, maxG, maxV, st);
+            if (rc) return rc;
         }
         if (f16 && (rc = f16_prepare(w, s, B, Mc, n_steps, st))) return rc;
     } else if (Mc > 0) {
@@ -3401,13 +3078,12 @@ extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx
                   (long)kvstride, B, Mc, Mk, 2 * d, 0);
         SD_CHECK_LAUNCH("kv_place_kernel");
     }
+    const long n = (long)R * w->J;
     for (int i = 0; i < n_steps; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
-        float *eps_i = eps_trace ? eps_trace + (size_t)i * R * w->J : nullptr;
+        float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
         // this step's token row -> row Mc of every trajectory, all layers in one launch
-        if (traj) {
-            if ((rc = decoder_step_traj(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, max_mode == 3, eps_i, max_mode == 3 ? nullptr : status))) return rc;
-        } else if (f16) {
+        if (f16) {
             if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i))) return rc;
         } else if (fold) {
             SD_LAUNCH(fold_place_kernel, dim3(grid_for((long)B * 4 * 2 * d), L), dim3(256), 0, st, s.gvstep + (size_t)i * 4 * 2 * d,
@@ -3426,85 +3102,72 @@ extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx
                                FoldArgs{nullptr, nullptr, 0, 0}, chain16);
             if (rc) return rc;
         }
-        if (trace) {
-            const long n = (long)R * w->J;
-            SD_LAUNCH(copy_rows_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, trace + (size_t)i * n, n,
-                               1L, (int)n);
-            SD_CHECK_LAUNCH("copy_rows_kernel");
-        }
+        if (trace && (rc = trace_copy(x, trace, i, n, st))) return rc;
     }
-    if (status) {
-        const long n = (long)R * w->J;
-        SD_LAUNCH(finite_check_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, status, SD_STATUS_NONFINITE);
-        SD_CHECK_LAUNCH("finite_check_kernel");
-    }
-    return 0;
+    return status ? finite_check(x, n, status, st) : 0;
+}
+
+extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
+                                  const float *coef, float *x, float *trace, float *eps_trace, float *workspace, int B, int T, int Mc,
+                                  int n_steps, int32_t *status, int max_mode, void *stream) {
+    int rc = check_denoiser(w);
+    if (rc) return rc;
+    if (!step_tokens || !coef || !x || !workspace || B <= 0 || T <= 0 || Mc < 0 || n_steps <= 0 || (Mc > 0 && !ctx))
+        return fail(SD_E_BADARG, "sd_ddim_sample: null pointer or empty shape");
+    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, "sd_ddim_sample_ex: max_mode must be -1, 0, 1, 2, 3 or 4");
+    // automatic = the highest mode that is valid for ANY weights: 3.  Mode 4's two-product Q | K | V site is opt-in (max_mode = 4):
+    // it is validated up to SD_SHARP_LOGIT_LIMIT and reports through `status` when a logit leaves that range
+    if (max_mode < 0) max_mode = 3;
+    if (max_mode == 4 && !status) return fail(SD_E_BADARG, "sd_ddim_sample_ex: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
+    if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
+    hipStream_t st = (hipStream_t)stream;
+    const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
+    const TrajFamily fam = traj_family(w, s, B, T, Mc, max_mode);
+    if (fam != TRAJ_NONE) return traj_rollout(TrajCall{fam, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status, max_mode);
+    return panel_rollout(w, s, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, max_mode, st);
 }
 
 // ---- the denoiser evaluated step by step on the trajectory kernels (the reference's own loop form) --------------------------
-// *generic: the shape runs on the generic trajectory kernels (sd_trajg.hip) instead of sd_traj.h's
-static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int max_mode, const char *who,
-                             Scratch *out, bool *precise, bool *generic) {
+static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int *max_mode, const char *who,
+                             Scratch *s, TrajFamily *fam) {
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!workspace || B <= 0 || T <= 0 || Mc < 0 || (n_tok != 1 && n_tok != B)) return fail(SD_E_BADARG, who);
-    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, who);
+    if (*max_mode < -1 || *max_mode > 4) return fail(SD_E_BADARG, who);
     if (T > w->T_max) return fail(SD_E_TOOBIG, who);
-    if (max_mode < 0) max_mode = 3;
-    const int d = w->d, Mk = Mc + 1;
-    *out = carve(workspace, (long)B * T, (long)B * Mk, d, w->L, n_tok, B);
-    const bool small = (long)B * Mk * 2 * d < (1L << 30);
-    *generic = false;
-    if (!(max_mode >= 3 && small && traj_ok(d, w->heads, T, Mk, w->J, w->L) && out->wf && out->wio)) {
-        if (!(max_mode >= 3 && trajg_ok(d, w->heads, T, Mk, w->J, w->L) && out->gws)) return SD_E_UNSUPPORTED;
-        *generic = true;
-    }
-    *precise = max_mode == 3 || *generic;
-    return 0;
+    if (*max_mode < 0) *max_mode = 3;
+    *s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_tok, B);
+    *fam = traj_family(w, *s, B, T, Mc, *max_mode);
+    return *fam == TRAJ_NONE ? SD_E_UNSUPPORTED : 0;
 }
 
 extern "C" int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
                                   int what, int max_mode, void *stream) {
     Scratch s;
-    bool precise, generic;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_prepare: bad argument", &s, &precise, &generic);
+    TrajFamily fam;
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, &max_mode, "sd_sampler_prepare: bad argument", &s, &fam);
     if (rc) return rc;
     if ((what & ~(SD_PREPARE_WEIGHTS | SD_PREPARE_CONTEXT)) || (Mc > 0 && (what & SD_PREPARE_CONTEXT) && !ctx))
         return fail(SD_E_BADARG, "sd_sampler_prepare: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (generic) {
-        if ((what & SD_PREPARE_WEIGHTS) && (rc = trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st))) return rc;
-        if ((what & SD_PREPARE_CONTEXT) && (rc = trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st))) return rc;
-        return 0;
-    }
-    if ((what & SD_PREPARE_WEIGHTS) && (rc = traj_prepare_weights(w, s, st))) return rc;
-    if ((what & SD_PREPARE_CONTEXT) && (rc = traj_prepare_ctx(w, s, ctx, B, Mc, st))) return rc;
+    const TrajCall c{fam, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    if ((what & SD_PREPARE_WEIGHTS) && (rc = c.prepare_weights())) return rc;
+    if ((what & SD_PREPARE_CONTEXT) && (rc = c.prepare_ctx(ctx))) return rc;
     return 0;
 }
 
 extern "C" int sd_sampler_eps(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
                               int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, void *stream) {
     Scratch s;
-    bool precise, generic;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_eps: bad argument", &s, &precise, &generic);
+    TrajFamily fam;
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, &max_mode, "sd_sampler_eps: bad argument", &s, &fam);
     if (rc) return rc;
     if (!step_tokens || !x || !eps) return fail(SD_E_BADARG, "sd_sampler_eps: null pointer");
-    if (!precise && !status) return fail(SD_E_BADARG, "sd_sampler_eps: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
-    hipStream_t st = (hipStream_t)stream;
-    if (status) {
-        if (int rz = zero_async(status, sizeof(int32_t), st)) return rz;
-    }
-    if (generic) {
-        if (n_tok > 1) {
-            SD_LAUNCH(step_map_kernel, dim3((unsigned)n_tok), dim3(64), 0, st, step_tokens, n_tok, w->d, s.stepmap);
-            SD_CHECK_LAUNCH("step_map_kernel");
-        }
-        if ((rc = trajg_prepare_steps(w, s.gws, step_tokens, s.kvstep, B, Mc, n_tok, st, n_tok > 1 ? s.stepmap : nullptr))) return rc;
-        return trajg_step(w, s.gws, const_cast<float *>(x), eps, B, T, Mc, 0, n_tok, nullptr, n_tok > 1, st, n_tok > 1 ? s.stepmap : nullptr);
-    }
-    if ((rc = traj_prepare_steps(w, s, step_tokens, n_tok, Mc, st, n_tok > 1))) return rc;
+    if (max_mode == 4 && fam == TRAJ_TUNED && !status) return fail(SD_E_BADARG, "sd_sampler_eps: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
+    const TrajCall c{fam, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
+    if ((rc = c.prepare_steps(step_tokens, n_tok > 1))) return rc;
     // x is only read (no DDIM coefficients: no update)
-    return decoder_step_traj(w, const_cast<float *>(x), s, B, T, Mc, 0, n_tok, nullptr, st, precise, eps, precise ? nullptr : status, n_tok > 1);
+    return c.step(const_cast<float *>(x), eps, 0, nullptr, n_tok > 1, max_mode, status);
 }
 
 // ======================================================================================

@@ -3,7 +3,8 @@
 // self-attention (reference: nn.TransformerDecoderLayer as built by soccer_diffusion/ml/model/decoder.py:26-35, norm_first;
 // forward of decoder.py:38-54), fc_out and the DDIM update - so the residual stream, q | k | v and the attention output
 // never leave the CU.  Same numerics as sd_f16x3.h: every product is three fp16 MFMAs on hi / lo operand pairs with fp32
-// accumulation; the cross-attention is the folded form of sd_kernels.hip (xattn_fold_kernel).
+// accumulation; the cross-attention is the folded form of sd_kernels.hip (xattn_fold_kernel).  Host side: sd_traj.hip (the sampler; interface
+// sd_traj_host.h) and sd_train_traj.hip (the training forward).
 //
 // Geometry.  Every row GEMM is computed TRANSPOSED, out^T[n][token] = W[n][:] . X[token][:], on v_mfma_f32_16x16x32_f16:
 // T = 100 pads to 7 token tiles of 16 (12 %; 32-row tiles would pad 28 %).  A = a 16-feature tile of W (fragment-major planes in
@@ -37,7 +38,6 @@
 namespace tj {
 
 constexpr int D = 256, HD = 64, NH = 4, TMAX = 100;
-constexpr int NTT_A = 7;                    // token tiles of the Stage-A experiment kernel (T = 97 .. 100)
 constexpr int NTHREADS = 512;
 constexpr int MAX_L = 8;
 constexpr float ACT = 8.0f;                 // scale of LayerNorm outputs, q, k, v, attention / GELU outputs (as sd_f16x3.h)
@@ -59,7 +59,6 @@ constexpr int LDS_STAT = LDS_K + TMAX * VROW;
 constexpr int LDS_BYTES = LDS_STAT + TMAX * 8 * 8;
 static_assert(LDS_SO + TMAX * QROW <= LDS_Q, "Q and O fit the freed half of the panel");
 static_assert(LDS_BYTES <= 163840 && LDS_P + TMAX * PROW <= LDS_STAT, "LDS budget");
-constexpr long HFRAG_FLOATS = 8L * 2 * NTT_A * 256;   // residual stream of one trajectory in fragment order (Stage-A kernel)
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -144,7 +143,7 @@ __device__ __forceinline__ void split_store(char *hi_at, char *lo_at, const f32x
 }
 
 // ---------------------------------------------------------------------------------------------------
-// once-per-call packing (host side: sd_kernels.hip, sampler mode 3)
+// once-per-call packing (host side: sd_traj.hip, sampler mode 3)
 // ---------------------------------------------------------------------------------------------------
 // W (N x K row-major fp32, zero-padded to Np x Kp with Np % 16 == 0, Kp % 32 == 0) -> [n-tile][k-step][plane][lane][8]:
 // lane = 16 g + i holds W[16 nt + i][32 ks + 8 g + 0..7] * scale as hi / lo.  maxbits: abs-max word (scale derived on the
@@ -271,37 +270,6 @@ static __global__ void pack_vstep16_kernel(const float *__restrict__ gvstep, lon
     }
 }
 
-// row-major [B][T][256] <-> fragment order [B][wave][a][tt][lane][4] (Stage-A kernel and tests): element r of lane 16 g + t
-// is feature 32 w + 16 a + 4 g + r of token 16 tt + t (tokens >= T: zero)
-static __global__ void to_hfrag_kernel(const float *__restrict__ rows, float *__restrict__ frag, int B, int T) {
-    const long total = (long)B * 8 * 2 * NTT_A * 64;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        long j = i >> 6;
-        const int tt = (int)(j % NTT_A); j /= NTT_A;
-        const int a = (int)(j & 1); j >>= 1;
-        const int w = (int)(j & 7);
-        const long b = j >> 3;
-        const int tok = 16 * tt + (lane & 15), n = 32 * w + 16 * a + 4 * (lane >> 4);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (tok < T) v = *reinterpret_cast<const f32x4 *>(rows + ((long)b * T + tok) * D + n);
-        *reinterpret_cast<f32x4 *>(frag + i * 4) = v;
-    }
-}
-static __global__ void from_hfrag_kernel(const float *__restrict__ frag, float *__restrict__ rows, int B, int T) {
-    const long total = (long)B * 8 * 2 * NTT_A * 64;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        long j = i >> 6;
-        const int tt = (int)(j % NTT_A); j /= NTT_A;
-        const int a = (int)(j & 1); j >>= 1;
-        const int w = (int)(j & 7);
-        const long b = j >> 3;
-        const int tok = 16 * tt + (lane & 15), n = 32 * w + 16 * a + 4 * (lane >> 4);
-        if (tok < T) *reinterpret_cast<f32x4 *>(rows + ((long)b * T + tok) * D + n) = *reinterpret_cast<const f32x4 *>(frag + i * 4);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // device pieces
 // ---------------------------------------------------------------------------------------------------
@@ -409,22 +377,6 @@ __device__ __forceinline__ StepScale step_scale(const LayerW &L) {
     const float sv = fminf(s5, s7);
     return StepScale{1.0f / (ACT * L.sc[6]), sv, sv / s5, sv / s7};
 }
-
-// ---------------------------------------------------------------------------------------------------
-// Stage-A experiment kernel (tools/exp/traj_layer.hip): h' = h + SelfAttention(LN1(h)), h in fragment order
-// ---------------------------------------------------------------------------------------------------
-struct SaArgs {
-    const float *h_in;
-    float *h_out;
-    const float *ln_w, *ln_b;
-    const f16 *w_in;
-    const float *b_in;
-    const f16 *w_o;
-    const float *b_o;
-    float s_in, s_o;
-    float scale_log2e;
-    int T, B;
-};
 
 // ---------------------------------------------------------------------------------------------------
 // One whole denoiser step of the sampler per launch: x -> embedding + positional rows -> L decoder layers -> fc_out -> DDIM update
@@ -1463,37 +1415,6 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
     TJ_STAMP(39);
 }
 
-
-static __device__ __forceinline__ void sa_body(const SaArgs &a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    Ctx c;
-    ctx_init(c, smem, a.T);
-    const long traj = blockIdx.x;
-    TJ_STAMP(0);
-    const float *hin = a.h_in + traj * HFRAG_FLOATS + (long)c.w * (2 * NTT * 256) + c.lane * 4;
-    f32x4 H[2][NTT];
-#pragma unroll
-    for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-        for (int tt = 0; tt < NTT; ++tt) H[aa][tt] = *reinterpret_cast<const f32x4 *>(hin + (aa * NTT + tt) * 256);
-    TJ_STAMP(1);
-    layer_norm_to_x<true>(c, H, a.ln_w, a.ln_b);
-    const float up = ACT * a.s_o;
-    scale_h(H, up);
-    TJ_STAMP(2);
-    const SaW sw{a.w_in, a.b_in, a.w_o, a.s_in, a.scale_log2e, nullptr};
-    Bias2 bo;
-    sa_block(c, sw, H, a.b_o, bo);
-    TJ_STAMP(31);
-    unscale_h(H, 1.0f / up, bo);
-    float *hout = a.h_out + traj * HFRAG_FLOATS + (long)c.w * (2 * NTT * 256) + c.lane * 4;
-#pragma unroll
-    for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-        for (int tt = 0; tt < NTT; ++tt) __builtin_nontemporal_store(H[aa][tt], reinterpret_cast<f32x4 *>(hout + (aa * NTT + tt) * 256));
-    TJ_STAMP(32);
-}
-
 template <bool WIDE = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1668,8 +1589,6 @@ static __device__ __forceinline__ void step_body(const StepArgs &a) {
     TJ_STAMP(40);
 }
 };   // struct TJ
-
-static __global__ __launch_bounds__(NTHREADS, 2) void traj_sa_kernel(SaArgs a) { TJ<NTT_A, false>::sa_body(a); }
 
 // sampler mode 3: NTT token tiles; PRECISE = three fp16 products at the Q | K | V site too
 template <int NTT, bool PRECISE>

@@ -1,0 +1,354 @@
+// Tuned trajectory step kernels of the sampler (modes 3 / 4: hidden_dim 256, 4 heads, horizon <= 100, <= 64 memory rows): the host side
+// of sd_traj.h - shape test, the three preparation stages, the step launch - and the step-token kernels that only this path launches.
+// Interface towards the sampler's driver (sd_kernels.hip): sd_traj_host.h, function for function what sd_trajg.h is for the generic family.
+//
+// Built without packed fp32 vector instructions (soccerdiffusion_amd/build.py, EXTRA_FLAGS): the step kernel lives on the overlap of
+// plain fp32 instructions with MFMAs.  build() checks the object.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/soccerdiffusion_hip.h"
+
+#include "sd_common.h"
+#include "sd_traj.h"
+#include "sd_traj_host.h"
+
+// ---- sampler mode 3: the trajectory-owning step kernel (sd_traj.h) ---------------------------------------
+// One launch per DDIM step: embedding, all layers (self-attention inside), fc_out and the DDIM update for one trajectory per
+// workgroup.  Same folded cross-attention blocks (gv, cb) and abs-max words as mode 2; the split planes are written in the
+// 16x16x32 fragment order of sd_traj.h into the same workspace regions.  SD_SAMPLER_TRAJ=0 in the environment keeps mode 2.
+bool traj_ok(int d, int heads, int T, int Mk, int J, int L) {
+    static const char *env = getenv("SD_SAMPLER_TRAJ");
+    if (env && strcmp(env, "0") == 0) return false;
+    // any joint count up to 32 (the embedding's K and fc_out's N are zero-padded to 32 in the packed planes; the reference's database
+    // has 22 joints: soccer_diffusion/dataset/models.py:222-247)
+    static const char *mr = getenv("SD_TRAJ_MAXROWS");   // A/B runs: memory rows beyond this go to the generic kernels (sd_trajg.hip) instead of the wide instantiation
+    const int max_rows = mr ? atoi(mr) : 64;
+    return f16_env_ok() && d == 256 && heads == 4 && T >= 1 && T <= tj::TMAX && Mk >= 1 && Mk <= (max_rows < 64 ? max_rows : 64) && J >= 1 && J <= 32 && L >= 1 &&
+           L <= tj::MAX_L;
+}
+// key tiles of 16 memory slots in the folded blocks: 1 for the trajectory kernels proper, 2 .. 4 for traj_step_wide_kernel (17 .. 64 rows)
+static int key_tiles(int Mk) { return Mk <= 16 ? 1 : (Mk + 15) / 16; }
+
+// the instantiation for ceil(T / 16) token tiles; precise = three fp16 products at the Q | K | V site too (sampler mode 3), else two (mode 4)
+typedef void (*TrajStepFn)(tj::StepArgs);
+static TrajStepFn traj_step_wide_fn(int ntt) {
+    switch (ntt) {
+        case 1: return tj::traj_step_wide_kernel<1>;
+        case 2: return tj::traj_step_wide_kernel<2>;
+        case 3: return tj::traj_step_wide_kernel<3>;
+        case 4: return tj::traj_step_wide_kernel<4>;
+        case 5: return tj::traj_step_wide_kernel<5>;
+        case 6: return tj::traj_step_wide_kernel<6>;
+        case 7: return tj::traj_step_wide_kernel<7>;
+        default: return nullptr;
+    }
+}
+template <bool PRECISE>
+static TrajStepFn traj_step_fn(int ntt) {
+    switch (ntt) {
+        case 1: return tj::traj_step_kernel<1, PRECISE>;
+        case 2: return tj::traj_step_kernel<2, PRECISE>;
+        case 3: return tj::traj_step_kernel<3, PRECISE>;
+        case 4: return tj::traj_step_kernel<4, PRECISE>;
+        case 5: return tj::traj_step_kernel<5, PRECISE>;
+        case 6: return tj::traj_step_kernel<6, PRECISE>;
+        case 7: return tj::traj_step_kernel<7, PRECISE>;
+        default: return nullptr;
+    }
+}
+
+// zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
+__global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows * ncols) mb[(i / ncols) * 8 + col0 + i % ncols] = 0u;
+}
+static int zero_word_cols(unsigned *mb, int rows, int col0, int ncols, hipStream_t st) {
+    SD_LAUNCH(zero_word_cols_kernel, dim3((unsigned)((rows * ncols + 63) / 64)), dim3(64), 0, st, mb, rows, col0, ncols);
+    SD_CHECK_LAUNCH("zero_word_cols_kernel");
+    return 0;
+}
+
+// The trajectory path prepares its operands in three independent stages (sd_ddim_sample_eps runs all three per call;
+// sd_sampler_prepare / sd_sampler_eps let a caller that evaluates the denoiser step by step - the reference's own loop,
+// soccer_diffusion/ml/inference/plot.py:122-131 - keep the first two across calls):
+//   weights: abs-max + split planes of every matrix (words 0 .. 3 of a layer's row of the abs-max table, 6 / 7 of row L)
+//   context: K / V of the context rows, the fold, its split blocks g16 / v16 (words 4 / 5, scales sc[4] / sc[5])
+//   steps:   K / V of the n_tok step tokens, their fold, the split step blocks (words 6 / 7, scales sc[6] / sc[7])
+int traj_prepare_weights(const sd_denoiser_weights *w, const TrajWs &s, hipStream_t st) {
+    const int d = w->d, L = w->L;
+    int rc = zero_word_cols(s.maxbits, L, 0, 4, st);
+    if (!rc) rc = zero_word_cols(s.maxbits + L * 8, 1, 6, 2, st);
+    if (rc) return rc;
+    for (int l = 0; l < L; ++l) {
+        const sd_layer_weights &lw = w->layers[l];
+        const float *mats[4] = {lw.sa_out_w, lw.lin1_w, lw.lin2_w, lw.sa_in_w};
+        const int rows[4] = {d, d, d, 3 * d};
+        for (int m = 0; m < 4; ++m) {
+            if ((rc = f16_absmax(mats[m], (long)rows[m] * d, s.maxbits + l * 8 + m, st))) return rc;
+        }
+    }
+    if ((rc = f16_absmax(w->emb_w, (long)d * w->J, s.maxbits + L * 8 + 6, st))) return rc;
+    if ((rc = f16_absmax(w->out_w, (long)d * w->J, s.maxbits + L * 8 + 7, st))) return rc;
+    SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)d * 4)), dim3(256), 0, st, w->emb_w, d, w->J, d, 32, s.maxbits + L * 8 + 6, 0.f, s.wio,
+              s.scales + L * 8 + 6);
+    SD_CHECK_LAUNCH("pack_w16_kernel");
+    SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)32 * d / 8)), dim3(256), 0, st, w->out_w, w->J, d, 32, d, s.maxbits + L * 8 + 7, 0.f,
+              s.wio + (size_t)2 * 32 * d, s.scales + L * 8 + 7);
+    SD_CHECK_LAUNCH("pack_w16_kernel");
+    for (int l = 0; l < L; ++l) {
+        const sd_layer_weights &lw = w->layers[l];
+        const float *mats[4] = {lw.sa_out_w, lw.lin1_w, lw.lin2_w, lw.sa_in_w};
+        const int rows[4] = {d, d, d, 3 * d};
+        for (int m = 0; m < 4; ++m) {
+            SD_LAUNCH(tj::pack_w16_kernel, dim3(grid_for((long)rows[m] * d / 8)), dim3(256), 0, st, mats[m], rows[m], d, rows[m], d, s.maxbits + l * 8 + m, 0.f,
+                      f16_wf(s.wf, l, d, m), s.scales + l * 8 + m);
+            SD_CHECK_LAUNCH("pack_w16_kernel");
+        }
+    }
+    return 0;
+}
+
+int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, hipStream_t st) {
+    const int d = w->d, L = w->L, nkt = key_tiles(Mc + 1);
+    const size_t gvstride = (size_t)B * nkt * 64 * 2 * d, cbstride = (size_t)B * nkt * 64;
+    int rc = zero_async(s.gv, L * gvstride * sizeof(float), st);   // unused key slots must be finite
+    if (!rc) rc = zero_async(s.cb, L * cbstride * sizeof(float), st);
+    if (!rc) rc = zero_word_cols(s.maxbits, L, 4, 2, st);
+    if (rc) return rc;
+    const size_t blk = (size_t)32 * d;   // halfs per (trajectory, head)
+    for (int l = 0; l < L; ++l) {
+        const sd_layer_weights &lw = w->layers[l];
+        unsigned *mb = s.maxbits + l * 8;
+        if (Mc > 0) {
+            const long rows = (long)B * Mc;
+            float *kvl = s.kvtmp + (size_t)l * B * Mc * 2 * d;
+            rc = linear(ctx, lw.ca_in_w + (size_t)d * d, lw.ca_in_b + d, nullptr, nullptr, nullptr, kvl, B * Mc, 2 * d, d, 0, st, 0);
+            if (rc) return rc;
+            rc = xattn_fold(kvl, rows, Mc, lw.ca_in_w, lw.ca_in_b, lw.ca_out_w, s.gv + l * gvstride, s.cb + l * cbstride, 64L * nkt, 16, d, mb + 4, mb + 5, st);
+            if (rc) return rc;
+        }
+        SD_LAUNCH(tj::pack_g16_kernel, dim3(grid_for((long)B * nkt * 4 * 16 * d / 8)), dim3(256), 0, st, s.gv + l * gvstride, (long)B * nkt, Mc, mb + 4,
+                  s.g16 + (size_t)l * B * nkt * 4 * blk, s.scales + l * 8 + 4, nkt);
+        SD_CHECK_LAUNCH("pack_g16_kernel");
+        SD_LAUNCH(tj::pack_v16_kernel, dim3(grid_for((long)B * nkt * 16 * 2 * 64)), dim3(256), 0, st, s.gv + l * gvstride, (long)B * nkt, Mc, mb + 5,
+                  s.v16 + (size_t)l * B * nkt * 4 * blk, s.scales + l * 8 + 5, nkt);
+        SD_CHECK_LAUNCH("pack_v16_kernel");
+    }
+    return 0;
+}
+
+// ---- the step tokens' part of the preparation, all layers in one launch each (a forward_with_context call of the reference's loop pays
+// it once per call: four launches instead of four per layer)
+struct StepFoldArgs { const float *wkv[tj::MAX_L], *bkv[tj::MAX_L], *wq[tj::MAX_L], *bq[tj::MAX_L], *woc[tj::MAX_L]; };
+// hidden_dim 256.  step_kv_kernel, grid (n_tok, L, 8), 256 threads: rows 64 z .. 64 z + 63 of K | V = Wkv tok + bkv (memory rows are not
+// layer-normed) -> kvstep[l][tok][2 D].  step_fold_all_kernel, grid (n_tok, L, 4 heads): the fold of xattn_fold_kernel for this one row and head:
+// G_h = Wq_h^T K_h, V'_h = Woc_h V_h, c_h = bq_h . K_h -> gvstep row [tok * 4 + h][2 D], cstep [tok * 4 + h]; abs-max of G / V' -> words 6 / 7 of
+// the layer's row.  (One workgroup per (token, layer) did all of it as a chain of dependent weight loads: 130 us for ONE token - what every
+// forward_with_context call of the reference's loop pays, 27 % of a B = 256 rollout; 16 rows in flight per wave: 100 us; the work of a token
+// and layer spread over 8 + 4 workgroups: see NOTEBOOK round 5.)
+__global__ __launch_bounds__(256) void step_kv_kernel(StepFoldArgs a, const float *__restrict__ tokens, float *__restrict__ kvstep, long n_tok,
+                                                      const int *__restrict__ map) {
+    constexpr int D = tj::D;
+    const int l = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long tok = blockIdx.x;
+    if (map && map[tok] != (int)tok) return;   // a duplicate of token 0: nobody reads its blocks
+    const f32x4 t4 = *reinterpret_cast<const f32x4 *>(tokens + tok * D + 4 * lane);
+    const float *wkv = a.wkv[l], *bkv = a.bkv[l];
+    const int o0 = blockIdx.z * 64 + wv * 16;
+    f32x4 w4[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) w4[u] = *reinterpret_cast<const f32x4 *>(wkv + (long)(o0 + u) * D + 4 * lane);
+    float *out = kvstep + ((long)l * n_tok + tok) * 2 * D;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const float s = wave_sum((w4[u][0] * t4[0] + w4[u][1] * t4[1]) + (w4[u][2] * t4[2] + w4[u][3] * t4[3]));
+        if (lane == 0) out[o0 + u] = s + bkv[o0 + u];
+    }
+}
+__global__ __launch_bounds__(256) void step_fold_all_kernel(StepFoldArgs a, const float *__restrict__ kvstep, long n_tok, float *__restrict__ gvstep,
+                                                            long gv_layer_stride, float *__restrict__ cstep, long c_layer_stride,
+                                                            unsigned *maxbits, const int *__restrict__ map) {
+    constexpr int D = tj::D, HD = tj::HD;
+    __shared__ __attribute__((aligned(16))) float sk[HD], sv[HD];
+    const int l = blockIdx.y, h = blockIdx.z, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long tok = blockIdx.x;
+    if (map && map[tok] != (int)tok) return;
+    const int n = threadIdx.x;
+    const float *wq = a.wq[l], *woc = a.woc[l] + (long)n * D;
+    // the head's weights first (64 + 16 loads per thread in flight), then its K / V slice
+    float wqv[HD];
+    f32x4 wov[HD / 4];
+#pragma unroll
+    for (int j = 0; j < HD; ++j) wqv[j] = wq[(long)(h * HD + j) * D + n];
+#pragma unroll
+    for (int j = 0; j < HD / 4; ++j) wov[j] = *reinterpret_cast<const f32x4 *>(woc + h * HD + 4 * j);
+    const float *kv = kvstep + ((long)l * n_tok + tok) * 2 * D;
+    if (threadIdx.x < HD) sk[threadIdx.x] = kv[h * HD + threadIdx.x];
+    else if (threadIdx.x < 2 * HD) sv[threadIdx.x - HD] = kv[D + h * HD + threadIdx.x - HD];
+    __syncthreads();
+    if (wv == 0) {   // the score bias of head h
+        const float c = wave_sum(a.bq[l][h * HD + lane] * sk[lane]);
+        if (lane == 0) cstep[l * c_layer_stride + tok * 4 + h] = c;
+    }
+    float g = 0.f, v = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) g += wqv[j] * sk[j];
+#pragma unroll
+    for (int j = 0; j < HD / 4; ++j) {
+        const f32x4 v4 = *reinterpret_cast<const f32x4 *>(sv + 4 * j);
+        v += (wov[j][0] * v4[0] + wov[j][1] * v4[1]) + (wov[j][2] * v4[2] + wov[j][3] * v4[3]);
+    }
+    float *out = gvstep + l * gv_layer_stride + tok * 4 * 2 * D;
+    out[(long)h * 2 * D + n] = g;
+    out[(long)h * 2 * D + D + n] = v;
+    float mg = fabsf(g), mv = fabsf(v);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mg = fmaxf(mg, __shfl_xor(mg, o, 64));
+        mv = fmaxf(mv, __shfl_xor(mv, o, 64));
+    }
+    if (lane == 0) {
+        const unsigned bg = __builtin_bit_cast(unsigned, mg), bv = __builtin_bit_cast(unsigned, mv);
+        if (bg > __atomic_load_n(maxbits + l * 8 + 6, __ATOMIC_RELAXED)) atomicMax(maxbits + l * 8 + 6, bg);
+        if (bv > __atomic_load_n(maxbits + l * 8 + 7, __ATOMIC_RELAXED)) atomicMax(maxbits + l * 8 + 7, bv);
+    }
+}
+// grid (blocks, L): tj::pack_gstep16_kernel + tj::pack_vstep16_kernel of every layer (scales from words 6 / 7 -> sc[6], sc[7]); with
+// no_ctx also sc[4] = sc[6], sc[5] = sc[7] (no context rows: the all-zero context blocks carry no scale of their own - a scale of 1 from an
+// abs-max of 0 would drag the common value scale of tj::step_scale down to 1)
+__global__ void pack_step16_all_kernel(const float *__restrict__ gvstep, long gv_layer_stride, long n_tok, const unsigned *maxbits,
+                                       f16 *__restrict__ gdst, long g_layer_stride, f16 *__restrict__ vdst, long v_layer_stride, float *scales,
+                                       int no_ctx, const int *__restrict__ map) {
+    constexpr int D = tj::D;
+    const int l = blockIdx.y;
+    const float sg = f16_scale_from_bits(maxbits[l * 8 + 6]), sv = f16_scale_from_bits(maxbits[l * 8 + 7]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        scales[l * 8 + 6] = sg;
+        scales[l * 8 + 7] = sv;
+        if (no_ctx) {
+            scales[l * 8 + 4] = sg;
+            scales[l * 8 + 5] = sv;
+        }
+    }
+    const float *src = gvstep + l * gv_layer_stride;
+    f16 *gd = gdst + l * g_layer_stride, *vd = vdst + l * v_layer_stride;
+    const long ng = n_tok * 4 * (D / 8), nv = n_tok * 4 * D;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < ng + nv; i += (long)gridDim.x * blockDim.x) {
+        if (i < ng) {
+            const int k8 = (int)(i % (D / 8));
+            const long ih = i / (D / 8);
+            if (map && map[ih >> 2] != (int)(ih >> 2)) continue;
+            f16x4 h0, l0, h1, l1;
+            const float *row = src + ih * 2 * D + tj::kperm(k8, 0);
+            f16_split4(*reinterpret_cast<const f32x4 *>(row), sg, h0, l0);
+            f16_split4(*reinterpret_cast<const f32x4 *>(row + 16), sg, h1, l1);
+            f16 *o = gd + ih * (8 * 2 * 32) + ((k8 >> 2) * 2) * 32 + (k8 & 3) * 8;
+            *reinterpret_cast<f16x4 *>(o) = h0;
+            *reinterpret_cast<f16x4 *>(o + 4) = h1;
+            *reinterpret_cast<f16x4 *>(o + 32) = l0;
+            *reinterpret_cast<f16x4 *>(o + 36) = l1;
+        } else {
+            const long j = i - ng;
+            const int n = (int)(j % D), head = (int)((j / D) & 3);
+            const long item = j / D / 4;
+            if (map && map[item] != (int)item) continue;
+            const float v = src[(item * 4 + head) * 2 * D + D + n] * sv;
+            const f16 h = (f16)v;
+            vd[(item * 2 + 0) * 4 * D + head * D + n] = h;
+            vd[(item * 2 + 1) * 4 * D + head * D + n] = (f16)(v - (float)h);
+        }
+    }
+}
+
+// n_tok step tokens (rows of `tokens`): one per DDIM step of a rollout, or one per trajectory of a single evaluation
+int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const float *tokens, int n_tok, int Mc, hipStream_t st, bool per_traj) {
+    const int d = w->d, L = w->L;
+    const size_t gvsstride = (size_t)n_tok * 4 * 2 * d, cssstride = (size_t)n_tok * 4;
+    const size_t blk = (size_t)32 * d;
+    int rc = zero_word_cols(s.maxbits, L, 6, 2, st);
+    if (rc) return rc;
+    const int *map = nullptr;
+    if (per_traj) {   // one token per trajectory: fold the distinct ones only (see step_map_kernel in sd_kernels.hip)
+        if ((rc = step_map(tokens, n_tok, d, s.stepmap, st))) return rc;
+        map = s.stepmap;
+    }
+    StepFoldArgs fa{};
+    for (int l = 0; l < L; ++l) {
+        const sd_layer_weights &lw = w->layers[l];
+        fa.wkv[l] = lw.ca_in_w + (size_t)d * d; fa.bkv[l] = lw.ca_in_b + d;
+        fa.wq[l] = lw.ca_in_w; fa.bq[l] = lw.ca_in_b; fa.woc[l] = lw.ca_out_w;
+    }
+    SD_LAUNCH(step_kv_kernel, dim3((unsigned)n_tok, (unsigned)L, 8), dim3(256), 0, st, fa, tokens, s.kvstep, (long)n_tok, map);
+    SD_CHECK_LAUNCH("step_kv_kernel");
+    SD_LAUNCH(step_fold_all_kernel, dim3((unsigned)n_tok, (unsigned)L, 4), dim3(256), 0, st, fa, s.kvstep, (long)n_tok, s.gvstep, (long)gvsstride, s.cstep,
+              (long)cssstride, s.maxbits, map);
+    SD_CHECK_LAUNCH("step_fold_all_kernel");
+    // per-layer regions as carved for mode 2 (n_tok * 4 * blk / n_tok * blk halfs), the step blocks packed densely inside
+    unsigned gx = grid_for((long)n_tok * 4 * (d / 8 + d));
+    SD_LAUNCH(pack_step16_all_kernel, dim3(gx, (unsigned)L), dim3(256), 0, st, s.gvstep, (long)gvsstride, (long)n_tok, s.maxbits, s.gstep16,
+              (long)((size_t)n_tok * 4 * blk), s.vstep16, (long)((size_t)n_tok * blk), s.scales, Mc == 0 ? 1 : 0, map);
+    SD_CHECK_LAUNCH("pack_step16_all_kernel");
+    return 0;
+}
+
+// one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
+// coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
+int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
+              bool per_traj, hipStream_t st, bool precise, int32_t *status) {
+    const int d = w->d, L = w->L, nkt = key_tiles(Mc + 1);
+    const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
+    tj::StepArgs a{};
+    a.nkt = nkt;
+    a.status = status;
+    a.x = x;
+    a.eps_out = eps;
+    a.w_emb = s.wio;
+    a.b_emb = w->emb_b;
+    a.pe = w->pe;
+    a.n1_w = w->layers[0].n1_w;
+    a.n1_b = w->layers[0].n1_b;
+    a.w_out = s.wio + (size_t)2 * 32 * d;
+    a.b_out = w->out_b;
+    a.sc_io = s.scales + L * 8 + 6;
+    if (coef) { a.c0 = coef[0]; a.c1 = coef[1]; a.c2 = coef[2]; a.c3 = coef[3]; }
+    a.scale_log2e = (1.0f / sqrtf((float)(d / w->heads))) * 1.44269504088896340736f;
+    a.T = T; a.B = B; a.J = w->J; a.L = L; a.Mk = Mc + 1; a.update_x = coef ? 1 : 0;
+    a.step_per_traj = per_traj ? 1 : 0;
+    a.step_map = per_traj ? s.stepmap : nullptr;
+    for (int l = 0; l < L; ++l) {
+        const sd_layer_weights &lw = w->layers[l];
+        tj::LayerW &q = a.layer[l];
+        q.n2_w = lw.n2_w; q.n2_b = lw.n2_b; q.n3_w = lw.n3_w; q.n3_b = lw.n3_b;
+        q.w_o = f16_wf(s.wf, l, d, 0); q.w_1 = f16_wf(s.wf, l, d, 1); q.w_2 = f16_wf(s.wf, l, d, 2); q.w_in = f16_wf(s.wf, l, d, 3);
+        q.b_in = lw.sa_in_b; q.b_o = lw.sa_out_b; q.b_1 = lw.lin1_b; q.b_2 = lw.lin2_b; q.b_oc = lw.ca_out_b;
+        q.sc = s.scales + l * 8;
+        q.g16 = s.g16 + (size_t)l * B * nkt * 4 * blk;
+        q.v16 = s.v16 + (size_t)l * B * nkt * 4 * blk;
+        q.cb = s.cb + l * cbstride;
+        // per-layer regions as carved for mode 2 (n_steps * 4 * blk / n_steps * blk halfs), the step blocks packed densely inside
+        q.gstep = s.gstep16 + (size_t)l * n_steps * 4 * blk + (size_t)i * (4 * 8 * 2 * 32);
+        q.vstep = s.vstep16 + (size_t)l * n_steps * blk + (size_t)i * (2 * 4 * d);
+        q.cstep = s.cstep + ((size_t)l * n_steps + i) * 4;
+        q.nln_w = l + 1 < L ? w->layers[l + 1].n1_w : nullptr;
+        q.nln_b = l + 1 < L ? w->layers[l + 1].n1_b : nullptr;
+    }
+    const int ntt = (T + 15) / 16;
+    // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
+    const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
+    const TrajStepFn fn = variant == 2 ? traj_step_wide_fn(ntt) : (precise ? traj_step_fn<true>(ntt) : traj_step_fn<false>(ntt));
+    if (!fn) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
+    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
+    static DevFlag attr_set[3][8];
+    if (!attr_set[variant][ntt]) {
+        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
+        if (e != hipSuccess) return fail((int)e, "traj_step_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        attr_set[variant][ntt] = true;
+    }
+    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a);
+    SD_CHECK_LAUNCH("traj_step_kernel");
+    return 0;
+}

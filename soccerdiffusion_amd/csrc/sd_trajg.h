@@ -11,7 +11,7 @@ struct sd_denoiser_weights;
 bool trajg_ok(int d, int heads, int T, int Mk, int J, int L);
 // floats of workspace behind the driver's own carve-up: split weight planes, the memory's K / V^T planes, step rows, scales
 size_t trajg_workspace_floats(int B, int Mc, int d, int L, int n_tok);
-// the three preparation stages of the trajectory path (see traj_prepare_* in sd_kernels.hip); kvtmp / kvstep: fp32 scratch of
+// the three preparation stages of the trajectory path (as traj_prepare_* of the tuned family: sd_traj_host.h); kvtmp / kvstep: fp32 scratch of
 // L * B * Mc * 2 d and L * n_tok * 2 d floats for the projected rows
 int trajg_prepare_weights(const sd_denoiser_weights *w, float *gws, int B, int Mc, int n_tok, hipStream_t st);
 int trajg_prepare_ctx(const sd_denoiser_weights *w, float *gws, const float *ctx, float *kvtmp, int B, int Mc, int n_tok, hipStream_t st);

@@ -1,9 +1,10 @@
-// Stage-A / Stage-B experiment: the trajectory-owning kernels of soccerdiffusion_amd/csrc/sd_traj.h on random
-// data, checked against an fp64 host restatement of the blocks they replace and timed per 4096 trajectories.
+// The trajectory-owning step kernel of soccerdiffusion_amd/csrc/sd_traj.h on random data, checked against an fp64 host restatement of
+// the blocks it replaces and timed per 4096 trajectories (part [B] of the experiment; part [A], the self-attention half
+// alone, went with its kernel once the whole step superseded it).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-value -Xclang -target-feature -Xclang -packed-fp32-ops -I include -I soccerdiffusion_amd/csrc tools/exp/traj_layer.hip -o tools/exp/traj_layer
 //   tools/exp/traj_layer [B=4096] [iters=20] [check=2] [L=4]
-// Prints (a) traj_sa_kernel: h + SelfAttention(LN1(h)) alone (Stage A), (b) traj_step_kernel: one whole denoiser step
-// (embedding, L layers with folded cross-attention and FFN, fc_out, DDIM update).  -DTJ_STAMPS adds the phase profile.
+// Prints [B] traj_step_kernel: one whole denoiser step (embedding, L layers with folded cross-attention and FFN, fc_out, DDIM update).
+// -DTJ_STAMPS adds the phase profile.
 #include "sd_traj.h"
 // -DTL_PRECISE=1: the three-product variant of the step kernel (sa_block_precise)
 #ifndef TL_PRECISE
@@ -141,63 +142,13 @@ int main(int argc, char **argv) {
     CK(hipMemset(d_st, 0, n_st * 8));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(tj::g_tj_stamps), &d_st, sizeof(d_st)));
 #endif
-    CK(hipFuncSetAttribute((const void *)tj::traj_sa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES));
     CK(hipFuncSetAttribute((const void *)(TL_STEP_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     int rc = 0;
 
-    // =============================================================================================== Stage A
-    {
-        vf h = randn((size_t)B * T * D), lnw = randu(D, 0.1f, 1.f), lnb = randu(D, 0.1f), win = randu((size_t)3 * D * D, 1.f / 16), bin = randu(3 * D, 0.1f),
-           wo = randu((size_t)D * D, 1.f / 16), bo = randu(D, 0.1f);
-        float *d_sc = dalloc<float>(2);
-        f16 *d_win16 = pack(win, 3 * D, D, 3 * D, D, d_sc), *d_wo16 = pack(wo, D, D, D, D, d_sc + 1);
-        float sc[2];
-        CK(hipMemcpy(sc, d_sc, 8, hipMemcpyDeviceToHost));
-        float *d_h = dev(h), *d_lnw = dev(lnw), *d_lnb = dev(lnb), *d_bin = dev(bin), *d_bo = dev(bo);
-        float *d_hf = dalloc<float>((size_t)B * tj::HFRAG_FLOATS), *d_of = dalloc<float>((size_t)B * tj::HFRAG_FLOATS), *d_out = dalloc<float>((size_t)B * T * D);
-        hipLaunchKernelGGL(tj::to_hfrag_kernel, dim3(2048), dim3(256), 0, 0, d_h, d_hf, B, T);
-        tj::SaArgs a{d_hf, d_of, d_lnw, d_lnb, d_win16, d_bin, d_wo16, d_bo, sc[0], sc[1], scale_log2e, T, B};
-        hipLaunchKernelGGL(tj::traj_sa_kernel, dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
-        CK(hipGetLastError());
-        hipLaunchKernelGGL(tj::from_hfrag_kernel, dim3(2048), dim3(256), 0, 0, d_of, d_out, B, T);
-        CK(hipDeviceSynchronize());
-        const int nc = ncheck < B ? ncheck : B;
-        vf got((size_t)nc * T * D);
-        CK(hipMemcpy(got.data(), d_out, got.size() * sizeof(float), hipMemcpyDeviceToHost));
-        double worst = 0;
-        for (int b = 0; b < nc; ++b) {
-            vd hh((size_t)T * D), x((size_t)T * D);
-            for (size_t i = 0; i < hh.size(); ++i) hh[i] = h[(size_t)b * T * D + i];
-            layer_norm(hh, lnw, lnb, x, T, D);
-            self_attention(hh, x, win, bin, wo, bo, T, D, H);
-            double num = 0, den = 0;
-            for (size_t i = 0; i < hh.size(); ++i) {
-                const double gvv = got[(size_t)b * T * D + i];
-                num += (gvv - hh[i]) * (gvv - hh[i]);
-                den += hh[i] * hh[i];
-            }
-            worst = fmax(worst, sqrt(num / den));
-        }
-        printf("[A] traj_sa_kernel: worst rel L2 error vs fp64 over %d trajectories %.3e (%s)\n", nc, worst, worst < 2e-5 ? "PASS" : "FAIL");
-        rc |= !(worst < 2e-5);   // (the Q | K | V projection reads one fp16 plane of LN1(h): ~5e-6 here, 4e-7 with both)
-        for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(tj::traj_sa_kernel, dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
-        CK(hipEventRecord(e0));
-        for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(tj::traj_sa_kernel, dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
-        CK(hipEventRecord(e1));
-        CK(hipEventSynchronize(e1));
-        float ms;
-        CK(hipEventElapsedTime(&ms, e0, e1));
-        const double us = ms * 1000.0 / iters;
-        const double mfma = 4.0 * (84 * 8 + 49 * 2 + 28 * 4 + 112 * 2) * 3.0;   // 16x16x32 MFMAs per trajectory
-        printf("[A] traj_sa_kernel: B=%d  %.1f us per launch = %.1f us per 4096 trajectories, executed %.0f TFLOP/s fp16 MFMA\n", B, us, us * 4096.0 / B,
-               mfma * 16384 * B / us * 1e-6);
-        CK(hipFree(d_h)); CK(hipFree(d_hf)); CK(hipFree(d_of)); CK(hipFree(d_out));
-    }
-
-    // =============================================================================================== Stage B: a whole step
+    // =============================================================================================== a whole step
     {
         vf x = randn((size_t)B * T * J), wemb = randu((size_t)D * J, 0.2f), bemb = randu(D, 0.1f), pe = randu((size_t)T * D, 1.0f), wout = randu((size_t)J * D, 1.f / 16),
            bout = randu(J, 0.1f);

@@ -1,13 +1,19 @@
 """Per-kernel register / scratch / occupancy table from hipcc's resource-usage remarks.
-usage: python tools/kernel_resources.py [substring]   (compiles sd_kernels.hip and sd_train.hip for gfx950)"""
+usage: python tools/kernel_resources.py [substring [unit ...]]   (compiles the named units, e.g. sd_traj sd_trajg - default: every unit of
+the library - for gfx950 with the product's flags: soccerdiffusion_amd.build.SRC / compile_cmd)"""
+import os
 import re
 import subprocess
 import sys
+import tempfile
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from soccerdiffusion_amd import build as b  # noqa: E402
 
 pat = sys.argv[1] if len(sys.argv) > 1 else ""
-for src in ("soccerdiffusion_amd/csrc/sd_kernels.hip", "soccerdiffusion_amd/csrc/sd_train.hip", "soccerdiffusion_amd/csrc/sd_train_chain.hip"):
-    out = subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Iinclude", "-c", src, "-o", "/dev/null",
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
+for src in [s for s in b.SRC if not sys.argv[2:] or os.path.splitext(os.path.basename(s))[0] in sys.argv[2:]]:
+    with tempfile.TemporaryDirectory() as tmp:
+        out = subprocess.run(b.compile_cmd(src, os.path.join(tmp, "unit.o"), verbose=True), cwd=b.CSRC, capture_output=True, text=True).stderr
     cur = None
     rows = {}
     for line in out.splitlines():

@@ -1,6 +1,6 @@
 """Phase profile of decoder_layer_kernel from in-kernel shader-clock stamps (diagnostic build).
 
-  tools/ab_build.sh stamps "-DSD_STAMPS"     # here
+  AB_TU=sd_kernels tools/ab_build.sh stamps "-DSD_STAMPS"     # here
   gpurun -- 'SD_HIP_LIB=$PWD/soccerdiffusion_amd/lib/variants/lib_stamps.so python tools/stamps.py'
 
 Runs 2 DDIM steps of the bench workload and prints, per layer launch, the median share of a workgroup's

@@ -641,6 +641,35 @@ int sd_head_pool_bwd(const float *dpooled, float *dx, int N, int HW, int C, void
 int sd_frames_area(const uint8_t *store, int64_t n_frames, const int64_t *index, int64_t n_slots, int R, const int32_t *taps, const float *weights,
                    int n_weights, float *out, void *stream);
 
+/* ---- closed-loop policy session (the receding-horizon tick of soccer_diffusion/ml/inference/ros.py:165-335), csrc/sd_session.hip.
+ * A sensor ring is an fp32 device buffer (B, L, C) - one ring of L rows per robot - with one int32 head word per robot's ring in device
+ * memory (head (B)): the index of the ring's OLDEST row, which is also where the next row is written.  Chronological row i of robot b is
+ * ring[b][(head[b] + i) % L].  The head lives on the device so that a launch's arguments are the same at every tick.  One workgroup owns
+ * a robot's ring: it reads the head, writes the rows, and moves the head after a barrier - no atomics.
+ *   sd_ring_push: appends n rows per robot, oldest first, from src (B, n, C) (device memory, or pinned host memory the device can read);
+ *     ring row = src row - sub (C) where sub is given (NULL: a copy); with n > L only the last L rows are written; head += n (mod L).
+ *   sd_ring_window: out (B, L, C) = the chronological window of the ring (a copy).
+ *   sd_session_windows: the same for up to SD_SESSION_MAX_RINGS rings in one launch; a view with wrap != 0 writes the reference's
+ *     (x + 3 * np.pi) % (2 * np.pi) (ros.py:266-273) as torch evaluates it on an fp32 tensor: a = x + float(3 pi), r = fmodf(a, float(2 pi)),
+ *     r += float(2 pi) where r != 0 and r < 0 - every operation exactly rounded.
+ *   sd_session_commit: x (B, T, J) the sampled normalised trajectory -> out (B, T, J) = x * std + mean - float(pi) (the published trajectory,
+ *     ros.py:313,327; product, sum and difference rounded one by one) and the same T rows pushed into the action-history ring (B, L, J)
+ *     (ros.py:316-318).  Every element is read once and stored to both places, so out may be x (in place).
+ * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
+#define SD_SESSION_MAX_RINGS 3
+typedef struct sd_ring_view {
+    const float *ring;     /* (B, L, C) */
+    const int32_t *head;   /* (B) */
+    float *out;            /* (B, L, C) */
+    int32_t L, C;
+    int32_t wrap, _pad;
+} sd_ring_view;
+int sd_ring_push(float *ring, int32_t *head, const float *src, const float *sub, int B, int L, int C, int n, void *stream);
+int sd_ring_window(const float *ring, const int32_t *head, float *out, int B, int L, int C, void *stream);
+int sd_session_windows(const sd_ring_view *views, int n_views, int B, void *stream);
+int sd_session_commit(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, int B, int T, int J, int L,
+                      void *stream);
+
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair
  * on the launch stream.  sd_profile_collect waits for them, returns the summed device

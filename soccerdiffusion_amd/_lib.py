@@ -104,6 +104,13 @@ class HeadGemmArgs(C.Structure):
                 + [("bias", C.c_void_p), ("scratch", C.c_void_p), ("accumulate", C.c_int32), ("_pad", C.c_int32)])
 
 
+class RingView(C.Structure):
+    """sd_ring_view (field order = header order)."""
+
+    _fields_ = [("ring", C.c_void_p), ("head", C.c_void_p), ("out", C.c_void_p), ("L", C.c_int32), ("C", C.c_int32), ("wrap", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors the header one to one (tests check the export list)
 SIGNATURES = {
     "sd_abi_version": (C.c_int, []),
@@ -204,6 +211,10 @@ SIGNATURES = {
     "sd_head_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_head_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_frames_area": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "sd_ring_push": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "sd_ring_window": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "sd_session_windows": (C.c_int, [C.POINTER(RingView), C.c_int, C.c_int, C.c_void_p]),
+    "sd_session_commit": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

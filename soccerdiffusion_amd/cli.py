@@ -5,6 +5,7 @@ soccer_diffusion/ml/inference/plot.py:21-135).
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out]     (ml/training/distill.py:25-224)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -402,6 +403,53 @@ def cmd_sample(args) -> int:
     return 0
 
 
+def synthetic_sensor_stream(n: int, params: dict, ticks: int, seed: int = 0) -> dict:
+    """A sensor stream for ``ticks`` control ticks of n robots, shaped like what ros.py's timers deliver (ros.py:155-163): per tick
+    ``trajectory_prediction_length`` joint-state and rotation samples (the resample rate) and two frames (10 Hz against the 0.2 s tick).
+    Sine-wave joints as raw angles around 0 (the node wraps them itself), unit quaternions, noise frames."""
+    g = torch.Generator().manual_seed(seed)
+    J, T = params["num_joints"], params["trajectory_prediction_length"]
+    total = ticks * T
+    phase = torch.rand(n, 1, J, generator=g) * 2 * math.pi
+    freq = 0.5 + torch.rand(n, 1, J, generator=g)
+    wave = torch.sin(2 * math.pi * freq * torch.arange(total).view(1, total, 1) / 50.0 + phase)
+    quat = torch.randn(n, total, 4, generator=g)
+    quat = quat / quat.norm(dim=-1, keepdim=True)
+    rot = quat if params["imu_orientation_embedding_method"] != "five_dim" else torch.cat([quat[..., :3], torch.sin(quat[..., 3:]), torch.cos(quat[..., 3:])], -1)
+    out = {"joint_state": wave.contiguous(), "rotation": rot.contiguous()}
+    if params.get("use_images"):
+        R = params.get("image_resolution", 480)
+        out["image_data"] = torch.rand(n, 2 * ticks, 3, R, R, generator=g)
+    return out
+
+
+def cmd_rollout(args) -> int:
+    """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep."""
+    from .session import PolicySession
+
+    if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
+        raise SystemExit("rollout needs --synthetic N (robots, N >= 1) and --ticks K (K >= 1)")
+    device = torch.device("cuda", _dist_env()[2])
+    torch.cuda.set_device(device)
+    session = PolicySession.from_checkpoint(args.checkpoint, device, num_inference_steps=args.steps, batch=args.synthetic, seed=args.seed)
+    params = session.hyperparams
+    stream = {k: v.to(device) for k, v in synthetic_sensor_stream(args.synthetic, params, args.ticks, seed=args.seed).items()}
+    T = params["trajectory_prediction_length"]
+    published = []
+    for k in range(args.ticks):
+        if params["use_joint_states"]:
+            session.push_joint_state(stream["joint_state"][:, k * T:(k + 1) * T])
+        if params["use_imu"]:
+            session.push_rotation(stream["rotation"][:, k * T:(k + 1) * T])
+        if params.get("use_images"):
+            session.push_image(stream["image_data"][:, 2 * k:2 * k + 2])
+        published.append(session.step())
+    traj = torch.stack(published).cpu()   # (K, N, T, J)
+    torch.save({"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}, args.output)
+    print(f"rolled out {args.ticks} ticks of {args.synthetic} robots, trajectories of shape {tuple(traj.shape[2:])} -> {args.output}")
+    return 0
+
+
 def params_need_context(params: dict) -> bool:
     return any(params.get(k, False) for k in ("use_action_history", "use_imu", "use_joint_states", "use_images", "use_gamestate"))
 
@@ -437,10 +485,17 @@ def main(argv: Optional[list] = None) -> int:
         p.add_argument("--image-size", type=str, default=None, metavar="HxW", help="--synthetic only: frame size when it is not the "
                        "square image_resolution of the config (BASELINE's image-conditioned case uses 480x640)")
         p.add_argument("--seed", type=int, default=0)
+    ro = sub.add_parser("rollout", help="drive a closed-loop policy session (the tick of the reference's ros.py) from a synthetic sensor stream")
+    ro.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
+    ro.add_argument("--synthetic", type=int, default=None, metavar="N", help="number of robots stepping in lockstep on a synthetic sensor stream")
+    ro.add_argument("--ticks", type=int, default=10, metavar="K", help="number of control ticks")
+    ro.add_argument("--output", "-o", type=str, default="rollout.pt", help="Where to save the K published trajectories")
+    ro.add_argument("--steps", type=int, default=30, help="Number of denoising steps per tick")
+    ro.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("soccerdiffusion_amd needs an MI355X (no CPU fallback)")
-    return {"train": cmd_train, "sample": cmd_sample, "distill": cmd_distill}[args.command](args)
+    return {"train": cmd_train, "sample": cmd_sample, "distill": cmd_distill, "rollout": cmd_rollout}[args.command](args)
 
 
 if __name__ == "__main__":

@@ -1459,3 +1459,69 @@ def resnet_head_backward(dy: Tensor, x: Tensor, feat: Tensor, conv_w: Optional[T
     head_gemm(N * HW, Cc, 32, _operand(dfeat, dz_k, (0, 0, HW)), _operand(conv_w, (0, 0, Cc), (0, 0, 1)), _operand(dx, (0, 0, Cc), (0, 0, 1)),
               device=dev)
     return dx
+
+
+# --------------------------------------------------------------------------------------
+# closed-loop policy session: device-side sensor rings (csrc/sd_session.hip; the stateful layer is session.py)
+# --------------------------------------------------------------------------------------
+def _ring_req(ring: Tensor, head: Tensor) -> tuple:
+    _req(ring, "ring"); _req(head, "head", torch.int32)
+    if ring.dim() != 3 or head.dim() != 1 or head.shape[0] != ring.shape[0] or head.device != ring.device:
+        raise ValueError(f"a ring is (B, L, C) fp32 with an int32 head word per robot, got {tuple(ring.shape)} and {tuple(head.shape)}")
+    return tuple(ring.shape)
+
+
+def ring_push(ring: Tensor, head: Tensor, rows: Tensor, sub: Optional[Tensor] = None) -> None:
+    """Appends rows (B, n, C), oldest first, to the ring (B, L, C) and advances its heads; ``sub`` (C) is subtracted from every row."""
+    B, L, Cc = _ring_req(ring, head)
+    _req(rows, "rows")
+    if rows.dim() != 3 or rows.shape[0] != B or rows.shape[2] != Cc or rows.device != ring.device:
+        raise ValueError(f"rows: expected ({B}, n, {Cc}) on {ring.device}, got {tuple(rows.shape)} on {rows.device}")
+    if sub is not None and (_req(sub, "sub").numel() != Cc or sub.device != ring.device):
+        raise ValueError(f"sub: expected {Cc} values on {ring.device}")
+    check(_lib.load().sd_ring_push(ring.data_ptr(), head.data_ptr(), rows.data_ptr(), _ptr(sub), B, L, Cc, rows.shape[1], _stream()), "sd_ring_push")
+
+
+def ring_window(ring: Tensor, head: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The chronological window (B, L, C) of a ring."""
+    shape = _ring_req(ring, head)
+    if out is None:
+        out = torch.empty_like(ring)
+    elif tuple(_req(out, "out").shape) != shape or out.device != ring.device:
+        raise ValueError(f"out: expected {shape} on {ring.device}")
+    check(_lib.load().sd_ring_window(ring.data_ptr(), head.data_ptr(), out.data_ptr(), *shape, _stream()), "sd_ring_window")
+    return out
+
+
+class SessionWindows:
+    """The argument block of ``sd_session_windows`` for up to three (ring, head, out, wrap) views of one batch: built once, launched at every
+    tick with the same arguments (the heads are device words)."""
+
+    def __init__(self, views: Sequence[tuple]):
+        if not 1 <= len(views) <= 3:
+            raise ValueError("one to three rings per launch")
+        self.tensors = []
+        self.array = (_lib.RingView * len(views))()
+        for i, (ring, head, out, wrap) in enumerate(views):
+            shape = _ring_req(ring, head)
+            if tuple(_req(out, "out").shape) != shape or out.device != ring.device or (i and shape[0] != self.B):
+                raise ValueError(f"view {i}: out {tuple(out.shape)} does not match its ring {shape}, or the batch differs")
+            self.B = shape[0]
+            self.tensors.append((ring, head, out))   # the block holds raw pointers: keep their owners alive
+            v = self.array[i]
+            v.ring, v.head, v.out, v.L, v.C, v.wrap = ring.data_ptr(), head.data_ptr(), out.data_ptr(), shape[1], shape[2], int(bool(wrap))
+
+    def launch(self) -> None:
+        check(_lib.load().sd_session_windows(self.array, len(self.array), self.B, _stream()), "sd_session_windows")
+
+
+def session_commit(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, head: Tensor) -> Tensor:
+    """The published trajectory x * std + mean - pi (B, T, J) of a sampled normalised one, also pushed into the action-history ring."""
+    B, L, J = _ring_req(ring, head)
+    _req(x, "x"); _req(mean, "mean"); _req(std, "std")
+    if x.dim() != 3 or x.shape[0] != B or x.shape[2] != J or mean.numel() != J or std.numel() != J or x.device != ring.device:
+        raise ValueError(f"x: expected ({B}, T, {J}) with {J} means and stds, got {tuple(x.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.load().sd_session_commit(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(), head.data_ptr(),
+                                        B, x.shape[1], J, L, _stream()), "sd_session_commit")
+    return out

@@ -1,0 +1,277 @@
+"""Closed-loop policy session: the receding-horizon tick of the reference's robot node (soccer_diffusion/ml/inference/ros.py:165-335) with
+the sensor buffers on the device.
+
+ros.py keeps every stream as a Python list of CPU tensors, stacks and uploads all of them at every tick and runs the image backbone on
+the whole frame window again, although only the frames that arrived since the last tick are new (its own TODO, ros.py:180-183).  A
+``PolicySession`` owns one ring per enabled modality in device memory (csrc/sd_session.hip): ``push_*`` appends rows, ``push_image``
+encodes the new frames only and stores their tokens, and ``step`` is windows -> context encoders -> rollout -> commit.  In eval mode a
+frame's token depends on that frame alone (BatchNorm on running statistics, no dropout), so caching it changes nothing but the batch the
+backbone kernels see.
+
+    s = PolicySession(model, num_inference_steps=30, batch=1, hyperparams=checkpoint["hyperparams"])
+    s.push_joint_state(q); s.push_rotation(r); s.push_image(frame)     # the callbacks / timers of ros.py:165-257
+    traj = s.step()                                                   # (B, T, J): what ros.py:321-335 publishes
+
+There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
+
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import ops
+
+KEYS = ("joint_command_history", "rotation", "joint_state")   # the ring modalities, in encode_input_data's order
+WRAPPED = {"joint_command_history": True, "rotation": False, "joint_state": True}   # (x + 3 pi) % (2 pi): ros.py:266-273
+DEFAULT_GAME_STATE = 2   # ros.py:274
+
+
+class _GraphedTick:
+    """Windows, context encoders and rollout of one session's tick as one captured hipGraph (linear; the warm-up and capture recipe of
+    ``ops.GraphedSampler``).  The graph changes no ring - the commit stays outside - so warming it up and capturing it leave the
+    session's state alone.  A call copies the noise into the captured buffer, replays, reads the range-guard word back as the eager
+    route does (``ops.ddim_sample_guarded``) and returns the captured sample buffer, which the next call overwrites."""
+
+    def __init__(self, session: "PolicySession", x_T: torch.Tensor):
+        m, dev = session.model, session.device
+        self.session = session
+        ts = ops.ddim_timesteps(session.n_steps)
+        self.packed = m.diffusion_action_generator.packed()
+        self.tokens = m.step_encoding.table(ts, dev)
+        self.coef = ops.ddim_coefficients(ts, ops.alphas_cumprod(), session.n_steps)
+        self.cap = ops.sampler_cap(self.packed, 3)
+        self.noise = x_T.clone()
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._run()   # outside capture: lazy module loads, the workspaces of this stream
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._run()
+
+    def _run(self) -> None:
+        self.ctx = self.session._context()
+        ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
+        self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap)
+
+    def __call__(self, x_T: torch.Tensor) -> torch.Tensor:
+        self.noise.copy_(x_T)
+        self.graph.replay()
+        if int(self.status.item()) == 0:
+            return self.x
+        # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
+        s = self.session
+        return s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3).contiguous()
+
+
+class PolicySession:
+    def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
+                 hyperparams: Optional[dict] = None, use_graph: bool = False):
+        """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
+        model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
+        ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
+        also read for ``distilled_decoder`` unless ``distilled`` says it.  ``use_graph``: windows, context encoders and rollout of
+        ``step`` are replayed from one captured hipGraph (not for a distilled decoder)."""
+        params = [p for p in model.parameters()]
+        if model.training:
+            raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
+        if not params or not all(p.is_cuda for p in params):
+            raise RuntimeError("PolicySession: the model is on the CPU; soccerdiffusion_amd has no CPU path - move it to the GPU (model.cuda())")
+        if batch < 1 or num_inference_steps < 1:
+            raise ValueError("batch and num_inference_steps must be positive")
+        self.model, self.B, self.n_steps = model, int(batch), int(num_inference_steps)
+        self.device = params[0].device
+        hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
+        self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
+        self.hyperparams = hp
+        self.T, self.J = model.trajectory_prediction_length, model.num_joints
+        self._seed, self._watched = int(seed), None
+        self.use_graph = bool(use_graph)
+        if self.use_graph and self.distilled:
+            raise ValueError("PolicySession: use_graph replays the rollout; a distilled decoder has none")
+        encoders = {"joint_command_history": model.action_history_encoder, "rotation": model.imu_encoder,
+                    "joint_state": model.joint_states_encoder}
+        self._encoders = {k: e for k, e in encoders.items() if e is not None}
+        self._shapes = {k: (e.max_seq_len, e.input_dim) for k, e in self._encoders.items()}
+        self._images = model.image_sequence_encoder
+        if self._images is not None:
+            seq = getattr(self._images, "transformer_encoder", None)   # SequenceEncoderType.NONE: the image encoder itself
+            self._image_encoder = self._images.image_encoder if seq is not None else self._images
+            self._sequence = seq
+            S = seq.max_seq_len if seq is not None else hp.get("image_context_length")
+            R = hp.get("image_resolution")
+            if S is None or R is None:
+                raise ValueError("PolicySession: a model with images needs hyperparams with image_resolution (and image_context_length "
+                                 "where it has no sequence encoder)")
+            self.S, self.R = int(S), int(R)
+        self.reset()
+
+    # ---- the plan: shapes from hyperparameters alone ---------------------------------------
+    @staticmethod
+    def plan(hyperparams: dict) -> dict:
+        """Ring shapes (rows, columns) per robot and the decoder's memory rows for a hyperparameter dictionary (a shipped YAML):
+        context tokens per modality = context length // encoder_patch_size, one per image, one for the game state; + the step token."""
+        hp, p = hyperparams, hyperparams["encoder_patch_size"]
+        J = hp["num_joints"]
+        rings, tokens = {}, 0
+        if hp["use_action_history"]:
+            rings["joint_command_history"] = (hp["action_context_length"], J)
+        if hp["use_imu"]:
+            rings["rotation"] = (hp["imu_context_length"], 5 if hp["imu_orientation_embedding_method"] == "five_dim" else 4)
+        if hp["use_joint_states"]:
+            rings["joint_state"] = (hp["joint_state_context_length"], J)
+        tokens = sum(L // p for L, _ in rings.values())
+        if hp["use_images"]:
+            rings["image_tokens"] = (hp["image_context_length"], hp["hidden_dim"])
+            tokens += hp["image_context_length"]
+        if hp["use_gamestate"]:
+            tokens += 1
+        return {"rings": rings, "context_rows": tokens, "memory_rows": tokens + 1, "trajectory": (hp["trajectory_prediction_length"], J)}
+
+    # ---- state -----------------------------------------------------------------------------
+    def _weights_key(self) -> tuple:
+        """ops.weights_generation() (FusedAdamW and replayed training graphs rewrite parameters without touching their version counters)
+        and the versions of every parameter and persistent buffer (BatchNorm statistics, mean, std)."""
+        if self._watched is None:   # (rebuilt by reset())
+            self._watched = list(self.model.parameters()) + [b for mod in self.model.modules() for n, b in mod._buffers.items()
+                                                             if b is not None and n not in mod._non_persistent_buffers_set]
+        return (ops.weights_generation(), tuple(t._version for t in self._watched))
+
+    def _check_weights(self, what: str) -> None:
+        if self._key != self._weights_key():
+            raise RuntimeError(f"PolicySession.{what}: the model's weights changed since the session was built; its cached image tokens "
+                               "belong to the old weights - call reset()")
+
+    def reset(self) -> None:
+        """Rings back to ``context_length`` rows of zeros (ros.py:87-106), the image ring to the token of an all-zero frame
+        (ros.py:88-92), the game state to 2, the noise generator to the seed; the current weights become the session's."""
+        if self.model.training:
+            raise RuntimeError("PolicySession.reset: the model is in train() mode - call model.eval()")
+        dev, B = self.device, self.B
+        new = lambda L, C: (torch.zeros(B, L, C, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+        self._rings = {k: new(L, C) for k, (L, C) in self._shapes.items()}
+        self._wins = {k: torch.empty_like(r) for k, (r, _) in self._rings.items()}
+        # the commit always has a ring to push into: without an action-history encoder a private one of T rows that nothing reads
+        self._action = self._rings.get("joint_command_history") or new(self.T, self.J)
+        self._launch = (ops.SessionWindows([(*self._rings[k], self._wins[k], WRAPPED[k]) for k in KEYS if k in self._rings])
+                        if self._rings else None)
+        self._game_state = torch.full((B,), DEFAULT_GAME_STATE, dtype=torch.int64, device=dev)
+        self._gen = torch.Generator(device=dev).manual_seed(self._seed)
+        self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._watched, self._graph = None, None
+        self._key = self._weights_key()
+        if self._images is not None:
+            d = self.model.hidden_dim
+            self._tokens = new(self.S, d)
+            self._token_win = torch.empty_like(self._tokens[0])
+            with torch.no_grad():
+                zero = self._image_encoder(torch.zeros(1, 1, 3, self.R, self.R, dtype=torch.float32, device=dev))   # (1, 1, d)
+            ops.ring_push(*self._tokens, zero.expand(B, self.S, d).contiguous())
+
+    # ---- pushes ----------------------------------------------------------------------------
+    def _rows(self, x: torch.Tensor, tail: tuple, name: str) -> torch.Tensor:
+        """(B, *tail) or (B, n, *tail) -> a contiguous fp32 device tensor (B, n, *tail); the caller's tensor is only read."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x)
+        if x.dim() == len(tail) + 1:
+            x = x.unsqueeze(1)
+        if x.dim() != len(tail) + 2 or x.shape[0] != self.B or tuple(x.shape[2:]) != tail:
+            raise ValueError(f"{name}: expected ({self.B}, {', '.join(map(str, tail))}) or ({self.B}, n, {', '.join(map(str, tail))}), "
+                             f"got {tuple(x.shape)}")
+        return x.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _push(self, key: str, x: torch.Tensor, name: str) -> None:
+        if key not in self._rings:
+            raise RuntimeError(f"PolicySession.{name}: the model has this modality switched off - there is no ring to push into")
+        ops.ring_push(*self._rings[key], self._rows(x, (self._shapes[key][1],), name))
+
+    def push_joint_state(self, q: torch.Tensor) -> None:
+        """Raw joint angles (B, J) or (B, n, J), oldest first, as ros.py:205-214 stores them (the wrap happens in ``step``)."""
+        self._push("joint_state", q, "push_joint_state")
+
+    def push_rotation(self, r: torch.Tensor) -> None:
+        """Orientation rows (B, 4 | 5) or (B, n, 4 | 5) (quaternion or the five-dimensional form: ros.py:216-253)."""
+        self._push("rotation", r, "push_rotation")
+
+    def push_image(self, frames: torch.Tensor) -> None:
+        """Frames (B, 3, R, R) or (B, n, 3, R, R), preprocessed as ros.py:191-200 and already at ``image_resolution``: encoded now by
+        the model's image encoder, on these frames only; the tokens go into the ring and no frame is kept."""
+        if self._images is None:
+            raise RuntimeError("PolicySession.push_image: the model has images switched off - there is no ring to push into")
+        self._check_weights("push_image")
+        if self.model.training:
+            raise RuntimeError("PolicySession.push_image: the model is in train() mode - call model.eval()")
+        x = self._rows(frames, (3, self.R, self.R), "push_image")
+        with torch.no_grad():
+            tokens = self._image_encoder(x)
+        ops.ring_push(*self._tokens, tokens.contiguous())
+
+    def set_game_state(self, idx) -> None:
+        """Game state index per robot (an int for all of them, or B of them); ros.py:274 feeds the constant 2."""
+        if isinstance(idx, int):
+            self._game_state.fill_(idx)
+        else:
+            self._game_state.copy_(torch.as_tensor(idx).reshape(self.B))
+
+    # ---- the tick --------------------------------------------------------------------------
+    def _context(self) -> list:
+        m = self.model
+        if self._launch is not None:
+            self._launch.launch()
+        ctx = [self._encoders[k](self._wins[k]) for k in KEYS if k in self._encoders]
+        if self._images is not None:
+            ops.ring_window(*self._tokens, out=self._token_win)
+            ctx.append(self._sequence(self._token_win) if self._sequence is not None else self._token_win)
+        if m.game_state_encoder is not None:
+            ctx.append(m.game_state_encoder(self._game_state))
+        return ctx
+
+    def windows(self) -> dict:
+        """Copies of the contiguous windows the next ``step`` would encode, keyed as ``encode_input_data``'s input (``image_tokens``:
+        the per-frame tokens, what the image sequence encoder reads)."""
+        if self._launch is not None:
+            self._launch.launch()
+        out = {k: w.clone() for k, w in self._wins.items()}
+        if self._images is not None:
+            out["image_tokens"] = ops.ring_window(*self._tokens)
+        if self.model.game_state_encoder is not None:
+            out["game_state"] = self._game_state.clone()
+        return out
+
+    def step(self, x_T: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One tick (ros.py:259-335): the published trajectory (B, T, J) = denormalised sample - pi, also appended to the action
+        history.  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator."""
+        m = self.model
+        self._check_weights("step")
+        if m.training:
+            raise RuntimeError("PolicySession.step: the model is in train() mode - call model.eval()")
+        shape = (self.B, self.T, self.J)
+        if x_T is None:
+            x_T = torch.randn(shape, dtype=torch.float32, device=self.device, generator=self._gen)
+        elif tuple(x_T.shape) != shape or not x_T.is_cuda or x_T.dtype != torch.float32:
+            raise ValueError(f"x_T: expected an fp32 tensor {shape} on {self.device}, got {tuple(x_T.shape)} {x_T.dtype} on {x_T.device}")
+        with torch.no_grad():
+            if self.use_graph:
+                if self._graph is None:   # first tick after construction / reset(): the rings are new
+                    self._graph = _GraphedTick(self, x_T)
+                return ops.session_commit(self._graph(x_T), m.mean, m.std, *self._action)
+            ctx = self._context()
+            if self.distilled:   # one forward at t = 0 (ros.py:293-298)
+                x = m.forward_with_context(ctx, x_T.contiguous(), self._t0)
+            else:
+                x = m.sample(ctx, x_T, self.n_steps, max_mode=3)
+            return ops.session_commit(x.contiguous(), m.mean, m.std, *self._action)
+
+    @classmethod
+    def from_checkpoint(cls, path: str, device=None, **kwargs) -> "PolicySession":
+        """A session on the model of a checkpoint written by ``cli train`` / ``cli distill`` (or by the reference)."""
+        from .cli import build_model
+
+        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        model = build_model(ckpt["hyperparams"]).to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        model.load_state_dict(ckpt["model_state_dict"])
+        return cls(model.eval(), hyperparams=ckpt["hyperparams"], **kwargs)

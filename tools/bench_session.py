@@ -1,0 +1,168 @@
+#!/usr/bin/env python3
+"""Tick latency of the closed control loop (soccer_diffusion/ml/inference/ros.py:259-335: budget 0.2 s per tick), PolicySession against
+the same tick written on the public API that exists without it - what ros.py does: Python lists of CPU tensors as sensor buffers, per
+tick append + trim, torch.stack(...).to(device) of every modality (the whole frame window included), the wrap on the device,
+encode_input_data on the full windows (the backbone on all ten frames), model.sample, ops.normalize(inverse) - pi, and the published rows
+back into the host-side action list.  Both ticks start from new sensor rows in host memory and end with the trajectory in host memory.
+
+Shapes: default.yaml and sim_scratch.yaml with their images (10 frames of 224 x 224, ResNet-18 without the final avgpool), per tick
+trajectory_prediction_length joint-state / rotation samples and two new frames (ros.py:155-163), 30 DDIM steps, B = 1, 16, 64 robots.
+Three variants run in one process, in alternating blocks of ticks - the list tick, the session, and the session with use_graph=True
+(windows, encoders and rollout replayed from one hipGraph) -; one JSON line per case with the median and the extremes of the blocks per
+variant and the spread (the largest range of a variant's blocks).  The list tick's sensor lists are ordinary pageable host tensors, as
+ros.py's are.  The first tick of the variants is compared as well (same sensor rows, same noise), and the host time of the session's
+stale-weights check (a scan of every parameter's version counter, twice per tick with images) is timed on its own.
+Exit status 1 when a session variant is slower than the list tick beyond the spread in any case, or a first tick differs by more than 1e-4.
+usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from soccerdiffusion_amd import cli, ops  # noqa: E402
+from soccerdiffusion_amd.session import PolicySession  # noqa: E402
+
+BASE = dict(action_context_length=100, trajectory_prediction_length=10, epochs=1, batch_size=1, lr=1e-4, train_denoising_timesteps=1000,
+            image_context_length=10, imu_context_length=100, joint_state_context_length=100, num_normalization_samples=10, num_joints=20,
+            use_images=True, image_sequence_encoder_type="transformer", image_encoder_type="resnet18", image_resolution=224,
+            image_use_final_avgpool=False, num_image_sequence_encoder_layers=1, distill_teacher_inference_steps=30)
+CONFIGS = {   # the values of the reference's YAML of the same name
+    "default": dict(hidden_dim=128, use_action_history=True, num_action_history_encoder_layers=2, use_imu=True,
+                    imu_orientation_embedding_method="quaternion", num_imu_encoder_layers=2, use_joint_states=True,
+                    joint_state_encoder_layers=2, num_decoder_layers=4, use_gamestate=True, encoder_patch_size=1),
+    "sim_scratch": dict(hidden_dim=256, use_action_history=True, num_action_history_encoder_layers=4, use_imu=True,
+                        imu_orientation_embedding_method="five_dim", num_imu_encoder_layers=2, use_joint_states=False,
+                        joint_state_encoder_layers=4, num_decoder_layers=6, use_gamestate=False, encoder_patch_size=5),
+}
+N_STEPS, NEW_FRAMES = 30, 2
+
+
+class ListNode:
+    """The tick as ros.py writes it, for B robots in lockstep (every list entry is (B, ...))."""
+
+    def __init__(self, model, params, B):
+        self.m, self.p, self.B, self.dev = model, params, B, torch.device("cuda")
+        J, R = params["num_joints"], params["image_resolution"]
+        rot = 5 if params["imu_orientation_embedding_method"] == "five_dim" else 4
+        self.len = {"joint_command_history": params["action_context_length"], "rotation": params["imu_context_length"],
+                    "joint_state": params["joint_state_context_length"], "image_data": params["image_context_length"]}
+        tail = {"joint_command_history": (J,), "rotation": (rot,), "joint_state": (J,), "image_data": (3, R, R)}
+        on = {"joint_command_history": params["use_action_history"], "rotation": params["use_imu"], "joint_state": params["use_joint_states"],
+              "image_data": params["use_images"]}
+        self.lists = {k: [torch.zeros(B, *tail[k])] * self.len[k] for k in tail if on[k]}     # ros.py:87-106
+
+    def append(self, key, rows):
+        if key in self.lists:
+            for i in range(rows.shape[1]):
+                self.lists[key].append(rows[:, i])
+            self.lists[key] = self.lists[key][-self.len[key]:]
+
+    def tick(self, new, x_T):
+        for key, rows in new.items():
+            self.append(key, rows)
+        batch = {}
+        for key, lst in self.lists.items():                                                     # ros.py:265-275
+            x = torch.stack(list(lst), dim=1).to(self.dev)
+            batch[key] = (x + 3 * np.pi) % (2 * np.pi) if key in ("joint_state", "joint_command_history") else x
+        if self.p["use_gamestate"]:
+            batch["game_state"] = torch.zeros(self.B, dtype=torch.long).to(self.dev) + 2
+        with torch.no_grad():
+            x = self.m.sample(self.m.encode_input_data(batch), x_T, N_STEPS)
+            traj = (ops.normalize(x.contiguous(), self.m.mean, self.m.std, inverse=True) - np.pi).cpu()   # ros.py:313-327
+        self.append("joint_command_history", traj)
+        return traj
+
+
+def session_tick(s, new, x_T):
+    if "joint_state" in new:
+        s.push_joint_state(new["joint_state"])
+    if "rotation" in new:
+        s.push_rotation(new["rotation"])
+    s.push_image(new["image_data"])
+    return s.step(x_T).cpu()
+
+
+def sensor_rows(params, B, g):
+    J, T, R = params["num_joints"], params["trajectory_prediction_length"], params["image_resolution"]
+    new = {"image_data": torch.rand(B, NEW_FRAMES, 3, R, R, generator=g)}
+    if params["use_joint_states"]:
+        new["joint_state"] = (torch.rand(B, T, J, generator=g) - 0.5) * 2 * np.pi
+    if params["use_imu"]:
+        new["rotation"] = torch.randn(B, T, 5 if params["imu_orientation_embedding_method"] == "five_dim" else 4, generator=g)
+    return new
+
+
+def block_ms(tick, news, x_T):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for new in news:
+        tick(new, x_T)          # (ends in a device-to-host copy of the trajectory: every tick is synchronised)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / len(news) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true", help="B = 1 and 16 only, fewer blocks")
+    ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--ticks", type=int, default=10, help="ticks per block")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_session.py measures on the GPU: no device found")
+    blocks = 3 if args.quick else args.blocks
+    failed = False
+    for name, over in CONFIGS.items():
+        params = {**BASE, **over}
+        torch.manual_seed(0)
+        model = cli.build_model(params).cuda().eval()
+        T, J = params["trajectory_prediction_length"], params["num_joints"]
+        for B in ((1, 16) if args.quick else (1, 16, 64)):
+            g = torch.Generator().manual_seed(7)
+            node, s = ListNode(model, params, B), PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params)
+            sg = PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params, use_graph=True)
+            x_T = torch.randn(B, T, J, device="cuda", generator=torch.Generator(device="cuda").manual_seed(8))
+            first = sensor_rows(params, B, g)
+            a, b, c = node.tick(first, x_T), session_tick(s, first, x_T), session_tick(sg, first, x_T)   # same state, rows, noise
+            err = float((b.double() - a.double()).norm() / a.double().norm())
+            err_graph = float((c.double() - b.double()).norm() / b.double().norm())
+            news = [sensor_rows(params, B, g) for _ in range(args.ticks)]
+            variants = (node.tick, lambda new, x: session_tick(s, new, x), lambda new, x: session_tick(sg, new, x))
+            for tick in variants:                                          # warm-up: one untimed block of every variant at this shape
+                block_ms(tick, news, x_T)
+            base, sess, graph = [], [], []
+            for _ in range(blocks):                                        # alternating blocks: drift of the box hits all of them
+                for tick, into in zip(variants, (base, sess, graph)):
+                    into.append(block_ms(tick, news, x_T))
+            mb, ms, mg = statistics.median(base), statistics.median(sess), statistics.median(graph)
+            spread = max(max(v) - min(v) for v in (base, sess, graph))
+            t0 = time.perf_counter()
+            for _ in range(200):
+                s._check_weights("bench")
+            check_us = (time.perf_counter() - t0) / 200 * 1e6
+            ok = bool(ms <= mb + spread and mg <= mb + spread and err < 1e-4 and err_graph < 1e-4)
+            failed = failed or not ok
+            rec = {"config": name, "B": B, "steps": N_STEPS, "frames_in_window": params["image_context_length"], "new_frames_per_tick": NEW_FRAMES,
+                   "frame_size": [params["image_resolution"]] * 2, "memory_rows": PolicySession.plan(params)["memory_rows"],
+                   "blocks": blocks, "ticks_per_block": args.ticks,
+                   "list_tick_ms": {"median": round(mb, 3), "min": round(min(base), 3), "max": round(max(base), 3)},
+                   "list_buffers": "pageable host memory",
+                   "session_tick_ms": {"median": round(ms, 3), "min": round(min(sess), 3), "max": round(max(sess), 3)},
+                   "session_graph_tick_ms": {"median": round(mg, 3), "min": round(min(graph), 3), "max": round(max(graph), 3)},
+                   "spread_ms": round(spread, 3), "gain": round(mb / ms, 3), "gain_graph": round(mb / mg, 3),
+                   "graph_minus_eager_ms": round(mg - ms, 3), "weights_check_us": round(check_us, 1),
+                   "session_not_slower_beyond_spread": ok, "first_tick_rel_err": float(f"{err:.3e}"),
+                   "first_tick_graph_vs_eager_rel_err": float(f"{err_graph:.3e}")}
+            print(json.dumps(rec), flush=True)
+            del node, s, sg
+    if failed:
+        raise SystemExit(1)
+
+
+if __name__ == "__main__":
+    main()

@@ -655,8 +655,24 @@ int sd_frames_area(const uint8_t *store, int64_t n_frames, const int64_t *index,
  *   sd_session_commit: x (B, T, J) the sampled normalised trajectory -> out (B, T, J) = x * std + mean - float(pi) (the published trajectory,
  *     ros.py:313,327; product, sum and difference rounded one by one) and the same T rows pushed into the action-history ring (B, L, J)
  *     (ros.py:316-318).  Every element is read once and stored to both places, so out may be x (in place).
+ * A subset of the robots (robots that tick at their own times, episodes that end robot by robot): the *_at forms take robots (S), int32
+ * indices in device memory, and launch S workgroups (per ring); workgroup s owns robot robots[s], and the caller's arrays are compact.
+ * The indices MUST BE DISTINCT: two workgroups of one launch that own the same ring race on its rows and its head word.  Nothing on the
+ * device checks that - it is the host's job, before the indices are uploaded (ops.robot_index).  An index outside [0, B) is tolerated:
+ * its workgroup performs no store.  Rings and head words of robots that are not named are neither read nor written.
+ *   sd_ring_push_at: src (S, n, C); block s is appended to the ring of robot robots[s], as sd_ring_push appends block b to robot b's.
+ *   sd_ring_window_at, sd_session_windows_at: out (S, L, C) per ring; row block s = the chronological window of robot robots[s], with
+ *     the same wrap and the same 16-byte path as sd_session_windows.
+ *   sd_session_commit_at: x and out (S, T, J); the T rows go into the action ring of robot robots[s] only, rounded as in sd_session_commit.
+ *   S == 0 (and n == 0 in a push) returns 0 without a launch.
+ *   sd_session_reset: the start state of an episode for the robots with mask[b] != 0 (mask (B) uint8 in device memory - a simulator's
+ *     done flags as they are; NULL: every robot), for up to SD_SESSION_MAX_RESET_RINGS rings in ONE launch of (B, n_rings) workgroups:
+ *     all L rows of the robot's ring = fill (C floats in device memory; NULL: zeros), its head word = 0 (by one thread, after a barrier),
+ *     and, in ring 0's workgroup, game_state[b] = game_state_value (game_state (B) int64; NULL: none).  A workgroup whose robot is not
+ *     selected returns at once.  The arguments are the same whichever robots are selected and the host reads nothing back.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
+#define SD_SESSION_MAX_RESET_RINGS 5
 typedef struct sd_ring_view {
     const float *ring;     /* (B, L, C) */
     const int32_t *head;   /* (B) */
@@ -664,11 +680,25 @@ typedef struct sd_ring_view {
     int32_t L, C;
     int32_t wrap, _pad;
 } sd_ring_view;
+typedef struct sd_ring_reset {
+    float *ring;         /* (B, L, C) */
+    int32_t *head;       /* (B) */
+    const float *fill;   /* (C), or NULL for zeros */
+    int32_t L, C;
+} sd_ring_reset;
 int sd_ring_push(float *ring, int32_t *head, const float *src, const float *sub, int B, int L, int C, int n, void *stream);
 int sd_ring_window(const float *ring, const int32_t *head, float *out, int B, int L, int C, void *stream);
 int sd_session_windows(const sd_ring_view *views, int n_views, int B, void *stream);
 int sd_session_commit(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, int B, int T, int J, int L,
                       void *stream);
+int sd_ring_push_at(float *ring, int32_t *head, const float *src, const float *sub, const int32_t *robots, int S, int B, int L, int C, int n,
+                    void *stream);
+int sd_ring_window_at(const float *ring, const int32_t *head, float *out, const int32_t *robots, int S, int B, int L, int C, void *stream);
+int sd_session_windows_at(const sd_ring_view *views, int n_views, const int32_t *robots, int S, int B, void *stream);
+int sd_session_commit_at(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, const int32_t *robots,
+                         int S, int B, int T, int J, int L, void *stream);
+int sd_session_reset(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value, int B,
+                     void *stream);
 
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair

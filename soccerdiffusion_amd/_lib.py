@@ -111,6 +111,12 @@ class RingView(C.Structure):
                 ("_pad", C.c_int32)]
 
 
+class RingReset(C.Structure):
+    """sd_ring_reset (field order = header order)."""
+
+    _fields_ = [("ring", C.c_void_p), ("head", C.c_void_p), ("fill", C.c_void_p), ("L", C.c_int32), ("C", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors the header one to one (tests check the export list)
 SIGNATURES = {
     "sd_abi_version": (C.c_int, []),
@@ -215,6 +221,11 @@ SIGNATURES = {
     "sd_ring_window": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "sd_session_windows": (C.c_int, [C.POINTER(RingView), C.c_int, C.c_int, C.c_void_p]),
     "sd_session_commit": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "sd_ring_push_at": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    "sd_ring_window_at": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "sd_session_windows_at": (C.c_int, [C.POINTER(RingView), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sd_session_commit_at": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]),
+    "sd_session_reset": (C.c_int, [C.POINTER(RingReset), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

@@ -424,18 +424,28 @@ def synthetic_sensor_stream(n: int, params: dict, ticks: int, seed: int = 0) -> 
 
 
 def cmd_rollout(args) -> int:
-    """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep."""
+    """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep.
+    --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
         raise SystemExit("rollout needs --synthetic N (robots, N >= 1) and --ticks K (K >= 1)")
+    episode = None
+    if args.episode_ticks is not None:
+        try:
+            lengths = [int(v) for v in args.episode_ticks.split(",")]
+        except ValueError:
+            lengths = []
+        if not lengths or min(lengths) < 1:
+            raise SystemExit("--episode-ticks takes positive tick counts E[,E...]")
+        episode = torch.tensor([lengths[b % len(lengths)] for b in range(args.synthetic)])
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, num_inference_steps=args.steps, batch=args.synthetic, seed=args.seed)
     params = session.hyperparams
     stream = {k: v.to(device) for k, v in synthetic_sensor_stream(args.synthetic, params, args.ticks, seed=args.seed).items()}
     T = params["trajectory_prediction_length"]
-    published = []
+    published, resets = [], []
     for k in range(args.ticks):
         if params["use_joint_states"]:
             session.push_joint_state(stream["joint_state"][:, k * T:(k + 1) * T])
@@ -444,8 +454,15 @@ def cmd_rollout(args) -> int:
         if params.get("use_images"):
             session.push_image(stream["image_data"][:, 2 * k:2 * k + 2])
         published.append(session.step())
+        if episode is not None:
+            resets.append((k + 1) % episode == 0)
+            if resets[-1].any():
+                session.reset(robots=resets[-1])
     traj = torch.stack(published).cpu()   # (K, N, T, J)
-    torch.save({"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}, args.output)
+    saved = {"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}
+    if episode is not None:
+        saved["resets"] = torch.stack(resets)   # (K, N): robot n was reset after tick k
+    torch.save(saved, args.output)
     print(f"rolled out {args.ticks} ticks of {args.synthetic} robots, trajectories of shape {tuple(traj.shape[2:])} -> {args.output}")
     return 0
 
@@ -491,6 +508,8 @@ def main(argv: Optional[list] = None) -> int:
     ro.add_argument("--ticks", type=int, default=10, metavar="K", help="number of control ticks")
     ro.add_argument("--output", "-o", type=str, default="rollout.pt", help="Where to save the K published trajectories")
     ro.add_argument("--steps", type=int, default=30, help="Number of denoising steps per tick")
+    ro.add_argument("--episode-ticks", type=str, default=None, metavar="E[,E...]", help="episode length in ticks, robot b's is E[b %% len(E)]: "
+                    "after its last tick that robot alone is reset and goes on; the output gains 'resets' (K, N)")
     ro.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():

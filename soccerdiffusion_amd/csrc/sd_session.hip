@@ -1,11 +1,15 @@
 // Closed-loop policy session: the buffer work of the receding-horizon tick (soccer_diffusion/ml/inference/ros.py:165-335) on the device.
-// Interface, ring layout and citations: include/soccerdiffusion_hip.h (sd_ring_push, sd_ring_window, sd_session_windows, sd_session_commit).
+// Interface, ring layout and citations: include/soccerdiffusion_hip.h (sd_ring_push, sd_ring_window, sd_session_windows, sd_session_commit,
+// their *_at forms for a subset of the robots, and sd_session_reset).
 //
 // ros.py keeps every sensor stream as a Python list of CPU tensors (append, then trim to the context length: ros.py:203,256-257,316-318)
 // and stacks + uploads every list at every tick (ros.py:265-275).  Here a stream is a ring (B, L, C) in device memory with one head word per
 // robot's ring: head = index of the oldest row = where the next row goes.  One workgroup owns one robot's ring: every thread reads the head,
 // the rows are written, and after a barrier thread 0 moves the head - nothing else in the launch reads it, so no atomics are needed.  Every
 // index is reduced mod L before it addresses memory: a head word that was overwritten by something else cannot send a store out of the ring.
+//
+// Which robot a workgroup owns: robot blockIdx.x, or robots[blockIdx.x] where the launch names a subset (the *_at entry points); the caller's
+// arrays (src, x, out) are then compact, one block per named robot.  A name outside [0, B) makes its workgroup return before any store.
 //
 // Arithmetic: contraction is off in this file.  The wrap and the published trajectory are compared bit for bit with torch's CPU expressions,
 // which round every product, sum and difference on its own.
@@ -19,6 +23,12 @@
 namespace ss {
 
 constexpr int THREADS = 256;
+
+// the robot of workgroup s, or -1 (no store) where the subset names a robot that does not exist; the same in every thread of the workgroup
+__device__ __forceinline__ int robot_of(const int32_t *robots, int s, int B) {
+    const int b = robots ? robots[s] : s;
+    return (unsigned)b < (unsigned)B ? b : -1;
+}
 
 __device__ __forceinline__ int head_of(const int32_t *head, int b, int L) {
     const int h = head[b] % L;
@@ -47,10 +57,11 @@ __device__ __forceinline__ void push_rows(float *ring, int h, int L, int C, int 
 }
 
 __global__ __launch_bounds__(THREADS) void ring_push_kernel(float *ring, int32_t *head, const float *__restrict__ src, const float *__restrict__ sub,
-                                                            int L, int C, int n) {
-    const int b = blockIdx.x;
+                                                            const int32_t *__restrict__ robots, int B, int L, int C, int n) {
+    const int b = robot_of(robots, blockIdx.x, B);
+    if (b < 0) return;
     const int h = head_of(head, b, L);
-    const float *s = src + (long)b * n * C;
+    const float *s = src + (long)blockIdx.x * n * C;
     push_rows(ring + (long)b * L * C, h, L, C, n, [&](int r, int c) {
         const float v = s[(long)r * C + c];
         return sub ? v - sub[c] : v;
@@ -61,15 +72,18 @@ __global__ __launch_bounds__(THREADS) void ring_push_kernel(float *ring, int32_t
 
 struct Views {
     sd_ring_view v[SD_SESSION_MAX_RINGS];
+    const int32_t *robots;
+    int B;
 };
 
-// grid (B, n_views): chronological row i of robot b = ring row (head + i) % L; 16-byte pieces where the rows allow it
+// grid (S, n_views): chronological row i of robot b = ring row (head + i) % L; 16-byte pieces where the rows allow it
 __global__ __launch_bounds__(THREADS) void ring_windows_kernel(Views a) {
     const sd_ring_view v = a.v[blockIdx.y];
-    const int b = blockIdx.x, L = v.L, C = v.C;
+    const int b = robot_of(a.robots, blockIdx.x, a.B), L = v.L, C = v.C;
+    if (b < 0) return;
     const int h = head_of(v.head, b, L);
     const float *ring = v.ring + (long)b * L * C;
-    float *out = v.out + (long)b * L * C;
+    float *out = v.out + (long)blockIdx.x * L * C;
     const bool vec = (C & 3) == 0 && !v.wrap && ((reinterpret_cast<uintptr_t>(v.ring) | reinterpret_cast<uintptr_t>(v.out)) & 15) == 0;
     if (vec) {
         const int C4 = C >> 2;
@@ -88,11 +102,13 @@ __global__ __launch_bounds__(THREADS) void ring_windows_kernel(Views a) {
 
 __global__ __launch_bounds__(THREADS) void session_commit_kernel(const float *x, const float *__restrict__ mean,
                                                                  const float *__restrict__ stdv, float *out, float *ring,
-                                                                 int32_t *head, int T, int J, int L) {
-    const int b = blockIdx.x;
+                                                                 int32_t *head, const int32_t *__restrict__ robots, int B, int T, int J,
+                                                                 int L) {
+    const int b = robot_of(robots, blockIdx.x, B);
+    if (b < 0) return;
     const int h = head_of(head, b, L);
-    const float *xb = x + (long)b * T * J;
-    float *ob = out + (long)b * T * J;
+    const float *xb = x + (long)blockIdx.x * T * J;
+    float *ob = out + (long)blockIdx.x * T * J;
     float *rb = ring + (long)b * L * J;
     const float pi = (float)M_PI;
     const int r0 = T > L ? T - L : 0;          // (as push_rows: with T > L only the last L rows reach the ring)
@@ -106,10 +122,31 @@ __global__ __launch_bounds__(THREADS) void session_commit_kernel(const float *x,
     if (threadIdx.x == 0) head[b] = (h + T % L) % L;
 }
 
-static int launch_windows(const Views &a, int n_views, int B, hipStream_t st) {
-    SD_LAUNCH(ring_windows_kernel, dim3((unsigned)B, (unsigned)n_views), dim3(THREADS), 0, st, a);
+static int launch_windows(const Views &a, int n_views, int S, hipStream_t st) {
+    SD_LAUNCH(ring_windows_kernel, dim3((unsigned)S, (unsigned)n_views), dim3(THREADS), 0, st, a);
     SD_CHECK_LAUNCH("ring_windows_kernel");
     return 0;
+}
+
+struct Resets {
+    sd_ring_reset r[SD_SESSION_MAX_RESET_RINGS];
+};
+
+// grid (B, n_rings): a selected robot's ring back to L rows of fill (zeros without one) and its head to 0; ring 0's workgroup also writes the
+// robot's game state.  The mask is read, never the head: a reset does not depend on what the head word holds.
+__global__ __launch_bounds__(THREADS) void session_reset_kernel(Resets a, const uint8_t *__restrict__ mask, int64_t *game_state,
+                                                                int64_t game_state_value) {
+    const int b = blockIdx.x;
+    if (mask && !mask[b]) return;
+    const sd_ring_reset r = a.r[blockIdx.y];
+    const int L = r.L, C = r.C;
+    float *ring = r.ring + (long)b * L * C;
+    for (int i = threadIdx.x; i < L * C; i += THREADS) ring[i] = r.fill ? r.fill[i % C] : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        r.head[b] = 0;
+        if (blockIdx.y == 0 && game_state) game_state[b] = game_state_value;
+    }
 }
 
 }   // namespace ss
@@ -120,7 +157,18 @@ extern "C" int sd_ring_push(float *ring, int32_t *head, const float *src, const 
     if (!ring || !head || !dims_ok(B, L, C) || n < 0 || (n > 0 && !src) || (long)n * C > 0x7fffffffL / 2)
         return fail(SD_E_BADARG, "sd_ring_push: ring, head and (for n > 0) src must be given; B, L, C > 0, n >= 0");
     if (n == 0) return 0;
-    SD_LAUNCH(ss::ring_push_kernel, dim3((unsigned)B), dim3(ss::THREADS), 0, (hipStream_t)stream, ring, head, src, sub, L, C, n);
+    SD_LAUNCH(ss::ring_push_kernel, dim3((unsigned)B), dim3(ss::THREADS), 0, (hipStream_t)stream, ring, head, src, sub, (const int32_t *)nullptr, B, L, C,
+              n);
+    SD_CHECK_LAUNCH("ring_push_kernel");
+    return 0;
+}
+
+extern "C" int sd_ring_push_at(float *ring, int32_t *head, const float *src, const float *sub, const int32_t *robots, int S, int B, int L, int C, int n,
+                               void *stream) {
+    if (!ring || !head || !dims_ok(B, L, C) || S < 0 || n < 0 || (long)n * C > 0x7fffffffL / 2 || (S > 0 && (!robots || (n > 0 && !src))))
+        return fail(SD_E_BADARG, "sd_ring_push_at: ring, head and (for S, n > 0) src and robots must be given; B, L, C > 0, S, n >= 0");
+    if (S == 0 || n == 0) return 0;
+    SD_LAUNCH(ss::ring_push_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, ring, head, src, sub, robots, B, L, C, n);
     SD_CHECK_LAUNCH("ring_push_kernel");
     return 0;
 }
@@ -129,7 +177,18 @@ extern "C" int sd_ring_window(const float *ring, const int32_t *head, float *out
     if (!ring || !head || !out || !dims_ok(B, L, C)) return fail(SD_E_BADARG, "sd_ring_window: ring, head and out must be given; B, L, C > 0");
     ss::Views a{};
     a.v[0].ring = ring; a.v[0].head = head; a.v[0].out = out; a.v[0].L = L; a.v[0].C = C;
+    a.B = B;
     return ss::launch_windows(a, 1, B, (hipStream_t)stream);
+}
+
+extern "C" int sd_ring_window_at(const float *ring, const int32_t *head, float *out, const int32_t *robots, int S, int B, int L, int C, void *stream) {
+    if (!ring || !head || !dims_ok(B, L, C) || S < 0 || (S > 0 && (!out || !robots)))
+        return fail(SD_E_BADARG, "sd_ring_window_at: ring, head and (for S > 0) out and robots must be given; B, L, C > 0, S >= 0");
+    if (S == 0) return 0;
+    ss::Views a{};
+    a.v[0].ring = ring; a.v[0].head = head; a.v[0].out = out; a.v[0].L = L; a.v[0].C = C;
+    a.robots = robots; a.B = B;
+    return ss::launch_windows(a, 1, S, (hipStream_t)stream);
 }
 
 extern "C" int sd_session_windows(const sd_ring_view *views, int n_views, int B, void *stream) {
@@ -141,14 +200,57 @@ extern "C" int sd_session_windows(const sd_ring_view *views, int n_views, int B,
             return fail(SD_E_BADARG, "sd_session_windows: every view needs ring, head and out; L, C > 0");
         a.v[i] = views[i];
     }
+    a.B = B;
     return ss::launch_windows(a, n_views, B, (hipStream_t)stream);
+}
+
+extern "C" int sd_session_windows_at(const sd_ring_view *views, int n_views, const int32_t *robots, int S, int B, void *stream) {
+    if (!views || n_views < 1 || n_views > SD_SESSION_MAX_RINGS || B <= 0 || S < 0 || (S > 0 && !robots))
+        return fail(SD_E_BADARG, "sd_session_windows_at: 1 .. 3 views, B > 0, S >= 0 and (for S > 0) robots");
+    ss::Views a{};
+    for (int i = 0; i < n_views; ++i) {
+        if (!views[i].ring || !views[i].head || !views[i].out || !dims_ok(B, views[i].L, views[i].C))
+            return fail(SD_E_BADARG, "sd_session_windows_at: every view needs ring, head and out; L, C > 0");
+        a.v[i] = views[i];
+    }
+    if (S == 0) return 0;
+    a.robots = robots; a.B = B;
+    return ss::launch_windows(a, n_views, S, (hipStream_t)stream);
 }
 
 extern "C" int sd_session_commit(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, int B, int T, int J,
                                  int L, void *stream) {
     if (!x || !mean || !stdv || !out || !ring || !head || !dims_ok(B, L, J) || !dims_ok(B, T, J))
         return fail(SD_E_BADARG, "sd_session_commit: x, mean, std, out, ring and head must be given; B, T, J, L > 0");
-    SD_LAUNCH(ss::session_commit_kernel, dim3((unsigned)B), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head, T, J, L);
+    SD_LAUNCH(ss::session_commit_kernel, dim3((unsigned)B), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head,
+              (const int32_t *)nullptr, B, T, J, L);
     SD_CHECK_LAUNCH("session_commit_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_commit_at(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, const int32_t *robots,
+                                    int S, int B, int T, int J, int L, void *stream) {
+    if (!mean || !stdv || !ring || !head || !dims_ok(B, L, J) || !dims_ok(B, T, J) || S < 0 || (S > 0 && (!x || !out || !robots)))
+        return fail(SD_E_BADARG, "sd_session_commit_at: mean, std, ring, head and (for S > 0) x, out and robots must be given; B, T, J, L > 0, S >= 0");
+    if (S == 0) return 0;
+    SD_LAUNCH(ss::session_commit_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head, robots, B, T, J,
+              L);
+    SD_CHECK_LAUNCH("session_commit_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_reset(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value, int B,
+                                void *stream) {
+    if (!rings || n_rings < 1 || n_rings > SD_SESSION_MAX_RESET_RINGS || B <= 0)
+        return fail(SD_E_BADARG, "sd_session_reset: 1 .. 5 rings and B > 0");
+    ss::Resets a{};
+    for (int i = 0; i < n_rings; ++i) {
+        if (!rings[i].ring || !rings[i].head || !dims_ok(B, rings[i].L, rings[i].C))
+            return fail(SD_E_BADARG, "sd_session_reset: every ring needs ring and head; L, C > 0");
+        a.r[i] = rings[i];
+    }
+    SD_LAUNCH(ss::session_reset_kernel, dim3((unsigned)B, (unsigned)n_rings), dim3(ss::THREADS), 0, (hipStream_t)stream, a, mask, game_state,
+              game_state_value);
+    SD_CHECK_LAUNCH("session_reset_kernel");
     return 0;
 }

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import sys
 from typing import Mapping, Optional, Sequence
 
@@ -1471,25 +1472,77 @@ def _ring_req(ring: Tensor, head: Tensor) -> tuple:
     return tuple(ring.shape)
 
 
-def ring_push(ring: Tensor, head: Tensor, rows: Tensor, sub: Optional[Tensor] = None) -> None:
-    """Appends rows (B, n, C), oldest first, to the ring (B, L, C) and advances its heads; ``sub`` (C) is subtracted from every row."""
+def robot_index(robots, B: int) -> Tensor:
+    """A subset of the robots of a batch as the int32 CPU tensor (S) the ``*_at`` entry points read once it is uploaded: a sequence of ints
+    or a 1-D integer CPU tensor, every index in [0, B), no index twice (two workgroups of one launch would own the same ring).  This is
+    the only validation there is - the device checks nothing but the range - and it needs no GPU."""
+    if isinstance(robots, Tensor):
+        if robots.is_cuda:
+            raise ValueError("robots: indices are validated on the host - pass a list or a CPU tensor (a device tensor would have to be read back)")
+        if robots.dim() != 1 or robots.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError(f"robots: expected a 1-D integer tensor of robot indices, got {tuple(robots.shape)} {robots.dtype}")
+        idx = [int(v) for v in robots.tolist()]
+    else:
+        try:
+            robots = idx = list(robots)
+        except TypeError:
+            raise ValueError(f"robots: expected a sequence of robot indices, got {robots!r}") from None
+        try:
+            idx = [operator.index(v) for v in idx if not isinstance(v, bool)]
+        except TypeError:
+            idx = None
+        if idx is None or len(idx) != len(robots):
+            raise ValueError(f"robots: expected a flat sequence of ints, got {robots!r}")
+    bad = [v for v in idx if not 0 <= v < B]
+    if bad:
+        raise ValueError(f"robots: index {bad[0]} is outside [0, {B})")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"robots: an index occurs twice in {idx}; one launch gives every named robot one workgroup")
+    return torch.tensor(idx, dtype=torch.int32)
+
+
+def _robots_on(robots, B: int, device) -> Tensor:
+    """``robots`` in device memory: an int32 device tensor is taken as it is (it came from ``robot_index``: PolicySession validates once per
+    call and hands the upload to several launches), anything else goes through ``robot_index`` first."""
+    if isinstance(robots, Tensor) and robots.is_cuda:
+        if robots.dtype != torch.int32 or robots.dim() != 1 or not robots.is_contiguous() or robots.device != device:
+            raise ValueError(f"robots: a device tensor must be the contiguous int32 upload of ops.robot_index on {device}")
+        return robots
+    return robot_index(robots, B).to(device)
+
+
+def ring_push(ring: Tensor, head: Tensor, rows: Tensor, sub: Optional[Tensor] = None, robots=None) -> None:
+    """Appends rows (B, n, C), oldest first, to the ring (B, L, C) and advances its heads; ``sub`` (C) is subtracted from every row.
+    ``robots`` (see ``robot_index``): rows is (S, n, C) and block s goes to robot robots[s]; no other robot's ring or head is touched."""
     B, L, Cc = _ring_req(ring, head)
     _req(rows, "rows")
-    if rows.dim() != 3 or rows.shape[0] != B or rows.shape[2] != Cc or rows.device != ring.device:
-        raise ValueError(f"rows: expected ({B}, n, {Cc}) on {ring.device}, got {tuple(rows.shape)} on {rows.device}")
+    r = None if robots is None else _robots_on(robots, B, ring.device)
+    S = B if r is None else r.numel()
+    if rows.dim() != 3 or rows.shape[0] != S or rows.shape[2] != Cc or rows.device != ring.device:
+        raise ValueError(f"rows: expected ({S}, n, {Cc}) on {ring.device}, got {tuple(rows.shape)} on {rows.device}")
     if sub is not None and (_req(sub, "sub").numel() != Cc or sub.device != ring.device):
         raise ValueError(f"sub: expected {Cc} values on {ring.device}")
-    check(_lib.load().sd_ring_push(ring.data_ptr(), head.data_ptr(), rows.data_ptr(), _ptr(sub), B, L, Cc, rows.shape[1], _stream()), "sd_ring_push")
+    if r is None:
+        check(_lib.load().sd_ring_push(ring.data_ptr(), head.data_ptr(), rows.data_ptr(), _ptr(sub), B, L, Cc, rows.shape[1], _stream()), "sd_ring_push")
+    else:
+        check(_lib.load().sd_ring_push_at(ring.data_ptr(), head.data_ptr(), rows.data_ptr(), _ptr(sub), r.data_ptr(), S, B, L, Cc, rows.shape[1],
+                                          _stream()), "sd_ring_push_at")
 
 
-def ring_window(ring: Tensor, head: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """The chronological window (B, L, C) of a ring."""
-    shape = _ring_req(ring, head)
+def ring_window(ring: Tensor, head: Tensor, out: Optional[Tensor] = None, robots=None) -> Tensor:
+    """The chronological window (B, L, C) of a ring; with ``robots`` the compact (S, L, C) windows of those robots, in their order."""
+    B, L, Cc = _ring_req(ring, head)
+    r = None if robots is None else _robots_on(robots, B, ring.device)
+    shape = (B if r is None else r.numel(), L, Cc)
     if out is None:
-        out = torch.empty_like(ring)
+        out = torch.empty(shape, dtype=torch.float32, device=ring.device)
     elif tuple(_req(out, "out").shape) != shape or out.device != ring.device:
         raise ValueError(f"out: expected {shape} on {ring.device}")
-    check(_lib.load().sd_ring_window(ring.data_ptr(), head.data_ptr(), out.data_ptr(), *shape, _stream()), "sd_ring_window")
+    if r is None:
+        check(_lib.load().sd_ring_window(ring.data_ptr(), head.data_ptr(), out.data_ptr(), *shape, _stream()), "sd_ring_window")
+    else:
+        check(_lib.load().sd_ring_window_at(ring.data_ptr(), head.data_ptr(), out.data_ptr(), r.data_ptr(), shape[0], B, L, Cc, _stream()),
+              "sd_ring_window_at")
     return out
 
 
@@ -1511,17 +1564,60 @@ class SessionWindows:
             v = self.array[i]
             v.ring, v.head, v.out, v.L, v.C, v.wrap = ring.data_ptr(), head.data_ptr(), out.data_ptr(), shape[1], shape[2], int(bool(wrap))
 
-    def launch(self) -> None:
-        check(_lib.load().sd_session_windows(self.array, len(self.array), self.B, _stream()), "sd_session_windows")
+    def launch(self, robots=None) -> None:
+        """``robots`` (S of them, see ``robot_index``): the same block and the same out buffers, of which the leading S row blocks
+        ``out[:S]`` then hold the compact windows of those robots (S <= B, so they fit; the rest of out is left as it was)."""
+        if robots is None:
+            check(_lib.load().sd_session_windows(self.array, len(self.array), self.B, _stream()), "sd_session_windows")
+            return
+        r = _robots_on(robots, self.B, self.tensors[0][0].device)
+        if r.numel() > self.B:
+            raise ValueError(f"robots: {r.numel()} robots do not fit the window buffers of a batch of {self.B}")
+        check(_lib.load().sd_session_windows_at(self.array, len(self.array), r.data_ptr(), r.numel(), self.B, _stream()), "sd_session_windows_at")
 
 
-def session_commit(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, head: Tensor) -> Tensor:
-    """The published trajectory x * std + mean - pi (B, T, J) of a sampled normalised one, also pushed into the action-history ring."""
+def session_commit(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, head: Tensor, robots=None) -> Tensor:
+    """The published trajectory x * std + mean - pi (B, T, J) of a sampled normalised one, also pushed into the action-history ring.
+    ``robots`` (see ``robot_index``): x is (S, T, J) and its rows go into the action rings of those robots only."""
     B, L, J = _ring_req(ring, head)
     _req(x, "x"); _req(mean, "mean"); _req(std, "std")
-    if x.dim() != 3 or x.shape[0] != B or x.shape[2] != J or mean.numel() != J or std.numel() != J or x.device != ring.device:
-        raise ValueError(f"x: expected ({B}, T, {J}) with {J} means and stds, got {tuple(x.shape)}")
+    r = None if robots is None else _robots_on(robots, B, ring.device)
+    S = B if r is None else r.numel()
+    if x.dim() != 3 or x.shape[0] != S or x.shape[2] != J or mean.numel() != J or std.numel() != J or x.device != ring.device:
+        raise ValueError(f"x: expected ({S}, T, {J}) with {J} means and stds, got {tuple(x.shape)}")
     out = torch.empty_like(x)
-    check(_lib.load().sd_session_commit(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(), head.data_ptr(),
-                                        B, x.shape[1], J, L, _stream()), "sd_session_commit")
+    if r is None:
+        check(_lib.load().sd_session_commit(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(), head.data_ptr(),
+                                            B, x.shape[1], J, L, _stream()), "sd_session_commit")
+    else:
+        check(_lib.load().sd_session_commit_at(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(), head.data_ptr(),
+                                               r.data_ptr(), S, B, x.shape[1], J, L, _stream()), "sd_session_commit_at")
     return out
+
+
+def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0) -> None:
+    """The start state of an episode for the robots a mask selects, in one launch (``sd_session_reset``): ``rings`` is up to five
+    (ring, head, fill) with ``fill`` a device row of C floats or None for zeros; ``mask`` (B) bool or uint8 on the device (None: every
+    robot) is read by the kernel only - nothing comes back to the host, so a simulator's ``done`` tensor can be passed as it is;
+    ``game_state`` (B) int64 receives ``game_state_value`` for the selected robots."""
+    if not 1 <= len(rings) <= 5:
+        raise ValueError("one to five rings per launch")
+    array = (_lib.RingReset * len(rings))()
+    B, dev = rings[0][0].shape[0], rings[0][0].device
+    for i, (ring, head, fill) in enumerate(rings):
+        shape = _ring_req(ring, head)
+        if shape[0] != B or ring.device != dev:
+            raise ValueError(f"ring {i}: {shape} on {ring.device} does not share the batch {B} on {dev}")
+        if fill is not None and (_req(fill, "fill").numel() != shape[2] or fill.device != dev):
+            raise ValueError(f"ring {i}: fill: expected {shape[2]} values on {dev}")
+        v = array[i]
+        v.ring, v.head, v.fill, v.L, v.C = ring.data_ptr(), head.data_ptr(), _ptr(fill), shape[1], shape[2]
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"mask: expected torch.bool or torch.uint8, got {mask.dtype}")
+        _req(mask, "mask", mask.dtype)
+        if tuple(mask.shape) != (B,) or mask.device != dev:
+            raise ValueError(f"mask: expected ({B},) on {dev}, got {tuple(mask.shape)} on {mask.device}")
+    if game_state is not None and (tuple(_req(game_state, "game_state", torch.int64).shape) != (B,) or game_state.device != dev):
+        raise ValueError(f"game_state: expected ({B},) int64 on {dev}")
+    check(_lib.load().sd_session_reset(array, len(rings), _ptr(mask), _ptr(game_state), int(game_state_value), B, _stream()), "sd_session_reset")

@@ -12,6 +12,11 @@ backbone kernels see.
     s.push_joint_state(q); s.push_rotation(r); s.push_image(frame)     # the callbacks / timers of ros.py:165-257
     traj = s.step()                                                   # (B, T, J): what ros.py:321-335 publishes
 
+Every entry point takes ``robots=`` for a subset of the batch (robots that tick at their own times, episodes that end robot by robot):
+
+    s.push_image(frame, robots=[2]); traj = s.step(robots=[0, 2])      # (2, T, J); robot 1's rings are neither read nor written
+    s.reset(robots=done)                                               # a (B,) bool mask, on the device as it is, or an index list
+
 There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
 
 from __future__ import annotations
@@ -146,9 +151,35 @@ class PolicySession:
             raise RuntimeError(f"PolicySession.{what}: the model's weights changed since the session was built; its cached image tokens "
                                "belong to the old weights - call reset()")
 
-    def reset(self) -> None:
+    def _subset(self, robots) -> tuple:
+        """(S, the indices on the host, the indices on the device) of ``ops.robot_index``: validated once per call."""
+        idx = ops.robot_index(robots, self.B)
+        return idx.numel(), idx, idx.to(self.device)
+
+    def _reset_some(self, robots) -> None:
+        if self.model.training:
+            raise RuntimeError("PolicySession.reset: the model is in train() mode - call model.eval()")
+        self._check_weights("reset")   # a part of the batch cannot adopt new weights: the other robots' tokens belong to the old ones
+        if isinstance(robots, torch.Tensor) and robots.dtype == torch.bool:
+            if tuple(robots.shape) != (self.B,) or (robots.is_cuda and robots.device != self.device):
+                raise ValueError(f"reset: a mask is ({self.B},) bool on the CPU or on {self.device}, got {tuple(robots.shape)} on {robots.device}")
+            mask = robots.to(self.device).contiguous()   # (a device mask stays where it is: nothing is read back)
+        else:
+            mask = torch.zeros(self.B, dtype=torch.bool)
+            mask[ops.robot_index(robots, self.B).long()] = True
+            mask = mask.to(self.device)
+        ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE)
+
+    def reset(self, robots=None) -> None:
         """Rings back to ``context_length`` rows of zeros (ros.py:87-106), the image ring to the token of an all-zero frame
-        (ros.py:88-92), the game state to 2, the noise generator to the seed; the current weights become the session's."""
+        (ros.py:88-92), the game state to 2, the noise generator to the seed; the current weights become the session's.
+        ``robots`` (an index list as ``ops.robot_index`` takes it, or a (B,) bool mask on the CPU or on the session's device, which is
+        used without a synchronisation): the end of those robots' episodes only.  Their rings, head words and game state go back to the
+        start state in one launch, the image-token ring to the zero-frame token of the last whole reset (the backbone does not run).
+        Nothing is allocated, a captured tick stays valid, the noise generator and the session's weights stay; weights that moved since
+        the last whole reset raise as in ``step``."""
+        if robots is not None:
+            return self._reset_some(robots)
         if self.model.training:
             raise RuntimeError("PolicySession.reset: the model is in train() mode - call model.eval()")
         dev, B = self.device, self.B
@@ -164,6 +195,7 @@ class PolicySession:
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
         self._watched, self._graph = None, None
         self._key = self._weights_key()
+        self._resettable = [(*r, None) for r in {id(r[0]): r for r in (*self._rings.values(), self._action)}.values()]
         if self._images is not None:
             d = self.model.hidden_dim
             self._tokens = new(self.S, d)
@@ -171,100 +203,126 @@ class PolicySession:
             with torch.no_grad():
                 zero = self._image_encoder(torch.zeros(1, 1, 3, self.R, self.R, dtype=torch.float32, device=dev))   # (1, 1, d)
             ops.ring_push(*self._tokens, zero.expand(B, self.S, d).contiguous())
+            self._resettable.append((*self._tokens, zero.reshape(d).clone()))   # kept: a partial reset writes this token again
 
     # ---- pushes ----------------------------------------------------------------------------
-    def _rows(self, x: torch.Tensor, tail: tuple, name: str) -> torch.Tensor:
-        """(B, *tail) or (B, n, *tail) -> a contiguous fp32 device tensor (B, n, *tail); the caller's tensor is only read."""
+    def _rows(self, x: torch.Tensor, tail: tuple, name: str, S: Optional[int] = None) -> torch.Tensor:
+        """(B, *tail) or (B, n, *tail) -> a contiguous fp32 device tensor (B, n, *tail); the caller's tensor is only read.  ``S``: the
+        leading dimension where the call names a subset of the robots."""
+        S = self.B if S is None else S
         if not isinstance(x, torch.Tensor):
             x = torch.as_tensor(x)
         if x.dim() == len(tail) + 1:
             x = x.unsqueeze(1)
-        if x.dim() != len(tail) + 2 or x.shape[0] != self.B or tuple(x.shape[2:]) != tail:
-            raise ValueError(f"{name}: expected ({self.B}, {', '.join(map(str, tail))}) or ({self.B}, n, {', '.join(map(str, tail))}), "
+        if x.dim() != len(tail) + 2 or x.shape[0] != S or tuple(x.shape[2:]) != tail:
+            raise ValueError(f"{name}: expected ({S}, {', '.join(map(str, tail))}) or ({S}, n, {', '.join(map(str, tail))}), "
                              f"got {tuple(x.shape)}")
         return x.to(device=self.device, dtype=torch.float32).contiguous()
 
-    def _push(self, key: str, x: torch.Tensor, name: str) -> None:
+    def _push(self, key: str, x: torch.Tensor, name: str, robots) -> None:
         if key not in self._rings:
             raise RuntimeError(f"PolicySession.{name}: the model has this modality switched off - there is no ring to push into")
-        ops.ring_push(*self._rings[key], self._rows(x, (self._shapes[key][1],), name))
+        if robots is None:
+            return ops.ring_push(*self._rings[key], self._rows(x, (self._shapes[key][1],), name))
+        S, _, dev_idx = self._subset(robots)
+        ops.ring_push(*self._rings[key], self._rows(x, (self._shapes[key][1],), name, S), robots=dev_idx)
 
-    def push_joint_state(self, q: torch.Tensor) -> None:
-        """Raw joint angles (B, J) or (B, n, J), oldest first, as ros.py:205-214 stores them (the wrap happens in ``step``)."""
-        self._push("joint_state", q, "push_joint_state")
+    def push_joint_state(self, q: torch.Tensor, robots=None) -> None:
+        """Raw joint angles (B, J) or (B, n, J), oldest first, as ros.py:205-214 stores them (the wrap happens in ``step``).
+        ``robots``: the leading dimension is ``len(robots)`` and only those robots' rings move."""
+        self._push("joint_state", q, "push_joint_state", robots)
 
-    def push_rotation(self, r: torch.Tensor) -> None:
-        """Orientation rows (B, 4 | 5) or (B, n, 4 | 5) (quaternion or the five-dimensional form: ros.py:216-253)."""
-        self._push("rotation", r, "push_rotation")
+    def push_rotation(self, r: torch.Tensor, robots=None) -> None:
+        """Orientation rows (B, 4 | 5) or (B, n, 4 | 5) (quaternion or the five-dimensional form: ros.py:216-253); ``robots`` as in
+        ``push_joint_state``."""
+        self._push("rotation", r, "push_rotation", robots)
 
-    def push_image(self, frames: torch.Tensor) -> None:
+    def push_image(self, frames: torch.Tensor, robots=None) -> None:
         """Frames (B, 3, R, R) or (B, n, 3, R, R), preprocessed as ros.py:191-200 and already at ``image_resolution``: encoded now by
-        the model's image encoder, on these frames only; the tokens go into the ring and no frame is kept."""
+        the model's image encoder, on these frames only; the tokens go into the ring and no frame is kept.  ``robots``: the leading
+        dimension is ``len(robots)``, the encoder sees ``len(robots) * n`` frames and only those robots' token rings move."""
         if self._images is None:
             raise RuntimeError("PolicySession.push_image: the model has images switched off - there is no ring to push into")
         self._check_weights("push_image")
         if self.model.training:
             raise RuntimeError("PolicySession.push_image: the model is in train() mode - call model.eval()")
-        x = self._rows(frames, (3, self.R, self.R), "push_image")
+        S, dev_idx = (None, None) if robots is None else self._subset(robots)[::2]
+        x = self._rows(frames, (3, self.R, self.R), "push_image", S)
+        if S == 0:
+            return
         with torch.no_grad():
             tokens = self._image_encoder(x)
-        ops.ring_push(*self._tokens, tokens.contiguous())
+        ops.ring_push(*self._tokens, tokens.contiguous(), robots=dev_idx)
 
-    def set_game_state(self, idx) -> None:
-        """Game state index per robot (an int for all of them, or B of them); ros.py:274 feeds the constant 2."""
-        if isinstance(idx, int):
+    def set_game_state(self, idx, robots=None) -> None:
+        """Game state index per robot (an int for all of them, or B of them); ros.py:274 feeds the constant 2.  ``robots``: for those
+        robots only (an int for all of them, or ``len(robots)`` of them)."""
+        if robots is not None:
+            S, _, dev_idx = self._subset(robots)
+            value = idx if isinstance(idx, int) else torch.as_tensor(idx).reshape(S).to(self.device)
+            self._game_state[dev_idx.long()] = value
+        elif isinstance(idx, int):
             self._game_state.fill_(idx)
         else:
             self._game_state.copy_(torch.as_tensor(idx).reshape(self.B))
 
     # ---- the tick --------------------------------------------------------------------------
-    def _context(self) -> list:
+    def _context(self, subset: Optional[tuple] = None) -> list:
+        """The context tokens of the batch, or of a ``_subset``: its compact windows are the leading S row blocks of the window buffers."""
         m = self.model
+        S, _, dev_idx = subset if subset is not None else (self.B, None, None)
         if self._launch is not None:
-            self._launch.launch()
-        ctx = [self._encoders[k](self._wins[k]) for k in KEYS if k in self._encoders]
+            self._launch.launch(dev_idx)
+        ctx = [self._encoders[k](self._wins[k][:S]) for k in KEYS if k in self._encoders]
         if self._images is not None:
-            ops.ring_window(*self._tokens, out=self._token_win)
-            ctx.append(self._sequence(self._token_win) if self._sequence is not None else self._token_win)
+            win = ops.ring_window(*self._tokens, out=self._token_win[:S], robots=dev_idx)
+            ctx.append(self._sequence(win) if self._sequence is not None else win)
         if m.game_state_encoder is not None:
-            ctx.append(m.game_state_encoder(self._game_state))
+            ctx.append(m.game_state_encoder(self._game_state if dev_idx is None else self._game_state[dev_idx.long()]))
         return ctx
 
-    def windows(self) -> dict:
+    def windows(self, robots=None) -> dict:
         """Copies of the contiguous windows the next ``step`` would encode, keyed as ``encode_input_data``'s input (``image_tokens``:
-        the per-frame tokens, what the image sequence encoder reads)."""
+        the per-frame tokens, what the image sequence encoder reads).  ``robots``: the compact windows (S, ...) of those robots."""
+        S, _, dev_idx = (self.B, None, None) if robots is None else self._subset(robots)
         if self._launch is not None:
-            self._launch.launch()
-        out = {k: w.clone() for k, w in self._wins.items()}
+            self._launch.launch(dev_idx)
+        out = {k: w[:S].clone() for k, w in self._wins.items()}
         if self._images is not None:
-            out["image_tokens"] = ops.ring_window(*self._tokens)
+            out["image_tokens"] = ops.ring_window(*self._tokens, robots=dev_idx)
         if self.model.game_state_encoder is not None:
-            out["game_state"] = self._game_state.clone()
+            out["game_state"] = self._game_state.clone() if dev_idx is None else self._game_state[dev_idx.long()]
         return out
 
-    def step(self, x_T: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step(self, x_T: Optional[torch.Tensor] = None, robots=None) -> torch.Tensor:
         """One tick (ros.py:259-335): the published trajectory (B, T, J) = denormalised sample - pi, also appended to the action
-        history.  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator."""
+        history.  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator.
+        ``robots``: the tick of those S robots alone - their windows, the context encoders and the rollout at batch S, the commit into
+        their action rings only; x_T and the result are (S, T, J).  A subset tick runs eagerly, on the same rings, also where
+        ``use_graph`` is set: the captured graph serves the whole batch."""
         m = self.model
         self._check_weights("step")
         if m.training:
             raise RuntimeError("PolicySession.step: the model is in train() mode - call model.eval()")
-        shape = (self.B, self.T, self.J)
+        subset = None if robots is None else self._subset(robots)
+        shape = (self.B if subset is None else subset[0], self.T, self.J)
         if x_T is None:
             x_T = torch.randn(shape, dtype=torch.float32, device=self.device, generator=self._gen)
         elif tuple(x_T.shape) != shape or not x_T.is_cuda or x_T.dtype != torch.float32:
             raise ValueError(f"x_T: expected an fp32 tensor {shape} on {self.device}, got {tuple(x_T.shape)} {x_T.dtype} on {x_T.device}")
+        if shape[0] == 0:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
         with torch.no_grad():
-            if self.use_graph:
+            if self.use_graph and subset is None:
                 if self._graph is None:   # first tick after construction / reset(): the rings are new
                     self._graph = _GraphedTick(self, x_T)
                 return ops.session_commit(self._graph(x_T), m.mean, m.std, *self._action)
-            ctx = self._context()
+            ctx = self._context(subset)
             if self.distilled:   # one forward at t = 0 (ros.py:293-298)
-                x = m.forward_with_context(ctx, x_T.contiguous(), self._t0)
+                x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:shape[0]])
             else:
                 x = m.sample(ctx, x_T, self.n_steps, max_mode=3)
-            return ops.session_commit(x.contiguous(), m.mean, m.std, *self._action)
+            return ops.session_commit(x.contiguous(), m.mean, m.std, *self._action, robots=None if subset is None else subset[2])
 
     @classmethod
     def from_checkpoint(cls, path: str, device=None, **kwargs) -> "PolicySession":

@@ -13,7 +13,15 @@ variant and the spread (the largest range of a variant's blocks).  The list tick
 ros.py's are.  The first tick of the variants is compared as well (same sensor rows, same noise), and the host time of the session's
 stale-weights check (a scan of every parameter's version counter, twice per tick with images) is timed on its own.
 Exit status 1 when a session variant is slower than the list tick beyond the spread in any case, or a first tick differs by more than 1e-4.
-usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10]"""
+
+--reset measures the end of an episode instead (B = 16 and 64): reset(robots=[one robot]), reset(robots=<device mask of half the robots>)
+and the whole reset() as the baseline, each followed by its first step(), with use_graph off and on, plus the ordinary tick without a
+reset.  One repetition is: two new frames and the other sensor rows pushed (untimed), synchronise, the reset, synchronise (= device plus
+host time of the reset), the step, synchronise.  A block is the mean of --ticks repetitions; the variants run in alternating blocks and
+every figure is the median over the blocks, with the extremes and the spread as above.  Exit status 1 when a partial reset plus its tick is
+slower than the whole reset plus its tick beyond the spread, or, with use_graph, when the tick after a partial reset is slower than an
+ordinary replayed tick beyond the spread.
+usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10] [--reset [--out profiles/session_partial_reset.jsonl]]"""
 import argparse
 import json
 import os
@@ -107,14 +115,102 @@ def block_ms(tick, news, x_T):
     return (time.perf_counter() - t0) / len(news) * 1e3
 
 
+def reset_block_ms(s, kind, news, x_T, mask):
+    """(reset ms, first step ms), each the mean over one block of repetitions."""
+    t_reset = t_step = 0.0
+    for new in news:
+        if "joint_state" in new:
+            s.push_joint_state(new["joint_state"])
+        if "rotation" in new:
+            s.push_rotation(new["rotation"])
+        s.push_image(new["image_data"])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if kind == "whole":
+            s.reset()
+        elif kind == "one":
+            s.reset(robots=[s.B // 2])
+        elif kind == "half_mask":
+            s.reset(robots=mask)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        s.step(x_T)
+        torch.cuda.synchronize()
+        t_reset, t_step = t_reset + (t1 - t0), t_step + (time.perf_counter() - t1)
+    return t_reset / len(news) * 1e3, t_step / len(news) * 1e3
+
+
+def reset_leg(args):
+    """Partial reset against whole reset, each with the tick that follows it (--reset)."""
+    blocks = 3 if args.quick else args.blocks
+    kinds = ("none", "one", "half_mask", "whole")
+    failed, lines = False, []
+    for name, over in CONFIGS.items():
+        params = {**BASE, **over}
+        torch.manual_seed(0)
+        model = cli.build_model(params).cuda().eval()
+        T, J = params["trajectory_prediction_length"], params["num_joints"]
+        for B in ((16,) if args.quick else (16, 64)):
+            g = torch.Generator().manual_seed(7)
+            sessions = {False: PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params),
+                        True: PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params, use_graph=True)}
+            x_T = torch.randn(B, T, J, device="cuda", generator=torch.Generator(device="cuda").manual_seed(8))
+            mask = (torch.arange(B, device="cuda") % 2 == 0)                 # a simulator's done flags: already on the device
+            news = [{k: v.cuda() for k, v in sensor_rows(params, B, g).items()} for _ in range(args.ticks)]
+            variants = [(graph, kind) for graph in (False, True) for kind in kinds]
+            for graph, kind in variants:                                      # warm-up: one untimed block of every variant
+                reset_block_ms(sessions[graph], kind, news, x_T, mask)
+            times = {v: [] for v in variants}
+            for _ in range(blocks):                                           # alternating blocks: drift of the box hits all of them
+                for v in variants:
+                    times[v].append(reset_block_ms(sessions[v[0]], v[1], news, x_T, mask))
+            rec = {"config": name, "B": B, "steps": N_STEPS, "new_frames_per_tick": NEW_FRAMES, "frame_size": [params["image_resolution"]] * 2,
+                   "blocks": blocks, "repetitions_per_block": args.ticks, "one_robot": B // 2, "mask_robots": int(mask.sum())}
+            ok = True
+            for graph in (False, True):
+                cols = {}
+                for kind in kinds:
+                    r, st = [t[0] for t in times[(graph, kind)]], [t[1] for t in times[(graph, kind)]]
+                    both = [a + b for a, b in zip(r, st)]
+                    cols[kind] = {"reset_ms": {"median": round(statistics.median(r), 3), "min": round(min(r), 3), "max": round(max(r), 3)},
+                                  "first_step_ms": {"median": round(statistics.median(st), 3), "min": round(min(st), 3), "max": round(max(st), 3)},
+                                  "reset_plus_step_ms": {"median": round(statistics.median(both), 3), "min": round(min(both), 3),
+                                                         "max": round(max(both), 3)}}
+                spread = max(c[f]["max"] - c[f]["min"] for c in cols.values() for f in ("reset_plus_step_ms", "first_step_ms"))
+                total = lambda kind: cols[kind]["reset_plus_step_ms"]["median"]
+                tick = lambda kind: cols[kind]["first_step_ms"]["median"]
+                not_slower = bool(total("one") <= total("whole") + spread and total("half_mask") <= total("whole") + spread)
+                cols.update(spread_ms=round(spread, 3), partial_not_slower_than_whole_beyond_spread=not_slower)
+                ok = ok and not_slower
+                if graph:
+                    replayed = bool(tick("one") <= tick("none") + spread and tick("half_mask") <= tick("none") + spread)
+                    cols["tick_after_partial_reset_costs_a_replayed_tick"] = replayed
+                    ok = ok and replayed
+                rec["use_graph" if graph else "eager"] = cols
+            failed = failed or not ok
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+            del sessions
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    if failed:
+        raise SystemExit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="B = 1 and 16 only, fewer blocks")
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--ticks", type=int, default=10, help="ticks per block")
+    ap.add_argument("--reset", action="store_true", help="measure partial and whole resets with the tick that follows them")
+    ap.add_argument("--out", type=str, default=None, help="--reset: also write the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_session.py measures on the GPU: no device found")
+    if args.reset:
+        return reset_leg(args)
     blocks = 3 if args.quick else args.blocks
     failed = False
     for name, over in CONFIGS.items():

@@ -101,33 +101,39 @@ const char *sd_last_error(void);
  * for batch B, horizon T (decoder tokens or encoder patches), memory tokens M. */
 size_t sd_workspace_floats(int B, int T, int M, int d, int L, int n_steps);
 
-/* Which kernels sd_ddim_sample runs for this shape (reporting only; results agree within fp32 rounding):
- *   0 = fp32 MFMA, per-step cross-attention projections;
- *   1 = fp32 MFMA with the cross-attention Q/out projections folded into the cached memory (heads 4, Mc + 1 <= 16, T >= 64);
- *   2 = mode 1 with every row GEMM and the self-attention as 3 fp16 MFMAs on split (hi + lo) operands, fp32
- *       accumulate (hidden_dim 256; SD_SAMPLER_GEMM=f32 in the environment selects mode 1 instead);
- *   3 = ONE launch per step: a workgroup owns a trajectory (embedding, every layer with its self-attention, fc_out, DDIM
- *       update; q | k | v and the residual stream never leave the CU; soccerdiffusion_amd/csrc/sd_traj.h).  Mode 2's
- *       arithmetic: three fp16 MFMAs per product on hi + lo operands at EVERY site.  hidden_dim 256, 4 heads, T <= 100 (one
- *       instantiation per ceil(T / 16) token tiles), Mc + 1 <= 64 memory rows (up to 16: one key tile in the folded
- *       cross-attention; 17 .. 64: the wide instantiation with 2 .. 4 key tiles - the reference's full-context configs, e.g.
- *       sim_scratch.yaml's 51 rows), any J <= 32 (the embedding's K and fc_out's N are zero-padded in the packed planes; the
- *       reference's database has 22 joints, soccer_diffusion/dataset/models.py:222-247); the layer count (<= 8) is checked at the
- *       call - a deeper model runs mode 2; SD_SAMPLER_TRAJ=0 in the environment selects mode 2.
- *       Every OTHER hidden_dim 128 / 256 / 512 shape - the reference's default.yaml (hidden_dim 128, 312 memory rows) and
- *       larger_model.yaml (hidden_dim 512, 8 layers, 312 memory rows), hidden_dim 256 with more than 64 memory rows - runs the GENERIC
- *       trajectory kernels (soccerdiffusion_amd/csrc/sd_trajg.hip): same ownership and arithmetic, geometry as a template parameter,
- *       the cross-attention un-folded with the memory's projected K / V streamed from HBM (any number of rows), T <= 100 (hidden_dim
- *       512: T <= 48 - a longer panel does not fit the CU's LDS; such a shape runs mode 2's unfused chains), 4 heads, J <= 32, <= 8 layers.
- *   4 = mode 3 with ONE exception: the Q | K | V projection of the self-attention reads a single fp16 plane of LayerNorm
- *       1's output (two MFMAs per product there, 11-bit activation operand), which frees the LDS that lets the four images
- *       of a head live side by side (two barriers per head instead of five; ~ 1.15 x mode 3).  The error this leaves in a
- *       logit grows with the logit: measured noise-prediction error against fp64 ~ 1e-5 x max |logit| (1.6e-5 on freshly
- *       initialised weights, 1e-4 at |logit| ~ 9, 1e-3 at 25; mode 3: 1e-6 throughout - tools/exp/eps_stress.py,
- *       profiles/r04_eps_stress.txt), so the kernel reports SD_STATUS_SHARP_LOGITS (below) when a logit leaves
- *       SD_SHARP_LOGIT_LIMIT and the caller repeats the rollout on mode 3.  Up to 16 memory rows; with more, max_mode = 4
- *       runs mode 3's wide instantiation.
- * Returns the mode an automatic call (max_mode = -1) runs: 3 where the trajectory kernel applies - mode 4 is opt-in. */
+/* Which kernels a sampler call (sd_ddim_sample*, sd_sampler_prepare / sd_sampler_eps) runs: one route per call, chosen from the shape, the
+ * cap and four A/B switches of the environment (soccerdiffusion_amd/csrc/sd_sampler_plan.h).  Results agree within fp32 rounding.
+ *   route              mode  what runs
+ *   CHAINS_F32          0    unfused row chains on the fp32 MFMA
+ *   CHAINS_F16          0    unfused row chains on split fp16 (chain_f16_kernel)
+ *   FUSED               0    fused decoder-layer kernel, the memory's K / V placed per step
+ *   FUSED_FOLD          1    the same with the cross-attention's Q / out projections folded into the cached memory
+ *   FUSED_FOLD_F16      2    decoder_layer_f16_kernel: mode 1 with every row GEMM and the self-attention as three fp16 MFMAs on hi + lo operands
+ *   TRAJ_TUNED          3    traj_step_kernel<.., true>: ONE launch per step, a workgroup owns a trajectory; three fp16 products at every site
+ *   TRAJ_TUNED_2P       4    traj_step_kernel<.., false>: two products at the Q | K | V site (~ 1.15 x; opt-in, see SD_STATUS_SHARP_LOGITS)
+ *   TRAJ_TUNED_WIDE     3    traj_step_wide_kernel: 2 .. 4 key tiles in the folded cross-attention
+ *   TRAJ_GENERIC        3    traj_step_generic_kernel<D, ..>: the memory's projected K / V streamed from HBM
+ * When each applies (Mk = Mc + 1 memory rows; the first that holds, from the bottom of the table upwards):
+ *   TRAJ_*: cap >= 3, 4 heads, J <= 32, L <= 8; off with SD_SAMPLER_TRAJ=0 or SD_SAMPLER_GEMM=f32.
+ *   TRAJ_TUNED / _2P / _WIDE: hidden_dim 256, T <= 100, Mk <= 64 (SD_TRAJ_MAXROWS lowers that), B * Mk * 2 d < 2^30 floats of K / V.
+ *     Mk <= 16: TRAJ_TUNED at cap 3, TRAJ_TUNED_2P at cap 4; Mk >= 17: TRAJ_TUNED_WIDE at either cap.
+ *   TRAJ_GENERIC: every other hidden_dim 128 / 256 (T <= 100) / 512 (T <= 48: a longer panel does not fit the CU's LDS) shape; off with SD_SAMPLER_TRAJG=0.
+ *   FUSED*: 4 heads, hidden_dim >= 128, (ceil(63 / T) + 1) * Mk <= 64 memory keys per 64-row panel, B * Mk * 2 d < 2^30.
+ *   FUSED_FOLD: cap >= 1, Mk <= 16, T >= 64.  FUSED_FOLD_F16: cap >= 2, hidden_dim 256, J % 4 == 0; off with SD_SAMPLER_GEMM=f32.
+ *   CHAINS_F16: cap >= 2, hidden_dim 128 / 256 / 512, J % 4 == 0, a memory the fused kernel does not take; off with SD_SAMPLER_GEMM=f32.
+ *   CHAINS_F32: everything else.
+ * sd_sampler_route: reporting only; max_mode as sd_ddim_sample_ex (-1 = 3), SD_E_BADARG outside -1 .. 4.
+ * sd_sampler_mode: the mode of sd_sampler_route(d, heads, T, Mc, J, 1, 1, 3) - it sees neither the layer count nor the batch. */
+#define SD_ROUTE_CHAINS_F32 0
+#define SD_ROUTE_CHAINS_F16 1
+#define SD_ROUTE_FUSED 2
+#define SD_ROUTE_FUSED_FOLD 3
+#define SD_ROUTE_FUSED_FOLD_F16 4
+#define SD_ROUTE_TRAJ_TUNED 5
+#define SD_ROUTE_TRAJ_TUNED_2P 6
+#define SD_ROUTE_TRAJ_TUNED_WIDE 7
+#define SD_ROUTE_TRAJ_GENERIC 8
+int sd_sampler_route(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode);
 int sd_sampler_mode(int d, int heads, int T, int Mc, int J);
 
 /* StepToken.forward — soccer_diffusion/ml/model/misc.py:25-35.
@@ -227,7 +233,7 @@ int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const flo
  *     three products everywhere, no status needed; 4: the guarded two-product Q | K | V site).
  * Both calls must see the same (w, workspace, B, T, Mc, n_tok, max_mode); workspace = sd_workspace_floats(B, T, max(Mc, 1), d, L,
  * n_tok) floats, owned by the caller and left alone between the calls.  Return SD_E_UNSUPPORTED (nothing launched) where the shape
- * does not take the trajectory kernels (sd_sampler_mode < 3): the caller then uses sd_denoiser_forward. */
+ * does not take the trajectory kernels (sd_sampler_route names no TRAJ route): the caller then uses sd_denoiser_forward. */
 #define SD_PREPARE_WEIGHTS 1
 #define SD_PREPARE_CONTEXT 2
 int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,

@@ -123,6 +123,7 @@ SIGNATURES = {
     "sd_last_error": (C.c_char_p, []),
     "sd_workspace_floats": (C.c_size_t, [C.c_int] * 6),
     "sd_sampler_mode": (C.c_int, [C.c_int] * 5),
+    "sd_sampler_route": (C.c_int, [C.c_int] * 8),
     "sd_step_token": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "sd_denoiser_forward": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_encoder_forward": (C.c_int, [C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -229,6 +230,17 @@ SIGNATURES = {
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }
+
+# SD_ROUTE_*: index = the number sd_sampler_route returns; the trajectory routes from TRAJ_TUNED on
+ROUTES = ("CHAINS_F32", "CHAINS_F16", "FUSED", "FUSED_FOLD", "FUSED_FOLD_F16", "TRAJ_TUNED", "TRAJ_TUNED_2P", "TRAJ_TUNED_WIDE", "TRAJ_GENERIC")
+
+
+def sampler_route(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: int, max_mode: int = -1) -> str:
+    """The name of the route a sampler call of this shape and cap runs (sd_sampler_route; reporting only)."""
+    rc = load().sd_sampler_route(d, heads, T, Mc, J, L, B, max_mode)
+    check(min(rc, 0), "sd_sampler_route")
+    return ROUTES[rc]
+
 
 KERNEL_CLASSES = ("panel_gemm_kernel", "attention_kernel", "patch_embed_kernel", "fc_out_kernel", "decoder_layer_kernel", "decoder_head_kernel",
                   "traj_step_kernel")

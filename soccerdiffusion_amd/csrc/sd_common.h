@@ -299,9 +299,6 @@ static inline unsigned grid_for(long n, int block = 256) {
 int linear(const float *A, const float *W, const float *bias, const float *ln_w, const float *ln_b, const float *res,
            float *out, int R, int N, int d, int act, hipStream_t s, int lda = 0);
 
-// the sampler's fp16 kernels are on (SD_SAMPLER_GEMM=f32 in the environment keeps the fp32-MFMA kernels: A/B runs); sd_kernels.hip
-bool f16_env_ok();
-
 // split weights of layer l inside the sampler's wf region (mode 2 and the tuned trajectory kernels, each in its own fragment order):
 // [Wo | W1 | W2 | in_proj (3 passes)], 12 d^2 halfs
 static inline f16 *f16_wf(f16 *wf, int l, int d, int which) {   // which: 0 Wo, 1 W1, 2 W2, 3 in_proj

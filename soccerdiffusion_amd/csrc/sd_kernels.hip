@@ -1293,6 +1293,7 @@ static int chain_b(const ChainBArgs &g, int d, hipStream_t s) {
 }
 
 #include "sd_f16x3.h"
+#include "sd_sampler_plan.h"
 #include "sd_traj_host.h"
 #include "sd_trajg.h"
 
@@ -1555,14 +1556,6 @@ static int decoder_head_f16(const F16HeadArgs &fa, hipStream_t s, int d = 256) {
 static int decoder_head(const DecoderHeadArgs &g, int d, hipStream_t s) {
     return launch_chain(g, d, decoder_head_kernel<64>, decoder_head_kernel<128>, decoder_head_kernel<256>,
                         decoder_head_kernel<512>, "decoder_head_kernel", s, SD_KCLASS_HEAD);
-}
-
-// true when the fused decoder-layer kernel applies: 4 heads == 4 waves each owning one head's
-// columns (D >= 128), and at most 64 memory keys among the trajectories touching a 64-row panel
-static bool fused_layer_ok(int d, int heads, int T, int Mk) {
-    if (heads != 4 || d < 128) return false;
-    const int n_traj = (63 + T - 1) / T + 1;
-    return (long)n_traj * Mk <= 64;
 }
 
 static int decoder_layer(const DecoderLayerArgs &g, int d, hipStream_t s) {
@@ -2540,17 +2533,6 @@ struct Scratch {  // carve-up of the caller's workspace (floats)
     float *gws;   // region of the generic trajectory kernels (sd_trajg.hip: hidden_dim 128 / 256 / 512, any memory length), or NULL
 };
 
-// the fp16x3 kernels are instantiated for hidden_dim 256 (the folded fp32 kernels serve the other sizes);
-// SD_SAMPLER_GEMM=f32 keeps the fp32-MFMA kernels (A/B runs)
-bool f16_env_ok() {
-    static const char *env = getenv("SD_SAMPLER_GEMM");
-    return !(env && strcmp(env, "f32") == 0);
-}
-static bool f16_ok(int d, int J) { return f16_env_ok() && d == 256 && J % 4 == 0; }
-
-// folded cross-attention applies: fused layer kernel, <= 16 key slots per head, <= 2 trajectories per panel
-static bool fold_ok(int d, int heads, int T, int Mk) { return heads == 4 && d >= 128 && Mk <= 16 && T >= 64; }
-
 static size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 // The one description of the workspace: walks the regions and assigns them from `ws`; *end (if given) receives the floats they take.
@@ -2650,22 +2632,15 @@ static int f16_prepare_chain(const sd_denoiser_weights *w, const Scratch &s, hip
     return w->d == 128 ? f16_prepare_chain_d<128>(w, s, st) : w->d == 256 ? f16_prepare_chain_d<256>(w, s, st) : f16_prepare_chain_d<512>(w, s, st);
 }
 
-// the unfused row chains run on the fp16 pipe when their split weights were prepared (sampler, hidden_dim 128 / 256 / 512;
-// SD_SAMPLER_GEMM=f32 keeps the fp32 kernels)
-static bool chain16_ok(int d, int J) {
-    return f16_env_ok() && (d == 128 || d == 256 || d == 512) && J % 4 == 0;
-}
-
+// plan: its fused and chain16 flags pick the layer kernels (sd_sampler_plan.h)
 template <typename KV>
-static int decoder_stack(const sd_denoiser_weights *w, const float *x, const Scratch &s, int B, int T, int Mk, KV kv,
-                         const TailArgs &tail, hipStream_t st, const FoldArgs &fold = FoldArgs{nullptr, nullptr, 0, 0},
-                         bool chain16 = false) {
+static int decoder_stack(const sd_denoiser_weights *w, const float *x, const Scratch &s, const SamplerPlan &plan, int B, int T, int Mk, KV kv,
+                         const TailArgs &tail, hipStream_t st, const FoldArgs &fold = FoldArgs{nullptr, nullptr, 0, 0}) {
     const int d = w->d, heads = w->heads;
     const long R = (long)B * T;
     const sd_layer_weights &l0 = w->layers[0];
     int rc;
-    const bool fused = fused_layer_ok(d, heads, T, Mk) && (long)B * Mk * 2 * d < (1L << 30);
-    chain16 = chain16 && !fused && s.wfc != nullptr;
+    const bool fused = plan.fused, chain16 = plan.chain16;
     if (chain16) {
         F16HeadArgs fh{DecoderHeadArgs{x, w->emb_w, w->emb_b, w->pe, l0.n1_w, l0.n1_b, l0.sa_in_w, l0.sa_in_b, s.h, s.qkv, R, T, w->J},
                        f16_wfc(s, 0, d, 5), s.scc + 2, 0, 0};   // the head reads sc[3]: the scale of layer 0's in_proj = scc[5]
@@ -2909,7 +2884,9 @@ extern "C" int sd_denoiser_forward(const sd_denoiser_weights *w, const float *x,
     }
     const float *kvbase = s.kv;
     const size_t kvstride = (size_t)B * M * 2 * d;
-    return decoder_stack(w, x, s, B, T, M, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_out, nullptr, nullptr}, st);
+    // one forward on the row panels, the memory's K / V projected above: no cap, hence no fold and no split-fp16 chains
+    return decoder_stack(w, x, s, panel_plan(d, w->heads, T, M, w->J, B, 0), B, T, M, [=](int l) { return kvbase + l * kvstride; },
+                         TailArgs{eps_out, nullptr, nullptr}, st);
 }
 
 extern "C" int sd_encoder_forward(const sd_encoder_weights *w, const float *x, float *out, float *workspace, int B,
@@ -2932,12 +2909,11 @@ extern "C" int sd_encoder_forward(const sd_encoder_weights *w, const float *x, f
     return 0;
 }
 
-extern "C" int sd_sampler_mode(int d, int heads, int T, int Mc, int J) {
-    const int Mk = Mc + 1;
-    if (traj_ok(d, heads, T, Mk, J, 1) || trajg_ok(d, heads, T, Mk, J, 1)) return 3;   // (the layer count is checked at the call: <= 8; mode 4 is opt-in)
-    if (!(fold_ok(d, heads, T, Mk) && fused_layer_ok(d, heads, T, Mk))) return 0;
-    if (!f16_ok(d, J)) return 1;
-    return 2;
+extern "C" int sd_sampler_mode(int d, int heads, int T, int Mc, int J) { return sampler_plan(d, heads, T, Mc, J, 1, 1, 3).mode(); }
+
+extern "C" int sd_sampler_route(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode) {
+    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, "sd_sampler_route: max_mode must be -1, 0, 1, 2, 3 or 4");
+    return sampler_plan(d, heads, T, Mc, J, L, B, max_mode < 0 ? 3 : max_mode).route;
 }
 
 extern "C" int sd_ddim_sample(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
@@ -2954,44 +2930,36 @@ extern "C" int sd_ddim_sample_ex(const sd_denoiser_weights *w, const float *ctx,
 
 // ---- the trajectory kernels (sampler modes 3 / 4): two families behind the same four stages ---------------------------------
 // tuned: sd_traj.hip (hidden_dim 256, <= 64 memory rows; its operands live in mode 2's workspace regions), generic: sd_trajg.hip (every
-// other hidden_dim 128 / 256 / 512 shape, whatever its memory length; its own region s.gws)
-enum TrajFamily { TRAJ_NONE, TRAJ_TUNED, TRAJ_GENERIC };
-static TrajFamily traj_family(const sd_denoiser_weights *w, const Scratch &s, int B, int T, int Mc, int max_mode) {
-    const int d = w->d, Mk = Mc + 1;
-    if (max_mode < 3) return TRAJ_NONE;
-    // the tuned kernel takes any horizon <= 100: it needs the folded blocks, not the row-panel kernels' T >= 64
-    if ((long)B * Mk * 2 * d < (1L << 30) && traj_ok(d, w->heads, T, Mk, w->J, w->L) && s.wf != nullptr && s.wio != nullptr) return TRAJ_TUNED;
-    if (trajg_ok(d, w->heads, T, Mk, w->J, w->L) && s.gws != nullptr) return TRAJ_GENERIC;
-    return TRAJ_NONE;
-}
+// other hidden_dim 128 / 256 / 512 shape, whatever its memory length; its own region s.gws).  The plan's route says which (sd_sampler_plan.h).
 
 // One sampler call on the trajectory kernels.  The three preparation stages are independent (sd_ddim_sample_eps runs all three per call;
 // sd_sampler_prepare / sd_sampler_eps let a caller that evaluates the denoiser step by step - the reference's own loop,
 // soccer_diffusion/ml/inference/plot.py:122-131 - keep the first two across calls).
 struct TrajCall {
-    TrajFamily fam;
+    SamplerPlan plan;
     const sd_denoiser_weights *w;
     const Scratch &s;
     int B, T, Mc, n_tok;
     hipStream_t st;
+    bool generic() const { return plan.route == SD_ROUTE_TRAJ_GENERIC; }
     TrajWs ws() const { return TrajWs{s.kvtmp, s.kvstep, s.gv, s.cb, s.gvstep, s.cstep, s.wf, s.g16, s.v16, s.gstep16, s.vstep16, s.wio, s.scales, s.maxbits, s.stepmap}; }
     int prepare_weights() const {
-        return fam == TRAJ_GENERIC ? trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st) : traj_prepare_weights(w, ws(), st);
+        return generic() ? trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st) : traj_prepare_weights(w, ws(), st);
     }
     int prepare_ctx(const float *ctx) const {
-        return fam == TRAJ_GENERIC ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st) : traj_prepare_ctx(w, ws(), ctx, B, Mc, st);
+        return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st) : traj_prepare_ctx(w, ws(), ctx, B, Mc, plan.key_tiles, st);
     }
     // per_traj: one token per trajectory (only the distinct ones are prepared: step_map_kernel), else one per DDIM step
     int prepare_steps(const float *tokens, bool per_traj) const {
-        if (fam != TRAJ_GENERIC) return traj_prepare_steps(w, ws(), tokens, n_tok, Mc, st, per_traj);
+        if (!generic()) return traj_prepare_steps(w, ws(), tokens, n_tok, Mc, st, per_traj);
         if (per_traj)
             if (int rc = step_map(tokens, n_tok, w->d, s.stepmap, st)) return rc;
         return trajg_prepare_steps(w, s.gws, tokens, s.kvstep, B, Mc, n_tok, st, per_traj ? s.stepmap : nullptr);
     }
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
-    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int max_mode, int32_t *status) const {
-        if (fam == TRAJ_GENERIC) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr);
-        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, max_mode == 3, max_mode == 3 ? nullptr : status);
+    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status) const {
+        if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr);
+        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status);
     }
 };
 
@@ -3008,7 +2976,7 @@ static int finite_check(const float *x, long n, int32_t *status, hipStream_t st)
 
 // the rollout on the trajectory kernels: one launch per DDIM step
 static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
-                        int32_t *status, int max_mode) {
+                        int32_t *status) {
     const long n = (long)c.B * c.T * c.w->J;
     int rc;
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
@@ -3018,34 +2986,31 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, max_mode, status))) return rc;
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
 }
 
 // the rollout on the row-panel kernels (sampler modes 0 - 2)
-static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const float *ctx, const float *step_tokens, const float *coef, float *x,
-                         float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, hipStream_t st) {
+static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const SamplerPlan &plan, const float *ctx, const float *step_tokens,
+                         const float *coef, float *x, float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, hipStream_t st) {
     const int d = w->d, R = B * T, L = w->L;
     int rc;
     // once per rollout: K/V of the context rows (placed as rows 0..Mc-1 of each trajectory's
     // [Mk][2d] block, Mk = Mc + 1) and of all n_steps step tokens, per layer
     const int Mk = Mc + 1;
     const size_t kvstride = (size_t)B * Mk * 2 * d, kvsstride = (size_t)n_steps * 2 * d;
-    const bool small = (long)B * Mk * 2 * d < (1L << 30);
-    const bool fold = max_mode >= 1 && fold_ok(d, w->heads, T, Mk) && fused_layer_ok(d, w->heads, T, Mk) && small;
+    const bool fold = plan.fold, f16 = plan.f16, chain16 = plan.chain16;
     const size_t gvstride = (size_t)B * 64 * 2 * d, cbstride = (size_t)B * 64;   // (the row-panel fold: Mk <= 16, one key tile)
     const size_t gvsstride = (size_t)n_steps * 4 * 2 * d, cssstride = (size_t)n_steps * 4;
-    const bool f16 = max_mode >= 2 && fold && f16_ok(d, w->J) && s.wf != nullptr;
-    const bool chain16 = max_mode >= 2 && !fold && chain16_ok(d, w->J) && s.wfc != nullptr && !fused_layer_ok(d, w->heads, T, Mk);
     if (status) {
         if (int rz = zero_async(status, sizeof(int32_t), st)) return rz;
     }
     for (int l = 0; l < L; ++l) {
         const sd_layer_weights &lw = w->layers[l];
         const float *wkv = lw.ca_in_w + (size_t)d * d, *bkv = lw.ca_in_b + d;
-        auto lin = max_mode >= 2 ? linear : linear32;
+        auto lin = plan.kv_fp32 ? linear32 : linear;
         if (Mc > 0) {
             rc = lin(ctx, wkv, bkv, nullptr, nullptr, nullptr, s.kvtmp + (size_t)l * B * Mc * 2 * d, B * Mc, 2 * d, d, 0, st, 0);
             if (rc) return rc;
@@ -3090,7 +3055,7 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const f
                       s.cstep + (size_t)i * 4, (long)gvsstride, (long)cssstride, s.gv, s.cb, (long)gvstride, (long)cbstride, B, Mc,
                       2 * d);
             SD_CHECK_LAUNCH("fold_place_kernel");
-            rc = decoder_stack(w, x, s, B, T, Mk, [=](int) { return (const float *)nullptr; }, TailArgs{eps_i, x, coef + 4 * i}, st,
+            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int) { return (const float *)nullptr; }, TailArgs{eps_i, x, coef + 4 * i}, st,
                                FoldArgs{s.gv, s.cb, gvstride, cbstride});
             if (rc) return rc;
         } else {
@@ -3098,8 +3063,7 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const f
                       s.kv, (long)kvstride, B, Mc, Mk, 2 * d, 1);
             SD_CHECK_LAUNCH("kv_place_kernel");
             const float *kvbase = s.kv;
-            rc = decoder_stack(w, x, s, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x, coef + 4 * i}, st,
-                               FoldArgs{nullptr, nullptr, 0, 0}, chain16);
+            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x, coef + 4 * i}, st);
             if (rc) return rc;
         }
         if (trace && (rc = trace_copy(x, trace, i, n, st))) return rc;
@@ -3122,34 +3086,33 @@ extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx
     if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
-    const TrajFamily fam = traj_family(w, s, B, T, Mc, max_mode);
-    if (fam != TRAJ_NONE) return traj_rollout(TrajCall{fam, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status, max_mode);
-    return panel_rollout(w, s, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, max_mode, st);
+    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode);
+    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status);
+    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st);
 }
 
 // ---- the denoiser evaluated step by step on the trajectory kernels (the reference's own loop form) --------------------------
-static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int *max_mode, const char *who,
-                             Scratch *s, TrajFamily *fam) {
+static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int max_mode, const char *who,
+                             Scratch *s, SamplerPlan *plan) {
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!workspace || B <= 0 || T <= 0 || Mc < 0 || (n_tok != 1 && n_tok != B)) return fail(SD_E_BADARG, who);
-    if (*max_mode < -1 || *max_mode > 4) return fail(SD_E_BADARG, who);
+    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, who);
     if (T > w->T_max) return fail(SD_E_TOOBIG, who);
-    if (*max_mode < 0) *max_mode = 3;
     *s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_tok, B);
-    *fam = traj_family(w, *s, B, T, Mc, *max_mode);
-    return *fam == TRAJ_NONE ? SD_E_UNSUPPORTED : 0;
+    *plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode < 0 ? 3 : max_mode);
+    return plan->traj() ? 0 : SD_E_UNSUPPORTED;
 }
 
 extern "C" int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
                                   int what, int max_mode, void *stream) {
     Scratch s;
-    TrajFamily fam;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, &max_mode, "sd_sampler_prepare: bad argument", &s, &fam);
+    SamplerPlan plan;
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_prepare: bad argument", &s, &plan);
     if (rc) return rc;
     if ((what & ~(SD_PREPARE_WEIGHTS | SD_PREPARE_CONTEXT)) || (Mc > 0 && (what & SD_PREPARE_CONTEXT) && !ctx))
         return fail(SD_E_BADARG, "sd_sampler_prepare: bad argument");
-    const TrajCall c{fam, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
     if ((what & SD_PREPARE_WEIGHTS) && (rc = c.prepare_weights())) return rc;
     if ((what & SD_PREPARE_CONTEXT) && (rc = c.prepare_ctx(ctx))) return rc;
     return 0;
@@ -3158,16 +3121,17 @@ extern "C" int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx
 extern "C" int sd_sampler_eps(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
                               int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, void *stream) {
     Scratch s;
-    TrajFamily fam;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, &max_mode, "sd_sampler_eps: bad argument", &s, &fam);
+    SamplerPlan plan;
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_eps: bad argument", &s, &plan);
     if (rc) return rc;
     if (!step_tokens || !x || !eps) return fail(SD_E_BADARG, "sd_sampler_eps: null pointer");
-    if (max_mode == 4 && fam == TRAJ_TUNED && !status) return fail(SD_E_BADARG, "sd_sampler_eps: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
-    const TrajCall c{fam, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    // (the tuned family at max_mode 4 needs the word whichever instantiation runs: the wide one included)
+    if (max_mode == 4 && plan.route != SD_ROUTE_TRAJ_GENERIC && !status) return fail(SD_E_BADARG, "sd_sampler_eps: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
+    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
     if ((rc = c.prepare_steps(step_tokens, n_tok > 1))) return rc;
     // x is only read (no DDIM coefficients: no update)
-    return c.step(const_cast<float *>(x), eps, 0, nullptr, n_tok > 1, max_mode, status);
+    return c.step(const_cast<float *>(x), eps, 0, nullptr, n_tok > 1, status);
 }
 
 // ======================================================================================

@@ -7,8 +7,6 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "../../include/soccerdiffusion_hip.h"
 
@@ -19,19 +17,14 @@
 // ---- sampler mode 3: the trajectory-owning step kernel (sd_traj.h) ---------------------------------------
 // One launch per DDIM step: embedding, all layers (self-attention inside), fc_out and the DDIM update for one trajectory per
 // workgroup.  Same folded cross-attention blocks (gv, cb) and abs-max words as mode 2; the split planes are written in the
-// 16x16x32 fragment order of sd_traj.h into the same workspace regions.  SD_SAMPLER_TRAJ=0 in the environment keeps mode 2.
+// 16x16x32 fragment order of sd_traj.h into the same workspace regions.
+// The shapes instantiated below (the environment's switches are the plan's business: sd_sampler_plan.h).  Any joint count up to 32: the
+// embedding's K and fc_out's N are zero-padded to 32 in the packed planes; the reference's database has 22 joints
+// (soccer_diffusion/dataset/models.py:222-247).  Key tiles of 16 memory slots in the folded blocks: 1 for the trajectory kernels proper,
+// 2 .. 4 for traj_step_wide_kernel (17 .. 64 rows).
 bool traj_ok(int d, int heads, int T, int Mk, int J, int L) {
-    static const char *env = getenv("SD_SAMPLER_TRAJ");
-    if (env && strcmp(env, "0") == 0) return false;
-    // any joint count up to 32 (the embedding's K and fc_out's N are zero-padded to 32 in the packed planes; the reference's database
-    // has 22 joints: soccer_diffusion/dataset/models.py:222-247)
-    static const char *mr = getenv("SD_TRAJ_MAXROWS");   // A/B runs: memory rows beyond this go to the generic kernels (sd_trajg.hip) instead of the wide instantiation
-    const int max_rows = mr ? atoi(mr) : 64;
-    return f16_env_ok() && d == 256 && heads == 4 && T >= 1 && T <= tj::TMAX && Mk >= 1 && Mk <= (max_rows < 64 ? max_rows : 64) && J >= 1 && J <= 32 && L >= 1 &&
-           L <= tj::MAX_L;
+    return d == 256 && heads == 4 && T >= 1 && T <= tj::TMAX && Mk >= 1 && Mk <= 64 && J >= 1 && J <= 32 && L >= 1 && L <= tj::MAX_L;
 }
-// key tiles of 16 memory slots in the folded blocks: 1 for the trajectory kernels proper, 2 .. 4 for traj_step_wide_kernel (17 .. 64 rows)
-static int key_tiles(int Mk) { return Mk <= 16 ? 1 : (Mk + 15) / 16; }
 
 // the instantiation for ceil(T / 16) token tiles; precise = three fp16 products at the Q | K | V site too (sampler mode 3), else two (mode 4)
 typedef void (*TrajStepFn)(tj::StepArgs);
@@ -112,8 +105,8 @@ int traj_prepare_weights(const sd_denoiser_weights *w, const TrajWs &s, hipStrea
     return 0;
 }
 
-int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, hipStream_t st) {
-    const int d = w->d, L = w->L, nkt = key_tiles(Mc + 1);
+int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, int nkt, hipStream_t st) {
+    const int d = w->d, L = w->L;
     const size_t gvstride = (size_t)B * nkt * 64 * 2 * d, cbstride = (size_t)B * nkt * 64;
     int rc = zero_async(s.gv, L * gvstride * sizeof(float), st);   // unused key slots must be finite
     if (!rc) rc = zero_async(s.cb, L * cbstride * sizeof(float), st);
@@ -298,8 +291,8 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
 // one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
 // coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-              bool per_traj, hipStream_t st, bool precise, int32_t *status) {
-    const int d = w->d, L = w->L, nkt = key_tiles(Mc + 1);
+              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status) {
+    const int d = w->d, L = w->L;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
     tj::StepArgs a{};
     a.nkt = nkt;

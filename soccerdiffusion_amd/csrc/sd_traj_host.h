@@ -3,6 +3,7 @@
 #ifndef SD_TRAJ_HOST_H
 #define SD_TRAJ_HOST_H
 #include "sd_common.h"
+#include "sd_sampler_plan.h"   // traj_ok: the shapes the tuned kernels are instantiated for
 struct sd_denoiser_weights;
 
 // The tuned path has no workspace region of its own: it writes its operands into the regions the driver carves for sampler mode 2
@@ -16,15 +17,13 @@ struct TrajWs {
     int *stepmap;
 };
 
-// shapes the tuned kernels take: hidden_dim 256, 4 heads, horizon <= 100, 1 .. 64 memory rows (SD_TRAJ_MAXROWS lowers that), <= 32
-// joints, <= 8 layers.  SD_SAMPLER_TRAJ=0 / SD_SAMPLER_GEMM=f32 in the environment switch them off.
-bool traj_ok(int d, int heads, int T, int Mk, int J, int L);
 // the three preparation stages (weights; context rows; n_tok step tokens - per_traj: one per trajectory, the distinct ones only)
 int traj_prepare_weights(const sd_denoiser_weights *w, const TrajWs &s, hipStream_t st);
-int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, hipStream_t st);
+// nkt: the plan's key tiles (SamplerPlan::key_tiles), the same for traj_prepare_ctx and traj_step of one workspace
+int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, int nkt, hipStream_t st);
 int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const float *tokens, int n_tok, int Mc, hipStream_t st, bool per_traj = false);
 // one denoiser step (+ DDIM update when coef != NULL); step index i of the n_tok prepared step blocks, or block b for trajectory b (per_traj).
 // precise: three fp16 products at the Q | K | V site (sampler mode 3), else two (mode 4, which reports sharp logits through status)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-              bool per_traj, hipStream_t st, bool precise, int32_t *status);
+              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status);
 #endif

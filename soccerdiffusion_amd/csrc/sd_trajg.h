@@ -4,11 +4,9 @@
 #define SD_TRAJG_H
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "sd_sampler_plan.h"   // trajg_ok: the shapes the generic kernels are instantiated for
 struct sd_denoiser_weights;
 
-// shapes the generic kernels take: hidden_dim 128 / 256 (horizon <= 100) or 512 (horizon <= 48), 4 heads, <= 8 layers, <= 32 joints, any
-// number of memory rows.  SD_SAMPLER_TRAJ=0 / SD_SAMPLER_GEMM=f32 in the environment switch them off with the other trajectory kernels.
-bool trajg_ok(int d, int heads, int T, int Mk, int J, int L);
 // floats of workspace behind the driver's own carve-up: split weight planes, the memory's K / V^T planes, step rows, scales
 size_t trajg_workspace_floats(int B, int Mc, int d, int L, int n_tok);
 // the three preparation stages of the trajectory path (as traj_prepare_* of the tuned family: sd_traj_host.h); kvtmp / kvstep: fp32 scratch of

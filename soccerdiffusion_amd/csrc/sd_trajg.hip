@@ -21,8 +21,6 @@
 #include "sd_trajg.h"
 #include "../../include/soccerdiffusion_hip.h"
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace tg {
@@ -1060,9 +1058,8 @@ StepFn step_fn(int ntt) {
 
 }   // namespace
 
+// the shapes step_fn is instantiated for (the environment's switches are the plan's business: sd_sampler_plan.h)
 bool trajg_ok(int d, int heads, int T, int Mk, int J, int L) {
-    static const char *e1 = getenv("SD_SAMPLER_TRAJ"), *e2 = getenv("SD_SAMPLER_GEMM"), *e3 = getenv("SD_SAMPLER_TRAJG");
-    if ((e1 && strcmp(e1, "0") == 0) || (e2 && strcmp(e2, "f32") == 0) || (e3 && strcmp(e3, "0") == 0)) return false;
     if (!(d == 128 || d == 256 || d == 512) || heads != 4) return false;
     return T >= 1 && T <= (d == 512 ? 48 : 100) && Mk >= 1 && J >= 1 && J <= 32 && L >= 1 && L <= tg::MAX_L;
 }

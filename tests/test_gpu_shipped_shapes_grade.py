@@ -46,20 +46,24 @@ GENERIC_EDGES = [
 TUNED_EDGES = [
     (256, 1, 2, 4, 1, 2),
     (256, 17, 3, 8, 2, 3),
-    (256, 10, 16, 20, 2, 2),     # 16 / 17 memory rows: the last folded shape, the first wide one
+    (256, 10, 16, 20, 2, 2),     # 17 / 18 memory rows (the step row included): the first wide shapes
     (256, 10, 17, 20, 2, 3),
-    (256, 10, 63, 20, 2, 2),
+    (256, 10, 63, 20, 2, 2),     # 64 memory rows: the last wide shape
     (256, 97, 7, 21, 2, 5),      # five trajectories: 0 and 4 are gated one by one through the `traj` figure
-    (256, 100, 15, 31, 2, 2),
+    (256, 100, 15, 31, 2, 2),    # 16 memory rows: the last folded shape of traj_step_kernel
 ]
+# the route (sd_sampler_route at cap 3) each list and comment above names
+EXPECTED_ROUTE = dict(zip(SHIPPED, ["TRAJ_GENERIC"] * 4 + ["TRAJ_TUNED_WIDE"] * 2 + ["TRAJ_TUNED"] * 2))
+EXPECTED_ROUTE.update({s: "TRAJ_GENERIC" for s in GENERIC_EDGES})
+EXPECTED_ROUTE.update(zip(TUNED_EDGES, ["TRAJ_TUNED", "TRAJ_TUNED", "TRAJ_TUNED_WIDE", "TRAJ_TUNED_WIDE", "TRAJ_TUNED_WIDE", "TRAJ_TUNED", "TRAJ_TUNED"]))
 
 
-def _family(d, T, Mc):
-    """The step kernel sd_sampler_mode 3 runs at a shape (csrc/sd_traj_host.h): the tuned hidden_dim-256 kernels up to 64 memory rows
-    (traj_step_kernel up to 16, traj_step_wide_kernel beyond), the generic family otherwise."""
-    if d == 256 and Mc <= 64:
-        return "tuned" if Mc <= 16 else "tuned wide"
-    return f"generic {d}"
+def _family(shape):
+    """(route, hidden_dim): the step kernel a call capped at mode 3 runs at a shape, as the library reports it (sd_sampler_route)."""
+    from soccerdiffusion_amd import _lib
+
+    d, T, Mc, J, L, B = shape
+    return _lib.sampler_route(d, 4, T, Mc, J, L, B, 3), d
 
 
 # The two families whose deep shipped configs measure above 4 x the fp32 oracle's error on the noise prediction
@@ -71,13 +75,12 @@ def _family(d, T, Mc):
 # kernels of mode 2 (the same split operands, accumulators of their own) and 1.2 - 1.3 x on a generic kernel rebuilt with such
 # accumulators (+ 6.7 % rollout time at larger_model.yaml's shape: not adopted here).  These two families carry the convolution tests'
 # factor (tests/test_gpu_conv.py: e < 8 * e32 + 2e-7) at 6 layers and more; every other shape, their own two-layer edges included, stays at 4.
-DEEP_FACTOR = {"generic 512": 8.0, "tuned wide": 8.0}
+DEEP_FACTOR = {("TRAJ_GENERIC", 512): 8.0, ("TRAJ_TUNED_WIDE", 256): 8.0}
 DEEP_LAYERS = 6
 
 
 def _factor(shape):
-    d, T, Mc, J, L, B = shape
-    return DEEP_FACTOR.get(_family(d, T, Mc), 4.0) if L >= DEEP_LAYERS else 4.0
+    return DEEP_FACTOR.get(_family(shape), 4.0) if shape[4] >= DEEP_LAYERS else 4.0
 
 
 def _case_id(v):
@@ -150,6 +153,14 @@ def test_parity_metrics_see_one_bad_row_and_never_pass_nan():
             assert_fp32_grade(got, want, want.float())
 
 
+@pytest.mark.parametrize("shape", SHIPPED + GENERIC_EDGES + TUNED_EDGES, ids=_case_id)
+def test_case_runs_the_family_it_names(shape):
+    """No GPU: the library reports the step kernel each case above was written for, and the 8 x factor goes to the two deep families only."""
+    assert _family(shape)[0] == EXPECTED_ROUTE[shape]
+    deep = shape in [(512, 10, 311, 20, 8, 2), (512, 10, 311, 22, 8, 1), (256, 10, 50, 20, 6, 2), (256, 10, 50, 22, 6, 1)]
+    assert _factor(shape) == (8.0 if deep else 4.0)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # 2. fp32 grade at the shapes that ship and at their tile edges
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -162,7 +173,7 @@ def test_mode3_rollout_is_fp32_grade_row_by_row(shape):
     from soccerdiffusion_amd import _lib, ops
 
     d, T, Mc, J, L, B = shape
-    assert _lib.load().sd_sampler_mode(d, 4, T, Mc, J) == 3
+    assert _lib.load().sd_sampler_mode(d, 4, T, Mc, J) == 3 and _family(shape)[0] == EXPECTED_ROUTE[shape]
     sd = ref.synthetic_state_dict(d, J, L, seed=17 + T + d)
     g = torch.Generator().manual_seed(T * 7 + Mc + d + J)
     x_T = torch.randn(B, T, J, generator=g)

@@ -40,7 +40,8 @@ for B in (1, 16, 256):
     for Mc in (50, 31, 10, 0):
         x = torch.randn(B, T, 20, device="cuda")
         ctx = torch.randn(B, Mc, 256, device="cuda") if Mc else None
-        rec = {"B": B, "T": T, "memory_rows": Mc + 1, "steps": n_steps, "sd_sampler_mode": _lib.load().sd_sampler_mode(256, 4, T, Mc, 20)}
+        rec = {"B": B, "T": T, "memory_rows": Mc + 1, "steps": n_steps, "sd_sampler_mode": _lib.load().sd_sampler_mode(256, 4, T, Mc, 20),
+               "sd_sampler_route": {mode: _lib.sampler_route(256, 4, T, Mc, 20, packed.L, B, mode) for mode in (2, 3, 4)}}
         status = torch.zeros(1, dtype=torch.int32, device="cuda")
         for mode in (2, 3, 4):
             rec[f"eager_max_mode_{mode}_ms"] = timed(lambda: ops.ddim_sample(packed, ctx, toks, coef, x, status=status, max_mode=mode))

@@ -64,7 +64,8 @@ for name, (d, L, Mc) in CONFIGS.items():
             x = torch.randn(B, T, J, device="cuda")
             ctx = torch.randn(B, Mc, d, device="cuda") if Mc else None
             rec = {"config": name, "hidden_dim": d, "layers": L, "memory_rows": Mc + 1, "T": T, "J": J, "B": B, "steps": n_steps,
-                   "sd_sampler_mode": _lib.load().sd_sampler_mode(d, 4, T, Mc, J)}
+                   "sd_sampler_mode": _lib.load().sd_sampler_mode(d, 4, T, Mc, J),
+                   "sd_sampler_route": {mode: _lib.sampler_route(d, 4, T, Mc, J, L, B, mode) for mode in (2, 3)}}
             n = 3 if B >= 1024 else 10
             for mode in (2, 3):
                 rec[f"eager_max_mode_{mode}_ms"] = timed(lambda: ops.ddim_sample(packed, ctx, toks, coef, x, max_mode=mode), n)

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
+from .derived import current, source_key
 
 Tensor = torch.Tensor
 _const_cache: dict = {}
@@ -167,15 +168,15 @@ def conv_wgrad(dy: Tensor, h: Tensor, weight_shape, stride: int, dy_amax: Option
 
 class PackedPair:
     """The forward planes of a convolution weight and the planes of its flipped transpose (the data gradient's weight), repacked together when
-    the weight changes (version counter or ``ops.weights_generation()``)."""
+    the weight changes (derived.py's rule)."""
 
     def __init__(self):
         self.fwd = self.bwd = None
         self.key = None
 
     def get(self, weight: Tensor):
-        key = (weight._version, ops.weights_generation(), weight.data_ptr())
-        if self.key != key or self.fwd.planes.device != weight.device:
+        key = source_key(weight)
+        if not current(self.key, key):
             w = weight.detach()
             wt = w.flip(2, 3).transpose(0, 1).contiguous()
             self.fwd, self.bwd = ops.PackedConv3x3(w.contiguous()), ops.PackedConv3x3(wt)
@@ -257,7 +258,7 @@ class StemPoolUnit(torch.autograd.Function):
     def forward(ctx, x, weight, gamma, beta, pk: "ops.PackedStem", running_mean, running_var, eps: float, momentum: float):
         x = x.contiguous()
         x_amax = ops.absmax_word(x)
-        y = stem_conv_raw(x, x_amax, pk.refresh(weight))
+        y = stem_conv_raw(x, x_amax, pk)
         p, word, idx, mean, rstd = bn_relu_pool_fwd(y, gamma.detach(), beta.detach(), running_mean, running_var, eps, momentum)
         ctx.save_for_backward(x, x_amax, y, idx, mean, rstd, gamma)
         ctx.mark_non_differentiable(word)

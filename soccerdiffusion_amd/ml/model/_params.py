@@ -9,6 +9,8 @@ import math
 import torch
 from torch import nn
 
+from ...derived import cache
+
 
 def _linear_init(weight: torch.Tensor, bias: torch.Tensor | None) -> None:
     # nn.Linear / nn.Conv1d default: kaiming_uniform(a=sqrt(5)) and U(+-1/sqrt(fan_in))
@@ -73,18 +75,16 @@ class LayerStack(nn.Module):
 
 
 class PackedWeightsMixin:
-    """Caches the C-ABI weight descriptor; rebuilt only when a parameter's storage moved
-    (``.to(device)``); in-place updates (optimizer steps, ``load_state_dict``) keep pointers."""
-
-    _packed = None
-    _packed_sig = None
+    """Caches the C-ABI weight descriptor (off the module: it holds ctypes pointers, which neither copy nor pickle); rebuilt only when a
+    parameter's storage moved (``.to(device)``, ``p.data = other``): it holds pointers, not values, so in-place updates (optimizer
+    steps, ``load_state_dict``) keep it."""
 
     def _signature(self):
         return tuple(p.data_ptr() for p in self.parameters())
 
     def _packed_weights(self, builder):
         sig = self._signature()
-        if self._packed is None or sig != self._packed_sig:
-            self._packed = builder()
-            self._packed_sig = sig
-        return self._packed
+        slot = cache(self, "packed")
+        if slot.get("sig") != sig:
+            slot["value"], slot["sig"] = builder(), sig
+        return slot["value"]

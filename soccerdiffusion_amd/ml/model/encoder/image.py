@@ -29,12 +29,12 @@ from __future__ import annotations
 from enum import Enum
 
 import os
-import weakref
 
 import torch
 from torch import nn
 
 from .... import ops
+from ....derived import cache, derived
 from .encoders import BaseEncoder
 
 
@@ -50,16 +50,15 @@ class SequenceEncoderType(Enum):
     NONE = "none"
 
 
-# Derived tensors of a module (packed weight planes, folded BatchNorm vectors) live OUTSIDE the module - keyed weakly by it - so that
-# ``copy.deepcopy`` / pickling of a model neither carries nor shares them.
-_DERIVED: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+def _planes(mod: nn.Module, kind):
+    """The packed fp16 planes (``kind``: ops.PackedConv3x3 / PackedStem / PackedTokenLinear) of ``mod.weight``, kept off the module by
+    derived.py and repacked in place when the weight changes (new planes only on another device)."""
+    w = mod.weight
+    return derived(mod, "planes", (w,), lambda old: kind(w) if old is None or old.planes.device != w.device else old.refresh(w))
 
 
-def _derived(mod: nn.Module) -> dict:
-    d = _DERIVED.get(mod)
-    if d is None:
-        d = _DERIVED[mod] = {}
-    return d
+def _packed(conv: nn.Conv2d) -> "ops.PackedConv3x3":
+    return _planes(conv, ops.PackedConv3x3)
 
 
 def _conv(cin, cout, k, stride=1, pad=0):
@@ -85,26 +84,13 @@ class _BasicBlock(nn.Module):
 
     @staticmethod
     def _bn_fold(bn: nn.BatchNorm2d):
-        """Inference BatchNorm as y = x * s + t per channel; cached on the module until one of its four tensors changes (four tiny
-        launches per convolution otherwise - a third of the robot's 10-frame forward)."""
-        key = (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version, bn.weight.device, bn.weight.data_ptr(),
-               ops.weights_generation())
-        store = _derived(bn)
-        hit = store.get("fold")
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-        s = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-        t = (bn.bias.detach() - bn.running_mean * s).contiguous()
-        s = s.contiguous()
-        store["fold"] = (key, s, t)
-        return s, t
+        """Inference BatchNorm as y = x * s + t per channel; kept until one of its four tensors changes (four tiny launches per
+        convolution otherwise - a third of the robot's 10-frame forward)."""
+        def fold(_old):
+            s = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
+            return s.contiguous(), (bn.bias.detach() - bn.running_mean * s).contiguous()
 
-    def _packed(self, name: str, conv: nn.Conv2d) -> "ops.PackedConv3x3":
-        store = _derived(conv)
-        pk = store.get("planes")
-        if pk is None or pk.planes.device != conv.weight.device:
-            pk = store["planes"] = ops.PackedConv3x3(conv.weight)
-        return pk.refresh(conv.weight)
+        return derived(bn, "fold", (bn.weight, bn.bias, bn.running_mean, bn.running_var), fold)
 
     def forward_nhwc(self, h: torch.Tensor, amax: torch.Tensor, words: torch.Tensor):
         """Inference on the hand-written kernels: h (N, H, W, C) fp32 NHWC with its abs-max word -> (h', its abs-max word): conv1 / bn1 /
@@ -112,12 +98,12 @@ class _BasicBlock(nn.Module):
         ``words``: two zeroed int32 words for the abs-max of conv1's and conv2's outputs."""
         a1, a2 = words[0:1], words[1:2]
         if self.downsample is None:
-            out = ops.conv3x3_bn_act(h, amax, self._packed("_pk1", self.conv1), *self._bn_fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
+            out = ops.conv3x3_bn_act(h, amax, _packed(self.conv1), *self._bn_fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
             idt = h
         else:   # the stage entry: 3 x 3 stride-2 conv1 and the 1 x 1 stride-2 shortcut (sd_conv_s2_bn_act)
-            out = ops.conv_s2_bn_act(h, amax, self._packed("_pk1", self.conv1), *self._bn_fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
-            idt = ops.conv_s2_bn_act(h, amax, self._packed("_pkd", self.downsample[0]), *self._bn_fold(self.downsample[1]), relu=False)
-        y = ops.conv3x3_bn_act(out, a1, self._packed("_pk2", self.conv2), *self._bn_fold(self.bn2), res=idt, relu=True, y_amax=a2, zero_amax=False)
+            out = ops.conv_s2_bn_act(h, amax, _packed(self.conv1), *self._bn_fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
+            idt = ops.conv_s2_bn_act(h, amax, _packed(self.downsample[0]), *self._bn_fold(self.downsample[1]), relu=False)
+        y = ops.conv3x3_bn_act(out, a1, _packed(self.conv2), *self._bn_fold(self.bn2), res=idt, relu=True, y_amax=a2, zero_amax=False)
         return y, a2
 
     def forward_train_nhwc(self, h: torch.Tensor, amax: torch.Tensor):
@@ -134,11 +120,10 @@ def _train_unit(h, amax, conv, bn, res, relu, pass_input=False):
     """conv + BatchNorm(training) (+ res) (+ ReLU) of a torchvision block under autograd on this package's kernels (conv_training.py)."""
     from .... import conv_training as ct
 
-    store = _derived(conv)
-    pair = store.get("pair")
-    if pair is None:
-        pair = store["pair"] = ct.PackedPair()
-    return ct.unit(h, amax, conv, bn, res, relu, pair, pass_input)
+    slot = cache(conv, "train")
+    if "pair" not in slot:
+        slot["pair"] = ct.PackedPair()
+    return ct.unit(h, amax, conv, bn, res, relu, slot["pair"], pass_input)
 
 
 def _train_ok(block) -> bool:
@@ -167,25 +152,23 @@ class _Bottleneck(nn.Module):
         out = self.relu(self.bn2(self.conv2(out)))
         return self.relu(self.bn3(self.conv3(out)) + idt)
 
-    _packed = _BasicBlock._packed
-
     def forward_nhwc(self, h: torch.Tensor, amax: torch.Tensor, words: torch.Tensor):
         """Inference on the hand-written kernels (as _BasicBlock.forward_nhwc): conv1 1 x 1 / bn1 / relu, conv2 3 x 3 with the block's stride /
         bn2 / relu, conv3 1 x 1 / bn3 / + identity (a 1 x 1 shortcut with the stride where the shapes differ) / relu.  ``words``: three
         zeroed int32 words for the abs-max of the three outputs."""
         fold = _BasicBlock._bn_fold
         a1, a2, a3 = words[0:1], words[1:2], words[2:3]
-        out = ops.conv3x3_bn_act(h, amax, self._packed("_pk1", self.conv1), *fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
+        out = ops.conv3x3_bn_act(h, amax, _packed(self.conv1), *fold(self.bn1), relu=True, y_amax=a1, zero_amax=False)
         stride = self.conv2.stride[0]
         conv2 = ops.conv3x3_bn_act if stride == 1 else ops.conv_s2_bn_act
-        out = conv2(out, a1, self._packed("_pk2", self.conv2), *fold(self.bn2), relu=True, y_amax=a2, zero_amax=False)
+        out = conv2(out, a1, _packed(self.conv2), *fold(self.bn2), relu=True, y_amax=a2, zero_amax=False)
         if self.downsample is None:
             idt = h
         elif stride == 1:
-            idt = ops.conv3x3_bn_act(h, amax, self._packed("_pkd", self.downsample[0]), *fold(self.downsample[1]), relu=False)
+            idt = ops.conv3x3_bn_act(h, amax, _packed(self.downsample[0]), *fold(self.downsample[1]), relu=False)
         else:
-            idt = ops.conv_s2_bn_act(h, amax, self._packed("_pkd", self.downsample[0]), *fold(self.downsample[1]), relu=False)
-        y = ops.conv3x3_bn_act(out, a2, self._packed("_pk3", self.conv3), *fold(self.bn3), res=idt, relu=True, y_amax=a3, zero_amax=False)
+            idt = ops.conv_s2_bn_act(h, amax, _packed(self.downsample[0]), *fold(self.downsample[1]), relu=False)
+        y = ops.conv3x3_bn_act(out, a2, _packed(self.conv3), *fold(self.bn3), res=idt, relu=True, y_amax=a3, zero_amax=False)
         return y, a3
 
     def forward_train_nhwc(self, h: torch.Tensor, amax: torch.Tensor):
@@ -228,10 +211,10 @@ class _ResNet(nn.Module):
         if not (x.is_cuda and x.dtype == torch.float32 and self.conv1.weight.dtype == torch.float32 and self.training
                 and os.environ.get("SD_CONV", "hip") != "torch"):
             return False
-        ok = self.__dict__.get("_train_ok")
-        if ok is None:
-            ok = self.__dict__["_train_ok"] = all(_train_ok(b) for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer)
-        return ok
+        slot = cache(self, "train")
+        if "ok" not in slot:
+            slot["ok"] = all(_train_ok(b) for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer)
+        return slot["ok"]
 
     def _hip_head(self, h: torch.Tensor):
         """(conv or None, fc) when the head is exactly AdaptiveAvgPool2d((1, 1)) or Conv2d(C, 32, 1, bias=True), then an nn.Linear (with bias)
@@ -266,11 +249,7 @@ class _ResNet(nn.Module):
                 y = self.conv1(x).permute(0, 2, 3, 1).contiguous()
                 h, amax = ct.bn_pool_unit(y, self.bn1)
             else:   # the stem kernel's bare convolution, and in the backward the stem's own weight-gradient kernel
-                store = _derived(self.conv1)
-                pk = store.get("planes")
-                if pk is None or pk.planes.device != x.device:
-                    pk = store["planes"] = ops.PackedStem(self.conv1.weight)
-                h, amax = ct.stem_pool_unit(x, self.conv1, self.bn1, pk)
+                h, amax = ct.stem_pool_unit(x, self.conv1, self.bn1, _planes(self.conv1, ops.PackedStem))
             for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
                 for blk in layer:
                     h, amax = blk.forward_train_nhwc(h, amax)
@@ -283,16 +262,12 @@ class _ResNet(nn.Module):
             # the whole inference forward on the hand-written kernels: the stem (conv1 / bn1 / relu / maxpool) in one launch from the NCHW
             # frames to an NHWC map, the basic blocks on NHWC tensors, back to an NCHW view for the head
             x = x.contiguous()
-            store = _derived(self.conv1)
-            pk = store.get("planes")
-            if pk is None or pk.planes.device != x.device:
-                pk = store["planes"] = ops.PackedStem(self.conv1.weight)
             # the abs-max words of the forward's activation tensors (frames, stem, up to three per block): one fill, allocated per call
             # (forwards on different streams / threads must not share them; the caching allocator hands the same block back)
             words = torch.zeros(64, dtype=torch.int32, device=x.device)
             amax = words[1:2]
-            h = ops.stem_conv_bn_relu_pool(x, ops.absmax_word(x, words[0:1], zero=False), pk.refresh(self.conv1.weight), *_BasicBlock._bn_fold(self.bn1),
-                                           y_amax=amax, zero_amax=False)
+            h = ops.stem_conv_bn_relu_pool(x, ops.absmax_word(x, words[0:1], zero=False), _planes(self.conv1, ops.PackedStem),
+                                           *_BasicBlock._bn_fold(self.bn1), y_amax=amax, zero_amax=False)
             at = 2
             for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
                 for blk in layer:
@@ -368,13 +343,8 @@ class _ShiftedWindowAttention(nn.Module):
 
 
 def _token_packed(lin: nn.Linear) -> "ops.PackedTokenLinear":
-    """The split fp16 planes of a Linear for sd_token_linear, cached off-module and repacked when the weight's version or
-    ops.weights_generation() (FusedAdamW's version-less updates) moves."""
-    store = _derived(lin)
-    pk = store.get("tok")
-    if pk is None or pk.device != lin.weight.device:
-        pk = store["tok"] = ops.PackedTokenLinear(lin.weight)
-    return pk.refresh(lin.weight)
+    """The split fp16 planes of a Linear for sd_token_linear."""
+    return _planes(lin, ops.PackedTokenLinear)
 
 
 class _StochasticDepth(nn.Module):       # torchvision.ops.StochasticDepth(p, "row")

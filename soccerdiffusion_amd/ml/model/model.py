@@ -7,30 +7,19 @@ reference class): ``sample`` runs the whole DDIM loop natively."""
 
 from __future__ import annotations
 
-import weakref
 from typing import Optional, Sequence
 
 import torch
 from torch import nn
 
-from ... import ops
+from ... import derived, ops
+from ...derived import cache as _model_cache   # (per-model caches: the loop samplers, the captured graphs)
 from .decoder import DiffusionActionGenerator
 from .encoder.encoders import GameStateEncoder, IMUEncoder, JointEncoder
 from .encoder.image import ImageEncoderType, SequenceEncoderType, image_sequence_encoder_factory
 from .misc import StepToken
 
 NUM_HEADS = 4  # fixed by the reference (model.py:57,71,85,115)
-
-# per-model caches (captured rollout graphs, the loop form's prepared workspaces): outside the module, keyed weakly by it, so that
-# copy.deepcopy / pickling of a model neither carries nor shares them
-_CACHES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def _model_cache(model: nn.Module, name: str) -> dict:
-    per = _CACHES.get(model)
-    if per is None:
-        per = _CACHES[model] = {}
-    return per.setdefault(name, {})
 
 
 class End2EndDiffusionTransformer(nn.Module):
@@ -155,7 +144,8 @@ class End2EndDiffusionTransformer(nn.Module):
             step = step.to(torch.float32 if step.is_floating_point() else torch.int64)
         tokens = ops.step_token(step.contiguous(), self.step_encoding._freq, self.step_encoding.token.detach()).view(n_tok, self.hidden_dim)
         # (dag.packed() rebuilds its descriptor when a parameter's storage moved: its identity stands for the pointers)
-        wkey = (id(packed), tuple(p._version for p in dag.parameters()), ops.weights_generation())
+        versions = derived.version_key(*dag.parameters())
+        wkey = None if versions is None else (id(packed), versions)
         return ls.eps(packed, list(context), tokens, x.contiguous(), wkey)
 
     # ---- extras ------------------------------------------------------------------------
@@ -238,10 +228,11 @@ class End2EndDiffusionTransformer(nn.Module):
             B, T, _ = x_T.shape
             Mc = 0 if ctx is None else ctx.shape[1]
             cap = ops.sampler_cap(packed, max_mode)   # as ops.ddim_sample_guarded
-            key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(),
-                   self.step_encoding.token._version, cap)
+            # the weights are read through pointers at replay (their addresses are the key); the step-token table is captured by value
+            token = derived.source_key(self.step_encoding.token)
+            key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(), token, cap)
             cache = _model_cache(self, "graphs")
-            if key not in cache:
+            if token is None or key not in cache:
                 cache.clear()  # one shape at a time: a graph pins its workspace
                 cache[key] = ops.GraphedSampler(packed, B, T, Mc, self.step_encoding.table(ts, x_T.device), coef, max_mode=cap)
             out = cache[key](ctx, x_T)

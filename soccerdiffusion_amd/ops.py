@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import DenoiserWeights, EncoderWeights, LayerWeights, check
+from .derived import bump_weights_generation, current, version_key, weights_generation  # noqa: F401  (callers use ops.weights_generation())
 
 Tensor = torch.Tensor
 NUM_TRAIN_TIMESTEPS = 1000
@@ -193,21 +194,6 @@ def pack_encoder(sd: Mapping[str, Tensor], device, prefix: str, heads: int = 4, 
 
 
 _ws_cache: dict = {}
-
-# Derived copies of the weights (split fp16 planes, folded BatchNorm vectors, the loop-form sampler's prepared workspace) are keyed on
-# the tensors' version counters - which do NOT move when FusedAdamW updates its flat buffer through a native kernel on raw pointers
-# (training.py) or when a captured training graph is replayed.  Every such update bumps this counter, and every cache key includes it.
-_weights_generation = 0
-
-
-def weights_generation() -> int:
-    return _weights_generation
-
-
-def bump_weights_generation() -> None:
-    global _weights_generation
-    _weights_generation += 1
-
 
 
 def workspace(n_floats: int, device) -> Tensor:
@@ -468,7 +454,8 @@ class LoopSampler:
     ``traj_step_kernel`` per call (plus the step tokens' K / V and fold).  What does not depend on x or the step - the split
     weight planes, the context's K / V folded with Wq / Woc - is prepared into a workspace this object owns and reused until the
     weights (``weights_key``) or the context tensors (identity and version counters; held here so that their addresses cannot be
-    recycled under the cache) change.  ``supported`` is False where the shape does not take these kernels."""
+    recycled under the cache) change; a context without version counters (inference tensors) is prepared on every call.  ``supported``
+    is False where the shape does not take these kernels."""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, n_tok: int, device, max_mode: int = 3):
         lib = _lib.load()
@@ -480,12 +467,12 @@ class LoopSampler:
         self.status = torch.zeros(1, dtype=torch.int32, device=device) if self.supported and self.max_mode == 4 else None
         self.weights_key = None
         self.context: list = []
-        self.versions: tuple = ()
+        self.versions = None
         self.prepares = 0   # (tests: how many times the context was folded)
 
     def _context_hit(self, context) -> bool:
         return (len(context) == len(self.context) and all(a is b for a, b in zip(context, self.context))
-                and tuple(c._version for c in context) == self.versions)
+                and current(self.versions, version_key(*context)))
 
     def eps(self, packed: _Packed, context, tokens: Tensor, x: Tensor, weights_key) -> Optional[Tensor]:
         """Noise prediction (B, T, J) or None when the library declines the shape (the caller falls back)."""
@@ -493,7 +480,7 @@ class LoopSampler:
         B, T, Mc, n_tok = self.shape
         _req(x, "x"); _req(tokens, "step tokens")
         what = 0
-        if weights_key != self.weights_key:
+        if not current(self.weights_key, weights_key):
             what = PREPARE_WEIGHTS | PREPARE_CONTEXT   # the fold multiplies the context's K / V with Wq / Woc
         elif not self._context_hit(context):
             what = PREPARE_CONTEXT
@@ -507,7 +494,7 @@ class LoopSampler:
                 self.supported = False
                 return None
             check(rc, "sd_sampler_prepare")
-            self.weights_key, self.context, self.versions = weights_key, list(context), tuple(c._version for c in context)
+            self.weights_key, self.context, self.versions = weights_key, list(context), version_key(*context)
             self.prepares += 1
         eps = torch.empty_like(x)
         rc = lib.sd_sampler_eps(C.byref(packed.struct), tokens.data_ptr(), x.data_ptr(), eps.data_ptr(), self.ws.data_ptr(), B, T, Mc, n_tok,
@@ -987,7 +974,7 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: flo
 # ---- image path: ResNet basic-block convolution (csrc/sd_conv.hip) -------------------------------------
 class PackedConv3x3:
     """A 3 x 3 (or 1 x 1) convolution weight (Cout, Cin, k, k) in the fragment order of ``sd_conv3x3_bn_act`` / ``sd_conv_s2_bn_act`` plus
-    the power-of-two scale the fp16 planes carry; repacked when the weight's version counter moves."""
+    the power-of-two scale the fp16 planes carry; ``refresh`` repacks in place (when: derived.py)."""
 
     def __init__(self, weight: Tensor):
         lib = _lib.load()
@@ -999,15 +986,12 @@ class PackedConv3x3:
         self.planes = torch.empty(lib.sd_conv_packed_halfs(Cout, Cin, kh), dtype=torch.float16, device=weight.device)
         self.scale = torch.empty(1, dtype=torch.float32, device=weight.device)
         self._word = torch.zeros(1, dtype=torch.int32, device=weight.device)
-        self.version = None
         self.refresh(weight)
 
     def refresh(self, weight: Tensor) -> "PackedConv3x3":
-        if self.version != (weight._version, _weights_generation):
-            w = weight.detach().contiguous()
-            check(_lib.load().sd_conv_pack(w.data_ptr(), self.Cout, self.Cin, self.ksize, self.planes.data_ptr(), self.scale.data_ptr(),
-                                           self._word.data_ptr(), _stream()), "sd_conv_pack")
-            self.version = (weight._version, _weights_generation)
+        w = weight.detach().contiguous()
+        check(_lib.load().sd_conv_pack(w.data_ptr(), self.Cout, self.Cin, self.ksize, self.planes.data_ptr(), self.scale.data_ptr(),
+                                       self._word.data_ptr(), _stream()), "sd_conv_pack")
         return self
 
 
@@ -1065,7 +1049,7 @@ def conv_s2_bn_act(x: Tensor, x_amax: Tensor, w: PackedConv3x3, bn_scale: Tensor
 
 
 class PackedStem:
-    """ResNet's first convolution (64, 3, 7, 7) in the fragment order of ``sd_stem_conv_bn_relu_pool``; repacked when the weight moves."""
+    """ResNet's first convolution (64, 3, 7, 7) in the fragment order of ``sd_stem_conv_bn_relu_pool``; ``refresh`` repacks in place."""
 
     def __init__(self, weight: Tensor):
         lib = _lib.load()
@@ -1075,15 +1059,12 @@ class PackedStem:
         self.planes = torch.empty(lib.sd_stem_packed_halfs(), dtype=torch.float16, device=weight.device)
         self.scale = torch.empty(1, dtype=torch.float32, device=weight.device)
         self._word = torch.zeros(1, dtype=torch.int32, device=weight.device)
-        self.version = None
         self.refresh(weight)
 
     def refresh(self, weight: Tensor) -> "PackedStem":
-        if self.version != (weight._version, _weights_generation):
-            w = weight.detach().contiguous()
-            check(_lib.load().sd_stem_pack(w.data_ptr(), self.planes.data_ptr(), self.scale.data_ptr(), self._word.data_ptr(), _stream()),
-                  "sd_stem_pack")
-            self.version = (weight._version, _weights_generation)
+        w = weight.detach().contiguous()
+        check(_lib.load().sd_stem_pack(w.data_ptr(), self.planes.data_ptr(), self.scale.data_ptr(), self._word.data_ptr(), _stream()),
+              "sd_stem_pack")
         return self
 
 
@@ -1133,14 +1114,6 @@ def _swin_req(t: Tensor, name: str, device=None, dtype=torch.float32, aligned: b
     return t
 
 
-def _version_key(t: Tensor):
-    """t._version, or None for a tensor without a version counter (an inference tensor): such a weight is repacked on every call."""
-    try:
-        return t._version
-    except RuntimeError:
-        return None
-
-
 def _swin_ln(ln, K: int, device, name: str):
     if ln is None:
         return None, None, 1e-5
@@ -1154,7 +1127,7 @@ def _swin_ln(ln, K: int, device, name: str):
 
 class PackedTokenLinear:
     """An nn.Linear weight (N, K), K a multiple of 32, in the fragment order of ``sd_token_linear`` (split fp16 planes) plus the inverse
-    power-of-two scale of each row; repacked when the weight's version counter or ``weights_generation()`` moves."""
+    power-of-two scale of each row; ``refresh`` repacks in place."""
 
     def __init__(self, weight: Tensor):
         lib = _lib.load()
@@ -1166,19 +1139,15 @@ class PackedTokenLinear:
         self.device = w.device
         self.planes = torch.empty(lib.sd_token_packed_halfs(self.N, self.K), dtype=torch.float16, device=w.device)
         self.w_inv = torch.empty(lib.sd_token_pad_cols(self.N), dtype=torch.float32, device=w.device)
-        self.version = None
         self.refresh(weight)
 
     def refresh(self, weight: Tensor) -> "PackedTokenLinear":
-        key = (_version_key(weight), weight.data_ptr(), _weights_generation)
-        if self.version != key or key[0] is None:
-            w = weight.detach()
-            _swin_req(w, "weight", self.device)
-            if tuple(w.shape) != (self.N, self.K):
-                raise ValueError("weight shape changed")
-            check(_lib.load().sd_token_pack(w.data_ptr(), self.N, self.K, self.planes.data_ptr(), self.w_inv.data_ptr(), _stream()),
-                  "sd_token_pack")
-            self.version = key
+        w = weight.detach()
+        _swin_req(w, "weight", self.device)
+        if tuple(w.shape) != (self.N, self.K):
+            raise ValueError("weight shape changed")
+        check(_lib.load().sd_token_pack(w.data_ptr(), self.N, self.K, self.planes.data_ptr(), self.w_inv.data_ptr(), _stream()),
+              "sd_token_pack")
         return self
 
 

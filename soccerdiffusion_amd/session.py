@@ -26,6 +26,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from .derived import current, version_key
 
 KEYS = ("joint_command_history", "rotation", "joint_state")   # the ring modalities, in encode_input_data's order
 WRAPPED = {"joint_command_history": True, "rotation": False, "joint_state": True}   # (x + 3 pi) % (2 pi): ros.py:266-273
@@ -138,16 +139,15 @@ class PolicySession:
         return {"rings": rings, "context_rows": tokens, "memory_rows": tokens + 1, "trajectory": (hp["trajectory_prediction_length"], J)}
 
     # ---- state -----------------------------------------------------------------------------
-    def _weights_key(self) -> tuple:
-        """ops.weights_generation() (FusedAdamW and replayed training graphs rewrite parameters without touching their version counters)
-        and the versions of every parameter and persistent buffer (BatchNorm statistics, mean, std)."""
+    def _weights_key(self):
+        """derived.version_key of every parameter and persistent buffer (BatchNorm statistics, mean, std)."""
         if self._watched is None:   # (rebuilt by reset())
             self._watched = list(self.model.parameters()) + [b for mod in self.model.modules() for n, b in mod._buffers.items()
                                                              if b is not None and n not in mod._non_persistent_buffers_set]
-        return (ops.weights_generation(), tuple(t._version for t in self._watched))
+        return version_key(*self._watched)
 
     def _check_weights(self, what: str) -> None:
-        if self._key != self._weights_key():
+        if not current(self._key, self._weights_key()):
             raise RuntimeError(f"PolicySession.{what}: the model's weights changed since the session was built; its cached image tokens "
                                "belong to the old weights - call reset()")
 

@@ -207,6 +207,38 @@ def test_eval_forward_sees_fused_adamw_updates():
     assert float((after - lib).abs().max() / lib.abs().max()) < 1e-4   # ... and it is the updated weights' result
 
 
+def test_eval_forward_sees_data_swaps():
+    """``p.data = other`` puts new storage behind a parameter and leaves its version counter alone: the packed planes (a convolution
+    weight) and the folded BatchNorm vectors (any of the four tensors, here the bias) are keyed on the addresses as well."""
+    from soccerdiffusion_amd.ml.model.encoder.image import ImageEncoderType, image_encoder_factory
+
+    torch.manual_seed(3)
+    enc = image_encoder_factory(ImageEncoderType.RESNET18, 64, True, 64).cuda().eval()
+    x = torch.rand(1, 2, 3, 64, 64, device="cuda")
+
+    def both_routes():
+        with torch.no_grad():
+            hip = enc(x)
+            os.environ["SD_CONV"] = "torch"
+            try:
+                lib = enc(x)
+            finally:
+                del os.environ["SD_CONV"]
+        assert float((hip - lib).abs().max() / lib.abs().max()) < 1e-4
+        return hip
+
+    before = both_routes()
+    blk = enc.encoder.layer1[0]
+    w, b = blk.conv1.weight, blk.bn1.bias
+    versions, ptrs = (w._version, b._version), (w.data_ptr(), b.data_ptr())
+    w.data = w.data * 1.5
+    scaled = both_routes()         # (each swap on its own is seen ...)
+    b.data = b.data + 0.5
+    after = both_routes()          # (... and both together)
+    assert (w._version, b._version) == versions and w.data_ptr() != ptrs[0] and b.data_ptr() != ptrs[1]
+    assert float((after - before).abs().max()) > 1e-3 and float((scaled - before).abs().max()) > 1e-3
+
+
 # the stem on a 480 x 640 frame, small / odd / ragged frames (conv and pool borders inside one tile), a single pixel
 @pytest.mark.parametrize("N,H,W", [(2, 480, 640), (3, 96, 128), (1, 37, 53), (2, 64, 64), (1, 7, 9), (1, 1, 1), (1, 30, 200)])
 def test_stem_conv_bn_relu_pool_matches_torch_cpu(ops, N, H, W):

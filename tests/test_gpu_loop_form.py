@@ -150,6 +150,34 @@ def test_loop_cache_follows_weights_and_context():
     check()
 
 
+def test_loop_form_under_inference_mode():
+    """A context made inside ``torch.inference_mode()`` has no version counters (reading one raises): it is never taken as current -
+    folded again on every call, the same bits as under ``no_grad`` -, and an ordinary context is cached again afterwards."""
+    d, J, L, T, B, Mc = 256, 20, 2, 16, 2, 5
+    m, _ = _model(d, J, L, T)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, T, J, generator=g).cuda()
+    cg = torch.randn(B, Mc, d, generator=g).cuda()
+    step = torch.full((B,), 300).cuda()
+    with torch.no_grad():
+        want = m.forward_with_context([cg], x, step)
+    ls = next(iter(_loop_cache(m).values()))
+    assert ls.supported and ls.prepares == 1
+    with torch.inference_mode():
+        for i in range(3):
+            inside = cg.clone()
+            assert inside.is_inference()
+            got = m.forward_with_context([inside], x, step)
+            assert torch.equal(got, want)
+            assert ls.prepares == 2 + i
+    with torch.no_grad():
+        assert torch.equal(m.forward_with_context([cg], x, step), want)
+        assert ls.prepares == 5   # (another list of tensors than the last call's)
+        assert torch.equal(m.forward_with_context([cg], x, step), want)
+        assert ls.prepares == 5
+    assert len(_loop_cache(m)) == 1
+
+
 def test_unsupported_shapes_fall_back():
     """hidden_dim 64 (BASELINE configs[0]) is not a trajectory-kernel shape: the call lands on sd_denoiser_forward as before."""
     d, J, L, T, B, Mc = 64, 20, 2, 16, 2, 10

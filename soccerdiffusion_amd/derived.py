@@ -33,13 +33,21 @@ def bump_weights_generation() -> None:
     _generation += 1
 
 
+def versions(*tensors):
+    """The per-tensor half of ``version_key``, or None when a tensor has no version counter: the whole key of copies whose owner is the
+    only one to rewrite their sources through raw pointers and refreshes them itself each time (a FusedAdamW's planes: the generation
+    moves with every optimizer's step, another one's included)."""
+    try:
+        return tuple([t._version for t in tensors])
+    except RuntimeError:
+        return None
+
+
 def version_key(*tensors):
     """(generation, versions), or None when a tensor has no version counter.  For long per-call lists whose addresses something else
     already covers; everything else takes ``source_key``."""
-    try:
-        return _generation, tuple([t._version for t in tensors])
-    except RuntimeError:
-        return None
+    v = versions(*tensors)
+    return None if v is None else (_generation, v)
 
 
 def source_key(*tensors):

@@ -1,0 +1,230 @@
+"""FusedAdamW - torch.optim.AdamW semantics on ONE flat fp32 buffer per quantity - and WeightPlanes, the one store of every copy the
+training kernels read instead of the flat parameter buffer itself: split fp16 planes of the d x d blocks and of their transposes, the fp32
+transposed gather that stands in for them, and the trajectory kernels' planes.  The optimizer owns its store and refreshes it where every
+rewrite of the buffer ends; lookups go from a tensor's address to the live store whose buffer contains it."""
+
+from __future__ import annotations
+
+import os
+import weakref
+from typing import Iterable
+
+import torch
+
+from . import derived, ops
+
+Tensor = torch.Tensor
+
+_STORES: list = []   # weak references to the stores that answer lookups; dead ones answer nothing and leave when the next store is built
+
+
+def planes_of(W: Tensor):
+    """The live store whose flat parameter buffer contains W's address (W: a parameter, a row slice such as W[d:], or detached - autograd
+    hands the nodes views, so the lookup is by address), else None."""
+    a = W.data_ptr()
+    for ref in _STORES:
+        s = ref()
+        if s is not None and s.lo <= a < s.hi:
+            return s
+    return None
+
+
+class WeightPlanes:
+    """The derived copies of one flat parameter buffer, refreshed by ONE gather / two pack launches per block width after every step (the
+    weights are final until the next one) instead of one strided copy or one in-register split per GEMM and workgroup:
+      * ``flat_wpk``: [planes of the blocks | planes of the transposed blocks], 2 d^2 halfs each - the fp16 hi | lo fragment planes the
+        panel kernel multiplies with (ops.pack_weight_blocks), so the ~45 GEMMs of a step stream 1-KiB fragments;
+      * ``flat_wt``: without planes (no GPU, SD_TRAIN_PACKED=0) an fp32 copy of every transposed block, same order, for the dX GEMMs;
+      * ``traj``: planes of whole matrices in the 16 x 16 x 32 fragment order of the trajectory kernels (csrc/sd_traj.h), for the slices
+        the stacks asked for (``traj_planes``); repacked by one launch.
+    ``blocks`` maps a block's address to (float offset of its transpose in flat_wt's order, d, parameter index).  A parameter's copies are
+    current while ``derived.versions`` of it is what the last refresh saw (load_state_dict, p.mul_(), ... move it; a write through
+    ``p.data`` does not - call ``optimizer.refresh_transposes()`` after one)."""
+
+    def __init__(self, flat_param: Tensor, params):
+        self.flat_param, dev = flat_param, flat_param.device
+        self.lo = flat_param.data_ptr()
+        self.hi = self.lo + 4 * flat_param.numel()
+        # gather index of every d x d block of the (N = k d, d) matrices, transposed
+        idx, blocks, self.params, at, out_at = [], [], [], 0, 0
+        for p in params:
+            k = p.numel()
+            if p.dim() == 2 and p.shape[1] in (64, 128, 256, 512) and p.shape[0] % p.shape[1] == 0:
+                N, d = p.shape
+                idx.append(at + torch.arange(k, dtype=torch.int64).view(N // d, d, d).transpose(1, 2).reshape(-1))
+                blocks += [(at + blk * d * d, out_at + blk * d * d, d, len(self.params)) for blk in range(N // d)]
+                self.params.append(p)
+                out_at += k
+            at += k
+        self.blocks = {self.lo + 4 * src: (off, d, pi) for src, off, d, pi in blocks}
+        self.total = out_at
+        self.seen = [None] * len(self.params)   # per parameter, the version key of the last refresh (None: never current)
+        # per block width, (source offsets, first block) of the pack launches
+        self.flat_wpk, self.launches = None, []
+        if idx and dev.type == "cuda" and os.environ.get("SD_TRAIN_PACKED", "1") != "0":
+            self.flat_wpk = torch.empty(4 * out_at, dtype=torch.float16, device=dev)
+            for d in sorted({b[2] for b in blocks}):
+                run = [b for b in blocks if b[2] == d]
+                # blocks of one width are contiguous in flat_wt only if no other width interleaves: pack run by run
+                runs, cur = [], [run[0]]
+                for b in run[1:]:
+                    if b[1] == cur[-1][1] + d * d:
+                        cur.append(b)
+                    else:
+                        runs.append(cur); cur = [b]
+                runs.append(cur)
+                for r in runs:
+                    self.launches.append((d, len(r), torch.tensor([b[0] for b in r], dtype=torch.int64, device=dev), 2 * r[0][1]))
+        self.wt_index = torch.cat(idx).to(dev) if idx and self.flat_wpk is None else None
+        self.flat_wt = torch.empty(out_at, dtype=torch.float32, device=dev) if idx and self.flat_wpk is None else None
+        self.traj, self.traj_at, self.traj_dev = None, {}, None   # planes, {(source float offset, rows): half offset}, device index arrays
+        if self.blocks and flat_param.is_cuda:
+            _STORES[:] = [r for r in _STORES if r() is not None] + [weakref.ref(self)]
+
+    def refresh(self) -> None:
+        if not self.blocks or not self.flat_param.is_cuda:
+            return
+        if self.flat_wt is not None:
+            torch.index_select(self.flat_param, 0, self.wt_index, out=self.flat_wt)
+        for d, n, src, half_off in self.launches:   # the transposition happens inside the pack kernel
+            ops.pack_weight_blocks(self.flat_param, src, n, d, self.flat_wpk[half_off:])
+            ops.pack_weight_blocks(self.flat_param, src, n, d, self.flat_wpk[2 * self.total + half_off:], transposed=True)
+        self.seen = [derived.versions(p) for p in self.params]
+        self._repack_traj()
+
+    def block(self, W: Tensor, p: int, d: int):
+        """Float offset of the transpose of block p of W in flat_wt's order while W's copies are current, else None."""
+        ent = self.blocks.get(W.data_ptr() + 4 * p * d * d)
+        if ent is not None and ent[1] == d and W.shape[1] == d and derived.current(self.seen[ent[2]], derived.versions(self.params[ent[2]])):
+            return ent[0]
+        return None
+
+    def traj_planes(self, slices) -> list:
+        """Addresses of the trajectory-kernel planes (ops.pack_weight_traj layout) of rows [row0, row0 + rows) of W for every (W, row0, rows)
+        of ``slices`` - a stack asks for all of its slices at once.  New ones register first (lazily: in the eager warm-up steps of a
+        graphed loop), then the buffer grows ONCE and every registered slice is repacked, so all the addresses returned hold together;
+        addresses handed out before a growth do not."""
+        at, n = [], len(self.traj_at)
+        for W, row0, rows in slices:
+            src = (W.data_ptr() - self.lo) // 4 + row0 * 256
+            if W.shape[1] != 256 or W.stride() != (256, 1) or rows % 16 or src + rows * 256 > self.flat_param.numel() or self.block(W, 0, 256) is None:
+                raise ValueError("trajectory-order planes are kept for current (N, 256) row-major matrices of this optimizer, 16 rows at a time")
+            at.append(self.traj_at.setdefault((src, rows), sum(2 * 256 * r for _, r in self.traj_at)))
+        if len(self.traj_at) > n:
+            dev = self.flat_param.device
+            self.traj = torch.empty(sum(2 * 256 * r for _, r in self.traj_at), dtype=torch.float16, device=dev)
+            self.traj_dev = (torch.tensor([s for s, _ in self.traj_at], dtype=torch.int64, device=dev),
+                             torch.tensor([r for _, r in self.traj_at], dtype=torch.int32, device=dev),
+                             torch.tensor(list(self.traj_at.values()), dtype=torch.int64, device=dev))
+            self._repack_traj()
+        return [self.traj.data_ptr() + 2 * a for a in at]
+
+    def _repack_traj(self) -> None:
+        if self.traj is not None:
+            ops.pack_weight_traj_multi(self.flat_param, *self.traj_dev, max(r for _, r in self.traj_at), self.traj)
+
+
+def _transposed_block(W: Tensor, p: int, d: int) -> Tensor:
+    s = planes_of(W)
+    off = s.block(W, p, d) if s is not None and s.flat_wt is not None else None
+    if off is not None:
+        return s.flat_wt[off : off + d * d].view(d, d)
+    return W[p * d : (p + 1) * d].t().contiguous()
+
+
+def _packed_weight(W: Tensor, p: int = 0, transposed: bool = False):
+    """Address of the planes of block p of W (and of the blocks behind it), or None when W has no current planes."""
+    d = W.shape[1]
+    s = planes_of(W)
+    if s is None or s.flat_wpk is None or W.stride() != (d, 1):
+        return None
+    off = s.block(W, p, d)
+    return None if off is None else s.flat_wpk.data_ptr() + 2 * (2 * off + (2 * s.total if transposed else 0))
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """AdamW(lr) with torch's defaults (betas 0.9/0.999, eps 1e-8, weight_decay 1e-2) as the
+    reference constructs it (train.py:162).  Parameters, gradients and both moments live in
+    four flat buffers (parameters are re-pointed to views), so a step is one kernel launch
+    and the data-parallel gradient exchange is one all-reduce.  ``state_dict()`` has torch
+    AdamW's layout (``state[i] = {step, exp_avg, exp_avg_sq}``), so checkpoints interchange.
+    Being a torch Optimizer, ``OneCycleLR`` drives ``lr`` and ``betas[0]`` as in the reference."""
+
+    def __init__(self, params: Iterable[Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2):
+        params = [p for p in params if p.requires_grad]
+        if not params:
+            raise ValueError("no trainable parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        dev = params[0].device
+        n = sum(p.numel() for p in params)
+        self.flat_param = torch.empty(n, dtype=torch.float32, device=dev)
+        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.flat_m = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.flat_v = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._step = 0
+        at = 0
+        for p in params:
+            k = p.numel()
+            self.flat_param[at : at + k].copy_(p.detach().reshape(-1))
+            p.data = self.flat_param[at : at + k].view(p.shape)
+            p.grad = self.flat_grad[at : at + k].view(p.shape)
+            self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.flat_m[at : at + k].view(p.shape),
+                             "exp_avg_sq": self.flat_v[at : at + k].view(p.shape)}
+            at += k
+        self.planes = WeightPlanes(self.flat_param, params)
+        self.refresh_transposes()
+
+    flat_wpk = property(lambda self: self.planes.flat_wpk)
+    flat_wt = property(lambda self: self.planes.flat_wt)
+
+    def refresh_transposes(self) -> None:
+        """The per-step refresh of the derived copies of the weights (WeightPlanes)."""
+        ops.bump_weights_generation()   # every path that rewrites flat_param ends here (step, step_from_device_hyper, broadcast)
+        self.planes.refresh()
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.flat_grad.zero_()
+        at = 0
+        for p in self.param_groups[0]["params"]:  # keep .grad aliased to the flat buffer
+            k = p.numel()
+            if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * at:
+                p.grad = self.flat_grad[at : at + k].view(p.shape)
+            at += k
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        g = self.param_groups[0]
+        self._step += 1
+        ops.adamw_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
+                       g["eps"], g["weight_decay"], self._step)
+        self.refresh_transposes()
+
+    @torch.no_grad()
+    def step_from_device_hyper(self, hyper7: Tensor) -> None:
+        """The update with its scalars read from device memory (``hyper_for_step``): what a captured graph replays.
+        Does NOT advance ``_step`` - the caller that fills ``hyper7`` does."""
+        ops.adamw_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, hyper7)
+        self.refresh_transposes()
+
+    def hyper_for_step(self, step: int, out) -> None:
+        """The seven scalars of update number ``step`` at the CURRENT lr / betas of the param group -> ``out`` (7 floats)."""
+        g = self.param_groups[0]
+        ops.adamw_hyper(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], step, out)
+
+    def state_dict(self):
+        for p in self.param_groups[0]["params"]:   # torch AdamW's per-parameter step counters, all equal here
+            self.state[p]["step"] = torch.tensor(float(self._step))
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        views = {id(p): (self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in self.param_groups[0]["params"]}
+        super().load_state_dict(state_dict)
+        steps = []
+        for p in self.param_groups[0]["params"]:
+            st = self.state[p]
+            m, v = views[id(p)]
+            m.copy_(st["exp_avg"]); v.copy_(st["exp_avg_sq"])
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+            steps.append(int(float(st["step"])))
+        self._step = max(steps) if steps else 0

@@ -17,35 +17,39 @@ block, its forward and backward are calls into libsoccerdiffusion_hip.so.
 from __future__ import annotations
 
 import os
-from typing import Iterable, Optional
+import weakref
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
 
 from . import ops
+from .optim import FusedAdamW, _packed_weight, _transposed_block, planes_of  # noqa: F401  (the optimizer's names stay importable from here)
 
 Tensor = torch.Tensor
 
 
+def _grad_views(*params):
+    """Where parameter gradients go.  When the ``.grad`` buffers of all of ``params`` - parameters, or (parameter, row slice) pairs - are
+    preallocated (FusedAdamW aliases them to one flat buffer and zeroes it per step), the backward kernels ACCUMULATE straight into them
+    (dW += dY^T X with fp32 atomics) and the autograd node returns None for those inputs: no zero-fill, no extra add kernel, no copy.
+    Returns those buffers, or None: fresh zeros are then handed back to autograd as usual."""
+    views = []
+    for item in params:
+        p, sl = item if isinstance(item, tuple) else (item, None)
+        if p.grad is None or not p.grad.is_cuda:
+            return None
+        views.append(p.grad if sl is None else p.grad[sl])
+    return views
+
+
 class _GradSink:
-    """Where a block's parameter gradients go.  When the parameters' ``.grad`` buffers are
-    preallocated (FusedAdamW aliases them to one flat buffer and zeroes it per step), the
-    backward kernels ACCUMULATE straight into them (dW += dY^T X with fp32 atomics) and the
-    autograd node returns None for those inputs: no zero-fill, no extra add kernel, no copy.
-    Otherwise fresh tensors are returned to autograd as usual."""
+    """_grad_views decided when the forward builds the node; the zeros, if any, are made in the backward."""
 
     __slots__ = ("views",)
 
     def __init__(self, *params_and_slices):
-        views = [] if params_and_slices else None
-        for item in params_and_slices:
-            p, sl = item if isinstance(item, tuple) else (item, None)
-            g = p.grad
-            if g is None or not g.is_cuda:
-                views = None
-                break
-            views.append(g if sl is None else g[sl])
-        self.views = views
+        self.views = _grad_views(*params_and_slices) if params_and_slices else None
 
     def target(self, i: int, like: Tensor):
         """(tensor to accumulate into, value to hand back to autograd)."""
@@ -55,62 +59,13 @@ class _GradSink:
         return z, z
 
 
-# Transposed d x d weight blocks for the dX GEMMs, keyed by the block's address: FusedAdamW fills it with ONE gather over
-# its flat parameter buffer after every step (the weights are final until the next one), instead of one strided copy
-# kernel per block and backward node (41 launches, 3 % of the B=256 step).  An entry is valid while its optimizer is alive
-# and the parameter's version counter is the one seen at the gather (load_state_dict, p.mul_(), ... bump it; a write
-# through ``p.data`` does not - call ``optimizer.refresh_transposes()`` after one).
-_WT_BLOCKS: dict = {}
-
-
-def _wt_entry(W: Tensor, p: int, d: int):
-    """(optimizer, float offset of block p's transpose in flat_wt) while the gather is current, else None."""
-    ent = _WT_BLOCKS.get(W.data_ptr() + 4 * p * d * d)
-    if ent is not None:
-        owner, off, bd, pi = ent
-        opt = owner()
-        if opt is not None and bd == d and W.shape[1] == d and opt._wt_params[pi]._version == opt._wt_versions[pi]:
-            return opt, off
-    return None
-
-
-def _transposed_block(W: Tensor, p: int, d: int) -> Tensor:
-    ent = _wt_entry(W, p, d)
-    if ent is not None and ent[0].flat_wt is not None:
-        return ent[0].flat_wt[ent[1] : ent[1] + d * d].view(d, d)
-    return W[p * d : (p + 1) * d].t().contiguous()
-
-
-# The same registry serves the split planes of the row GEMMs: after every step FusedAdamW also splits each block and each
-# transposed block into the fp16 hi | lo fragment planes the panel kernel multiplies with (ops.pack_weight_blocks, two
-# launches), so the ~45 GEMMs of a step stream 1-KiB fragments instead of splitting fp32 weights in registers in every
-# workgroup.  flat_wpk holds [planes of the blocks | planes of the transposed blocks], 2 d^2 halfs each, in flat_wt's order.
-def _packed_weight(W: Tensor, p: int = 0, transposed: bool = False):
-    """Address of the planes of block p of W (and of the blocks behind it), or None when W has no current planes."""
-    d = W.shape[1]
-    if W.stride() != (d, 1):
-        return None
-    ent = _wt_entry(W, p, d)
-    if ent is None or ent[0].flat_wpk is None:
-        return None
-    opt, off = ent
-    return opt.flat_wpk.data_ptr() + 2 * (2 * off + (2 * opt._wt_total if transposed else 0))
-
-
-# Planes of whole weight matrices in the 16 x 16 x 32 fragment order of the trajectory kernels (csrc/sd_traj.h), for the layer-forward
-# kernel sd_train_layer_fwd: a second, lazily built set beside flat_wpk.  A matrix registers with its optimizer on first use (in the
-# eager warm-up steps of a graphed loop); from then on FusedAdamW.refresh_transposes repacks every registered matrix in one launch.
-def _packed_weight_traj(W: Tensor, row0: int = 0, rows: Optional[int] = None):
-    """Address of the trajectory-kernel planes of rows [row0, row0 + rows) of W (N x 256, row-major, owned by a FusedAdamW), else None."""
-    d = W.shape[1]
-    if d != 256 or W.stride() != (d, 1):
-        return None
-    ent = _wt_entry(W, 0, d)
-    if ent is None:
-        return None
-    opt = ent[0]
-    rows = W.shape[0] - row0 if rows is None else rows
-    return opt.traj_planes(W, row0, rows)
+def _grad_targets(*params):
+    """(tensors to accumulate into, values to hand back to autograd), decided and made in the backward."""
+    views = _grad_views(*params)
+    if views is not None:
+        return views, [None] * len(params)
+    z = [torch.zeros_like(p[0][p[1]] if isinstance(p, tuple) else p) for p in params]
+    return z, z
 
 
 def _linear(A: Tensor, W: Tensor, b, ln=None, res=None, drop=None) -> Tensor:
@@ -121,14 +76,6 @@ def _linear(A: Tensor, W: Tensor, b, ln=None, res=None, drop=None) -> Tensor:
     if drop is not None:
         return ops.linear_dropout(A.contiguous(), W, b, res, drop)
     return ops.linear(A, W, b, ln=ln, res=res)
-
-
-# ---- weight gradients ----------------------------------------------------------------------------------------------
-# dW += dY^T X depends on dY and on a saved activation only.  (Round 2 could enqueue these GEMMs on a parallel branch of the captured
-# graph; the branch overlapped - 1.0 of 5.2 ms of kernel time concurrent - but both sides slowed down by as much, 5.85 vs
-# 5.83 ms per step, so the variant and its switch are gone.)
-def _dw(dY: Tensor, X: Tensor, dW: Tensor, db: Optional[Tensor]) -> None:
-    ops.gemm_tn(dY, X, dW, db)
 
 
 def _dx_through_weight(dy2d: Tensor, W: Tensor) -> Tensor:
@@ -209,7 +156,7 @@ class _LNLinear(Function):
         n, mean, rstd = ops.layernorm_fwd(x2, ln_w, ln_b)  # recomputed, not stored
         (dg, rg), (dbeta, rbeta) = ctx.sink.target(0, ln_w), ctx.sink.target(1, ln_w)
         (dW, rW), (db, rb) = ctx.sink.target(2, W), ctx.sink.target(3, W[:, 0])
-        _dw(dpre, n, dW, db)
+        ops.gemm_tn(dpre, n, dW, db)
         dn = _dx_through_weight(dpre, W)
         # the residual branch's gradient of the same h (left by _LinearRes.backward, which ran first) is added inside the
         # LayerNorm backward kernel instead of by an autograd accumulation kernel
@@ -240,7 +187,7 @@ class _LinearRes(Function):
         dy2 = dy.contiguous().view(-1, W.shape[0])
         dym = ops.dropout(dy2, ctx.drop) if ctx.drop is not None else dy2   # gradient of the dropped branch; the residual gets dy
         (dW, rW), (db, rb) = ctx.sink.target(0, W), ctx.sink.target(1, W[:, 0])
-        _dw(dym, a2, dW, db)
+        ops.gemm_tn(dym, a2, dW, db)
         da = _dx_through_weight(dym, W)
         if ctx.link is not None:   # h's other consumer is the _LNLinear that shares this link: it adds dy inside its kernel
             ctx.link["dres"] = dy2
@@ -264,7 +211,7 @@ class _Linear(Function):
         a2, W = ctx.saved_tensors
         dy2 = dy.contiguous().view(-1, W.shape[0])
         (dW, rW), (db, rb) = ctx.sink.target(0, W), ctx.sink.target(1, W[:, 0])
-        _dw(dy2, a2, dW, db)
+        ops.gemm_tn(dy2, a2, dW, db)
         da = _dx_through_weight(dy2, W) if ctx.needs_input_grad[0] else None
         return (da.view(ctx.shape) if da is not None else None), rW, rb, None
 
@@ -318,9 +265,9 @@ class _CrossAttention(Function):
 # registry could hand a reused allocation the stale maximum of a freed tensor.  The consumer reads the attribute
 # from the very object it was handed (before any view) and also checks the shape and the tensor's version counter - an in-place
 # update after registration (autograd's InputBuffer accumulating into a gradient it holds the last reference to, an in-place hook)
-# would leave a stale, too-small maximum behind; anything else takes the block-floating GEMM.
+# would leave a stale, too-small maximum behind; anything else takes the block-floating GEMM.  (This pair versions an
+# ACTIVATION, for the length of one step: the only read of ``._version`` outside derived.py, whose rule is about weights.)
 def _amax_register(t: Tensor, table: Tensor, slot_addr: int, scratch_addr: int) -> None:
-    import weakref
     t._sd_amax = (weakref.ref(table), slot_addr, scratch_addr, tuple(t.shape), t._version)
 
 
@@ -344,13 +291,21 @@ def _dw_skinny(dY: Tensor, X: Tensor, dW: Tensor, db, known: Tensor, small: Tens
     ops.gemm_tn_grouped([(dY, X, dW, db, ay, ax)])
 
 
-def _grad_targets(*params):
-    """(tensors to accumulate into, values to hand back to autograd): straight into the preallocated ``.grad`` buffers
-    (FusedAdamW's flat buffer, zeroed per step: no zero-fill, no accumulation kernel) when every parameter has one."""
-    if all(p.grad is not None and p.grad.is_cuda for p in params):
-        return [p.grad for p in params], [None] * len(params)
-    z = [torch.zeros_like(p) for p in params]
-    return z, z
+def _embed_dw(x: Tensor, W: Tensor, b: Tensor, dy: Tensor):
+    """The embedding's weight and bias gradient from the gradient ``dy`` of its output: (dy as rows, values to hand back to autograd)."""
+    d = W.shape[0]
+    if W.dim() == 2:
+        patches = x.reshape(-1, x.shape[-1])
+    else:  # (d, C, p): patch rows in (c, k) order, a layout copy
+        _, C, p = W.shape
+        B, S, _ = x.shape
+        n = S // p
+        patches = x[:, : n * p].reshape(B, n, p, C).permute(0, 1, 3, 2).reshape(B * n, C * p).contiguous()
+    (dW, db), (rW, rb) = _grad_targets(W, b)
+    ent = _amax_lookup(dy) if dy.is_contiguous() else None   # the very tensor the stack's backward produced
+    dy2 = dy.contiguous().view(-1, d)
+    _dw_skinny(dy2, patches, dW.view(d, patches.shape[1]), db, known=dy2, small=patches, ent=ent)
+    return dy2, rW, rb
 
 
 class _PatchEmbed(Function):
@@ -366,17 +321,7 @@ class _PatchEmbed(Function):
     def backward(ctx, dy):
         x, W, b = ctx.saved_tensors
         d = W.shape[0]
-        if W.dim() == 2:
-            patches = x.reshape(-1, x.shape[-1])
-        else:  # (d, C, p): patch rows in (c, k) order, a layout copy
-            _, C, p = W.shape
-            B, S, _ = x.shape
-            n = S // p
-            patches = x[:, : n * p].reshape(B, n, p, C).permute(0, 1, 3, 2).reshape(B * n, C * p).contiguous()
-        (dW, db), (rW, rb) = _grad_targets(W, b)
-        ent = _amax_lookup(dy) if dy.is_contiguous() else None   # the very tensor the stack's backward produced
-        dy2 = dy.contiguous().view(-1, d)
-        _dw_skinny(dy2, patches, dW.view(d, patches.shape[1]), db, known=dy2, small=patches, ent=ent)
+        dy2, rW, rb = _embed_dw(x, W, b, dy)
         dx = None
         if ctx.needs_input_grad[0]:
             # only the image tokens are a differentiable input (they come from the ResNet): kernel size 1, C = d
@@ -393,36 +338,20 @@ class _EmbedHead(Function):
     _PatchEmbed sends it."""
 
     @staticmethod
-    def forward(ctx, x, W, b, pe, n1w, n1b, Wqkv, bqkv, amax_n1: int):
+    def forward(ctx, x, W, b, pe, n1w, n1b, w_qkv: int, bqkv, amax_n1: int):
         ctx.save_for_backward(x, W, b)
         x = x.contiguous()
         w_emb = ops.pack_weight_traj(W.detach().contiguous())     # (256, J): a 4-us launch per step
-        h0, n1, qkv = ops.train_head_fwd(x, w_emb.data_ptr(), b.detach(), pe, (n1w.detach(), n1b.detach()), _packed_weight_traj(Wqkv), bqkv.detach(),
-                                         amax_n1)
+        h0, n1, qkv = ops.train_head_fwd(x, w_emb.data_ptr(), b.detach(), pe, (n1w.detach(), n1b.detach()), w_qkv, bqkv.detach(), amax_n1)
         ctx.mark_non_differentiable(n1, qkv)
         return h0, n1, qkv
 
     @staticmethod
     def backward(ctx, dy, _dn, _dqkv):
-        if ctx.needs_input_grad[0]:   # (_embed_head_ok sends a differentiable x to _PatchEmbed, which raises as well)
+        if ctx.needs_input_grad[0]:   # (train_route sends a differentiable x to _PatchEmbed, which raises as well)
             raise NotImplementedError("the denoiser's embedding has no gradient with respect to the noisy trajectory")
-        x, W, b = ctx.saved_tensors
-        d = W.shape[0]
-        patches = x.reshape(-1, x.shape[-1])
-        (dW, db), (rW, rb) = _grad_targets(W, b)
-        ent = _amax_lookup(dy) if dy.is_contiguous() else None
-        dy2 = dy.contiguous().view(-1, d)
-        _dw_skinny(dy2, patches, dW.view(d, patches.shape[1]), db, known=dy2, small=patches, ent=ent)
+        _, rW, rb = _embed_dw(*ctx.saved_tensors, dy)
         return None, rW, rb, None, None, None, None, None, None
-
-
-def _embed_head_ok(gen, x: Tensor, layers) -> bool:
-    import os
-
-    W = gen.embedding.weight
-    J = x.shape[-1]
-    return (os.environ.get("SD_TRAIN_TRAJ", "1") != "0" and x.is_cuda and not x.requires_grad and W.dim() == 2 and W.shape[0] == 256 and J % 4 == 0 and 4 <= J <= 32
-            and x.shape[1] <= 100 and gen.num_heads == 4 and _packed_weight_traj(layers[0].self_attn.in_proj_weight) is not None)
 
 
 class _FcOut(Function):
@@ -526,7 +455,7 @@ def _layer(lp, h, heads, memory=None, ffn_norm=None, dc=None, li: int = 0):
 # five chain launches, two attention backward kernels and seven weight-gradient GEMMs.  A layer therefore hands its
 # successor (h, LN1(h), qkv); the successor's backward differentiates LN1 / in_proj (they are its parameters).
 # Conditions (else the per-operation nodes above run): hidden_dim 64 / 128 / 256, dim_feedforward == hidden_dim, every
-# weight owned by a FusedAdamW that keeps its split planes current.  SD_TRAIN_FUSED=0 turns the path off (A/B runs).
+# weight owned by a FusedAdamW that keeps its split planes current (train_route).
 _DEC_PARAMS = ("norm1.weight", "norm1.bias", "self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
                "self_attn.out_proj.bias", "norm2.weight", "norm2.bias", "multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias",
                "multihead_attn.out_proj.weight", "multihead_attn.out_proj.bias", "norm3.weight", "norm3.bias", "linear1.weight",
@@ -545,19 +474,55 @@ def _layer_params(lp, decoder: bool) -> list:
     return out
 
 
-def _fused_ok(layers, d: int, decoder: bool) -> bool:
-    if os.environ.get("SD_TRAIN_FUSED", "1") == "0" or d not in (64, 128, 256) or not layers:
-        return False
-    for lp in layers:
-        P = _layer_params(lp, decoder)
-        if any((not t.is_cuda) or t.dtype != torch.float32 for t in P):
-            return False
-        mats = [t for t in P if t.dim() == 2]
-        if any(t.shape[1] != d or t.shape[0] % d != 0 for t in mats) or lp.linear1.weight.shape[0] != d:
-            return False
-        if any(_packed_weight(t) is None or _packed_weight(t, 0, transposed=True) is None for t in mats):
-            return False
-    return True
+def _stack_facts(layers, d: int, decoder: bool):
+    """What train_route asks about a stack's weights: (``params_ok``, ``ffn_is_d``, ``block_planes``, the ONE store that keeps planes for all
+    of its matrices - the one that can keep their trajectory-order planes too - or None)."""
+    P = [t for lp in layers for t in _layer_params(lp, decoder)]
+    mats = [t for t in P if t.dim() == 2]
+    params_ok = (bool(layers) and all(t.is_cuda and t.dtype == torch.float32 for t in P)
+                 and all(t.shape[1] == d and t.shape[0] % d == 0 for t in mats))
+    # (the planes of a block and of its transpose are packed and retired together: one lookup answers for both)
+    block_planes = params_ok and all(_packed_weight(t) is not None for t in mats)
+    stores = {id(s): s for s in map(planes_of, mats)} if block_planes else {}
+    return params_ok, all(lp.linear1.weight.shape[0] == d for lp in layers), block_planes, next(iter(stores.values())) if len(stores) == 1 else None
+
+
+class TrainRoute(NamedTuple):
+    stack: str          # "per_op": the per-operation nodes above; "chains": _fused_stack
+    embed_head: bool    # the decoder's embedding + LN1 + QKV of layer 0 as one trajectory-owning launch (_EmbedHead)
+    traj_layers: bool   # every decoder layer's forward as one trajectory-owning launch (sd_train_layer_fwd)
+
+
+def train_route(*, decoder: bool, d: int, heads: int, T: int, M: int, J: int, ffn_is_d: bool, params_ok: bool, block_planes: bool,
+                traj_planes: bool, x_differentiable: bool, layer_fwd_ok=None) -> TrainRoute:
+    """Which kernels run for a layer stack: decided once per forward, here, from plain facts (DESIGN.md has the table).  ``M``: memory rows
+    including the step token (0: an encoder); ``params_ok``: at least one layer and every layer parameter CUDA fp32 of the expected shape;
+    ``block_planes`` / ``traj_planes``: a FusedAdamW keeps current block planes (and their transposes) for every matrix / can keep
+    trajectory-order planes for the matrices the two flags need.  The callers' ``traj_planes`` carries three things this function does not
+    see: ONE optimizer owns every matrix of the stack (a stack split over two runs as row chains), x is on the GPU, and the embedding
+    weight is 2-D (always, for the decoder's nn.Linear).  The flags are independent: d = 256 with 17 memory rows enters through
+    the head launch and runs its layers as row chains.  SD_TRAIN_FUSED=0 / SD_TRAIN_TRAJ=0 (A/B runs) are read here and nowhere else.
+    ``layer_fwd_ok`` stands in for ops.train_layer_fwd_ok (d 256, 4 heads, 1 <= T <= 100, 1 <= M <= 16) where the library is not loaded."""
+    if not (os.environ.get("SD_TRAIN_FUSED", "1") != "0" and d in (64, 128, 256) and params_ok and ffn_is_d and block_planes):
+        return TrainRoute("per_op", False, False)
+    traj = decoder and traj_planes and os.environ.get("SD_TRAIN_TRAJ", "1") != "0"
+    return TrainRoute("chains",
+                      traj and not x_differentiable and d == 256 and J % 4 == 0 and 4 <= J <= 32 and T <= 100 and heads == 4,
+                      traj and M > 0 and bool((layer_fwd_ok or ops.train_layer_fwd_ok)(d, heads, T, M)))
+
+
+def _traj_slices(layers, route: TrainRoute) -> dict:
+    """{name: (W, first row, rows)} of every matrix the trajectory launches of a decoder stack read, in launch order - and of no other (each
+    registered slice is pack work per step): "head", layer 0's in-projection; per layer li, under (li, field of sd_train_layer_fwd_args),
+    Wo, the query rows of Wc, Woc, W1, W2 and the successor's in-projection."""
+    d = 256
+    out = {"head": (layers[0].self_attn.in_proj_weight, 0, 3 * d)} if route.embed_head else {}
+    for li, lp in enumerate(layers if route.traj_layers else ()):
+        out.update({(li, "w_o"): (lp.self_attn.out_proj.weight, 0, d), (li, "w_q"): (lp.multihead_attn.in_proj_weight, 0, d),
+                    (li, "w_oc"): (lp.multihead_attn.out_proj.weight, 0, d), (li, "w_1"): (lp.linear1.weight, 0, d), (li, "w_2"): (lp.linear2.weight, 0, d)})
+        if li + 1 < len(layers):
+            out[li, "w_n"] = (layers[li + 1].self_attn.in_proj_weight, 0, 3 * d)
+    return out
 
 
 # abs-max words of a layer (row li of the stack's int32 table; bits of max |x|, atomically max-ed by the chains' row passes):
@@ -568,11 +533,17 @@ AMAX_WORDS = 64   # SD_AMAX_WORDS: the producers spread their atomics over this 
 _AX_SLOTS = 20                             # with a scratch slot each for their small operand); _AX_MEM: the memory (row 0)
 
 
-class _FusedCfg:
-    __slots__ = ("heads", "dc", "li", "decoder", "next_ln", "next_w", "next_b", "amax")
+def _ax(amax: Tensor, layer: int, slot: int) -> int:
+    """Address of abs-max word ``slot`` of row ``layer`` of a stack's table."""
+    return amax.data_ptr() + 4 * AMAX_WORDS * (layer * _AX_SLOTS + slot)
 
-    def __init__(self, heads, dc, li, decoder, nxt, amax):
+
+class _FusedCfg:
+    __slots__ = ("heads", "dc", "li", "decoder", "next_ln", "next_w", "next_b", "amax", "tw")
+
+    def __init__(self, heads, dc, li, decoder, nxt, amax, tw=None):
         self.heads, self.dc, self.li, self.decoder, self.amax = heads, dc, li, decoder, amax
+        self.tw = tw   # the plane addresses of sd_train_layer_fwd (train_route's traj_layers), else None: attention + row chains
         if nxt is not None:
             self.next_ln = (nxt.norm1.weight.detach(), nxt.norm1.bias.detach())
             self.next_w, self.next_b = nxt.self_attn.in_proj_weight.detach(), nxt.self_attn.in_proj_bias.detach()
@@ -584,11 +555,7 @@ class _FusedCfg:
 
     def ax(self, idx: int, layer_offset: int = 0) -> int:
         """Address of abs-max word ``idx`` of this layer (or of the next one)."""
-        return self.amax.data_ptr() + 4 * AMAX_WORDS * ((self.li + layer_offset) * _AX_SLOTS + idx)
-
-    @property
-    def ax_mem(self) -> int:
-        return self.amax.data_ptr() + 4 * AMAX_WORDS * _AX_MEM   # row 0
+        return _ax(self.amax, self.li + layer_offset, idx)
 
     def drop(self, kind: int):
         return self.dc.site(self.li, kind) if self.dc is not None else None
@@ -622,25 +589,6 @@ def _mem_side(device):
 TRAJ_LAYERS = [0]   # decoder layers whose forward ran as ONE trajectory-owning launch (tests assert which path ran)
 
 
-def _traj_layer_weights(cfg, P, h: Tensor, memory: Tensor):
-    """The plane addresses sd_train_layer_fwd needs, or None when the layer does not qualify (shape, SD_TRAIN_TRAJ=0, weights that no
-    FusedAdamW keeps planes for): the per-op / row-chain launches run instead."""
-    import os
-
-    if os.environ.get("SD_TRAIN_TRAJ", "1") == "0" or not h.is_cuda or memory is None:
-        return None
-    B, T, d = h.shape
-    if not ops.train_layer_fwd_ok(d, cfg.heads, T, memory.shape[1]):
-        return None
-    (n1w, n1b, Wqkv, bqkv, Wo, bo, n2w, n2b, Wc, bc, Woc, boc, nfw, nfb, W1, b1, W2, b2) = P
-    for _ in range(2):   # a slice that registers on first use re-allocates the plane buffer: resolve the addresses again afterwards
-        w = dict(w_o=_packed_weight_traj(Wo), w_q=_packed_weight_traj(Wc, 0, d), w_oc=_packed_weight_traj(Woc), w_1=_packed_weight_traj(W1),
-                 w_2=_packed_weight_traj(W2), w_n=_packed_weight_traj(cfg.next_w) if cfg.next_w is not None else None)
-    if any(v is None for k, v in w.items() if k != "w_n") or (cfg.next_w is not None and w["w_n"] is None):
-        return None
-    return w
-
-
 class _FusedLayer(Function):
     """One pre-norm transformer layer (nn.TransformerDecoderLayer with memory, nn.TransformerEncoderLayer without) given
     (h, LN1(h), qkv = LN1(h) Wqkv^T + b); returns (h', LN1'(h'), qkv') for the next layer (empty tensors after the last)."""
@@ -649,89 +597,58 @@ class _FusedLayer(Function):
     def forward(ctx, h, n1, qkv, memory, cfg: _FusedCfg, *P):
         B, T, d = h.shape
         R = B * T
-        dec = cfg.decoder
+        dec, last = cfg.decoder, cfg.next_w is None
         heads, p, seed = cfg.heads, cfg.p, cfg.seed
         if dec:
             (n1w, n1b, Wqkv, bqkv, Wo, bo, n2w, n2b, Wc, bc, Woc, boc, nfw, nfb, W1, b1, W2, b2) = P
         else:
             (n1w, n1b, Wqkv, bqkv, Wo, bo, nfw, nfb, W1, b1, W2, b2) = P
         h = h.contiguous()
-        side = None
         if dec:   # the memory's K/V projection beside the self-attention and chain A
             M = memory.shape[1]
-            mem2 = memory.reshape(B * M, d)
             kv = _new(B, M, 2 * d, like=h)
             side = _mem_side(h.device)
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    ops.linear_packed(mem2, _packed_weight(Wc, 1), 2 * d, bc[d:], out=kv.view(B * M, 2 * d))
-            else:
-                ops.linear_packed(mem2, _packed_weight(Wc, 1), 2 * d, bc[d:], out=kv.view(B * M, 2 * d))
-        tw = _traj_layer_weights(cfg, P, h, memory) if dec else None
-        if tw is not None:
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                ops.linear_packed(memory.reshape(B * M, d), _packed_weight(Wc, 1), 2 * d, bc[d:], out=kv.view(B * M, 2 * d))
+            h1, n2, q = _new(B, T, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
+        h2, nf, pre, u, h3 = _new(B, T, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
+        nn1, qkv2 = (_new(0, like=h), _new(0, like=h)) if last else (_new(R, d, like=h), _new(B, T, 3 * d, like=h))
+        ax_out = cfg.ax(_AX_OUT) if last else None   # the stack's output feeds fc_out (decoder): its weight gradient needs this abs-max
+        if cfg.tw is not None:
             # ---- ONE launch for the whole layer forward: a workgroup per trajectory (csrc/sd_train_traj.hip) ----
-            a_sa, h1, q, a_ca, h2, h3 = (_new(B, T, d, like=h) for _ in range(6))
-            n2, nf, pre, u = (_new(R, d, like=h) for _ in range(4))
-            lse_sa, lse_ca = _new(B, heads, T, like=h), _new(B, heads, T, like=h)
-            if cfg.next_w is not None:
-                nn1, qkv2 = _new(R, d, like=h), _new(B, T, 3 * d, like=h)
-            else:
-                nn1, qkv2 = _new(0, like=h), _new(0, like=h)
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
+            a_sa, a_ca, lse_sa, lse_ca = _new(B, T, d, like=h), _new(B, T, d, like=h), _new(B, heads, T, like=h), _new(B, heads, T, like=h)
+            torch.cuda.current_stream().wait_stream(side)
             TRAJ_LAYERS[0] += 1
             ops.train_layer_fwd(
                 B, T, M, heads,
                 tensors=dict(h=h, qkv=qkv, a_sa=a_sa, lse_sa=lse_sa, h1=h1, n2=n2, q=q, kv=kv, a_ca=a_ca, lse_ca=lse_ca, h2=h2, nf=nf, pre=pre, u=u,
-                             h3=h3, nn1=nn1 if cfg.next_w is not None else None, qkv2=qkv2 if cfg.next_w is not None else None,
+                             h3=h3, nn1=None if last else nn1, qkv2=None if last else qkv2,
                              b_o=bo, b_q=bc, b_oc=boc, b_1=b1, b_2=b2, b_n=cfg.next_b, n2_w=n2w, n2_b=n2b, n3_w=nfw, n3_b=nfb,
-                             nn_w=cfg.next_ln[0] if cfg.next_w is not None else None, nn_b=cfg.next_ln[1] if cfg.next_w is not None else None),
-                weights=tw, p=p, seed=seed,
-                sites=(cfg.site(SITE_SA_PROBS), cfg.site(SITE_SA_OUT), cfg.site(SITE_CA_PROBS), cfg.site(SITE_CA_OUT), cfg.site(SITE_FFN_ACT),
-                       cfg.site(SITE_FFN_OUT)),
-                amax=(cfg.ax(_AX_ASA), cfg.ax(_AX_N2), cfg.ax(_AX_ACA), cfg.ax(_AX_NF), cfg.ax(_AX_U),
-                      cfg.ax(_AX_N1, 1) if cfg.next_w is not None else None, cfg.ax(_AX_OUT) if cfg.next_w is None else None))
-            if cfg.next_w is None:
-                _amax_register(h3, cfg.amax, cfg.ax(_AX_OUT), cfg.ax(_AX_SCR))
-            ctx.cfg = cfg
-            ctx.n_c = 6
-            ctx.set_materialize_grads(False)
-            ctx.save_for_backward(h, n1, qkv, memory, a_sa, lse_sa, h2, nf, pre, u, h1, n2, q, kv, a_ca, lse_ca, *P)
-            ctx.mark_non_differentiable(nn1, qkv2)
-            return h3, nn1, qkv2
-        a_sa, lse_sa = ops.attention_lse(qkv[..., :d], qkv[..., d : 2 * d], qkv[..., 2 * d :], heads, cfg.drop(SITE_SA_PROBS))
-        saved_c = ()
-        if dec:
-            h1, n2, q = _new(B, T, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
-            ops.train_fwd_chain(R, d, h, a=a_sa, wo=_packed_weight(Wo), bo=bo, h_out=h1, nln=(n2w, n2b), nn_out=n2,
-                                wn=_packed_weight(Wc), bn=bc, y_out=q, n_next=1, p=p, seed=seed, sites=(cfg.site(SITE_SA_OUT), 0, 0),
-                                amax=(cfg.ax(_AX_ASA), None, None, cfg.ax(_AX_N2)))
-            if side is not None:
+                             nn_w=None if last else cfg.next_ln[0], nn_b=None if last else cfg.next_ln[1]),
+                weights=cfg.tw, p=p, seed=seed, sites=tuple(cfg.site(k) for k in range(6)),   # SITE_* in their own order
+                amax=(cfg.ax(_AX_ASA), cfg.ax(_AX_N2), cfg.ax(_AX_ACA), cfg.ax(_AX_NF), cfg.ax(_AX_U), None if last else cfg.ax(_AX_N1, 1), ax_out))
+        else:
+            a_sa, lse_sa = ops.attention_lse(qkv[..., :d], qkv[..., d : 2 * d], qkv[..., 2 * d :], heads, cfg.drop(SITE_SA_PROBS))
+            if dec:
+                ops.train_fwd_chain(R, d, h, a=a_sa, wo=_packed_weight(Wo), bo=bo, h_out=h1, nln=(n2w, n2b), nn_out=n2,
+                                    wn=_packed_weight(Wc), bn=bc, y_out=q, n_next=1, p=p, seed=seed, sites=(cfg.site(SITE_SA_OUT), 0, 0),
+                                    amax=(cfg.ax(_AX_ASA), None, None, cfg.ax(_AX_N2)))
                 torch.cuda.current_stream().wait_stream(side)
-            a_ca, lse_ca = ops.attention_lse(q, kv[..., :d], kv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
-            a_in, w_in, b_in, h_res, site_out, ax_a = a_ca, Woc, boc, h1, cfg.site(SITE_CA_OUT), _AX_ACA
-            saved_c = (h1, n2, q, kv, a_ca, lse_ca)
-        else:
-            a_in, w_in, b_in, h_res, site_out, ax_a = a_sa, Wo, bo, h, cfg.site(SITE_SA_OUT), _AX_ASA
-        h2, nf, pre, u, h3 = _new(B, T, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
-        if cfg.next_w is not None:
-            nn1, qkv2 = _new(R, d, like=h), _new(B, T, 3 * d, like=h)
-            nxt = dict(nln=cfg.next_ln, nn_out=nn1, wn=_packed_weight(cfg.next_w), bn=cfg.next_b, y_out=qkv2, n_next=3)
-        else:
-            nn1, qkv2 = _new(0, like=h), _new(0, like=h)
-            nxt = {}
-        ops.train_fwd_chain(R, d, h_res, a=a_in, wo=_packed_weight(w_in), bo=b_in, h_out=h2, ln=(nfw, nfb), n_out=nf,
-                            w1=_packed_weight(W1), b1=b1, pre=pre, u=u, w2=_packed_weight(W2), b2=b2, h2_out=h3, p=p, seed=seed,
-                            sites=(site_out, cfg.site(SITE_FFN_ACT), cfg.site(SITE_FFN_OUT)),
-                            amax=(cfg.ax(ax_a), cfg.ax(_AX_NF), cfg.ax(_AX_U), cfg.ax(_AX_N1, 1), cfg.ax(_AX_OUT) if cfg.next_w is None else None),
-                            **nxt)
-        if cfg.next_w is None:   # the stack's output feeds fc_out (decoder): its weight gradient needs this abs-max
-            _amax_register(h3, cfg.amax, cfg.ax(_AX_OUT), cfg.ax(_AX_SCR))
+                a_ca, lse_ca = ops.attention_lse(q, kv[..., :d], kv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
+                a_in, w_in, b_in, h_res, site_out, ax_a = a_ca, Woc, boc, h1, cfg.site(SITE_CA_OUT), _AX_ACA
+            else:
+                a_in, w_in, b_in, h_res, site_out, ax_a = a_sa, Wo, bo, h, cfg.site(SITE_SA_OUT), _AX_ASA
+            nxt = {} if last else dict(nln=cfg.next_ln, nn_out=nn1, wn=_packed_weight(cfg.next_w), bn=cfg.next_b, y_out=qkv2, n_next=3)
+            ops.train_fwd_chain(R, d, h_res, a=a_in, wo=_packed_weight(w_in), bo=b_in, h_out=h2, ln=(nfw, nfb), n_out=nf,
+                                w1=_packed_weight(W1), b1=b1, pre=pre, u=u, w2=_packed_weight(W2), b2=b2, h2_out=h3, p=p, seed=seed,
+                                sites=(site_out, cfg.site(SITE_FFN_ACT), cfg.site(SITE_FFN_OUT)),
+                                amax=(cfg.ax(ax_a), cfg.ax(_AX_NF), cfg.ax(_AX_U), cfg.ax(_AX_N1, 1), ax_out), **nxt)
+        if last:
+            _amax_register(h3, cfg.amax, ax_out, cfg.ax(_AX_SCR))
         ctx.cfg = cfg
-        ctx.n_c = len(saved_c)
         ctx.set_materialize_grads(False)   # LN1'(h') and qkv' carry no gradient: autograd would hand zeros of their size to backward
-        ctx.save_for_backward(h, n1, qkv, memory if dec else None, a_sa, lse_sa, h2, nf, pre, u, *saved_c, *P)
+        ctx.save_for_backward(h, n1, qkv, memory if dec else None, a_sa, lse_sa, h2, nf, pre, u, *((h1, n2, q, kv, a_ca, lse_ca) if dec else ()), *P)
         ctx.mark_non_differentiable(nn1, qkv2)
         return h3, nn1, qkv2
 
@@ -741,7 +658,8 @@ class _FusedLayer(Function):
         dec, heads, p, seed = cfg.decoder, cfg.heads, cfg.p, cfg.seed
         sv = ctx.saved_tensors
         h, n1, qkv, memory, a_sa, lse_sa, h2, nf, pre, u = sv[:10]
-        saved_c, P = sv[10 : 10 + ctx.n_c], sv[10 + ctx.n_c :]
+        n_c = 6 if dec else 0   # the cross-attention's tensors
+        saved_c, P = sv[10 : 10 + n_c], sv[10 + n_c :]
         B, T, d = h.shape
         R = B * T
         if dec:
@@ -749,10 +667,7 @@ class _FusedLayer(Function):
             h1, n2, q, kv, a_ca, lse_ca = saved_c
         else:
             (n1w, n1b, Wqkv, bqkv, Wo, bo, nfw, nfb, W1, b1, W2, b2) = P
-        # where the parameter gradients go: straight into the preallocated .grad buffers (FusedAdamW's flat buffer), else
-        # fresh tensors handed back to autograd
-        direct = all(t.grad is not None and t.grad.is_cuda for t in P)
-        G = [t.grad if direct else torch.zeros_like(t) for t in P]
+        G, back = _grad_targets(*P)
         g = dict(zip(_DEC_PARAMS if dec else _ENC_PARAMS, G))
         nf_name = "norm3" if dec else "norm2"
         wT = lambda W, blk=0: _packed_weight(W, blk, transposed=True)   # noqa: E731
@@ -786,14 +701,13 @@ class _FusedLayer(Function):
             if ctx.needs_input_grad[3]:   # (the learned half of the step token sits in the memory)
                 dmem = _new(*memory.shape, like=h)
             mside = _mem_side(h.device)
-            if mside is not None:
-                mside.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(mside if mside is not None else torch.cuda.current_stream()):
+            mside.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(mside):
                 if grouped:
                     ops.absmax(dkv.view(B * M, 2 * d), cfg.ax(_AX_DKV))
-                    dws.append((dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:], cfg.ax(_AX_DKV), cfg.ax_mem))
+                    dws.append((dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:], cfg.ax(_AX_DKV), _ax(cfg.amax, 0, _AX_MEM)))
                 else:
-                    _dw(dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:])
+                    ops.gemm_tn(dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:])
                 if dmem is not None:   # both column passes in one launch
                     ops.train_bwd_chain(B * M, d, dkv.view(B * M, 2 * d), wT(Wc, 1), dmem.view(B * M, d), passes=2)
             dh1 = _new(B, T, d, like=h)
@@ -818,34 +732,37 @@ class _FusedLayer(Function):
         if cfg.li == 0:   # the gradient of the stack's input feeds the embedding's weight gradient
             _amax_register(dh, cfg.amax, cfg.ax(_AX_DX), cfg.ax(_AX_SCR2))
         dws.append((dqkv.view(R, 3 * d), n1, g["self_attn.in_proj_weight"], g["self_attn.in_proj_bias"], cfg.ax(_AX_DQKV), cfg.ax(_AX_N1)))
-        if dec and _mem_side(h.device) is not None:
-            torch.cuda.current_stream().wait_stream(_mem_side(h.device))   # dmem and the abs-max of dkv
+        if dec:
+            torch.cuda.current_stream().wait_stream(mside)   # dmem and the abs-max of dkv
         if grouped:
             ops.gemm_tn_grouped(dws)
         else:
             for dY, X, dW, db, _, _ in dws:
-                _dw(dY, X, dW, db)
-        return (dh, None, None, dmem, None) + tuple(None if direct else t for t in G)
+                ops.gemm_tn(dY, X, dW, db)
+        return (dh, None, None, dmem, None) + tuple(back)
 
 
 FUSED_STACKS = [0]   # how many layer stacks went through the fused path (tests assert that it is the path that ran)
 
 
-def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, embed=None) -> Tensor:
-    """``embed`` = (x, gen): the stack starts from the raw trajectory - embedding, LayerNorm 1 and the Q | K | V projection of layer 0 in
-    one trajectory-owning launch (_EmbedHead) - instead of from an embedded ``h``."""
+def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, route: TrainRoute, store=None, embed=None) -> Tensor:
+    """``embed`` = (x, gen) with route.embed_head: the stack starts from the raw trajectory - embedding, LayerNorm 1 and the Q | K | V
+    projection of layer 0 in one trajectory-owning launch (_EmbedHead) - instead of from an embedded ``h``."""
     FUSED_STACKS[0] += 1
-    lp0 = layers[0]
+    lp0, L = layers[0], len(layers)
     dev = embed[0].device if embed is not None else h.device
     d = lp0.norm1.weight.shape[0]
-    amax = torch.zeros(len(layers) + 1, _AX_SLOTS, AMAX_WORDS, dtype=torch.int32, device=dev)
+    amax = torch.zeros(L + 1, _AX_SLOTS, AMAX_WORDS, dtype=torch.int32, device=dev)
     if memory is not None and d % 128 == 0:
-        ops.absmax(memory.reshape(-1, d), amax.data_ptr() + 4 * AMAX_WORDS * _AX_MEM)
+        ops.absmax(memory.reshape(-1, d), _ax(amax, 0, _AX_MEM))
+    # the trajectory launches' planes: every slice of the stack in one request, so no address is resolved before a later registration grows the buffer
+    slices = _traj_slices(layers, route)
+    tw = dict(zip(slices, store.traj_planes(slices.values()))) if slices else {}
     if embed is not None:
         x, gen = embed
         pe = gen.positional_encoding.pe[0, : x.shape[1]].contiguous()
-        h, n1, qkv = _EmbedHead.apply(x, gen.embedding.weight, gen.embedding.bias, pe, lp0.norm1.weight, lp0.norm1.bias, lp0.self_attn.in_proj_weight,
-                                      lp0.self_attn.in_proj_bias, amax.data_ptr() + 4 * AMAX_WORDS * _AX_N1)
+        h, n1, qkv = _EmbedHead.apply(x, gen.embedding.weight, gen.embedding.bias, pe, lp0.norm1.weight, lp0.norm1.bias, tw["head"], lp0.self_attn.in_proj_bias,
+                                      _ax(amax, 0, _AX_N1))
         B, T, d = h.shape
     else:
         B, T, d = h.shape
@@ -854,11 +771,13 @@ def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, 
             n1, qkv = _new(B * T, d, like=h), _new(B, T, 3 * d, like=h)
             ops.train_fwd_chain(B * T, d, h.detach(), nln=(lp0.norm1.weight, lp0.norm1.bias), nn_out=n1,
                                 wn=_packed_weight(lp0.self_attn.in_proj_weight), bn=lp0.self_attn.in_proj_bias, y_out=qkv, n_next=3,
-                                amax=(None, None, None, amax.data_ptr() + 4 * AMAX_WORDS * _AX_N1))
+                                amax=(None, None, None, _ax(amax, 0, _AX_N1)))
     for li, lp in enumerate(layers):
         if hooks:
             _layer_input_hook(h, li)
-        cfg = _FusedCfg(heads, dc, li, decoder, layers[li + 1] if li + 1 < len(layers) else None, amax)
+        # traj_layers is a property of the stack: every layer passes the same shape test, and "chains" already required planes for every layer
+        lw = {k: tw.get((li, k)) for k in ("w_o", "w_q", "w_oc", "w_1", "w_2", "w_n")} if route.traj_layers else None
+        cfg = _FusedCfg(heads, dc, li, decoder, layers[li + 1] if li + 1 < L else None, amax, lw)
         h, n1, qkv = _FusedLayer.apply(h, n1, qkv, memory, cfg, *_layer_params(lp, decoder))
     return h
 
@@ -870,13 +789,14 @@ def denoiser_forward_autograd(gen, x: Tensor, memory: Tensor) -> Tensor:
     memory = memory.contiguous()
     dc = gen.dropout.for_call(gen.training)
     layers = list(gen.transformer_decoder.layers)
-    d_model = gen.embedding.weight.shape[0]
-    if _fused_ok(layers, d_model, decoder=True) and _embed_head_ok(gen, x, layers):
-        h = _fused_stack(layers, None, gen.num_heads, memory, dc, decoder=True, hooks=True, embed=(x, gen))
-        return _FcOut.apply(h, gen.fc_out.weight, gen.fc_out.bias)
-    h = _PatchEmbed.apply(x, gen.embedding.weight, gen.embedding.bias, pe)
-    if _fused_ok(layers, h.shape[-1], decoder=True):
-        h = _fused_stack(layers, h, gen.num_heads, memory, dc, decoder=True, hooks=True)
+    W = gen.embedding.weight
+    params_ok, ffn_is_d, block_planes, store = _stack_facts(layers, W.shape[0], decoder=True)
+    route = train_route(decoder=True, d=W.shape[0], heads=gen.num_heads, T=T, M=memory.shape[1], J=x.shape[-1], ffn_is_d=ffn_is_d, params_ok=params_ok,
+                        block_planes=block_planes, traj_planes=store is not None and x.is_cuda and W.dim() == 2, x_differentiable=x.requires_grad)
+    h = None if route.embed_head else _PatchEmbed.apply(x, W, gen.embedding.bias, pe)
+    if route.stack == "chains":
+        h = _fused_stack(layers, h, gen.num_heads, memory, dc, decoder=True, hooks=True, route=route, store=store,
+                         embed=(x, gen) if route.embed_head else None)
     else:
         for li, lp in enumerate(layers):
             _layer_input_hook(h, li)
@@ -891,179 +811,14 @@ def encoder_forward_autograd(enc, x: Tensor) -> Tensor:
     h = _PatchEmbed.apply(x, enc.embedding.weight, enc.embedding.bias, pe)
     dc = enc.dropout.for_call(enc.training)
     layers = list(enc.transformer_encoder.layers)
-    if _fused_ok(layers, h.shape[-1], decoder=False):
-        return _fused_stack(layers, h, enc.num_heads, None, dc, decoder=False, hooks=False)
+    params_ok, ffn_is_d, block_planes, _ = _stack_facts(layers, h.shape[-1], decoder=False)
+    route = train_route(decoder=False, d=h.shape[-1], heads=enc.num_heads, T=n, M=0, J=x.shape[-1], ffn_is_d=ffn_is_d, params_ok=params_ok,
+                        block_planes=block_planes, traj_planes=False, x_differentiable=x.requires_grad)
+    if route.stack == "chains":
+        return _fused_stack(layers, h, enc.num_heads, None, dc, decoder=False, hooks=False, route=route)
     for li, lp in enumerate(layers):
         h = _layer(lp, h, enc.num_heads, memory=None, ffn_norm=lp.norm2, dc=dc, li=li)
     return h
-
-
-# --------------------------------------------------------------------------------------
-# optimizer: torch.optim.AdamW semantics on ONE flat fp32 buffer per quantity
-# --------------------------------------------------------------------------------------
-class FusedAdamW(torch.optim.Optimizer):
-    """AdamW(lr) with torch's defaults (betas 0.9/0.999, eps 1e-8, weight_decay 1e-2) as the
-    reference constructs it (train.py:162).  Parameters, gradients and both moments live in
-    four flat buffers (parameters are re-pointed to views), so a step is one kernel launch
-    and the data-parallel gradient exchange is one all-reduce.  ``state_dict()`` has torch
-    AdamW's layout (``state[i] = {step, exp_avg, exp_avg_sq}``), so checkpoints interchange.
-    Being a torch Optimizer, ``OneCycleLR`` drives ``lr`` and ``betas[0]`` as in the reference."""
-
-    def __init__(self, params: Iterable[Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2):
-        params = [p for p in params if p.requires_grad]
-        if not params:
-            raise ValueError("no trainable parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        dev = params[0].device
-        n = sum(p.numel() for p in params)
-        self.flat_param = torch.empty(n, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat_m = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat_v = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._step = 0
-        at = 0
-        for p in params:
-            k = p.numel()
-            self.flat_param[at : at + k].copy_(p.detach().reshape(-1))
-            p.data = self.flat_param[at : at + k].view(p.shape)
-            p.grad = self.flat_grad[at : at + k].view(p.shape)
-            self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.flat_m[at : at + k].view(p.shape),
-                             "exp_avg_sq": self.flat_v[at : at + k].view(p.shape)}
-            at += k
-        # gather index of every d x d block of the (N = k d, d) matrices, transposed (see _WT_BLOCKS)
-        idx, self._wt_blocks, self._wt_params, at, out_at = [], [], [], 0, 0
-        for p in params:
-            k = p.numel()
-            if p.dim() == 2 and p.shape[1] in (64, 128, 256, 512) and p.shape[0] % p.shape[1] == 0:
-                N, d = p.shape
-                idx.append(at + torch.arange(k, dtype=torch.int64).view(N // d, d, d).transpose(1, 2).reshape(-1))
-                for blk in range(N // d):
-                    self._wt_blocks.append((self.flat_param.data_ptr() + 4 * (at + blk * d * d), out_at + blk * d * d, d,
-                                            len(self._wt_params)))
-                self._wt_params.append(p)
-                out_at += k
-            at += k
-        self._wt_total = out_at
-        # split planes of the same blocks (see _packed_weight): per block width, (source offsets, first block) of the launch
-        self.flat_wpk, self._pk_launches = None, []
-        if idx and dev.type == "cuda" and os.environ.get("SD_TRAIN_PACKED", "1") != "0":
-            self.flat_wpk = torch.empty(4 * out_at, dtype=torch.float16, device=dev)
-            base = self.flat_param.data_ptr()
-            for d in sorted({b[2] for b in self._wt_blocks}):
-                run = [b for b in self._wt_blocks if b[2] == d]
-                # blocks of one width are contiguous in flat_wt only if no other width interleaves: pack run by run
-                runs, cur = [], [run[0]]
-                for b in run[1:]:
-                    if b[1] == cur[-1][1] + d * d:
-                        cur.append(b)
-                    else:
-                        runs.append(cur); cur = [b]
-                runs.append(cur)
-                for r in runs:
-                    fwd = torch.tensor([(b[0] - base) // 4 for b in r], dtype=torch.int64, device=dev)
-                    wt = torch.tensor([b[1] for b in r], dtype=torch.int64, device=dev)
-                    self._pk_launches.append((d, len(r), fwd, wt, 2 * r[0][1]))
-        # without planes (no GPU, SD_TRAIN_PACKED=0): an fp32 copy of every W^T block from one gather per step
-        self._wt_index = torch.cat(idx).to(dev) if idx and self.flat_wpk is None else None
-        self.flat_wt = torch.empty(out_at, dtype=torch.float32, device=dev) if idx and self.flat_wpk is None else None
-        self._wt_versions = []
-        self.refresh_transposes()
-
-    def refresh_transposes(self) -> None:
-        """The per-step derived copies of the weights: the split planes of every d x d block and of its transpose (two
-        launches per block width; the transposition happens inside the pack kernel), or - without planes - an fp32 gather
-        of the transposed blocks (one kernel; see _WT_BLOCKS)."""
-        ops.bump_weights_generation()   # every path that rewrites flat_param ends here (step, step_from_device_hyper, broadcast)
-        if not self._wt_blocks or not self.flat_param.is_cuda:
-            return
-        import weakref
-        if self.flat_wt is not None:
-            torch.index_select(self.flat_param, 0, self._wt_index, out=self.flat_wt)
-        for d, n, fwd, wt, half_off in self._pk_launches:
-            ops.pack_weight_blocks(self.flat_param, fwd, n, d, self.flat_wpk[half_off:])
-            ops.pack_weight_blocks(self.flat_param, fwd, n, d, self.flat_wpk[2 * self._wt_total + half_off:], transposed=True)
-        self._wt_versions = [p._version for p in self._wt_params]
-        self._refresh_traj()
-        if not getattr(self, "_wt_registered", False):
-            owner = weakref.ref(self)
-            for key, off, d, pi in self._wt_blocks:
-                _WT_BLOCKS[key] = (owner, off, d, pi)   # no tensor references: a dead optimizer's entries are inert
-            self._wt_registered = True
-
-    def traj_planes(self, W: Tensor, row0: int, rows: int):
-        """Address of the trajectory-kernel planes (ops.pack_weight_traj layout) of rows [row0, row0 + rows) of parameter W, which lives
-        in this optimizer's flat buffer; registers the slice on first use and repacks all registered slices."""
-        src = (W.data_ptr() - self.flat_param.data_ptr()) // 4 + row0 * 256
-        if src < 0 or src + rows * 256 > self.flat_param.numel() or rows % 16:
-            return None
-        reg = self.__dict__.setdefault("_traj_reg", {"index": {}, "src": [], "rows": [], "dst": [], "halfs": 0, "planes": None, "dev": None})
-        at = reg["index"].get((src, rows))
-        if at is None:
-            at = reg["halfs"]
-            reg["index"][(src, rows)] = at
-            reg["src"].append(src); reg["rows"].append(rows); reg["dst"].append(at)
-            reg["halfs"] += rows * 256 * 2
-            reg["planes"] = None   # (re)allocated and repacked below
-        if reg["planes"] is None:
-            dev = self.flat_param.device
-            reg["planes"] = torch.empty(reg["halfs"], dtype=torch.float16, device=dev)
-            reg["dev"] = (torch.tensor(reg["src"], dtype=torch.int64, device=dev), torch.tensor(reg["rows"], dtype=torch.int32, device=dev),
-                          torch.tensor(reg["dst"], dtype=torch.int64, device=dev))
-            self._refresh_traj()
-        return reg["planes"].data_ptr() + 2 * at
-
-    def _refresh_traj(self) -> None:
-        reg = self.__dict__.get("_traj_reg")
-        if reg and reg["planes"] is not None:
-            s, r, d = reg["dev"]
-            ops.pack_weight_traj_multi(self.flat_param, s, r, d, max(reg["rows"]), reg["planes"])
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.flat_grad.zero_()
-        at = 0
-        for p in self.param_groups[0]["params"]:  # keep .grad aliased to the flat buffer
-            k = p.numel()
-            if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * at:
-                p.grad = self.flat_grad[at : at + k].view(p.shape)
-            at += k
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        g = self.param_groups[0]
-        self._step += 1
-        ops.adamw_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
-                       g["eps"], g["weight_decay"], self._step)
-        self.refresh_transposes()
-
-    @torch.no_grad()
-    def step_from_device_hyper(self, hyper7: Tensor) -> None:
-        """The update with its scalars read from device memory (``hyper_for_step``): what a captured graph replays.
-        Does NOT advance ``_step`` - the caller that fills ``hyper7`` does."""
-        ops.adamw_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, hyper7)
-        self.refresh_transposes()
-
-    def hyper_for_step(self, step: int, out) -> None:
-        """The seven scalars of update number ``step`` at the CURRENT lr / betas of the param group -> ``out`` (7 floats)."""
-        g = self.param_groups[0]
-        ops.adamw_hyper(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], step, out)
-
-    def state_dict(self):
-        for p in self.param_groups[0]["params"]:   # torch AdamW's per-parameter step counters, all equal here
-            self.state[p]["step"] = torch.tensor(float(self._step))
-        return super().state_dict()
-
-    def load_state_dict(self, state_dict):
-        views = {id(p): (self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in self.param_groups[0]["params"]}
-        super().load_state_dict(state_dict)
-        steps = []
-        for p in self.param_groups[0]["params"]:
-            st = self.state[p]
-            m, v = views[id(p)]
-            m.copy_(st["exp_avg"]); v.copy_(st["exp_avg_sq"])
-            st["exp_avg"], st["exp_avg_sq"] = m, v
-            steps.append(int(float(st["step"])))
-        self._step = max(steps) if steps else 0
 
 
 def broadcast_parameters(optimizer: FusedAdamW, model=None, src: int = 0, group=None) -> None:

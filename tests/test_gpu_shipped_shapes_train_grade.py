@@ -69,11 +69,14 @@ EDGES = [_ctx("edge", s) for s in [
     (256, 10, 15, 20), (256, 10, 16, 20),                         # M = 16 / 17: the last trajectory-owning forward, the first row chain
     (512, 10, 311, 22),                                           # the per-operation route
     (64, 16, 10, 20)]]                                            # d % 128 != 0: ungrouped weight gradients
+# the route each edge's comment names (training.TrainRoute: stack, embed_head, traj_layers); the head launch needs d = 256 only
+EDGE_ROUTES = [("chains", False, False)] * 4 + [("chains", True, True), ("chains", True, False), ("per_op", False, False), ("chains", False, False)]
 DROPOUT = [_ctx("dropout", s) for s in [(128, 10, 311, 20), (512, 10, 311, 20), (256, 10, 40, 20)]]
+DROPOUT_ROUTES = [("chains", False, False), ("per_op", False, False), ("chains", True, False)]   # 41 memory rows: row chains behind the head
 DROPOUT_P = 0.1
 
 # fused layer stacks a step runs once a FusedAdamW keeps split weight planes (training._fused_stack): the decoder and every sequence
-# encoder of the config; none at hidden_dim 512 (training._fused_ok)
+# encoder of the config; none at hidden_dim 512 (training.train_route)
 FULL_STACKS = {"default": 4, "sim_scratch": 3, "larger_model": 0}
 # the blocks that are zero by construction are the attention count of the config (key bias of each): decoder layers x 2 + encoder layers
 ZERO_COUNT = {"default": 14, "larger_model": 28, "sim_scratch": 18}
@@ -105,10 +108,20 @@ ROUTE_FACTOR = {
 }
 
 
+def _route(case, fused):
+    """training.train_route for the decoder of a case (the shipped configs have dim_feedforward = hidden_dim and fp32 weights; a FusedAdamW -
+    `fused` - keeps every kind of plane).  The full models' memories have 41 / 302 rows: any count above 16 routes alike."""
+    from soccerdiffusion_amd import training
+
+    return training.train_route(decoder=True, d=case.d, heads=HEADS, T=case.T, M=41 if case.kind == "full" else case.Mc + 1, J=case.J,
+                                ffn_is_d=True, params_ok=True, block_planes=fused, traj_planes=fused, x_differentiable=False)
+
+
 def _family(case, fused):
-    if case.d == 512 or not fused:
+    route = _route(case, fused)
+    if route.stack == "per_op":
         route = f"per-operation {case.d}"
-    elif case.d == 256 and case.kind != "full" and case.Mc + 1 <= 16:
+    elif route.traj_layers:
         route = "trajectory forward 256"
     else:
         route = f"row chains {case.d}"
@@ -337,6 +350,9 @@ def test_full_model_step_is_fp32_grade(case, fused):
     the database's 22 (_PatchEmbed), with the fused row chains and on the per-operation nodes."""
     m, pred, loss, grads, stacks, layers = _gpu_step(case, fused)
     assert (stacks, layers) == (FULL_STACKS[case.config] if fused else 0, 0)
+    # row chains at 128 / 256, entered through the head launch at 256 x 20 joints; per-operation at 512 and without planes
+    chains = fused and case.config != "larger_model"
+    assert _route(case, fused) == (("chains", case.d == 256 and case.J == 20, False) if chains else ("per_op", False, False))
     _gate(case, fused, (pred, loss, grads), *_references(case))
 
 
@@ -348,6 +364,7 @@ def test_decoder_pretraining_step_is_fp32_grade(case, fused):
     its query side has no gradient."""
     m, pred, loss, grads, stacks, layers = _gpu_step(case, fused)
     assert (stacks, layers) == ((1, case.L) if fused else (0, 0))
+    assert _route(case, fused) == (("chains", case.J == 20, True) if fused else ("per_op", False, False))   # the head launch: J % 4 == 0
     _gate(case, fused, (pred, loss, grads), *_references(case))
 
 
@@ -359,6 +376,7 @@ def test_route_edges_are_fp32_grade(case):
     m, pred, loss, grads, stacks, layers = _gpu_step(case, True)
     assert stacks == (0 if case.d == 512 else 1)
     assert layers == (case.L if case.d == 256 and case.Mc + 1 <= 16 else 0)
+    assert _route(case, True) == EDGE_ROUTES[EDGES.index(case)]
     _gate(case, True, (pred, loss, grads), *_references(case))
 
 
@@ -371,6 +389,7 @@ def test_step_with_dropout_is_fp32_grade_under_the_same_masks(case):
 
     m, pred, loss, grads, stacks, layers = _gpu_step(case, True, p=DROPOUT_P)
     assert (stacks, layers) == (0 if case.d == 512 else 1, 0)
+    assert _route(case, True) == DROPOUT_ROUTES[DROPOUT.index(case)]
     gen = m.diffusion_action_generator
     regenerate = _decoder_masks(ops, gen, gen.dropout.calls, case.B, case.T, case.Mc + 1, case.d, HEADS)
     seen = {}

@@ -201,6 +201,97 @@ def test_optimizer_keeps_split_planes_current(ops):
     assert tr._packed_weight(W) is not None
 
 
+def _planes_answer(ops, tr, W, opt):
+    """_packed_weight of W and of its W[d:] slice resolves into ``opt``'s own plane buffer, and a 5-row probe through those planes
+    matches fp64 at the bar of the plane tests above."""
+    d = W.shape[1]
+    lo = opt.flat_wpk.data_ptr()
+    probe = _rand(5, d, seed=7).cuda()
+    for Wv in (W, W[d:]):
+        wpk = tr._packed_weight(Wv)
+        assert wpk is not None and lo <= wpk < lo + 2 * opt.flat_wpk.numel()
+        got = ops.linear_packed(probe, wpk, Wv.shape[0], None)
+        assert rel_err(got, probe.double().cpu() @ Wv.detach().double().cpu().t()) < 1e-5
+
+
+def test_each_live_optimizer_answers_for_its_own_weights_and_a_collected_one_for_none(ops):
+    """Lookups go from a tensor's address to the live store whose flat buffer contains it (optim.planes_of): nothing is keyed by block
+    address process-wide, so a collected optimizer answers nothing and a new one answers for itself from its first refresh - whether or
+    not its buffer landed where a dead one's was."""
+    import gc
+
+    from soccerdiffusion_amd import training as tr
+
+    d = 64
+
+    def matrix(seed):
+        return torch.nn.Parameter(_rand(3 * d, d, seed=seed, scale=0.1).cuda())
+
+    W1, W2 = matrix(1), matrix(2)
+    o1, o2 = tr.FusedAdamW([W1], lr=1e-2), tr.FusedAdamW([W2], lr=1e-2)
+    _planes_answer(ops, tr, W1, o1)
+    _planes_answer(ops, tr, W2, o2)
+    del o2
+    gc.collect()
+    assert tr._packed_weight(W2) is None and tr._packed_weight(W2[d:]) is None and tr._packed_weight(W2, 1, transposed=True) is None
+    _planes_answer(ops, tr, W1, o1)
+    del W2   # its flat buffer may be recycled for the next optimizer's, or not
+    W3 = matrix(3)
+    o3 = tr.FusedAdamW([W3], lr=1e-2)
+    _planes_answer(ops, tr, W3, o3)
+    _planes_answer(ops, tr, W1, o1)
+
+
+def test_trajectory_planes_keep_their_addresses_over_steps_and_a_growth_is_followed(ops, monkeypatch):
+    """The trajectory-order planes of a decoder stack (WeightPlanes.traj_planes: all slices of the stack in one request): registered by
+    the first forward, at the same addresses after optimizer steps that repack them, and - when one more slice registers and the buffer
+    grows - resolved anew by the next forward.  The prediction is held to the row-chain route (SD_TRAIN_TRAJ=0) on the same weights at
+    the bar of test_trajectory_layer_forward_equals_the_row_chain_path."""
+    from soccerdiffusion_amd import training as tr
+    from soccerdiffusion_amd.synthetic import synthetic_state_dict
+    from test_gpu_model import _build
+
+    d, J, L, B, T, Mc = 256, 20, 2, 2, 10, 3
+    g = torch.Generator().manual_seed(13)
+    x_t, ctx, t = torch.randn(B, T, J, generator=g).cuda(), [torch.randn(B, Mc, d, generator=g).cuda()], torch.randint(0, 1000, (B,), generator=g).cuda()
+    m = _build(dict(d=d, J=J, L=L, T=T), full=False).set_dropout(0.0).cuda()
+    m.load_state_dict(synthetic_state_dict(d, J, L, seed=8))
+    m.train()
+    opt = m._opt = tr.FusedAdamW(m.parameters(), lr=1e-3)
+    store, layers = opt.planes, list(m.diffusion_action_generator.transformer_decoder.layers)
+    slices = list(tr._traj_slices(layers, tr.TrainRoute("chains", True, True)).values())
+    assert len(slices) == 6 * L   # layer 0's in-projection for the head, five matrices per layer, the successors' in-projections
+
+    def forward(traj):
+        monkeypatch.setenv("SD_TRAIN_TRAJ", traj)
+        before = tr.TRAJ_LAYERS[0]
+        pred = m.forward_with_context(ctx, x_t, t).detach()
+        assert tr.TRAJ_LAYERS[0] - before == (L if traj == "1" else 0)
+        return pred
+
+    def check():
+        got = forward("1")
+        assert rel_err(got, forward("0")) < 2e-6
+        return got
+
+    assert not store.traj_at
+    first = check()
+    assert len(store.traj_at) == len(slices)
+    addrs = store.traj_planes(slices)
+    assert len(set(addrs)) == len(slices) and len(store.traj_at) == len(slices)
+    for seed in (1, 2):
+        opt.flat_grad.copy_(_rand(opt.flat_grad.numel(), seed=seed).cuda())
+        opt.step()
+    moved = check()
+    assert rel_err(moved, first) > 1e-3                      # (the steps did move the weights)
+    assert store.traj_planes(slices) == addrs and len(store.traj_at) == len(slices)
+    store.traj_planes([(layers[0].multihead_attn.in_proj_weight, d, 2 * d)])   # one more slice, by hand: the buffer grows
+    assert len(store.traj_at) == len(slices) + 1
+    opt.flat_grad.copy_(_rand(opt.flat_grad.numel(), seed=3).cuda())
+    opt.step()                                               # new weights: planes read at a pre-growth address would be the old ones
+    assert rel_err(check(), moved) > 1e-3
+
+
 def _amax_word(t):
     """Device int32 word with the bits of max |t| (what the fused chains leave behind for the grouped GEMM)."""
     w = torch.zeros(64, dtype=torch.int32, device=t.device)    # SD_AMAX_WORDS words, the maximum counts

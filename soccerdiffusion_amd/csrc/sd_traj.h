@@ -61,10 +61,23 @@ static_assert(LDS_SO + TMAX * QROW <= LDS_Q, "Q and O fit the freed half of the 
 static_assert(LDS_BYTES <= 163840 && LDS_P + TMAX * PROW <= LDS_STAT, "LDS budget");
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // A/B switch of the schedule change measured in NOTEBOOK.md, round 6 addendum (0 restores the earlier code; the results are the same bits)
 #ifndef TJ_V_UNDER_SCORES
 #define TJ_V_UNDER_SCORES 1     // mode 3: the V projection's MFMAs under the scores / softmax phase instead of in the Q | K | V projection
+#endif
+// A/B switches of the latency changes measured in NOTEBOOK.md, round 7 addendum (the old value restores the earlier code; same bits)
+#ifndef TJ_EARLY_PARAMS
+#define TJ_EARLY_PARAMS 15      // biases and scales requested a phase ahead of the barrier they used to follow (bits below; 0: where they are consumed)
+#endif
+#define TJ_EARLY_QK 1           //   the Q / K bias behind B1: before the projection GEMM
+#define TJ_EARLY_V 2            //   the V bias behind B3: before the scores / V GEMM phase
+#define TJ_EARLY_XSC 4          //   the cross-attention's scales behind its "before P" barrier: before the score GEMM
+#define TJ_EARLY_FF 8           //   the feed-forward's two scales: with the biases b1 / b2
+#ifndef TJ_PV_SPLIT_UNDER
+#define TJ_PV_SPLIT_UNDER 1     // mode 3's att_pv: the hi / lo split of key pair kp + 1 between the MFMAs of pair kp (0: all pairs up front)
 #endif
 // diagnostic build (-DTJ_STAMPS): every wave of the first TJ_STAMP_WGS workgroups records the shader clock at phase boundaries
 #ifdef TJ_STAMPS
@@ -372,11 +385,11 @@ constexpr long STEP_G_HALFS = 4 * 8 * 2 * 32, STEP_V_HALFS = 2 * 4 * D;
 // probabilities of the context slots are multiplied by m_c = s_v / sc[5], the step token's by m_s = s_v / sc[7] - powers of two <= 1, one of
 // them 1: the kind with the larger values is exact, the other loses only what is below the larger kind's resolution.
 struct StepScale { float c_gs, s_v, m_c, m_s; };
-__device__ __forceinline__ StepScale step_scale(const LayerW &L) {
-    const float s5 = L.sc[5], s7 = L.sc[7];
+__device__ __forceinline__ StepScale step_scale(float s5, float s6, float s7) {
     const float sv = fminf(s5, s7);
-    return StepScale{1.0f / (ACT * L.sc[6]), sv, sv / s5, sv / s7};
+    return StepScale{1.0f / (ACT * s6), sv, sv / s5, sv / s7};
 }
+__device__ __forceinline__ StepScale step_scale(const LayerW &L) { return step_scale(L.sc[5], L.sc[6], L.sc[7]); }
 
 // ---------------------------------------------------------------------------------------------------
 // One whole denoiser step of the sampler per launch: x -> embedding + positional rows -> L decoder layers -> fc_out -> DDIM update
@@ -833,6 +846,8 @@ static __device__ __forceinline__ void att_scores(const Ctx &c, const SaW &a, co
 }
 // att_pv: O^T = V^T P^T with P^T straight from the score accumulators, V^T through transposing LDS reads; O / psum -> LDS planes
 // rows_out (training): the attention output of this head also goes to HBM, [token][ld] at the head's 64 columns (unscaled); amax: running max |.| of it
+// SPLIT_UNDER: the hi / lo split of P runs between the MFMAs instead of in front of them (mode 3, where it was measured)
+template <bool SPLIT_UNDER = false>
 static __device__ __forceinline__ void att_pv(const Ctx &c, const f32x4 (&S)[NTT], float psum, const char *Vb, char *Ob, float *rows_out = nullptr,
                                               int ld = 0, float *amax = nullptr) {
     const int w = c.w, g = c.g, t = c.t;
@@ -841,31 +856,86 @@ static __device__ __forceinline__ void att_pv(const Ctx &c, const f32x4 (&S)[NTT
     for (int ft = 0; ft < 4; ++ft) O[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int q4 = t >> 2, p4 = t & 3;
     // 16 steps (key pair kp, feature tile ft) of three MFMAs; the V^T fragments (four transposing reads) come three steps ahead
-    f16x8 ph[NKP], pl[NKP];
+    const auto vload = [&](int s, f16x8 (&vf)[4][2]) __attribute__((always_inline)) {
+        const int kp = s >> 2, ft = s & 3;
+        const int r0 = min(32 * kp + 4 * g + q4, c.T - 1), r1 = min(32 * kp + 16 + 4 * g + q4, c.T - 1);
+        const char *v0 = Vb + r0 * VROW + 8 * p4, *v1 = Vb + r1 * VROW + 8 * p4;
 #pragma unroll
-    for (int kp = 0; kp < NKP; ++kp) {
-        // P fragment of keys 32 kp ..: elements 0..3 = tile 2 kp, 4..7 = tile 2 kp + 1 (beyond the last tile: zero)
-        const f32x4 pa4 = S[2 * kp], pb4 = 2 * kp + 1 < NTT ? S[2 * kp + 1 < NTT ? 2 * kp + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
-        f16x4 pah, pal, pbh, pbl;
-        split4(pa4, pah, pal);
-        split4(pb4, pbh, pbl);
-        ph[kp] = __builtin_shufflevector(pah, pbh, 0, 1, 2, 3, 4, 5, 6, 7);
-        pl[kp] = __builtin_shufflevector(pal, pbl, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    f16x8 vf[4][2];
-    ring_pipe<4 * NKP, 4>(
-        [&](int s) __attribute__((always_inline)) {
-            const int kp = s >> 2, ft = s & 3;
-            const int r0 = min(32 * kp + 4 * g + q4, c.T - 1), r1 = min(32 * kp + 16 + 4 * g + q4, c.T - 1);
-            const char *v0 = Vb + r0 * VROW + 8 * p4, *v1 = Vb + r1 * VROW + 8 * p4;
-#pragma unroll
-            for (int pn = 0; pn < 2; ++pn) {
-                const s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v0 + pn * 128 + ft * 32));
-                const s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v1 + pn * 128 + ft * 32));
-                vf[s & 3][pn] = __builtin_shufflevector(__builtin_bit_cast(f16x4, x0), __builtin_bit_cast(f16x4, x1), 0, 1, 2, 3, 4, 5, 6, 7);
+        for (int pn = 0; pn < 2; ++pn) {
+            const s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v0 + pn * 128 + ft * 32));
+            const s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v1 + pn * 128 + ft * 32));
+            vf[s & 3][pn] = __builtin_shufflevector(__builtin_bit_cast(f16x4, x0), __builtin_bit_cast(f16x4, x1), 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+    };
+    if constexpr (SPLIT_UNDER) {
+        f16x8 vf[4][2];
+        // P fragment of keys 32 kp ..: elements 0..3 = tile 2 kp, 4..7 = tile 2 kp + 1 (beyond the last tile: zero), as hi / lo planes.  Only
+        // pair 0 is split up front; a quarter of pair kp + 1 (two probabilities: six vector instructions) follows each of the four MFMA groups
+        // of pair kp, two instructions behind each MFMA - plain fp32 / convert instructions beside a wave's own MFMAs are nearly free up to
+        // that rate (profiles/r03_mfma_valu_overlap.txt).  Same conversions per element as split4: the same bits.
+        unsigned ph[2][4], pl[2][4];   // [kp & 1][quarter]: two fp16 each
+        const auto psplit = [&](int kp, int q) __attribute__((always_inline)) {
+            const int kt = 2 * kp + (q >> 1);
+            f16x2 h = {0, 0}, l = {0, 0};
+            if (kt < NTT) {
+                const f32x2 x = {S[kt < NTT ? kt : 0][2 * (q & 1)], S[kt < NTT ? kt : 0][2 * (q & 1) + 1]};
+                h = __builtin_convertvector(x, f16x2);
+                l = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), f16x2);
             }
-        },
-        [&](int s) __attribute__((always_inline)) { mma3<S_PV>(O[s & 3], vf[s & 3][0], vf[s & 3][1], ph[s >> 2], pl[s >> 2]); });
+            ph[kp & 1][q] = __builtin_bit_cast(unsigned, h);
+            pl[kp & 1][q] = __builtin_bit_cast(unsigned, l);
+            // (the values exist HERE: without this hipcc computes the lo parts of a whole pair in front of the pair's first MFMA)
+            if (kt < NTT) asm volatile("" : "+v"(ph[kp & 1][q]), "+v"(pl[kp & 1][q]));
+        };
+        const auto pfrag = [](const unsigned (&p)[4]) __attribute__((always_inline)) { return __builtin_bit_cast(f16x8, u32x4{p[0], p[1], p[2], p[3]}); };
+#pragma unroll
+        for (int q = 0; q < 4; ++q) psplit(0, q);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) vload(s, vf);
+#pragma unroll
+        for (int s = 0; s < 4 * NKP; ++s) {
+            const int kp = s >> 2;
+            if (s + 3 < 4 * NKP) vload(s + 3, vf);
+            __builtin_amdgcn_sched_barrier(0);
+            mma3<S_PV>(O[s & 3], vf[s & 3][0], vf[s & 3][1], pfrag(ph[kp & 1]), pfrag(pl[kp & 1]));
+            if (kp + 1 < NKP) {
+                psplit(kp + 1, s & 3);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {   // MFMA, two vector instructions, three times
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+        // 16 steps (key pair kp, feature tile ft) of three MFMAs; the V^T fragments (four transposing reads) come three steps ahead
+        f16x8 ph[NKP], pl[NKP];
+#pragma unroll
+        for (int kp = 0; kp < NKP; ++kp) {
+            // P fragment of keys 32 kp ..: elements 0..3 = tile 2 kp, 4..7 = tile 2 kp + 1 (beyond the last tile: zero)
+            const f32x4 pa4 = S[2 * kp], pb4 = 2 * kp + 1 < NTT ? S[2 * kp + 1 < NTT ? 2 * kp + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
+            f16x4 pah, pal, pbh, pbl;
+            split4(pa4, pah, pal);
+            split4(pb4, pbh, pbl);
+            ph[kp] = __builtin_shufflevector(pah, pbh, 0, 1, 2, 3, 4, 5, 6, 7);
+            pl[kp] = __builtin_shufflevector(pal, pbl, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        f16x8 vf[4][2];
+        ring_pipe<4 * NKP, 4>(
+            [&](int s) __attribute__((always_inline)) {
+                const int kp = s >> 2, ft = s & 3;
+                const int r0 = min(32 * kp + 4 * g + q4, c.T - 1), r1 = min(32 * kp + 16 + 4 * g + q4, c.T - 1);
+                const char *v0 = Vb + r0 * VROW + 8 * p4, *v1 = Vb + r1 * VROW + 8 * p4;
+#pragma unroll
+                for (int pn = 0; pn < 2; ++pn) {
+                    const s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v0 + pn * 128 + ft * 32));
+                    const s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(v1 + pn * 128 + ft * 32));
+                    vf[s & 3][pn] = __builtin_shufflevector(__builtin_bit_cast(f16x4, x0), __builtin_bit_cast(f16x4, x1), 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+            },
+            [&](int s) __attribute__((always_inline)) { mma3<S_PV>(O[s & 3], vf[s & 3][0], vf[s & 3][1], ph[s >> 2], pl[s >> 2]); });
+    }
     // O^T tile ft: features 16 ft + 4 g + r of query 16 w + t, times ACT / sum -> LDS planes
     const float inv = 1.0f / psum;
     const int tok = 16 * w + t;
@@ -917,7 +987,9 @@ static __device__ __forceinline__ void unscale_h(f32x4 (&H)[2][NTT], float f, co
 // both planes, i.e. the whole X panel, which leaves TWO buffers for the four images of a head: Q, later O, in LDS_Q; K, later V, in
 // LDS_K.  Five barriers per head, every wave in the same phase (the fast variant's two-barrier, complementary-job structure needs
 // the 51 KB that the second plane occupies) - except between B2 and B3, where a wave has two jobs, the scores of its query tile and the
-// V projection of its token half, and the two waves of a SIMD take them in opposite order.
+// V projection of its token half, and the two waves of a SIMD take them in opposite order.  What a phase needs from L2 right behind its
+// barrier is requested a phase ahead (the Q | K bias before the projection GEMM, the V bias after B2): a workgroup is alone on its CU
+// and nothing else hides those round trips (NOTEBOOK.md, round 7 addendum).
 // ---------------------------------------------------------------------------------------------------
 static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW &a, int h, f32x4 (&H)[2][NTT]) {
     const Ctx c = ctx_local(c0);
@@ -926,6 +998,12 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     HeadAcc acc;
     head_zero(acc);
     if (h == 1) TJ_STAMP(17);   // (diagnostic build: the phases of head 1)
+    const int w3 = w & 3;
+#if TJ_EARLY_PARAMS & TJ_EARLY_QK
+    // the Q / K bias of the write phase behind B1: requested here, its round trip passes under the projection GEMM
+    f32x4 bqk = *reinterpret_cast<const f32x4 *>(a.b_in + (w < 4 ? 0 : D) + HD * h + 16 * w3 + 4 * g);
+    __builtin_amdgcn_sched_barrier(0);
+#endif
     {
         const int nt0 = (w < 4 ? 0 : 16) + 4 * h + (w & 3);     // Q tile (waves 0..3) or K tile (waves 4..7)
         const f16 *pa0 = a.w_in + (long)nt0 * (8 * 2 * 512);
@@ -956,8 +1034,11 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     if (h == 1) TJ_STAMP(18);
     TJ_SYNC(2);            // B1: the previous head's readers of Q / O and K / V are done
     {   // Q or K tile -> LDS planes (features 16 (w & 3) + 4 g + r of the head, natural order on both operands of the scores)
-        const int w3 = w & 3;
+#if TJ_EARLY_PARAMS & TJ_EARLY_QK
+        const f32x4 bv = bqk * ACT;
+#else
         const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.b_in + (w < 4 ? 0 : D) + HD * h + 16 * w3 + 4 * g) * ACT;
+#endif
         char *dst = w < 4 ? Qb : Kb;
         const int chunk = (2 * (w3 & 1) + (g >> 1)) | ((w3 >> 1) << 3);
 #pragma unroll
@@ -972,6 +1053,11 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     TJ_SYNC(2);            // B2: Q, K complete
     f32x4 S[NTT];
     float psum = 1.f;
+#if TJ_EARLY_PARAMS & TJ_EARLY_V
+    // the V bias of the write phase behind B3: its round trip passes under the scores / V GEMM phase
+    f32x4 bvv = *reinterpret_cast<const f32x4 *>(a.b_in + 2 * D + HD * h + 16 * (w >> 1) + 4 * g);
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 #if TJ_V_UNDER_SCORES
     // The V projection of this wave's token half (same k order and product order as inside the projection: acc.a1 has the same bits)
     // shares the phase with the scores: the two waves of a SIMD (w, w + 4) take the jobs in opposite order, so that one's MFMAs
@@ -997,7 +1083,11 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     if (h == 1) TJ_STAMP(20);
     TJ_SYNC(3);            // B3: K is dead
     {   // V piece -> rows [token][hi 64 | lo 64] (features 16 (w >> 1) + 4 g + r) over K
+#if TJ_EARLY_PARAMS & TJ_EARLY_V
+        const f32x4 bv = bvv * ACT;
+#else
         const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.b_in + 2 * D + HD * h + 16 * (w >> 1) + 4 * g) * ACT;
+#endif
         const int tt1 = (w & 1) ? NH0 : 0, n1 = (w & 1) ? NTT - NH0 : NH0;
 #pragma unroll
         for (int i = 0; i < NH0; ++i) {
@@ -1011,7 +1101,7 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     if (h == 1) TJ_STAMP(21);
     TJ_SYNC(3);            // B4: V complete (every wave has read its Q fragments: O may overwrite Q)
     AK64 wo;
-    if (w < NTT) att_pv(ctx_local(c0), S, psum, Kb, Qb);
+    if (w < NTT) att_pv<(TJ_PV_SPLIT_UNDER != 0)>(ctx_local(c0), S, psum, Kb, Qb);
     // the out-projection's weight fragments: their L2 round trip passes under the barrier
     head_out_load(c, a, h, wo);
     if (h == 1) TJ_STAMP(22);
@@ -1248,6 +1338,14 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
     // Lanes of slot Mc read the step token's shared row instead of their trajectory's block.
     LnAffine aff2;
     ln_affine_load(c0, L.n2_w, L.n2_b, aff2);
+#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
+    // The four scales of the cross-attention's softmax (used behind its "before P" barrier) as well: wave-uniform, so they wait in scalar
+    // registers from the end of LayerNorm 2 on - the score phase is where the kernel's vector registers peak.
+    float sc4 = 0.f, sc5 = 0.f, sc6 = 0.f, sc7 = 0.f;
+    if constexpr (!WIDE) {
+        sc4 = L.sc[4], sc5 = L.sc[5], sc6 = L.sc[6], sc7 = L.sc[7];
+    }
+#endif
     f16x8 gfr[8][2];
     if constexpr (!WIDE) {
         const int hh = c0.w >> 1, Mc = Mk - 1;
@@ -1278,6 +1376,10 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         // The score biases, the step token's value columns and the folded values of this trajectory (48 registers, HBM) are requested before
         // the score GEMM: an HBM round trip under load is longer than the softmax, and a load consumed before an older one has returned
         // waits for that one too (loads return in order).
+#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
+        const auto uni = [](float v) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+        sc4 = uni(sc4), sc5 = uni(sc5), sc6 = uni(sc6), sc7 = uni(sc7);
+#endif
         f32x4 cbv = *reinterpret_cast<const f32x4 *>(L.cb + traj * 64 + hh * 16 + 4 * c.g);
         const float cs = L.cstep[sblk * 4 + hh];
         __builtin_amdgcn_sched_barrier(0);
@@ -1317,8 +1419,13 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         // softmax over the Mk key slots (accumulator rows 4 g + r) of each token (lane column)
         // the step token's slot carries the scales of the step blocks (sc[6], sc[7]): a score multiplier of its own, and both kinds of
         // probability are brought to the common value scale s_v = min(sc[5], sc[7]) (step_scale)
+#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
+        const float c_g = 1.0f / (ACT * sc4);
+        const StepScale ss = step_scale(sc5, sc6, sc7);
+#else
         const float c_g = 1.0f / (ACT * L.sc[4]);
         const StepScale ss = step_scale(L);
+#endif
         f32x4 cg4 = {c_g, c_g, c_g, c_g};
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1385,10 +1492,18 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) U[a][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#if TJ_EARLY_PARAMS & TJ_EARLY_FF
+        const float sc1 = L.sc[1];   // with b1: both land under the W1 GEMM
+#endif
         const Bias2 b1 = bias_load(c, L.b_1);
         gemm_x2<S_W1>(c, U, L.w_1);
         TJ_STAMP(36);
+#if TJ_EARLY_PARAMS & TJ_EARLY_FF
+        const float c1 = 1.0f / (ACT * sc1);
+        const float sc2 = L.sc[2];   // with b2
+#else
         const float c1 = 1.0f / (ACT * L.sc[1]);
+#endif
         const Bias2 b2 = bias_load(c, L.b_2);   // lands under the GELU
         TJ_SYNC(6);   // every wave has read LN3(h): the panel receives gelu(u)
 #pragma unroll
@@ -1405,7 +1520,11 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         }
         TJ_SYNC(7);
         TJ_STAMP(37);
+#if TJ_EARLY_PARAMS & TJ_EARLY_FF
+        const float up = ACT * sc2;
+#else
         const float up = ACT * L.sc[2];
+#endif
         scale_h(H, up);
         gemm_x2<S_W2>(c, H, L.w_2);
         unscale_h(H, 1.0f / up, b2);

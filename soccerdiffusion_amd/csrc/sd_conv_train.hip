@@ -387,11 +387,6 @@ struct WgradArgs {
     int rows_per_item;   // output image rows per work item
     int n_row_items;     // ceil(N * Ho / rows_per_item)
 };
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
     const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;

@@ -45,26 +45,6 @@ __global__ void f16_absmax_kernel(const float *__restrict__ x, long n, unsigned 
     if ((threadIdx.x & 63) == 0 && b > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, b);
 }
 
-// rows of [G (D) | V' (D)]: separate maxima
-__global__ void f16_absmax_gv_kernel(const float *__restrict__ gv, long rows, int D, unsigned *outG, unsigned *outV) {
-    float mg = 0.f, mv = 0.f;
-    const long n = rows * 2 * D;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float a = fabsf(gv[i]);
-        if ((i % (2 * D)) < D) mg = fmaxf(mg, a);
-        else mv = fmaxf(mv, a);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        mv = fmaxf(mv, __shfl_xor(mv, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(outG, __builtin_bit_cast(unsigned, mg));
-        atomicMax(outV, __builtin_bit_cast(unsigned, mv));
-    }
-}
-
 // W (N x D, row-major fp32, N a multiple of D) -> fragment-major split planes
 //   dst[pass = n / D][wn][ks][tn][plane][lane][8],  n = pass*D + wn*WN + tn*32 + (lane & 31),  k = ks*16 + 8*(lane >> 5) + e
 template <int D>
@@ -465,7 +445,7 @@ struct F16LayerArgs {
     const f16 *g16, *v16;                     // this layer: per (trajectory, head) blocks of 32*D halfs
     const f16 *gstep, *vstep;                 // this layer and step: 4 head blocks / one block
     const float *cstep;                       // 4 score biases of the step token
-    int qkv_head_major;                       // layout of g.b.qkv (f16_store_qkv) - what attention_f16_head_kernel reads
+    int qkv_head_major;                       // layout of g.b.qkv (f16_store_qkv) - what attention_f16_head_lv_kernel reads
     int h_frag;                               // g.a.h is in accumulator order (f16_load_h / f16_store_h)
     int next_head;                            // last layer only: go on with the NEXT step's head on the updated x (head.g.x unused)
     F16HeadArgs head;
@@ -886,415 +866,24 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_head_f16_kern
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Self-attention of the sampler on the fp16 pipe (head dim 64, T <= 128).  Same structure as attention_pipe_kernel:
-// one workgroup per sample streams (head, 64-key chunk) units, wave w owns queries 32w..32w+31, S^T = K Q^T so that a
-// query is a lane column and P^T is the B operand of O^T = V^T P^T straight from the accumulator.  K and V are split
-// into fp16 pairs when a chunk is staged (K rows as they are, V transposed: the A operand of O^T needs 8 keys of one
-// feature per lane), Q when a head's fragments are fetched, P after the exponentials.  With the k-slot order of a
-// 16-key group defined as {4*half + 0..3, 8 + 4*half + 0..3}, a lane's 8 consecutive accumulator registers ARE its
-// B fragment, and the matching V^T fragment is two 8-byte LDS reads.
+// Self-attention of the sampler on the fp16 pipe (head dim 64, T <= 128): one workgroup per (sample, head), wave w owns queries
+// 32w..32w+31, S^T = K Q^T so that a query is a lane column and P^T is the B operand of O^T = V^T P^T straight from the
+// accumulator.  All T keys of the head are staged at once - one HBM round trip for the workgroup - and the softmax is a single pass
+// over 4 score tiles.  K and V are split into fp16 pairs when they are staged (K rows as they are, V transposed: the A operand of
+// O^T needs 8 keys of one feature per lane), Q when its fragments are fetched, P after the exponentials.  With the k-slot order of
+// a 16-key group defined as {4*half + 0..3, 8 + 4*half + 0..3}, a lane's 8 consecutive accumulator registers ARE its B fragment,
+// and the matching V^T fragment is two 8-byte LDS reads.
+// V^T is staged into K's LDS after the scores (one more barrier pair): 34 KB of LDS instead of 68, so 3-4 workgroups per CU
+// instead of 2 keep the HBM queues fed while others compute.
 // ---------------------------------------------------------------------------------------------------
 constexpr float F16_QKV_SCALE = 8.0f;
-#ifndef SD_ATT16_WGS
-#define SD_ATT16_WGS 2
-#endif
-constexpr int ATT16_PITCH = 136;   // halfs per LDS row: {hi[64], lo[64]} + 8 (272 B: 16 rows hit 16 distinct 4-bank groups)
-
-__global__ __launch_bounds__(256, SD_ATT16_WGS) void attention_f16_kernel(const float *__restrict__ qkv, int ld, float *__restrict__ out, int ldo,
-                                                              int T, int heads, float scale_log2e) {
-    constexpr int HD = 64, KC = 64;
-    __shared__ __attribute__((aligned(16))) f16 sK[KC * ATT16_PITCH];
-    __shared__ __attribute__((aligned(16))) f16 sV[HD * ATT16_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int b = blockIdx.x, D = heads * HD;
-    const int nchunks = (T + KC - 1) / KC, nunits = heads * nchunks;
-    const int qi = wave * 32 + l31;
-    const bool wave_active = wave * 32 < T, q_ok = qi < T;
-    const float *base = qkv + (long)b * T * ld;   // workgroup-uniform: scalar base, 32-bit offsets below
-    const float c_s = scale_log2e / (F16_QKV_SCALE * F16_QKV_SCALE);          // raw S^T accumulator -> log2-domain score
-    const float c_o = 1.0f / F16_QKV_SCALE;                                   // P carries its 2^10 into the row sum as well
-
-    // staging: K pieces (key = idx / 16, 4 features) keep rows contiguous; V pieces put the 64 keys on the lanes so that
-    // the transposed 2-byte LDS writes of one instruction are contiguous.  Inside a 16-key group V^T stores key k at
-    // position (k&3) + 4*((k>>3)&1) + 8*((k>>2)&1): the 8 k-slots of a lane half are then one 16-byte read.
-    unsigned koff[4], voff[4];   // global offsets (floats) of this thread's pieces relative to (chunk, head)
-    int klds[4], vlds[4], krow[4], vrow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + 256 * i;
-        krow[i] = idx >> 4;
-        const int kc4 = idx & 15;
-        vrow[i] = idx & 63;
-        const int vc4 = idx >> 6;
-        koff[i] = (unsigned)(krow[i] * ld + kc4 * 4);
-        voff[i] = (unsigned)(vrow[i] * ld + vc4 * 4);
-        klds[i] = krow[i] * ATT16_PITCH + kc4 * 4;
-        const int k16 = vrow[i] & 15;
-        vlds[i] = (vc4 * 4) * ATT16_PITCH + (vrow[i] & ~15) + (k16 & 3) + 4 * ((k16 >> 3) & 1) + 8 * ((k16 >> 2) & 1);
-    }
-    f32x4 kreg[4], vreg[4];
-    auto fetch = [&](int u) {
-        const int h = u / nchunks, kc0 = (u - h * nchunks) * KC;
-        const float *kb = base + (long)kc0 * ld + D + h * HD;   // uniform
-        const int left = T - kc0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, d = a;
-            if (krow[i] < left) a = *reinterpret_cast<const f32x4 *>(kb + koff[i]);
-            if (vrow[i] < left) d = *reinterpret_cast<const f32x4 *>(kb + D + voff[i]);
-            kreg[i] = a;
-            vreg[i] = d;
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f16x4 hh, ll;
-            f16_split4(kreg[i], F16_QKV_SCALE, hh, ll);
-            *reinterpret_cast<f16x4 *>(sK + klds[i]) = hh;
-            *reinterpret_cast<f16x4 *>(sK + klds[i] + HD) = ll;
-            f16_split4(vreg[i], F16_QKV_SCALE, hh, ll);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sV[vlds[i] + e * ATT16_PITCH] = hh[e];
-                sV[vlds[i] + e * ATT16_PITCH + KC] = ll[e];
-            }
-        }
-    };
-    f32x4 qraw[8];
-    f16x8 qf[4][2];
-    const unsigned qoff = (unsigned)((q_ok ? qi : 0) * ld + 8 * half);
-    auto fetch_q = [&](int h) {
-        const float *qb = base + h * HD;   // uniform
-#pragma unroll
-        for (int i = 0; i < 8; ++i) qraw[i] = *reinterpret_cast<const f32x4 *>(qb + qoff + (unsigned)((i >> 1) * 16 + (i & 1) * 4));
-    };
-    fetch(0);
-    fetch_q(0);
-    f32x16 o[2];
-    float m_run = -INFINITY, l_part = 0.f;
-
-    for (int u = 0; u < nunits; ++u) {
-        const int h = u / nchunks, c = u - h * nchunks, kc0 = c * KC;
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 0);
-        __syncthreads();   // every wave is done reading the previous unit's K/V
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 1);
-        stage();
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 2);
-        if (u + 1 < nunits) fetch(u + 1);
-        if (c == 0) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                f16x4 h0, l0, h1, l1;
-                f16_split4(qraw[2 * ks], F16_QKV_SCALE, h0, l0);
-                f16_split4(qraw[2 * ks + 1], F16_QKV_SCALE, h1, l1);
-                qf[ks][0] = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                qf[ks][1] = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-            }
-            m_run = -INFINITY;
-            l_part = 0.f;
-        }
-        if (c == nchunks - 1 && h + 1 < heads) fetch_q(h + 1);
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 3);
-        __syncthreads();
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 4);
-        if (!wave_active) continue;
-        const int n_valid = min(T - kc0, KC);             // keys of this chunk
-        const int kt_valid = (n_valid + 31) / 32;
-        f32x16 sc[2];
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            if (kt < kt_valid) {
-                const f16 *kp = sK + (kt * 32 + l31) * ATT16_PITCH + 8 * half;
-                f16x8 kf[2][2];
-                kf[0][0] = *reinterpret_cast<const f16x8 *>(kp);
-                kf[0][1] = *reinterpret_cast<const f16x8 *>(kp + HD);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    if (ks + 1 < 4) {
-                        kf[(ks + 1) & 1][0] = *reinterpret_cast<const f16x8 *>(kp + (ks + 1) * 16);
-                        kf[(ks + 1) & 1][1] = *reinterpret_cast<const f16x8 *>(kp + HD + (ks + 1) * 16);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ks == 0) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0][1], qf[0][0], zero16, 0, 0, 0);
-                    else sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks & 1][1], qf[ks][0], sc[kt], 0, 0, 0);
-                    sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks & 1][0], qf[ks][1], sc[kt], 0, 0, 0);
-                    sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks & 1][0], qf[ks][0], sc[kt], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                sc[kt] = zero16;
-            }
-        }
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 5);
-        if (n_valid < KC) {   // wave-uniform: only the last chunk of a head has keys to mask
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    if (key >= n_valid) sc[kt][r] = -INFINITY;
-                }
-        }
-        float m_c = sc[0][0];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {   // v_max3_f32: hipcc keeps two v_max_f32 for nested fmaxf
-            if (r == 0) asm("v_max_f32 %0, %1, %2" : "=v"(m_c) : "v"(sc[0][0]), "v"(sc[1][0]));
-            else asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m_c) : "v"(m_c), "v"(sc[0][r]), "v"(sc[1][r]));
-        }
-        m_c = fmaxf(m_c, __shfl_xor(m_c, 32, 64));
-        const float m_new = fmaxf(m_run, m_c);
-        const float mb = m_new * c_s - 10.0f;             // the 2^10 of F16_P_SCALE rides in the exponent
-        float psum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(sc[kt][r] * c_s - mb);
-                sc[kt][r] = pv;
-                psum += pv;
-            }
-        if (c == 0) {   // wave-uniform: first chunk of a head, nothing to rescale
-            l_part = psum;
-        } else {
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c_s);
-            l_part = l_part * alpha + psum;
-#pragma unroll
-            for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[ft][r] *= alpha;
-        }
-        m_run = m_new;
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 6);
-        // O^T += V^T P^T, 16 keys per step: registers 8*j2 .. 8*j2+7 of tile kt are this lane's B fragment
-#pragma unroll
-        for (int gg = 0; gg < 4; ++gg) {
-            const int kt = gg >> 1, j2 = gg & 1;
-            if (kt * 32 + j2 * 16 >= n_valid) break;   // wave-uniform: no live key in this and the later groups
-            f16x8 ph, pl;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float t = sc[kt][8 * j2 + e];
-                ph[e] = (f16)t;
-                pl[e] = (f16)(t - (float)ph[e]);
-            }
-            const f16 *vp = sV + l31 * ATT16_PITCH + kt * 32 + j2 * 16 + 8 * half;
-#pragma unroll
-            for (int ft = 0; ft < 2; ++ft) {
-                const f16x8 vh = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16_PITCH);
-                const f16x8 vl = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16_PITCH + KC);
-                if (c == 0 && gg == 0) o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, zero16, 0, 0, 0);
-                else o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o[ft], 0, 0, 0);
-                o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o[ft], 0, 0, 0);
-                o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o[ft], 0, 0, 0);
-            }
-        }
-        if (u == 2) SD_STAMP(SD_STAMP_ATT_SLOT, 7);
-        if (u == 3) SD_STAMP(SD_STAMP_ATT_SLOT, 8);
-        if (c == nchunks - 1) {
-            const float l_tot = l_part + __shfl_xor(l_part, 32, 64);
-            const float inv = c_o / l_tot;
-            if (q_ok) {
-                float *op = out + ((long)b * T + qi) * ldo + h * HD;
-#pragma unroll
-                for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const f32x4 t = {o[ft][4 * g4] * inv, o[ft][4 * g4 + 1] * inv, o[ft][4 * g4 + 2] * inv, o[ft][4 * g4 + 3] * inv};
-                        *reinterpret_cast<f32x4 *>(op + ft * 32 + 8 * g4 + 4 * half) = t;
-                    }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Same computation, one workgroup per (sample, head): all T <= 128 keys of the head are staged at once, so a
-// workgroup pays one HBM round trip and two barriers in total (the streaming kernel above pays them per 64-key
-// chunk: its (head, chunk) unit took 14 k cycles against 1.5 k of MFMA and 3 k of VALU work - tools/stamps.py),
-// and the softmax is a single pass over 4 score tiles.
-// ---------------------------------------------------------------------------------------------------
-constexpr int ATT16H_KP = 136;   // K rows: {hi[64], lo[64]} + 8 halfs
-constexpr int ATT16H_VP = 264;   // V^T rows: {hi[128 keys], lo[128 keys]} + 8 halfs (528 B = 132 dwords = 4 mod 64)
-constexpr size_t ATT16H_LDS = (size_t)(128 * ATT16H_KP + 64 * ATT16H_VP) * sizeof(f16);
-
-// HM: qkv is the head-major buffer written by f16_store_qkv ([sample][head][q|k|v][token][64]); else [token][3D] rows.
-template <bool HM>
-__global__ __launch_bounds__(256, 2) void attention_f16_head_kernel(const float *__restrict__ qkv, int ld_rm, float *__restrict__ out, int ldo,
-                                                                   int T, int heads, float scale_log2e) {
-    constexpr int HD = 64;
-    extern __shared__ __attribute__((aligned(16))) f16 smem16[];
-    f16 *sK = smem16, *sV = smem16 + 128 * ATT16H_KP;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int b = blockIdx.x / heads, h = blockIdx.x - b * heads, D = heads * HD;
-    const int qi = wave * 32 + l31;
-    const bool q_ok = qi < T;
-    // workgroup-uniform bases of this head's Q, K, V rows and their row stride
-    const int ld = HM ? HD : ld_rm;
-    const float *base = HM ? qkv + (long)blockIdx.x * 3 * T * HD : qkv + (long)b * T * ld_rm + h * HD;
-    const long k_at = HM ? (long)T * HD : D, v_at = 2 * k_at;
-    const float c_s = scale_log2e / (F16_QKV_SCALE * F16_QKV_SCALE);
-    const float c_o = 1.0f / F16_QKV_SCALE;
-
-    SD_STAMP(SD_STAMP_ATT_SLOT, 0);
-    // every load of the workgroup is issued before anything is converted
-    f32x4 kreg[8], vreg[8], qraw[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int idx = tid + 256 * i;
-        const int krow = idx >> 4, kc4 = idx & 15;   // K: 16 pieces per key row
-        const int vrow = idx & 127, vc4 = idx >> 7;  // V: the keys on the lanes (transposed 2-byte LDS writes stay contiguous)
-        f32x4 a = {0.f, 0.f, 0.f, 0.f}, d = a;
-        if (krow < T) a = *reinterpret_cast<const f32x4 *>(base + k_at + (unsigned)(krow * ld + kc4 * 4));
-        if (vrow < T) d = *reinterpret_cast<const f32x4 *>(base + v_at + (unsigned)(vrow * ld + vc4 * 4));
-        kreg[i] = a;
-        vreg[i] = d;
-    }
-    {
-        const unsigned qoff = (unsigned)((q_ok ? qi : 0) * ld + 8 * half);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) qraw[i] = *reinterpret_cast<const f32x4 *>(base + qoff + (unsigned)((i >> 1) * 16 + (i & 1) * 4));
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int idx = tid + 256 * i;
-        const int krow = idx >> 4, kc4 = idx & 15;
-        const int vrow = idx & 127, vc4 = idx >> 7;
-        f16x4 hh, ll;
-        f16_split4(kreg[i], F16_QKV_SCALE, hh, ll);
-        *reinterpret_cast<f16x4 *>(sK + krow * ATT16H_KP + kc4 * 4) = hh;
-        *reinterpret_cast<f16x4 *>(sK + krow * ATT16H_KP + HD + kc4 * 4) = ll;
-        f16_split4(vreg[i], F16_QKV_SCALE, hh, ll);
-        const int k16 = vrow & 15;   // key position inside its 16-key group: the 8 k-slots of a lane half contiguous
-        const int vpos = (vrow & ~15) + (k16 & 3) + 4 * ((k16 >> 3) & 1) + 8 * ((k16 >> 2) & 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            sV[(vc4 * 4 + e) * ATT16H_VP + vpos] = hh[e];
-            sV[(vc4 * 4 + e) * ATT16H_VP + 128 + vpos] = ll[e];
-        }
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 2);
-    f16x8 qf[4][2];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        f16x4 h0, l0, h1, l1;
-        f16_split4(qraw[2 * ks], F16_QKV_SCALE, h0, l0);
-        f16_split4(qraw[2 * ks + 1], F16_QKV_SCALE, h1, l1);
-        qf[ks][0] = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        qf[ks][1] = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 3);
-    __syncthreads();
-    SD_STAMP(SD_STAMP_ATT_SLOT, 4);
-    if (wave * 32 >= T) return;   // no barrier follows
-    const int kt_valid = (T + 31) / 32;
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 sc[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-        if (kt < kt_valid) {
-            const f16 *kp = sK + (kt * 32 + l31) * ATT16H_KP + 8 * half;
-            f16x8 kf[4][2];   // the tile's 8 fragments in one go: one LDS latency per tile
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                kf[ks][0] = *reinterpret_cast<const f16x8 *>(kp + ks * 16);
-                kf[ks][1] = *reinterpret_cast<const f16x8 *>(kp + HD + ks * 16);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                if (ks == 0) sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0][1], qf[0][0], zero16, 0, 0, 0);
-                else sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks][1], qf[ks][0], sc[kt], 0, 0, 0);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks][0], qf[ks][1], sc[kt], 0, 0, 0);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks][0], qf[ks][0], sc[kt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sc[kt][r] = -INFINITY;
-        }
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 5);
-    {   // keys past T in the last live tile
-        const int kt = kt_valid - 1;   // wave-uniform
-#pragma unroll
-        for (int t4 = 0; t4 < 4; ++t4)
-            if (t4 == kt && (T & 31)) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (t4 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half >= T) sc[t4][r] = -INFINITY;
-            }
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float m01, m23;
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m01) : "v"(m), "v"(sc[0][r]), "v"(sc[1][r]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m23) : "v"(m01), "v"(sc[2][r]), "v"(sc[3][r]));
-        m = m23;
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float mb = m * c_s - 10.0f;   // the 2^10 of F16_P_SCALE rides in the exponent
-    float psum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float pv = __builtin_amdgcn_exp2f(sc[kt][r] * c_s - mb);
-            sc[kt][r] = pv;
-            psum += pv;
-        }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 6);
-    f32x16 o[2];
-    const int n_groups = (T + 15) / 16;   // live 16-key groups
-#pragma unroll
-    for (int gg = 0; gg < 8; ++gg) {
-        if (gg >= n_groups) break;   // wave-uniform
-        const int kt = gg >> 1, j2 = gg & 1;
-        f16x8 ph, pl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float t = sc[kt][8 * j2 + e];
-            ph[e] = (f16)t;
-            pl[e] = (f16)(t - (float)ph[e]);
-        }
-        const f16 *vp = sV + l31 * ATT16H_VP + gg * 16 + 8 * half;
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) {
-            const f16x8 vh = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16H_VP);
-            const f16x8 vl = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16H_VP + 128);
-            if (gg == 0) o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, zero16, 0, 0, 0);
-            else o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o[ft], 0, 0, 0);
-            o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o[ft], 0, 0, 0);
-            o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o[ft], 0, 0, 0);
-        }
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 7);
-    const float l_tot = psum + __shfl_xor(psum, 32, 64);
-    const float inv = c_o / l_tot;
-    if (q_ok) {
-        float *op = out + ((long)b * T + qi) * ldo + h * HD;
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const f32x4 t = {o[ft][4 * g4] * inv, o[ft][4 * g4 + 1] * inv, o[ft][4 * g4 + 2] * inv, o[ft][4 * g4 + 3] * inv};
-                *reinterpret_cast<f32x4 *>(op + ft * 32 + 8 * g4 + 4 * half) = t;
-            }
-    }
-    SD_STAMP(SD_STAMP_ATT_SLOT, 8);
-}
-
-// The same kernel with V^T staged into K's LDS after the scores (one more barrier pair): 34 KB of LDS instead of 68, so
-// 3-4 workgroups per CU instead of 2 keep the HBM queues fed while others compute.
+constexpr int ATT16LV_KP = 136;   // K rows: {hi[64], lo[64]} + 8 halfs (272 B: 16 rows hit 16 distinct 4-bank groups)
+constexpr int ATT16LV_VP = 264;   // V^T rows: {hi[128 keys], lo[128 keys]} + 8 halfs (528 B = 132 dwords = 4 mod 64)
 #ifndef SD_ATT_LV_OCC
 #define SD_ATT_LV_OCC 3
 #endif
-constexpr size_t ATT16LV_LDS = (size_t)(128 * ATT16H_KP > 64 * ATT16H_VP ? 128 * ATT16H_KP : 64 * ATT16H_VP) * sizeof(f16);
+constexpr size_t ATT16LV_LDS = (size_t)(128 * ATT16LV_KP > 64 * ATT16LV_VP ? 128 * ATT16LV_KP : 64 * ATT16LV_VP) * sizeof(f16);
+// HM: qkv is the head-major buffer written by f16_store_qkv ([sample][head][q|k|v][token][64]); else [token][3D] rows.
 // DROP (training forward): dropout on the probabilities, see attention_kernel; instantiated for HM = false only, so the
 // sampler's kernel (register-tight at 3 workgroups per CU) is untouched.
 template <bool HM, bool DROP = false>
@@ -1342,8 +931,8 @@ __global__ __launch_bounds__(256, SD_ATT_LV_OCC) void attention_f16_head_lv_kern
         const int krow = idx >> 4, kc4 = idx & 15;
         f16x4 hh, ll;
         f16_split4(kreg[i], F16_QKV_SCALE, hh, ll);
-        *reinterpret_cast<f16x4 *>(sK + krow * ATT16H_KP + kc4 * 4) = hh;
-        *reinterpret_cast<f16x4 *>(sK + krow * ATT16H_KP + HD + kc4 * 4) = ll;
+        *reinterpret_cast<f16x4 *>(sK + krow * ATT16LV_KP + kc4 * 4) = hh;
+        *reinterpret_cast<f16x4 *>(sK + krow * ATT16LV_KP + HD + kc4 * 4) = ll;
     }
     SD_STAMP(SD_STAMP_ATT_SLOT, 2);
     f16x8 qf[4][2];
@@ -1366,7 +955,7 @@ __global__ __launch_bounds__(256, SD_ATT_LV_OCC) void attention_f16_head_lv_kern
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
         if (kt < kt_valid) {
-            const f16 *kp = sK + (kt * 32 + l31) * ATT16H_KP + 8 * half;
+            const f16 *kp = sK + (kt * 32 + l31) * ATT16LV_KP + 8 * half;
             f16x8 kf[4][2];   // the tile's 8 fragments in one go: one LDS latency per tile
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -1410,8 +999,8 @@ __global__ __launch_bounds__(256, SD_ATT_LV_OCC) void attention_f16_head_lv_kern
         const int vpos = (vrow & ~15) + (k16 & 3) + 4 * ((k16 >> 3) & 1) + 8 * ((k16 >> 2) & 1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            sV[(vc4 * 4 + e) * ATT16H_VP + vpos] = hh[e];
-            sV[(vc4 * 4 + e) * ATT16H_VP + 128 + vpos] = ll[e];
+            sV[(vc4 * 4 + e) * ATT16LV_VP + vpos] = hh[e];
+            sV[(vc4 * 4 + e) * ATT16LV_VP + 128 + vpos] = ll[e];
         }
     }
     SD_STAMP(SD_STAMP_ATT_SLOT, 6);
@@ -1466,11 +1055,11 @@ __global__ __launch_bounds__(256, SD_ATT_LV_OCC) void attention_f16_head_lv_kern
             ph[e] = (f16)t;
             pl[e] = (f16)(t - (float)ph[e]);
         }
-        const f16 *vp = sV + l31 * ATT16H_VP + gg * 16 + 8 * half;
+        const f16 *vp = sV + l31 * ATT16LV_VP + gg * 16 + 8 * half;
 #pragma unroll
         for (int ft = 0; ft < 2; ++ft) {
-            const f16x8 vh = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16H_VP);
-            const f16x8 vl = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16H_VP + 128);
+            const f16x8 vh = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16LV_VP);
+            const f16x8 vl = *reinterpret_cast<const f16x8 *>(vp + ft * 32 * ATT16LV_VP + 128);
             if (gg == 0) o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, zero16, 0, 0, 0);
             else o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o[ft], 0, 0, 0);
             o[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o[ft], 0, 0, 0);

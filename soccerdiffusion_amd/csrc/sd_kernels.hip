@@ -668,7 +668,7 @@ extern "C" int sd_debug_set_stamps(void *buf, long wgs) {
 #else
 #define SD_STAMP(slot, i)
 #endif
-#define SD_STAMP_ATT_SLOT 5    /* attention_f16_kernel, unit 2 of the last launch (stamp 8: same point one unit later) */
+#define SD_STAMP_ATT_SLOT 5    /* attention_f16_head_lv_kernel */
 #define SD_STAMP_HEAD_SLOT 4   /* diagnostic builds, L = 4: the head kernel's stamps go behind the layers' */
 
 struct DecoderLayerArgs {
@@ -1472,29 +1472,10 @@ static int attention_f16(const float *qkv, float *out, int B, int T, int d, int 
         SD_CHECK_LAUNCH("attention_f16_head_lv_kernel");
         return 0;
     }
-    // default: one workgroup per (sample, head), V^T staged late into K's LDS (35 KB of LDS, 3 workgroups per CU);
-    // A/B runs: "stage2" = K and V^T staged together (69 KB, 2 per CU), "stream" = the per-sample streaming kernel
-    static const char *env = getenv("SD_ATT16");
-    if (!head_major && !lse2 && env && strcmp(env, "stream") == 0) {
-        SD_LAUNCH(attention_f16_kernel, dim3(B), dim3(256), 0, s, qkv, 3 * d, out, d, T, heads, sl2e);
-        SD_CHECK_LAUNCH("attention_f16_kernel");
-        return 0;
-    }
-    if (lse2 || !(env && strcmp(env, "stage2") == 0)) {
-        if (head_major) SD_LAUNCH((attention_f16_head_lv_kernel<true>), dim3(B * heads), dim3(256), ATT16LV_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e, lse2, DropoutArgs{});
-        else SD_LAUNCH((attention_f16_head_lv_kernel<false>), dim3(B * heads), dim3(256), ATT16LV_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e, lse2, DropoutArgs{});
-        SD_CHECK_LAUNCH("attention_f16_head_lv_kernel");
-        return 0;
-    }
-    static DevFlag attr_set;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)attention_f16_head_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT16H_LDS);
-        (void)hipFuncSetAttribute((const void *)attention_f16_head_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT16H_LDS);
-        attr_set = true;
-    }
-    if (head_major) SD_LAUNCH((attention_f16_head_kernel<true>), dim3(B * heads), dim3(256), ATT16H_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e);
-    else SD_LAUNCH((attention_f16_head_kernel<false>), dim3(B * heads), dim3(256), ATT16H_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e);
-    SD_CHECK_LAUNCH("attention_f16_head_kernel");
+    // one workgroup per (sample, head), V^T staged late into K's LDS (35 KB of LDS, 3 workgroups per CU)
+    if (head_major) SD_LAUNCH((attention_f16_head_lv_kernel<true>), dim3(B * heads), dim3(256), ATT16LV_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e, lse2, DropoutArgs{});
+    else SD_LAUNCH((attention_f16_head_lv_kernel<false>), dim3(B * heads), dim3(256), ATT16LV_LDS, s, qkv, 3 * d, out, d, T, heads, sl2e, lse2, DropoutArgs{});
+    SD_CHECK_LAUNCH("attention_f16_head_lv_kernel");
     return 0;
 }
 

@@ -122,14 +122,6 @@ __device__ __forceinline__ void f16_gemm(f32x16 (&acc)[PanelCfg<D>::TM][PanelCfg
 
 constexpr float F16_W_SCALE = 256.0f;
 
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false)));
-    return v;
-}
-
 // amax (training): the bits of the largest |value| of the panel are atomically max-ed into one of the SD_AMAX_WORDS words at
 // amax (sd_gemm_tn_grouped's scale = the maximum over the words).  One word for all of a launch's 1 600 waves serialises
 // them in one L2 atomic unit: +6 us per row pass measured; spread by workgroup, a word sees ~25.

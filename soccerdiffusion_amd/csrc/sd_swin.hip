@@ -12,10 +12,10 @@
 // operand tile of a (window, head) in the attention.  LayerNorm, GELU (erff) and softmax are fp32.
 #include "../../include/soccerdiffusion_hip.h"
 #include "sd_common.h"
+#include "sd_mfma16.h"
 
 namespace sw {
 
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // a . b on split operands: lo.hi + hi.lo + hi.hi (lo.lo is below fp32 rounding)
 __device__ __forceinline__ f32x4 mfma16x3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x4 c) {
     c = mfma16(al, bh, c);
@@ -29,19 +29,6 @@ __device__ __forceinline__ void split8(const float (&v)[8], float s, f16x8 &h, f
         h[e] = (f16)x;
         l[e] = (f16)(x - (float)h[e]);
     }
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// max inside each group of 16 consecutive lanes (one DPP row), as row16_sum
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false)));
-    return v;
 }
 __device__ __forceinline__ float scale_for(float amax) { return f16_scale_from_bits(__builtin_bit_cast(unsigned, amax)); }
 

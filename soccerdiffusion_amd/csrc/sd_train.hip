@@ -38,21 +38,6 @@
 // reduction), two power-of-two scales, split into fp16 hi + lo, 24 fp16 MFMAs into a zero-initialised sub-accumulator,
 // which is then added - un-scaled - to the fp32 accumulator of the whole chunk (block floating point per 32 rows).
 // --------------------------------------------------------------------------------------
-// max inside each group of 16 consecutive lanes (one DPP row): 4 VALU-rate steps, no LDS round trips
-__device__ __forceinline__ float row16_maxf(float v) {
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false)));
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(256, 2) void gemm_tn16_kernel(const float *__restrict__ dY, int ldy, const float *__restrict__ X, int ldx,
                                                             float *dW, int ldw, float *db, long R, int N, int K) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -286,8 +271,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn16d_kernel(const float *__restr
         }
         // 16 partial maxima per operand (4 waves x 4 DPP rows) go to LDS; everyone reduces them after the barrier: no
         // cross-row shuffles (12 dependent ds_bpermute round trips per slab before)
-        my = row16_maxf(my);
-        mx = row16_maxf(mx);
+        my = row16_max(my);
+        mx = row16_max(mx);
         if ((lane & 15) == 0) {
             sMax2[grp][0][wave * 4 + (lane >> 4)] = my;
             sMax2[grp][1][wave * 4 + (lane >> 4)] = mx;

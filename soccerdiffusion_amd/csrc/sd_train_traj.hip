@@ -39,11 +39,6 @@ struct Args {
     int J;
 };
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 __device__ __forceinline__ void emit_amax(unsigned *words, float m, int lane) {
     if (!words) return;
     m = wave_max(m);
@@ -179,7 +174,7 @@ struct L {
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt) {
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                    mma3<S_EMB>(acc, we[n][0], we[n][1], K::lds16(Qb + K::q_at(c, tt, 0, 0)), K::lds16(Qb + K::q_at(c, tt, 1, 0)));
+                    mma3<S_EMB>(acc, we[n][0], we[n][1], lds16(Qb + K::q_at(c, tt, 0, 0)), lds16(Qb + K::q_at(c, tt, 1, 0)));
                     H[n][tt] = acc * c_e + (be[n] + pe4[n][tt]);
                     if (K::tok_ok(c, tt))
                         SD_NT_STORE(H[n][tt], reinterpret_cast<f32x4 *>(a.h3 + (row0 + K::tok_of(c, tt)) * D + 32 * c.w + 16 * n + 4 * c.g));
@@ -289,8 +284,8 @@ struct L {
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
                     const int ks = 2 * hh + kk;
-                    const f16x8 kh = K::lds16(Kp + K::x_off(cl.t, cl.g | (ks << 3))), kl = K::lds16(Kp + K::x_off(cl.t, cl.g | 4 | (ks << 3)));
-                    mma3<S_XSC>(S[hh], kh, kl, K::lds16(X + K::x_at(cl, cl.w, 0, ks)), K::lds16(X + K::x_at(cl, cl.w, 1, ks)));
+                    const f16x8 kh = lds16(Kp + K::x_off(cl.t, cl.g | (ks << 3))), kl = lds16(Kp + K::x_off(cl.t, cl.g | 4 | (ks << 3)));
+                    mma3<S_XSC>(S[hh], kh, kl, lds16(X + K::x_at(cl, cl.w, 0, ks)), lds16(X + K::x_at(cl, cl.w, 1, ks)));
                 }
             }
             // every q fragment this wave needs is in registers: its tile's rows of the panel may now receive the attention output
@@ -319,7 +314,7 @@ struct L {
                 for (int ft = 0; ft < 4; ++ft) {
                     const char *vrow = VT + (HD * hh + 16 * ft + cl.t) * VT_PITCH + 16 * cl.g;
                     O[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    mma3<S_XPV>(O[ft], K::lds16(vrow), K::lds16(vrow + 64), ph, pl);
+                    mma3<S_XPV>(O[ft], lds16(vrow), lds16(vrow + 64), ph, pl);
                 }
                 if (q_ok) {
                     const float inv = 1.0f / psum, inv1 = inv * (1.0f / ACT);

@@ -32,6 +32,7 @@
 // padded keys are masked, padded queries never leave the workgroup).
 #pragma once
 #include "sd_common.h"
+#include "sd_mfma16.h"
 #include "soccerdiffusion_hip.h"   // SD_STATUS_SHARP_LOGITS, SD_SHARP_LOGIT_LIMIT
 #include <type_traits>
 
@@ -64,21 +65,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// A/B switch of the schedule change measured in NOTEBOOK.md, round 6 addendum (0 restores the earlier code; the results are the same bits)
-#ifndef TJ_V_UNDER_SCORES
-#define TJ_V_UNDER_SCORES 1     // mode 3: the V projection's MFMAs under the scores / softmax phase instead of in the Q | K | V projection
-#endif
-// A/B switches of the latency changes measured in NOTEBOOK.md, round 7 addendum (the old value restores the earlier code; same bits)
-#ifndef TJ_EARLY_PARAMS
-#define TJ_EARLY_PARAMS 15      // biases and scales requested a phase ahead of the barrier they used to follow (bits below; 0: where they are consumed)
-#endif
-#define TJ_EARLY_QK 1           //   the Q / K bias behind B1: before the projection GEMM
-#define TJ_EARLY_V 2            //   the V bias behind B3: before the scores / V GEMM phase
-#define TJ_EARLY_XSC 4          //   the cross-attention's scales behind its "before P" barrier: before the score GEMM
-#define TJ_EARLY_FF 8           //   the feed-forward's two scales: with the biases b1 / b2
-#ifndef TJ_PV_SPLIT_UNDER
-#define TJ_PV_SPLIT_UNDER 1     // mode 3's att_pv: the hi / lo split of key pair kp + 1 between the MFMAs of pair kp (0: all pairs up front)
-#endif
 // diagnostic build (-DTJ_STAMPS): every wave of the first TJ_STAMP_WGS workgroups records the shader clock at phase boundaries
 #ifdef TJ_STAMPS
 constexpr int TJ_NSTAMP = 96, TJ_STAMP_WGS = 512;
@@ -103,8 +89,7 @@ __device__ __forceinline__ void tj_sync() {
 #define TJ_SYNC(site) __syncthreads()
 #endif
 
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-// c += (ah + al) (bh + bl) without lo.lo, small terms first.
+// The three products of sd_mfma16.h's mma3, tagged with the GEMM site.
 // Precision experiment (tools/exp/precision_sites.sh, NOTEBOOK.md 5.11): -DTJ_DROP_ALO=<mask> / -DTJ_DROP_BLO=<mask> drop the
 // A-lo x B-hi / A-hi x B-lo product at the GEMM sites whose bit is set (A = weights, K, V^T, G, V'^T; B = activations, Q, P).
 #ifndef TJ_DROP_ALO
@@ -116,43 +101,13 @@ __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __bu
 enum Site { S_QKV = 1, S_SCORES = 2, S_PV = 4, S_OUT = 8, S_XSC = 16, S_XPV = 32, S_W1 = 64, S_W2 = 128, S_EMB = 256, S_FC = 512 };
 template <int SITE = 0>
 __device__ __forceinline__ void mma3(f32x4 &c, f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl) {
-    if constexpr (!(TJ_DROP_ALO & SITE)) c = mfma16(al, bh, c);
-    if constexpr (!(TJ_DROP_BLO & SITE)) c = mfma16(ah, bl, c);
-    c = mfma16(ah, bh, c);
-}
-
-// all-reduce over the four 16-lane rows of a wave (lanes t, t+16, t+32, t+48): two v_permlane*_swap, no LDS round trip.
-// (__builtin_amdgcn_permlane32_swap(v, v) folds its two results into one on ROCm 7.2: inline assembly, checked on gfx950
-// by tools/exp/perm_test.hip.)
-__device__ __forceinline__ float rows4_sum(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    v = a + b;
-    a = v;
-    b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-__device__ __forceinline__ float rows4_max(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    v = fmaxf(a, b);
-    a = v;
-    b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-
-// x (already scaled) as hi = fp16(x), lo = fp16(x - hi): v_cvt_pk_f16_f32 both ways, 3 VALU instructions per element
-__device__ __forceinline__ void split4(const f32x4 &x, f16x4 &h, f16x4 &l) {
-    h = __builtin_convertvector(x, f16x4);
-    l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), f16x4);
-}
-__device__ __forceinline__ void split_store(char *hi_at, char *lo_at, const f32x4 &v) {
-    f16x4 h, l;
-    split4(v, h, l);
-    *reinterpret_cast<f16x4 *>(hi_at) = h;
-    *reinterpret_cast<f16x4 *>(lo_at) = l;
+    if constexpr ((TJ_DROP_ALO | TJ_DROP_BLO) & SITE) {
+        if constexpr (!(TJ_DROP_ALO & SITE)) c = mfma16(al, bh, c);
+        if constexpr (!(TJ_DROP_BLO & SITE)) c = mfma16(ah, bl, c);
+        c = mfma16(ah, bh, c);
+    } else {
+        ::mma3(c, ah, al, bh, bl);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -220,26 +175,6 @@ static __global__ void pack_g16_kernel(const float *__restrict__ gv, long items,
         *reinterpret_cast<f16x4 *>(o + 516) = l1;
     }
 }
-// Folded keys of the step tokens: gvstep rows [item * 4 + head][2 D] -> [item][head][ks][plane][g][8]
-static __global__ void pack_gstep16_kernel(const float *__restrict__ gvstep, long items, const unsigned *maxbits, f16 *__restrict__ dst,
-                                    float *scale_out) {
-    const float scale = f16_scale_from_bits(*maxbits);
-    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) *scale_out = scale;
-    const long total = items * 4 * (D / 8);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int k8 = (int)(i % (D / 8));
-        const long ih = i / (D / 8);
-        f16x4 h0, l0, h1, l1;
-        const float *row = gvstep + ih * 2 * D + kperm(k8, 0);
-        f16_split4(*reinterpret_cast<const f32x4 *>(row), scale, h0, l0);
-        f16_split4(*reinterpret_cast<const f32x4 *>(row + 16), scale, h1, l1);
-        f16 *o = dst + ih * (8 * 2 * 32) + ((k8 >> 2) * 2) * 32 + (k8 & 3) * 8;
-        *reinterpret_cast<f16x4 *>(o) = h0;
-        *reinterpret_cast<f16x4 *>(o + 4) = h1;
-        *reinterpret_cast<f16x4 *>(o + 32) = l0;
-        *reinterpret_cast<f16x4 *>(o + 36) = l1;
-    }
-}
 // Folded values of the context rows -> per item [n-tile 16][kk 2][plane][lane = 16 g + i][8]: V'^T[n = 16 nt + i][k = 32 kk + 8 g + e],
 // k = head * 16 + slot
 static __global__ void pack_v16_kernel(const float *__restrict__ gv, long items, int n_slots, const unsigned *maxbits, f16 *__restrict__ dst,
@@ -265,21 +200,6 @@ static __global__ void pack_v16_kernel(const float *__restrict__ gv, long items,
             o[e] = hh[e];
             o[512 + e] = ll[e];
         }
-    }
-}
-// Folded values of the step tokens -> [item][plane][head][n]
-static __global__ void pack_vstep16_kernel(const float *__restrict__ gvstep, long items, const unsigned *maxbits, f16 *__restrict__ dst,
-                                           float *scale_out = nullptr) {
-    const float scale = f16_scale_from_bits(*maxbits);
-    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) *scale_out = scale;
-    const long total = items * 4 * D;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int n = (int)(i % D), head = (int)((i / D) & 3);
-        const long item = i / D / 4;
-        const float v = gvstep[(item * 4 + head) * 2 * D + D + n] * scale;
-        const f16 h = (f16)v;
-        dst[(item * 2 + 0) * 4 * D + head * D + n] = h;
-        dst[(item * 2 + 1) * 4 * D + head * D + n] = (f16)(v - (float)h);
     }
 }
 
@@ -497,8 +417,6 @@ static __device__ __forceinline__ unsigned x1_off(int tok, int chunk) { return (
 static __device__ __forceinline__ unsigned x_off(int tok, int chunk) { return (unsigned)(tok * XROW + ((chunk ^ (tok & 15)) << 4)); }
 static __device__ __forceinline__ unsigned q_off(int tok, int chunk) { return (unsigned)(tok * QROW + ((chunk ^ (tok & 15)) << 4)); }
 static __device__ __forceinline__ unsigned p_off(int tok, int chunk) { return (unsigned)(tok * PROW + ((chunk ^ (tok & 15)) << 4)); }
-
-static __device__ __forceinline__ f16x8 lds16(const char *p) { return *reinterpret_cast<const f16x8 *>(p); }
 
 // H[0][tt], H[1][tt] (features 32 w + 4 g + r and 32 w + 16 + 4 g + r of this lane's token in tile tt) -> X panel, as split planes
 // of value * ACT: slot g of k-step w (kperm), one 16-byte store per plane
@@ -999,46 +917,22 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     head_zero(acc);
     if (h == 1) TJ_STAMP(17);   // (diagnostic build: the phases of head 1)
     const int w3 = w & 3;
-#if TJ_EARLY_PARAMS & TJ_EARLY_QK
     // the Q / K bias of the write phase behind B1: requested here, its round trip passes under the projection GEMM
     f32x4 bqk = *reinterpret_cast<const f32x4 *>(a.b_in + (w < 4 ? 0 : D) + HD * h + 16 * w3 + 4 * g);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     {
         const int nt0 = (w < 4 ? 0 : 16) + 4 * h + (w & 3);     // Q tile (waves 0..3) or K tile (waves 4..7)
         const f16 *pa0 = a.w_in + (long)nt0 * (8 * 2 * 512);
-#if TJ_V_UNDER_SCORES
         // Q | K only: the V tile (acc.a1) is not needed before B3 and its MFMAs run under the scores phase (below)
         gemm_pipe(c, pa0, pa0, [&](int tt, f16x8 a0h, f16x8 a0l, f16x8, f16x8, f16x8 bh, f16x8 bl) __attribute__((always_inline)) {
             mma3<S_QKV>(acc.a0[tt], a0h, a0l, bh, bl);
         });
-#else
-        const int nt1 = 32 + 4 * h + (w >> 1);                   // V tile, token half w & 1
-        const f16 *pa1 = a.w_in + (long)nt1 * (8 * 2 * 512);
-        auto run = [&](auto odd_c) __attribute__((always_inline)) {
-            constexpr bool OD = decltype(odd_c)::value;
-            gemm_pipe(c, pa0, pa1, [&](int tt, f16x8 a0h, f16x8 a0l, f16x8 a1h, f16x8 a1l, f16x8 bh, f16x8 bl) __attribute__((always_inline)) {
-                mma3<S_QKV>(acc.a0[tt], a0h, a0l, bh, bl);
-                if constexpr (!OD) {
-                    if (tt < NH0) mma3<S_QKV>(acc.a1[tt < NH0 ? tt : 0], a1h, a1l, bh, bl);
-                } else {
-                    if (tt >= NH0) mma3<S_QKV>(acc.a1[tt >= NH0 ? tt - NH0 : 0], a1h, a1l, bh, bl);
-                }
-            });
-        };
-        if (w & 1) run(std::true_type{});
-        else run(std::false_type{});
-#endif
     }
     const float c_in = 1.0f / a.s_in;   // accumulator -> ACT * value
     if (h == 1) TJ_STAMP(18);
     TJ_SYNC(2);            // B1: the previous head's readers of Q / O and K / V are done
     {   // Q or K tile -> LDS planes (features 16 (w & 3) + 4 g + r of the head, natural order on both operands of the scores)
-#if TJ_EARLY_PARAMS & TJ_EARLY_QK
         const f32x4 bv = bqk * ACT;
-#else
-        const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.b_in + (w < 4 ? 0 : D) + HD * h + 16 * w3 + 4 * g) * ACT;
-#endif
         char *dst = w < 4 ? Qb : Kb;
         const int chunk = (2 * (w3 & 1) + (g >> 1)) | ((w3 >> 1) << 3);
 #pragma unroll
@@ -1053,15 +947,12 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     TJ_SYNC(2);            // B2: Q, K complete
     f32x4 S[NTT];
     float psum = 1.f;
-#if TJ_EARLY_PARAMS & TJ_EARLY_V
     // the V bias of the write phase behind B3: its round trip passes under the scores / V GEMM phase
     f32x4 bvv = *reinterpret_cast<const f32x4 *>(a.b_in + 2 * D + HD * h + 16 * (w >> 1) + 4 * g);
     __builtin_amdgcn_sched_barrier(0);
-#endif
-#if TJ_V_UNDER_SCORES
-    // The V projection of this wave's token half (same k order and product order as inside the projection: acc.a1 has the same bits)
-    // shares the phase with the scores: the two waves of a SIMD (w, w + 4) take the jobs in opposite order, so that one's MFMAs
-    // run beside the other's softmax.  The X panel is intact until the last head; wave 7 has no query tile.
+    // The V projection of this wave's token half (the k order and product order of the Q | K projection) shares the phase with the
+    // scores: the two waves of a SIMD (w, w + 4) take the jobs in opposite order, so that one's MFMAs run beside the other's softmax.
+    // The X panel is intact until the last head; wave 7 has no query tile.
     if (w >= 4 && w < NTT) att_scores(ctx_local(c0), a, Qb, Kb, S, psum);
     {
         const f16 *pa1 = a.w_in + (long)(32 + 4 * h + (w >> 1)) * (8 * 2 * 512);   // V tile, token half w & 1
@@ -1077,17 +968,10 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
         }
     }
     if (w < 4 && w < NTT) att_scores(ctx_local(c0), a, Qb, Kb, S, psum);
-#else
-    if (w < NTT) att_scores(ctx_local(c0), a, Qb, Kb, S, psum);
-#endif
     if (h == 1) TJ_STAMP(20);
     TJ_SYNC(3);            // B3: K is dead
     {   // V piece -> rows [token][hi 64 | lo 64] (features 16 (w >> 1) + 4 g + r) over K
-#if TJ_EARLY_PARAMS & TJ_EARLY_V
         const f32x4 bv = bvv * ACT;
-#else
-        const f32x4 bv = *reinterpret_cast<const f32x4 *>(a.b_in + 2 * D + HD * h + 16 * (w >> 1) + 4 * g) * ACT;
-#endif
         const int tt1 = (w & 1) ? NH0 : 0, n1 = (w & 1) ? NTT - NH0 : NH0;
 #pragma unroll
         for (int i = 0; i < NH0; ++i) {
@@ -1101,7 +985,7 @@ static __device__ __forceinline__ void sa_head_precise(const Ctx &c0, const SaW 
     if (h == 1) TJ_STAMP(21);
     TJ_SYNC(3);            // B4: V complete (every wave has read its Q fragments: O may overwrite Q)
     AK64 wo;
-    if (w < NTT) att_pv<(TJ_PV_SPLIT_UNDER != 0)>(ctx_local(c0), S, psum, Kb, Qb);
+    if (w < NTT) att_pv<true>(ctx_local(c0), S, psum, Kb, Qb);
     // the out-projection's weight fragments: their L2 round trip passes under the barrier
     head_out_load(c, a, h, wo);
     if (h == 1) TJ_STAMP(22);
@@ -1338,14 +1222,12 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
     // Lanes of slot Mc read the step token's shared row instead of their trajectory's block.
     LnAffine aff2;
     ln_affine_load(c0, L.n2_w, L.n2_b, aff2);
-#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
     // The four scales of the cross-attention's softmax (used behind its "before P" barrier) as well: wave-uniform, so they wait in scalar
     // registers from the end of LayerNorm 2 on - the score phase is where the kernel's vector registers peak.
     float sc4 = 0.f, sc5 = 0.f, sc6 = 0.f, sc7 = 0.f;
     if constexpr (!WIDE) {
         sc4 = L.sc[4], sc5 = L.sc[5], sc6 = L.sc[6], sc7 = L.sc[7];
     }
-#endif
     f16x8 gfr[8][2];
     if constexpr (!WIDE) {
         const int hh = c0.w >> 1, Mc = Mk - 1;
@@ -1376,10 +1258,8 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         // The score biases, the step token's value columns and the folded values of this trajectory (48 registers, HBM) are requested before
         // the score GEMM: an HBM round trip under load is longer than the softmax, and a load consumed before an older one has returned
         // waits for that one too (loads return in order).
-#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
         const auto uni = [](float v) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
         sc4 = uni(sc4), sc5 = uni(sc5), sc6 = uni(sc6), sc7 = uni(sc7);
-#endif
         f32x4 cbv = *reinterpret_cast<const f32x4 *>(L.cb + traj * 64 + hh * 16 + 4 * c.g);
         const float cs = L.cstep[sblk * 4 + hh];
         __builtin_amdgcn_sched_barrier(0);
@@ -1419,13 +1299,8 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         // softmax over the Mk key slots (accumulator rows 4 g + r) of each token (lane column)
         // the step token's slot carries the scales of the step blocks (sc[6], sc[7]): a score multiplier of its own, and both kinds of
         // probability are brought to the common value scale s_v = min(sc[5], sc[7]) (step_scale)
-#if TJ_EARLY_PARAMS & TJ_EARLY_XSC
         const float c_g = 1.0f / (ACT * sc4);
         const StepScale ss = step_scale(sc5, sc6, sc7);
-#else
-        const float c_g = 1.0f / (ACT * L.sc[4]);
-        const StepScale ss = step_scale(L);
-#endif
         f32x4 cg4 = {c_g, c_g, c_g, c_g};
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1492,18 +1367,12 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) U[a][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if TJ_EARLY_PARAMS & TJ_EARLY_FF
         const float sc1 = L.sc[1];   // with b1: both land under the W1 GEMM
-#endif
         const Bias2 b1 = bias_load(c, L.b_1);
         gemm_x2<S_W1>(c, U, L.w_1);
         TJ_STAMP(36);
-#if TJ_EARLY_PARAMS & TJ_EARLY_FF
         const float c1 = 1.0f / (ACT * sc1);
         const float sc2 = L.sc[2];   // with b2
-#else
-        const float c1 = 1.0f / (ACT * L.sc[1]);
-#endif
         const Bias2 b2 = bias_load(c, L.b_2);   // lands under the GELU
         TJ_SYNC(6);   // every wave has read LN3(h): the panel receives gelu(u)
 #pragma unroll
@@ -1520,11 +1389,7 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
         }
         TJ_SYNC(7);
         TJ_STAMP(37);
-#if TJ_EARLY_PARAMS & TJ_EARLY_FF
         const float up = ACT * sc2;
-#else
-        const float up = ACT * L.sc[2];
-#endif
         scale_h(H, up);
         gemm_x2<S_W2>(c, H, L.w_2);
         unscale_h(H, 1.0f / up, b2);
@@ -1539,12 +1404,6 @@ static __device__ __forceinline__ void step_body(const StepArgs &a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     ctx_init(c, smem, a.T);
-#ifdef TJ_PRIO_YOUNG   // A/B: static priority for the second-dispatched quartet (it loses every MFMA arbitration to its SIMD partner)
-    if (c.w >= 4) __builtin_amdgcn_s_setprio(TJ_PRIO_YOUNG);
-#endif
-#ifdef TJ_PRIO_OLD
-    if (c.w < 4) __builtin_amdgcn_s_setprio(TJ_PRIO_OLD);
-#endif
     const long traj = blockIdx.x;
     const int J = a.J;
     TJ_STAMP(0);

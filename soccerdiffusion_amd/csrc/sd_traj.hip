@@ -210,7 +210,8 @@ __global__ __launch_bounds__(256) void step_fold_all_kernel(StepFoldArgs a, cons
         if (bv > __atomic_load_n(maxbits + l * 8 + 7, __ATOMIC_RELAXED)) atomicMax(maxbits + l * 8 + 7, bv);
     }
 }
-// grid (blocks, L): tj::pack_gstep16_kernel + tj::pack_vstep16_kernel of every layer (scales from words 6 / 7 -> sc[6], sc[7]); with
+// grid (blocks, L): the step tokens' folded keys -> [item][head][ks][plane][g][8] and folded values -> [item][plane][head][n] of every layer
+// (scales from words 6 / 7 -> sc[6], sc[7]); with
 // no_ctx also sc[4] = sc[6], sc[5] = sc[7] (no context rows: the all-zero context blocks carry no scale of their own - a scale of 1 from an
 // abs-max of 0 would drag the common value scale of tj::step_scale down to 1)
 __global__ void pack_step16_all_kernel(const float *__restrict__ gvstep, long gv_layer_stride, long n_tok, const unsigned *maxbits,

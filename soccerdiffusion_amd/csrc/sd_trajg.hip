@@ -18,6 +18,7 @@
 // hidden_dim 512: the panel of a 100-token trajectory (200 KB as split planes) does not fit the CU's 160 KB of LDS: T <= 48 there
 // (every shipped config has trajectory_prediction_length 10); longer horizons at 512 stay on the row-panel kernels (sampler mode 2).
 #include "sd_common.h"
+#include "sd_mfma16.h"
 #include "sd_trajg.h"
 #include "../../include/soccerdiffusion_hip.h"
 #include <math.h>
@@ -30,42 +31,6 @@ constexpr float ACT = 8.0f;      // scale of LayerNorm outputs, q, k, v, attenti
 constexpr float PSC = 1024.0f;   // scale of probabilities
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-// c += (ah + al) (bh + bl) without lo.lo, small terms first
-__device__ __forceinline__ void mma3(f32x4 &c, f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl) {
-    c = mfma16(al, bh, c);
-    c = mfma16(ah, bl, c);
-    c = mfma16(ah, bh, c);
-}
-__device__ __forceinline__ float rows4_sum(float v) {   // all-reduce over lanes t, t + 16, t + 32, t + 48 (sd_traj.h)
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    v = a + b;
-    a = v;
-    b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-__device__ __forceinline__ float rows4_max(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    v = fmaxf(a, b);
-    a = v;
-    b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ void split4(const f32x4 &x, f16x4 &h, f16x4 &l) {
-    h = __builtin_convertvector(x, f16x4);
-    l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), f16x4);
-}
-__device__ __forceinline__ void split_store(char *hi_at, char *lo_at, const f32x4 &v) {
-    f16x4 h, l;
-    split4(v, h, l);
-    *reinterpret_cast<f16x4 *>(hi_at) = h;
-    *reinterpret_cast<f16x4 *>(lo_at) = l;
-}
-__device__ __forceinline__ f16x8 lds16(const char *p) { return *reinterpret_cast<const f16x8 *>(p); }
 __device__ __forceinline__ f16x8 glb16(const f16 *p) { return *reinterpret_cast<const f16x8 *>(p); }
 __device__ __forceinline__ f16x8 zero8() { return f16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
 
@@ -537,12 +502,7 @@ struct TG {
         c = ctx_local(c0); g = c.g; t = c.t;
         f32x4 S[NTT];
         float psum = 1.f;
-#if defined(TG_ABL) && (TG_ABL & 8)
-        for (int kt = 0; kt < NTT; ++kt) S[kt] = f32x4{1.f, 1.f, 1.f, 1.f};
-        if (false) {
-#else
         if (w < NTT) {
-#endif
             // scores S^T[key][query] = K Q^T of query tile w
             f16x8 qf[KH][2];
             const int qtok = min(16 * w + t, c.T - 1);
@@ -592,11 +552,7 @@ struct TG {
         }
         __syncthreads();   // B4: V complete (every wave has read its Q fragments: O may overwrite Q)
         c = ctx_local(c0); g = c.g; t = c.t;
-#if defined(TG_ABL) && (TG_ABL & 16)
-        if (false) {
-#else
         if (w < NTT) {
-#endif
             // O^T = V^T P^T: P^T straight from the score accumulators (key order 16 (e >> 2) + 4 g + (e & 3) inside a pair of key tiles),
             // V^T through transposing LDS reads
             constexpr int NKP = (NTT + 1) / 2;
@@ -638,9 +594,6 @@ struct TG {
         __syncthreads();   // B5: O complete
         c = ctx_local(c0); g = c.g; t = c.t;
         // out-projection of this head: K = HD
-#if defined(TG_ABL) && (TG_ABL & 64)
-        if (false)
-#endif
 #pragma unroll
         for (int kk = 0; kk < KH; ++kk) {
             f16x8 wo[NA][2];
@@ -824,18 +777,13 @@ struct TG {
             const float up = ACT * L.sc[SC_O];
             const BiasV bo = bias_load(c, L.b_o);
             scale_h(H, up);
-#if !(defined(TG_ABL) && (TG_ABL & 1))
 #pragma unroll 1
             for (int h = 0; h < 4; ++h) sa_head(c, L, h, H, a.scale_log2e);
-#endif
             unscale_h(H, 1.0f / up, bo);
         }
         layer_norm_to_x(c, H, L.n2_w, L.n2_b);
-#if !(defined(TG_ABL) && (TG_ABL & 2))
         cross_block(c, L, H, traj, a, sblk);
-#endif
         layer_norm_to_x(c, H, L.n3_w, L.n3_b);
-#if !(defined(TG_ABL) && (TG_ABL & 4))
         // ---- feed-forward: h += W2 gelu(W1 LN3(h) + b1) + b2
         {
             f32x4 U[NA][NTT];
@@ -863,7 +811,6 @@ struct TG {
             gemm_own(c0, H, L.w_2);
             unscale_h(H, 1.0f / up, bb2);
         }
-#endif
     }
 
     static __device__ __forceinline__ void step_body(const StepArgs &a) {
@@ -988,7 +935,6 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_kernel(StepArgs a)
 
 }   // namespace tg
 
-#ifndef TG_NO_HOST   // (register-pressure experiments compile single instantiations of the kernel without the dispatch below)
 // ======================================================================================
 // host side
 // ======================================================================================
@@ -1205,4 +1151,3 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, i
     SD_CHECK_LAUNCH("traj_step_generic_kernel");
     return 0;
 }
-#endif   // TG_NO_HOST

@@ -245,8 +245,7 @@ def test_guarded_sampler_leaves_mode4_on_sharp_attention(ops):
 
 
 @pytest.mark.parametrize("env", [{"SD_SAMPLER_GEMM": "f32"}, {"SD_SAMPLER_TRAJ": "0"}, {"SD_SAMPLER_TRAJ": "0", "SD_QKV": "rows"},
-                                 {"SD_SAMPLER_TRAJ": "0", "SD_QKV": "rows", "SD_ATT16": "stream"}, {"SD_SAMPLER_TRAJ": "0", "SD_MERGE_HEAD": "0"},
-                                 {"SD_SAMPLER_TRAJ": "0", "SD_H": "rows"}, {"SD_SAMPLER_TRAJ": "0", "SD_ATT16": "stage2"}])
+                                 {"SD_SAMPLER_TRAJ": "0", "SD_MERGE_HEAD": "0"}, {"SD_SAMPLER_TRAJ": "0", "SD_H": "rows"}])
 def test_sampler_kernel_variants_agree_with_oracle(env):
     """The alternative kernel selections of sd_ddim_sample (fp32-MFMA fold, row-major q|k|v with the per-head or the
     streaming fp16 attention) are read from the environment once per process: run each in a child process against the

@@ -19,6 +19,44 @@
 #include <random>
 #include <vector>
 
+// The step token's folded blocks packed on their own (the library packs them with every layer's in one launch: sd_traj.hip,
+// pack_step16_all_kernel).
+// Folded keys of the step tokens: gvstep rows [item * 4 + head][2 D] -> [item][head][ks][plane][g][8]
+static __global__ void pack_gstep16_kernel(const float *__restrict__ gvstep, long items, const unsigned *maxbits, f16 *__restrict__ dst,
+                                    float *scale_out) {
+    const float scale = f16_scale_from_bits(*maxbits);
+    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) *scale_out = scale;
+    const long total = items * 4 * (tj::D / 8);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int k8 = (int)(i % (tj::D / 8));
+        const long ih = i / (tj::D / 8);
+        f16x4 h0, l0, h1, l1;
+        const float *row = gvstep + ih * 2 * tj::D + tj::kperm(k8, 0);
+        f16_split4(*reinterpret_cast<const f32x4 *>(row), scale, h0, l0);
+        f16_split4(*reinterpret_cast<const f32x4 *>(row + 16), scale, h1, l1);
+        f16 *o = dst + ih * (8 * 2 * 32) + ((k8 >> 2) * 2) * 32 + (k8 & 3) * 8;
+        *reinterpret_cast<f16x4 *>(o) = h0;
+        *reinterpret_cast<f16x4 *>(o + 4) = h1;
+        *reinterpret_cast<f16x4 *>(o + 32) = l0;
+        *reinterpret_cast<f16x4 *>(o + 36) = l1;
+    }
+}
+// Folded values of the step tokens -> [item][plane][head][n]
+static __global__ void pack_vstep16_kernel(const float *__restrict__ gvstep, long items, const unsigned *maxbits, f16 *__restrict__ dst,
+                                           float *scale_out = nullptr) {
+    const float scale = f16_scale_from_bits(*maxbits);
+    if (scale_out && blockIdx.x == 0 && threadIdx.x == 0) *scale_out = scale;
+    const long total = items * 4 * tj::D;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int n = (int)(i % tj::D), head = (int)((i / tj::D) & 3);
+        const long item = i / tj::D / 4;
+        const float v = gvstep[(item * 4 + head) * 2 * tj::D + tj::D + n] * scale;
+        const f16 h = (f16)v;
+        dst[(item * 2 + 0) * 4 * tj::D + head * tj::D + n] = h;
+        dst[(item * 2 + 1) * 4 * tj::D + head * tj::D + n] = (f16)(v - (float)h);
+    }
+}
+
 #define CK(x)                                                                          \
     do {                                                                               \
         hipError_t e_ = (x);                                                           \
@@ -194,8 +232,8 @@ int main(int argc, char **argv) {
             f16 *g16 = dalloc<f16>((size_t)B * 4 * 8 * 2 * 512), *v16 = dalloc<f16>((size_t)B * 16 * 2 * 2 * 512), *gs = dalloc<f16>(4 * 8 * 2 * 32), *vs = dalloc<f16>(2 * 4 * D);
             hipLaunchKernelGGL(tj::pack_g16_kernel, dim3(2048), dim3(256), 0, 0, d_gv, (long)B, Mc, dmb, g16, sc + 4);
             hipLaunchKernelGGL(tj::pack_v16_kernel, dim3(2048), dim3(256), 0, 0, d_gv, (long)B, Mc, dmb + 1, v16, sc + 5);
-            hipLaunchKernelGGL(tj::pack_gstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb, gs, sc + 6);       // (round 5: the step blocks' own scales)
-            hipLaunchKernelGGL(tj::pack_vstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb + 1, vs, sc + 7);
+            hipLaunchKernelGGL(pack_gstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb, gs, sc + 6);       // (round 5: the step blocks' own scales)
+            hipLaunchKernelGGL(pack_vstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb + 1, vs, sc + 7);
             CK(hipDeviceSynchronize());
             CK(hipFree(d_gv));
             w.g16 = g16; w.v16 = v16; w.gstep = gs; w.vstep = vs; w.cb = dev(h.cb); w.cstep = dev(h.cstep);

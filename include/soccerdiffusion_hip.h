@@ -618,7 +618,14 @@ int sd_swin_head_pool(const float *x, const float *ln_w, const float *ln_b, floa
  *     index outside [0, n_frames)) = a zero frame -> out (n_slots, 3, R, R) fp32, 1 <= R <= 480, one launch.  An integer factor 480 / R
  *     takes OpenCV's resizeAreaFast (taps / weights unused, may be NULL); any other R takes resizeArea with computeResizeAreaTab's table
  *     of one axis (both axes are 480 -> R): taps (3 R) int32 = first source index, tap count, offset into weights per output index;
- *     weights (n_weights <= 1440) fp32.  fp32 without FMA contraction, round half to even. */
+ *     weights (n_weights <= 1440) fp32.  fp32 without FMA contraction, round half to even.
+ *   sd_camera_intake: the robot node's preprocessing (soccer_diffusion/ml/inference/ros.py:186-200: cv2.resize(img, (R, R)) with the default
+ *     INTER_LINEAR, then the same ToDtype and Normalize) of raw camera frames: frames (n_frames, H, W, 3) uint8 in device memory at any
+ *     address (no alignment is asked for), 1 <= H, W, R <= 4096 -> out (n_frames, 3, R, R) fp32, out[c] from source channel c, or 2 - c
+ *     with bgr != 0.  cv::resize's three routes, chosen here: H == R and W == R the source pixel; H == 2 R and W == 2 R INTER_AREA's
+ *     (2 x 2 block sum + 2) >> 2; anything else the separable 11-bit fixed-point bilinear pass with the tables of ops.linear_taps
+ *     (W -> R: xidx (R) int32 first tap, xcoef (R, 2) int16 summing to 2048; H -> R: yidx, ycoef; unused and may be NULL on the other two
+ *     routes): h = S[s] c0 + S[min(s + 1, W - 1)] c1, v = (((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2. */
 /* ---- the ResNet encoder heads (soccer_diffusion/ml/model/encoder/image.py:61-83), csrc/sd_head.hip: avgpool -> fc, or the no-avgpool
  * head's Conv2d(C, 32, 1) + bias flattened in NCHW order -> fc, forward and backward, from the last block's NHWC map.
  *   sd_head_gemm: C (M x N) = A (M x K) B (K x N) (+ bias (N)), or C += that with accumulate; fp32 FMA.  Element (i, j) of an operand is
@@ -646,6 +653,8 @@ int sd_head_pool_bwd(const float *dpooled, float *dx, int N, int HW, int C, void
 
 int sd_frames_area(const uint8_t *store, int64_t n_frames, const int64_t *index, int64_t n_slots, int R, const int32_t *taps, const float *weights,
                    int n_weights, float *out, void *stream);
+int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int bgr, int R, const int32_t *xidx, const int16_t *xcoef,
+                     const int32_t *yidx, const int16_t *ycoef, float *out, void *stream);
 
 /* ---- closed-loop policy session (the receding-horizon tick of soccer_diffusion/ml/inference/ros.py:165-335), csrc/sd_session.hip.
  * A sensor ring is an fp32 device buffer (B, L, C) - one ring of L rows per robot - with one int32 head word per robot's ring in device
@@ -670,6 +679,11 @@ int sd_frames_area(const uint8_t *store, int64_t n_frames, const int64_t *index,
  *   sd_ring_window_at, sd_session_windows_at: out (S, L, C) per ring; row block s = the chronological window of robot robots[s], with
  *     the same wrap and the same 16-byte path as sd_session_windows.
  *   sd_session_commit_at: x and out (S, T, J); the T rows go into the action ring of robot robots[s] only, rounded as in sd_session_commit.
+ *   sd_ring_push_quat: quats (S, n, 4) xyzw orientation samples as the IMU delivers them (ros.py:216-253) into the rotation ring, whose
+ *     width says what is stored: C == 4 the rows unchanged, C == 5 dataset.quats_to_5d's row (axis xyz, sin angle, cos angle) -
+ *     utils/utils.py:9-24 - computed in fp64 with the same operations in the same order (squared norm, the eps^2 guard, normalise, the
+ *     (3 eps)^2 identity test giving axis (1, 0, 0) and angle 0, theta = 2 acos(clamp(w)), axis, sin, cos) and rounded to fp32 once.
+ *     robots NULL: S == B and workgroup b owns robot b; otherwise as sd_ring_push_at.  n > L keeps the last L rows.
  *   S == 0 (and n == 0 in a push) returns 0 without a launch.
  *   sd_session_reset: the start state of an episode for the robots with mask[b] != 0 (mask (B) uint8 in device memory - a simulator's
  *     done flags as they are; NULL: every robot), for up to SD_SESSION_MAX_RESET_RINGS rings in ONE launch of (B, n_rings) workgroups:
@@ -699,6 +713,7 @@ int sd_session_commit(const float *x, const float *mean, const float *stdv, floa
                       void *stream);
 int sd_ring_push_at(float *ring, int32_t *head, const float *src, const float *sub, const int32_t *robots, int S, int B, int L, int C, int n,
                     void *stream);
+int sd_ring_push_quat(float *ring, int32_t *head, const float *quats, const int32_t *robots, int S, int B, int L, int C, int n, void *stream);
 int sd_ring_window_at(const float *ring, const int32_t *head, float *out, const int32_t *robots, int S, int B, int L, int C, void *stream);
 int sd_session_windows_at(const sd_ring_view *views, int n_views, const int32_t *robots, int S, int B, void *stream);
 int sd_session_commit_at(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, const int32_t *robots,

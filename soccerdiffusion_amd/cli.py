@@ -5,7 +5,7 @@ soccer_diffusion/ml/inference/plot.py:21-135).
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -423,6 +423,35 @@ def synthetic_sensor_stream(n: int, params: dict, ticks: int, seed: int = 0) -> 
     return out
 
 
+def raw_sensor_stream(n: int, params: dict, ticks: int, camera: tuple = (480, 640), seed: int = 0) -> dict:
+    """``synthetic_sensor_stream`` as the sensors deliver it, before the node's preprocessing (ros.py:186-253): the same joint states,
+    ``orientation`` as unit xyzw quaternions (n, total, 4) and ``camera`` as uint8 rgb frames (n, 2 ticks, H, W, 3) of the camera's size."""
+    g = torch.Generator().manual_seed(seed)
+    J, T = params["num_joints"], params["trajectory_prediction_length"]
+    total = ticks * T
+    phase = torch.rand(n, 1, J, generator=g) * 2 * math.pi
+    freq = 0.5 + torch.rand(n, 1, J, generator=g)
+    wave = torch.sin(2 * math.pi * freq * torch.arange(total).view(1, total, 1) / 50.0 + phase)
+    quat = torch.randn(n, total, 4, generator=g)
+    quat = quat / quat.norm(dim=-1, keepdim=True)
+    out = {"joint_state": wave.contiguous(), "orientation": quat.contiguous()}
+    if params.get("use_images"):
+        out["camera"] = torch.randint(0, 256, (n, 2 * ticks, camera[0], camera[1], 3), dtype=torch.uint8, generator=g)
+    return out
+
+
+def _camera_size(text: str) -> tuple:
+    from . import ops
+
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        h = w = 0
+    if not (1 <= h <= ops.CAMERA_MAX and 1 <= w <= ops.CAMERA_MAX):
+        raise SystemExit(f"--camera takes HxW with 1 <= H, W <= {ops.CAMERA_MAX}, got {text!r}")
+    return h, w
+
+
 def cmd_rollout(args) -> int:
     """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep.
     --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again."""
@@ -430,6 +459,9 @@ def cmd_rollout(args) -> int:
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
         raise SystemExit("rollout needs --synthetic N (robots, N >= 1) and --ticks K (K >= 1)")
+    if args.camera is not None and not args.raw:
+        raise SystemExit("--camera is the frame size of the --raw stream")
+    camera = _camera_size(args.camera or "480x640")
     episode = None
     if args.episode_ticks is not None:
         try:
@@ -443,15 +475,23 @@ def cmd_rollout(args) -> int:
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, num_inference_steps=args.steps, batch=args.synthetic, seed=args.seed)
     params = session.hyperparams
-    stream = {k: v.to(device) for k, v in synthetic_sensor_stream(args.synthetic, params, args.ticks, seed=args.seed).items()}
+    if args.raw:
+        stream = raw_sensor_stream(args.synthetic, params, args.ticks, camera, seed=args.seed)
+    else:
+        stream = synthetic_sensor_stream(args.synthetic, params, args.ticks, seed=args.seed)
+    stream = {k: v.to(device) for k, v in stream.items()}
     T = params["trajectory_prediction_length"]
     published, resets = [], []
     for k in range(args.ticks):
         if params["use_joint_states"]:
             session.push_joint_state(stream["joint_state"][:, k * T:(k + 1) * T])
-        if params["use_imu"]:
+        if params["use_imu"] and args.raw:
+            session.push_orientation(stream["orientation"][:, k * T:(k + 1) * T])
+        elif params["use_imu"]:
             session.push_rotation(stream["rotation"][:, k * T:(k + 1) * T])
-        if params.get("use_images"):
+        if params.get("use_images") and args.raw:
+            session.push_camera(stream["camera"][:, 2 * k:2 * k + 2])
+        elif params.get("use_images"):
             session.push_image(stream["image_data"][:, 2 * k:2 * k + 2])
         published.append(session.step())
         if episode is not None:
@@ -510,6 +550,9 @@ def main(argv: Optional[list] = None) -> int:
     ro.add_argument("--steps", type=int, default=30, help="Number of denoising steps per tick")
     ro.add_argument("--episode-ticks", type=str, default=None, metavar="E[,E...]", help="episode length in ticks, robot b's is E[b %% len(E)]: "
                     "after its last tick that robot alone is reset and goes on; the output gains 'resets' (K, N)")
+    ro.add_argument("--raw", action="store_true", help="the stream carries what the sensors deliver - xyzw quaternions and uint8 camera frames - "
+                    "and the session preprocesses it on the device (push_orientation, push_camera)")
+    ro.add_argument("--camera", type=str, default=None, metavar="HxW", help="--raw only: the camera's frame size (default 480x640)")
     ro.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():

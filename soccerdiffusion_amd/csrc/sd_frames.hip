@@ -191,6 +191,167 @@ __global__ __launch_bounds__(THREADS) void frames_area_kernel(Args a) {
     }
 }
 
+
+// ---- camera intake: the robot node's frame preprocessing (soccer_diffusion/ml/inference/ros.py:186-200 - cv2.resize(img, (R, R)) with the
+// default INTER_LINEAR, ToDtype(float32, scale=True), Normalize(ImageNet)) on raw (H, W, 3) uint8 frames.  Interface: sd_camera_intake.
+//
+// cv::resize for 8-bit INTER_LINEAR (imgproc/src/resize.cpp), restated in DESIGN.md section 2:
+//   - H == R and W == R: the source pixel;
+//   - H == 2 R and W == 2 R: cv::resize turns INTER_LINEAR into INTER_AREA (resizeAreaFast): (2 x 2 block sum + 2) >> 2;
+//   - anything else: resizeGeneric_ with HResizeLinear / VResizeLinear in 11-bit fixed point.  Per axis a first tap index and a pair of
+//     int16 coefficients that sum to 2048 (built on the host: ops.linear_taps), the second tap at min(first + 1, size - 1); horizontally
+//     h = S[s] c0 + S[s + 1] c1 in int32, vertically (((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2 with arithmetic shifts.
+//
+// A workgroup owns one frame and one band of output rows.  The (at most two) source rows of an output row are staged in two LDS slots,
+// source row s in slot s & 1 - the two rows of an output are neighbours, so they never share a slot - and a slot that already holds the
+// row an output needs is not loaded again (up-scaling: consecutive outputs share source rows).  Rows of 3 W bytes start anywhere: a row is
+// staged at its global address's offset inside a 16-byte unit, so its 16-byte aligned middle moves with 16-byte loads and LDS stores and only
+// the ragged head and tail move byte by byte.  The horizontal taps are read from LDS and combined in registers; the value v is an integer in
+// 0 .. 255, so normalize(v, c) comes from a 3 x 256 table the workgroup computes once with normalize itself (the same bits); a thread's
+// consecutive columns are consecutive x of a channel plane.
+constexpr int CAM_MAX = 4096;                  // H, W, R <= 4096: a staged row is at most 12 KiB
+constexpr int CAM_COLS = 3;                    // (channel, x) columns a thread keeps its taps in registers for: 3 R <= 768
+constexpr int CAM_ROWS_PER_BAND = 8;
+enum { CAM_COPY = 0, CAM_AREA2 = 1, CAM_LINEAR = 2 };
+
+struct CamArgs {
+    const uint8_t *frames;
+    int H, W, bgr, R;
+    int bands, row_stride;                     // row_stride: LDS bytes per staged row, a multiple of 16, >= 3 W + 15
+    const int32_t *xidx, *yidx;
+    const int16_t *xcoef, *ycoef;
+    float *out;
+};
+
+struct CamTap {
+    int c, x;                                  // the output's channel plane and column
+    int p0, p1;                                // byte offsets of the two horizontal taps inside a source row
+    int c0, c1;
+};
+
+template <int MODE>
+__device__ __forceinline__ CamTap cam_tap(const CamArgs &a, int col) {
+    CamTap q;
+    q.c = col / a.R;
+    q.x = col - q.c * a.R;
+    const int cs = a.bgr ? 2 - q.c : q.c;
+    int s = q.x, s1 = q.x;
+    q.c0 = 2048;
+    q.c1 = 0;
+    if constexpr (MODE == CAM_AREA2) {
+        s = 2 * q.x;
+        s1 = s + 1;
+    }
+    if constexpr (MODE == CAM_LINEAR) {        // clamped: no table entry can address outside the staged row
+        s = min(max(a.xidx[q.x], 0), a.W - 1);
+        s1 = min(s + 1, a.W - 1);
+        q.c0 = a.xcoef[2 * q.x];
+        q.c1 = a.xcoef[2 * q.x + 1];
+    }
+    q.p0 = 3 * s + cs;
+    q.p1 = 3 * s1 + cs;
+    return q;
+}
+
+template <int MODE, bool SMALL>
+__global__ __launch_bounds__(THREADS) void camera_intake_kernel(CamArgs a) {
+    extern __shared__ uint4 cam_lds[];         // two staged rows, then the 3 x 256 normalised values
+    uint8_t *rows = reinterpret_cast<uint8_t *>(cam_lds);
+    float *lut = reinterpret_cast<float *>(rows + 2 * a.row_stride);
+
+    const int R = a.R, t = threadIdx.x, rb = 3 * a.W;
+    const long slot = blockIdx.x / a.bands;
+    const int band = blockIdx.x % a.bands;
+    const int y0 = band * CAM_ROWS_PER_BAND, y1 = min(R, y0 + CAM_ROWS_PER_BAND);
+    const long plane = (long)R * R;
+    const uint8_t *frame = a.frames + slot * ((long)a.H * rb);
+    float *out = a.out + slot * 3 * plane;
+
+    for (int i = t; i < 3 * 256; i += THREADS) lut[i] = normalize((float)(i & 255), i >> 8);
+
+    const int ncol = 3 * R;
+    CamTap taps[SMALL ? CAM_COLS : 1];
+    if constexpr (SMALL) {
+#pragma unroll
+        for (int j = 0; j < CAM_COLS; ++j) taps[j] = cam_tap<MODE>(a, min(t + j * THREADS, ncol - 1));
+    }
+
+    int held[2] = {-1, -1}, off[2] = {0, 0};   // the source row a slot holds, and where its byte 0 lies in the slot (0 .. 15)
+    // source row s -> slot s & 1; `turn` rotates the threads so that the two rows of one output are fetched by different waves
+    auto stage = [&](int s, int turn) {
+        const int k = s & 1;
+        const uint8_t *g = frame + (long)s * rb;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(g) & 15);
+        const int head = mis ? min(16 - mis, rb) : 0;
+        const int nvec = (rb - head) >> 4, tail = rb - head - (nvec << 4);
+        uint8_t *l = rows + k * a.row_stride + mis;          // row byte j at l[j]: l + head is 16-byte aligned, as g + head is
+        const uint4 *gv = reinterpret_cast<const uint4 *>(g + head);
+        uint4 *lv = reinterpret_cast<uint4 *>(l + head);
+        for (int i = (t + turn * (THREADS / 2)) % THREADS; i < nvec + head + tail; i += THREADS) {
+            if (i < nvec) {
+                lv[i] = gv[i];
+            } else {
+                const int j = i - nvec < head ? i - nvec : head + (nvec << 4) + (i - nvec - head);
+                l[j] = g[j];
+            }
+        }
+        held[k] = s;
+        off[k] = mis;
+    };
+
+    for (int y = y0; y < y1; ++y) {
+        int sa = y, sb = y, b0 = 2048, b1 = 0;
+        if constexpr (MODE == CAM_AREA2) {
+            sa = 2 * y;
+            sb = sa + 1;
+        }
+        if constexpr (MODE == CAM_LINEAR) {
+            sa = min(max(a.yidx[y], 0), a.H - 1);
+            sb = min(sa + 1, a.H - 1);
+            b0 = a.ycoef[2 * y];
+            b1 = a.ycoef[2 * y + 1];
+        }
+        const bool need_a = held[sa & 1] != sa, need_b = sb != sa && held[sb & 1] != sb;
+        if (need_a || need_b) {                // (the same in every thread)
+            __syncthreads();                   // the rows of the previous output are no longer read
+            if (need_a) stage(sa, 0);
+            if (need_b) stage(sb, 1);
+            __syncthreads();                   // (the first one also publishes lut)
+        }
+        const uint8_t *ra = rows + (sa & 1) * a.row_stride + off[sa & 1];
+        const uint8_t *rbp = rows + (sb & 1) * a.row_stride + off[sb & 1];
+        float *orow = out + (long)y * R;
+        auto emit = [&](const CamTap &q) {
+            int v;
+            if constexpr (MODE == CAM_COPY) {
+                v = ra[q.p0];
+            } else if constexpr (MODE == CAM_AREA2) {
+                v = ((int)ra[q.p0] + (int)ra[q.p1] + (int)rbp[q.p0] + (int)rbp[q.p1] + 2) >> 2;
+            } else {
+                const int h0 = (int)ra[q.p0] * q.c0 + (int)ra[q.p1] * q.c1;
+                const int h1 = (int)rbp[q.p0] * q.c0 + (int)rbp[q.p1] * q.c1;
+                v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+            }
+            v = min(max(v, 0), 255);           // saturate_cast<uchar>
+            orow[q.c * plane + q.x] = lut[q.c * 256 + v];
+        };
+        if constexpr (SMALL) {
+#pragma unroll
+            for (int j = 0; j < CAM_COLS; ++j)
+                if (t + j * THREADS < ncol) emit(taps[j]);
+        } else {
+            for (int col = t; col < ncol; col += THREADS) emit(cam_tap<MODE>(a, col));
+        }
+    }
+}
+
+template <int MODE>
+static void launch_camera(const CamArgs &a, long blocks, hipStream_t st) {
+    const size_t lds = 2 * (size_t)a.row_stride + 3 * 256 * sizeof(float);    // <= 2 * 12320 + 3072 bytes
+    if (3 * a.R <= CAM_COLS * THREADS) SD_LAUNCH((camera_intake_kernel<MODE, true>), dim3((unsigned)blocks), dim3(THREADS), lds, st, a);
+    else SD_LAUNCH((camera_intake_kernel<MODE, false>), dim3((unsigned)blocks), dim3(THREADS), lds, st, a);
+}
+
 }   // namespace fr
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -217,5 +378,28 @@ extern "C" int sd_frames_area(const uint8_t *store, int64_t n_frames, const int6
     if (k) SD_LAUNCH(fr::frames_area_kernel<true>, dim3((unsigned)blocks), dim3(fr::THREADS), 0, (hipStream_t)stream, a);
     else SD_LAUNCH(fr::frames_area_kernel<false>, dim3((unsigned)blocks), dim3(fr::THREADS), 0, (hipStream_t)stream, a);
     SD_CHECK_LAUNCH("frames_area_kernel");
+    return 0;
+}
+
+extern "C" int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int bgr, int R, const int32_t *xidx, const int16_t *xcoef,
+                                const int32_t *yidx, const int16_t *ycoef, float *out, void *stream) {
+    if (H < 1 || H > fr::CAM_MAX || W < 1 || W > fr::CAM_MAX || R < 1 || R > fr::CAM_MAX || n_frames < 0 || (n_frames > 0 && (!frames || !out)))
+        return fail(SD_E_BADARG, "sd_camera_intake: 1 <= H, W, R <= 4096, frames and out for n_frames > 0");
+    // cv::resize's routes for INTER_LINEAR: nothing to do at the same size, INTER_AREA (resizeAreaFast) at an exact factor 2 on both axes
+    const int mode = (H == R && W == R) ? fr::CAM_COPY : ((H == 2 * R && W == 2 * R) ? fr::CAM_AREA2 : fr::CAM_LINEAR);
+    if (mode == fr::CAM_LINEAR && (!xidx || !xcoef || !yidx || !ycoef))
+        return fail(SD_E_BADARG, "sd_camera_intake: the linear route needs the tap tables of both axes");
+    if (n_frames == 0) return 0;
+    fr::CamArgs a{};
+    a.frames = frames; a.H = H; a.W = W; a.bgr = bgr != 0; a.R = R;
+    a.bands = (R + fr::CAM_ROWS_PER_BAND - 1) / fr::CAM_ROWS_PER_BAND;
+    a.row_stride = (3 * W + 15 + 15) / 16 * 16;
+    a.xidx = xidx; a.yidx = yidx; a.xcoef = xcoef; a.ycoef = ycoef; a.out = out;
+    const int64_t blocks = n_frames * a.bands;
+    if (blocks > 0x7fffffffL) return fail(SD_E_BADDIM, "sd_camera_intake: grid too large");
+    if (mode == fr::CAM_COPY) fr::launch_camera<fr::CAM_COPY>(a, blocks, (hipStream_t)stream);
+    else if (mode == fr::CAM_AREA2) fr::launch_camera<fr::CAM_AREA2>(a, blocks, (hipStream_t)stream);
+    else fr::launch_camera<fr::CAM_LINEAR>(a, blocks, (hipStream_t)stream);
+    SD_CHECK_LAUNCH("camera_intake_kernel");
     return 0;
 }

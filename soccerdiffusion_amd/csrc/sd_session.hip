@@ -1,6 +1,6 @@
 // Closed-loop policy session: the buffer work of the receding-horizon tick (soccer_diffusion/ml/inference/ros.py:165-335) on the device.
 // Interface, ring layout and citations: include/soccerdiffusion_hip.h (sd_ring_push, sd_ring_window, sd_session_windows, sd_session_commit,
-// their *_at forms for a subset of the robots, and sd_session_reset).
+// their *_at forms for a subset of the robots, sd_ring_push_quat and sd_session_reset).
 //
 // ros.py keeps every sensor stream as a Python list of CPU tensors (append, then trim to the context length: ros.py:203,256-257,316-318)
 // and stacks + uploads every list at every tick (ros.py:265-275).  Here a stream is a ring (B, L, C) in device memory with one head word per
@@ -66,6 +66,46 @@ __global__ __launch_bounds__(THREADS) void ring_push_kernel(float *ring, int32_t
         const float v = s[(long)r * C + c];
         return sub ? v - sub[c] : v;
     });
+    __syncthreads();                           // every thread has read the head
+    if (threadIdx.x == 0) head[b] = (h + n % L) % L;
+}
+
+// dataset.quats_to_5d (soccer_diffusion/utils/utils.py:9-24 with transforms3d's quat2axangle) of one xyzw quaternion: (axis xyz, sin angle,
+// cos angle), in fp64 with numpy's operations in numpy's order - contraction is off - and one rounding to fp32 per value
+__device__ __forceinline__ void quat_to_5d(const float *q, float *row) {
+    double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double eps = 2.220446049250313e-16;                  // np.finfo(np.float64).eps
+    const double nq = w * w + x * x + y * y + z * z;
+    const bool tiny = nq < eps * eps;
+    const double s = sqrt(tiny ? 1.0 : nq);
+    w = w / s; x = x / s; y = y / s; z = z / s;
+    const double len2 = x * x + y * y + z * z;
+    const bool ident = tiny || len2 < (3 * eps) * (3 * eps);
+    const double theta = ident ? 0.0 : 2 * acos(fmin(fmax(w, -1.0), 1.0));
+    const double inv = 1.0 / sqrt(ident ? 1.0 : len2);
+    row[0] = ident ? 1.f : (float)(x * inv);
+    row[1] = ident ? 0.f : (float)(y * inv);
+    row[2] = ident ? 0.f : (float)(z * inv);
+    row[3] = (float)sin(theta);
+    row[4] = (float)cos(theta);
+}
+
+// quats (S, n, 4) xyzw -> the rotation ring (B, L, C): C == 4 the rows as they are, C == 5 quat_to_5d of them; a thread owns whole rows
+__global__ __launch_bounds__(THREADS) void ring_push_quat_kernel(float *ring, int32_t *head, const float *__restrict__ quats,
+                                                                 const int32_t *__restrict__ robots, int B, int L, int C, int n) {
+    const int b = robot_of(robots, blockIdx.x, B);
+    if (b < 0) return;
+    const int h = head_of(head, b, L);
+    const float *q = quats + (long)blockIdx.x * n * 4;
+    float *rb = ring + (long)b * L * C;
+    for (int r = (n > L ? n - L : 0) + threadIdx.x; r < n; r += THREADS) {   // (as push_rows: with n > L only the last L rows)
+        float *row = rb + (long)((h + r) % L) * C;
+        if (C == 5) {
+            quat_to_5d(q + (long)r * 4, row);
+        } else {
+            for (int c = 0; c < 4; ++c) row[c] = q[(long)r * 4 + c];
+        }
+    }
     __syncthreads();                           // every thread has read the head
     if (threadIdx.x == 0) head[b] = (h + n % L) % L;
 }
@@ -170,6 +210,18 @@ extern "C" int sd_ring_push_at(float *ring, int32_t *head, const float *src, con
     if (S == 0 || n == 0) return 0;
     SD_LAUNCH(ss::ring_push_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, ring, head, src, sub, robots, B, L, C, n);
     SD_CHECK_LAUNCH("ring_push_kernel");
+    return 0;
+}
+
+extern "C" int sd_ring_push_quat(float *ring, int32_t *head, const float *quats, const int32_t *robots, int S, int B, int L, int C, int n,
+                                 void *stream) {
+    if (!ring || !head || !dims_ok(B, L, C) || (C != 4 && C != 5) || S < 0 || n < 0 || (long)n * 5 > 0x7fffffffL / 2 || (!robots && S != B) ||
+        (S > 0 && n > 0 && !quats))
+        return fail(SD_E_BADARG, "sd_ring_push_quat: ring, head and (for S, n > 0) quats must be given; B, L > 0, C = 4 or 5, S, n >= 0, S = B "
+                                 "without robots");
+    if (S == 0 || n == 0) return 0;
+    SD_LAUNCH(ss::ring_push_quat_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, ring, head, quats, robots, B, L, C, n);
+    SD_CHECK_LAUNCH("ring_push_quat_kernel");
     return 0;
 }
 

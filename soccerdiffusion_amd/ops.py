@@ -1336,6 +1336,89 @@ def frames_area(store: Tensor, index: Tensor, R: int, out: Optional[Tensor] = No
     return out
 
 
+# ---- camera intake: OpenCV INTER_LINEAR of raw camera frames + the reference's normalisation (csrc/sd_frames.hip) ------------------------
+CAMERA_MAX = 4096   # sd_camera_intake: 1 <= H, W, R <= 4096
+LINEAR_BITS = 11    # INTER_RESIZE_COEF_BITS: the coefficient pair of a tap sums to 1 << 11
+
+
+def linear_taps(src: int, dst: int) -> tuple:
+    """cv::resize's INTER_LINEAR table of one axis src -> dst for 8-bit images (imgproc/src/resize.cpp, restated in DESIGN.md section 2):
+    (index int32 (dst,), coef int16 (dst, 2)).  Output d reads source index[d] with coef[d, 0] and min(index[d] + 1, src - 1) with
+    coef[d, 1].  scale = 1 / (dst / src) in doubles; f = float32((d + 0.5) scale - 0.5), s = floor(f), f -= s in fp32; s < 0 -> (0, 0),
+    s >= src - 1 -> (src - 1, 0); coef = cvRound((1 - f) 2048), cvRound(f 2048) from fp32 products, round half to even."""
+    for name, v in (("src", src), ("dst", dst)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name}: an int >= 1, got {v!r}")
+    scale = 1.0 / (dst / src)
+    one, unit = np.float32(1.0), np.float32(1 << LINEAR_BITS)
+    index, coef = np.empty(dst, np.int32), np.empty((dst, 2), np.int16)
+    for d in range(dst):
+        f = np.float32((d + 0.5) * scale - 0.5)
+        s = math.floor(f)
+        f = np.float32(f - np.float32(s))
+        if s < 0:
+            s, f = 0, np.float32(0.0)
+        if s >= src - 1:
+            s, f = src - 1, np.float32(0.0)
+        index[d] = s
+        coef[d] = (int(np.rint(np.float32(one - f) * unit)), int(np.rint(f * unit)))
+    return index, coef
+
+
+def camera_route(H: int, W: int, R: int) -> str:
+    """The route cv2.resize(frame, (R, R)) with INTER_LINEAR takes for an (H, W) frame: "copy" at the same size, "area2" at an exact
+    factor 2 on both axes (cv::resize turns INTER_LINEAR into INTER_AREA there), "linear" for everything else."""
+    if H == R and W == R:
+        return "copy"
+    if H == 2 * R and W == 2 * R:
+        return "area2"
+    return "linear"
+
+
+_linear_tables: dict = {}
+
+
+def _linear_table(src: int, R: int, device) -> tuple:
+    key = (src, R, str(device))
+    if key not in _linear_tables:
+        index, coef = linear_taps(src, R)
+        _linear_tables[key] = (torch.from_numpy(index).to(device), torch.from_numpy(coef).to(device))
+    return _linear_tables[key]
+
+
+def camera_intake(frames: Tensor, R: int, order: str = "rgb", out: Optional[Tensor] = None) -> Tensor:
+    """The robot node's frame preprocessing (ros.py:186-200) in one launch: cv2.resize(frame, (R, R)) with the default INTER_LINEAR - bit for
+    bit as restated in DESIGN.md section 2 - then x / 255, (x - ImageNet mean) / std, channels first.  frames (..., H, W, 3) uint8 on the
+    device, at any address (a slice of a larger buffer is read in place); ``order``: "rgb", or "bgr" for frames whose channels arrive in
+    OpenCV's order -> (..., 3, R, R) float32 with the channels in the model's order.  1 <= H, W, R <= 4096."""
+    if not isinstance(frames, Tensor) or frames.dtype != torch.uint8:
+        raise ValueError(f"frames: expected a uint8 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() < 3 or frames.shape[-1] != 3:
+        raise ValueError(f"frames: expected (..., H, W, 3), got {tuple(frames.shape)}")
+    H, W = int(frames.shape[-3]), int(frames.shape[-2])
+    if not (1 <= H <= CAMERA_MAX and 1 <= W <= CAMERA_MAX):
+        raise ValueError(f"frames: 1 <= H, W <= {CAMERA_MAX}, got {H} x {W}")
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"order: 'rgb' or 'bgr', got {order!r}")
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= CAMERA_MAX:
+        raise ValueError(f"R: an int in 1 .. {CAMERA_MAX}, got {R!r}")
+    R = int(R)
+    _swin_req(frames, "frames", dtype=torch.uint8)
+    dev = frames.device
+    shape = (*frames.shape[:-3], 3, R, R)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(_swin_req(out, "out", dev).shape) != shape:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected {shape}")
+    xi = xc = yi = yc = None
+    if camera_route(H, W, R) == "linear":
+        (xi, xc), (yi, yc) = _linear_table(W, R, dev), _linear_table(H, R, dev)
+    n = frames.numel() // (H * W * 3)
+    check(_lib.load().sd_camera_intake(frames.data_ptr(), n, H, W, int(order == "bgr"), R, _ptr(xi), _ptr(xc), _ptr(yi), _ptr(yc), out.data_ptr(),
+                                       _stream()), "sd_camera_intake")
+    return out
+
+
 # ---- the ResNet encoder heads (csrc/sd_head.hip): avgpool -> fc, or Conv2d(C, 32, 1) + bias flattened NCHW -> fc ------------------------
 def _operand(t: Tensor, row=(0, 0, 0), col=(0, 0, 0)):
     """sd_strided_operand: element (i, j) at ((i / d) s1 + (i % d) s0) + ((j / d') s1' + (j % d') s0') floats from t's start (d = 0: i s0)."""
@@ -1496,6 +1579,22 @@ def ring_push(ring: Tensor, head: Tensor, rows: Tensor, sub: Optional[Tensor] = 
     else:
         check(_lib.load().sd_ring_push_at(ring.data_ptr(), head.data_ptr(), rows.data_ptr(), _ptr(sub), r.data_ptr(), S, B, L, Cc, rows.shape[1],
                                           _stream()), "sd_ring_push_at")
+
+
+def ring_push_quat(ring: Tensor, head: Tensor, quats: Tensor, robots=None) -> None:
+    """Appends orientation samples quats (B, n, 4), xyzw and oldest first, to the rotation ring (B, L, 4 | 5) and advances its heads.  The
+    ring's width says what is stored: 4 columns the quaternions as they are, 5 columns ``dataset.quats_to_5d``'s rows (axis, sin angle,
+    cos angle), computed on the device in fp64 and rounded to fp32 once.  ``robots``: as in ``ring_push``."""
+    B, L, Cc = _ring_req(ring, head)
+    if Cc not in (4, 5):
+        raise ValueError(f"a rotation ring has 4 (quaternion) or 5 (five_dim) columns, got {Cc}")
+    _req(quats, "quats")
+    r = None if robots is None else _robots_on(robots, B, ring.device)
+    S = B if r is None else r.numel()
+    if quats.dim() != 3 or quats.shape[0] != S or quats.shape[2] != 4 or quats.device != ring.device:
+        raise ValueError(f"quats: expected ({S}, n, 4) on {ring.device}, got {tuple(quats.shape)} on {quats.device}")
+    check(_lib.load().sd_ring_push_quat(ring.data_ptr(), head.data_ptr(), quats.data_ptr(), _ptr(r), S, B, L, Cc, quats.shape[1], _stream()),
+          "sd_ring_push_quat")
 
 
 def ring_window(ring: Tensor, head: Tensor, out: Optional[Tensor] = None, robots=None) -> Tensor:

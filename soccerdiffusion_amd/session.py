@@ -10,6 +10,7 @@ backbone kernels see.
 
     s = PolicySession(model, num_inference_steps=30, batch=1, hyperparams=checkpoint["hyperparams"])
     s.push_joint_state(q); s.push_rotation(r); s.push_image(frame)     # the callbacks / timers of ros.py:165-257
+    s.push_orientation(quat); s.push_camera(frame_u8)                 # the same from raw sensor data: xyzw quaternions, uint8 (H, W, 3) frames
     traj = s.step()                                                   # (B, T, J): what ros.py:321-335 publishes
 
 Every entry point takes ``robots=`` for a subset of the batch (robots that tick at their own times, episodes that end robot by robot):
@@ -237,22 +238,70 @@ class PolicySession:
         ``push_joint_state``."""
         self._push("rotation", r, "push_rotation", robots)
 
-    def push_image(self, frames: torch.Tensor, robots=None) -> None:
-        """Frames (B, 3, R, R) or (B, n, 3, R, R), preprocessed as ros.py:191-200 and already at ``image_resolution``: encoded now by
-        the model's image encoder, on these frames only; the tokens go into the ring and no frame is kept.  ``robots``: the leading
-        dimension is ``len(robots)``, the encoder sees ``len(robots) * n`` frames and only those robots' token rings move."""
-        if self._images is None:
-            raise RuntimeError("PolicySession.push_image: the model has images switched off - there is no ring to push into")
-        self._check_weights("push_image")
-        if self.model.training:
-            raise RuntimeError("PolicySession.push_image: the model is in train() mode - call model.eval()")
+    def push_orientation(self, q: torch.Tensor, robots=None) -> None:
+        """Orientation samples as the IMU delivers them: xyzw quaternions (B, 4) or (B, n, 4), oldest first (ros.py:216-253).  The
+        rotation ring's own width decides what is stored: the quaternions as they are, or, for ``imu_orientation_embedding_method:
+        five_dim``, ``dataset.quats_to_5d``'s rows, computed on the device (``ops.ring_push_quat``); ``robots`` as in ``push_joint_state``."""
+        if "rotation" not in self._rings:
+            raise RuntimeError("PolicySession.push_orientation: the model has this modality switched off - there is no ring to push into")
         S, dev_idx = (None, None) if robots is None else self._subset(robots)[::2]
-        x = self._rows(frames, (3, self.R, self.R), "push_image", S)
-        if S == 0:
+        ops.ring_push_quat(*self._rings["rotation"], self._rows(q, (4,), "push_orientation", S), robots=dev_idx)
+
+    def _image_gate(self, name: str) -> None:
+        if self._images is None:
+            raise RuntimeError(f"PolicySession.{name}: the model has images switched off - there is no ring to push into")
+        self._check_weights(name)
+        if self.model.training:
+            raise RuntimeError(f"PolicySession.{name}: the model is in train() mode - call model.eval()")
+
+    def _push_frames(self, x: torch.Tensor, dev_idx) -> None:
+        """Preprocessed fp32 frames (S, n, 3, R, R) on the device -> their tokens into the token rings of the batch or of ``dev_idx``."""
+        if x.shape[0] == 0:
             return
         with torch.no_grad():
             tokens = self._image_encoder(x)
         ops.ring_push(*self._tokens, tokens.contiguous(), robots=dev_idx)
+
+    def push_image(self, frames: torch.Tensor, robots=None) -> None:
+        """Frames (B, 3, R, R) or (B, n, 3, R, R), preprocessed as ros.py:191-200 and already at ``image_resolution``: encoded now by
+        the model's image encoder, on these frames only; the tokens go into the ring and no frame is kept.  ``robots``: the leading
+        dimension is ``len(robots)``, the encoder sees ``len(robots) * n`` frames and only those robots' token rings move."""
+        self._image_gate("push_image")
+        S, dev_idx = (None, None) if robots is None else self._subset(robots)[::2]
+        self._push_frames(self._rows(frames, (3, self.R, self.R), "push_image", S), dev_idx)
+
+    def push_camera(self, frames: torch.Tensor, robots=None, interpolation: str = "linear", order: str = "rgb") -> None:
+        """Raw camera frames, uint8 (B, H, W, 3) or (B, n, H, W, 3) of any size: preprocessed on the device, then handled as
+        ``push_image`` handles its frames.  A CPU tensor is uploaded as uint8 (``non_blocking``), a device tensor is read in place.
+        ``interpolation``: "linear" is the robot node's preprocessing (ros.py:186-200: cv2.resize's default INTER_LINEAR, [0, 1] scaling,
+        ImageNet mean / std: ``ops.camera_intake``); "area" is the training set's (dataset/pytorch.py:209-211: INTER_AREA of 480 x 480
+        frames: ``ops.frames_area``).  ``order``: "rgb", or "bgr" where the channels arrive in OpenCV's order; ``robots`` as in
+        ``push_image``."""
+        self._image_gate("push_camera")
+        S, dev_idx = (None, None) if robots is None else self._subset(robots)[::2]
+        S = self.B if S is None else S
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+            raise ValueError(f"push_camera: expected a uint8 tensor, got {getattr(frames, 'dtype', type(frames))}")
+        if frames.dim() == 4:
+            frames = frames.unsqueeze(1)
+        if frames.dim() != 5 or frames.shape[0] != S or frames.shape[-1] != 3:
+            raise ValueError(f"push_camera: expected ({S}, H, W, 3) or ({S}, n, H, W, 3), got {tuple(frames.shape)}")
+        if interpolation not in ("linear", "area"):
+            raise ValueError(f"interpolation: 'linear' or 'area', got {interpolation!r}")
+        if order not in ("rgb", "bgr"):
+            raise ValueError(f"order: 'rgb' or 'bgr', got {order!r}")
+        if interpolation == "area" and tuple(frames.shape[2:4]) != (ops.FRAME_SIZE, ops.FRAME_SIZE):
+            raise ValueError(f"push_camera: interpolation='area' is the preprocessing of the recordings' {ops.FRAME_SIZE} x {ops.FRAME_SIZE} "
+                             f"frames, got {frames.shape[2]} x {frames.shape[3]}")
+        frames = frames.to(self.device, non_blocking=True).contiguous()
+        if interpolation == "linear":
+            x = ops.camera_intake(frames, self.R, order=order)
+        else:
+            if order == "bgr":
+                frames = frames.flip(-1)
+            index = torch.arange(S * frames.shape[1], device=self.device).view(S, frames.shape[1])
+            x = ops.frames_area(frames.view(-1, ops.FRAME_SIZE, ops.FRAME_SIZE, 3), index, self.R)
+        self._push_frames(x, dev_idx)
 
     def set_game_state(self, idx, robots=None) -> None:
         """Game state index per robot (an int for all of them, or B of them); ros.py:274 feeds the constant 2.  ``robots``: for those

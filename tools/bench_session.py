@@ -21,7 +21,14 @@ host time of the reset), the step, synchronise.  A block is the mean of --ticks 
 every figure is the median over the blocks, with the extremes and the spread as above.  Exit status 1 when a partial reset plus its tick is
 slower than the whole reset plus its tick beyond the spread, or, with use_graph, when the tick after a partial reset is slower than an
 ordinary replayed tick beyond the spread.
-usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10] [--reset [--out profiles/session_partial_reset.jsonl]]"""
+
+--raw HxW measures the session's two sensor intakes against each other: per tick two uint8 camera frames (H, W, 3) and xyzw quaternions in
+host memory through push_camera / push_orientation, against two fp32 frames that are already (3, R, R) and rotation rows that are already in
+the model's form through push_image / push_rotation - the second one leaves out the host's cv2.resize, scaling, normalisation and
+quats_to_5d, which this tool does not time (cv2 is not a dependency, and another resize would not be the node's).  Two eager sessions on one
+model, alternating blocks, medians, extremes and spread as above; no exit status depends on it.
+usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10] [--reset [--out profiles/session_partial_reset.jsonl]]
+                                     [--raw 480x640 [--out profiles/session_raw_tick.jsonl]]"""
 import argparse
 import json
 import os
@@ -199,18 +206,81 @@ def reset_leg(args):
         raise SystemExit(1)
 
 
+def raw_tick(s, new, x_T):
+    if "joint_state" in new:
+        s.push_joint_state(new["joint_state"])
+    if "orientation" in new:
+        s.push_orientation(new["orientation"])
+    s.push_camera(new["camera"])
+    return s.step(x_T).cpu()
+
+
+def raw_leg(args):
+    """Raw sensor data through push_camera / push_orientation against preprocessed data through push_image / push_rotation (--raw HxW)."""
+    H, W = cli._camera_size(args.raw)
+    blocks = 3 if args.quick else args.blocks
+    lines = []
+    for name, over in CONFIGS.items():
+        params = {**BASE, **over}
+        torch.manual_seed(0)
+        model = cli.build_model(params).cuda().eval()
+        T, J = params["trajectory_prediction_length"], params["num_joints"]
+        for B in ((1, 16) if args.quick else (1, 16, 64)):
+            g = torch.Generator().manual_seed(7)
+            s_pre, s_raw = (PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params) for _ in range(2))
+            x_T = torch.randn(B, T, J, device="cuda", generator=torch.Generator(device="cuda").manual_seed(8))
+            pre = [sensor_rows(params, B, g) for _ in range(args.ticks)]
+            raw = []
+            for new in pre:
+                r = {"camera": torch.randint(0, 256, (B, NEW_FRAMES, H, W, 3), dtype=torch.uint8, generator=g)}
+                if "joint_state" in new:
+                    r["joint_state"] = new["joint_state"]
+                if "rotation" in new:
+                    r["orientation"] = torch.randn(B, T, 4, generator=g)
+                raw.append(r)
+            variants = ((lambda new, x: session_tick(s_pre, new, x), pre), (lambda new, x: raw_tick(s_raw, new, x), raw))
+            for tick, news in variants:                                    # warm-up: one untimed block of both
+                block_ms(tick, news, x_T)
+            t_pre, t_raw = [], []
+            for _ in range(blocks):                                        # alternating blocks: drift of the box hits both
+                for (tick, news), into in zip(variants, (t_pre, t_raw)):
+                    into.append(block_ms(tick, news, x_T))
+            mp, mr = statistics.median(t_pre), statistics.median(t_raw)
+            spread = max(max(v) - min(v) for v in (t_pre, t_raw))
+            R = params["image_resolution"]
+            rec = {"config": name, "B": B, "steps": N_STEPS, "new_frames_per_tick": NEW_FRAMES, "camera": [H, W], "frame_size": [R, R],
+                   "blocks": blocks, "ticks_per_block": args.ticks,
+                   "host_bytes_per_tick": {"preprocessed_fp32": B * NEW_FRAMES * 12 * R * R, "raw_uint8": B * NEW_FRAMES * 3 * H * W},
+                   "preprocessed_tick_ms": {"median": round(mp, 3), "min": round(min(t_pre), 3), "max": round(max(t_pre), 3)},
+                   "raw_tick_ms": {"median": round(mr, 3), "min": round(min(t_raw), 3), "max": round(max(t_raw), 3)},
+                   "spread_ms": round(spread, 3), "raw_minus_preprocessed_ms": round(mr - mp, 3),
+                   "difference_beyond_spread": bool(abs(mr - mp) > spread),
+                   "host_preprocessing": "not timed: the preprocessed variant's frames and rotation rows are made outside the timed blocks"}
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+            del s_pre, s_raw
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="B = 1 and 16 only, fewer blocks")
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--ticks", type=int, default=10, help="ticks per block")
     ap.add_argument("--reset", action="store_true", help="measure partial and whole resets with the tick that follows them")
-    ap.add_argument("--out", type=str, default=None, help="--reset: also write the JSON lines to this file")
+    ap.add_argument("--raw", type=str, default=None, metavar="HxW", help="measure raw uint8 camera frames of this size and quaternions through "
+                    "push_camera / push_orientation against preprocessed ones through push_image / push_rotation")
+    ap.add_argument("--out", type=str, default=None, help="--reset, --raw: also write the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_session.py measures on the GPU: no device found")
     if args.reset:
         return reset_leg(args)
+    if args.raw:
+        return raw_leg(args)
     blocks = 3 if args.quick else args.blocks
     failed = False
     for name, over in CONFIGS.items():

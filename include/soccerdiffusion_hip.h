@@ -509,6 +509,17 @@ int sd_adamw_step(float *p, const float *g, float *m, float *v, long n, double l
 int sd_adamw_step_dev(float *p, const float *g, float *m, float *v, long n, const float *hyper7_dev, void *stream);
 int sd_adamw_hyper(double lr, double beta1, double beta2, double eps, double weight_decay, long step, float *hyper7_host);
 
+/* sd_adamw_step / sd_adamw_step_dev plus an exponential moving average of the weights in the SAME launch: p, m, v come out bit
+ * for bit as from those two, then ema[i] += ema_weight * (p_new[i] - ema[i]) on the value just computed (one more read and one
+ * more write per element, no pass of its own).  ema_weight in [0, 1] is the weight of THIS update (1 - decay after warmup; the
+ * caller owns the schedule); the _dev form reads it from *ema_weight_dev - a pointer of its own, since the graphed step keeps
+ * the dropout epoch in the word behind hyper7.  16-byte loads and stores where all five buffers are 16-byte aligned, element by
+ * element otherwise; any n >= 1. */
+int sd_adamw_ema_step(float *p, const float *g, float *m, float *v, float *ema, long n, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, long step, double ema_weight, void *stream);
+int sd_adamw_ema_step_dev(float *p, const float *g, float *m, float *v, float *ema, long n, const float *hyper7_dev,
+                          const float *ema_weight_dev, void *stream);
+
 /* Per-step part of the dropout mask key from DEVICE memory: when set (non-NULL), every dropout kernel adds *device_word to
  * the high half of its Philox key at run time, so a hipGraph replay of a training step draws fresh masks once the host has
  * changed the word.  Process-wide; NULL switches it off. */

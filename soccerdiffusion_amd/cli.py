@@ -2,17 +2,20 @@
 the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
-    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10]
-    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema]
+    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
 file (`--data file.pt`: dict with `joint_command` (N,T,J) and the optional context keys of
 the reference's `Result` dataclass) or from a synthetic sine-wave generator (`--synthetic N`); wandb and matplotlib are not used; under torchrun
 (WORLD_SIZE > 1) training is data parallel with one RCCL all-reduce of the flat gradient
-per step and `sample` shards the rollouts over the ranks.
+per step and `sample` shards the rollouts over the ranks; `--ema-decay` keeps an exponential
+moving average of the weights inside the optimizer step (optim.FusedAdamW) and the checkpoint
+gains `ema_model_state_dict` and `ema`, which `--ema` / `--ema-teacher` load instead of the
+last iterate (the reference's ml/preliminary scripts kept and sampled such an average).
 """
 
 from __future__ import annotations
@@ -155,6 +158,42 @@ def load_data(args, params: dict) -> dict:
     return synthetic_dataset(args.synthetic, params, seed=args.seed, image_size=size)
 
 
+EMA_KEY = "ema_model_state_dict"
+
+
+def ema_model_state(checkpoint: dict, flag: str, path: str) -> dict:
+    """The EMA weights of a checkpoint for ``flag``; a checkpoint trained without --ema-decay ends the command."""
+    if EMA_KEY not in checkpoint:
+        raise SystemExit(f"{flag}: checkpoint {path} has no '{EMA_KEY}' (it was trained without --ema-decay)")
+    return checkpoint[EMA_KEY]
+
+
+def _ema_decay(text: str) -> float:
+    try:
+        value = float(text)
+    except ValueError:
+        value = float("nan")
+    if not 0.0 < value < 1.0:
+        raise argparse.ArgumentTypeError(f"--ema-decay takes a decay in the open interval (0, 1), got {text!r}")
+    return value
+
+
+def _restore_ema(optimizer, model, checkpoint: Optional[dict]) -> None:
+    """The optimizer's EMA from the checkpoint's keys; a checkpoint without them leaves it at the loaded parameters."""
+    if optimizer.flat_ema is None or checkpoint is None:
+        return
+    if EMA_KEY in checkpoint and "ema" in checkpoint:
+        optimizer.load_ema_state_dict(model, checkpoint[EMA_KEY], checkpoint["ema"]["num_updates"])
+    else:
+        logger.warning("the checkpoint holds no EMA: the average starts from the loaded parameters")
+
+
+def _ema_checkpoint_keys(optimizer, model) -> dict:
+    if optimizer.flat_ema is None:
+        return {}
+    return {EMA_KEY: optimizer.ema_state_dict(model), "ema": optimizer.ema_state()}
+
+
 def shard_plan(n_total: int, batch_size: int, rank: int, world: int):
     """Sample indices of this rank and the number of optimizer steps per epoch, the SAME on every rank.
 
@@ -239,9 +278,13 @@ def cmd_train(args) -> int:
     model.train()
     model.set_dropout(args.dropout, seed=args.seed + 7919 * rank)   # every rank its own mask stream
 
-    optimizer = training.FusedAdamW(model.parameters(), lr=params["lr"])
+    ema_decay, ema_warmup = args.ema_decay, not args.no_ema_warmup
+    if ema_decay is None and checkpoint is not None and "ema" in checkpoint:   # a resumed run goes on averaging as it did
+        ema_decay, ema_warmup = checkpoint["ema"]["decay"], checkpoint["ema"]["warmup"]
+    optimizer = training.FusedAdamW(model.parameters(), lr=params["lr"], ema_decay=ema_decay, ema_warmup=ema_warmup)
     if checkpoint is not None and "optimizer_state_dict" in checkpoint:
         optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
+    _restore_ema(optimizer, model, checkpoint)
     if world > 1:  # ... and rank 0's parameters, moments and buffers are what every rank starts from, whatever happened above
         training.broadcast_parameters(optimizer, model)
     bs = params["batch_size"]
@@ -271,7 +314,7 @@ def cmd_train(args) -> int:
         if rank == 0:
             torch.save({"model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch}, args.output)
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model)}, args.output)
     if world > 1:
         import torch.distributed as dist
 
@@ -304,7 +347,7 @@ def cmd_distill(args) -> int:
     params["distilled_decoder"] = True  # flags the student (distill.py:62)
 
     teacher = build_model(params).to(device)
-    teacher.load_state_dict(checkpoint["model_state_dict"])
+    teacher.load_state_dict(ema_model_state(checkpoint, "--ema-teacher", args.checkpoint) if args.ema_teacher else checkpoint["model_state_dict"])
     # distill.py:127-131 never calls teacher_model.eval(): the reference's teacher rollout (and its context encoders) run
     # with dropout 0.1 live.  --teacher-dropout reproduces that (a Python loop over the training kernels); the default
     # is the clean teacher on the native sampler.
@@ -317,7 +360,7 @@ def cmd_distill(args) -> int:
     # the student's context encoders never see a gradient (the context comes from the teacher under
     # no_grad), so torch's AdamW leaves them untouched; the flat optimizer therefore only owns the rest
     trainable = [p for n, p in student.named_parameters() if n.startswith(("diffusion_action_generator.", "step_encoding."))]
-    optimizer = training.FusedAdamW(trainable, lr=params["lr"])
+    optimizer = training.FusedAdamW(trainable, lr=params["lr"], ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
     if world > 1:
         training.broadcast_parameters(optimizer, student)
 
@@ -356,7 +399,7 @@ def cmd_distill(args) -> int:
         if rank == 0:
             torch.save({"model_state_dict": student.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch}, args.output)
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student)}, args.output)
     if world > 1:
         import torch.distributed as dist
 
@@ -374,7 +417,7 @@ def cmd_sample(args) -> int:
     checkpoint = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
     params = checkpoint["hyperparams"]
     model = build_model(params).to(device)
-    model.load_state_dict(checkpoint["model_state_dict"])
+    model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
     model.eval()
     n = args.num_samples
     mine = torch.arange(rank, n, world)  # embarrassingly parallel over ranks, no collective
@@ -473,7 +516,8 @@ def cmd_rollout(args) -> int:
         episode = torch.tensor([lengths[b % len(lengths)] for b in range(args.synthetic)])
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
-    session = PolicySession.from_checkpoint(args.checkpoint, device, num_inference_steps=args.steps, batch=args.synthetic, seed=args.seed)
+    session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
+                                            seed=args.seed)
     params = session.hyperparams
     if args.raw:
         stream = raw_sensor_stream(args.synthetic, params, args.ticks, camera, seed=args.seed)
@@ -528,6 +572,7 @@ def main(argv: Optional[list] = None) -> int:
     sa.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
     sa.add_argument("--num_samples", type=int, default=10, help="Number of samples to generate")
     sa.add_argument("--output", "-o", type=str, default="samples.pt", help="Where to save the sampled trajectories")
+    sa.add_argument("--ema", action="store_true", help="sample from the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
     di = sub.add_parser("distill", help="distil the multi-step model into a single-step model (flags of the reference's distill.py)")
     di.add_argument("config", type=str, help="Path to the training configuration file")
     di.add_argument("checkpoint", type=str, help="Path to the checkpoint to load for the teacher model")
@@ -535,6 +580,12 @@ def main(argv: Optional[list] = None) -> int:
     di.add_argument("--dropout", type=float, default=0.1, help="dropout probability of the student (and of the teacher with --teacher-dropout)")
     di.add_argument("--teacher-dropout", action="store_true", help="leave the teacher in train mode during its rollout, as the "
                     "reference's distill.py does (it never calls teacher_model.eval())")
+    di.add_argument("--ema-teacher", action="store_true", help="build the teacher from the checkpoint's EMA weights (train --ema-decay)")
+    for p in (tr, di):
+        p.add_argument("--ema-decay", type=_ema_decay, default=None, metavar="D", help="keep an exponential moving average of the trained "
+                       "weights with decay D in (0, 1), updated inside the optimizer step; the checkpoint gains ema_model_state_dict and ema")
+        p.add_argument("--no-ema-warmup", action="store_true", help="weight 1 - D from the first update on, instead of "
+                       "1 - min(D, (1 + t) / (10 + t)) after t updates")
     for p in (tr, sa, di):
         p.add_argument("--data", type=str, default=None, help="tensor file with joint_command (+ context keys)")
         p.add_argument("--db", type=str, default=None, help="SQLite database in the reference's schema (SOCCER_DIFFUSION_DB_PATH of the reference)")
@@ -553,8 +604,12 @@ def main(argv: Optional[list] = None) -> int:
     ro.add_argument("--raw", action="store_true", help="the stream carries what the sensors deliver - xyzw quaternions and uint8 camera frames - "
                     "and the session preprocesses it on the device (push_orientation, push_camera)")
     ro.add_argument("--camera", type=str, default=None, metavar="HxW", help="--raw only: the camera's frame size (default 480x640)")
+    ro.add_argument("--ema", action="store_true", help="run the session on the checkpoint's EMA weights (train --ema-decay)")
     ro.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    for flag in ("ema", "ema_teacher"):   # asked for EMA weights the checkpoint does not hold: say so before anything touches the GPU
+        if getattr(args, flag, False):
+            ema_model_state(torch.load(args.checkpoint, map_location="cpu", weights_only=True), "--" + flag.replace("_", "-"), args.checkpoint)
     if not torch.cuda.is_available():
         raise SystemExit("soccerdiffusion_amd needs an MI355X (no CPU fallback)")
     return {"train": cmd_train, "sample": cmd_sample, "distill": cmd_distill, "rollout": cmd_rollout}[args.command](args)

@@ -1121,6 +1121,101 @@ extern "C" int sd_adamw_step(float *p, const float *g, float *m, float *v, long 
     return 0;
 }
 
+// AdamW and the weight EMA in one launch: the update above, expression for expression (p, m, v come out bit for bit as from
+// adamw_kernel / adamw_dev_kernel), then ema += w (p_new - ema) on the parameter still in its register - the EMA costs one more
+// read and one more write per element and no pass of its own.  The subtraction rounds once and the fma once.
+// Contraction is OFF for the AdamW part: the two plain kernels compile to a separate multiply and add at every site (the packed fp32
+// forms pair the products up before any fma could form), and only unfused operations here repeat their roundings whatever the
+// scheduler makes of four elements side by side; tests/test_gpu_ema.py holds the two to the same bits.
+struct adamw_scalars {
+    float decay, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, ema_w;
+};
+
+__device__ __forceinline__ void adamw_ema_update(float &pi, const float gi, float &mi, float &vi, float &ei, const adamw_scalars &h) {
+#pragma clang fp contract(off)
+    pi = pi * h.decay;
+    mi = mi + h.one_minus_b1 * (gi - mi);
+    vi = vi * h.b2 + h.one_minus_b2 * (gi * gi);
+    const float denom = sqrtf(vi) / h.bc2_sqrt + h.eps;
+    pi = pi - h.step_size * (mi / denom);
+    ei = __builtin_fmaf(h.ema_w, pi - ei, ei);
+}
+
+// n4 = n / 4 when all five buffers are 16-byte aligned (one dwordx4 load / store per buffer and lane), else 0; the elements behind
+// 4 n4 - the < 4 of the tail, or all of them - take the scalar loop.  Five streams, no reuse: grid-stride, nothing in LDS.
+__device__ __forceinline__ void adamw_ema_body(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                               float *__restrict__ v, float *__restrict__ ema, long n, long n4, const adamw_scalars &h) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v),
+           *e4 = reinterpret_cast<float4 *>(ema);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = tid; i < n4; i += nth) {
+        const float4 gq = g4[i];
+        float4 pq = p4[i], mq = m4[i], vq = v4[i], eq = e4[i];
+        adamw_ema_update(pq.x, gq.x, mq.x, vq.x, eq.x, h);
+        adamw_ema_update(pq.y, gq.y, mq.y, vq.y, eq.y, h);
+        adamw_ema_update(pq.z, gq.z, mq.z, vq.z, eq.z, h);
+        adamw_ema_update(pq.w, gq.w, mq.w, vq.w, eq.w, h);
+        p4[i] = pq;
+        m4[i] = mq;
+        v4[i] = vq;
+        e4[i] = eq;
+    }
+    for (long i = 4 * n4 + tid; i < n; i += nth) {
+        float pi = p[i], mi = m[i], vi = v[i], ei = ema[i];
+        adamw_ema_update(pi, g[i], mi, vi, ei, h);
+        p[i] = pi;
+        m[i] = mi;
+        v[i] = vi;
+        ema[i] = ei;
+    }
+}
+
+__global__ void adamw_ema_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                                 float *__restrict__ ema, long n, long n4, adamw_scalars h) {
+    adamw_ema_body(p, g, m, v, ema, n, n4, h);
+}
+
+// The scalars from DEVICE memory, as adamw_dev_kernel reads them; the EMA weight through a pointer of its own (word 7 of the graphed
+// step's buffer is the dropout epoch).
+__global__ void adamw_ema_dev_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                                     float *__restrict__ ema, long n, long n4, const float *__restrict__ hyper,
+                                     const float *__restrict__ ema_w) {
+    const adamw_scalars h = {hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], ema_w[0]};
+    adamw_ema_body(p, g, m, v, ema, n, n4, h);
+}
+
+static long adamw_ema_wide(const float *p, const float *g, const float *m, const float *v, const float *ema, long n) {
+    const uintptr_t any = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+    return (any & 15) == 0 ? n / 4 : 0;
+}
+
+static unsigned adamw_ema_grid(long n, long n4) { return grid_for(n4 > 0 ? n4 : n); }
+
+extern "C" int sd_adamw_ema_step(float *p, const float *g, float *m, float *v, float *ema, long n, double lr, double beta1, double beta2,
+                                 double eps, double weight_decay, long step, double ema_weight, void *stream) {
+    if (!p || !g || !m || !v || !ema || n <= 0 || step <= 0 || !(ema_weight >= 0.0 && ema_weight <= 1.0))
+        return fail(SD_E_BADARG, "sd_adamw_ema_step: bad argument");
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const adamw_scalars h = {(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                             (float)(lr / bc1), (float)sqrt(bc2), (float)eps, (float)ema_weight};
+    const long n4 = adamw_ema_wide(p, g, m, v, ema, n);
+    SD_LAUNCH(adamw_ema_kernel, dim3(adamw_ema_grid(n, n4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, n4, h);
+    SD_CHECK_LAUNCH("adamw_ema_kernel");
+    return 0;
+}
+
+extern "C" int sd_adamw_ema_step_dev(float *p, const float *g, float *m, float *v, float *ema, long n, const float *hyper7_dev,
+                                     const float *ema_weight_dev, void *stream) {
+    if (!p || !g || !m || !v || !ema || !hyper7_dev || !ema_weight_dev || n <= 0)
+        return fail(SD_E_BADARG, "sd_adamw_ema_step_dev: bad argument");
+    const long n4 = adamw_ema_wide(p, g, m, v, ema, n);
+    SD_LAUNCH(adamw_ema_dev_kernel, dim3(adamw_ema_grid(n, n4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, n4, hyper7_dev,
+              ema_weight_dev);
+    SD_CHECK_LAUNCH("adamw_ema_dev_kernel");
+    return 0;
+}
+
 // out[c] += sum_r src[r*row_stride + c]   (bias-like gradients over strided rows)
 __global__ void colsum_kernel(const float *__restrict__ src, long row_stride, long rows, int width, float *out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;

@@ -971,6 +971,29 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: flo
                             weight_decay, step, _stream()), "sd_adamw_step")
 
 
+def adamw_ema_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, ema: Tensor, lr: float, beta1: float, beta2: float, eps: float,
+                   weight_decay: float, step: int, ema_weight: float) -> None:
+    """``adamw_step`` and ``ema += ema_weight (p_new - ema)`` in the same launch."""
+    lib = _lib.load()
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _req(t, n)
+    if ema.numel() != p.numel():
+        raise ValueError("ema must have as many elements as p")
+    check(lib.sd_adamw_ema_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                                weight_decay, step, ema_weight, _stream()), "sd_adamw_ema_step")
+
+
+def adamw_ema_step_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, ema: Tensor, hyper7: Tensor, ema_weight: Tensor) -> None:
+    """``adamw_step_dev`` and the EMA in the same launch, this update's weight read from the device float ``ema_weight``."""
+    lib = _lib.load()
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (hyper7, "hyper7"), (ema_weight, "ema_weight")):
+        _req(t, n)
+    if hyper7.numel() < 7 or ema_weight.numel() < 1 or ema.numel() != p.numel():
+        raise ValueError("hyper7 needs 7 floats, ema_weight one, ema as many elements as p")
+    check(lib.sd_adamw_ema_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), hyper7.data_ptr(),
+                                    ema_weight.data_ptr(), _stream()), "sd_adamw_ema_step_dev")
+
+
 # ---- image path: ResNet basic-block convolution (csrc/sd_conv.hip) -------------------------------------
 class PackedConv3x3:
     """A 3 x 3 (or 1 x 1) convolution weight (Cout, Cin, k, k) in the fragment order of ``sd_conv3x3_bn_act`` / ``sd_conv_s2_bn_act`` plus

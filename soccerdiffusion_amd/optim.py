@@ -5,9 +5,10 @@ rewrite of the buffer ends; lookups go from a tensor's address to the live store
 
 from __future__ import annotations
 
+import contextlib
 import os
 import weakref
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 
@@ -148,13 +149,25 @@ class FusedAdamW(torch.optim.Optimizer):
     four flat buffers (parameters are re-pointed to views), so a step is one kernel launch
     and the data-parallel gradient exchange is one all-reduce.  ``state_dict()`` has torch
     AdamW's layout (``state[i] = {step, exp_avg, exp_avg_sq}``), so checkpoints interchange.
-    Being a torch Optimizer, ``OneCycleLR`` drives ``lr`` and ``betas[0]`` as in the reference."""
+    Being a torch Optimizer, ``OneCycleLR`` drives ``lr`` and ``betas[0]`` as in the reference.
+
+    ``ema_decay`` (None = off: nothing allocated, the plain kernels run): an exponential moving average of the parameters in a
+    fifth flat buffer ``flat_ema``, initialised to them and updated by the SAME launch as the AdamW step, eager or replayed
+    (``ema += w_t (p_new - ema)``).  The weight of the update that follows t completed ones is
+    ``w_t = 1 - min(ema_decay, (1 + t) / (10 + t))`` with ``ema_warmup`` (0.9, 0.818.., .. down to ``1 - ema_decay``: a young average
+    forgets its initial weights quickly) and ``1 - ema_decay`` without.  This rule is this package's OWN definition: the reference's
+    lineage took its EMA from ``ema_pytorch`` (``EMA(model, beta=0.9999)``), and neither that nor ``diffusers``' EMAModel is
+    installed here to pin the warmup against - only the fixed point, ``1 - ema_decay``, is common to all of them.  ``state_dict()``
+    stays torch AdamW's; the average travels as a model state dict (``ema_state_dict`` / ``load_ema_state_dict``) beside
+    ``ema_state()``.  Sampling from it in mid-training: ``with optimizer.ema_weights(): ...``."""
 
     def __init__(self, params: Iterable[Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2):
+                 weight_decay: float = 1e-2, ema_decay: Optional[float] = None, ema_warmup: bool = True):
         params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
+        if ema_decay is not None and not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"ema_decay must lie in (0, 1) or be None, got {ema_decay!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         dev = params[0].device
         n = sum(p.numel() for p in params)
@@ -172,6 +185,9 @@ class FusedAdamW(torch.optim.Optimizer):
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.flat_m[at : at + k].view(p.shape),
                              "exp_avg_sq": self.flat_v[at : at + k].view(p.shape)}
             at += k
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
+        self.ema_updates = 0   # completed EMA updates (its own count: an average may start in the middle of a run)
+        self.flat_ema = self.flat_param.clone() if ema_decay is not None else None
         self.planes = WeightPlanes(self.flat_param, params)
         self.refresh_transposes()
 
@@ -196,16 +212,89 @@ class FusedAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         g = self.param_groups[0]
         self._step += 1
-        ops.adamw_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
-                       g["eps"], g["weight_decay"], self._step)
+        if self.flat_ema is None:
+            ops.adamw_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
+                           g["eps"], g["weight_decay"], self._step)
+        else:
+            ops.adamw_ema_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, self.flat_ema, g["lr"], g["betas"][0],
+                               g["betas"][1], g["eps"], g["weight_decay"], self._step, self.ema_weight_for_step(self.ema_updates))
+            self.ema_updates += 1
         self.refresh_transposes()
 
     @torch.no_grad()
-    def step_from_device_hyper(self, hyper7: Tensor) -> None:
+    def step_from_device_hyper(self, hyper7: Tensor, ema_weight: Optional[Tensor] = None) -> None:
         """The update with its scalars read from device memory (``hyper_for_step``): what a captured graph replays.
-        Does NOT advance ``_step`` - the caller that fills ``hyper7`` does."""
-        ops.adamw_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, hyper7)
+        Does NOT advance ``_step`` (nor ``ema_updates``) - the caller that fills ``hyper7`` does.  With an EMA, ``ema_weight`` is the
+        device float that holds ``ema_weight_for_step(ema_updates)`` when the update runs."""
+        if self.flat_ema is None:
+            ops.adamw_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, hyper7)
+        else:
+            if ema_weight is None:
+                raise ValueError("this optimizer keeps an EMA: the update needs the device word with its weight")
+            ops.adamw_ema_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, self.flat_ema, hyper7, ema_weight)
         self.refresh_transposes()
+
+    # ---- weight EMA ---------------------------------------------------------------------
+    def ema_weight_for_step(self, t: int) -> float:
+        """w_t of the class comment: the weight of the EMA update that follows ``t`` completed ones."""
+        if self.ema_decay is None:
+            raise RuntimeError("this optimizer keeps no EMA (ema_decay=None)")
+        if t < 0:
+            raise ValueError("t counts completed updates: >= 0")
+        return 1.0 - (min(self.ema_decay, (1 + t) / (10 + t)) if self.ema_warmup else self.ema_decay)
+
+    def ema_state(self) -> dict:
+        """What a checkpoint keeps beside ``ema_state_dict``: plain types."""
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "num_updates": self.ema_updates}
+
+    def _ema_view(self, t: Tensor):
+        """The slice of flat_ema that stands for ``t`` if ``t`` is one of this optimizer's parameters (by address), else None."""
+        off = t.data_ptr() - self.flat_param.data_ptr()
+        if self.flat_ema is None or t.numel() == 0 or not 0 <= off < 4 * self.flat_param.numel():
+            return None
+        return self.flat_ema[off // 4 : off // 4 + t.numel()].view(t.shape)
+
+    def ema_state_dict(self, model) -> dict:
+        """``model.state_dict()`` with every tensor this optimizer owns replaced by its EMA view; everything else - buffers such as
+        ``mean`` / ``std`` and BatchNorm statistics, frozen parameters, parameters left to no optimizer - is the live model's."""
+        if self.flat_ema is None:
+            raise RuntimeError("this optimizer keeps no EMA (ema_decay=None)")
+        out = model.state_dict()
+        for k, t in out.items():
+            e = self._ema_view(t)
+            if e is not None:
+                out[k] = e
+        return out
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, model, ema_model_state_dict: dict, num_updates: int) -> None:
+        """Resume: flat_ema from a dict written by ``ema_state_dict`` (the entries of the tensors this optimizer owns in ``model``)."""
+        for k, t in model.state_dict().items():
+            e = self._ema_view(t)
+            if e is not None:
+                e.copy_(ema_model_state_dict[k])
+        self.ema_updates = int(num_updates)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the model runs on its EMA weights: the contents of flat_param and flat_ema are exchanged on entry and exchanged back
+        on exit (also after an exception), and the derived copies are refreshed both times, so every kernel - training stacks, samplers,
+        their packed planes - follows.  Take no optimizer step inside."""
+        if self.flat_ema is None:
+            raise RuntimeError("this optimizer keeps no EMA (ema_decay=None)")
+
+        def exchange():
+            with torch.no_grad():
+                held = self.flat_param.clone()
+                self.flat_param.copy_(self.flat_ema)
+                self.flat_ema.copy_(held)
+            self.refresh_transposes()
+
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
 
     def hyper_for_step(self, step: int, out) -> None:
         """The seven scalars of update number ``step`` at the CURRENT lr / betas of the param group -> ``out`` (7 floats)."""

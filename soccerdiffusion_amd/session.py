@@ -374,11 +374,15 @@ class PolicySession:
             return ops.session_commit(x.contiguous(), m.mean, m.std, *self._action, robots=None if subset is None else subset[2])
 
     @classmethod
-    def from_checkpoint(cls, path: str, device=None, **kwargs) -> "PolicySession":
-        """A session on the model of a checkpoint written by ``cli train`` / ``cli distill`` (or by the reference)."""
+    def from_checkpoint(cls, path: str, device=None, ema: bool = False, **kwargs) -> "PolicySession":
+        """A session on the model of a checkpoint written by ``cli train`` / ``cli distill`` (or by the reference).  ``ema=True``: on the
+        checkpoint's ``ema_model_state_dict`` (``cli train --ema-decay``) instead of the last iterate; ValueError if it holds none."""
         from .cli import build_model
 
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        key = "ema_model_state_dict" if ema else "model_state_dict"
+        if key not in ckpt:
+            raise ValueError(f"checkpoint {path} has no '{key}' (ema=True needs one trained with --ema-decay)")
         model = build_model(ckpt["hyperparams"]).to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-        model.load_state_dict(ckpt["model_state_dict"])
+        model.load_state_dict(ckpt[key])
         return cls(model.eval(), hyperparams=ckpt["hyperparams"], **kwargs)

@@ -830,11 +830,14 @@ def broadcast_parameters(optimizer: FusedAdamW, model=None, src: int = 0, group=
 
     if not dist.is_initialized() or dist.get_world_size(group) <= 1:
         return
-    for buf in (optimizer.flat_param, optimizer.flat_m, optimizer.flat_v):
+    ema = getattr(optimizer, "flat_ema", None)   # afterwards a deterministic function of identical parameters: no exchange of its own
+    for buf in (optimizer.flat_param, optimizer.flat_m, optimizer.flat_v) + (() if ema is None else (ema,)):
         dist.broadcast(buf, src=src, group=group)
-    step = torch.tensor([optimizer._step], dtype=torch.int64, device=optimizer.flat_param.device)
+    step = torch.tensor([optimizer._step, getattr(optimizer, "ema_updates", 0)], dtype=torch.int64, device=optimizer.flat_param.device)
     dist.broadcast(step, src=src, group=group)
-    optimizer._step = int(step.item())
+    optimizer._step = int(step[0].item())
+    if ema is not None:
+        optimizer.ema_updates = int(step[1].item())
     if model is not None:
         lo = optimizer.flat_param.data_ptr()
         hi = lo + 4 * optimizer.flat_param.numel()
@@ -859,12 +862,17 @@ def assert_replicas_equal(optimizer: FusedAdamW, group=None) -> None:
     if not dist.is_initialized() or dist.get_world_size(group) <= 1:
         return
     p = optimizer.flat_param.double()
-    sig = torch.stack([p.sum(), (p * p).sum()])
+    sig = [p.sum(), (p * p).sum()]
+    if getattr(optimizer, "flat_ema", None) is not None:
+        e = optimizer.flat_ema.double()
+        sig += [e.sum(), (e * e).sum()]
+    sig = torch.stack(sig)
     lo, hi = sig.clone(), sig.clone()
     dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
     dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
     if not torch.equal(lo, hi):
-        raise RuntimeError(f"data-parallel replicas diverged: parameter checksums differ across ranks ({lo.tolist()} .. {hi.tolist()})")
+        raise RuntimeError(f"data-parallel replicas diverged: parameter{' / EMA' if sig.numel() > 2 else ''} checksums differ across ranks "
+                           f"({lo.tolist()} .. {hi.tolist()})")
 
 
 def allreduce_gradients(optimizer: FusedAdamW, world_size: int, group=None) -> None:
@@ -987,9 +995,10 @@ class GraphedTrainStep:
     """``train_step`` captured into a hipGraph and replayed (decoder-pretraining path or full model, static shapes).
 
     The B = 256 step is ~120 kernel launches issued from Python through autograd; rocprofv3 shows the GPU idle for
-    ~18 % of the step waiting for them.  A replay has no host work beyond one 32-byte upload.  What changes from step to
+    ~18 % of the step waiting for them.  A replay has no host work beyond one 32-byte upload (36 with a weight EMA).  What changes from step to
     step cannot sit in kernel arguments, which a graph freezes, so it comes from device memory instead:
       * AdamW's scalars (OneCycleLR's lr and cycled beta1, the bias corrections) - ``sd_adamw_step_dev``;
+      * with ``FusedAdamW(ema_decay=...)`` the weight of the coming EMA update, a ninth word - ``sd_adamw_ema_step_dev``, same launch;
       * the per-step part of the dropout key - ``sd_set_dropout_epoch`` (process-wide; reset by ``close()``);
       * timesteps and noise come from ``generator`` (registered with the graph: torch advances its Philox offset per replay).
     The first ``eager_steps`` calls run the ordinary ``train_step`` (they are real training steps and warm every lazy
@@ -1011,8 +1020,11 @@ class GraphedTrainStep:
         self.eager_dp = world_size > 1 and not self.split
         self.graph = None
         dev = optimizer.flat_param.device
-        self.hyper = torch.zeros(8, dtype=torch.float32, device=dev)       # 7 AdamW scalars + the dropout epoch word
-        self._ring = [torch.zeros(8, dtype=torch.float32).pin_memory() for _ in range(8)]
+        # 7 AdamW scalars + the dropout epoch word (+ with an EMA the weight of the coming EMA update): ONE pinned upload per step
+        self.ema = optimizer.flat_ema is not None
+        words = 9 if self.ema else 8
+        self.hyper = torch.zeros(words, dtype=torch.float32, device=dev)
+        self._ring = [torch.zeros(words, dtype=torch.float32).pin_memory() for _ in range(8)]
         self._events = [None] * 8
         self._n = 0
         self._epoch = 0
@@ -1042,6 +1054,8 @@ class GraphedTrainStep:
         self.opt.hyper_for_step(self.opt._step + 1, host)
         self._epoch = (self._epoch + 1) & 0x7FFFFFFF
         host[7:8].view(torch.int32)[0] = self._epoch
+        if self.ema:
+            host[8] = self.opt.ema_weight_for_step(self.opt.ema_updates)
         self.hyper.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -1063,8 +1077,11 @@ class GraphedTrainStep:
         loss = mse_loss(pred, noise)
         loss.backward()
         if not self.split:
-            self.opt.step_from_device_hyper(self.hyper[:7])
+            self._update()
         return loss.detach()
+
+    def _update(self):
+        self.opt.step_from_device_hyper(self.hyper[:7], self.hyper[8:9] if self.ema else None)
 
     def __call__(self, joint_targets: Tensor, context=None, input_data=None) -> Tensor:
         if self.eager_left > 0 or self.eager_dp:
@@ -1085,8 +1102,9 @@ class GraphedTrainStep:
         ops.bump_weights_generation()   # the replayed update rewrote the flat parameter buffer without any Python-side hook
         if self.split:
             allreduce_gradients(self.opt, self.world)
-            self.opt.step_from_device_hyper(self.hyper[:7])
+            self._update()
         self.opt._step += 1
+        self.opt.ema_updates += int(self.ema)
         if self.lr_sched is not None:
             self.lr_sched.step()
         return self._loss

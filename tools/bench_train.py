@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Secondary metric: training trajectories/s (one fwd + bwd + AdamW per trajectory) at BASELINE
 config 2: decoder d=256, L=4, B=256, T=100, J=20, M=11 (decoder-pretraining path), fp32.
-N>1 under torchrun: data parallel, one flat-gradient all-reduce per step."""
+N>1 under torchrun: data parallel, one flat-gradient all-reduce per step.
+--ema-decay D: the same step with the weight EMA riding in the AdamW launch (FusedAdamW(ema_decay=D))."""
 import argparse, json, os, sys, time
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +14,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--ema-decay", type=float, default=None)
     args = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dev = torch.device("cuda", local)
@@ -32,7 +34,7 @@ def main():
                   use_gamestate=False, encoder_patch_size=10)
     torch.manual_seed(0)
     model = cli.build_model(params).to(dev).train()
-    opt = training.FusedAdamW(model.parameters(), lr=1e-4)
+    opt = training.FusedAdamW(model.parameters(), lr=1e-4, ema_decay=args.ema_decay)
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=1e-4, total_steps=args.steps + args.warmup + 1)
     ns = DDIMScheduler(beta_schedule="squaredcos_cap_v2", clip_sample=False)
     B = args.batch
@@ -59,7 +61,8 @@ def main():
         flops = 3 * 478_478_336 * B * world * args.steps
         print(json.dumps({"metric": "training trajectories/s (fwd+bwd+AdamW, d=256 L=4 T=100 J=20 M=11, fp32)",
                           "value": round(world * B * args.steps / dt, 1), "n_gpus": world, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                          "batch_per_gpu": B, "algorithmic_tflops": round(flops / dt / 1e12, 2), "loss": float(loss)}))
+                          "batch_per_gpu": B, "algorithmic_tflops": round(flops / dt / 1e12, 2), "loss": float(loss),
+                          **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_floats": opt.flat_ema.numel()})}))
     if world > 1:
         dist.destroy_process_group()
 

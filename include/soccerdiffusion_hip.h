@@ -221,6 +221,28 @@ int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const flo
                        const float *coef, float *x, float *trace, float *eps_trace, float *workspace,
                        int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream);
 
+/* sd_ddim_sample_eps with pinned leading rows (conditioning by inpainting: the first rows of the new trajectory are held to the rows of
+ * the one the robot is still executing).  Row t of trajectory b is pinned iff t < pin_rows[b].
+ *   pin_x0 (B,T,J): the known rows, in normalised space; only the pinned rows are read.  pin_noise (B,T,J): the rollout's start noise
+ *   (what x holds on entry); it must not alias x.  pin_rows (B) int32 in device memory, 0 <= pin_rows[b] <= T: a batch may mix pinned
+ *   and unpinned trajectories (pin_rows[b] = 0), and a captured graph needs no new arguments when the counts change.
+ *   On entry:     pinned elements of x = c0[0] * pin_x0 + c1[0] * pin_noise           (coef[i] = (c0, c1, c2, c3) as for sd_ddim_sample)
+ *   after step i: pinned elements of x = c2[i] * pin_x0 + c3[i] * pin_noise in place of the DDIM update; every other element gets the
+ *                 update of sd_ddim_sample_eps unchanged.  eps_trace stays the network's prediction for all rows.
+ * With the sampler's leading spacing c2[i] == c0[i+1] and c3[i] == c1[i+1]: at the entry of every step the pinned rows are the forward-
+ * noised pin_x0 at that step's t - exactly a training-time add_noise sample, which the network reads through self-attention.  The last
+ * step has c2 = 1, c3 = 0: the pinned rows of the returned sample equal pin_x0 bit for bit (finite noise).
+ * Kernels: on the trajectory routes (SD_ROUTE_TRAJ_*) the lane that stores a step's DDIM update stores the pinned value instead, in the
+ * same single launch (pinned instantiations of the step kernels); on the row-panel and chain routes one elementwise launch follows each
+ * step's update (on SD_ROUTE_FUSED_FOLD_F16 every step's head is then a launch of its own: the head merged into the previous step's last
+ * layer would read x before the pinned rows are rewritten).  The entry overwrite is one elementwise launch per rollout on every
+ * route.  Mode 4's two-product kernels have no pinned twin: max_mode = 4 runs the mode-3 kernels (and needs no status word).
+ * Everything else as sd_ddim_sample_eps.
+ * SD_E_BADARG on a NULL pin pointer or pin_noise == x, before any launch. */
+int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                       float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                       const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, void *stream);
+
 /* The denoiser evaluated ONE step at a time on the trajectory kernels of sampler modes 3 / 4 - the reference's own loop form,
  *   for t in scheduler.timesteps: eps = model.forward_with_context(ctx, x, t); x = scheduler.step(eps, t, x).prev_sample
  * (soccer_diffusion/ml/inference/plot.py:122-131, ml/training/distill.py:179-189, ml/inference/ros.py:301-310), whose
@@ -701,6 +723,14 @@ int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int 
  *     all L rows of the robot's ring = fill (C floats in device memory; NULL: zeros), its head word = 0 (by one thread, after a barrier),
  *     and, in ring 0's workgroup, game_state[b] = game_state_value (game_state (B) int64; NULL: none).  A workgroup whose robot is not
  *     selected returns at once.  The arguments are the same whichever robots are selected and the host reads nothing back.
+ * Overlapping ticks (a session that carries the tail of one tick's trajectory into the next as pinned rows of sd_ddim_sample_pin):
+ *   sd_session_commit_carry, sd_session_commit_carry_at: sd_session_commit / sd_session_commit_at that also prepare the next tick, in the
+ *     same ONE launch.  All T rows are published, rounded the same way; only the first `advance` of them - the commands executed before
+ *     the next tick - go into the action ring (head += advance); rows [advance, advance + carry) of x, as sampled (normalised space),
+ *     become rows [0, carry) of pin_x0[robot] (pin_x0 (B, T, J)) and pin_rows[robot] = carry (pin_rows (B) int32).  advance, carry >= 0,
+ *     advance + carry <= T.  x and out are indexed by workgroup (compact in the _at form), pin_x0 and pin_rows by robot.
+ *   sd_session_reset_carry: sd_session_reset that also sets pin_rows[b] = 0 for the selected robots (ring 0's workgroup): their next tick
+ *     is unpinned.  One launch, nothing read back.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
 #define SD_SESSION_MAX_RESET_RINGS 5
@@ -731,6 +761,13 @@ int sd_session_commit_at(const float *x, const float *mean, const float *stdv, f
                          int S, int B, int T, int J, int L, void *stream);
 int sd_session_reset(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value, int B,
                      void *stream);
+int sd_session_commit_carry(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, int B, int T, int J,
+                            int L, int advance, int carry, float *pin_x0, int32_t *pin_rows, void *stream);
+int sd_session_commit_carry_at(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head,
+                               const int32_t *robots, int S, int B, int T, int J, int L, int advance, int carry, float *pin_x0,
+                               int32_t *pin_rows, void *stream);
+int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value,
+                           int32_t *pin_rows, int B, void *stream);
 
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair

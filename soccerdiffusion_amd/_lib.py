@@ -134,6 +134,7 @@ SIGNATURES = {
     "sd_ddim_sample": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_ddim_sample_ex": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_ddim_sample_eps": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_ddim_sample_pin": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sd_bn_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int]),
     "sd_bn_train_fwd": (C.c_int, [C.c_void_p] * 12 + [C.c_int64, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "sd_convt3x3_s2": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 5 + [C.c_void_p]),
@@ -231,6 +232,9 @@ SIGNATURES = {
     "sd_session_windows_at": (C.c_int, [C.POINTER(RingView), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sd_session_commit_at": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]),
     "sd_session_reset": (C.c_int, [C.POINTER(RingReset), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "sd_session_commit_carry": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p] * 3),
+    "sd_session_commit_carry_at": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_void_p] * 3),
+    "sd_session_reset_carry": (C.c_int, [C.POINTER(RingReset), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

@@ -5,7 +5,7 @@ soccer_diffusion/ml/inference/plot.py:21-135).
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -497,13 +497,17 @@ def _camera_size(text: str) -> tuple:
 
 def cmd_rollout(args) -> int:
     """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep.
-    --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again."""
+    --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again.
+    --carry K [--advance S]: overlapping ticks - S trajectory points (default T - K) pass between two ticks, the sensor rows of S points
+    arrive per tick, and the first K rows of a tick's trajectory are pinned to rows [S, S + K) of the previous one."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
         raise SystemExit("rollout needs --synthetic N (robots, N >= 1) and --ticks K (K >= 1)")
     if args.camera is not None and not args.raw:
         raise SystemExit("--camera is the frame size of the --raw stream")
+    if args.advance is not None and not args.carry and args.advance < 1:
+        raise SystemExit("--advance takes a positive number of trajectory points")
     camera = _camera_size(args.camera or "480x640")
     episode = None
     if args.episode_ticks is not None:
@@ -517,14 +521,14 @@ def cmd_rollout(args) -> int:
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
-                                            seed=args.seed)
+                                            seed=args.seed, carry=args.carry, advance=args.advance)
     params = session.hyperparams
     if args.raw:
         stream = raw_sensor_stream(args.synthetic, params, args.ticks, camera, seed=args.seed)
     else:
         stream = synthetic_sensor_stream(args.synthetic, params, args.ticks, seed=args.seed)
     stream = {k: v.to(device) for k, v in stream.items()}
-    T = params["trajectory_prediction_length"]
+    T = session.advance   # trajectory points - sensor rows - between two ticks: the whole horizon without --carry / --advance
     published, resets = [], []
     for k in range(args.ticks):
         if params["use_joint_states"]:
@@ -544,6 +548,8 @@ def cmd_rollout(args) -> int:
                 session.reset(robots=resets[-1])
     traj = torch.stack(published).cpu()   # (K, N, T, J)
     saved = {"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}
+    if args.carry or args.advance is not None:
+        saved.update(carry=session.carry, advance=session.advance)
     if episode is not None:
         saved["resets"] = torch.stack(resets)   # (K, N): robot n was reset after tick k
     torch.save(saved, args.output)
@@ -605,6 +611,10 @@ def main(argv: Optional[list] = None) -> int:
                     "and the session preprocesses it on the device (push_orientation, push_camera)")
     ro.add_argument("--camera", type=str, default=None, metavar="HxW", help="--raw only: the camera's frame size (default 480x640)")
     ro.add_argument("--ema", action="store_true", help="run the session on the checkpoint's EMA weights (train --ema-decay)")
+    ro.add_argument("--carry", type=int, default=0, metavar="K", help="overlapping ticks: the first K rows of every tick's trajectory are pinned to "
+                    "the rows of the previous one that fall in the overlap (PolicySession(carry=K))")
+    ro.add_argument("--advance", type=int, default=None, metavar="S", help="trajectory points between two ticks (default: horizon - K); a tick "
+                    "commits that many rows to the action history")
     ro.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     for flag in ("ema", "ema_teacher"):   # asked for EMA weights the checkpoint does not hold: say so before anything touches the GPU

@@ -301,6 +301,14 @@ __device__ __forceinline__ f32x4 dropout_quad(const DropoutArgs &a, unsigned lon
     return m;
 }
 
+// Pinned leading rows of a rollout (sd_ddim_sample_pin): row t of trajectory b is pinned iff t < rows[b]; its elements of x are
+// ck * x0 + cn * noise instead of the DDIM update - (ck, cn) = (c0, c1) of step 0 on entry, (c2, c3) of step i after step i.
+// The trajectory step kernels' pinned instantiations take it beside their StepArgs; ddim_pin_kernel (sd_kernels.hip) does the rest.
+struct PinArgs {
+    const float *x0, *noise;   // [B][T][J] each: the known rows (normalised space) and the rollout's start noise
+    const int *rows;           // [B] in device memory, 0 <= rows[b] <= T
+};
+
 static inline unsigned grid_for(long n, int block = 256) {
     long g = (n + block - 1) / block;
     if (g > 256 * 8) g = 256 * 8;

@@ -2493,6 +2493,18 @@ __global__ void finite_check_kernel(const float *__restrict__ x, long n, int *st
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, bit);
 }
 
+// Pinned leading rows of a rollout (PinArgs, sd_common.h): x[b][t][:] = ck * x0 + cn * noise for t < rows[b], every other element left as
+// it is.  Once per rollout with (c0, c1) of step 0 - the entry overwrite, on every route - and after every step's DDIM update with that
+// step's (c2, c3) on the row-panel and chain routes; the trajectory step kernels' pinned instantiations do the latter in their own epilogue.
+__global__ void ddim_pin_kernel(float *__restrict__ x, PinArgs pin, float ck, float cn, long n, int T, int J) {
+    const long per = (long)T * J;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / per;
+        const int t = (int)((i - b * per) / J);
+        if (t < pin.rows[b]) x[i] = ck * pin.x0[i] + cn * pin.noise[i];
+    }
+}
+
 
 // ======================================================================================
 // Layer drivers
@@ -2737,7 +2749,7 @@ static int f16_prepare(const sd_denoiser_weights *w, const Scratch &s, int B, in
 
 // one denoiser step + DDIM update on the fp16x3 kernels (step index i selects the step-token blocks)
 static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scratch &s, int B, int T, int Mc, int i, int n_steps,
-                             const float *coef, hipStream_t st, float *eps = nullptr) {
+                             const float *coef, hipStream_t st, float *eps = nullptr, bool pinned = false) {
     const int d = w->d, heads = w->heads, L = w->L, Mk = Mc + 1;
     const long R = (long)B * T;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)B * 64;
@@ -2749,9 +2761,10 @@ static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scrat
     const int hfrag = !(henv && strcmp(henv, "rows") == 0);
     F16HeadArgs fh{DecoderHeadArgs{x, w->emb_w, w->emb_b, w->pe, l0.n1_w, l0.n1_b, l0.sa_in_w, l0.sa_in_b, s.h, s.qkv, R, T, w->J},
                    f16_wf(s.wf, 0, d, 3), s.scales, hm ? 1 : 0, hfrag};
-    // the head of steps 1.. runs inside the previous step's last layer kernel (SD_MERGE_HEAD=0: always its own launch; A/B runs)
+    // the head of steps 1.. runs inside the previous step's last layer kernel (SD_MERGE_HEAD=0: always its own launch; A/B runs).
+    // Not in a pinned rollout: the merged head would embed x as the DDIM update left it, before ddim_pin_kernel has rewritten the pinned rows
     static const char *menv = getenv("SD_MERGE_HEAD");
-    const bool merge = !(menv && strcmp(menv, "0") == 0) && T >= 64 && w->J <= 64;
+    const bool merge = !(menv && strcmp(menv, "0") == 0) && T >= 64 && w->J <= 64 && !pinned;
     int rc = 0;
     if (i == 0 || !merge) rc = decoder_head_f16(fh, st);
     if (rc) return rc;
@@ -2938,9 +2951,10 @@ struct TrajCall {
         return trajg_prepare_steps(w, s.gws, tokens, s.kvstep, B, Mc, n_tok, st, per_traj ? s.stepmap : nullptr);
     }
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
-    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status) const {
-        if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr);
-        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status);
+    // pin: the pinned instantiations (the caller's plan is a three-product one)
+    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr) const {
+        if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr, pin);
+        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status, pin);
     }
 };
 
@@ -2955,19 +2969,28 @@ static int finite_check(const float *x, long n, int32_t *status, hipStream_t st)
     return 0;
 }
 
-// the rollout on the trajectory kernels: one launch per DDIM step
+// pinned rows of x <- ck * x0 + cn * noise (ddim_pin_kernel)
+static int ddim_pin(float *x, const PinArgs &pin, float ck, float cn, int B, int T, int J, hipStream_t st) {
+    const long n = (long)B * T * J;
+    SD_LAUNCH(ddim_pin_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, pin, ck, cn, n, T, J);
+    SD_CHECK_LAUNCH("ddim_pin_kernel");
+    return 0;
+}
+
+// the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once)
 static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
-                        int32_t *status) {
+                        int32_t *status, const PinArgs *pin = nullptr) {
     const long n = (long)c.B * c.T * c.w->J;
     int rc;
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
     if ((rc = c.prepare_weights())) return rc;
     if ((rc = c.prepare_ctx(ctx))) return rc;
     if ((rc = c.prepare_steps(step_tokens, false))) return rc;
+    if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status))) return rc;
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
@@ -2975,7 +2998,8 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
 
 // the rollout on the row-panel kernels (sampler modes 0 - 2)
 static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const SamplerPlan &plan, const float *ctx, const float *step_tokens,
-                         const float *coef, float *x, float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, hipStream_t st) {
+                         const float *coef, float *x, float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, hipStream_t st,
+                         const PinArgs *pin = nullptr) {
     const int d = w->d, R = B * T, L = w->L;
     int rc;
     // once per rollout: K/V of the context rows (placed as rows 0..Mc-1 of each trajectory's
@@ -3025,12 +3049,13 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
         SD_CHECK_LAUNCH("kv_place_kernel");
     }
     const long n = (long)R * w->J;
+    if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], B, T, w->J, st))) return rc;
     for (int i = 0; i < n_steps; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
         // this step's token row -> row Mc of every trajectory, all layers in one launch
         if (f16) {
-            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i))) return rc;
+            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i, pin != nullptr))) return rc;
         } else if (fold) {
             SD_LAUNCH(fold_place_kernel, dim3(grid_for((long)B * 4 * 2 * d), L), dim3(256), 0, st, s.gvstep + (size_t)i * 4 * 2 * d,
                       s.cstep + (size_t)i * 4, (long)gvsstride, (long)cssstride, s.gv, s.cb, (long)gvstride, (long)cbstride, B, Mc,
@@ -3047,14 +3072,16 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
             rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x, coef + 4 * i}, st);
             if (rc) return rc;
         }
+        // these routes are many launches per step already: the pinned rows are one more, behind the fused DDIM sites
+        if (pin && (rc = ddim_pin(x, *pin, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, st))) return rc;
     }
     return status ? finite_check(x, n, status, st) : 0;
 }
 
-extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
-                                  const float *coef, float *x, float *trace, float *eps_trace, float *workspace, int B, int T, int Mc,
-                                  int n_steps, int32_t *status, int max_mode, void *stream) {
+static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                           float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream,
+                           const PinArgs *pin) {
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!step_tokens || !coef || !x || !workspace || B <= 0 || T <= 0 || Mc < 0 || n_steps <= 0 || (Mc > 0 && !ctx))
@@ -3068,8 +3095,25 @@ extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
     const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode);
-    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status);
-    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st);
+    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin);
+    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin);
+}
+
+extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
+                                  const float *coef, float *x, float *trace, float *eps_trace, float *workspace, int B, int T, int Mc,
+                                  int n_steps, int32_t *status, int max_mode, void *stream) {
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr);
+}
+
+// Mode 4's two-product instantiations have no pinned twin: max_mode 4 is read as 3 (and needs no status word)
+extern "C" int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                  float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                  int max_mode, const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, void *stream) {
+    if (!pin_x0 || !pin_noise || !pin_rows) return fail(SD_E_BADARG, "sd_ddim_sample_pin: pin_x0, pin_noise and pin_rows must be given");
+    if (pin_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_pin: pin_noise must not alias x (x is overwritten by the first step)");
+    const PinArgs pin{pin_x0, pin_noise, pin_rows};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode == 4 ? 3 : max_mode,
+                           stream, &pin);
 }
 
 // ---- the denoiser evaluated step by step on the trajectory kernels (the reference's own loop form) --------------------------

@@ -1,6 +1,7 @@
 // Closed-loop policy session: the buffer work of the receding-horizon tick (soccer_diffusion/ml/inference/ros.py:165-335) on the device.
 // Interface, ring layout and citations: include/soccerdiffusion_hip.h (sd_ring_push, sd_ring_window, sd_session_windows, sd_session_commit,
-// their *_at forms for a subset of the robots, sd_ring_push_quat and sd_session_reset).
+// their *_at forms for a subset of the robots, sd_ring_push_quat, sd_session_reset, and sd_session_commit_carry(_at) / sd_session_reset_carry for a
+// session whose ticks overlap).
 //
 // ros.py keeps every sensor stream as a Python list of CPU tensors (append, then trim to the context length: ros.py:203,256-257,316-318)
 // and stacks + uploads every list at every tick (ros.py:265-275).  Here a stream is a ring (B, L, C) in device memory with one head word per
@@ -162,6 +163,37 @@ __global__ __launch_bounds__(THREADS) void session_commit_kernel(const float *x,
     if (threadIdx.x == 0) head[b] = (h + T % L) % L;
 }
 
+// session_commit_kernel that also prepares the next tick: all T rows are published (the same expression), the first `advance` of them - the
+// commands executed before the next tick - go to the action ring, rows [advance, advance + carry) of x (normalised space, as sampled) become
+// rows [0, carry) of the robot's pin_x0 block and pin_rows[robot] = carry.  x is indexed by workgroup, pin_x0 and pin_rows by robot.
+__global__ __launch_bounds__(THREADS) void session_commit_carry_kernel(const float *x, const float *__restrict__ mean,
+                                                                       const float *__restrict__ stdv, float *out, float *ring,
+                                                                       int32_t *head, const int32_t *__restrict__ robots, int B, int T, int J,
+                                                                       int L, int advance, int carry, float *pin_x0, int32_t *pin_rows) {
+    const int b = robot_of(robots, blockIdx.x, B);
+    if (b < 0) return;
+    const int h = head_of(head, b, L);
+    const float *xb = x + (long)blockIdx.x * T * J;
+    float *ob = out + (long)blockIdx.x * T * J;
+    float *rb = ring + (long)b * L * J;
+    float *pb = pin_x0 + (long)b * T * J;
+    const float pi = (float)M_PI;
+    const int r0 = advance > L ? advance - L : 0;   // (as push_rows: with advance > L only the last L rows reach the ring)
+    for (int i = threadIdx.x; i < T * J; i += THREADS) {
+        const int r = i / J, c = i - r * J;
+        const float xv = xb[i];                             // read once: out may be x
+        const float v = (xv * stdv[c] + mean[c]) - pi;
+        ob[i] = v;
+        if (r >= r0 && r < advance) rb[(long)((h + r) % L) * J + c] = v;
+        if (r >= advance && r < advance + carry) pb[i - advance * J] = xv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        head[b] = (h + advance % L) % L;
+        pin_rows[b] = carry;
+    }
+}
+
 static int launch_windows(const Views &a, int n_views, int S, hipStream_t st) {
     SD_LAUNCH(ring_windows_kernel, dim3((unsigned)S, (unsigned)n_views), dim3(THREADS), 0, st, a);
     SD_CHECK_LAUNCH("ring_windows_kernel");
@@ -186,6 +218,25 @@ __global__ __launch_bounds__(THREADS) void session_reset_kernel(Resets a, const 
     if (threadIdx.x == 0) {
         r.head[b] = 0;
         if (blockIdx.y == 0 && game_state) game_state[b] = game_state_value;
+    }
+}
+
+// session_reset_kernel for a session with carry: ring 0's workgroup also zeroes the robot's pin_rows word - its next tick is unpinned
+__global__ __launch_bounds__(THREADS) void session_reset_carry_kernel(Resets a, const uint8_t *__restrict__ mask, int64_t *game_state,
+                                                                      int64_t game_state_value, int32_t *pin_rows) {
+    const int b = blockIdx.x;
+    if (mask && !mask[b]) return;
+    const sd_ring_reset r = a.r[blockIdx.y];
+    const int L = r.L, C = r.C;
+    float *ring = r.ring + (long)b * L * C;
+    for (int i = threadIdx.x; i < L * C; i += THREADS) ring[i] = r.fill ? r.fill[i % C] : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        r.head[b] = 0;
+        if (blockIdx.y == 0) {
+            pin_rows[b] = 0;
+            if (game_state) game_state[b] = game_state_value;
+        }
     }
 }
 
@@ -288,6 +339,49 @@ extern "C" int sd_session_commit_at(const float *x, const float *mean, const flo
     SD_LAUNCH(ss::session_commit_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head, robots, B, T, J,
               L);
     SD_CHECK_LAUNCH("session_commit_kernel");
+    return 0;
+}
+
+static bool carry_ok(int T, int advance, int carry) { return advance >= 0 && carry >= 0 && advance + carry <= T; }
+
+extern "C" int sd_session_commit_carry(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head, int B, int T,
+                                       int J, int L, int advance, int carry, float *pin_x0, int32_t *pin_rows, void *stream) {
+    if (!x || !mean || !stdv || !out || !ring || !head || !pin_x0 || !pin_rows || !dims_ok(B, L, J) || !dims_ok(B, T, J) || !carry_ok(T, advance, carry))
+        return fail(SD_E_BADARG, "sd_session_commit_carry: x, mean, std, out, ring, head, pin_x0 and pin_rows must be given; B, T, J, L > 0, "
+                                 "advance, carry >= 0, advance + carry <= T");
+    SD_LAUNCH(ss::session_commit_carry_kernel, dim3((unsigned)B), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head,
+              (const int32_t *)nullptr, B, T, J, L, advance, carry, pin_x0, pin_rows);
+    SD_CHECK_LAUNCH("session_commit_carry_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_commit_carry_at(const float *x, const float *mean, const float *stdv, float *out, float *ring, int32_t *head,
+                                          const int32_t *robots, int S, int B, int T, int J, int L, int advance, int carry, float *pin_x0,
+                                          int32_t *pin_rows, void *stream) {
+    if (!mean || !stdv || !ring || !head || !pin_x0 || !pin_rows || !dims_ok(B, L, J) || !dims_ok(B, T, J) || !carry_ok(T, advance, carry) || S < 0 ||
+        (S > 0 && (!x || !out || !robots)))
+        return fail(SD_E_BADARG, "sd_session_commit_carry_at: mean, std, ring, head, pin_x0, pin_rows and (for S > 0) x, out and robots must be given; "
+                                 "B, T, J, L > 0, S >= 0, advance, carry >= 0, advance + carry <= T");
+    if (S == 0) return 0;
+    SD_LAUNCH(ss::session_commit_carry_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, x, mean, stdv, out, ring, head, robots, B,
+              T, J, L, advance, carry, pin_x0, pin_rows);
+    SD_CHECK_LAUNCH("session_commit_carry_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value,
+                                      int32_t *pin_rows, int B, void *stream) {
+    if (!rings || n_rings < 1 || n_rings > SD_SESSION_MAX_RESET_RINGS || B <= 0 || !pin_rows)
+        return fail(SD_E_BADARG, "sd_session_reset_carry: 1 .. 5 rings, pin_rows and B > 0");
+    ss::Resets a{};
+    for (int i = 0; i < n_rings; ++i) {
+        if (!rings[i].ring || !rings[i].head || !dims_ok(B, rings[i].L, rings[i].C))
+            return fail(SD_E_BADARG, "sd_session_reset_carry: every ring needs ring and head; L, C > 0");
+        a.r[i] = rings[i];
+    }
+    SD_LAUNCH(ss::session_reset_carry_kernel, dim3((unsigned)B, (unsigned)n_rings), dim3(ss::THREADS), 0, (hipStream_t)stream, a, mask, game_state,
+              game_state_value, pin_rows);
+    SD_CHECK_LAUNCH("session_reset_carry_kernel");
     return 0;
 }
 

@@ -1399,8 +1399,10 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
     TJ_STAMP(39);
 }
 
-template <bool WIDE = false>
-static __device__ __forceinline__ void step_body(const StepArgs &a) {
+// PIN: the lanes that store the DDIM update store c2 * x0 + c3 * noise instead for the tokens below pin.rows[traj] (PinArgs, sd_common.h);
+// the noise prediction is written for every row all the same.  No barrier and no LDS of its own.
+template <bool WIDE = false, bool PIN = false>
+static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     ctx_init(c, smem, a.T);
@@ -1478,6 +1480,8 @@ static __device__ __forceinline__ void step_body(const StepArgs &a) {
     // ---- fc_out + DDIM: eps^T = Wout . h^T + b.  h has no a-priori bound: one power-of-two scale per token
     {
         float *stat = reinterpret_cast<float *>(c.smem + LDS_STAT);
+        int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
+        if constexpr (PIN) pin_rows = pin.rows[traj];
         float am[NTT];
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
@@ -1536,12 +1540,20 @@ static __device__ __forceinline__ void step_body(const StepArgs &a) {
                 const int j0 = 16 * n + 4 * c.g;
                 if (!ok || j0 >= J) continue;
                 const long at = (traj * a.T + tok) * J + j0;
+                bool pinned = false;
+                if constexpr (PIN) pinned = tok < pin_rows;
                 if (J & 3) {   // rows of J floats are not 16-byte aligned, the last group of four is ragged: element by element
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (j0 + r >= J) continue;
                         const float e = E[n][r] * c_o + a.b_out[j0 + r];
                         if (a.eps_out) a.eps_out[at + r] = e;
+                        if constexpr (PIN) {
+                            if (a.update_x && pinned) {
+                                a.x[at + r] = a.c2 * pin.x0[at + r] + a.c3 * pin.noise[at + r];
+                                continue;
+                            }
+                        }
                         if (a.update_x) {
                             const float x0 = (a.x[at + r] - a.c1 * e) / a.c0;
                             a.x[at + r] = a.c2 * x0 + a.c3 * e;
@@ -1551,6 +1563,13 @@ static __device__ __forceinline__ void step_body(const StepArgs &a) {
                 }
                 const f32x4 e = E[n] * c_o + *reinterpret_cast<const f32x4 *>(a.b_out + j0);
                 if (a.eps_out) *reinterpret_cast<f32x4 *>(a.eps_out + at) = e;
+                if constexpr (PIN) {
+                    if (a.update_x && pinned) {
+                        const f32x4 k = *reinterpret_cast<const f32x4 *>(pin.x0 + at), nz = *reinterpret_cast<const f32x4 *>(pin.noise + at);
+                        *reinterpret_cast<f32x4 *>(a.x + at) = a.c2 * k + a.c3 * nz;
+                        continue;
+                    }
+                }
                 if (a.update_x) {
                     const f32x4 xv = *reinterpret_cast<const f32x4 *>(a.x + at);
                     f32x4 xn;
@@ -1574,6 +1593,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_kernel(StepArgs a) { TJ
 // ... with 17 .. 64 memory rows (2 .. 4 key tiles in the folded cross-attention: cross_wide); three products everywhere
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_kernel(StepArgs a) { TJ<NTT, true>::template step_body<true>(a); }
+// the pinned twins of the mode-3 kernel (three products everywhere) and of the wide one (sd_ddim_sample_pin); mode 4 has none
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_pin_kernel(StepArgs a, PinArgs pin) { TJ<NTT, true>::template step_body<false, true>(a, pin); }
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_pin_kernel(StepArgs a, PinArgs pin) { TJ<NTT, true>::template step_body<true, true>(a, pin); }
 
 
 }   // namespace tj

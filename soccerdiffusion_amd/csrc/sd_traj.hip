@@ -54,6 +54,21 @@ static TrajStepFn traj_step_fn(int ntt) {
     }
 }
 
+// the pinned twins (sd_ddim_sample_pin): the mode-3 kernel and the wide one; mode 4's two-product instantiations have none
+typedef void (*TrajStepPinFn)(tj::StepArgs, PinArgs);
+static TrajStepPinFn traj_step_pin_fn(int ntt, bool wide) {
+    switch (ntt) {
+        case 1: return wide ? tj::traj_step_wide_pin_kernel<1> : tj::traj_step_pin_kernel<1>;
+        case 2: return wide ? tj::traj_step_wide_pin_kernel<2> : tj::traj_step_pin_kernel<2>;
+        case 3: return wide ? tj::traj_step_wide_pin_kernel<3> : tj::traj_step_pin_kernel<3>;
+        case 4: return wide ? tj::traj_step_wide_pin_kernel<4> : tj::traj_step_pin_kernel<4>;
+        case 5: return wide ? tj::traj_step_wide_pin_kernel<5> : tj::traj_step_pin_kernel<5>;
+        case 6: return wide ? tj::traj_step_wide_pin_kernel<6> : tj::traj_step_pin_kernel<6>;
+        case 7: return wide ? tj::traj_step_wide_pin_kernel<7> : tj::traj_step_pin_kernel<7>;
+        default: return nullptr;
+    }
+}
+
 // zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
 __global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -292,7 +307,7 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
 // one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
 // coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status) {
+              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin) {
     const int d = w->d, L = w->L;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
     tj::StepArgs a{};
@@ -335,6 +350,20 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *ep
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
     const TrajStepFn fn = variant == 2 ? traj_step_wide_fn(ntt) : (precise ? traj_step_fn<true>(ntt) : traj_step_fn<false>(ntt));
     if (!fn) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
+    if (pin) {
+        if (!coef || variant == 0) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
+        const TrajStepPinFn pfn = traj_step_pin_fn(ntt, variant == 2);
+        ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
+        static DevFlag pin_attr_set[2][8];
+        if (!pin_attr_set[variant - 1][ntt]) {
+            const hipError_t e = hipFuncSetAttribute((const void *)pfn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
+            if (e != hipSuccess) return fail((int)e, "traj_step_pin_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+            pin_attr_set[variant - 1][ntt] = true;
+        }
+        SD_LAUNCH(pfn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a, *pin);
+        SD_CHECK_LAUNCH("traj_step_pin_kernel");
+        return 0;
+    }
     ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
     static DevFlag attr_set[3][8];
     if (!attr_set[variant][ntt]) {

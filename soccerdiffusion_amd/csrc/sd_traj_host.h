@@ -23,7 +23,8 @@ int traj_prepare_weights(const sd_denoiser_weights *w, const TrajWs &s, hipStrea
 int traj_prepare_ctx(const sd_denoiser_weights *w, const TrajWs &s, const float *ctx, int B, int Mc, int nkt, hipStream_t st);
 int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const float *tokens, int n_tok, int Mc, hipStream_t st, bool per_traj = false);
 // one denoiser step (+ DDIM update when coef != NULL); step index i of the n_tok prepared step blocks, or block b for trajectory b (per_traj).
-// precise: three fp16 products at the Q | K | V site (sampler mode 3), else two (mode 4, which reports sharp logits through status)
+// precise: three fp16 products at the Q | K | V site (sampler mode 3), else two (mode 4, which reports sharp logits through status).
+// pin (needs coef and precise: mode 4 has no pinned twin): rows below pin->rows[b] become c2 * x0 + c3 * noise in the same launch
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status);
+              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin = nullptr);
 #endif

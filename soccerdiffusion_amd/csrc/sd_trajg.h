@@ -4,6 +4,7 @@
 #define SD_TRAJG_H
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "sd_common.h"          // PinArgs
 #include "sd_sampler_plan.h"   // trajg_ok: the shapes the generic kernels are instantiated for
 struct sd_denoiser_weights;
 
@@ -16,7 +17,8 @@ int trajg_prepare_ctx(const sd_denoiser_weights *w, float *gws, const float *ctx
 // map (or NULL): per-trajectory step tokens, trajectory b uses the rows of token map[b] (step_map_kernel: duplicates of token 0 are prepared once)
 int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *tokens, float *kvstep, int B, int Mc, int n_tok, hipStream_t st,
                         const int *map = nullptr);
-// one denoiser step (+ DDIM update when coef != NULL); step index i of the n_tok prepared step rows, or row b for trajectory b (per_traj)
+// one denoiser step (+ DDIM update when coef != NULL); step index i of the n_tok prepared step rows, or row b for trajectory b (per_traj).
+// pin (needs coef): the pinned instantiation - rows below pin->rows[b] become c2 * x0 + c3 * noise in the same launch
 int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-               bool per_traj, hipStream_t st, const int *map = nullptr);
+               bool per_traj, hipStream_t st, const int *map = nullptr, const PinArgs *pin = nullptr);
 #endif

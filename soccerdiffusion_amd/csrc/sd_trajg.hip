@@ -813,7 +813,9 @@ struct TG {
         }
     }
 
-    static __device__ __forceinline__ void step_body(const StepArgs &a) {
+    // PIN: the lanes that store the DDIM update store c2 * x0 + c3 * noise instead for the tokens below pin.rows[traj] (PinArgs, sd_common.h)
+    template <bool PIN = false>
+    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}) {
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -864,6 +866,8 @@ struct TG {
         // ---- fc_out + DDIM: eps^T = Wout . h^T + b.  h has no a-priori bound: one power-of-two scale per token
         {
             float *stat = reinterpret_cast<float *>(c.smem + c.oS);
+            int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
+            if constexpr (PIN) pin_rows = pin.rows[traj];
             float am[NTT];
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
@@ -914,11 +918,19 @@ struct TG {
                     const int j0 = 16 * n + 4 * c.g;
                     if (!ok || j0 >= J) continue;
                     const long at = (traj * a.T + tok) * J + j0;
+                    bool pinned = false;
+                    if constexpr (PIN) pinned = tok < pin_rows;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (j0 + r >= J) continue;
                         const float e = E[n][r] * c_o + a.b_out[j0 + r];
                         if (a.eps_out) a.eps_out[at + r] = e;
+                        if constexpr (PIN) {
+                            if (a.update_x && pinned) {
+                                a.x[at + r] = a.c2 * pin.x0[at + r] + a.c3 * pin.noise[at + r];
+                                continue;
+                            }
+                        }
                         if (a.update_x) {   // the oracle's fp32 op order (oracle/ddim_ref.py)
                             const float x0 = (a.x[at + r] - a.c1 * e) / a.c0;
                             a.x[at + r] = a.c2 * x0 + a.c3 * e;
@@ -932,6 +944,9 @@ struct TG {
 
 template <int D, int NTT>
 __global__ __launch_bounds__(NTHREADS) void traj_step_generic_kernel(StepArgs a) { TG<D, NTT>::step_body(a); }
+// its pinned twin (sd_ddim_sample_pin)
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_pin_kernel(StepArgs a, PinArgs pin) { TG<D, NTT>::template step_body<true>(a, pin); }
 
 }   // namespace tg
 
@@ -996,6 +1011,26 @@ StepFn step_fn(int ntt) {
             case 5: return tg::traj_step_generic_kernel<D, 5>;
             case 6: return tg::traj_step_generic_kernel<D, 6>;
             case 7: return tg::traj_step_generic_kernel<D, 7>;
+            default: break;
+        }
+    }
+    return nullptr;
+}
+typedef void (*StepPinFn)(tg::StepArgs, PinArgs);
+template <int D>
+StepPinFn step_pin_fn(int ntt) {
+    switch (ntt) {
+        case 1: return tg::traj_step_generic_pin_kernel<D, 1>;
+        case 2: return tg::traj_step_generic_pin_kernel<D, 2>;
+        case 3: return tg::traj_step_generic_pin_kernel<D, 3>;
+        default: break;
+    }
+    if constexpr (D <= 256) {
+        switch (ntt) {
+            case 4: return tg::traj_step_generic_pin_kernel<D, 4>;
+            case 5: return tg::traj_step_generic_pin_kernel<D, 5>;
+            case 6: return tg::traj_step_generic_pin_kernel<D, 6>;
+            case 7: return tg::traj_step_generic_pin_kernel<D, 7>;
             default: break;
         }
     }
@@ -1104,7 +1139,7 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
 }
 
 int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-               bool per_traj, hipStream_t st, const int *map) {
+               bool per_traj, hipStream_t st, const int *map, const PinArgs *pin) {
     const int d = w->d, L = w->L;
     const GScratch s = gcarve(gws, B, Mc, d, L, n_tok);
     tg::StepArgs a{};
@@ -1136,16 +1171,23 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, i
     }
     const int ntt = (T + 15) / 16;
     const StepFn fn = d == 128 ? step_fn<128>(ntt) : d == 256 ? step_fn<256>(ntt) : step_fn<512>(ntt);
-    if (!fn) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
+    const StepPinFn pfn = d == 128 ? step_pin_fn<128>(ntt) : d == 256 ? step_pin_fn<256>(ntt) : step_pin_fn<512>(ntt);
+    if (!fn || !pfn) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
+    if (pin && !coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     const int hd = d / 4;
     const size_t lds = (size_t)T * (4 * d + 4 * hd + (4 * hd + 32) + 64);
     ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-    static DevFlag attr_set[3][8];
+    static DevFlag attr_set[2][3][8];
     const int di = d == 128 ? 0 : d == 256 ? 1 : 2;
-    if (!attr_set[di][ntt]) {
-        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    if (!attr_set[pin ? 1 : 0][di][ntt]) {
+        const hipError_t e = hipFuncSetAttribute(pin ? (const void *)pfn : (const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
         if (e != hipSuccess) return fail((int)e, "traj_step_generic_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        attr_set[di][ntt] = true;
+        attr_set[pin ? 1 : 0][di][ntt] = true;
+    }
+    if (pin) {
+        SD_LAUNCH(pfn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a, *pin);
+        SD_CHECK_LAUNCH("traj_step_generic_pin_kernel");
+        return 0;
     }
     SD_LAUNCH(fn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a);
     SD_CHECK_LAUNCH("traj_step_generic_kernel");

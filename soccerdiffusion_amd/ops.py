@@ -303,14 +303,55 @@ STATUS_NONFINITE = 1  # SD_STATUS_NONFINITE
 STATUS_SHARP_LOGITS = 2  # SD_STATUS_SHARP_LOGITS (sampler mode 4: a self-attention logit beyond the validated range)
 
 
+def pin_rows(rows, B: int, T: int, device) -> Tensor:
+    """The pinned-row counts of ``ddim_sample(pin=(known, rows))`` as the (B,) int32 device tensor the kernels read: an int (the same
+    count for every trajectory), or B of them as a sequence or a tensor.  Counts outside [0, T] raise ValueError where they can be seen
+    without a read-back - an int, a sequence, a host tensor; a device tensor is converted as it is (an int32 one is used in place)."""
+    if isinstance(rows, Tensor) and rows.is_cuda:
+        if tuple(rows.shape) != (B,) or rows.dtype.is_floating_point or rows.dtype == torch.bool:
+            raise ValueError(f"pin rows: expected ({B},) integers, got {tuple(rows.shape)} {rows.dtype}")
+        return rows.to(device=device, dtype=torch.int32).contiguous()
+    if isinstance(rows, bool) or (isinstance(rows, Tensor) and (rows.dtype.is_floating_point or rows.dtype == torch.bool)):
+        raise ValueError(f"pin rows: expected an int or ({B},) integers, got {rows!r}")
+    try:
+        host = torch.full((B,), operator.index(rows), dtype=torch.int64)
+    except TypeError:
+        try:
+            host = torch.as_tensor(rows).to(torch.int64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"pin rows: expected an int or ({B},) integers, got {rows!r}") from None
+    if tuple(host.shape) != (B,):
+        raise ValueError(f"pin rows: expected an int or ({B},) integers, got shape {tuple(host.shape)}")
+    if B and (int(host.min()) < 0 or int(host.max()) > T):
+        raise ValueError(f"pin rows: every count must lie in [0, {T}] (the horizon), got {host.tolist()}")
+    return host.to(torch.int32).to(device)
+
+
+def _pin_req(pin, B: int, T: int, J: int, device) -> tuple:
+    """(known, rows) of a pinned call, validated: known (B, T, J) fp32 on the device, rows through ``pin_rows``."""
+    try:
+        known, rows = pin
+    except (TypeError, ValueError):
+        raise ValueError("pin: expected (known, rows)") from None
+    rows = pin_rows(rows, B, T, device)
+    if not isinstance(known, Tensor) or tuple(known.shape) != (B, T, J):
+        raise ValueError(f"pin known: expected a ({B}, {T}, {J}) tensor, got {tuple(getattr(known, 'shape', ()))}")
+    _req(known, "pin known")
+    if known.device != device:
+        raise ValueError(f"pin known: expected a tensor on {device}, got {known.device}")
+    return known, rows
+
+
 class GraphedSampler:
     """The whole rollout (n_steps x (L x 2 + 3) kernel launches of ``sd_ddim_sample``) captured
     once into a hipGraph and replayed: removes the per-launch host cost, which dominates at
     small batch (the robot's B = 1, 30-step rollout).  Static shapes; the inputs are copied
     into the captured buffers before every replay.  ``status`` (one int32 on the device) is
-    the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay."""
+    the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay.  ``pin=True`` captures ``sd_ddim_sample_pin`` on static
+    pin buffers (known rows, start noise, row counts): a replay copies the call's ``pin=(known, rows)`` into them, so one graph
+    serves every pinning, none (rows = 0) included."""
 
-    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1):
+    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False):
         dev = step_tokens.device
         self.packed, self.coef = packed, np.ascontiguousarray(coef, dtype=np.float32)
         self.tokens = step_tokens.contiguous()
@@ -318,6 +359,9 @@ class GraphedSampler:
         self.x = torch.zeros(B, T, packed.J, dtype=torch.float32, device=dev)
         self.ctx = torch.zeros(B, Mc, packed.d, dtype=torch.float32, device=dev) if Mc > 0 else None
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pin = None
+        if pin:   # (known, noise, rows)
+            self.pin = (torch.zeros_like(self.x), torch.zeros_like(self.x), torch.zeros(B, dtype=torch.int32, device=dev))
         lib = _lib.load()
         self.ws = torch.empty(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, len(self.coef)),
                               dtype=torch.float32, device=dev)
@@ -333,35 +377,54 @@ class GraphedSampler:
 
     def _run(self):
         B, T, _ = self.x.shape
+        if self.pin is not None:
+            check(_lib.load().sd_ddim_sample_pin(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
+                                                 self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None, None,
+                                                 self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
+                                                 len(self.coef), self.status.data_ptr(), self.max_mode, *[t.data_ptr() for t in self.pin],
+                                                 _stream()), "sd_ddim_sample_pin")
+            return
         check(_lib.load().sd_ddim_sample_ex(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
                                             self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None,
                                             self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
                                             len(self.coef), self.status.data_ptr(), self.max_mode, _stream()),
               "sd_ddim_sample_ex")
 
-    def replay_into(self, ctx: Optional[Tensor], x_T: Tensor) -> Tensor:
+    def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None) -> Tensor:
         """Copies the inputs into the captured buffers, replays, and returns the captured x buffer itself
         (overwritten by the next replay)."""
+        if (pin is None) != (self.pin is None):
+            raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
         self.x.copy_(x_T)
         if self.ctx is not None:
             self.ctx.copy_(ctx)
+        if pin is not None:
+            known, rows = _pin_req(pin, *self.x.shape, self.x.device)
+            self.pin[0].copy_(known)
+            self.pin[1].copy_(x_T)
+            self.pin[2].copy_(rows)
         self.graph.replay()
         return self.x
 
-    def __call__(self, ctx: Optional[Tensor], x_T: Tensor) -> Tensor:
-        return self.replay_into(ctx, x_T).clone()
+    def __call__(self, ctx: Optional[Tensor], x_T: Tensor, pin=None) -> Tensor:
+        return self.replay_into(ctx, x_T, pin).clone()
 
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False):
+                eps_trace: bool = False, pin=None):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
     appended to the returned tuple.
     ``status`` (int32 tensor of one element on the device) receives the range-guard word of
     ``sd_ddim_sample_ex`` - not read here, so the call stays asynchronous; ``max_mode`` caps the kernel selection
-    (see ``ddim_sample_guarded``)."""
+    (see ``ddim_sample_guarded``).
+    ``pin = (known, rows)``: conditioning by inpainting (``sd_ddim_sample_pin``).  ``known`` (B, T, J) in normalised space; ``rows`` an
+    int or (B,) counts (``pin_rows``): row t of trajectory b is held to ``known`` iff t < rows[b] - on entry c0[0] known + c1[0] x_T,
+    after step i c2[i] known + c3[i] x_T in place of the DDIM update, so the returned rows equal ``known`` exactly; every other row is
+    sampled to fit, reading the pinned ones through self-attention.  The noise of the pinned rows is ``x_T`` itself (with ``inplace``
+    a private copy of it is taken first).  ``max_mode`` 4 runs the mode-3 kernels.  ``pin=None`` is the call without any of this."""
     lib = _lib.load()
     _req(x_T, "x_T"); _req(step_tokens, "step_tokens")
     B, T, J = x_T.shape
@@ -377,10 +440,20 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         raise ValueError("coef must be (n_steps, 4)")
     if status is not None:
         _req(status, "status", torch.int32)
+    if pin is not None:
+        pin = _pin_req(pin, B, T, J, x_T.device)
     x = x_T if inplace else x_T.clone()
     tr = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if trace else None
     et = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if eps_trace else None
     ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, n_steps), x.device)
+    if pin is not None:
+        noise = x_T.clone() if inplace else x_T   # never x itself: the first step overwrites x
+        check(lib.sd_ddim_sample_pin(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
+                                     coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
+                                     B, T, Mc, n_steps, _ptr(status), int(max_mode), pin[0].data_ptr(), noise.data_ptr(), pin[1].data_ptr(),
+                                     _stream()), "sd_ddim_sample_pin")
+        out = (x,) + ((tr,) if trace else ()) + ((et,) if eps_trace else ())
+        return out if len(out) > 1 else x
     check(lib.sd_ddim_sample_eps(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
                                  coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
                                  B, T, Mc, n_steps, _ptr(status), int(max_mode), _stream()), "sd_ddim_sample_eps")
@@ -408,18 +481,21 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
-                        trace: bool = False, max_mode: Optional[int] = None):
+                        trace: bool = False, max_mode: Optional[int] = None, pin=None):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
-    beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there."""
+    beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
+    ``pin``: as in ``ddim_sample``; every repeat carries it."""
     import warnings
 
+    if pin is not None:   # validated and uploaded once for all repeats
+        pin = _pin_req(pin, *x_T.shape, x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
-    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap)
+    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin)
     word = int(status.item())
     if word == 0:
         return out
@@ -429,7 +505,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         # of the checkpoint, so later calls with these weights start there.
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
-            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3)
+            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -438,7 +514,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     if mode >= 2:
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1)
+        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
@@ -1686,11 +1762,43 @@ def session_commit(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, head: Ten
     return out
 
 
-def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0) -> None:
+def session_commit_carry(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, head: Tensor, advance: int, carry: int, pin_x0: Tensor,
+                         pin_rows: Tensor, robots=None) -> Tensor:
+    """``session_commit`` that also prepares the next tick, in the same one launch (``sd_session_commit_carry``): all T rows are
+    published, the first ``advance`` of them - the commands executed before the next tick - go into the action ring, rows
+    [advance, advance + carry) of x, as sampled, become rows [0, carry) of ``pin_x0[robot]`` (B, T, J) and ``pin_rows[robot]`` (B) int32
+    becomes ``carry``.  ``robots``: x is (S, T, J); only those robots' rings, pin rows and counts move."""
+    B, L, J = _ring_req(ring, head)
+    _req(x, "x"); _req(mean, "mean"); _req(std, "std"); _req(pin_x0, "pin_x0"); _req(pin_rows, "pin_rows", torch.int32)
+    r = None if robots is None else _robots_on(robots, B, ring.device)
+    S = B if r is None else r.numel()
+    if x.dim() != 3 or x.shape[0] != S or x.shape[2] != J or mean.numel() != J or std.numel() != J or x.device != ring.device:
+        raise ValueError(f"x: expected ({S}, T, {J}) with {J} means and stds, got {tuple(x.shape)}")
+    T = x.shape[1]
+    if tuple(pin_x0.shape) != (B, T, J) or tuple(pin_rows.shape) != (B,) or pin_x0.device != ring.device or pin_rows.device != ring.device:
+        raise ValueError(f"pin_x0 / pin_rows: expected ({B}, {T}, {J}) fp32 and ({B},) int32 on {ring.device}")
+    advance, carry = int(advance), int(carry)
+    if advance < 0 or carry < 0 or advance + carry > T:
+        raise ValueError(f"advance, carry >= 0 and advance + carry <= {T}, got {advance} and {carry}")
+    out = torch.empty_like(x)
+    if r is None:
+        check(_lib.load().sd_session_commit_carry(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(), head.data_ptr(),
+                                                  B, T, J, L, advance, carry, pin_x0.data_ptr(), pin_rows.data_ptr(), _stream()),
+              "sd_session_commit_carry")
+    else:
+        check(_lib.load().sd_session_commit_carry_at(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), ring.data_ptr(),
+                                                     head.data_ptr(), r.data_ptr(), S, B, T, J, L, advance, carry, pin_x0.data_ptr(),
+                                                     pin_rows.data_ptr(), _stream()), "sd_session_commit_carry_at")
+    return out
+
+
+def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0,
+                  pin_rows: Optional[Tensor] = None) -> None:
     """The start state of an episode for the robots a mask selects, in one launch (``sd_session_reset``): ``rings`` is up to five
     (ring, head, fill) with ``fill`` a device row of C floats or None for zeros; ``mask`` (B) bool or uint8 on the device (None: every
     robot) is read by the kernel only - nothing comes back to the host, so a simulator's ``done`` tensor can be passed as it is;
-    ``game_state`` (B) int64 receives ``game_state_value`` for the selected robots."""
+    ``game_state`` (B) int64 receives ``game_state_value`` for the selected robots.  ``pin_rows`` (B) int32: the carried-row counts of a
+    session with overlapping ticks, zeroed for the selected robots in the same launch (``sd_session_reset_carry``)."""
     if not 1 <= len(rings) <= 5:
         raise ValueError("one to five rings per launch")
     array = (_lib.RingReset * len(rings))()
@@ -1711,4 +1819,10 @@ def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_st
             raise ValueError(f"mask: expected ({B},) on {dev}, got {tuple(mask.shape)} on {mask.device}")
     if game_state is not None and (tuple(_req(game_state, "game_state", torch.int64).shape) != (B,) or game_state.device != dev):
         raise ValueError(f"game_state: expected ({B},) int64 on {dev}")
+    if pin_rows is not None:
+        if tuple(_req(pin_rows, "pin_rows", torch.int32).shape) != (B,) or pin_rows.device != dev:
+            raise ValueError(f"pin_rows: expected ({B},) int32 on {dev}")
+        check(_lib.load().sd_session_reset_carry(array, len(rings), _ptr(mask), _ptr(game_state), int(game_state_value), pin_rows.data_ptr(), B,
+                                                 _stream()), "sd_session_reset_carry")
+        return
     check(_lib.load().sd_session_reset(array, len(rings), _ptr(mask), _ptr(game_state), int(game_state_value), B, _stream()), "sd_session_reset")

@@ -18,6 +18,13 @@ Every entry point takes ``robots=`` for a subset of the batch (robots that tick 
     s.push_image(frame, robots=[2]); traj = s.step(robots=[0, 2])      # (2, T, J); robot 1's rings are neither read nor written
     s.reset(robots=done)                                               # a (B,) bool mask, on the device as it is, or an index list
 
+Overlapping ticks (``carry=K``): a tick commits the first ``advance`` rows of its trajectory to the action history and carries the
+next K rows into the following tick, whose first K rows are pinned to them at every denoising step (``ops.ddim_sample(pin=...)``) - the
+new trajectory continues the one the robot is still executing instead of being an unrelated draw:
+
+    s = PolicySession(model, batch=1, carry=4, advance=5, hyperparams=hp)   # T = 10: tick every 5 points, 4 points held across the seam
+    traj = s.step()                                                         # traj[:, :4] == the previous tick's traj[:, 5:9], bit for bit
+
 There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
 
 from __future__ import annotations
@@ -38,7 +45,9 @@ class _GraphedTick:
     """Windows, context encoders and rollout of one session's tick as one captured hipGraph (linear; the warm-up and capture recipe of
     ``ops.GraphedSampler``).  The graph changes no ring - the commit stays outside - so warming it up and capturing it leave the
     session's state alone.  A call copies the noise into the captured buffer, replays, reads the range-guard word back as the eager
-    route does (``ops.ddim_sample_guarded``) and returns the captured sample buffer, which the next call overwrites."""
+    route does (``ops.ddim_sample_guarded``) and returns the captured sample buffer, which the next call overwrites.  A session with
+    carry captures the pinned rollout on the session's own pin buffers, which the commit outside the graph rewrites: the same graph
+    serves a first tick (no rows pinned), every later one and the ticks after a partial reset."""
 
     def __init__(self, session: "PolicySession", x_T: torch.Tensor):
         m, dev = session.model, session.device
@@ -63,7 +72,8 @@ class _GraphedTick:
     def _run(self) -> None:
         self.ctx = self.session._context()
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
-        self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap)
+        self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap,
+                                 pin=self.session._pin())
 
     def __call__(self, x_T: torch.Tensor) -> torch.Tensor:
         self.noise.copy_(x_T)
@@ -72,17 +82,24 @@ class _GraphedTick:
             return self.x
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
         s = self.session
-        return s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3).contiguous()
+        return s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, pin=s._pin()).contiguous()
 
 
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
-                 hyperparams: Optional[dict] = None, use_graph: bool = False):
+                 hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
         also read for ``distilled_decoder`` unless ``distilled`` says it.  ``use_graph``: windows, context encoders and rollout of
-        ``step`` are replayed from one captured hipGraph (not for a distilled decoder)."""
+        ``step`` are replayed from one captured hipGraph (not for a distilled decoder).
+        ``carry`` / ``advance`` (overlapping ticks): a tick pushes the first ``advance`` rows of its trajectory into the action history
+        (default: T - carry) and pins the first ``carry`` rows of the next tick to its rows [advance, advance + carry), in normalised
+        space as sampled, at every denoising step.  ``advance`` is the number of trajectory points between two ticks.  carry = 0 with
+        the default advance is the session without any of this, launch for launch.  Not for a distilled decoder (no rollout to pin)."""
+        hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
+        self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
+        self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -92,8 +109,6 @@ class PolicySession:
             raise ValueError("batch and num_inference_steps must be positive")
         self.model, self.B, self.n_steps = model, int(batch), int(num_inference_steps)
         self.device = params[0].device
-        hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
-        self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.hyperparams = hp
         self.T, self.J = model.trajectory_prediction_length, model.num_joints
         self._seed, self._watched = int(seed), None
@@ -116,6 +131,36 @@ class PolicySession:
                                  "where it has no sequence encoder)")
             self.S, self.R = int(S), int(R)
         self.reset()
+
+    @staticmethod
+    def check_carry(T: int, carry: int = 0, advance: Optional[int] = None, distilled: bool = False) -> tuple:
+        """(carry, advance) of a session with horizon T, validated (no device needed): advance defaults to T - carry; ValueError if
+        carry < 0, advance < 1, advance + carry > T, or carry > 0 with a distilled decoder."""
+        carry = int(carry)
+        if carry < 0:
+            raise ValueError(f"carry: the number of rows held across two ticks cannot be negative, got {carry}")
+        advance = int(T) - carry if advance is None else int(advance)
+        if advance < 1:
+            raise ValueError(f"advance: a tick must commit at least one row (T = {T}, carry = {carry}), got {advance}")
+        if advance + carry > T:
+            raise ValueError(f"advance + carry = {advance} + {carry} exceeds the horizon T = {T}")
+        if carry > 0 and distilled:
+            raise ValueError("carry: a distilled decoder is one forward at t = 0 - there is no rollout whose rows could be pinned")
+        return carry, advance
+
+    @property
+    def _carrying(self) -> bool:
+        """The commit is the carrying one: anything but carry = 0 with the whole trajectory pushed."""
+        return self.carry > 0 or self.advance != self.T
+
+    def _pin(self, dev_idx=None):
+        """``pin`` of the tick's rollout: the session's pin buffers (of the robots ``dev_idx``), or None for a session without carry."""
+        if self.carry == 0:
+            return None
+        if dev_idx is None:
+            return self._pin_x0, self._pin_rows
+        i = dev_idx.long()
+        return self._pin_x0[i], self._pin_rows[i]
 
     # ---- the plan: shapes from hyperparameters alone ---------------------------------------
     @staticmethod
@@ -169,7 +214,7 @@ class PolicySession:
             mask = torch.zeros(self.B, dtype=torch.bool)
             mask[ops.robot_index(robots, self.B).long()] = True
             mask = mask.to(self.device)
-        ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE)
+        ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE, pin_rows=self._pin_rows if self._carrying else None)
 
     def reset(self, robots=None) -> None:
         """Rings back to ``context_length`` rows of zeros (ros.py:87-106), the image ring to the token of an all-zero frame
@@ -178,7 +223,8 @@ class PolicySession:
         used without a synchronisation): the end of those robots' episodes only.  Their rings, head words and game state go back to the
         start state in one launch, the image-token ring to the zero-frame token of the last whole reset (the backbone does not run).
         Nothing is allocated, a captured tick stays valid, the noise generator and the session's weights stay; weights that moved since
-        the last whole reset raise as in ``step``."""
+        the last whole reset raise as in ``step``.  With ``carry`` the robots' carried-row counts are zeroed in the same launch: their
+        next tick is unpinned, a first tick."""
         if robots is not None:
             return self._reset_some(robots)
         if self.model.training:
@@ -194,6 +240,9 @@ class PolicySession:
         self._game_state = torch.full((B,), DEFAULT_GAME_STATE, dtype=torch.int64, device=dev)
         self._gen = torch.Generator(device=dev).manual_seed(self._seed)
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
+        if self._carrying:   # the rows carried into the next tick (normalised space) and how many per robot: 0 until a tick has committed
+            self._pin_x0 = torch.zeros(B, self.T, self.J, dtype=torch.float32, device=dev)
+            self._pin_rows = torch.zeros(B, dtype=torch.int32, device=dev)
         self._watched, self._graph = None, None
         self._key = self._weights_key()
         self._resettable = [(*r, None) for r in {id(r[0]): r for r in (*self._rings.values(), self._action)}.values()]
@@ -345,7 +394,8 @@ class PolicySession:
 
     def step(self, x_T: Optional[torch.Tensor] = None, robots=None) -> torch.Tensor:
         """One tick (ros.py:259-335): the published trajectory (B, T, J) = denormalised sample - pi, also appended to the action
-        history.  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator.
+        history (its first ``advance`` rows in a session with overlapping ticks, whose first ``carry`` rows equal rows
+        [advance, advance + carry) of the robot's previous tick).  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator.
         ``robots``: the tick of those S robots alone - their windows, the context encoders and the rollout at batch S, the commit into
         their action rings only; x_T and the result are (S, T, J).  A subset tick runs eagerly, on the same rings, also where
         ``use_graph`` is set: the captured graph serves the whole batch."""
@@ -365,13 +415,20 @@ class PolicySession:
             if self.use_graph and subset is None:
                 if self._graph is None:   # first tick after construction / reset(): the rings are new
                     self._graph = _GraphedTick(self, x_T)
-                return ops.session_commit(self._graph(x_T), m.mean, m.std, *self._action)
+                return self._commit(self._graph(x_T), None)
             ctx = self._context(subset)
+            dev_idx = None if subset is None else subset[2]
             if self.distilled:   # one forward at t = 0 (ros.py:293-298)
                 x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:shape[0]])
             else:
-                x = m.sample(ctx, x_T, self.n_steps, max_mode=3)
-            return ops.session_commit(x.contiguous(), m.mean, m.std, *self._action, robots=None if subset is None else subset[2])
+                x = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx))
+            return self._commit(x.contiguous(), dev_idx)
+
+    def _commit(self, x: torch.Tensor, dev_idx) -> torch.Tensor:
+        m = self.model
+        if not self._carrying:
+            return ops.session_commit(x, m.mean, m.std, *self._action, robots=dev_idx)
+        return ops.session_commit_carry(x, m.mean, m.std, *self._action, self.advance, self.carry, self._pin_x0, self._pin_rows, robots=dev_idx)
 
     @classmethod
     def from_checkpoint(cls, path: str, device=None, ema: bool = False, **kwargs) -> "PolicySession":

@@ -27,8 +27,14 @@ host memory through push_camera / push_orientation, against two fp32 frames that
 the model's form through push_image / push_rotation - the second one leaves out the host's cv2.resize, scaling, normalisation and
 quats_to_5d, which this tool does not time (cv2 is not a dependency, and another resize would not be the node's).  Two eager sessions on one
 model, alternating blocks, medians, extremes and spread as above; no exit status depends on it.
+
+--carry K measures what overlapping ticks cost: PolicySession(carry=K) - the first K rows of every tick pinned to the previous tick's,
+the rollout on the pinned instantiations of the step kernels plus one entry launch, the carrying commit - against the session without
+carry, eager and with use_graph, four sessions on one model fed the same sensor rows in alternating blocks; medians, extremes and spread
+as above, the cost of the pin stated as the difference of the medians.  No exit status depends on it.
 usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10] [--reset [--out profiles/session_partial_reset.jsonl]]
-                                     [--raw 480x640 [--out profiles/session_raw_tick.jsonl]]"""
+                                     [--raw 480x640 [--out profiles/session_raw_tick.jsonl]]
+                                     [--carry 4 [--out profiles/session_carry.jsonl]]"""
 import argparse
 import json
 import os
@@ -265,6 +271,48 @@ def raw_leg(args):
             f.write("\n".join(lines) + "\n")
 
 
+def carry_leg(args):
+    """The session with carry against the session without, eager and replayed from a graph (--carry K)."""
+    blocks = 3 if args.quick else args.blocks
+    lines = []
+    for name, over in CONFIGS.items():
+        params = {**BASE, **over}
+        torch.manual_seed(0)
+        model = cli.build_model(params).cuda().eval()
+        T, J = params["trajectory_prediction_length"], params["num_joints"]
+        for B in ((1, 16) if args.quick else (1, 16, 64)):
+            g = torch.Generator().manual_seed(7)
+            keys = [(graph, carry) for graph in (False, True) for carry in (0, args.carry)]
+            sessions = {k: PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params, use_graph=k[0], carry=k[1]) for k in keys}
+            x_T = torch.randn(B, T, J, device="cuda", generator=torch.Generator(device="cuda").manual_seed(8))
+            news = [sensor_rows(params, B, g) for _ in range(args.ticks)]
+            for k in keys:                                                 # warm-up: one untimed block of every variant (and the capture)
+                block_ms(lambda new, x: session_tick(sessions[k], new, x), news, x_T)
+            times = {k: [] for k in keys}
+            for _ in range(blocks):                                        # alternating blocks: drift of the box hits all of them
+                for k in keys:
+                    times[k].append(block_ms(lambda new, x: session_tick(sessions[k], new, x), news, x_T))
+            col = lambda v: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+            spread = max(max(v) - min(v) for v in times.values())
+            med = {k: statistics.median(v) for k, v in times.items()}
+            rec = {"config": name, "B": B, "steps": N_STEPS, "new_frames_per_tick": NEW_FRAMES, "frame_size": [params["image_resolution"]] * 2,
+                   "memory_rows": PolicySession.plan(params)["memory_rows"], "blocks": blocks, "ticks_per_block": args.ticks,
+                   "carry": args.carry, "advance": sessions[(False, args.carry)].advance,
+                   "eager": {"carry_0_tick_ms": col(times[(False, 0)]), "carry_tick_ms": col(times[(False, args.carry)]),
+                             "pin_cost_ms": round(med[(False, args.carry)] - med[(False, 0)], 3)},
+                   "use_graph": {"carry_0_tick_ms": col(times[(True, 0)]), "carry_tick_ms": col(times[(True, args.carry)]),
+                                 "pin_cost_ms": round(med[(True, args.carry)] - med[(True, 0)], 3)},
+                   "spread_ms": round(spread, 3)}
+            rec["pin_cost_beyond_spread"] = bool(max(abs(rec["eager"]["pin_cost_ms"]), abs(rec["use_graph"]["pin_cost_ms"])) > spread)
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+            del sessions
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="B = 1 and 16 only, fewer blocks")
@@ -273,7 +321,9 @@ def main():
     ap.add_argument("--reset", action="store_true", help="measure partial and whole resets with the tick that follows them")
     ap.add_argument("--raw", type=str, default=None, metavar="HxW", help="measure raw uint8 camera frames of this size and quaternions through "
                     "push_camera / push_orientation against preprocessed ones through push_image / push_rotation")
-    ap.add_argument("--out", type=str, default=None, help="--reset, --raw: also write the JSON lines to this file")
+    ap.add_argument("--carry", type=int, default=None, metavar="K", help="measure PolicySession(carry=K) against the session without carry, "
+                    "eager and with use_graph")
+    ap.add_argument("--out", type=str, default=None, help="--reset, --raw, --carry: also write the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_session.py measures on the GPU: no device found")
@@ -281,6 +331,8 @@ def main():
         return reset_leg(args)
     if args.raw:
         return raw_leg(args)
+    if args.carry is not None:
+        return carry_leg(args)
     blocks = 3 if args.quick else args.blocks
     failed = False
     for name, over in CONFIGS.items():

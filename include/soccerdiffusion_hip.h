@@ -102,7 +102,7 @@ const char *sd_last_error(void);
 size_t sd_workspace_floats(int B, int T, int M, int d, int L, int n_steps);
 
 /* Which kernels a sampler call (sd_ddim_sample*, sd_sampler_prepare / sd_sampler_eps) runs: one route per call, chosen from the shape, the
- * cap and four A/B switches of the environment (soccerdiffusion_amd/csrc/sd_sampler_plan.h).  Results agree within fp32 rounding.
+ * cap and five A/B switches of the environment (soccerdiffusion_amd/csrc/sd_sampler_plan.h).  Results agree within fp32 rounding.
  *   route              mode  what runs
  *   CHAINS_F32          0    unfused row chains on the fp32 MFMA
  *   CHAINS_F16          0    unfused row chains on split fp16 (chain_f16_kernel)
@@ -134,6 +134,19 @@ size_t sd_workspace_floats(int B, int T, int M, int d, int L, int n_steps);
 #define SD_ROUTE_TRAJ_TUNED_WIDE 7
 #define SD_ROUTE_TRAJ_GENERIC 8
 int sd_sampler_route(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode);
+/* The rollout form of the TRAJ_TUNED / TRAJ_TUNED_2P routes.  FUSED: every DDIM step of a trajectory in one launch of
+ * traj_step_rollout_kernel (a workgroup keeps its CU and its trajectory's folded planes stay in the Infinity Cache; at most 64 steps per
+ * launch, longer rollouts in chunks) - sd_ddim_sample / _ex / _eps calls without trace and eps_trace.  PER_STEP: one launch per step - calls
+ * that return something per step (trace, eps_trace), pinned calls, the loop form (sd_sampler_eps), every other route, and every call with
+ * SD_TRAJ_ROLLOUT=steps in the environment.  Both forms compute the same bits.
+ * Asked through sd_sampler_route with max_mode = SD_ASK_ROLLOUT + cap (0 .. 4) [+ SD_ASK_TRACE] [+ SD_ASK_PIN] [+ SD_ASK_LOOP]: the return is
+ * SD_ROLLOUT_* of that kind of call instead of the route. */
+#define SD_ASK_ROLLOUT 0x100
+#define SD_ASK_TRACE 0x10
+#define SD_ASK_PIN 0x20
+#define SD_ASK_LOOP 0x40
+#define SD_ROLLOUT_PER_STEP 0
+#define SD_ROLLOUT_FUSED 1
 int sd_sampler_mode(int d, int heads, int T, int Mc, int J);
 
 /* StepToken.forward — soccer_diffusion/ml/model/misc.py:25-35.

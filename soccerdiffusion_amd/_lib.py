@@ -250,6 +250,19 @@ def sampler_route(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: int, m
     return ROUTES[rc]
 
 
+ROLLOUTS = ("PER_STEP", "FUSED")   # SD_ROLLOUT_*
+
+
+def sampler_rollout(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: int, max_mode: int = -1, *, trace: bool = False, pin: bool = False,
+                    loop: bool = False) -> str:
+    """The rollout form of a sampler call of this shape, cap and kind (sd_sampler_route with SD_ASK_ROLLOUT; reporting only): "FUSED" = every
+    DDIM step in one launch, "PER_STEP" = one launch per step.  trace: the call returns the samples or the noise predictions of every step."""
+    ask = 0x100 + (3 if max_mode < 0 else max_mode) + (0x10 if trace else 0) + (0x20 if pin else 0) + (0x40 if loop else 0)
+    rc = load().sd_sampler_route(d, heads, T, Mc, J, L, B, ask)
+    check(min(rc, 0), "sd_sampler_route")
+    return ROLLOUTS[rc]
+
+
 KERNEL_CLASSES = ("panel_gemm_kernel", "attention_kernel", "patch_embed_kernel", "fc_out_kernel", "decoder_layer_kernel", "decoder_head_kernel",
                   "traj_step_kernel")
 

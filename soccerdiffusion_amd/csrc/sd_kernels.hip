@@ -2903,11 +2903,20 @@ extern "C" int sd_encoder_forward(const sd_encoder_weights *w, const float *x, f
     return 0;
 }
 
-extern "C" int sd_sampler_mode(int d, int heads, int T, int Mc, int J) { return sampler_plan(d, heads, T, Mc, J, 1, 1, 3).mode(); }
+extern "C" int sd_sampler_mode(int d, int heads, int T, int Mc, int J) { return sampler_plan(d, heads, T, Mc, J, 1, 1, 3, CALL_ROLLOUT).mode(); }
 
 extern "C" int sd_sampler_route(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode) {
+    // SD_ASK_ROLLOUT + cap (0 .. 4) [+ SD_ASK_TRACE / _PIN / _LOOP]: the rollout form of that kind of call instead of its route
+    int call = -1;
+    if (max_mode >= SD_ASK_ROLLOUT && max_mode < 2 * SD_ASK_ROLLOUT) {
+        call = (max_mode & SD_ASK_TRACE ? CALL_TRACE : 0) | (max_mode & SD_ASK_PIN ? CALL_PIN : 0) | (max_mode & SD_ASK_LOOP ? CALL_LOOP : 0);
+        max_mode &= 7;
+        // (as sd_ddim_sample_pin: mode 4 has no pinned twin and is read as 3)
+        if ((call & CALL_PIN) && max_mode == 4) max_mode = 3;
+    }
     if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, "sd_sampler_route: max_mode must be -1, 0, 1, 2, 3 or 4");
-    return sampler_plan(d, heads, T, Mc, J, L, B, max_mode < 0 ? 3 : max_mode).route;
+    const SamplerPlan plan = sampler_plan(d, heads, T, Mc, J, L, B, max_mode < 0 ? 3 : max_mode, call < 0 ? CALL_ROLLOUT : call);
+    return call < 0 ? plan.route : plan.rollout_fused ? SD_ROLLOUT_FUSED : SD_ROLLOUT_PER_STEP;
 }
 
 extern "C" int sd_ddim_sample(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
@@ -2977,7 +2986,8 @@ static int ddim_pin(float *x, const PinArgs &pin, float ck, float cn, int B, int
     return 0;
 }
 
-// the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once)
+// the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once), or - the plan's rollout_fused -
+// one launch of the rollout kernel per TRAJ_ROLLOUT_MAX_STEPS steps
 static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
                         int32_t *status, const PinArgs *pin = nullptr) {
     const long n = (long)c.B * c.T * c.w->J;
@@ -2987,6 +2997,14 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     if ((rc = c.prepare_ctx(ctx))) return rc;
     if ((rc = c.prepare_steps(step_tokens, false))) return rc;
     if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
+    if (c.plan.rollout_fused) {
+        if (trace || eps_trace || pin || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
+        for (int i0 = 0; i0 < c.n_tok; i0 += TRAJ_ROLLOUT_MAX_STEPS) {
+            const int nn = c.n_tok - i0 < TRAJ_ROLLOUT_MAX_STEPS ? c.n_tok - i0 : TRAJ_ROLLOUT_MAX_STEPS;
+            if ((rc = traj_steps_fused(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status))) return rc;
+        }
+        return status ? finite_check(x, n, status, c.st) : 0;
+    }
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
@@ -3094,7 +3112,8 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
     if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
-    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode);
+    const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | (pin ? CALL_PIN : 0);
+    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, call);
     if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin);
     return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin);
 }
@@ -3125,7 +3144,7 @@ static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int
     if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, who);
     if (T > w->T_max) return fail(SD_E_TOOBIG, who);
     *s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_tok, B);
-    *plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode < 0 ? 3 : max_mode);
+    *plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode < 0 ? 3 : max_mode, CALL_LOOP);
     return plan->traj() ? 0 : SD_E_UNSUPPORTED;
 }
 

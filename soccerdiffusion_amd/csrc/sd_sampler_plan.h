@@ -1,5 +1,5 @@
 // Which kernels one sampler call runs: the ONE place that decides it.  Host-only, plain C++17, no HIP: a pure function of eight integers and
-// the four A/B switches of the environment.  sd_kernels.hip builds a plan once per entry point and hands it down; sd_sampler_mode and
+// the five A/B switches of the environment.  sd_kernels.hip builds a plan once per entry point and hands it down; sd_sampler_mode and
 // sd_sampler_route report it.  Not part of the public ABI (the SD_ROUTE_* numbers are: include/soccerdiffusion_hip.h).
 #ifndef SD_SAMPLER_PLAN_H
 #define SD_SAMPLER_PLAN_H
@@ -27,9 +27,11 @@ inline bool fused_layer_ok(int d, int heads, int T, int Mk) {
 //   SD_SAMPLER_GEMM=f32  no split-fp16 kernels at all: no trajectory kernels, no mode 2, no fp16 row chains
 //   SD_SAMPLER_TRAJG=0   no generic trajectory kernels
 //   SD_TRAJ_MAXROWS=n    memory rows beyond n go to the generic kernels instead of the tuned family's wide instantiation
+//   SD_TRAJ_ROLLOUT=steps  no rollout kernel: every rollout on the tuned kernels is one launch per DDIM step
 struct SamplerSwitches {
     bool traj, f16, trajg;
     int max_rows;
+    bool rollout;
 };
 inline const SamplerSwitches &sampler_switches() {
     static const SamplerSwitches sw = [] {
@@ -38,13 +40,23 @@ inline const SamplerSwitches &sampler_switches() {
             return e && strcmp(e, value) == 0;
         };
         const char *mr = getenv("SD_TRAJ_MAXROWS");
-        return SamplerSwitches{!is("SD_SAMPLER_TRAJ", "0"), !is("SD_SAMPLER_GEMM", "f32"), !is("SD_SAMPLER_TRAJG", "0"), mr ? atoi(mr) : 64};
+        return SamplerSwitches{!is("SD_SAMPLER_TRAJ", "0"), !is("SD_SAMPLER_GEMM", "f32"), !is("SD_SAMPLER_TRAJG", "0"), mr ? atoi(mr) : 64,
+                               !is("SD_TRAJ_ROLLOUT", "steps")};
     }();
     return sw;
 }
 
+// What a sampler call asks for besides its shape (a set of bits): the plan's rollout form depends on it, the route does not.
+enum SamplerCall {
+    CALL_ROLLOUT = 0,   // sd_ddim_sample*: the whole rollout, only its end is returned
+    CALL_TRACE = 1,     // ... with the sample or the noise prediction of every step (trace / eps_trace)
+    CALL_PIN = 2,       // ... with pinned leading rows (sd_ddim_sample_pin)
+    CALL_LOOP = 4,      // the loop form: one denoiser evaluation per call (sd_sampler_eps)
+};
+
 struct SamplerPlan {
     int route;       // SD_ROUTE_*
+    bool rollout_fused;   // TRAJ_TUNED / TRAJ_TUNED_2P: all DDIM steps of a trajectory in one launch (traj_step_rollout_kernel); false: one launch per step
     int key_tiles;   // tuned trajectory family: tiles of 16 memory slots in the folded blocks (1; 2 .. 4: the wide instantiation)
     bool precise;    // tuned trajectory family: three fp16 products at the Q | K | V site too (false: mode 4, which reports through the status word)
     bool kv_fp32;    // row panels: the memory's K / V projections stay on the fp32 MFMA (caps 0 and 1: the rerun path after SD_STATUS_NONFINITE)
@@ -73,7 +85,8 @@ inline SamplerPlan panel_plan(int d, int heads, int T, int Mk, int J, int B, int
 }
 
 // One sampler call: Mc context rows (+ the step row), L layers, B trajectories, max_mode already resolved to 0 .. 4.
-inline SamplerPlan sampler_plan(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode) {
+// call: SamplerCall bits.
+inline SamplerPlan sampler_plan(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int call) {
     const SamplerSwitches &sw = sampler_switches();
     const int Mk = Mc + 1;
     if (max_mode >= 3 && sw.traj && sw.f16) {
@@ -84,6 +97,8 @@ inline SamplerPlan sampler_plan(int d, int heads, int T, int Mc, int J, int L, i
             // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
             p.precise = max_mode == 3 || p.key_tiles > 1;
             p.route = p.key_tiles > 1 ? SD_ROUTE_TRAJ_TUNED_WIDE : p.precise ? SD_ROUTE_TRAJ_TUNED : SD_ROUTE_TRAJ_TUNED_2P;
+            // the rollout kernel exists for the one-key-tile instantiations; it returns nothing per step and has no pinned twin
+            p.rollout_fused = sw.rollout && p.key_tiles == 1 && call == CALL_ROLLOUT;
             return p;
         }
         if (sw.trajg && trajg_ok(d, heads, T, Mk, J, L)) {

@@ -84,9 +84,14 @@ __device__ __forceinline__ void tj_sync() {
     if (blockIdx.x < TJ_STAMP_WGS && (threadIdx.x & 63) == 0) g_tj_stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * TJ_NSTAMP + 64 + SITE] += t1 - t0;
 }
 #define TJ_SYNC(site) tj_sync<site>()
+// the first wait of the cross-attention's score loop made visible: 13 requests (score biases, the folded values and the step token's value
+// columns) follow the 16 fragments of the folded keys, so the first fragment has landed when 28 are outstanding - where the score loop's own
+// first s_waitcnt stands in the listing
+#define TJ_WAIT_FIRST_KEY() asm volatile("s_waitcnt vmcnt(28)" ::: "memory")
 #else
 #define TJ_STAMP(i) do {} while (0)
 #define TJ_SYNC(site) __syncthreads()
+#define TJ_WAIT_FIRST_KEY() do {} while (0)
 #endif
 
 // The three products of sd_mfma16.h's mma3, tagged with the GEMM site.
@@ -335,6 +340,19 @@ struct StepArgs {
     LayerW layer[MAX_L];
 };
 
+// The per-step scalars of a rollout launch (traj_step_rollout_kernel): they travel in the kernel argument, so a launch carries at most
+// ROLL_MAX_STEPS DDIM steps (1 KiB of coefficients) and a longer rollout is launched in chunks.  Step i of the launch reads step block i
+// of the layers' gstep / vstep / cstep (the host points them at the chunk's first step).
+constexpr int ROLL_MAX_STEPS = 64;
+struct RollArgs {
+    int n_steps;
+    float coef[ROLL_MAX_STEPS][4];   // sqrt a_t, sqrt(1 - a_t), sqrt a_prev, sqrt(1 - a_prev) of each step
+};
+struct RolloutArgs {   // the rollout kernel's one parameter: the kernel-argument segment is exactly this
+    StepArgs a;
+    RollArgs r;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // The kernel family.  NTT = ceil(T / 16) token tiles (T <= 100: 1 .. 7; tiles 0 .. NTT-2 are full, the last holds tokens
 // 16 (NTT-1) .. T-1 and its other lanes clamp to T-1).  PRECISE: the Q | K | V projection reads both planes of LayerNorm 1 (three
@@ -363,6 +381,18 @@ static __device__ __forceinline__ void ctx_init(Ctx &c, char *smem, int T) {
         c.xa[m2] = (unsigned)(c.t * XROW) + in_row;
         c.xa6[m2] = (unsigned)(c.tok6 * XROW) + in_row6;
     }
+}
+
+// The rollout kernel's context: the layer loop's lesson (ctx_local) for the step loop.  No per-lane value is kept live around the loop or
+// across the layers - not even the thread index: the lane number comes from the execution mask where it is needed (head and tail of a
+// step), the wave number waits in a scalar register.
+static __device__ __forceinline__ Ctx ctx_fresh(char *smem, int wave, int T) {
+    Ctx c1;
+    c1.smem = smem;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(c1.lane));
+    c1.w = wave;
+    c1.T = T;
+    return ctx_local(c1);
 }
 
 // A copy of the context whose per-lane values the compiler must treat as new: every address derived from them is then
@@ -1290,6 +1320,8 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
                 },
                 [&](int s) __attribute__((always_inline)) { mma3<S_XSC>(S[s % N1D], gfr[s / N1D][0], gfr[s / N1D][1], xb[s % 3][0], xb[s % 3][1]); });
         };
+        TJ_WAIT_FIRST_KEY();
+        TJ_STAMP(53);
         if (odd) scores(std::true_type{});
         else scores(std::false_type{});
 #pragma unroll
@@ -1399,13 +1431,27 @@ static __device__ __forceinline__ void decoder_layer(const Ctx &c0, const LayerW
     TJ_STAMP(39);
 }
 
+// The DDIM update of the step kernels, rounding for rounding.  There it is written as (x - c1 e) / c0 and c2 x0 + c3 e and hipcc contracts it
+// to x0 = fma(-c1, e, x) / c0, fma(c2, x0, c3 e); with the coefficients of the rollout kernel (a row of its table instead of four kernel
+// arguments) the same expression contracts to fma(c3, e, c2 x0), one rounding apart: the rollout kernel spells the step kernels' form out.
+static __device__ __forceinline__ float ddim_update(float x, float e, const f32x4 &k) {
+    const float x0 = __builtin_fmaf(-k[1], e, x) / k[0];
+    const float ce = k[3] * e;
+    return __builtin_fmaf(k[2], x0, ce);
+}
+
 // PIN: the lanes that store the DDIM update store c2 * x0 + c3 * noise instead for the tokens below pin.rows[traj] (PinArgs, sd_common.h);
 // the noise prediction is written for every row all the same.  No barrier and no LDS of its own.
-template <bool WIDE = false, bool PIN = false>
-static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}) {
+// ROLL: one iteration of the rollout kernel's step loop - the DDIM coefficients and the step block come from the caller (roll_coef,
+// roll_step) instead of the launch's StepArgs, x of the DDIM update is requested before the fc_out GEMM instead of behind it, and a
+// barrier closes the step: the next one stages the x this one stored (same CU, same L1: workgroup scope) and reuses the statistics rows.
+template <bool WIDE = false, bool PIN = false, bool ROLL = false>
+static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
+                                                 int roll_step = 0, int roll_wave = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
-    ctx_init(c, smem, a.T);
+    if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
+    else ctx_init(c, smem, a.T);
     const long traj = blockIdx.x;
     const int J = a.J;
     TJ_STAMP(0);
@@ -1428,10 +1474,11 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         }
         __builtin_amdgcn_sched_barrier(0);
         const float *xr = a.x + traj * (long)a.T * J;
+        const int tid = ROLL ? 64 * c.w + c.lane : (int)threadIdx.x;   // (rollout: the thread index is not kept around the step loop)
         if (J & 3) {
             // any joint count <= 32 (the reference's database has 22: soccer_diffusion/dataset/models.py:222-247): one thread per (token,
             // 8-joint chunk), scalar loads (rows are not 16-byte aligned), joints >= J zero
-            for (int i = threadIdx.x; i < a.T * 4; i += NTHREADS) {
+            for (int i = tid; i < a.T * 4; i += NTHREADS) {
                 const int tok = i >> 2, chunk = i & 3;
                 f16x8 h8, l8;
 #pragma unroll
@@ -1446,7 +1493,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
             }
         }
         const int nvec = (J & 3) ? 0 : a.T * J / 4;
-        for (int i = threadIdx.x; i < nvec; i += NTHREADS) {
+        for (int i = tid; i < nvec; i += NTHREADS) {
             const f32x4 v = *reinterpret_cast<const f32x4 *>(xr + 4 * i) * XSC;
             const int tok = (4 * i) / J, j0 = 4 * i - tok * J;     // 4 consecutive joints of one token
             const int chunk = j0 >> 3;
@@ -1476,9 +1523,14 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
     layer_norm_to_x<!PRECISE>(c, H, a.n1_w, a.n1_b);
     TJ_STAMP(2);
 #pragma unroll 1
-    for (int l = 0; l < a.L; ++l) decoder_layer<WIDE>(c, a.layer[l], H, traj, a.Mk, a.scale_log2e, a.status, a.nkt, a.step_per_traj ? (a.step_map ? (long)a.step_map[traj] : traj) : 0L);
+    for (int l = 0; l < a.L; ++l) decoder_layer<WIDE>(c, a.layer[l], H, traj, a.Mk, a.scale_log2e, a.status, a.nkt,
+                                                           ROLL ? (long)roll_step : a.step_per_traj ? (a.step_map ? (long)a.step_map[traj] : traj) : 0L);
     // ---- fc_out + DDIM: eps^T = Wout . h^T + b.  h has no a-priori bound: one power-of-two scale per token
+    const Ctx &c_step = c;
     {
+        Ctx c_tail;
+        if constexpr (ROLL) c_tail = ctx_fresh(smem, roll_wave, a.T);
+        const Ctx &c = ROLL ? c_tail : c_step;
         float *stat = reinterpret_cast<float *>(c.smem + LDS_STAT);
         int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
         if constexpr (PIN) pin_rows = pin.rows[traj];
@@ -1513,6 +1565,16 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
                     for (int pl = 0; pl < 2; ++pl) wf[n][ks][pl] = *reinterpret_cast<const f16x8 *>(a.w_out + ((long)(n * 8 + ks) * 2 + pl) * 512 + c.lane * 8);
+        }
+        // rollout: this lane's x of the DDIM update as well (stored by the previous step, visible since the barrier that closed it)
+        f32x4 xpre[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        if constexpr (ROLL) {
+            if (c.w < NTT && !(J & 3) && (c.w < NTT - 1 || c.ok6)) {
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+                    if (16 * n + 4 * c.g < J) xpre[n] = *reinterpret_cast<const f32x4 *>(a.x + (traj * a.T + tok) * J + 16 * n + 4 * c.g);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
@@ -1554,6 +1616,10 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                                 continue;
                             }
                         }
+                        if constexpr (ROLL) {
+                            if (a.update_x) a.x[at + r] = ddim_update(a.x[at + r], e, roll_coef);
+                            continue;
+                        }
                         if (a.update_x) {
                             const float x0 = (a.x[at + r] - a.c1 * e) / a.c0;
                             a.x[at + r] = a.c2 * x0 + a.c3 * e;
@@ -1571,12 +1637,16 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                     }
                 }
                 if (a.update_x) {
-                    const f32x4 xv = *reinterpret_cast<const f32x4 *>(a.x + at);
+                    const f32x4 xv = ROLL ? xpre[n] : *reinterpret_cast<const f32x4 *>(a.x + at);
                     f32x4 xn;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {   // the oracle's fp32 op order (oracle/ddim_ref.py, as fc_out_kernel)
-                        const float x0 = (xv[r] - a.c1 * e[r]) / a.c0;
-                        xn[r] = a.c2 * x0 + a.c3 * e[r];
+                        if constexpr (ROLL) {
+                            xn[r] = ddim_update(xv[r], e[r], roll_coef);
+                        } else {
+                            const float x0 = (xv[r] - a.c1 * e[r]) / a.c0;
+                            xn[r] = a.c2 * x0 + a.c3 * e[r];
+                        }
                     }
                     *reinterpret_cast<f32x4 *>(a.x + at) = xn;
                 }
@@ -1584,6 +1654,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         }
     }
     TJ_STAMP(40);
+    if constexpr (ROLL) __syncthreads();
 }
 };   // struct TJ
 
@@ -1598,6 +1669,27 @@ template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_pin_kernel(StepArgs a, PinArgs pin) { TJ<NTT, true>::template step_body<false, true>(a, pin); }
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_pin_kernel(StepArgs a, PinArgs pin) { TJ<NTT, true>::template step_body<true, true>(a, pin); }
+// All DDIM steps of a trajectory in ONE launch: the step loop around the very step of traj_step_kernel<NTT, PRECISE>.  A workgroup keeps its
+// CU for the whole rollout, so at any time the chip holds one trajectory per CU and their folded cross-attention planes (g16 / v16 / cb:
+// 525 KB per trajectory at 4 layers) stay in the Infinity Cache from the second step on, where one launch per step streams every other
+// trajectory's planes past between two uses.  x goes through memory between steps (8 KB per trajectory, L2).
+// The kernel argument is read anew in every step, through a laundered pointer to its segment: hipcc otherwise hoists the scalar loads of the
+// ~ 40 pointers a step uses out of the step loop, keeps them in scalar registers around it and spills those into vector registers, which
+// the step has none to spare of (NTT = 7: 62 spilled scalars and 68 - 116 bytes of scratch per lane; with this, ctx_fresh and no thread
+// index inside the loop: 241 registers, no scratch).
+template <int NTT, bool PRECISE>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_rollout_kernel(RolloutArgs) {
+    typedef const __attribute__((address_space(4))) RolloutArgs *KernArg;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_steps = ((KernArg)__builtin_amdgcn_kernarg_segment_ptr())->r.n_steps;
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        KernArg ka = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const RolloutArgs &k = *(const RolloutArgs *)ka;
+        TJ<NTT, PRECISE>::template step_body<false, false, true>(k.a, PinArgs{}, f32x4{k.r.coef[i][0], k.r.coef[i][1], k.r.coef[i][2], k.r.coef[i][3]}, i, wave);
+    }
+}
 
 
 }   // namespace tj

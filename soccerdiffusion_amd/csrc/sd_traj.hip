@@ -54,6 +54,22 @@ static TrajStepFn traj_step_fn(int ntt) {
     }
 }
 
+// the rollout kernel (all DDIM steps of a trajectory in one launch) of the same two instantiation rows
+typedef void (*TrajRolloutFn)(tj::RolloutArgs);
+template <bool PRECISE>
+static TrajRolloutFn traj_rollout_fn(int ntt) {
+    switch (ntt) {
+        case 1: return tj::traj_step_rollout_kernel<1, PRECISE>;
+        case 2: return tj::traj_step_rollout_kernel<2, PRECISE>;
+        case 3: return tj::traj_step_rollout_kernel<3, PRECISE>;
+        case 4: return tj::traj_step_rollout_kernel<4, PRECISE>;
+        case 5: return tj::traj_step_rollout_kernel<5, PRECISE>;
+        case 6: return tj::traj_step_rollout_kernel<6, PRECISE>;
+        case 7: return tj::traj_step_rollout_kernel<7, PRECISE>;
+        default: return nullptr;
+    }
+}
+
 // the pinned twins (sd_ddim_sample_pin): the mode-3 kernel and the wide one; mode 4's two-product instantiations have none
 typedef void (*TrajStepPinFn)(tj::StepArgs, PinArgs);
 static TrajStepPinFn traj_step_pin_fn(int ntt, bool wide) {
@@ -304,10 +320,9 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
     return 0;
 }
 
-// one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
-// coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
-int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin) {
+// the kernel argument of step i of the n_steps prepared ones (the rollout kernel: of the steps from i on)
+static tj::StepArgs step_args(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
+                              bool per_traj, int nkt, int32_t *status) {
     const int d = w->d, L = w->L;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
     tj::StepArgs a{};
@@ -345,6 +360,14 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *ep
         q.nln_w = l + 1 < L ? w->layers[l + 1].n1_w : nullptr;
         q.nln_b = l + 1 < L ? w->layers[l + 1].n1_b : nullptr;
     }
+    return a;
+}
+
+// one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
+// coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
+int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
+              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin) {
+    const tj::StepArgs a = step_args(w, s, x, eps, B, T, Mc, i, n_steps, coef, per_traj, nkt, status);
     const int ntt = (T + 15) / 16;
     // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
@@ -373,5 +396,33 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *ep
     }
     SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a);
     SD_CHECK_LAUNCH("traj_step_kernel");
+    return 0;
+}
+
+// DDIM steps i0 .. i0 + n - 1 of the n_steps prepared ones in ONE launch, x updated in place (n <= TRAJ_ROLLOUT_MAX_STEPS; one key tile).
+// Step for step the arithmetic of traj_step; profiled under the same class.
+int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, float *x, int B, int T, int Mc, int i0, int n, int n_steps, const float *coef,
+                     hipStream_t st, bool precise, int32_t *status) {
+    static_assert(TRAJ_ROLLOUT_MAX_STEPS == tj::ROLL_MAX_STEPS, "one cap on both sides of the interface");
+    static_assert(sizeof(tj::RolloutArgs) <= 4096, "kernel argument");
+    if (n < 1 || n > tj::ROLL_MAX_STEPS || i0 < 0 || i0 + n > n_steps || !coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
+    tj::RolloutArgs ra{};
+    ra.a = step_args(w, s, x, nullptr, B, T, Mc, i0, n_steps, coef + 4 * i0, false, 1, status);
+    tj::RollArgs &r = ra.r;
+    r.n_steps = n;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 4; ++k) r.coef[i][k] = coef[4 * (i0 + i) + k];
+    const int ntt = (T + 15) / 16;
+    const TrajRolloutFn fn = precise ? traj_rollout_fn<true>(ntt) : traj_rollout_fn<false>(ntt);
+    if (!fn) return fail(SD_E_BADARG, "traj_step_rollout_kernel: horizon out of range");
+    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
+    static DevFlag attr_set[2][8];
+    if (!attr_set[precise ? 1 : 0][ntt]) {
+        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
+        if (e != hipSuccess) return fail((int)e, "traj_step_rollout_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        attr_set[precise ? 1 : 0][ntt] = true;
+    }
+    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, ra);
+    SD_CHECK_LAUNCH("traj_step_rollout_kernel");
     return 0;
 }

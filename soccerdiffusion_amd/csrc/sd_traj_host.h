@@ -27,4 +27,10 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
 // pin (needs coef and precise: mode 4 has no pinned twin): rows below pin->rows[b] become c2 * x0 + c3 * noise in the same launch
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
               bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin = nullptr);
+// DDIM steps i0 .. i0 + n - 1 of the n_tok prepared ones in ONE launch of the rollout kernel (the plan's rollout_fused: one key tile, nothing
+// returned per step, no pin); n <= TRAJ_ROLLOUT_MAX_STEPS - the per-step scalars travel in the kernel argument - so the driver launches a
+// longer rollout in chunks.  coef: the rollout's whole table (4 per step).
+constexpr int TRAJ_ROLLOUT_MAX_STEPS = 64;
+int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, float *x, int B, int T, int Mc, int i0, int n, int n_tok, const float *coef,
+                     hipStream_t st, bool precise, int32_t *status);
 #endif

@@ -4,13 +4,20 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-value -Xclang -target-feature -Xclang -packed-fp32-ops -I include -I soccerdiffusion_amd/csrc tools/exp/traj_layer.hip -o tools/exp/traj_layer
 //   tools/exp/traj_layer [B=4096] [iters=20] [check=2] [L=4]
 // Prints [B] traj_step_kernel: one whole denoiser step (embedding, L layers with folded cross-attention and FFN, fc_out, DDIM update).
-// -DTJ_STAMPS adds the phase profile.
+// -DTJ_STAMPS adds the phase profile.  -DTL_ROLLOUT=n: the phase profile and the timing on traj_step_rollout_kernel with n DDIM steps per
+// launch (n <= 64; every step reads a copy of the one step block; the stamps are those of the last step, the barrier sums are per step).
 #include "sd_traj.h"
 // -DTL_PRECISE=1: the three-product variant of the step kernel (sa_block_precise)
 #ifndef TL_PRECISE
 #define TL_PRECISE 0
 #endif
 #define TL_STEP_KERNEL tj::traj_step_kernel<7, (TL_PRECISE != 0)>
+#ifndef TL_ROLLOUT
+#define TL_ROLLOUT 0
+#endif
+#define TL_ROLLOUT_KERNEL tj::traj_step_rollout_kernel<7, (TL_PRECISE != 0)>
+static_assert(TL_ROLLOUT >= 0 && TL_ROLLOUT <= tj::ROLL_MAX_STEPS, "steps per launch");
+constexpr int TL_NBLK = TL_ROLLOUT > 0 ? TL_ROLLOUT : 1;   // step blocks per layer
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -181,6 +188,7 @@ int main(int argc, char **argv) {
     CK(hipMemcpyToSymbol(HIP_SYMBOL(tj::g_tj_stamps), &d_st, sizeof(d_st)));
 #endif
     CK(hipFuncSetAttribute((const void *)(TL_STEP_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES));
+    CK(hipFuncSetAttribute((const void *)(TL_ROLLOUT_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -229,20 +237,39 @@ int main(int argc, char **argv) {
             mv = std::max(mv, maxbits(h.gvstep.data() + D, 4, D, 2 * D));
             unsigned *dmb = dev(std::vector<unsigned>{mg, mv});
             float *d_gv = dev(h.gv), *d_gvs = dev(h.gvstep);
-            f16 *g16 = dalloc<f16>((size_t)B * 4 * 8 * 2 * 512), *v16 = dalloc<f16>((size_t)B * 16 * 2 * 2 * 512), *gs = dalloc<f16>(4 * 8 * 2 * 32), *vs = dalloc<f16>(2 * 4 * D);
+            f16 *g16 = dalloc<f16>((size_t)B * 4 * 8 * 2 * 512), *v16 = dalloc<f16>((size_t)B * 16 * 2 * 2 * 512), *gs = dalloc<f16>((size_t)TL_NBLK * 4 * 8 * 2 * 32), *vs = dalloc<f16>((size_t)TL_NBLK * 2 * 4 * D);
             hipLaunchKernelGGL(tj::pack_g16_kernel, dim3(2048), dim3(256), 0, 0, d_gv, (long)B, Mc, dmb, g16, sc + 4);
             hipLaunchKernelGGL(tj::pack_v16_kernel, dim3(2048), dim3(256), 0, 0, d_gv, (long)B, Mc, dmb + 1, v16, sc + 5);
             hipLaunchKernelGGL(pack_gstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb, gs, sc + 6);       // (round 5: the step blocks' own scales)
             hipLaunchKernelGGL(pack_vstep16_kernel, dim3(4), dim3(256), 0, 0, d_gvs, 1L, dmb + 1, vs, sc + 7);
             CK(hipDeviceSynchronize());
             CK(hipFree(d_gv));
-            w.g16 = g16; w.v16 = v16; w.gstep = gs; w.vstep = vs; w.cb = dev(h.cb); w.cstep = dev(h.cstep);
+            vf cstep_all;
+            for (int i = 0; i < TL_NBLK; ++i) cstep_all.insert(cstep_all.end(), h.cstep.begin(), h.cstep.end());
+            for (int i = 1; i < TL_NBLK; ++i) {   // the rollout kernel's step i reads block i: copies of the one step block
+                CK(hipMemcpy(gs + (size_t)i * tj::STEP_G_HALFS, gs, tj::STEP_G_HALFS * sizeof(f16), hipMemcpyDeviceToDevice));
+                CK(hipMemcpy(vs + (size_t)i * tj::STEP_V_HALFS, vs, tj::STEP_V_HALFS * sizeof(f16), hipMemcpyDeviceToDevice));
+            }
+            w.g16 = g16; w.v16 = v16; w.gstep = gs; w.vstep = vs; w.cb = dev(h.cb); w.cstep = dev(cstep_all);
             w.nln_w = l + 1 < L ? dev(hl[l + 1].n1w) : nullptr;
             w.nln_b = l + 1 < L ? dev(hl[l + 1].n1b) : nullptr;
         }
         hipLaunchKernelGGL((TL_STEP_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
+        // the profiled / timed launch: one step, or TL_ROLLOUT steps in one launch of the rollout kernel (x stays put: update_x = 0)
+        const auto launch = [&]() {
+            if (TL_ROLLOUT > 0) {
+                tj::RolloutArgs ra{};
+                ra.a = a;
+                ra.r.n_steps = TL_ROLLOUT;
+                for (int i = 0; i < TL_ROLLOUT; ++i)
+                    for (int k = 0; k < 4; ++k) ra.r.coef[i][k] = coef[k];
+                hipLaunchKernelGGL((TL_ROLLOUT_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, ra);
+            } else {
+                hipLaunchKernelGGL((TL_STEP_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
+            }
+        };
         const int nc = ncheck < B ? ncheck : B;
         vf geps((size_t)nc * T * J), gx((size_t)nc * T * J);
         CK(hipMemcpy(geps.data(), d_eps, geps.size() * 4, hipMemcpyDeviceToHost));
@@ -315,7 +342,8 @@ int main(int argc, char **argv) {
         {
             a.update_x = 0;
             CK(hipMemset(d_st, 0, n_st * 8));
-            hipLaunchKernelGGL((TL_STEP_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
+            launch();
+            CK(hipGetLastError());
             CK(hipDeviceSynchronize());
             std::vector<unsigned long long> st(n_st);
             CK(hipMemcpy(st.data(), d_st, n_st * 8, hipMemcpyDeviceToHost));
@@ -417,6 +445,22 @@ int main(int argc, char **argv) {
                 printf("  %-37s", names[i]);
                 for (int wi = 0; wi < 4; ++wi) printf(" %9.0f", mean(ws[wi], i));
                 printf("\n");
+                if (i != 33) continue;
+                // ... split at the score loop's first wait for a folded key (stamp 53, behind a wait of its own for the first fragment)
+                const char *jn[2] = {"  xattn: V' requests + first key wait", "  xattn: scores + softmax behind it"};
+                const int from[2] = {32, 53}, to[2] = {53, 33};
+                for (int k = 0; k < 2; ++k) {
+                    printf("  %-37s", jn[k]);
+                    for (int wi = 0; wi < 4; ++wi) {
+                        double sum = 0;
+                        for (int b = 0; b < nwg; ++b) {
+                            const unsigned long long *p = &st[((size_t)b * 8 + ws[wi]) * tj::TJ_NSTAMP];
+                            sum += (double)(p[to[k]] - p[from[k]]);
+                        }
+                        printf(" %9.0f", sum / nwg);
+                    }
+                    printf("\n");
+                }
             }
             {   // inside the last LayerNorm executed (LN3 of the last layer; stamp 34 precedes it)
                 const char *jn[4] = {"  LN3: per-wave statistics", "  LN3: exchange barrier", "  LN3: combine 8 waves", "  LN3: normalise, split, store"};
@@ -447,6 +491,7 @@ int main(int argc, char **argv) {
                 for (int w0 = 0; w0 < 8; ++w0) {
                     double sum = 0;
                     for (int b = 0; b < nwg; ++b) sum += (double)st[((size_t)b * 8 + w0) * tj::TJ_NSTAMP + 64 + sidx];
+                    sum /= TL_NBLK;   // (the rollout kernel adds every step's wait to the slot)
                     printf(" %6.0f", sum / nwg);
                     tot[w0] += sum / nwg;
                 }
@@ -460,14 +505,16 @@ int main(int argc, char **argv) {
 #endif
         a.update_x = 0;   // timing: x stays put (the same work; only the final store differs)
         a.eps_out = nullptr;
-        for (int i = 0; i < 2; ++i) hipLaunchKernelGGL((TL_STEP_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
+        for (int i = 0; i < 2; ++i) launch();
         CK(hipEventRecord(e0));
-        for (int i = 0; i < iters; ++i) hipLaunchKernelGGL((TL_STEP_KERNEL), dim3(B), dim3(tj::NTHREADS), tj::LDS_BYTES, 0, a);
+        for (int i = 0; i < iters; ++i) launch();
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
+        CK(hipGetLastError());
         float ms;
         CK(hipEventElapsedTime(&ms, e0, e1));
-        const double us = ms * 1000.0 / iters;
+        const double us = ms * 1000.0 / iters / TL_NBLK;
+        if (TL_ROLLOUT > 0) printf("[B] traj_step_rollout_kernel, %d steps per launch:\n", TL_ROLLOUT);
         printf("[B] traj_step_kernel: B=%d L=%d  %.1f us per step = %.1f us per 4096 trajectories;  50 steps -> %.0f trajectories/s\n", B, L, us, us * 4096.0 / B,
                B / (us * 50e-6));
     }

@@ -256,6 +256,32 @@ int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx, const flo
                        float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                        const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, void *stream);
 
+/* Several draws per observation from one shared context: sd_ddim_sample_pin with `draws` trajectories per context.  ctx (B / draws, Mc, d);
+ * trajectory b reads context b / draws (the draws of a context are contiguous); x, trace, eps_trace, the pin arrays and the status word
+ * are per trajectory as ever.  pin_x0 = pin_noise = pin_rows = NULL: unpinned.
+ *   On the trajectory routes (SD_ROUTE_TRAJ_*) the context is projected, folded and packed once per CONTEXT - the abs-max words and scales
+ *   are taken over the B / draws contexts, and a maximum over duplicates is the same maximum, so the planes are bit for bit those of the
+ *   call on the repeated context - and shared-context instantiations of the step kernels read them at b / draws (pinned and unpinned calls
+ *   run the same kernel: a pinned call stays one launch per step; an unpinned one-key-tile rollout without traces is the fused rollout
+ *   form).  The tuned kernels' size limit (sd_sampler_route_draws) counts contexts, not trajectories.  The result equals
+ *   sd_ddim_sample_eps / _pin on the repeated context bit for bit.
+ *   On the routes without trajectory kernels (modes 0 - 2, the rerun at max_mode 1 after SD_STATUS_NONFINITE included) one gather launch
+ *   expands the context rows to B in the workspace and the kernels of old run on the copy: correct, but not shared.
+ *   draws == 1 is the existing call, launch for launch; so is any valid draws with Mc = 0 (nothing to share).  workspace:
+ *   sd_workspace_floats(B, ...) as for the other calls (the tail of the plane regions stays unused).
+ * SD_E_BADARG (nothing launched): draws < 1, B % draws != 0, or only some of the pin pointers NULL. */
+int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                         float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                         const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, int draws, void *stream);
+/* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
+int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
+
+/* The representative of each context's draws: index[c] = argmin_i sum_k |x[c,i] - x[c,k]|^2 over the G draws of context c (x (C, G, T, J), the
+ * space the sampler works in), and, with out (C, T, J) != NULL, out[c] = x[c, index[c]].  One workgroup per context, fp32 in fixed orders
+ * (a pair's distance is computed once, so d(i,k) == d(k,i); the score sums k = 0 .. G-1 in that order, the zero self term included; ties go
+ * to the lowest index, so bitwise-equal draws tie exactly); no atomics: the result does not depend on scheduling.  1 <= G <= 64. */
+int sd_select_medoid(const float *x, int32_t *index, float *out /* or NULL */, int C, int G, int T, int J, void *stream);
+
 /* The denoiser evaluated ONE step at a time on the trajectory kernels of sampler modes 3 / 4 - the reference's own loop form,
  *   for t in scheduler.timesteps: eps = model.forward_with_context(ctx, x, t); x = scheduler.step(eps, t, x).prev_sample
  * (soccer_diffusion/ml/inference/plot.py:122-131, ml/training/distill.py:179-189, ml/inference/ros.py:301-310), whose

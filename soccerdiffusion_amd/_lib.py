@@ -135,6 +135,9 @@ SIGNATURES = {
     "sd_ddim_sample_ex": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_ddim_sample_eps": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_ddim_sample_pin": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sd_ddim_sample_draws": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_sampler_route_draws": (C.c_int, [C.c_int] * 9),
+    "sd_select_medoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_bn_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int]),
     "sd_bn_train_fwd": (C.c_int, [C.c_void_p] * 12 + [C.c_int64, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "sd_convt3x3_s2": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 5 + [C.c_void_p]),
@@ -247,6 +250,14 @@ def sampler_route(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: int, m
     """The name of the route a sampler call of this shape and cap runs (sd_sampler_route; reporting only)."""
     rc = load().sd_sampler_route(d, heads, T, Mc, J, L, B, max_mode)
     check(min(rc, 0), "sd_sampler_route")
+    return ROUTES[rc]
+
+
+def sampler_route_draws(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: int, draws: int, max_mode: int = -1) -> str:
+    """``sampler_route`` of a shared-context call (sd_ddim_sample_draws): B trajectories, ``draws`` per context - the tuned kernels' size
+    limit counts the B / draws contexts (sd_sampler_route_draws; reporting only)."""
+    rc = load().sd_sampler_route_draws(d, heads, T, Mc, J, L, B, max_mode, draws)
+    check(min(rc, 0), "sd_sampler_route_draws")
     return ROUTES[rc]
 
 

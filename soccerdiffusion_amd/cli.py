@@ -426,7 +426,10 @@ def cmd_sample(args) -> int:
     B = len(mine)
     if B == 0:
         return 0
-    x_T = torch.randn(B, params["trajectory_prediction_length"], params["num_joints"], device=device, generator=gen)
+    G = args.draws
+    if G > 1 and params.get("distilled_decoder", False):
+        raise SystemExit("--draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
+    x_T = torch.randn(B * G, params["trajectory_prediction_length"], params["num_joints"], device=device, generator=gen)
     with torch.no_grad():
         if params_need_context(params):
             batch = source.batch(mine % source.n)
@@ -437,12 +440,17 @@ def cmd_sample(args) -> int:
         if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         else:
-            traj = model.sample(context, x_T, args.steps)
+            traj = model.sample(context, x_T, args.steps, draws=G)   # G draws for each of the B contexts, which are encoded once
+        if G > 1:
+            medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
     out = args.output if world == 1 else f"{args.output}.rank{rank}"
-    torch.save({"trajectories": traj.cpu(), "noise": x_T.cpu(), "steps": args.steps, "indices": mine}, out)
+    saved = {"trajectories": traj.cpu(), "noise": x_T.cpu(), "steps": args.steps, "indices": mine}
+    if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
+        saved.update(trajectories=saved["trajectories"].view(B, G, *traj.shape[1:]), draws=G, medoid=medoid.cpu())
+    torch.save(saved, out)
     if rank == 0:
-        print(f"sampled {n} trajectories of shape {tuple(traj.shape[1:])} with {args.steps} DDIM steps -> {args.output}")
+        print(f"sampled {n}{f' x {G}' if G > 1 else ''} trajectories of shape {tuple(traj.shape[1:])} with {args.steps} DDIM steps -> {args.output}")
     return 0
 
 
@@ -521,7 +529,7 @@ def cmd_rollout(args) -> int:
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
-                                            seed=args.seed, carry=args.carry, advance=args.advance)
+                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws)
     params = session.hyperparams
     if args.raw:
         stream = raw_sensor_stream(args.synthetic, params, args.ticks, camera, seed=args.seed)
@@ -550,6 +558,8 @@ def cmd_rollout(args) -> int:
     saved = {"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}
     if args.carry or args.advance is not None:
         saved.update(carry=session.carry, advance=session.advance)
+    if args.draws > 1:
+        saved["draws"] = session.draws   # every published trajectory is the medoid of that many draws
     if episode is not None:
         saved["resets"] = torch.stack(resets)   # (K, N): robot n was reset after tick k
     torch.save(saved, args.output)
@@ -561,8 +571,17 @@ def params_need_context(params: dict) -> bool:
     return any(params.get(k, False) for k in ("use_action_history", "use_imu", "use_joint_states", "use_images", "use_gamestate"))
 
 
-def main(argv: Optional[list] = None) -> int:
-    logging.basicConfig(level=os.environ.get("LOGLEVEL", "INFO"))
+def _draws(text: str) -> int:
+    try:
+        g = int(text)
+    except ValueError:
+        g = 0
+    if not 1 <= g <= 64:
+        raise argparse.ArgumentTypeError(f"--draws takes a number of draws per context in [1, 64], got {text!r}")
+    return g
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="cli", description="SoccerDiffusion denoiser on MI355X: train / sample")
     sub = ap.add_subparsers(dest="command", required=True)
     tr = sub.add_parser("train", help="train the model (flags of the reference's train.py)")
@@ -579,6 +598,8 @@ def main(argv: Optional[list] = None) -> int:
     sa.add_argument("--num_samples", type=int, default=10, help="Number of samples to generate")
     sa.add_argument("--output", "-o", type=str, default="samples.pt", help="Where to save the sampled trajectories")
     sa.add_argument("--ema", action="store_true", help="sample from the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
+    sa.add_argument("--draws", type=_draws, default=1, metavar="G", help="G draws for each of the --num_samples contexts, sampled on the shared "
+                    "folded context: the file gains draws and medoid (n,), trajectories becomes (n, G, T, J)")
     di = sub.add_parser("distill", help="distil the multi-step model into a single-step model (flags of the reference's distill.py)")
     di.add_argument("config", type=str, help="Path to the training configuration file")
     di.add_argument("checkpoint", type=str, help="Path to the checkpoint to load for the teacher model")
@@ -615,8 +636,15 @@ def main(argv: Optional[list] = None) -> int:
                     "the rows of the previous one that fall in the overlap (PolicySession(carry=K))")
     ro.add_argument("--advance", type=int, default=None, metavar="S", help="trajectory points between two ticks (default: horizon - K); a tick "
                     "commits that many rows to the action history")
+    ro.add_argument("--draws", type=_draws, default=1, metavar="G", help="G draws per robot and tick from the once-encoded context; their medoid is "
+                    "committed and published (PolicySession(draws=G))")
     ro.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv: Optional[list] = None) -> int:
+    logging.basicConfig(level=os.environ.get("LOGLEVEL", "INFO"))
+    args = build_parser().parse_args(argv)
     for flag in ("ema", "ema_teacher"):   # asked for EMA weights the checkpoint does not hold: say so before anything touches the GPU
         if getattr(args, flag, False):
             ema_model_state(torch.load(args.checkpoint, map_location="cpu", weights_only=True), "--" + flag.replace("_", "-"), args.checkpoint)

@@ -2944,12 +2944,15 @@ struct TrajCall {
     const Scratch &s;
     int B, T, Mc, n_tok;
     hipStream_t st;
+    int draws = 1;   // sd_ddim_sample_draws: trajectory b reads context b / draws, prepared once (1: every trajectory its own, the kernels of old)
     bool generic() const { return plan.route == SD_ROUTE_TRAJ_GENERIC; }
     TrajWs ws() const { return TrajWs{s.kvtmp, s.kvstep, s.gv, s.cb, s.gvstep, s.cstep, s.wf, s.g16, s.v16, s.gstep16, s.vstep16, s.wio, s.scales, s.maxbits, s.stepmap}; }
     int prepare_weights() const {
         return generic() ? trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st) : traj_prepare_weights(w, ws(), st);
     }
     int prepare_ctx(const float *ctx) const {
+        // shared contexts: B / draws rows of context are projected, folded and packed; the tail of the plane regions stays unused
+        if (draws > 1) return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st, B / draws) : traj_prepare_ctx(w, ws(), ctx, B / draws, Mc, plan.key_tiles, st);
         return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st) : traj_prepare_ctx(w, ws(), ctx, B, Mc, plan.key_tiles, st);
     }
     // per_traj: one token per trajectory (only the distinct ones are prepared: step_map_kernel), else one per DDIM step
@@ -2962,6 +2965,11 @@ struct TrajCall {
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
     // pin: the pinned instantiations (the caller's plan is a three-product one)
     int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr) const {
+        if (draws > 1) {   // the shared-context instantiations (one kernel for pinned and unpinned calls)
+            if (per_traj) return fail(SD_E_BADARG, "TrajCall: shared contexts exist for rollouts only");
+            if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, false, st, nullptr, pin, draws);
+            return traj_step_draws(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status, pin, draws);
+        }
         if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr, pin);
         return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status, pin);
     }
@@ -3001,7 +3009,9 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
         if (trace || eps_trace || pin || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
         for (int i0 = 0; i0 < c.n_tok; i0 += TRAJ_ROLLOUT_MAX_STEPS) {
             const int nn = c.n_tok - i0 < TRAJ_ROLLOUT_MAX_STEPS ? c.n_tok - i0 : TRAJ_ROLLOUT_MAX_STEPS;
-            if ((rc = traj_steps_fused(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status))) return rc;
+            if (c.draws > 1) rc = traj_steps_fused_draws(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status, c.draws);
+            else rc = traj_steps_fused(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status);
+            if (rc) return rc;
         }
         return status ? finite_check(x, n, status, c.st) : 0;
     }
@@ -3097,9 +3107,18 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
     return status ? finite_check(x, n, status, st) : 0;
 }
 
+// Context rows of a shared-context call on the routes without trajectory kernels (modes 0 - 2): dst[b] = src[b / draws], rows of `per` floats
+__global__ void ctx_expand_kernel(const float *__restrict__ src, float *__restrict__ dst, long n, long per, int draws) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / per;
+        dst[i] = src[(b / draws) * per + (i - b * per)];
+    }
+}
+
+// draws: trajectories per context (ctx holds B / draws of them); 1: every trajectory its own - the calls of old
 static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                            float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream,
-                           const PinArgs *pin) {
+                           const PinArgs *pin, int draws = 1) {
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!step_tokens || !coef || !x || !workspace || B <= 0 || T <= 0 || Mc < 0 || n_steps <= 0 || (Mc > 0 && !ctx))
@@ -3113,8 +3132,16 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
     const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | (pin ? CALL_PIN : 0);
-    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, call);
-    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin);
+    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, call, draws);
+    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st, draws}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin);
+    if (draws > 1) {
+        // No sharing on the row-panel routes: the B / draws context rows are expanded to B in the workspace (the K | V region, which these
+        // routes fill only after the context has been projected) and the kernels of old run on the copy.
+        const long per = (long)Mc * w->d, nx = (long)B * per;
+        SD_LAUNCH(ctx_expand_kernel, dim3(grid_for(nx)), dim3(256), 0, st, ctx, s.kv, nx, per, draws);
+        SD_CHECK_LAUNCH("ctx_expand_kernel");
+        ctx = s.kv;
+    }
     return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin);
 }
 
@@ -3133,6 +3160,29 @@ extern "C" int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx
     const PinArgs pin{pin_x0, pin_noise, pin_rows};
     return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode == 4 ? 3 : max_mode,
                            stream, &pin);
+}
+
+// `draws` trajectories per context: ctx (B / draws, Mc, d), trajectory b reads context b / draws.  On the trajectory routes the context is
+// projected, folded and packed once per CONTEXT and the shared instantiations of the step kernels read it; modes 0 - 2 expand the rows and
+// run as ever (correct, not shared).  Pin pointers all NULL: unpinned.  draws == 1 or Mc == 0: the call of old, launch for launch.
+extern "C" int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                    float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                    int max_mode, const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, int draws, void *stream) {
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_draws: draws must be >= 1 and divide B");
+    const int n_pin = (pin_x0 ? 1 : 0) + (pin_noise ? 1 : 0) + (pin_rows ? 1 : 0);
+    if (n_pin != 0 && n_pin != 3) return fail(SD_E_BADARG, "sd_ddim_sample_draws: pin_x0, pin_noise and pin_rows must be given together");
+    if (Mc <= 0) draws = 1;   // no context rows: nothing to share
+    if (n_pin == 0) return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, draws);
+    if (pin_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_draws: pin_noise must not alias x (x is overwritten by the first step)");
+    const PinArgs pin{pin_x0, pin_noise, pin_rows};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode == 4 ? 3 : max_mode,
+                           stream, &pin, draws);
+}
+
+// sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)
+extern "C" int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws) {
+    if (max_mode < -1 || max_mode > 4 || draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_sampler_route_draws: bad argument");
+    return sampler_plan(d, heads, T, Mc, J, L, B, max_mode < 0 ? 3 : max_mode, CALL_ROLLOUT, Mc > 0 ? draws : 1).route;
 }
 
 // ---- the denoiser evaluated step by step on the trajectory kernels (the reference's own loop form) --------------------------

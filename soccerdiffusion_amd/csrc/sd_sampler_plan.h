@@ -85,13 +85,14 @@ inline SamplerPlan panel_plan(int d, int heads, int T, int Mk, int J, int B, int
 }
 
 // One sampler call: Mc context rows (+ the step row), L layers, B trajectories, max_mode already resolved to 0 .. 4.
-// call: SamplerCall bits.
-inline SamplerPlan sampler_plan(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int call) {
+// call: SamplerCall bits.  draws: trajectories per context (sd_ddim_sample_draws; B is a multiple of it) - the tuned kernels' folded blocks
+// exist once per CONTEXT, so their size limit counts B / draws; everything else is a function of the same integers.
+inline SamplerPlan sampler_plan(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int call, int draws = 1) {
     const SamplerSwitches &sw = sampler_switches();
     const int Mk = Mc + 1;
     if (max_mode >= 3 && sw.traj && sw.f16) {
         // the tuned kernels take any horizon <= 100: they need the folded blocks, not the row-panel kernels' T >= 64
-        if ((long)B * Mk * 2 * d < (1L << 30) && Mk <= sw.max_rows && traj_ok(d, heads, T, Mk, J, L)) {
+        if ((long)(B / (draws > 0 ? draws : 1)) * Mk * 2 * d < (1L << 30) && Mk <= sw.max_rows && traj_ok(d, heads, T, Mk, J, L)) {
             SamplerPlan p{};
             p.key_tiles = (Mk + 15) / 16;
             // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)

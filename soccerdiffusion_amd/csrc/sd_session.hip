@@ -385,6 +385,81 @@ extern "C" int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, c
     return 0;
 }
 
+// ---- the representative of a context's draws (sd_ddim_sample_draws + select="medoid") ------------------------------------------------
+// One workgroup per context: index[c] = argmin_i sum_k |x[c, i] - x[c, k]|^2 over the G draws (T x J each, the sampler's normalised space),
+// and optionally out[c] = x[c, index[c]].  fp32 in fixed orders, so the choice does not depend on scheduling and bitwise-equal draws tie
+// exactly: the distance of a pair i < k is computed ONCE - lane l of a wave sums elements l, l + 64, ... of (x_i - x_k)^2 in that order, the
+// 64 partial sums meet in the xor butterfly 32, 16, .. 1 (every lane ends with the same bits) - and stored as d[i][k] and d[k][i]; the score
+// of draw i is d[i][0] + d[i][1] + ... + d[i][G - 1] in that order (d[i][i] = 0 included); the lowest index among the smallest scores wins.
+// No atomics; contraction is off in this file, so every product and sum rounds on its own.
+namespace ss {
+constexpr int MEDOID_MAX_G = 64;
+__global__ __launch_bounds__(THREADS) void select_medoid_kernel(const float *__restrict__ x, int32_t *__restrict__ index, float *__restrict__ out,
+                                                                  int G, int n) {
+    __shared__ float dist[MEDOID_MAX_G][MEDOID_MAX_G + 1];
+    __shared__ float score[MEDOID_MAX_G];
+    __shared__ int best;
+    const int c = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float *xc = x + (long)c * G * n;
+    if ((int)threadIdx.x < G) dist[threadIdx.x][threadIdx.x] = 0.f;
+    const int pairs = G * (G - 1) / 2;
+    for (int p = wv; p < pairs; p += THREADS / 64) {
+        // pair p of the row-major list (0,1) (0,2) .. (0,G-1) (1,2) ..: wave-uniform
+        int i = 0, left = p;
+        while (left >= G - 1 - i) {
+            left -= G - 1 - i;
+            ++i;
+        }
+        const int k = i + 1 + left;
+        const float *a = xc + (long)i * n, *b = xc + (long)k * n;
+        float acc = 0.f;
+        for (int e = lane; e < n; e += 64) {
+            const float df = a[e] - b[e];
+            acc = acc + df * df;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
+        if (lane == 0) {
+            dist[i][k] = acc;
+            dist[k][i] = acc;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < G) {
+        float sc = 0.f;
+        for (int k = 0; k < G; ++k) sc = sc + dist[threadIdx.x][k];
+        score[threadIdx.x] = sc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int bi = 0;
+        float bs = score[0];
+        for (int i = 1; i < G; ++i)
+            if (score[i] < bs) {
+                bs = score[i];
+                bi = i;
+            }
+        best = bi;
+        index[c] = bi;
+    }
+    __syncthreads();
+    if (out) {
+        const float *src = xc + (long)best * n;
+        float *dst = out + (long)c * n;
+        for (int e = threadIdx.x; e < n; e += THREADS) dst[e] = src[e];
+    }
+}
+}   // namespace ss
+
+extern "C" int sd_select_medoid(const float *x, int32_t *index, float *out, int C, int G, int T, int J, void *stream) {
+    if (!x || !index || C <= 0 || G < 1 || G > ss::MEDOID_MAX_G || T <= 0 || J <= 0 || (long)T * J > (1L << 30))
+        return fail(SD_E_BADARG, "sd_select_medoid: x and index must be given; C, T, J > 0, 1 <= G <= 64");
+    if (out == x) return fail(SD_E_BADARG, "sd_select_medoid: out must not alias x");
+    SD_LAUNCH(ss::select_medoid_kernel, dim3((unsigned)C), dim3(ss::THREADS), 0, (hipStream_t)stream, x, index, out, G, T * J);
+    SD_CHECK_LAUNCH("select_medoid_kernel");
+    return 0;
+}
+
 extern "C" int sd_session_reset(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value, int B,
                                 void *stream) {
     if (!rings || n_rings < 1 || n_rings > SD_SESSION_MAX_RESET_RINGS || B <= 0)

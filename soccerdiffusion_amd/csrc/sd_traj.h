@@ -1445,14 +1445,19 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // ROLL: one iteration of the rollout kernel's step loop - the DDIM coefficients and the step block come from the caller (roll_coef,
 // roll_step) instead of the launch's StepArgs, x of the DDIM update is requested before the fc_out GEMM instead of behind it, and a
 // barrier closes the step: the next one stages the x this one stored (same CU, same L1: workgroup scope) and reuses the statistics rows.
-template <bool WIDE = false, bool PIN = false, bool ROLL = false>
+// DRAWS: the shared-context instantiations (sd_ddim_sample_draws) - `draws` consecutive trajectories read ONE context's folded blocks
+// (g16 / v16 / cb of context traj / draws: a scalar quotient, once per launch or per step of the rollout loop); x, eps, the pinned rows,
+// the status word and the step block stay per trajectory.  Their pin is a runtime option (pin.rows NULL: nothing pinned), so that
+// "shared" and "shared + pinned" are one kernel.
+template <bool WIDE = false, bool PIN = false, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
-                                                 int roll_step = 0, int roll_wave = 0) {
+                                                 int roll_step = 0, int roll_wave = 0, int draws = 1) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
     else ctx_init(c, smem, a.T);
     const long traj = blockIdx.x;
+    const long cidx = DRAWS ? (long)((unsigned)blockIdx.x / (unsigned)draws) : traj;   // whose folded context blocks this workgroup reads
     const int J = a.J;
     TJ_STAMP(0);
     f32x4 H[2][NTT];
@@ -1523,7 +1528,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
     layer_norm_to_x<!PRECISE>(c, H, a.n1_w, a.n1_b);
     TJ_STAMP(2);
 #pragma unroll 1
-    for (int l = 0; l < a.L; ++l) decoder_layer<WIDE>(c, a.layer[l], H, traj, a.Mk, a.scale_log2e, a.status, a.nkt,
+    for (int l = 0; l < a.L; ++l) decoder_layer<WIDE>(c, a.layer[l], H, cidx, a.Mk, a.scale_log2e, a.status, a.nkt,
                                                            ROLL ? (long)roll_step : a.step_per_traj ? (a.step_map ? (long)a.step_map[traj] : traj) : 0L);
     // ---- fc_out + DDIM: eps^T = Wout . h^T + b.  h has no a-priori bound: one power-of-two scale per token
     const Ctx &c_step = c;
@@ -1533,7 +1538,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         const Ctx &c = ROLL ? c_tail : c_step;
         float *stat = reinterpret_cast<float *>(c.smem + LDS_STAT);
         int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
-        if constexpr (PIN) pin_rows = pin.rows[traj];
+        if constexpr (PIN) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
         float am[NTT];
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
@@ -1691,5 +1696,36 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_rollout_kernel(RolloutA
     }
 }
 
+// The shared-context twins (sd_ddim_sample_draws with draws > 1): trajectory b reads the folded blocks of context b / draws, prepared once
+// per context.  One kernel per (NTT, PRECISE) / wide NTT serves pinned and unpinned calls (pin.rows NULL: unpinned; the two-product
+// instantiations are never given pinned rows - mode 4 has no pinned form), and the rollout kernel has its twin for the unpinned
+// one-key-tile calls.  draws == 1 never comes here: it launches the kernels above.
+template <int NTT, bool PRECISE>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_draws_kernel(StepArgs a, PinArgs pin, int draws) {
+    TJ<NTT, PRECISE>::template step_body<false, true, false, true>(a, pin, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_draws_kernel(StepArgs a, PinArgs pin, int draws) {
+    TJ<NTT, true>::template step_body<true, true, false, true>(a, pin, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws);
+}
+struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
+    RolloutArgs ra;
+    int draws;
+};
+// (the step loop of traj_step_rollout_kernel; the group size is re-read with the rest of the argument, the quotient taken anew in every step)
+template <int NTT, bool PRECISE>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_rollout_draws_kernel(RolloutDrawsArgs) {
+    typedef const __attribute__((address_space(4))) RolloutDrawsArgs *KernArg;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_steps = ((KernArg)__builtin_amdgcn_kernarg_segment_ptr())->ra.r.n_steps;
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        KernArg ka = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const RolloutDrawsArgs &k = *(const RolloutDrawsArgs *)ka;
+        TJ<NTT, PRECISE>::template step_body<false, false, true, true>(k.ra.a, PinArgs{}, f32x4{k.ra.r.coef[i][0], k.ra.r.coef[i][1], k.ra.r.coef[i][2], k.ra.r.coef[i][3]},
+                                                                       i, wave, k.draws);
+    }
+}
 
 }   // namespace tj

@@ -321,10 +321,12 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
 }
 
 // the kernel argument of step i of the n_steps prepared ones (the rollout kernel: of the steps from i on)
-static tj::StepArgs step_args(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-                              bool per_traj, int nkt, int32_t *status) {
+// C: the contexts traj_prepare_ctx folded (the layers' plane regions are C blocks long); B itself, except for a shared-context call
+// (sd_traj_draws.hip), whose B trajectories read C = B / draws contexts
+tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
+                            bool per_traj, int nkt, int32_t *status, int C) {
     const int d = w->d, L = w->L;
-    const size_t blk = (size_t)32 * d, cbstride = (size_t)B * nkt * 64;
+    const size_t blk = (size_t)32 * d, cbstride = (size_t)C * nkt * 64;
     tj::StepArgs a{};
     a.nkt = nkt;
     a.status = status;
@@ -350,8 +352,8 @@ static tj::StepArgs step_args(const sd_denoiser_weights *w, const TrajWs &s, flo
         q.w_o = f16_wf(s.wf, l, d, 0); q.w_1 = f16_wf(s.wf, l, d, 1); q.w_2 = f16_wf(s.wf, l, d, 2); q.w_in = f16_wf(s.wf, l, d, 3);
         q.b_in = lw.sa_in_b; q.b_o = lw.sa_out_b; q.b_1 = lw.lin1_b; q.b_2 = lw.lin2_b; q.b_oc = lw.ca_out_b;
         q.sc = s.scales + l * 8;
-        q.g16 = s.g16 + (size_t)l * B * nkt * 4 * blk;
-        q.v16 = s.v16 + (size_t)l * B * nkt * 4 * blk;
+        q.g16 = s.g16 + (size_t)l * C * nkt * 4 * blk;
+        q.v16 = s.v16 + (size_t)l * C * nkt * 4 * blk;
         q.cb = s.cb + l * cbstride;
         // per-layer regions as carved for mode 2 (n_steps * 4 * blk / n_steps * blk halfs), the step blocks packed densely inside
         q.gstep = s.gstep16 + (size_t)l * n_steps * 4 * blk + (size_t)i * (4 * 8 * 2 * 32);
@@ -367,7 +369,7 @@ static tj::StepArgs step_args(const sd_denoiser_weights *w, const TrajWs &s, flo
 // coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
               bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin) {
-    const tj::StepArgs a = step_args(w, s, x, eps, B, T, Mc, i, n_steps, coef, per_traj, nkt, status);
+    const tj::StepArgs a = traj_step_args(w, s, x, eps, B, T, Mc, i, n_steps, coef, per_traj, nkt, status, B);
     const int ntt = (T + 15) / 16;
     // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
@@ -407,7 +409,7 @@ int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, float *x, in
     static_assert(sizeof(tj::RolloutArgs) <= 4096, "kernel argument");
     if (n < 1 || n > tj::ROLL_MAX_STEPS || i0 < 0 || i0 + n > n_steps || !coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
     tj::RolloutArgs ra{};
-    ra.a = step_args(w, s, x, nullptr, B, T, Mc, i0, n_steps, coef + 4 * i0, false, 1, status);
+    ra.a = traj_step_args(w, s, x, nullptr, B, T, Mc, i0, n_steps, coef + 4 * i0, false, 1, status, B);
     tj::RollArgs &r = ra.r;
     r.n_steps = n;
     for (int i = 0; i < n; ++i)

@@ -33,4 +33,11 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *ep
 constexpr int TRAJ_ROLLOUT_MAX_STEPS = 64;
 int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, float *x, int B, int T, int Mc, int i0, int n, int n_tok, const float *coef,
                      hipStream_t st, bool precise, int32_t *status);
+// Shared-context calls (sd_ddim_sample_draws, draws > 1; sd_traj_draws.hip): the B trajectories read the folded blocks of C = B / draws
+// contexts - traj_prepare_ctx ran with C - through the shared instantiations of the step kernels.  pin may be NULL (one kernel serves
+// both); the two-product kernels (precise false) take no pin.  Otherwise traj_step / traj_steps_fused argument for argument.
+int traj_step_draws(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
+                    hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin, int draws);
+int traj_steps_fused_draws(const sd_denoiser_weights *w, const TrajWs &s, float *x, int B, int T, int Mc, int i0, int n, int n_tok, const float *coef,
+                           hipStream_t st, bool precise, int32_t *status, int draws);
 #endif

@@ -814,12 +814,15 @@ struct TG {
     }
 
     // PIN: the lanes that store the DDIM update store c2 * x0 + c3 * noise instead for the tokens below pin.rows[traj] (PinArgs, sd_common.h)
-    template <bool PIN = false>
-    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}) {
+    // DRAWS: the shared-context instantiation (sd_ddim_sample_draws) - trajectory b reads the K / V planes of context b / draws; its pin is a
+    // runtime option (pin.rows NULL: nothing pinned)
+    template <bool PIN = false, bool DRAWS = false>
+    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1) {
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
         const long traj = blockIdx.x;
+        const long cidx = DRAWS ? (long)((unsigned)blockIdx.x / (unsigned)draws) : traj;
         const int J = a.J;
         f32x4 H[NA][NTT];
         // ---- embedding: h^T = Wemb . x^T + b + pe^T.  x rows -> the K buffer as split planes (k = joint, zero-padded to 32)
@@ -860,14 +863,14 @@ struct TG {
         layer_norm_to_x(c, H, a.layer[0].n1_w, a.layer[0].n1_b);
 #pragma unroll 1
         for (int l = 0; l < a.L; ++l) {
-            decoder_layer(c, a.layer[l], H, traj, a, sblk);
+            decoder_layer(c, a.layer[l], H, cidx, a, sblk);
             if (l + 1 < a.L) layer_norm_to_x(c, H, a.layer[l + 1].n1_w, a.layer[l + 1].n1_b);
         }
         // ---- fc_out + DDIM: eps^T = Wout . h^T + b.  h has no a-priori bound: one power-of-two scale per token
         {
             float *stat = reinterpret_cast<float *>(c.smem + c.oS);
             int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
-            if constexpr (PIN) pin_rows = pin.rows[traj];
+            if constexpr (PIN) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
             float am[NTT];
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
@@ -947,6 +950,11 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_kernel(StepArgs a)
 // its pinned twin (sd_ddim_sample_pin)
 template <int D, int NTT>
 __global__ __launch_bounds__(NTHREADS) void traj_step_generic_pin_kernel(StepArgs a, PinArgs pin) { TG<D, NTT>::template step_body<true>(a, pin); }
+// the shared-context twin (draws > 1 trajectories per context; pinned or not: pin.rows NULL)
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_draws_kernel(StepArgs a, PinArgs pin, int draws) {
+    TG<D, NTT>::template step_body<true, true>(a, pin, draws);
+}
 
 }   // namespace tg
 
@@ -1036,6 +1044,26 @@ StepPinFn step_pin_fn(int ntt) {
     }
     return nullptr;
 }
+typedef void (*StepDrawsFn)(tg::StepArgs, PinArgs, int);
+template <int D>
+StepDrawsFn step_draws_fn(int ntt) {
+    switch (ntt) {
+        case 1: return tg::traj_step_generic_draws_kernel<D, 1>;
+        case 2: return tg::traj_step_generic_draws_kernel<D, 2>;
+        case 3: return tg::traj_step_generic_draws_kernel<D, 3>;
+        default: break;
+    }
+    if constexpr (D <= 256) {
+        switch (ntt) {
+            case 4: return tg::traj_step_generic_draws_kernel<D, 4>;
+            case 5: return tg::traj_step_generic_draws_kernel<D, 5>;
+            case 6: return tg::traj_step_generic_draws_kernel<D, 6>;
+            case 7: return tg::traj_step_generic_draws_kernel<D, 7>;
+            default: break;
+        }
+    }
+    return nullptr;
+}
 
 }   // namespace
 
@@ -1091,10 +1119,13 @@ int trajg_prepare_weights(const sd_denoiser_weights *w, float *gws, int B, int M
     return 0;
 }
 
-int trajg_prepare_ctx(const sd_denoiser_weights *w, float *gws, const float *ctx, float *kvtmp, int B, int Mc, int n_tok, hipStream_t st) {
+// C > 0: a shared-context call (sd_ddim_sample_draws) - ctx holds C = B / draws contexts; their planes are the first C blocks of every
+// layer's region (carved for B, the tail unused), the abs-max words taken over the C contexts
+int trajg_prepare_ctx(const sd_denoiser_weights *w, float *gws, const float *ctx, float *kvtmp, int B, int Mc, int n_tok, hipStream_t st, int C) {
     const int d = w->d, L = w->L;
     const GScratch s = gcarve(gws, B, Mc, d, L, n_tok);
     if (Mc == 0) return 0;   // no planes; the context scales are set from the step tokens' (trajg_prepare_steps)
+    if (C > 0) B = C;        // (the carve-up is the call's; from here on B counts contexts)
     int rc;
     SD_LAUNCH(tg::zero_word_cols16_kernel, dim3(1), dim3(64), 0, st, s.maxbits, L, (int)tg::SC_K, 2);
     SD_CHECK_LAUNCH("zero_word_cols16_kernel");
@@ -1139,9 +1170,10 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
 }
 
 int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-               bool per_traj, hipStream_t st, const int *map, const PinArgs *pin) {
+               bool per_traj, hipStream_t st, const int *map, const PinArgs *pin, int draws) {
     const int d = w->d, L = w->L;
     const GScratch s = gcarve(gws, B, Mc, d, L, n_tok);
+    if (draws < 1 || B % draws || (draws > 1 && per_traj)) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
     tg::StepArgs a{};
     a.x = x;
     a.eps_out = eps;
@@ -1176,6 +1208,20 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, i
     if (pin && !coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     const int hd = d / 4;
     const size_t lds = (size_t)T * (4 * d + 4 * hd + (4 * hd + 32) + 64);
+    if (draws > 1) {   // trajectory b reads the planes of context b / draws: the shared instantiation, pinned or not
+        const StepDrawsFn dfn = d == 128 ? step_draws_fn<128>(ntt) : d == 256 ? step_draws_fn<256>(ntt) : step_draws_fn<512>(ntt);
+        ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
+        static DevFlag draws_attr_set[3][8];
+        const int di = d == 128 ? 0 : d == 256 ? 1 : 2;
+        if (!draws_attr_set[di][ntt]) {
+            const hipError_t e = hipFuncSetAttribute((const void *)dfn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+            if (e != hipSuccess) return fail((int)e, "traj_step_generic_draws_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+            draws_attr_set[di][ntt] = true;
+        }
+        SD_LAUNCH(dfn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a, pin ? *pin : PinArgs{nullptr, nullptr, nullptr}, draws);
+        SD_CHECK_LAUNCH("traj_step_generic_draws_kernel");
+        return 0;
+    }
     ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
     static DevFlag attr_set[2][3][8];
     const int di = d == 128 ? 0 : d == 256 ? 1 : 2;

@@ -342,6 +342,20 @@ def _pin_req(pin, B: int, T: int, J: int, device) -> tuple:
     return known, rows
 
 
+def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
+    """``draws`` of a sampler call, validated before any launch: an int >= 1 with ``n_ctx * draws == B`` (n_ctx None: no context rows -
+    the draws then only have to divide B)."""
+    if isinstance(draws, bool) or not isinstance(draws, int):
+        raise ValueError(f"draws: expected an int >= 1, got {draws!r}")
+    if draws < 1:
+        raise ValueError(f"draws: expected an int >= 1, got {draws}")
+    if B % draws:
+        raise ValueError(f"draws: {B} trajectories are not a multiple of draws = {draws}")
+    if n_ctx is not None and n_ctx * draws != B:
+        raise ValueError(f"context shape mismatch: {n_ctx} contexts x {draws} draws != {B} trajectories")
+    return draws
+
+
 class GraphedSampler:
     """The whole rollout (n_steps x (L x 2 + 3) kernel launches of ``sd_ddim_sample``) captured
     once into a hipGraph and replayed: removes the per-launch host cost, which dominates at
@@ -349,15 +363,18 @@ class GraphedSampler:
     into the captured buffers before every replay.  ``status`` (one int32 on the device) is
     the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay.  ``pin=True`` captures ``sd_ddim_sample_pin`` on static
     pin buffers (known rows, start noise, row counts): a replay copies the call's ``pin=(known, rows)`` into them, so one graph
-    serves every pinning, none (rows = 0) included."""
+    serves every pinning, none (rows = 0) included.  ``draws`` > 1 captures ``sd_ddim_sample_draws``: the context buffer holds B / draws
+    contexts, trajectory b reads context b // draws."""
 
-    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False):
+    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
+                 draws: int = 1):
         dev = step_tokens.device
+        self.draws = _draws_req(draws, B, None)
         self.packed, self.coef = packed, np.ascontiguousarray(coef, dtype=np.float32)
         self.tokens = step_tokens.contiguous()
         self.max_mode = int(max_mode)
         self.x = torch.zeros(B, T, packed.J, dtype=torch.float32, device=dev)
-        self.ctx = torch.zeros(B, Mc, packed.d, dtype=torch.float32, device=dev) if Mc > 0 else None
+        self.ctx = torch.zeros(B // self.draws, Mc, packed.d, dtype=torch.float32, device=dev) if Mc > 0 else None
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pin = None
         if pin:   # (known, noise, rows)
@@ -377,6 +394,14 @@ class GraphedSampler:
 
     def _run(self):
         B, T, _ = self.x.shape
+        if self.draws > 1:
+            pins = [t.data_ptr() for t in self.pin] if self.pin is not None else [None, None, None]
+            check(_lib.load().sd_ddim_sample_draws(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
+                                                   self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None, None,
+                                                   self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
+                                                   len(self.coef), self.status.data_ptr(), self.max_mode, *pins, self.draws, _stream()),
+                  "sd_ddim_sample_draws")
+            return
         if self.pin is not None:
             check(_lib.load().sd_ddim_sample_pin(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
                                                  self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None, None,
@@ -395,6 +420,8 @@ class GraphedSampler:
         (overwritten by the next replay)."""
         if (pin is None) != (self.pin is None):
             raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
+        if self.ctx is not None and tuple(ctx.shape) != tuple(self.ctx.shape):
+            raise ValueError(f"context shape mismatch: expected {tuple(self.ctx.shape)} ({self.draws} draws per context), got {tuple(ctx.shape)}")
         self.x.copy_(x_T)
         if self.ctx is not None:
             self.ctx.copy_(ctx)
@@ -412,7 +439,7 @@ class GraphedSampler:
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False, pin=None):
+                eps_trace: bool = False, pin=None, draws: int = 1):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -424,7 +451,11 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     int or (B,) counts (``pin_rows``): row t of trajectory b is held to ``known`` iff t < rows[b] - on entry c0[0] known + c1[0] x_T,
     after step i c2[i] known + c3[i] x_T in place of the DDIM update, so the returned rows equal ``known`` exactly; every other row is
     sampled to fit, reading the pinned ones through self-attention.  The noise of the pinned rows is ``x_T`` itself (with ``inplace``
-    a private copy of it is taken first).  ``max_mode`` 4 runs the mode-3 kernels.  ``pin=None`` is the call without any of this."""
+    a private copy of it is taken first).  ``max_mode`` 4 runs the mode-3 kernels.  ``pin=None`` is the call without any of this.
+    ``draws`` = G > 1: several draws per observation (``sd_ddim_sample_draws``).  ``ctx`` is (B / G, Mc, d) and trajectory b reads context
+    b // G: the context is projected and folded once per context and the G draws share its planes - bit for bit the result of the call with
+    ``ctx.repeat_interleave(G, 0)``, without the G copies.  Everything else (``x_T``, the traces, ``pin``, ``status``) stays per trajectory."""
+    draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
     lib = _lib.load()
     _req(x_T, "x_T"); _req(step_tokens, "step_tokens")
     B, T, J = x_T.shape
@@ -433,7 +464,7 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     if ctx is not None:
         _req(ctx, "context")
         Mc = ctx.shape[1]
-        if ctx.shape[0] != B or ctx.shape[2] != packed.d:
+        if ctx.shape[0] * draws != B or ctx.shape[2] != packed.d:
             raise ValueError("context shape mismatch")
     coef = np.ascontiguousarray(coef, dtype=np.float32)
     if coef.shape != (n_steps, 4):
@@ -446,6 +477,16 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     tr = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if trace else None
     et = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if eps_trace else None
     ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, n_steps), x.device)
+    if draws > 1:
+        pins = [None, None, None]
+        if pin is not None:
+            noise = x_T.clone() if inplace else x_T   # never x itself: the first step overwrites x
+            pins = [pin[0].data_ptr(), noise.data_ptr(), pin[1].data_ptr()]
+        check(lib.sd_ddim_sample_draws(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
+                                       coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
+                                       B, T, Mc, n_steps, _ptr(status), int(max_mode), *pins, draws, _stream()), "sd_ddim_sample_draws")
+        out = (x,) + ((tr,) if trace else ()) + ((et,) if eps_trace else ())
+        return out if len(out) > 1 else x
     if pin is not None:
         noise = x_T.clone() if inplace else x_T   # never x itself: the first step overwrites x
         check(lib.sd_ddim_sample_pin(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
@@ -481,21 +522,22 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
-                        trace: bool = False, max_mode: Optional[int] = None, pin=None):
+                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin``: as in ``ddim_sample``; every repeat carries it."""
+    ``pin`` and ``draws``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context rows: correct, not shared)."""
     import warnings
 
+    draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
     if pin is not None:   # validated and uploaded once for all repeats
         pin = _pin_req(pin, *x_T.shape, x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
-    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin)
+    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws)
     word = int(status.item())
     if word == 0:
         return out
@@ -505,7 +547,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         # of the checkpoint, so later calls with these weights start there.
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
-            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin)
+            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -514,10 +556,35 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     if mode >= 2:
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin)
+        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
+
+
+def select_medoid(x: Tensor, draws: int, gather: bool = True, index: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """The representative of each context's draws (``sd_select_medoid``): ``x`` (C * draws, T, J) - the draws of a context contiguous, as
+    ``ddim_sample(draws=...)`` returns them - or (C, draws, T, J).  Returns ``(index, chosen)``: index (C,) int32 with
+    index[c] = argmin_i sum_k |x[c, i] - x[c, k]|^2 (ties to the lowest index), and chosen (C, T, J) = x[c, index[c]] bit for bit, or None
+    without ``gather``.  One launch, no read-back.  ``index`` / ``out``: buffers to write into (a session's static ones)."""
+    if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= 64:
+        raise ValueError(f"select_medoid: draws must be an int in [1, 64], got {draws!r}")
+    _req(x, "x")
+    if x.dim() == 4:
+        if x.shape[1] != draws:
+            raise ValueError(f"select_medoid: x {tuple(x.shape)} does not hold {draws} draws per context")
+        Cn, _, T, J = x.shape
+    elif x.dim() == 3 and x.shape[0] % draws == 0 and x.shape[0] > 0:
+        Cn, T, J = x.shape[0] // draws, x.shape[1], x.shape[2]
+    else:
+        raise ValueError(f"select_medoid: expected (C * {draws}, T, J) or (C, {draws}, T, J), got {tuple(x.shape)}")
+    if index is None:
+        index = torch.empty(Cn, dtype=torch.int32, device=x.device)
+    if gather and out is None:
+        out = torch.empty(Cn, T, J, dtype=torch.float32, device=x.device)
+    check(_lib.load().sd_select_medoid(x.data_ptr(), index.data_ptr(), out.data_ptr() if gather else None, Cn, draws, T, J, _stream()),
+          "sd_select_medoid")
+    return index, (out if gather else None)
 
 
 PREPARE_WEIGHTS, PREPARE_CONTEXT = 1, 2   # SD_PREPARE_*

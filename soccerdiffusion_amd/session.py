@@ -25,10 +25,18 @@ new trajectory continues the one the robot is still executing instead of being a
     s = PolicySession(model, batch=1, carry=4, advance=5, hyperparams=hp)   # T = 10: tick every 5 points, 4 points held across the seam
     traj = s.step()                                                         # traj[:, :4] == the previous tick's traj[:, 5:9], bit for bit
 
+Several draws per tick (``draws=G``): the context is encoded once per robot, G trajectories are sampled from it on the shared folded
+context (``ops.ddim_sample(draws=G)``), and the medoid of the G - the draw with the smallest summed squared distance to the others - is
+chosen on the device, committed and returned instead of a single, possibly outlying, sample:
+
+    s = PolicySession(model, batch=2, draws=4, hyperparams=hp)
+    traj, all_draws, index = s.step(return_draws=True)                      # (2, T, J), (2, 4, T, J), (2,): traj[b] == all_draws[b, index[b]]
+
 There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
 
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -39,6 +47,7 @@ from .derived import current, version_key
 KEYS = ("joint_command_history", "rotation", "joint_state")   # the ring modalities, in encode_input_data's order
 WRAPPED = {"joint_command_history": True, "rotation": False, "joint_state": True}   # (x + 3 pi) % (2 pi): ros.py:266-273
 DEFAULT_GAME_STATE = 2   # ros.py:274
+SELECTORS = ("medoid",)   # PolicySession(select=...): which of a tick's draws is committed
 
 
 class _GraphedTick:
@@ -70,24 +79,36 @@ class _GraphedTick:
             self._run()
 
     def _run(self) -> None:
-        self.ctx = self.session._context()
+        s = self.session
+        self.ctx = s._context()
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
-        self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap,
-                                 pin=self.session._pin())
+        if s.draws == 1:
+            self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, pin=s._pin())
+            return
+        # G draws per robot on the shared context, and their medoid: the selection is part of the captured tick
+        self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, pin=s._pin(),
+                                   draws=s.draws)
+        self.index, self.x = ops.select_medoid(self.all, s.draws)
 
-    def __call__(self, x_T: torch.Tensor) -> torch.Tensor:
+    def __call__(self, x_T: torch.Tensor):
+        """The sample (B, T, J); with draws > 1: (the selected sample, all draws (B * G, T, J), index (B,))."""
         self.noise.copy_(x_T)
         self.graph.replay()
-        if int(self.status.item()) == 0:
-            return self.x
-        # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
         s = self.session
-        return s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, pin=s._pin()).contiguous()
+        if int(self.status.item()) == 0:
+            return self.x if s.draws == 1 else (self.x, self.all, self.index)
+        # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
+        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, pin=s._pin(), draws=s.draws).contiguous()
+        if s.draws == 1:
+            return x
+        index, chosen = ops.select_medoid(x, s.draws)
+        return chosen, x, index
 
 
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
-                 hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None):
+                 hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
+                 select: str = "medoid"):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -96,10 +117,15 @@ class PolicySession:
         ``carry`` / ``advance`` (overlapping ticks): a tick pushes the first ``advance`` rows of its trajectory into the action history
         (default: T - carry) and pins the first ``carry`` rows of the next tick to its rows [advance, advance + carry), in normalised
         space as sampled, at every denoising step.  ``advance`` is the number of trajectory points between two ticks.  carry = 0 with
-        the default advance is the session without any of this, launch for launch.  Not for a distilled decoder (no rollout to pin)."""
+        the default advance is the session without any of this, launch for launch.  Not for a distilled decoder (no rollout to pin).
+        ``draws`` = G / ``select``: a tick samples G trajectories per robot from the once-encoded context and commits and returns the
+        one ``select`` names - "medoid": the draw closest to all others (``ops.select_medoid``, on the device).  With ``carry`` all G
+        draws share the seam and the carried rows come from the selected draw.  draws = 1 is the session without any of this, launch
+        for launch (no selection launch).  Not for a distilled decoder (one forward at t = 0 has no sampling to repeat)."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
+        self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -148,6 +174,18 @@ class PolicySession:
             raise ValueError("carry: a distilled decoder is one forward at t = 0 - there is no rollout whose rows could be pinned")
         return carry, advance
 
+    @staticmethod
+    def check_draws(draws: int = 1, select: str = "medoid", distilled: bool = False) -> tuple:
+        """(draws, select) of a session, validated (no device needed): ValueError unless draws is an int in [1, 64] and select a known
+        selector, or if draws > 1 with a distilled decoder."""
+        if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= 64:
+            raise ValueError(f"draws: the number of trajectories sampled per robot and tick is an int in [1, 64], got {draws!r}")
+        if select not in SELECTORS:
+            raise ValueError(f"select: one of {SELECTORS}, got {select!r}")
+        if draws > 1 and distilled:
+            raise ValueError("draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
+        return draws, select
+
     @property
     def _carrying(self) -> bool:
         """The commit is the carrying one: anything but carry = 0 with the whole trajectory pushed."""
@@ -158,9 +196,15 @@ class PolicySession:
         if self.carry == 0:
             return None
         if dev_idx is None:
-            return self._pin_x0, self._pin_rows
-        i = dev_idx.long()
-        return self._pin_x0[i], self._pin_rows[i]
+            known, rows = self._pin_x0, self._pin_rows
+        else:
+            i = dev_idx.long()
+            known, rows = self._pin_x0[i], self._pin_rows[i]
+        if self.draws > 1:   # every draw of a robot is pinned to the robot's carried rows: all draws share the seam
+            S, G = rows.shape[0], self.draws
+            known = known.unsqueeze(1).expand(S, G, self.T, self.J).reshape(S * G, self.T, self.J).contiguous()
+            rows = rows.unsqueeze(1).expand(S, G).reshape(S * G).contiguous()
+        return known, rows
 
     # ---- the plan: shapes from hyperparameters alone ---------------------------------------
     @staticmethod
@@ -392,37 +436,62 @@ class PolicySession:
             out["game_state"] = self._game_state.clone() if dev_idx is None else self._game_state[dev_idx.long()]
         return out
 
-    def step(self, x_T: Optional[torch.Tensor] = None, robots=None) -> torch.Tensor:
+    def step(self, x_T: Optional[torch.Tensor] = None, robots=None, return_draws: bool = False):
         """One tick (ros.py:259-335): the published trajectory (B, T, J) = denormalised sample - pi, also appended to the action
         history (its first ``advance`` rows in a session with overlapping ticks, whose first ``carry`` rows equal rows
         [advance, advance + carry) of the robot's previous tick).  ``x_T``: the start noise (B, T, J) (only read); default: drawn from the session's device generator.
         ``robots``: the tick of those S robots alone - their windows, the context encoders and the rollout at batch S, the commit into
         their action rings only; x_T and the result are (S, T, J).  A subset tick runs eagerly, on the same rings, also where
-        ``use_graph`` is set: the captured graph serves the whole batch."""
+        ``use_graph`` is set: the captured graph serves the whole batch.
+        A session with ``draws`` = G > 1 samples G trajectories per robot - ``x_T`` is (B * G, T, J), robot b's draws contiguous - and
+        commits and returns the selected one; ``return_draws=True`` returns ``(trajectory, draws (B, G, T, J), index (B,) int32)``, the
+        draws denormalised like the trajectory (``trajectory[b]`` is ``draws[b, index[b]]`` bit for bit).  With draws = 1 the draws
+        are the trajectory itself and the index is 0."""
         m = self.model
         self._check_weights("step")
         if m.training:
             raise RuntimeError("PolicySession.step: the model is in train() mode - call model.eval()")
         subset = None if robots is None else self._subset(robots)
-        shape = (self.B if subset is None else subset[0], self.T, self.J)
+        G = self.draws
+        S = self.B if subset is None else subset[0]
+        shape = (S * G, self.T, self.J)
         if x_T is None:
             x_T = torch.randn(shape, dtype=torch.float32, device=self.device, generator=self._gen)
         elif tuple(x_T.shape) != shape or not x_T.is_cuda or x_T.dtype != torch.float32:
             raise ValueError(f"x_T: expected an fp32 tensor {shape} on {self.device}, got {tuple(x_T.shape)} {x_T.dtype} on {x_T.device}")
-        if shape[0] == 0:
-            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if S == 0:
+            empty = torch.empty((0, self.T, self.J), dtype=torch.float32, device=self.device)
+            if not return_draws:
+                return empty
+            return empty, empty.view(0, G, self.T, self.J), torch.empty(0, dtype=torch.int32, device=self.device)
         with torch.no_grad():
+            dev_idx = None if subset is None else subset[2]
             if self.use_graph and subset is None:
                 if self._graph is None:   # first tick after construction / reset(): the rings are new
                     self._graph = _GraphedTick(self, x_T)
-                return self._commit(self._graph(x_T), None)
-            ctx = self._context(subset)
-            dev_idx = None if subset is None else subset[2]
-            if self.distilled:   # one forward at t = 0 (ros.py:293-298)
-                x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:shape[0]])
+                x = self._graph(x_T)
             else:
-                x = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx))
-            return self._commit(x.contiguous(), dev_idx)
+                ctx = self._context(subset)
+                if self.distilled:   # one forward at t = 0 (ros.py:293-298)
+                    x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
+                elif G == 1:
+                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx))
+                else:   # the context was encoded once per robot; its G draws share the folded planes
+                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx), draws=G).contiguous()
+                    index, chosen = ops.select_medoid(every, G)
+                    x = (chosen, every, index)
+            if G == 1:
+                out = self._commit(x.contiguous(), dev_idx)
+                if not return_draws:
+                    return out
+                return out, out.unsqueeze(1), torch.zeros(S, dtype=torch.int32, device=self.device)
+            chosen, every, index = x
+            out = self._commit(chosen, dev_idx)
+            if not return_draws:
+                return out
+            # the commit's expression, one rounding per operation (sd_session.hip: contraction off): (x * std + mean) - pi
+            every = (every.view(S, G, self.T, self.J) * m.std + m.mean) - math.pi
+            return out, every, index.clone()
 
     def _commit(self, x: torch.Tensor, dev_idx) -> torch.Tensor:
         m = self.model

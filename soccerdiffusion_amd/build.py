@@ -106,6 +106,26 @@ def count_packed_fp32(asm: str) -> dict:
     return counts
 
 
+def llvm_tool(name: str):
+    """The toolchain's own llvm tool (clang-offload-bundler, llvm-objdump, llvm-readelf) beside the compiler, or None."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "lib", "llvm", "bin", name)
+    return path if os.path.exists(path) else None
+
+
+def unbundle(obj: str, co: str) -> bool:
+    """Writes the gfx950 code object of a unit's object file to `co`; False where the tools that take the object apart (objcopy, the
+    offload bundler) are missing."""
+    bundler = llvm_tool("clang-offload-bundler")
+    if not shutil.which("objcopy") or not bundler:
+        return False
+    fat = co + ".fatbin"
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+    subprocess.run([bundler, "--type=o", f"--targets=hipv4-amdgcn-amd-amdhsa--{ARCH}", f"--input={fat}", f"--output={co}", "--unbundle"],
+                   check=True, capture_output=True)
+    os.remove(fat)
+    return True
+
+
 def packed_fp32_in_traj_kernels(obj: str):
     """count_packed_fp32 of a unit's object file, or None where the tools that take the
     object apart (objcopy, the offload bundler, llvm-objdump) are missing.  EXTRA_FLAGS removes the packed fp32 operations from that
@@ -113,15 +133,11 @@ def packed_fp32_in_traj_kernels(obj: str):
     effect on the code of every unit in STEP_KERNEL_UNITS."""
     import tempfile
 
-    llvm = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "lib", "llvm", "bin")
-    bundler, objdump = os.path.join(llvm, "clang-offload-bundler"), os.path.join(llvm, "llvm-objdump")
-    if not shutil.which("objcopy") or not os.path.exists(bundler) or not os.path.exists(objdump):
-        return None
+    objdump = llvm_tool("llvm-objdump")
     with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "k.co")
-        subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
-        subprocess.run([bundler, "--type=o", f"--targets=hipv4-amdgcn-amd-amdhsa--{ARCH}", f"--input={fat}", f"--output={co}", "--unbundle"],
-                       check=True, capture_output=True)
+        co = os.path.join(tmp, "k.co")
+        if not objdump or not unbundle(obj, co):
+            return None
         asm = subprocess.run([objdump, "-d", co], check=True, capture_output=True, text=True).stdout
     return count_packed_fp32(asm)
 

@@ -4,8 +4,12 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <atomic>
+#include <type_traits>
 #include <vector>
+
+#include "../../include/soccerdiffusion_hip.h"   // SD_E_*, SD_KCLASS_*
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -308,6 +312,59 @@ struct PinArgs {
     const float *x0, *noise;   // [B][T][J] each: the known rows (normalised space) and the rollout's start noise
     const int *rows;           // [B] in device memory, 0 <= rows[b] <= T
 };
+
+// One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
+// (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
+struct StepReq {
+    float *x, *eps;      // [B][T][J]; eps NULL: the noise prediction is not returned
+    int B, T, Mc;
+    int i, n_tok;        // step index i of the n_tok prepared step blocks (per_traj: block b for trajectory b, i = 0)
+    const float *coef;   // the 4 DDIM coefficients of step i (traj_steps_fused: the rollout's whole table), or NULL: no update, x is only read
+    bool per_traj;
+    int32_t *status;     // range-guard word of the two-product kernels (SD_STATUS_SHARP_LOGITS), or NULL
+    const PinArgs *pin;  // or NULL; needs coef
+    int draws;           // trajectories per context: trajectory b reads context b / draws (1: its own)
+};
+
+// A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.
+// The one table of the step kernels' instantiations - by_ntt<7>(ntt, [](auto n) { return tj::traj_step_wide_kernel<decltype(n)::value>; }) -
+// which names exactly the MAX instantiations 1 .. MAX.
+template <int MAX, class F>
+auto by_ntt(int ntt, F f) -> decltype(f(std::integral_constant<int, 1>{})) {
+    static_assert(MAX >= 1 && MAX <= 7, "tile counts 1 .. 7 (a horizon of at most 112 rows)");
+    switch (ntt) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: if constexpr (MAX >= 2) return f(std::integral_constant<int, 2>{}); break;
+        case 3: if constexpr (MAX >= 3) return f(std::integral_constant<int, 3>{}); break;
+        case 4: if constexpr (MAX >= 4) return f(std::integral_constant<int, 4>{}); break;
+        case 5: if constexpr (MAX >= 5) return f(std::integral_constant<int, 5>{}); break;
+        case 6: if constexpr (MAX >= 6) return f(std::integral_constant<int, 6>{}); break;
+        case 7: if constexpr (MAX >= 7) return f(std::integral_constant<int, 7>{}); break;
+        default: break;
+    }
+    return nullptr;
+}
+
+// The launch of a trajectory step kernel, whatever its family and form: one workgroup per trajectory, timed under SD_KCLASS_TRAJ_STEP,
+// the kernel's dynamic-LDS limit raised to max_lds once per device (attr_set: the caller's flag of this very kernel), the launch
+// checked under the kernel's name.  fn NULL (no such instantiation): SD_E_BADARG.
+template <class Fn, class... Args>
+int launch_step_kernel(Fn fn, const char *name, DevFlag &attr_set, int max_lds, int B, int threads, size_t lds, hipStream_t st, const Args &...args) {
+    if (!fn) return fail(SD_E_BADARG, name);
+    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
+    if (!attr_set) {
+        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+        if (e != hipSuccess) {
+            static thread_local char msg[128];   // (fail keeps the pointer)
+            snprintf(msg, sizeof msg, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize)", name);
+            return fail((int)e, msg);
+        }
+        attr_set = true;
+    }
+    SD_LAUNCH(fn, dim3((unsigned)B), dim3((unsigned)threads), lds, st, args...);
+    SD_CHECK_LAUNCH(name);
+    return 0;
+}
 
 static inline unsigned grid_for(long n, int block = 256) {
     long g = (n + block - 1) / block;

@@ -2950,10 +2950,10 @@ struct TrajCall {
     int prepare_weights() const {
         return generic() ? trajg_prepare_weights(w, s.gws, B, Mc, n_tok, st) : traj_prepare_weights(w, ws(), st);
     }
+    // C = B / draws rows of context are projected, folded and packed; with shared contexts the tail of the plane regions stays unused
     int prepare_ctx(const float *ctx) const {
-        // shared contexts: B / draws rows of context are projected, folded and packed; the tail of the plane regions stays unused
-        if (draws > 1) return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st, B / draws) : traj_prepare_ctx(w, ws(), ctx, B / draws, Mc, plan.key_tiles, st);
-        return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st) : traj_prepare_ctx(w, ws(), ctx, B, Mc, plan.key_tiles, st);
+        const int C = B / draws;
+        return generic() ? trajg_prepare_ctx(w, s.gws, ctx, s.kvtmp, B, Mc, n_tok, st, C) : traj_prepare_ctx(w, ws(), ctx, C, Mc, plan.key_tiles, st);
     }
     // per_traj: one token per trajectory (only the distinct ones are prepared: step_map_kernel), else one per DDIM step
     int prepare_steps(const float *tokens, bool per_traj) const {
@@ -2964,14 +2964,17 @@ struct TrajCall {
     }
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
     // pin: the pinned instantiations (the caller's plan is a three-product one)
+    // (draws > 1: the shared-context instantiations; either family refuses them for per_traj)
+    StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin) const {
+        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws};
+    }
     int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr) const {
-        if (draws > 1) {   // the shared-context instantiations (one kernel for pinned and unpinned calls)
-            if (per_traj) return fail(SD_E_BADARG, "TrajCall: shared contexts exist for rollouts only");
-            if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, false, st, nullptr, pin, draws);
-            return traj_step_draws(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status, pin, draws);
-        }
-        if (generic()) return trajg_step(w, s.gws, x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, per_traj ? s.stepmap : nullptr, pin);
-        return traj_step(w, ws(), x, eps, B, T, Mc, i, n_tok, coef, per_traj, st, plan.key_tiles, plan.precise, plan.precise ? nullptr : status, pin);
+        const StepReq r = req(x, eps, i, coef, per_traj, status, pin);
+        return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
+    }
+    // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
+    int steps_fused(float *x, int i0, int n, const float *coef, int32_t *status) const {
+        return traj_steps_fused(w, ws(), req(x, nullptr, i0, coef, false, status, nullptr), n, st, plan.precise);
     }
 };
 
@@ -3009,9 +3012,7 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
         if (trace || eps_trace || pin || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
         for (int i0 = 0; i0 < c.n_tok; i0 += TRAJ_ROLLOUT_MAX_STEPS) {
             const int nn = c.n_tok - i0 < TRAJ_ROLLOUT_MAX_STEPS ? c.n_tok - i0 : TRAJ_ROLLOUT_MAX_STEPS;
-            if (c.draws > 1) rc = traj_steps_fused_draws(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status, c.draws);
-            else rc = traj_steps_fused(c.w, c.ws(), x, c.B, c.T, c.Mc, i0, nn, c.n_tok, coef, c.st, c.plan.precise, c.plan.precise ? nullptr : status);
-            if (rc) return rc;
+            if ((rc = c.steps_fused(x, i0, nn, coef, status))) return rc;
         }
         return status ? finite_check(x, n, status, c.st) : 0;
     }
@@ -3115,10 +3116,23 @@ __global__ void ctx_expand_kernel(const float *__restrict__ src, float *__restri
     }
 }
 
-// draws: trajectories per context (ctx holds B / draws of them); 1: every trajectory its own - the calls of old
+// Every sd_ddim_sample* entry point.  draws: trajectories per context (ctx holds B / draws of them); 1: every trajectory its own.
+// The pin pointers: all three or none (pin_required: all three).  Mode 4's two-product instantiations have no pinned twin: a pinned call
+// reads max_mode 4 as 3 (and needs no status word).
 static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                            float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream,
-                           const PinArgs *pin, int draws = 1) {
+                           const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, bool pin_required, int draws) {
+    const int n_pin = (pin_x0 ? 1 : 0) + (pin_noise ? 1 : 0) + (pin_rows ? 1 : 0);
+    if (pin_required ? n_pin != 3 : (n_pin != 0 && n_pin != 3))
+        return fail(SD_E_BADARG, pin_required ? "sd_ddim_sample_pin: pin_x0, pin_noise and pin_rows must be given"
+                                              : "sd_ddim_sample_draws: pin_x0, pin_noise and pin_rows must be given together");
+    if (n_pin && pin_noise == x)
+        return fail(SD_E_BADARG, pin_required ? "sd_ddim_sample_pin: pin_noise must not alias x (x is overwritten by the first step)"
+                                              : "sd_ddim_sample_draws: pin_noise must not alias x (x is overwritten by the first step)");
+    const PinArgs pin_args{pin_x0, pin_noise, pin_rows};
+    const PinArgs *pin = n_pin ? &pin_args : nullptr;
+    if (pin && max_mode == 4) max_mode = 3;
+    if (Mc <= 0) draws = 1;   // no context rows: nothing to share
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!step_tokens || !coef || !x || !workspace || B <= 0 || T <= 0 || Mc < 0 || n_steps <= 0 || (Mc > 0 && !ctx))
@@ -3148,35 +3162,26 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
 extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
                                   const float *coef, float *x, float *trace, float *eps_trace, float *workspace, int B, int T, int Mc,
                                   int n_steps, int32_t *status, int max_mode, void *stream) {
-    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr);
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, 1);
 }
 
-// Mode 4's two-product instantiations have no pinned twin: max_mode 4 is read as 3 (and needs no status word)
 extern "C" int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
                                   float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
                                   int max_mode, const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, void *stream) {
-    if (!pin_x0 || !pin_noise || !pin_rows) return fail(SD_E_BADARG, "sd_ddim_sample_pin: pin_x0, pin_noise and pin_rows must be given");
-    if (pin_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_pin: pin_noise must not alias x (x is overwritten by the first step)");
-    const PinArgs pin{pin_x0, pin_noise, pin_rows};
-    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode == 4 ? 3 : max_mode,
-                           stream, &pin);
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, pin_x0, pin_noise, pin_rows,
+                           true, 1);
 }
 
 // `draws` trajectories per context: ctx (B / draws, Mc, d), trajectory b reads context b / draws.  On the trajectory routes the context is
 // projected, folded and packed once per CONTEXT and the shared instantiations of the step kernels read it; modes 0 - 2 expand the rows and
-// run as ever (correct, not shared).  Pin pointers all NULL: unpinned.  draws == 1 or Mc == 0: the call of old, launch for launch.
+// run as ever (correct, not shared).  Pin pointers all NULL: unpinned.  draws == 1 or Mc == 0: sd_ddim_sample_eps / _pin, launch for launch.
 extern "C" int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
                                     float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
                                     int max_mode, const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, int draws, void *stream) {
     if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_draws: draws must be >= 1 and divide B");
-    const int n_pin = (pin_x0 ? 1 : 0) + (pin_noise ? 1 : 0) + (pin_rows ? 1 : 0);
-    if (n_pin != 0 && n_pin != 3) return fail(SD_E_BADARG, "sd_ddim_sample_draws: pin_x0, pin_noise and pin_rows must be given together");
-    if (Mc <= 0) draws = 1;   // no context rows: nothing to share
-    if (n_pin == 0) return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, draws);
-    if (pin_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_draws: pin_noise must not alias x (x is overwritten by the first step)");
-    const PinArgs pin{pin_x0, pin_noise, pin_rows};
-    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode == 4 ? 3 : max_mode,
-                           stream, &pin, draws);
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, pin_x0, pin_noise, pin_rows,
+                           false, draws);
 }
 
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)

@@ -439,28 +439,10 @@ __global__ void pack_w16_multi_kernel(const float *__restrict__ base, const long
 
 typedef void (*Fn)(Args);
 static Fn head_kernel_for(int ntt) {
-    switch (ntt) {
-        case 1: return train_head_fwd_kernel<1>;
-        case 2: return train_head_fwd_kernel<2>;
-        case 3: return train_head_fwd_kernel<3>;
-        case 4: return train_head_fwd_kernel<4>;
-        case 5: return train_head_fwd_kernel<5>;
-        case 6: return train_head_fwd_kernel<6>;
-        case 7: return train_head_fwd_kernel<7>;
-        default: return nullptr;
-    }
+    return by_ntt<7>(ntt, [](auto n) -> Fn { return train_head_fwd_kernel<decltype(n)::value>; });
 }
 static Fn kernel_for(int ntt) {
-    switch (ntt) {
-        case 1: return train_layer_fwd_kernel<1>;
-        case 2: return train_layer_fwd_kernel<2>;
-        case 3: return train_layer_fwd_kernel<3>;
-        case 4: return train_layer_fwd_kernel<4>;
-        case 5: return train_layer_fwd_kernel<5>;
-        case 6: return train_layer_fwd_kernel<6>;
-        case 7: return train_layer_fwd_kernel<7>;
-        default: return nullptr;
-    }
+    return by_ntt<7>(ntt, [](auto n) -> Fn { return train_layer_fwd_kernel<decltype(n)::value>; });
 }
 
 }   // namespace tjt

@@ -1,5 +1,7 @@
 // Tuned trajectory step kernels of the sampler (modes 3 / 4: hidden_dim 256, 4 heads, horizon <= 100, <= 64 memory rows): the host side
-// of sd_traj.h - shape test, the three preparation stages, the step launch - and the step-token kernels that only this path launches.
+// of sd_traj.h - shape test, the three preparation stages, the step launch (traj_step) and the rollout launch (traj_steps_fused), each
+// for every form of the kernel: plain, pinned, shared context (the last one's instantiations compile in sd_traj_draws.hip) - and the
+// step-token kernels that only this path launches.
 // Interface towards the sampler's driver (sd_kernels.hip): sd_traj_host.h, function for function what sd_trajg.h is for the generic family.
 //
 // Built without packed fp32 vector instructions (soccerdiffusion_amd/build.py, EXTRA_FLAGS): the step kernel lives on the overlap of
@@ -26,64 +28,36 @@ bool traj_ok(int d, int heads, int T, int Mk, int J, int L) {
     return d == 256 && heads == 4 && T >= 1 && T <= tj::TMAX && Mk >= 1 && Mk <= 64 && J >= 1 && J <= 32 && L >= 1 && L <= tj::MAX_L;
 }
 
-// the instantiation for ceil(T / 16) token tiles; precise = three fp16 products at the Q | K | V site too (sampler mode 3), else two (mode 4)
+// The kernel pointers.  Token tiles: ntt = ceil(T / 16), 1 .. 7 (by_ntt: sd_common.h).  Variant: 0 = two fp16 products at the Q | K | V
+// site (sampler mode 4), 1 = three (mode 3), 2 = the wide kernel (more than 16 memory rows: three products everywhere, whatever the mode
+// asked for).  The pinned twins (sd_ddim_sample_pin) exist for variants 1 and 2, the rollout kernel (all DDIM steps of a trajectory in one
+// launch) for 0 and 1.
 typedef void (*TrajStepFn)(tj::StepArgs);
-static TrajStepFn traj_step_wide_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tj::traj_step_wide_kernel<1>;
-        case 2: return tj::traj_step_wide_kernel<2>;
-        case 3: return tj::traj_step_wide_kernel<3>;
-        case 4: return tj::traj_step_wide_kernel<4>;
-        case 5: return tj::traj_step_wide_kernel<5>;
-        case 6: return tj::traj_step_wide_kernel<6>;
-        case 7: return tj::traj_step_wide_kernel<7>;
-        default: return nullptr;
-    }
-}
-template <bool PRECISE>
-static TrajStepFn traj_step_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tj::traj_step_kernel<1, PRECISE>;
-        case 2: return tj::traj_step_kernel<2, PRECISE>;
-        case 3: return tj::traj_step_kernel<3, PRECISE>;
-        case 4: return tj::traj_step_kernel<4, PRECISE>;
-        case 5: return tj::traj_step_kernel<5, PRECISE>;
-        case 6: return tj::traj_step_kernel<6, PRECISE>;
-        case 7: return tj::traj_step_kernel<7, PRECISE>;
-        default: return nullptr;
-    }
-}
-
-// the rollout kernel (all DDIM steps of a trajectory in one launch) of the same two instantiation rows
-typedef void (*TrajRolloutFn)(tj::RolloutArgs);
-template <bool PRECISE>
-static TrajRolloutFn traj_rollout_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tj::traj_step_rollout_kernel<1, PRECISE>;
-        case 2: return tj::traj_step_rollout_kernel<2, PRECISE>;
-        case 3: return tj::traj_step_rollout_kernel<3, PRECISE>;
-        case 4: return tj::traj_step_rollout_kernel<4, PRECISE>;
-        case 5: return tj::traj_step_rollout_kernel<5, PRECISE>;
-        case 6: return tj::traj_step_rollout_kernel<6, PRECISE>;
-        case 7: return tj::traj_step_rollout_kernel<7, PRECISE>;
-        default: return nullptr;
-    }
-}
-
-// the pinned twins (sd_ddim_sample_pin): the mode-3 kernel and the wide one; mode 4's two-product instantiations have none
 typedef void (*TrajStepPinFn)(tj::StepArgs, PinArgs);
-static TrajStepPinFn traj_step_pin_fn(int ntt, bool wide) {
-    switch (ntt) {
-        case 1: return wide ? tj::traj_step_wide_pin_kernel<1> : tj::traj_step_pin_kernel<1>;
-        case 2: return wide ? tj::traj_step_wide_pin_kernel<2> : tj::traj_step_pin_kernel<2>;
-        case 3: return wide ? tj::traj_step_wide_pin_kernel<3> : tj::traj_step_pin_kernel<3>;
-        case 4: return wide ? tj::traj_step_wide_pin_kernel<4> : tj::traj_step_pin_kernel<4>;
-        case 5: return wide ? tj::traj_step_wide_pin_kernel<5> : tj::traj_step_pin_kernel<5>;
-        case 6: return wide ? tj::traj_step_wide_pin_kernel<6> : tj::traj_step_pin_kernel<6>;
-        case 7: return wide ? tj::traj_step_wide_pin_kernel<7> : tj::traj_step_pin_kernel<7>;
-        default: return nullptr;
-    }
+typedef void (*TrajRolloutFn)(tj::RolloutArgs);
+static TrajStepFn traj_step_fn(int ntt, int variant) {
+    return by_ntt<7>(ntt, [variant](auto n) {
+        constexpr int N = decltype(n)::value;
+        return variant == 2 ? tj::traj_step_wide_kernel<N> : variant == 1 ? tj::traj_step_kernel<N, true> : tj::traj_step_kernel<N, false>;
+    });
 }
+static TrajStepPinFn traj_step_pin_fn(int ntt, int variant) {
+    return by_ntt<7>(ntt, [variant](auto n) {
+        constexpr int N = decltype(n)::value;
+        return variant == 2 ? tj::traj_step_wide_pin_kernel<N> : tj::traj_step_pin_kernel<N>;
+    });
+}
+static TrajRolloutFn traj_rollout_fn(int ntt, bool precise) {
+    return by_ntt<7>(ntt, [precise](auto n) {
+        constexpr int N = decltype(n)::value;
+        return precise ? tj::traj_step_rollout_kernel<N, true> : tj::traj_step_rollout_kernel<N, false>;
+    });
+}
+// sd_traj_draws.hip: the shared-context instantiations of the same rows (one kernel serves pinned and unpinned calls: pin.rows NULL)
+typedef void (*TrajStepDrawsFn)(tj::StepArgs, PinArgs, int);
+typedef void (*TrajRolloutDrawsFn)(tj::RolloutDrawsArgs);
+TrajStepDrawsFn traj_step_draws_fn(int ntt, int variant);
+TrajRolloutDrawsFn traj_rollout_draws_fn(int ntt, bool precise);
 
 // zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
 __global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
@@ -320,18 +294,16 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
     return 0;
 }
 
-// the kernel argument of step i of the n_steps prepared ones (the rollout kernel: of the steps from i on)
-// C: the contexts traj_prepare_ctx folded (the layers' plane regions are C blocks long); B itself, except for a shared-context call
-// (sd_traj_draws.hip), whose B trajectories read C = B / draws contexts
-tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-                            bool per_traj, int nkt, int32_t *status, int C) {
-    const int d = w->d, L = w->L;
+// the kernel argument of step r.i of the r.n_tok prepared ones (the rollout kernel: of the steps from r.i on); coef: that step's four
+// C = B / draws: the contexts traj_prepare_ctx folded (the layers' plane regions are C blocks long)
+static tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, const float *coef, int nkt) {
+    const int d = w->d, L = w->L, C = r.B / r.draws, n_steps = r.n_tok, i = r.i;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)C * nkt * 64;
     tj::StepArgs a{};
     a.nkt = nkt;
-    a.status = status;
-    a.x = x;
-    a.eps_out = eps;
+    a.status = r.status;
+    a.x = r.x;
+    a.eps_out = r.eps;
     a.w_emb = s.wio;
     a.b_emb = w->emb_b;
     a.pe = w->pe;
@@ -342,9 +314,9 @@ tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s, float
     a.sc_io = s.scales + L * 8 + 6;
     if (coef) { a.c0 = coef[0]; a.c1 = coef[1]; a.c2 = coef[2]; a.c3 = coef[3]; }
     a.scale_log2e = (1.0f / sqrtf((float)(d / w->heads))) * 1.44269504088896340736f;
-    a.T = T; a.B = B; a.J = w->J; a.L = L; a.Mk = Mc + 1; a.update_x = coef ? 1 : 0;
-    a.step_per_traj = per_traj ? 1 : 0;
-    a.step_map = per_traj ? s.stepmap : nullptr;
+    a.T = r.T; a.B = r.B; a.J = w->J; a.L = L; a.Mk = r.Mc + 1; a.update_x = coef ? 1 : 0;
+    a.step_per_traj = r.per_traj ? 1 : 0;
+    a.step_map = r.per_traj ? s.stepmap : nullptr;
     for (int l = 0; l < L; ++l) {
         const sd_layer_weights &lw = w->layers[l];
         tj::LayerW &q = a.layer[l];
@@ -365,66 +337,48 @@ tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s, float
     return a;
 }
 
-// one denoiser step + DDIM update in ONE launch (step index i selects the step-token blocks)
-// coef NULL: no DDIM update (x is only read); per_traj: trajectory b reads step block b of the n_steps prepared ones (i = 0)
-int traj_step(const sd_denoiser_weights *w, const TrajWs &s, float *x, float *eps, int B, int T, int Mc, int i, int n_steps, const float *coef,
-              bool per_traj, hipStream_t st, int nkt, bool precise, int32_t *status, const PinArgs *pin) {
-    const tj::StepArgs a = traj_step_args(w, s, x, eps, B, T, Mc, i, n_steps, coef, per_traj, nkt, status, B);
-    const int ntt = (T + 15) / 16;
-    // more than 16 memory rows: the wide instantiation (three products everywhere, whatever the mode asked for)
+// B a multiple of draws; more than one draw per context exists for rollouts (one step token per DDIM step) only
+static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 && r.B % r.draws == 0 && !(r.draws > 1 && r.per_traj); }
+
+// one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
+// as a runtime option
+int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise) {
+    const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
-    const TrajStepFn fn = variant == 2 ? traj_step_wide_fn(ntt) : (precise ? traj_step_fn<true>(ntt) : traj_step_fn<false>(ntt));
-    if (!fn) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
-    if (pin) {
-        if (!coef || variant == 0) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
-        const TrajStepPinFn pfn = traj_step_pin_fn(ntt, variant == 2);
-        ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-        static DevFlag pin_attr_set[2][8];
-        if (!pin_attr_set[variant - 1][ntt]) {
-            const hipError_t e = hipFuncSetAttribute((const void *)pfn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
-            if (e != hipSuccess) return fail((int)e, "traj_step_pin_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            pin_attr_set[variant - 1][ntt] = true;
-        }
-        SD_LAUNCH(pfn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a, *pin);
-        SD_CHECK_LAUNCH("traj_step_pin_kernel");
-        return 0;
-    }
-    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-    static DevFlag attr_set[3][8];
-    if (!attr_set[variant][ntt]) {
-        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
-        if (e != hipSuccess) return fail((int)e, "traj_step_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        attr_set[variant][ntt] = true;
-    }
-    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, a);
-    SD_CHECK_LAUNCH("traj_step_kernel");
-    return 0;
+    if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
+    if (!traj_groups_ok(r)) return fail(SD_E_BADARG, "traj_step_draws_kernel: B must be a multiple of draws >= 1 (per-trajectory step tokens: draws = 1)");
+    if (r.pin && (!r.coef || variant == 0)) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
+    const tj::StepArgs a = traj_step_args(w, s, r, r.coef, nkt);
+    static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][variant][ntt]
+    DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][variant][ntt];
+    if (r.draws > 1)
+        return launch_step_kernel(traj_step_draws_fn(ntt, variant), "traj_step_draws_kernel", flag, tj::LDS_BYTES, r.B, tj::NTHREADS, tj::LDS_BYTES, st,
+                                  a, r.pin ? *r.pin : PinArgs{nullptr, nullptr, nullptr}, r.draws);
+    if (r.pin)
+        return launch_step_kernel(traj_step_pin_fn(ntt, variant), "traj_step_pin_kernel", flag, tj::LDS_BYTES, r.B, tj::NTHREADS, tj::LDS_BYTES, st, a, *r.pin);
+    return launch_step_kernel(traj_step_fn(ntt, variant), "traj_step_kernel", flag, tj::LDS_BYTES, r.B, tj::NTHREADS, tj::LDS_BYTES, st, a);
 }
 
-// DDIM steps i0 .. i0 + n - 1 of the n_steps prepared ones in ONE launch, x updated in place (n <= TRAJ_ROLLOUT_MAX_STEPS; one key tile).
+// DDIM steps r.i .. r.i + n - 1 of the r.n_tok prepared ones in ONE launch, x updated in place (n <= TRAJ_ROLLOUT_MAX_STEPS; one key tile).
 // Step for step the arithmetic of traj_step; profiled under the same class.
-int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, float *x, int B, int T, int Mc, int i0, int n, int n_steps, const float *coef,
-                     hipStream_t st, bool precise, int32_t *status) {
+int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, int n, hipStream_t st, bool precise) {
     static_assert(TRAJ_ROLLOUT_MAX_STEPS == tj::ROLL_MAX_STEPS, "one cap on both sides of the interface");
-    static_assert(sizeof(tj::RolloutArgs) <= 4096, "kernel argument");
-    if (n < 1 || n > tj::ROLL_MAX_STEPS || i0 < 0 || i0 + n > n_steps || !coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
-    tj::RolloutArgs ra{};
-    ra.a = traj_step_args(w, s, x, nullptr, B, T, Mc, i0, n_steps, coef + 4 * i0, false, 1, status, B);
-    tj::RollArgs &r = ra.r;
-    r.n_steps = n;
+    static_assert(sizeof(tj::RolloutDrawsArgs) <= 4096, "kernel argument (RolloutArgs and the group size)");
+    const int ntt = (r.T + 15) / 16;
+    if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_rollout_kernel: horizon out of range");
+    if (n < 1 || n > tj::ROLL_MAX_STEPS || r.i < 0 || r.i + n > r.n_tok || !r.coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
+    if (!traj_groups_ok(r) || r.eps || r.per_traj || r.pin)
+        return fail(SD_E_BADARG, "traj_step_rollout_kernel: B a multiple of draws; nothing returned per step, no per-trajectory tokens, no pin");
+    tj::RolloutDrawsArgs da{};
+    da.draws = r.draws;
+    da.ra.a = traj_step_args(w, s, r, r.coef + 4 * r.i, 1);
+    da.ra.r.n_steps = n;
     for (int i = 0; i < n; ++i)
-        for (int k = 0; k < 4; ++k) r.coef[i][k] = coef[4 * (i0 + i) + k];
-    const int ntt = (T + 15) / 16;
-    const TrajRolloutFn fn = precise ? traj_rollout_fn<true>(ntt) : traj_rollout_fn<false>(ntt);
-    if (!fn) return fail(SD_E_BADARG, "traj_step_rollout_kernel: horizon out of range");
-    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-    static DevFlag attr_set[2][8];
-    if (!attr_set[precise ? 1 : 0][ntt]) {
-        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, tj::LDS_BYTES);
-        if (e != hipSuccess) return fail((int)e, "traj_step_rollout_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        attr_set[precise ? 1 : 0][ntt] = true;
-    }
-    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tj::NTHREADS), (size_t)tj::LDS_BYTES, st, ra);
-    SD_CHECK_LAUNCH("traj_step_rollout_kernel");
-    return 0;
+        for (int k = 0; k < 4; ++k) da.ra.r.coef[i][k] = r.coef[4 * (r.i + i) + k];
+    static DevFlag attr_set[2][2][8];   // [own | shared context][precise][ntt]
+    if (r.draws > 1)
+        return launch_step_kernel(traj_rollout_draws_fn(ntt, precise), "traj_step_rollout_draws_kernel", attr_set[1][precise][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS,
+                                  tj::LDS_BYTES, st, da);
+    return launch_step_kernel(traj_rollout_fn(ntt, precise), "traj_step_rollout_kernel", attr_set[0][precise][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS, tj::LDS_BYTES, st,
+                              da.ra);
 }

@@ -1004,70 +1004,32 @@ int zero_words(unsigned *p, int n, hipStream_t st) {
     return 0;
 }
 
+// The kernel pointers: f(hidden_dim, token tiles) for the instantiated pairs - 1 .. 7 tiles (by_ntt: sd_common.h) at hidden_dim 128 and
+// 256, 1 .. 3 at 512 - and nullptr for every other
+template <class F>
+auto by_d_ntt(int d, int ntt, F f) {
+    using std::integral_constant;
+    return d == 128   ? by_ntt<7>(ntt, [f](auto n) { return f(integral_constant<int, 128>{}, n); })
+           : d == 256 ? by_ntt<7>(ntt, [f](auto n) { return f(integral_constant<int, 256>{}, n); })
+           : d == 512 ? by_ntt<3>(ntt, [f](auto n) { return f(integral_constant<int, 512>{}, n); })
+                      : nullptr;
+}
 typedef void (*StepFn)(tg::StepArgs);
-template <int D>
-StepFn step_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tg::traj_step_generic_kernel<D, 1>;
-        case 2: return tg::traj_step_generic_kernel<D, 2>;
-        case 3: return tg::traj_step_generic_kernel<D, 3>;
-        default: break;
-    }
-    if constexpr (D <= 256) {
-        switch (ntt) {
-            case 4: return tg::traj_step_generic_kernel<D, 4>;
-            case 5: return tg::traj_step_generic_kernel<D, 5>;
-            case 6: return tg::traj_step_generic_kernel<D, 6>;
-            case 7: return tg::traj_step_generic_kernel<D, 7>;
-            default: break;
-        }
-    }
-    return nullptr;
-}
 typedef void (*StepPinFn)(tg::StepArgs, PinArgs);
-template <int D>
-StepPinFn step_pin_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tg::traj_step_generic_pin_kernel<D, 1>;
-        case 2: return tg::traj_step_generic_pin_kernel<D, 2>;
-        case 3: return tg::traj_step_generic_pin_kernel<D, 3>;
-        default: break;
-    }
-    if constexpr (D <= 256) {
-        switch (ntt) {
-            case 4: return tg::traj_step_generic_pin_kernel<D, 4>;
-            case 5: return tg::traj_step_generic_pin_kernel<D, 5>;
-            case 6: return tg::traj_step_generic_pin_kernel<D, 6>;
-            case 7: return tg::traj_step_generic_pin_kernel<D, 7>;
-            default: break;
-        }
-    }
-    return nullptr;
-}
 typedef void (*StepDrawsFn)(tg::StepArgs, PinArgs, int);
-template <int D>
-StepDrawsFn step_draws_fn(int ntt) {
-    switch (ntt) {
-        case 1: return tg::traj_step_generic_draws_kernel<D, 1>;
-        case 2: return tg::traj_step_generic_draws_kernel<D, 2>;
-        case 3: return tg::traj_step_generic_draws_kernel<D, 3>;
-        default: break;
-    }
-    if constexpr (D <= 256) {
-        switch (ntt) {
-            case 4: return tg::traj_step_generic_draws_kernel<D, 4>;
-            case 5: return tg::traj_step_generic_draws_kernel<D, 5>;
-            case 6: return tg::traj_step_generic_draws_kernel<D, 6>;
-            case 7: return tg::traj_step_generic_draws_kernel<D, 7>;
-            default: break;
-        }
-    }
-    return nullptr;
+StepFn step_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepFn { return tg::traj_step_generic_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+StepPinFn step_pin_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepPinFn { return tg::traj_step_generic_pin_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+StepDrawsFn step_draws_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 
 }   // namespace
 
-// the shapes step_fn is instantiated for (the environment's switches are the plan's business: sd_sampler_plan.h)
+// the shapes by_d_ntt names an instantiation for (the environment's switches are the plan's business: sd_sampler_plan.h)
 bool trajg_ok(int d, int heads, int T, int Mk, int J, int L) {
     if (!(d == 128 || d == 256 || d == 512) || heads != 4) return false;
     return T >= 1 && T <= (d == 512 ? 48 : 100) && Mk >= 1 && J >= 1 && J <= 32 && L >= 1 && L <= tg::MAX_L;
@@ -1119,13 +1081,13 @@ int trajg_prepare_weights(const sd_denoiser_weights *w, float *gws, int B, int M
     return 0;
 }
 
-// C > 0: a shared-context call (sd_ddim_sample_draws) - ctx holds C = B / draws contexts; their planes are the first C blocks of every
-// layer's region (carved for B, the tail unused), the abs-max words taken over the C contexts
+// ctx holds C = B / draws contexts; their planes are the first C blocks of every layer's region (carved for B: with shared contexts the
+// tail stays unused), the abs-max words taken over the C contexts
 int trajg_prepare_ctx(const sd_denoiser_weights *w, float *gws, const float *ctx, float *kvtmp, int B, int Mc, int n_tok, hipStream_t st, int C) {
     const int d = w->d, L = w->L;
     const GScratch s = gcarve(gws, B, Mc, d, L, n_tok);
     if (Mc == 0) return 0;   // no planes; the context scales are set from the step tokens' (trajg_prepare_steps)
-    if (C > 0) B = C;        // (the carve-up is the call's; from here on B counts contexts)
+    B = C;                   // (the carve-up is the call's; from here on B counts contexts)
     int rc;
     SD_LAUNCH(tg::zero_word_cols16_kernel, dim3(1), dim3(64), 0, st, s.maxbits, L, (int)tg::SC_K, 2);
     SD_CHECK_LAUNCH("zero_word_cols16_kernel");
@@ -1169,25 +1131,27 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
     return 0;
 }
 
-int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, int B, int T, int Mc, int i, int n_tok, const float *coef,
-               bool per_traj, hipStream_t st, const int *map, const PinArgs *pin, int draws) {
-    const int d = w->d, L = w->L;
-    const GScratch s = gcarve(gws, B, Mc, d, L, n_tok);
-    if (draws < 1 || B % draws || (draws > 1 && per_traj)) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
+int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipStream_t st, const int *map) {
+    const int d = w->d, L = w->L, T = r.T;
+    const GScratch s = gcarve(gws, r.B, r.Mc, d, L, r.n_tok);
+    if (r.draws < 1 || r.B % r.draws || (r.draws > 1 && r.per_traj)) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
+    const int ntt = (T + 15) / 16;
+    if (ntt < 1 || ntt > (d == 512 ? 3 : 7)) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
+    if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     tg::StepArgs a{};
-    a.x = x;
-    a.eps_out = eps;
+    a.x = r.x;
+    a.eps_out = r.eps;
     a.w_emb = s.wio;
     a.b_emb = w->emb_b;
     a.pe = w->pe;
     a.w_out = s.wio + (size_t)2 * 32 * d;
     a.b_out = w->out_b;
     a.sc_io = s.scales + L * 16;
-    if (coef) { a.c0 = coef[0]; a.c1 = coef[1]; a.c2 = coef[2]; a.c3 = coef[3]; }
+    if (r.coef) { a.c0 = r.coef[0]; a.c1 = r.coef[1]; a.c2 = r.coef[2]; a.c3 = r.coef[3]; }
     a.scale_log2e = (1.0f / sqrtf((float)(d / w->heads))) * 1.44269504088896340736f;
-    a.T = T; a.B = B; a.J = w->J; a.L = L; a.Mc = Mc; a.nkp = s.nkp; a.update_x = coef ? 1 : 0;
-    a.step_per_traj = per_traj ? 1 : 0;
-    a.step_map = per_traj ? map : nullptr;
+    a.T = T; a.B = r.B; a.J = w->J; a.L = L; a.Mc = r.Mc; a.nkp = s.nkp; a.update_x = r.coef ? 1 : 0;
+    a.step_per_traj = r.per_traj ? 1 : 0;
+    a.step_map = r.per_traj ? map : nullptr;
     a.kv_traj_halfs = (long)s.nkp * 64 * d;
     for (int l = 0; l < L; ++l) {
         const sd_layer_weights &lw = w->layers[l];
@@ -1199,43 +1163,16 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, float *x, float *eps, i
         q.sc = s.scales + l * 16;
         q.kp = s.kp + (size_t)l * s.kv_layer_halfs;
         q.vp = s.vp + (size_t)l * s.kv_layer_halfs;
-        q.kvs = s.kvs + (size_t)l * s.kvs_layer_halfs + (size_t)(per_traj ? 0 : i) * 4 * d;
+        q.kvs = s.kvs + (size_t)l * s.kvs_layer_halfs + (size_t)(r.per_traj ? 0 : r.i) * 4 * d;
     }
-    const int ntt = (T + 15) / 16;
-    const StepFn fn = d == 128 ? step_fn<128>(ntt) : d == 256 ? step_fn<256>(ntt) : step_fn<512>(ntt);
-    const StepPinFn pfn = d == 128 ? step_pin_fn<128>(ntt) : d == 256 ? step_pin_fn<256>(ntt) : step_pin_fn<512>(ntt);
-    if (!fn || !pfn) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
-    if (pin && !coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     const int hd = d / 4;
     const size_t lds = (size_t)T * (4 * d + 4 * hd + (4 * hd + 32) + 64);
-    if (draws > 1) {   // trajectory b reads the planes of context b / draws: the shared instantiation, pinned or not
-        const StepDrawsFn dfn = d == 128 ? step_draws_fn<128>(ntt) : d == 256 ? step_draws_fn<256>(ntt) : step_draws_fn<512>(ntt);
-        ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-        static DevFlag draws_attr_set[3][8];
-        const int di = d == 128 ? 0 : d == 256 ? 1 : 2;
-        if (!draws_attr_set[di][ntt]) {
-            const hipError_t e = hipFuncSetAttribute((const void *)dfn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-            if (e != hipSuccess) return fail((int)e, "traj_step_generic_draws_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            draws_attr_set[di][ntt] = true;
-        }
-        SD_LAUNCH(dfn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a, pin ? *pin : PinArgs{nullptr, nullptr, nullptr}, draws);
-        SD_CHECK_LAUNCH("traj_step_generic_draws_kernel");
-        return 0;
-    }
-    ProfScope prof(SD_KCLASS_TRAJ_STEP, st);
-    static DevFlag attr_set[2][3][8];
-    const int di = d == 128 ? 0 : d == 256 ? 1 : 2;
-    if (!attr_set[pin ? 1 : 0][di][ntt]) {
-        const hipError_t e = hipFuncSetAttribute(pin ? (const void *)pfn : (const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        if (e != hipSuccess) return fail((int)e, "traj_step_generic_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        attr_set[pin ? 1 : 0][di][ntt] = true;
-    }
-    if (pin) {
-        SD_LAUNCH(pfn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a, *pin);
-        SD_CHECK_LAUNCH("traj_step_generic_pin_kernel");
-        return 0;
-    }
-    SD_LAUNCH(fn, dim3((unsigned)B), dim3(tg::NTHREADS), lds, st, a);
-    SD_CHECK_LAUNCH("traj_step_generic_kernel");
-    return 0;
+    constexpr int MAX_LDS = 163840;
+    static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
+    DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.draws > 1)   // trajectory b reads the planes of context b / draws: the shared instantiation, pinned or not
+        return launch_step_kernel(step_draws_fn(d, ntt), "traj_step_generic_draws_kernel", flag, MAX_LDS, r.B, tg::NTHREADS, lds, st, a,
+                                  r.pin ? *r.pin : PinArgs{nullptr, nullptr, nullptr}, r.draws);
+    if (r.pin) return launch_step_kernel(step_pin_fn(d, ntt), "traj_step_generic_pin_kernel", flag, MAX_LDS, r.B, tg::NTHREADS, lds, st, a, *r.pin);
+    return launch_step_kernel(step_fn(d, ntt), "traj_step_generic_kernel", flag, MAX_LDS, r.B, tg::NTHREADS, lds, st, a);
 }

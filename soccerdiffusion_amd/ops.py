@@ -356,15 +356,29 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
     return draws
 
 
+def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
+                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int):
+    """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
+    ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
+    ``sd_ddim_sample_pin``, launch for launch.  Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
+    B, T, _ = x.shape
+    check(_lib.load().sd_ddim_sample_draws(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                           x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1], len(coef),
+                                           _ptr(status), int(max_mode), *[_ptr(t) for t in (pin or (None, None, None))], draws, _stream()),
+          "sd_ddim_sample_draws")
+    out = (x,) + tuple(t for t in (tr, et) if t is not None)
+    return out if len(out) > 1 else x
+
+
 class GraphedSampler:
     """The whole rollout (n_steps x (L x 2 + 3) kernel launches of ``sd_ddim_sample``) captured
     once into a hipGraph and replayed: removes the per-launch host cost, which dominates at
     small batch (the robot's B = 1, 30-step rollout).  Static shapes; the inputs are copied
     into the captured buffers before every replay.  ``status`` (one int32 on the device) is
-    the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay.  ``pin=True`` captures ``sd_ddim_sample_pin`` on static
+    the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay.  ``pin=True`` captures the pinned call on static
     pin buffers (known rows, start noise, row counts): a replay copies the call's ``pin=(known, rows)`` into them, so one graph
-    serves every pinning, none (rows = 0) included.  ``draws`` > 1 captures ``sd_ddim_sample_draws``: the context buffer holds B / draws
-    contexts, trajectory b reads context b // draws."""
+    serves every pinning, none (rows = 0) included.  ``draws`` > 1: the context buffer holds B / draws contexts, trajectory b reads
+    context b // draws.  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
                  draws: int = 1):
@@ -393,27 +407,7 @@ class GraphedSampler:
             self._run()
 
     def _run(self):
-        B, T, _ = self.x.shape
-        if self.draws > 1:
-            pins = [t.data_ptr() for t in self.pin] if self.pin is not None else [None, None, None]
-            check(_lib.load().sd_ddim_sample_draws(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
-                                                   self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None, None,
-                                                   self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
-                                                   len(self.coef), self.status.data_ptr(), self.max_mode, *pins, self.draws, _stream()),
-                  "sd_ddim_sample_draws")
-            return
-        if self.pin is not None:
-            check(_lib.load().sd_ddim_sample_pin(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
-                                                 self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None, None,
-                                                 self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
-                                                 len(self.coef), self.status.data_ptr(), self.max_mode, *[t.data_ptr() for t in self.pin],
-                                                 _stream()), "sd_ddim_sample_pin")
-            return
-        check(_lib.load().sd_ddim_sample_ex(C.byref(self.packed.struct), _ptr(self.ctx), self.tokens.data_ptr(),
-                                            self.coef.ctypes.data_as(_lib.c_float_p), self.x.data_ptr(), None,
-                                            self.ws.data_ptr(), B, T, 0 if self.ctx is None else self.ctx.shape[1],
-                                            len(self.coef), self.status.data_ptr(), self.max_mode, _stream()),
-              "sd_ddim_sample_ex")
+        _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws)
 
     def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None) -> Tensor:
         """Copies the inputs into the captured buffers, replays, and returns the captured x buffer itself
@@ -477,29 +471,9 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     tr = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if trace else None
     et = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if eps_trace else None
     ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, n_steps), x.device)
-    if draws > 1:
-        pins = [None, None, None]
-        if pin is not None:
-            noise = x_T.clone() if inplace else x_T   # never x itself: the first step overwrites x
-            pins = [pin[0].data_ptr(), noise.data_ptr(), pin[1].data_ptr()]
-        check(lib.sd_ddim_sample_draws(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
-                                       coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
-                                       B, T, Mc, n_steps, _ptr(status), int(max_mode), *pins, draws, _stream()), "sd_ddim_sample_draws")
-        out = (x,) + ((tr,) if trace else ()) + ((et,) if eps_trace else ())
-        return out if len(out) > 1 else x
-    if pin is not None:
-        noise = x_T.clone() if inplace else x_T   # never x itself: the first step overwrites x
-        check(lib.sd_ddim_sample_pin(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
-                                     coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
-                                     B, T, Mc, n_steps, _ptr(status), int(max_mode), pin[0].data_ptr(), noise.data_ptr(), pin[1].data_ptr(),
-                                     _stream()), "sd_ddim_sample_pin")
-        out = (x,) + ((tr,) if trace else ()) + ((et,) if eps_trace else ())
-        return out if len(out) > 1 else x
-    check(lib.sd_ddim_sample_eps(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(),
-                                 coef.ctypes.data_as(_lib.c_float_p), x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(),
-                                 B, T, Mc, n_steps, _ptr(status), int(max_mode), _stream()), "sd_ddim_sample_eps")
-    out = (x,) + ((tr,) if trace else ()) + ((et,) if eps_trace else ())
-    return out if len(out) > 1 else x
+    if pin is not None:   # (known, noise, rows); the noise never x itself: the first step overwrites x
+        pin = (pin[0], x_T.clone() if inplace else x_T, pin[1])
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws)
 
 
 def default_sampler_cap() -> int:

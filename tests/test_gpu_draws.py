@@ -137,29 +137,71 @@ def test_chunk_boundary_of_the_fused_rollout():
     _shared_equals_repeated(CHUNK["chunk65"], 2, 7300)
 
 
-def test_one_draw_through_the_new_entry_point_is_the_old_call():
-    from soccerdiffusion_amd import _lib, ops
+def _counted(call):
+    """Launches of the step-kernel class made by call() (a native entry point through ctypes; its return code is checked)."""
+    from soccerdiffusion_amd import _lib
 
-    d, Mc, T, J, n_steps, mode, _, _, _ = ROUTES["tuned-fused"]
-    setup = Setup.get(d, J, n_steps)
-    x_T, ctx, _ = _inputs(7400, CN, 1, d, Mc, T, J)
     lib = _lib.load()
     ncls = len(_lib.KERNEL_CLASSES)
-    want, _, n_old = _call(setup, ctx, x_T, mode, 1)
-    x = x_T.clone()
-    ws = ops.workspace(lib.sd_workspace_floats(CN, T, Mc, d, L, n_steps), x.device)
     torch.cuda.synchronize()
     lib.sd_profile_enable(1)
     try:
-        _lib.check(lib.sd_ddim_sample_draws(C.byref(setup.packed.struct), ctx.data_ptr(), setup.toks.data_ptr(), setup.coef.ctypes.data_as(_lib.c_float_p),
-                                            x.data_ptr(), None, None, ws.data_ptr(), CN, T, Mc, n_steps, None, mode, None, None, None, 1,
-                                            torch.cuda.current_stream().cuda_stream), "sd_ddim_sample_draws")
+        _lib.check(call(), "native sampler call")
         torch.cuda.synchronize()
     finally:
         lib.sd_profile_enable(0)
     ms, cnt = (C.c_double * ncls)(), (C.c_long * ncls)()
     _lib.check(lib.sd_profile_collect(ms, cnt, ncls), "sd_profile_collect")
-    assert torch.equal(x, want[0]) and int(cnt[_lib.KERNEL_CLASSES.index("traj_step_kernel")]) == n_old == 1
+    return int(cnt[_lib.KERNEL_CLASSES.index("traj_step_kernel")])
+
+
+def test_one_draw_through_the_new_entry_point_is_the_old_call():
+    """ops.ddim_sample and GraphedSampler always go through sd_ddim_sample_draws, so the "old call" side is made here, through ctypes: every
+    older entry point against sd_ddim_sample_draws(draws = 1) and against ops.ddim_sample, bit for bit and launch for launch - unpinned
+    (the fused rollout form: one launch) and pinned (one launch per step)."""
+    from soccerdiffusion_amd import _lib, ops
+
+    d, Mc, T, J, n_steps, mode, _, _, _ = ROUTES["tuned-fused"]
+    assert (d, L, T, J, Mc, CN, n_steps, mode) == (256, 2, 10, 20, 9, 3, 3, 3)
+    setup = Setup.get(d, J, n_steps)
+    x_T, ctx, known = _inputs(7400, CN, 1, d, Mc, T, J)
+    lib = _lib.load()
+    ws = ops.workspace(lib.sd_workspace_floats(CN, T, Mc, d, L, n_steps), x_T.device)
+    head = (C.byref(setup.packed.struct), ctx.data_ptr(), setup.toks.data_ptr(), setup.coef.ctypes.data_as(_lib.c_float_p))
+    shape, st = (CN, T, Mc, n_steps), torch.cuda.current_stream().cuda_stream
+
+    # unpinned
+    want, _, n_ops = _call(setup, ctx, x_T, mode, 1)
+    assert n_ops == 1
+    calls = {
+        "sd_ddim_sample": lambda x: lib.sd_ddim_sample(*head, x, None, ws.data_ptr(), *shape, st),
+        "sd_ddim_sample_ex": lambda x: lib.sd_ddim_sample_ex(*head, x, None, ws.data_ptr(), *shape, None, mode, st),
+        "sd_ddim_sample_eps": lambda x: lib.sd_ddim_sample_eps(*head, x, None, None, ws.data_ptr(), *shape, None, mode, st),
+        "sd_ddim_sample_draws": lambda x: lib.sd_ddim_sample_draws(*head, x, None, None, ws.data_ptr(), *shape, None, mode, None, None, None, 1, st),
+    }
+    for name, fn in calls.items():
+        x = x_T.clone()
+        assert _counted(lambda: fn(x.data_ptr())) == 1, name
+        assert torch.equal(x, want[0]), name
+
+    # pinned
+    rows = torch.tensor([0, 3, 10], dtype=torch.int32, device="cuda")
+    want, _, n_ops = _call(setup, ctx, x_T, mode, 1, pin=(known, rows), eps_trace=True)
+    assert n_ops == n_steps and len(want) == 2
+    pins = (known.data_ptr(), x_T.data_ptr(), rows.data_ptr())
+    calls = {
+        "sd_ddim_sample_pin": lambda x, et: lib.sd_ddim_sample_pin(*head, x, None, et, ws.data_ptr(), *shape, None, mode, *pins, st),
+        "sd_ddim_sample_draws": lambda x, et: lib.sd_ddim_sample_draws(*head, x, None, et, ws.data_ptr(), *shape, None, mode, *pins, 1, st),
+    }
+    for name, fn in calls.items():
+        x, et = x_T.clone(), torch.empty(n_steps, CN, T, J, device="cuda")
+        assert _counted(lambda: fn(x.data_ptr(), et.data_ptr())) == n_steps, name
+        assert torch.equal(x, want[0]) and torch.equal(et, want[1]), name
+    assert torch.equal(want[0][1, :3], known[1, :3]) and torch.equal(want[0][2], known[2])
+
+    # the captured form of the pinned call
+    graphed = ops.GraphedSampler(setup.packed, CN, T, Mc, setup.toks, setup.coef, max_mode=mode, pin=True)
+    assert torch.equal(graphed(ctx, x_T, pin=(known, rows)), want[0])
 
 
 def _mixed_rows(T, B):

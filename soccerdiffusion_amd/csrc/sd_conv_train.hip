@@ -7,11 +7,13 @@
 //   * its backward: the two per-channel reductions (sum g, sum g x_hat; g = the incoming gradient behind the ReLU mask), then
 //     dy = gamma rstd (g - mean g - x_hat mean(g x_hat)), with the abs-max word of dy for the data-gradient convolution;
 //   * the convolution's weight gradient dW[co][ci][tap] = sum over output pixels of dY[pixel][co] X[pixel * stride + tap - pad][ci]: a
-//     "TN" product whose contraction runs over pixels, on the fp16 matrix pipe with block floating point per 32 pixels (as
-//     gemm_tn16_kernel of sd_train.hip: gradients have no a-priori magnitude), fp32 atomics into torch's (Cout, Cin, k, k) layout.
-// The data gradient needs no kernel of its own: it is the forward kernel (sd_conv3x3_bn_act / sd_conv1x1_bn_act with an identity
-// epilogue) on the flipped, transposed weights - for the stride-2 stage entries on dY dilated with zeros (host side:
-// soccerdiffusion_amd/conv_training.py).
+//     "TN" product whose contraction runs over pixels, on the fp16 matrix pipe.  3 x 3 with both abs-max words: the strip-walking
+//     kernel (one scale per tensor, partial tiles per group of steps, a reduction kernel: no atomics, deterministic; stride 2 as four
+//     parity-class launches).  1 x 1, and 3 x 3 without the words: the per-wave kernel (one scale per tensor from the words, else block
+//     floating point per 32 pixels; fp32 atomics into torch's (Cout, Cin, k, k) layout).  The stem: stem_wgrad_kernel, no atomics.
+// The stride-1 data gradient needs no kernel of its own: it is the forward kernel (sd_conv3x3_bn_act / sd_conv1x1_bn_act with an identity
+// epilogue) on the flipped, transposed weights; the stride-2 stage entries run the transposed kernels of sd_conv.hip (sd_convt3x3_s2 by
+// output parity class, sd_convt1x1_s2), no zero-dilated dY (host side: soccerdiffusion_amd/conv_training.py).
 #include "../../include/soccerdiffusion_hip.h"
 #include "sd_common.h"
 #include <stdlib.h>
@@ -99,13 +101,32 @@ __global__ __launch_bounds__(256) void partial_sum_kernel(const float *__restric
     }
 }
 
-// sums of (y - pivot) and (y - pivot)^2 per channel; pivot = the first pixel's value of the channel (keeps the variance formula
-// q / n - (s / n)^2 free of the cancellation a large mean would cause)
+// sums of (y - pivot) and (y - pivot)^2 per channel.  The pivot keeps the variance formula q / n - (s / n)^2 free of the cancellation a large
+// mean would cause; what is left grows like 1 + d^2, d = (pivot - mean) / sigma, on the fp32 roundings of q and s.  ONE pixel as the pivot
+// lies 3 - 4 sigma off on a few of 512 channels (rstd 6 - 14 x, the mean up to 8 x the error of torch's fp32 operator, measured channel
+// by channel: tests/test_gpu_conv_grade.py), so the pivot is the mean of min(npix, 8) pixels spread evenly over the WHOLE tensor, pixel
+// p (npix / P): neighbours in one corner of the first image are correlated (and may lie in the padding's shadow), pixels from eight
+// places of the batch are not.  The same fp32 expression in both kernels: the same bits.
+constexpr int BN_PIVOT = 8;
+template <class V>
+__device__ __forceinline__ V bn_pivot(const float *__restrict__ y, long npix, int C, int c0) {
+    const int P = npix < BN_PIVOT ? (int)npix : BN_PIVOT;
+    const long step = npix / P;   // (P - 1) step < npix
+    V s = *reinterpret_cast<const V *>(y + c0);
+    for (int p = 1; p < P; ++p) s = s + *reinterpret_cast<const V *>(y + p * step * C + c0);
+    return s * (1.0f / (float)P);
+}
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float *__restrict__ y, long npix, int C, float *part) {
+    int pc0 = -1;   // the channel group `pv` belongs to (one per 1024-channel pass of channel_reduce)
+    f32x4 pv = {0.f, 0.f, 0.f, 0.f};
     channel_reduce<f32x4>(
         npix, C, part, [&](long p, int c0) { return *reinterpret_cast<const f32x4 *>(y + p * C + c0); },
         [&](const f32x4 &yv, int c0, f32x4 &s, f32x4 &q) {
-            const f32x4 v = yv - *reinterpret_cast<const f32x4 *>(y + c0);
+            if (c0 != pc0) {
+                pv = bn_pivot<f32x4>(y, npix, C, c0);
+                pc0 = c0;
+            }
+            const f32x4 v = yv - pv;
             s = s + v;
             q = q + v * v;
         });
@@ -115,7 +136,7 @@ __global__ void bn_finalize_kernel(const double *acc, const float *__restrict__ 
                                    float *rstd, float *running_mean, float *running_var) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const double n = (double)npix, s = acc[2 * c] / n, var = fmax(acc[2 * c + 1] / n - s * s, 0.0), m = (double)y[c] + s;
+    const double n = (double)npix, s = acc[2 * c] / n, var = fmax(acc[2 * c + 1] / n - s * s, 0.0), m = (double)bn_pivot<float>(y, npix, C, c) + s;
     mean[c] = (float)m;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {

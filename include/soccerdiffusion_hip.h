@@ -301,6 +301,34 @@ int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *wo
                        int what, int max_mode, void *stream);
 int sd_sampler_eps(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
                    int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, void *stream);
+/* The loop form with a group size: the two calls above with ctx (B / draws, Mc, d), trajectory b reads context b / draws (the draws of a
+ * context are contiguous).  The context is projected, folded and packed once per CONTEXT, exactly as sd_ddim_sample_draws does it, and the
+ * shared-context instantiations of the step kernels read it; the tuned kernels' size limit counts contexts.  n_tok is 1 or B as before; with
+ * n_tok = B trajectory b reads its own step token and only the distinct tokens are folded - the denoiser at K timesteps of the same window
+ * is B = C K trajectories, draws = K, reading C folded contexts.  eps equals sd_sampler_eps on the repeated context bit for bit.
+ * workspace: sd_workspace_floats(B, ...) (the tail of the plane regions stays unused).  draws == 1 or Mc == 0: the calls above, launch for
+ * launch (they are the draws = 1 case of these).  SD_E_BADARG (nothing launched): draws < 1 or B % draws != 0.  SD_E_UNSUPPORTED as above:
+ * the caller expands the context rows and uses the existing path. */
+int sd_sampler_prepare_draws(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
+                             int what, int max_mode, int draws, void *stream);
+int sd_sampler_eps_draws(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
+                         int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, int draws, void *stream);
+
+/* ---- held-out evaluation (csrc/sd_eval.hip; soccerdiffusion_amd/evaluation.py) --------------------------------------------
+ * Both kernels: fp32, contraction off, no atomics, every sum in a fixed order that depends on the shape alone (written out at the top of
+ * sd_eval.hip), so two runs agree bit for bit.
+ *   sd_eval_sqerr_rows: out[r] = (1 / per) sum_i (a[r,i] - b[r,i])^2 for `rows` rows of `per` floats - with per = T J the loss of one
+ *     trajectory.  One workgroup per row.
+ *   sd_eval_trajectory_errors: x (C, G, T, J) samples in the sampler's normalised space, target (C, T, J) the recorded joint commands as the
+ *     data source delivers them (radians in [0, 2 pi)).  Per element y = x std + mean (one rounding per operation, as sd_session_commit),
+ *     d = y - target and, with angular != 0, d -= 2 pi rintf(d / (2 pi)): the angles are stored modulo 2 pi, so an error of 2 pi - 0.01 is
+ *     an error of 0.01.  err (C, G) = mean of d^2 over T J; row_err (C, G, T) or NULL = mean over J; joint_err (C, G, J) or NULL = mean over
+ *     T; best (C) or NULL = argmin over g of err, ties to the lowest index.  One workgroup per context.  1 <= G <= 64, J <= 32, T >= 1.
+ * SD_E_BADARG (nothing launched) outside those limits or with a required pointer NULL. */
+int sd_eval_sqerr_rows(const float *a, const float *b, float *out, long rows, long per, void *stream);
+int sd_eval_trajectory_errors(const float *x, const float *target, const float *mean, const float *stdv, float *err, float *row_err /* or NULL */,
+                              float *joint_err /* or NULL */, int32_t *best /* or NULL */, int C, int G, int T, int J, int angular,
+                              void *stream);
 
 /* ---- image path: ResNet basic-block convolution -------------------------------------------------------
  * y = act(BatchNorm_eval(conv3x3(x, w; stride 1, padding 1)) [+ res]) - torchvision BasicBlock's conv1/bn1/relu and

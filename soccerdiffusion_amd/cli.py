@@ -5,6 +5,7 @@ soccer_diffusion/ml/inference/plot.py:21-135).
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
+    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [-o report.json]   (evaluation.py)
     python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
@@ -15,7 +16,10 @@ the reference's `Result` dataclass) or from a synthetic sine-wave generator (`--
 per step and `sample` shards the rollouts over the ranks; `--ema-decay` keeps an exponential
 moving average of the weights inside the optimizer step (optim.FusedAdamW) and the checkpoint
 gains `ema_model_state_dict` and `ema`, which `--ema` / `--ema-teacher` load instead of the
-last iterate (the reference's ml/preliminary scripts kept and sampled such an average).
+last iterate (the reference's ml/preliminary scripts kept and sampled such an average);
+`train` / `distill --val-fraction F` hold the last (or a random) fraction of the windows out of training and of the normaliser fit,
+evaluate them every `--val-every` epochs (evaluation.evaluate) and record the reports in the checkpoint's `validation` entry, and
+`evaluate` prints that report for any checkpoint as one JSON line.
 """
 
 from __future__ import annotations
@@ -261,7 +265,12 @@ def cmd_train(args) -> int:
     gen = torch.Generator().manual_seed(args.seed + rank)
     source = data_source(args, params, device)
     n_total = source.n
-    norm_idx = torch.randint(0, n_total, (params["num_normalization_samples"],), generator=torch.Generator().manual_seed(args.seed))
+    val = _holdout(args, n_total)
+    if val is None:
+        norm_idx = torch.randint(0, n_total, (params["num_normalization_samples"],), generator=torch.Generator().manual_seed(args.seed))
+    else:   # held-out windows are neither trained on nor seen by the normaliser
+        norm_idx = val.train_idx[torch.randint(0, len(val.train_idx), (params["num_normalization_samples"],),
+                                               generator=torch.Generator().manual_seed(args.seed))]
     from .dataset import fit_normalizer as fit_rows
 
     mean, std = fit_rows(source.batch(norm_idx)["joint_command"].cpu())  # train.py:108-110
@@ -288,7 +297,11 @@ def cmd_train(args) -> int:
     if world > 1:  # ... and rank 0's parameters, moments and buffers are what every rank starts from, whatever happened above
         training.broadcast_parameters(optimizer, model)
     bs = params["batch_size"]
-    shard, steps_per_epoch = shard_plan(n_total, bs, rank, world)
+    if val is None:
+        shard, steps_per_epoch = shard_plan(n_total, bs, rank, world)
+    else:
+        shard, steps_per_epoch = shard_plan(len(val.train_idx), bs, rank, world)
+        shard = val.train_idx[shard]
     lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=params["lr"], total_steps=params["epochs"] * steps_per_epoch)
     scheduler = DDIMScheduler(beta_schedule="squaredcos_cap_v2", clip_sample=False)
     scheduler.config["num_train_timesteps"] = params["train_denoising_timesteps"]
@@ -310,11 +323,14 @@ def cmd_train(args) -> int:
                                            world_size=world, generator=dev_gen)
             if i % 20 == 0 and rank == 0:
                 print(f"Epoch {epoch}, it {i}, Loss: {float(loss):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}", flush=True)
+        if val is not None and rank == 0:   # (the other ranks wait at the collective below)
+            val.run(model, optimizer, source, epoch, params["epochs"])
         training.assert_replicas_equal(optimizer)   # one pair of tiny all-reduces per epoch
         if rank == 0:
             torch.save({"model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model)}, args.output)
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model), **({} if val is None else {"validation": val.entry()})},
+                       args.output)
     if world > 1:
         import torch.distributed as dist
 
@@ -368,7 +384,12 @@ def cmd_distill(args) -> int:
     source = data_source(args, params, device)
     n_total = source.n
     bs = params["batch_size"]
-    shard, steps_per_epoch = shard_plan(n_total, bs, rank, world)
+    val = _holdout(args, n_total, distilled=True)
+    if val is None:
+        shard, steps_per_epoch = shard_plan(n_total, bs, rank, world)
+    else:
+        shard, steps_per_epoch = shard_plan(len(val.train_idx), bs, rank, world)
+        shard = val.train_idx[shard]
     lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=params["lr"], total_steps=params["epochs"] * steps_per_epoch)
     dev_gen = torch.Generator(device=device).manual_seed(args.seed + 1000 * rank)
     n_teacher = params["distill_teacher_inference_steps"]
@@ -395,16 +416,124 @@ def cmd_distill(args) -> int:
             mean_loss += float(loss)
             if i % 20 == 0 and rank == 0:
                 print(f"Epoch {epoch}, it {i}, Loss: {mean_loss / (i + 1):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}", flush=True)
+        if val is not None and rank == 0:
+            val.run(student, optimizer, source, epoch, params["epochs"])
         training.assert_replicas_equal(optimizer)
         if rank == 0:
             torch.save({"model_state_dict": student.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student)}, args.output)
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student), **({} if val is None else {"validation": val.entry()})},
+                       args.output)
     if world > 1:
         import torch.distributed as dist
 
         dist.barrier()
         dist.destroy_process_group()
+    return 0
+
+
+class _Holdout:
+    """The held-out windows of a `train` / `distill --val-fraction` run and the reports on them (the checkpoint's `validation` entry)."""
+
+    def __init__(self, args, n_total: int, distilled: bool):
+        from .evaluation import holdout_split
+
+        self.fraction, self.split, self.seed = args.val_fraction, args.val_split, args.seed
+        self.every, self.draws, self.steps, self.distilled = args.val_every, args.val_draws, args.val_steps, distilled
+        self.train_idx, self.val_idx = holdout_split(n_total, self.fraction, self.seed, self.split)
+        self.history: list = []
+
+    def run(self, model, optimizer, source, epoch: int, epochs: int) -> None:
+        """Every `--val-every` epochs and after the last one: the last iterate and, where the optimizer keeps one, the average.  The model
+        returns to the mode it was in; nothing it trains with (parameters, moments, dropout seeds, generators) is written."""
+        from .evaluation import evaluate
+
+        if (epoch + 1) % self.every and epoch + 1 != epochs:
+            return
+        was_training = model.training
+        model.eval()
+        try:
+            kw = dict(steps=self.steps, draws=self.draws, seed=self.seed, distilled=self.distilled)
+            entry = {"epoch": epoch, "last": evaluate(model, source, self.val_idx, **kw)}
+            if optimizer.flat_ema is not None:
+                with optimizer.ema_weights():
+                    entry["ema"] = evaluate(model, source, self.val_idx, **kw)
+        finally:
+            model.train(was_training)
+        self.history.append(entry)
+        line = ", ".join(f"{name}: " + " ".join(f"{k} {r[k]:.5f}" for k in ("val_loss", "rmse_first_draw", "rmse_medoid") if r[k] is not None)
+                         for name, r in entry.items() if name != "epoch")
+        print(f"Epoch {epoch}, validation on {len(self.val_idx)} windows - {line}", flush=True)
+
+    def entry(self) -> dict:
+        return {"fraction": self.fraction, "split": self.split, "seed": self.seed, "n_val": len(self.val_idx), "history": self.history}
+
+
+def _holdout(args, n_total: int, distilled: bool = False) -> Optional[_Holdout]:
+    return None if args.val_fraction is None else _Holdout(args, n_total, distilled)
+
+
+def _timesteps(text: str) -> list:
+    try:
+        return [int(v) for v in text.split(",")]
+    except ValueError:
+        raise SystemExit(f"--timesteps takes integers a,b,..., got {text!r}") from None
+
+
+def validate_evaluation_args(args) -> None:
+    """The arguments of `evaluate` and of the --val-* flags, checked before anything touches the GPU."""
+    from . import evaluation
+
+    try:
+        if getattr(args, "val_fraction", None) is not None:
+            evaluation.check_fraction(args.val_fraction)
+        for name in ("val_draws", "draws") if args.command == "evaluate" else ("val_draws",):   # (sample / rollout --draws: checked by the parser)
+            if getattr(args, name, None) is not None:
+                evaluation.check_draws(getattr(args, name))
+        for name in ("val_every", "val_steps", "steps"):
+            if getattr(args, name, None) is not None and getattr(args, name) < 1:
+                raise ValueError(f"--{name.replace('_', '-')} must be positive, got {getattr(args, name)}")
+        if getattr(args, "timesteps", None) is not None:
+            evaluation.check_timesteps(_timesteps(args.timesteps))
+        if args.command == "evaluate":
+            evaluation.default_timesteps(args.grid)
+            if args.all and args.val_fraction is not None:
+                raise ValueError("--all evaluates every window: not with --val-fraction")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
+def cmd_evaluate(args) -> int:
+    """The report of evaluation.evaluate on the held-out windows of a data source, as one JSON line.  A checkpoint written by
+    `train --val-fraction` carries the fraction, split and seed of its split: they are the defaults, so the same windows are used."""
+    import json
+
+    from .evaluation import evaluate, holdout_split
+
+    device = torch.device("cuda", _dist_env()[2])
+    torch.cuda.set_device(device)
+    checkpoint = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
+    params = checkpoint["hyperparams"]
+    recorded = checkpoint.get("validation", {})
+    if args.seed is None:
+        args.seed = recorded.get("seed", 0)
+    fraction = args.val_fraction if args.val_fraction is not None else recorded.get("fraction")
+    split = args.val_split or recorded.get("split", "tail")
+    if not args.all and fraction is None:
+        raise SystemExit("evaluate: give --val-fraction F, or --all for every window (the checkpoint records no split)")
+    model = build_model(params).to(device)
+    model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
+    model.eval()
+    source = data_source(args, params, device)
+    idx = torch.arange(source.n) if args.all else holdout_split(source.n, fraction, args.seed, split)[1]
+    report = evaluate(model, source, idx, steps=args.steps, draws=args.draws, grid=args.grid, seed=args.seed,
+                      max_mode=3 if args.max_mode is None else args.max_mode, timesteps=_timesteps(args.timesteps) if args.timesteps else None,
+                      distilled=bool(params.get("distilled_decoder", False)))
+    line = json.dumps(report)
+    print(line)
+    if args.output:
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
     return 0
 
 
@@ -613,13 +742,34 @@ def build_parser() -> argparse.ArgumentParser:
                        "weights with decay D in (0, 1), updated inside the optimizer step; the checkpoint gains ema_model_state_dict and ema")
         p.add_argument("--no-ema-warmup", action="store_true", help="weight 1 - D from the first update on, instead of "
                        "1 - min(D, (1 + t) / (10 + t)) after t updates")
-    for p in (tr, sa, di):
+    for p in (tr, di):
+        p.add_argument("--val-fraction", type=float, default=None, metavar="F", help="hold this fraction of the windows out of training and of the "
+                       "normaliser fit and evaluate them (evaluation.evaluate); the checkpoint gains a validation entry")
+        p.add_argument("--val-split", type=str, default="tail", choices=("tail", "random"), help="which windows: the last block (default) or a seeded "
+                       "random subset")
+        p.add_argument("--val-every", type=int, default=1, metavar="E", help="evaluate every E epochs (and after the last one)")
+        p.add_argument("--val-draws", type=int, default=1, metavar="G", help="draws per held-out window (1 .. 64)")
+        p.add_argument("--val-steps", type=int, default=30, metavar="N", help="DDIM steps of the held-out samples")
+    ev = sub.add_parser("evaluate", help="held-out validation loss and sampled-trajectory errors of a checkpoint, as one JSON line")
+    ev.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
+    ev.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
+    ev.add_argument("--draws", type=int, default=1, metavar="G", help="draws per window (1 .. 64): rmse of the first, the medoid and the best")
+    ev.add_argument("--grid", type=int, default=8, metavar="K", help="timesteps of the loss grid, t_k = (2k + 1) 1000 // (2K)")
+    ev.add_argument("--timesteps", type=str, default=None, metavar="a,b,...", help="the loss grid's timesteps (0 .. 999) instead of --grid")
+    ev.add_argument("--val-fraction", type=float, default=None, metavar="F", help="evaluate the held-out fraction F of the data source "
+                    "(default: the checkpoint's validation entry)")
+    ev.add_argument("--val-split", type=str, default=None, choices=("tail", "random"), help="default: the checkpoint's, else tail")
+    ev.add_argument("--all", action="store_true", help="evaluate every window of the data source")
+    ev.add_argument("--ema", action="store_true", help="evaluate the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
+    ev.add_argument("--max-mode", type=int, default=None, choices=(0, 1, 2, 3, 4), help="highest sampler mode of the sampled trajectories (default 3)")
+    ev.add_argument("--output", "-o", type=str, default=None, help="also write the report to this file")
+    for p in (tr, sa, di, ev):
         p.add_argument("--data", type=str, default=None, help="tensor file with joint_command (+ context keys)")
         p.add_argument("--db", type=str, default=None, help="SQLite database in the reference's schema (SOCCER_DIFFUSION_DB_PATH of the reference)")
         p.add_argument("--synthetic", type=int, default=None, metavar="N", help="train / sample on N synthetic sine-wave samples")
         p.add_argument("--image-size", type=str, default=None, metavar="HxW", help="--synthetic only: frame size when it is not the "
                        "square image_resolution of the config (BASELINE's image-conditioned case uses 480x640)")
-        p.add_argument("--seed", type=int, default=0)
+        p.add_argument("--seed", type=int, default=None if p is ev else 0)
     ro = sub.add_parser("rollout", help="drive a closed-loop policy session (the tick of the reference's ros.py) from a synthetic sensor stream")
     ro.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
     ro.add_argument("--synthetic", type=int, default=None, metavar="N", help="number of robots stepping in lockstep on a synthetic sensor stream")
@@ -645,12 +795,13 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv: Optional[list] = None) -> int:
     logging.basicConfig(level=os.environ.get("LOGLEVEL", "INFO"))
     args = build_parser().parse_args(argv)
+    validate_evaluation_args(args)
     for flag in ("ema", "ema_teacher"):   # asked for EMA weights the checkpoint does not hold: say so before anything touches the GPU
         if getattr(args, flag, False):
             ema_model_state(torch.load(args.checkpoint, map_location="cpu", weights_only=True), "--" + flag.replace("_", "-"), args.checkpoint)
     if not torch.cuda.is_available():
         raise SystemExit("soccerdiffusion_amd needs an MI355X (no CPU fallback)")
-    return {"train": cmd_train, "sample": cmd_sample, "distill": cmd_distill, "rollout": cmd_rollout}[args.command](args)
+    return {"train": cmd_train, "sample": cmd_sample, "distill": cmd_distill, "rollout": cmd_rollout, "evaluate": cmd_evaluate}[args.command](args)
 
 
 if __name__ == "__main__":

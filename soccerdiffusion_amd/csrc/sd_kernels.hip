@@ -2964,7 +2964,7 @@ struct TrajCall {
     }
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
     // pin: the pinned instantiations (the caller's plan is a three-product one)
-    // (draws > 1: the shared-context instantiations; either family refuses them for per_traj)
+    // (draws > 1: the shared-context instantiations; with per_traj the context index b / draws and the step block step_map[b] are separate)
     StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin) const {
         return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws};
     }
@@ -3191,46 +3191,61 @@ extern "C" int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, in
 }
 
 // ---- the denoiser evaluated step by step on the trajectory kernels (the reference's own loop form) --------------------------
-static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int max_mode, const char *who,
-                             Scratch *s, SamplerPlan *plan) {
+// draws: trajectories per context (sd_sampler_*_draws; 1: every trajectory its own).  Validated here, before anything is launched.
+static int sampler_eval_args(const sd_denoiser_weights *w, float *workspace, int B, int T, int Mc, int n_tok, int max_mode, int *draws,
+                             const char *who, Scratch *s, SamplerPlan *plan) {
     int rc = check_denoiser(w);
     if (rc) return rc;
     if (!workspace || B <= 0 || T <= 0 || Mc < 0 || (n_tok != 1 && n_tok != B)) return fail(SD_E_BADARG, who);
+    if (*draws < 1 || B % *draws) return fail(SD_E_BADARG, who);
     if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, who);
     if (T > w->T_max) return fail(SD_E_TOOBIG, who);
+    if (Mc == 0) *draws = 1;   // no context rows: nothing to share
     *s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_tok, B);
-    *plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode < 0 ? 3 : max_mode, CALL_LOOP);
+    *plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode < 0 ? 3 : max_mode, CALL_LOOP, *draws);
     return plan->traj() ? 0 : SD_E_UNSUPPORTED;
 }
 
-extern "C" int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
-                                  int what, int max_mode, void *stream) {
+// ctx (B / draws, Mc, d): projected, folded and packed once per context, as sd_ddim_sample_draws does it
+extern "C" int sd_sampler_prepare_draws(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
+                                        int what, int max_mode, int draws, void *stream) {
     Scratch s;
     SamplerPlan plan;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_prepare: bad argument", &s, &plan);
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, &draws, "sd_sampler_prepare: bad argument", &s, &plan);
     if (rc) return rc;
     if ((what & ~(SD_PREPARE_WEIGHTS | SD_PREPARE_CONTEXT)) || (Mc > 0 && (what & SD_PREPARE_CONTEXT) && !ctx))
         return fail(SD_E_BADARG, "sd_sampler_prepare: bad argument");
-    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream, draws};
     if ((what & SD_PREPARE_WEIGHTS) && (rc = c.prepare_weights())) return rc;
     if ((what & SD_PREPARE_CONTEXT) && (rc = c.prepare_ctx(ctx))) return rc;
     return 0;
 }
 
-extern "C" int sd_sampler_eps(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
-                              int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, void *stream) {
+extern "C" int sd_sampler_prepare(const sd_denoiser_weights *w, const float *ctx, float *workspace, int B, int T, int Mc, int n_tok,
+                                  int what, int max_mode, void *stream) {
+    return sd_sampler_prepare_draws(w, ctx, workspace, B, T, Mc, n_tok, what, max_mode, 1, stream);
+}
+
+// trajectory b reads the planes of context b / draws and - n_tok = B - its own step token (the distinct ones folded once: step_map)
+extern "C" int sd_sampler_eps_draws(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
+                                    int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, int draws, void *stream) {
     Scratch s;
     SamplerPlan plan;
-    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, "sd_sampler_eps: bad argument", &s, &plan);
+    int rc = sampler_eval_args(w, workspace, B, T, Mc, n_tok, max_mode, &draws, "sd_sampler_eps: bad argument", &s, &plan);
     if (rc) return rc;
     if (!step_tokens || !x || !eps) return fail(SD_E_BADARG, "sd_sampler_eps: null pointer");
     // (the tuned family at max_mode 4 needs the word whichever instantiation runs: the wide one included)
     if (max_mode == 4 && plan.route != SD_ROUTE_TRAJ_GENERIC && !status) return fail(SD_E_BADARG, "sd_sampler_eps: max_mode 4 needs a status word (SD_STATUS_SHARP_LOGITS)");
-    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream};
+    const TrajCall c{plan, w, s, B, T, Mc, n_tok, (hipStream_t)stream, draws};
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
     if ((rc = c.prepare_steps(step_tokens, n_tok > 1))) return rc;
     // x is only read (no DDIM coefficients: no update)
     return c.step(const_cast<float *>(x), eps, 0, nullptr, n_tok > 1, status);
+}
+
+extern "C" int sd_sampler_eps(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
+                              int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, void *stream) {
+    return sd_sampler_eps_draws(w, step_tokens, x, eps, workspace, B, T, Mc, n_tok, status, max_mode, 1, stream);
 }
 
 // ======================================================================================

@@ -337,8 +337,9 @@ static tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s
     return a;
 }
 
-// B a multiple of draws; more than one draw per context exists for rollouts (one step token per DDIM step) only
-static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 && r.B % r.draws == 0 && !(r.draws > 1 && r.per_traj); }
+// B a multiple of draws.  The step kernels index the context (b / draws) and the step block (per_traj: step_map[b]) separately, so a group
+// of draws may carry per-trajectory step tokens (sd_sampler_eps_draws); the rollout kernel has no per-trajectory tokens at all.
+static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 && r.B % r.draws == 0; }
 
 // one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
 // as a runtime option
@@ -346,7 +347,7 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, h
     const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
     if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
-    if (!traj_groups_ok(r)) return fail(SD_E_BADARG, "traj_step_draws_kernel: B must be a multiple of draws >= 1 (per-trajectory step tokens: draws = 1)");
+    if (!traj_groups_ok(r)) return fail(SD_E_BADARG, "traj_step_draws_kernel: B must be a multiple of draws >= 1");
     if (r.pin && (!r.coef || variant == 0)) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
     const tj::StepArgs a = traj_step_args(w, s, r, r.coef, nkt);
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][variant][ntt]

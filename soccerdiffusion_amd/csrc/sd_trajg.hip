@@ -1134,7 +1134,7 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
 int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipStream_t st, const int *map) {
     const int d = w->d, L = w->L, T = r.T;
     const GScratch s = gcarve(gws, r.B, r.Mc, d, L, r.n_tok);
-    if (r.draws < 1 || r.B % r.draws || (r.draws > 1 && r.per_traj)) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
+    if (r.draws < 1 || r.B % r.draws) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
     const int ntt = (T + 15) / 16;
     if (ntt < 1 || ntt > (d == 512 ? 3 : 7)) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
     if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");

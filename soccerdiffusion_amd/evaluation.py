@@ -1,0 +1,165 @@
+"""Held-out evaluation: what a checkpoint, a step count, a sampler mode or a number of draws costs or buys on windows the model has not
+seen.  The reference offers a picture per sample (soccer_diffusion/ml/inference/plot.py); this is the number.
+
+    train_idx, val_idx = holdout_split(source.n, 0.1, seed)
+    report = evaluate(model.eval(), source, val_idx, steps=30, draws=8, grid=8)
+
+Two measurements per held-out window, both on the context encoded once:
+  the training loss on a grid of K timesteps (``ops.noise_loss_grid``: one denoiser evaluation of C K trajectories that share C folded
+  contexts and read K distinct step tokens), and
+  the error of G sampled trajectories against the recorded one, in radians and modulo 2 pi (``ops.trajectory_errors``), for the first draw,
+  for the medoid of the draws - what ``PolicySession`` commits - and for the best draw, which needs the answer and is a diagnostic only.
+All randomness comes from one device generator seeded from ``seed`` alone, so two checkpoints are judged on the same draws and neither the
+global generator nor a session's or a training run's is touched.  The split is by window; splitting by recording is out of scope."""
+
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence
+
+import torch
+
+NUM_TRAIN_TIMESTEPS = 1000
+SPLITS = ("tail", "random")
+MAX_DRAWS = 64
+CONTEXT_KEYS = ("joint_command_history", "rotation", "joint_state", "image_data", "game_state")
+
+
+def holdout_split(n: int, fraction: float, seed: int, split: str = "tail"):
+    """``(train_idx, val_idx)``: sorted, disjoint int64 index tensors whose union is ``range(n)``; n_val = min(n - 1, max(1, round(n f))).
+    ``tail`` holds out the last n_val indices - neighbouring windows of a recording overlap in time, so a contiguous block leaks only at
+    its edge; ``random`` holds out the first n_val entries of ``torch.randperm(n)`` under a generator seeded with ``seed``."""
+    check_fraction(fraction)
+    if split not in SPLITS:
+        raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 2:
+        raise ValueError(f"holdout_split needs at least 2 windows, got {n!r}")
+    n_val = min(n - 1, max(1, int(round(n * fraction))))
+    if split == "tail":
+        return torch.arange(n - n_val), torch.arange(n - n_val, n)
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+    return perm[n_val:].sort().values, perm[:n_val].sort().values
+
+
+def check_fraction(fraction) -> float:
+    if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not 0.0 < float(fraction) < 1.0:
+        raise ValueError(f"the held-out fraction must lie in the open interval (0, 1), got {fraction!r}")
+    return float(fraction)
+
+
+def check_draws(draws) -> int:
+    if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= MAX_DRAWS:
+        raise ValueError(f"draws must be an int in [1, {MAX_DRAWS}], got {draws!r}")
+    return draws
+
+
+def default_timesteps(K: int) -> list:
+    """The midpoints of K equal parts of the training range: t_k = (2 k + 1) 1000 // (2 K)."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= NUM_TRAIN_TIMESTEPS:
+        raise ValueError(f"the loss grid takes 1 .. {NUM_TRAIN_TIMESTEPS} timesteps, got {K!r}")
+    return [(2 * k + 1) * NUM_TRAIN_TIMESTEPS // (2 * K) for k in range(K)]
+
+
+def check_timesteps(timesteps: Sequence[int]) -> list:
+    ts = list(timesteps)
+    if not ts or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < NUM_TRAIN_TIMESTEPS for t in ts):
+        raise ValueError(f"grid timesteps must be ints in 0 .. {NUM_TRAIN_TIMESTEPS - 1}, got {ts!r}")
+    return ts
+
+
+def _f64(t) -> torch.Tensor:
+    return torch.as_tensor(t).detach().to("cpu", torch.float64)
+
+
+def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool) -> dict:
+    """The report from the per-batch marginals, in fp64 on the host.  A part holds, for its C windows: ``err`` (C, G), ``row_err`` (C, G, T),
+    ``joint_err`` (C, G, J) (mean squared errors in radians^2: ``ops.trajectory_errors``), ``best`` (C,) and ``medoid`` (C,) draw indices,
+    ``spread`` (C, G) the mean squared distance of every draw to the medoid, and ``loss`` (C, K) or None (a distilled decoder predicts no
+    noise).  Every window weighs the same, whichever batch it came in."""
+    err = torch.cat([_f64(p["err"]) for p in parts])
+    row = torch.cat([_f64(p["row_err"]) for p in parts])
+    joint = torch.cat([_f64(p["joint_err"]) for p in parts])
+    best = torch.cat([torch.as_tensor(p["best"]).to("cpu", torch.int64) for p in parts])
+    med = torch.cat([torch.as_tensor(p["medoid"]).to("cpu", torch.int64) for p in parts])
+    spread = torch.cat([_f64(p["spread"]) for p in parts])
+    n = err.shape[0]
+    at = torch.arange(n)
+    report = {"n_windows": int(n), "val_loss": None, "val_loss_by_t": None}
+    if all(p.get("loss") is not None for p in parts):
+        loss = torch.cat([_f64(p["loss"]) for p in parts])
+        by_t = loss.mean(0)
+        report["val_loss"] = float(by_t.mean())
+        report["val_loss_by_t"] = [[int(t), float(v)] for t, v in zip(timesteps, by_t)]
+    report.update(
+        rmse_first_draw=math.sqrt(float(err[:, 0].mean())),
+        rmse_medoid=math.sqrt(float(err[at, med].mean())),
+        rmse_best_of_G=math.sqrt(float(err[at, best].mean())),
+        rmse_by_row=[math.sqrt(float(v)) for v in row[at, med].mean(0)],
+        rmse_by_joint=[math.sqrt(float(v)) for v in joint[at, med].mean(0)],
+        spread=math.sqrt(float(spread.mean())),
+        steps=int(steps), draws=int(draws), max_mode=int(max_mode), angular=bool(angular))
+    return report
+
+
+def _has_context(model) -> bool:
+    return any(e is not None for e in (model.action_history_encoder, model.imu_encoder, model.joint_states_encoder, model.image_sequence_encoder,
+                                       model.game_state_encoder))
+
+
+@torch.no_grad()
+def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int = 8, batch: int = 64, seed: int = 0, max_mode: int = 3,
+             angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None) -> dict:
+    """The report (a plain dict of Python floats, ints and lists) of ``model`` on the windows ``idx`` of ``source`` (``cli.DataSource``), in
+    batches of ``batch`` windows from ``source.batch``.  The model must be in ``eval()``.  Per batch: the context is encoded once; the loss
+    grid runs at ``timesteps`` (default ``default_timesteps(grid)``); ``draws`` = G trajectories per window are sampled with ``steps`` DDIM
+    steps (``model.sample(draws=G)``); ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
+    student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None.
+    A model without context encoders (decoder pretraining) gets ten random context rows per window from the same generator.
+    ``keep``: a list that receives, per batch, the tensors the marginals were computed from (tests).
+    rmse_* are in radians; ``rmse_by_row`` / ``rmse_by_joint`` refer to the medoid draw; ``spread`` is the root mean squared distance, in
+    radians, of the G draws to their medoid."""
+    from . import ops
+
+    if model.training:
+        raise RuntimeError("evaluate: the model must be in eval() (dropout would be live)")
+    G = check_draws(draws)
+    ts = check_timesteps(timesteps) if timesteps is not None else default_timesteps(grid)
+    if steps < 1 or batch < 1:
+        raise ValueError("evaluate: steps and batch must be positive")
+    idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+    if idx.numel() == 0:
+        raise ValueError("evaluate: no windows to evaluate")
+    device = model.mean.device
+    gen = torch.Generator(device=device).manual_seed(int(seed))
+    t_dev = torch.tensor(ts, dtype=torch.int64, device=device)
+    acp = ops.alphas_cumprod().to(device)
+    K, d = len(ts), model.hidden_dim
+    parts = []
+    for at in range(0, idx.numel(), batch):
+        data = source.batch(idx[at : at + batch])
+        target = data["joint_command"].to(torch.float32).contiguous()
+        Cn, T, J = target.shape
+        if _has_context(model):
+            ctx = model.encode_input_data({k: data[k].contiguous() for k in CONTEXT_KEYS if k in data})
+        else:
+            ctx = [torch.randn(Cn, 10, d, device=device, generator=gen)]
+        part = {"loss": None}
+        if not distilled:
+            noise = torch.randn(Cn * K, T, J, device=device, generator=gen)
+            x0n = ops.normalize(target, model.mean, model.std)
+            part["loss"], eps = ops.noise_loss_grid(model, ctx, x0n, noise, t_dev, acp=acp, return_eps=True)
+        x_T = torch.randn(Cn * G, T, J, device=device, generator=gen)
+        if distilled:
+            x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
+        else:
+            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G)
+        x = x.contiguous()
+        part["medoid"], chosen = ops.select_medoid(x, G)
+        part["err"], part["row_err"], part["joint_err"], part["best"] = ops.trajectory_errors(x, target, model.mean, model.std, draws=G, angular=angular)
+        # the distance of every draw to the medoid, in radians: the same kernel against the denormalised medoid, nothing to wrap
+        part["spread"] = ops.trajectory_errors(x, ops.normalize(chosen, model.mean, model.std, inverse=True), model.mean, model.std, draws=G,
+                                               angular=False)[0]
+        if keep is not None:
+            keep.append({"x": x, "target": target, "medoid_x": chosen, **({} if distilled else {"eps": eps, "noise": noise}), **part})
+        parts.append({k: (None if v is None else v.cpu()) for k, v in part.items()})
+    return assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular)

@@ -92,25 +92,32 @@ class End2EndDiffusionTransformer(nn.Module):
         return self.forward_with_context(self.encode_input_data(input_data), noisy_action_predictions, step)
 
     def forward_with_context(self, context: Sequence[torch.Tensor], noisy_action_predictions: torch.Tensor,
-                             step: torch.Tensor) -> torch.Tensor:
+                             step: torch.Tensor, draws: int = 1) -> torch.Tensor:
         """Predicted noise for x_t given precomputed context tokens; the step token is the
-        LAST memory row (model.py:176).  ``step`` is int64 or float, shape (B,) (or (1,) at B=1)."""
+        LAST memory row (model.py:176).  ``step`` is int64 or float, shape (B,) (or (1,) at B=1).
+        ``draws`` = G > 1 (not in the reference): the context tensors hold C rows, ``x`` C * G trajectories, trajectory b reads context
+        b // G.  On the trajectory kernels the context is folded once per row (``ops.LoopSampler(draws=G)``); elsewhere the rows are
+        expanded and the call is the one with ``draws`` = 1 - the same result, only not shared."""
         x = noisy_action_predictions
         B = x.shape[0]
+        if draws != 1:
+            ops._draws_req(draws, B, context[0].shape[0] if len(context) else None)
         if step.dim() == 0:
             step = step.reshape(1)
         if step.shape[0] != B and step.shape[0] != 1:
             raise RuntimeError(f"step has {step.shape[0]} entries for a batch of {B}")  # torch.cat would fail too
         step = step.to(x.device)
-        eps = self._loop_form_eps(context, x, step)
+        eps = self._loop_form_eps(context, x, step, draws)
         if eps is not None:
             return eps
+        if draws != 1:
+            return self.forward_with_context([c.repeat_interleave(draws, 0) for c in context], x, step)
         if step.shape[0] != B:
             step = step.expand(B)
         memory = self._assemble_memory(context, step, B, x.device)
         return self.diffusion_action_generator(x, memory)
 
-    def _loop_form_eps(self, context, x: torch.Tensor, step: torch.Tensor) -> Optional[torch.Tensor]:
+    def _loop_form_eps(self, context, x: torch.Tensor, step: torch.Tensor, draws: int = 1) -> Optional[torch.Tensor]:
         """Inference calls (no tape, no live dropout) on shapes the trajectory kernels take run ``ops.LoopSampler``: the reference's
         loops call this method once per DDIM step with the same context (plot.py:122-131, distill.py:179-189, ros.py:301-310), so the
         weights' split planes and the context's folded K / V are prepared on the first call and reused by the following ones.
@@ -124,20 +131,20 @@ class End2EndDiffusionTransformer(nn.Module):
         if torch.is_grad_enabled() and (x.requires_grad or any(c.requires_grad for c in context)
                                         or any(p.requires_grad for p in dag.parameters()) or self.step_encoding.token.requires_grad):
             return None
-        if any((not c.is_cuda) or c.dtype != torch.float32 or c.dim() != 3 or c.shape[0] != x.shape[0] for c in context):
+        if any((not c.is_cuda) or c.dtype != torch.float32 or c.dim() != 3 or c.shape[0] * draws != x.shape[0] for c in context):
             return None
         B, T, _ = x.shape
         Mc = sum(int(c.shape[1]) for c in context)
         n_tok = 1 if step.shape[0] == 1 else B
         packed = dag.packed()
         cap = min(ops.sampler_cap(packed), 3)   # (mode 4 needs its status word read back: a host synchronisation per call)
-        key = (B, T, Mc, n_tok, x.device, cap)
+        key = (B, T, Mc, n_tok, x.device, cap) if draws == 1 else (B, T, Mc, n_tok, x.device, cap, draws)
         cache = _model_cache(self, "loop")
         ls = cache.get(key)
         if ls is None:
             if len(cache) >= 4:
                 cache.clear()   # a prepared workspace is pinned memory: a handful of shapes at a time
-            ls = cache[key] = ops.LoopSampler(packed, B, T, Mc, n_tok, x.device, max_mode=cap)
+            ls = cache[key] = ops.LoopSampler(packed, B, T, Mc, n_tok, x.device, max_mode=cap, draws=draws)
         if not ls.supported:
             return None
         if step.dtype not in (torch.int64, torch.float32):

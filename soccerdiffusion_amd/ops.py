@@ -572,13 +572,18 @@ class LoopSampler:
     weight planes, the context's K / V folded with Wq / Woc - is prepared into a workspace this object owns and reused until the
     weights (``weights_key``) or the context tensors (identity and version counters; held here so that their addresses cannot be
     recycled under the cache) change; a context without version counters (inference tensors) is prepared on every call.  ``supported``
-    is False where the shape does not take these kernels."""
+    is False where the shape does not take these kernels.
+    ``draws`` = G > 1: the context tensors hold C = B / G rows and trajectory b reads context b // G (``sd_sampler_prepare_draws`` /
+    ``sd_sampler_eps_draws``): folded once per context, bit for bit the result on ``ctx.repeat_interleave(G, 0)``.  With ``n_tok`` = B
+    every trajectory still reads its own step token - the denoiser at G timesteps of the same window."""
 
-    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, n_tok: int, device, max_mode: int = 3):
+    def __init__(self, packed: _Packed, B: int, T: int, Mc: int, n_tok: int, device, max_mode: int = 3, draws: int = 1):
         lib = _lib.load()
+        self.draws = _draws_req(draws, B, None)
         self.shape = (B, T, Mc, n_tok)
         self.max_mode = int(max_mode)
-        self.supported = _lib.sampler_route(packed.d, packed.heads, T, Mc, packed.J, packed.L, B, self.max_mode).startswith("TRAJ_")
+        self.supported = _lib.sampler_route_draws(packed.d, packed.heads, T, Mc, packed.J, packed.L, B, self.draws if Mc > 0 else 1,
+                                                  self.max_mode).startswith("TRAJ_")
         self.ws = (torch.empty(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, n_tok), dtype=torch.float32, device=device)
                    if self.supported else None)
         self.status = torch.zeros(1, dtype=torch.int32, device=device) if self.supported and self.max_mode == 4 else None
@@ -606,21 +611,88 @@ class LoopSampler:
             if Mc > 0:
                 ctx = (context[0] if len(context) == 1 else torch.cat(list(context), dim=1)).contiguous()
                 _req(ctx, "context")
-            rc = lib.sd_sampler_prepare(C.byref(packed.struct), _ptr(ctx), self.ws.data_ptr(), B, T, Mc, n_tok, what, self.max_mode, _stream())
+                if ctx.shape[0] * self.draws != B:
+                    raise ValueError(f"context shape mismatch: {ctx.shape[0]} contexts x {self.draws} draws != {B} trajectories")
+            rc = lib.sd_sampler_prepare_draws(C.byref(packed.struct), _ptr(ctx), self.ws.data_ptr(), B, T, Mc, n_tok, what, self.max_mode, self.draws,
+                                              _stream())
             if rc == E_UNSUPPORTED:
                 self.supported = False
                 return None
-            check(rc, "sd_sampler_prepare")
+            check(rc, "sd_sampler_prepare_draws")
             self.weights_key, self.context, self.versions = weights_key, list(context), version_key(*context)
             self.prepares += 1
         eps = torch.empty_like(x)
-        rc = lib.sd_sampler_eps(C.byref(packed.struct), tokens.data_ptr(), x.data_ptr(), eps.data_ptr(), self.ws.data_ptr(), B, T, Mc, n_tok,
-                                _ptr(self.status), self.max_mode, _stream())
+        rc = lib.sd_sampler_eps_draws(C.byref(packed.struct), tokens.data_ptr(), x.data_ptr(), eps.data_ptr(), self.ws.data_ptr(), B, T, Mc, n_tok,
+                                      _ptr(self.status), self.max_mode, self.draws, _stream())
         if rc == E_UNSUPPORTED:
             self.supported = False
             return None
-        check(rc, "sd_sampler_eps")
+        check(rc, "sd_sampler_eps_draws")
         return eps
+
+
+def sqerr_rows(a: Tensor, b: Tensor) -> Tensor:
+    """(rows,) = mean over everything behind the first dimension of (a - b)^2 (``sd_eval_sqerr_rows``: fp32, fixed summation order)."""
+    _req(a, "a"); _req(b, "b")
+    if a.shape != b.shape or a.dim() < 1 or a.numel() == 0 or a.device != b.device:
+        raise ValueError(f"sqerr_rows: expected two equal non-empty shapes on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    rows = a.shape[0]
+    out = torch.empty(rows, dtype=torch.float32, device=a.device)
+    check(_lib.load().sd_eval_sqerr_rows(a.data_ptr(), b.data_ptr(), out.data_ptr(), rows, a.numel() // rows, _stream()), "sd_eval_sqerr_rows")
+    return out
+
+
+def trajectory_errors(x: Tensor, target: Tensor, mean: Tensor, std: Tensor, draws: int = 1, angular: bool = True):
+    """Errors of sampled trajectories against the recorded ones (``sd_eval_trajectory_errors``, one launch).  ``x`` (C * draws, T, J) or
+    (C, draws, T, J) in the sampler's normalised space, ``target`` (C, T, J) the joint commands as the data source delivers them (radians in
+    [0, 2 pi)).  d = (x std + mean) - target, with ``angular`` reduced modulo 2 pi into [-pi, pi].  Returns ``(err, row_err, joint_err, best)``:
+    the mean of d^2 over (T, J) as (C, draws), over J as (C, draws, T), over T as (C, draws, J), and best (C,) int32 = argmin over the draws
+    of err (ties to the lowest index)."""
+    if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= 64:
+        raise ValueError(f"trajectory_errors: draws must be an int in [1, 64], got {draws!r}")
+    _req(x, "x"); _req(target, "target"); _req(mean, "mean"); _req(std, "std")
+    if target.dim() != 3 or target.shape[0] == 0:
+        raise ValueError(f"trajectory_errors: target must be (C, T, J), got {tuple(target.shape)}")
+    Cn, T, J = target.shape
+    if tuple(x.shape) not in ((Cn * draws, T, J), (Cn, draws, T, J)):
+        raise ValueError(f"trajectory_errors: expected x ({Cn} * {draws}, {T}, {J}), got {tuple(x.shape)}")
+    if tuple(mean.shape) != (J,) or tuple(std.shape) != (J,) or not 1 <= J <= 32:
+        raise ValueError(f"trajectory_errors: mean and std must be ({J},) with J <= 32, got {tuple(mean.shape)} and {tuple(std.shape)}")
+    dev = x.device
+    if any(t.device != dev for t in (target, mean, std)):
+        raise ValueError("trajectory_errors: x, target, mean and std must be on one device")
+    err = torch.empty(Cn, draws, dtype=torch.float32, device=dev)
+    row_err = torch.empty(Cn, draws, T, dtype=torch.float32, device=dev)
+    joint_err = torch.empty(Cn, draws, J, dtype=torch.float32, device=dev)
+    best = torch.empty(Cn, dtype=torch.int32, device=dev)
+    check(_lib.load().sd_eval_trajectory_errors(x.data_ptr(), target.data_ptr(), mean.data_ptr(), std.data_ptr(), err.data_ptr(), row_err.data_ptr(),
+                                                joint_err.data_ptr(), best.data_ptr(), Cn, draws, T, J, int(bool(angular)), _stream()),
+          "sd_eval_trajectory_errors")
+    return err, row_err, joint_err, best
+
+
+def noise_loss_grid(model, ctx_list, x0n: Tensor, noise: Tensor, timesteps: Tensor, acp: Optional[Tensor] = None, return_eps: bool = False):
+    """The training loss of C held-out windows at K timesteps each: (C, K) with [c, k] = mean over (T, J) of
+    (eps(x_t, t_k | context c) - noise[c K + k])^2, x_t = ``ddim_add_noise(x0n[c], noise[c K + k], t_k)``.  ``model``: an
+    ``End2EndDiffusionTransformer`` in ``eval()``; ``ctx_list``: its context tensors for the C windows (``encode_input_data``);
+    ``x0n`` (C, T, J) normalised; ``noise`` (C K, T, J); ``timesteps`` (K,) int64 on the device.  One denoiser evaluation of C K trajectories
+    through ``model.forward_with_context(..., draws=K)``: the context is folded once per window and each trajectory reads its own step token
+    (K distinct ones are folded); where the library declines the shape the context rows are expanded and the existing path runs - the same
+    result, only not shared.  ``return_eps``: also the prediction (C K, T, J)."""
+    _req(x0n, "x0n"); _req(noise, "noise"); _req(timesteps, "timesteps", torch.int64)
+    if x0n.dim() != 3 or timesteps.dim() != 1 or timesteps.numel() == 0:
+        raise ValueError("noise_loss_grid: x0n must be (C, T, J) and timesteps (K,)")
+    Cn, T, J = x0n.shape
+    K = timesteps.shape[0]
+    if tuple(noise.shape) != (Cn * K, T, J):
+        raise ValueError(f"noise_loss_grid: noise must be ({Cn * K}, {T}, {J}), got {tuple(noise.shape)}")
+    acp = alphas_cumprod().to(x0n.device) if acp is None else acp
+    t_all = timesteps.repeat(Cn)                                   # trajectory c K + k is window c at timestep k
+    x_t = ddim_add_noise(x0n.repeat_interleave(K, 0).contiguous(), noise, t_all, acp)
+    with torch.no_grad():
+        eps = model.forward_with_context(list(ctx_list), x_t, t_all, draws=K)
+    loss = sqerr_rows(eps.contiguous(), noise).view(Cn, K)
+    return (loss, eps) if return_eps else loss
 
 
 def _chain16_possible(packed: _Packed) -> bool:

@@ -273,6 +273,25 @@ int sd_ddim_sample_pin(const sd_denoiser_weights *w, const float *ctx, const flo
 int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                          float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                          const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, int draws, void *stream);
+/* sd_ddim_sample_draws with held ELEMENTS instead of pinned leading rows ("hold" is the element form, "pin" the leading-row form): joints
+ * another module owns, keyframes, or both.  Element (b, t, j) is held iff bit j of hold_mask[b][t] is set.
+ *   hold_mask (B,T) int32 in device memory: one word per (trajectory, row); J <= 32, bits >= J are never read.  hold_x0, hold_noise
+ *   (B,T,J) as pin_x0, pin_noise; only held elements are read; hold_noise must not alias x.  A captured graph needs no new arguments
+ *   when the mask changes.
+ *   On entry:     held elements of x = c0[0] * hold_x0 + c1[0] * hold_noise
+ *   after step i: held elements of x = c2[i] * hold_x0 + c3[i] * hold_noise in place of the DDIM update; every other element gets the
+ *                 update unchanged; eps_trace stays the network's prediction for all elements.  The last step (1, 0) returns hold_x0 on
+ *                 the held elements bit for bit.  A mask whose set rows are exactly the leading pin_rows[b] full rows is the pinned call.
+ * Kernels: on the trajectory routes the hold instantiations of the step kernels (one per family and tile count; `draws` is a runtime
+ * argument, so draws == 1 and draws > 1 run the same kernel) - the lane that stores the update of (token, 4 joints) loads the token's mask
+ * word once, and reads hold_x0 / hold_noise only where one of its four bits is set; one launch per step (no fused rollout form, no mode-4
+ * twin: max_mode = 4 runs the mode-3 kernels).  On the row-panel and chain routes one elementwise launch follows each step's update, as
+ * for the pin (SD_ROUTE_FUSED_FOLD_F16: every step's head a launch of its own).  The entry overwrite is one elementwise launch per
+ * rollout on every route.  The route is that of the pinned call of the same shape.
+ * SD_E_BADARG (nothing launched): a NULL hold pointer, hold_noise == x, draws < 1, B % draws != 0, or J > 32. */
+int sd_ddim_sample_hold(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                        float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                        const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, void *stream);
 /* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
 int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
 
@@ -798,6 +817,16 @@ int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int 
  *     advance + carry <= T.  x and out are indexed by workgroup (compact in the _at form), pin_x0 and pin_rows by robot.
  *   sd_session_reset_carry: sd_session_reset that also sets pin_rows[b] = 0 for the selected robots (ring 0's workgroup): their next tick
  *     is unpinned.  One launch, nothing read back.
+ * Held joints (a session that hands sd_ddim_sample_hold a mask: joints another module owns, a motor that is switched off):
+ *   sd_session_hold: ONE launch, one workgroup per selected robot (robots as in the _at forms; NULL: S == B).  set != 0: values of the n
+ *     joints `joints` (n int32 in HOST memory, read before the launch; 0 <= joint < J <= 32) - radians as published, values[s][t][k] at
+ *     s * stride_robot + t * stride_row + k, a stride of 0 broadcasts - are normalised, ((v + pi) - mean[j]) / std[j] with every
+ *     operation rounded on its own (the inverse of the commit's expression), and written to pin_x0[b][t][j] for all T rows; the joints'
+ *     bits are set in held[b] (held (B) int32).  set == 0: the bits are cleared, pin_x0 stays, values / mean / std may be NULL.  One
+ *     thread moves the robot's word after the values are written: no atomics.
+ *   sd_session_hold_mask: ONE launch composes a tick's mask, mask[(s * draws + g)][t] = held[b] | (t < pin_rows[b] ? all J bits : 0) for
+ *     robot b = robots[s] (NULL: s) and every draw g; mask (S * draws, T) int32; pin_rows NULL: no carried rows.  It reads device buffers
+ *     only: inside a captured tick it serves every later hold, release and reset.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
 #define SD_SESSION_MAX_RESET_RINGS 5
@@ -835,6 +864,10 @@ int sd_session_commit_carry_at(const float *x, const float *mean, const float *s
                                int32_t *pin_rows, void *stream);
 int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value,
                            int32_t *pin_rows, int B, void *stream);
+int sd_session_hold(float *pin_x0, int32_t *held, const float *values, int64_t stride_robot, int64_t stride_row, const int32_t *joints, int n,
+                    const float *mean, const float *stdv, const int32_t *robots, int S, int B, int T, int J, int set, void *stream);
+int sd_session_hold_mask(int32_t *mask, const int32_t *held, const int32_t *pin_rows, const int32_t *robots, int S, int B, int T, int J,
+                         int draws, void *stream);
 
 /* ---- measurement hooks (bench.py roofline leg; not part of the reference's surface) ----
  * While enabled, every kernel launch made by this library is bracketed by a hipEvent pair

@@ -3,10 +3,10 @@ the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
     python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -559,6 +559,16 @@ def cmd_sample(args) -> int:
     if G > 1 and params.get("distilled_decoder", False):
         raise SystemExit("--draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
     x_T = torch.randn(B * G, params["trajectory_prediction_length"], params["num_joints"], device=device, generator=gen)
+    hold = None
+    if args.hold:   # the joints held at every row of every trajectory, in the space of the file's trajectories (x * std + mean)
+        if params.get("distilled_decoder", False):
+            raise SystemExit("--hold: a distilled decoder is one forward at t = 0 - there is no rollout in which a joint could be held")
+        joints, values = _hold_joints(args.hold, params["num_joints"])
+        known, mask = torch.zeros_like(x_T), torch.zeros(params["num_joints"], dtype=torch.bool, device=device)
+        mean, std = model.mean.reshape(-1), model.std.reshape(-1)
+        known[:, :, joints] = (torch.tensor(values, device=device) - mean[joints]) / std[joints]
+        mask[joints] = True
+        hold = (known, mask)
     with torch.no_grad():
         if params_need_context(params):
             batch = source.batch(mine % source.n)
@@ -569,12 +579,14 @@ def cmd_sample(args) -> int:
         if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         else:
-            traj = model.sample(context, x_T, args.steps, draws=G)   # G draws for each of the B contexts, which are encoded once
+            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
             medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
     out = args.output if world == 1 else f"{args.output}.rank{rank}"
     saved = {"trajectories": traj.cpu(), "noise": x_T.cpu(), "steps": args.steps, "indices": mine}
+    if hold is not None:
+        saved["hold"] = dict(args.hold)   # {joint: the value it was held at}
     if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
         saved.update(trajectories=saved["trajectories"].view(B, G, *traj.shape[1:]), draws=G, medoid=medoid.cpu())
     torch.save(saved, out)
@@ -636,7 +648,8 @@ def cmd_rollout(args) -> int:
     """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep.
     --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again.
     --carry K [--advance S]: overlapping ticks - S trajectory points (default T - K) pass between two ticks, the sensor rows of S points
-    arrive per tick, and the first K rows of a tick's trajectory are pinned to rows [S, S + K) of the previous one."""
+    arrive per tick, and the first K rows of a tick's trajectory are pinned to rows [S, S + K) of the previous one.
+    --hold J=V[,J=V...]: joint J of every robot is held at V radians (as published) inside every tick's rollout, from the first tick on."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
@@ -658,8 +671,10 @@ def cmd_rollout(args) -> int:
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
-                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws)
+                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold))
     params = session.hyperparams
+    if args.hold:
+        session.hold(*_hold_joints(args.hold, params["num_joints"]))
     if args.raw:
         stream = raw_sensor_stream(args.synthetic, params, args.ticks, camera, seed=args.seed)
     else:
@@ -687,6 +702,8 @@ def cmd_rollout(args) -> int:
     saved = {"trajectories": traj, "ticks": args.ticks, "steps": args.steps, "seed": args.seed}
     if args.carry or args.advance is not None:
         saved.update(carry=session.carry, advance=session.advance)
+    if args.hold:
+        saved["hold"] = dict(args.hold)   # {joint: the radians it was held at}
     if args.draws > 1:
         saved["draws"] = session.draws   # every published trajectory is the medoid of that many draws
     if episode is not None:
@@ -710,6 +727,23 @@ def _draws(text: str) -> int:
     return g
 
 
+def _hold(text: str) -> list:
+    """--hold J=V[,J=V...] -> [(joint, value)]; the joints are checked against the model's joint count where it is known."""
+    try:
+        pairs = [(int(j), float(v)) for j, v in (item.split("=") for item in text.split(","))]
+    except ValueError:
+        pairs = []
+    if not pairs or min(j for j, _ in pairs) < 0 or len({j for j, _ in pairs}) != len(pairs):
+        raise argparse.ArgumentTypeError(f"--hold takes JOINT=RADIANS[,JOINT=RADIANS...] with distinct joint indices >= 0, got {text!r}")
+    return pairs
+
+
+def _hold_joints(pairs: list, J: int) -> tuple:
+    if J > 32 or max(j for j, _ in pairs) >= J:
+        raise SystemExit(f"--hold: joint indices lie in [0, {J}) and the model has at most 32 joints")
+    return [j for j, _ in pairs], [v for _, v in pairs]
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="cli", description="SoccerDiffusion denoiser on MI355X: train / sample")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -729,6 +763,8 @@ def build_parser() -> argparse.ArgumentParser:
     sa.add_argument("--ema", action="store_true", help="sample from the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
     sa.add_argument("--draws", type=_draws, default=1, metavar="G", help="G draws for each of the --num_samples contexts, sampled on the shared "
                     "folded context: the file gains draws and medoid (n,), trajectories becomes (n, G, T, J)")
+    sa.add_argument("--hold", type=_hold, default=None, metavar="J=V[,J=V...]", help="joint J is held at V in every row of every trajectory and "
+                    "the other joints are sampled to fit (model.sample(hold=...)); V in the space of the file's trajectories")
     di = sub.add_parser("distill", help="distil the multi-step model into a single-step model (flags of the reference's distill.py)")
     di.add_argument("config", type=str, help="Path to the training configuration file")
     di.add_argument("checkpoint", type=str, help="Path to the checkpoint to load for the teacher model")
@@ -786,6 +822,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "the rows of the previous one that fall in the overlap (PolicySession(carry=K))")
     ro.add_argument("--advance", type=int, default=None, metavar="S", help="trajectory points between two ticks (default: horizon - K); a tick "
                     "commits that many rows to the action history")
+    ro.add_argument("--hold", type=_hold, default=None, metavar="J=V[,J=V...]", help="joint J of every robot is held at V radians (as published) "
+                    "inside every tick's rollout (PolicySession(holds=True).hold)")
     ro.add_argument("--draws", type=_draws, default=1, metavar="G", help="G draws per robot and tick from the once-encoded context; their medoid is "
                     "committed and published (PolicySession(draws=G))")
     ro.add_argument("--seed", type=int, default=0)

@@ -313,6 +313,15 @@ struct PinArgs {
     const int *rows;           // [B] in device memory, 0 <= rows[b] <= T
 };
 
+// Held elements of a rollout (sd_ddim_sample_hold): the element form of the pin - element (b, t, j) is held iff bit j of mask[b][t] is
+// set (J <= 32; bits >= J are never read), and is ck * x0 + cn * noise with the pin's (ck, cn).  A struct of its own: the pinned kernels'
+// argument layout, and so their code, stays what it is.  The trajectory step kernels' hold instantiations take it beside their StepArgs;
+// ddim_hold_kernel (sd_kernels.hip) does the rest.
+struct HoldArgs {
+    const float *x0, *noise;   // [B][T][J] each, as PinArgs
+    const int *mask;           // [B][T] in device memory
+};
+
 // One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
 // (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
 struct StepReq {
@@ -324,6 +333,7 @@ struct StepReq {
     int32_t *status;     // range-guard word of the two-product kernels (SD_STATUS_SHARP_LOGITS), or NULL
     const PinArgs *pin;  // or NULL; needs coef
     int draws;           // trajectories per context: trajectory b reads context b / draws (1: its own)
+    const HoldArgs *hold = nullptr;   // or NULL; needs coef, excludes pin (one hold kernel serves every draws >= 1)
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

@@ -2504,6 +2504,15 @@ __global__ void ddim_pin_kernel(float *__restrict__ x, PinArgs pin, float ck, fl
         if (t < pin.rows[b]) x[i] = ck * pin.x0[i] + cn * pin.noise[i];
     }
 }
+// Held elements of a rollout (HoldArgs, sd_common.h), the element form of the kernel above and launched where it is: x[b][t][j] = ck * x0 +
+// cn * noise where bit j of mask[b][t] is set (J <= 32), every other element left as it is.
+__global__ void ddim_hold_kernel(float *__restrict__ x, HoldArgs hold, float ck, float cn, long n, int J) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / J;
+        const int j = (int)(i - row * J);
+        if (((unsigned)hold.mask[row] >> j) & 1u) x[i] = ck * hold.x0[i] + cn * hold.noise[i];
+    }
+}
 
 
 // ======================================================================================
@@ -2965,11 +2974,12 @@ struct TrajCall {
     // step i (+ DDIM update when coef != NULL).  Mode 4 (tuned family only): two products at the Q | K | V site, sharp logits reported in *status
     // pin: the pinned instantiations (the caller's plan is a three-product one)
     // (draws > 1: the shared-context instantiations; with per_traj the context index b / draws and the step block step_map[b] are separate)
-    StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin) const {
-        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws};
+    // hold: the hold instantiations (held elements; never beside a pin)
+    StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr) const {
+        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold};
     }
-    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr) const {
-        const StepReq r = req(x, eps, i, coef, per_traj, status, pin);
+    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) const {
+        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold);
         return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
     }
     // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
@@ -2996,11 +3006,18 @@ static int ddim_pin(float *x, const PinArgs &pin, float ck, float cn, int B, int
     SD_CHECK_LAUNCH("ddim_pin_kernel");
     return 0;
 }
+// held elements of x <- ck * x0 + cn * noise (ddim_hold_kernel)
+static int ddim_hold(float *x, const HoldArgs &hold, float ck, float cn, int B, int T, int J, hipStream_t st) {
+    const long n = (long)B * T * J;
+    SD_LAUNCH(ddim_hold_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, hold, ck, cn, n, J);
+    SD_CHECK_LAUNCH("ddim_hold_kernel");
+    return 0;
+}
 
 // the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once), or - the plan's rollout_fused -
 // one launch of the rollout kernel per TRAJ_ROLLOUT_MAX_STEPS steps
 static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
-                        int32_t *status, const PinArgs *pin = nullptr) {
+                        int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) {
     const long n = (long)c.B * c.T * c.w->J;
     int rc;
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
@@ -3008,8 +3025,9 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     if ((rc = c.prepare_ctx(ctx))) return rc;
     if ((rc = c.prepare_steps(step_tokens, false))) return rc;
     if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
+    if (hold && (rc = ddim_hold(x, *hold, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
     if (c.plan.rollout_fused) {
-        if (trace || eps_trace || pin || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
+        if (trace || eps_trace || pin || hold || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
         for (int i0 = 0; i0 < c.n_tok; i0 += TRAJ_ROLLOUT_MAX_STEPS) {
             const int nn = c.n_tok - i0 < TRAJ_ROLLOUT_MAX_STEPS ? c.n_tok - i0 : TRAJ_ROLLOUT_MAX_STEPS;
             if ((rc = c.steps_fused(x, i0, nn, coef, status))) return rc;
@@ -3019,7 +3037,7 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin))) return rc;
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
@@ -3028,7 +3046,7 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
 // the rollout on the row-panel kernels (sampler modes 0 - 2)
 static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const SamplerPlan &plan, const float *ctx, const float *step_tokens,
                          const float *coef, float *x, float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, hipStream_t st,
-                         const PinArgs *pin = nullptr) {
+                         const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) {
     const int d = w->d, R = B * T, L = w->L;
     int rc;
     // once per rollout: K/V of the context rows (placed as rows 0..Mc-1 of each trajectory's
@@ -3079,12 +3097,13 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
     }
     const long n = (long)R * w->J;
     if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], B, T, w->J, st))) return rc;
+    if (hold && (rc = ddim_hold(x, *hold, coef[0], coef[1], B, T, w->J, st))) return rc;
     for (int i = 0; i < n_steps; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
         // this step's token row -> row Mc of every trajectory, all layers in one launch
         if (f16) {
-            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i, pin != nullptr))) return rc;
+            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i, pin != nullptr || hold != nullptr))) return rc;
         } else if (fold) {
             SD_LAUNCH(fold_place_kernel, dim3(grid_for((long)B * 4 * 2 * d), L), dim3(256), 0, st, s.gvstep + (size_t)i * 4 * 2 * d,
                       s.cstep + (size_t)i * 4, (long)gvsstride, (long)cssstride, s.gv, s.cb, (long)gvstride, (long)cbstride, B, Mc,
@@ -3103,6 +3122,7 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
         }
         // these routes are many launches per step already: the pinned rows are one more, behind the fused DDIM sites
         if (pin && (rc = ddim_pin(x, *pin, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
+        if (hold && (rc = ddim_hold(x, *hold, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, st))) return rc;
     }
     return status ? finite_check(x, n, status, st) : 0;
@@ -3121,7 +3141,8 @@ __global__ void ctx_expand_kernel(const float *__restrict__ src, float *__restri
 // reads max_mode 4 as 3 (and needs no status word).
 static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                            float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream,
-                           const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, bool pin_required, int draws) {
+                           const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, bool pin_required, int draws,
+                           const HoldArgs *hold = nullptr) {
     const int n_pin = (pin_x0 ? 1 : 0) + (pin_noise ? 1 : 0) + (pin_rows ? 1 : 0);
     if (pin_required ? n_pin != 3 : (n_pin != 0 && n_pin != 3))
         return fail(SD_E_BADARG, pin_required ? "sd_ddim_sample_pin: pin_x0, pin_noise and pin_rows must be given"
@@ -3131,7 +3152,7 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
                                               : "sd_ddim_sample_draws: pin_noise must not alias x (x is overwritten by the first step)");
     const PinArgs pin_args{pin_x0, pin_noise, pin_rows};
     const PinArgs *pin = n_pin ? &pin_args : nullptr;
-    if (pin && max_mode == 4) max_mode = 3;
+    if ((pin || hold) && max_mode == 4) max_mode = 3;
     if (Mc <= 0) draws = 1;   // no context rows: nothing to share
     int rc = check_denoiser(w);
     if (rc) return rc;
@@ -3145,9 +3166,9 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
     if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
-    const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | (pin ? CALL_PIN : 0);
+    const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | ((pin || hold) ? CALL_PIN : 0);   // the plan treats a hold as a pinned call
     const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, call, draws);
-    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st, draws}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin);
+    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st, draws}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin, hold);
     if (draws > 1) {
         // No sharing on the row-panel routes: the B / draws context rows are expanded to B in the workspace (the K | V region, which these
         // routes fill only after the context has been projected) and the kernels of old run on the copy.
@@ -3156,7 +3177,7 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
         SD_CHECK_LAUNCH("ctx_expand_kernel");
         ctx = s.kv;
     }
-    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin);
+    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin, hold);
 }
 
 extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
@@ -3182,6 +3203,20 @@ extern "C" int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *c
     if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_draws: draws must be >= 1 and divide B");
     return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, pin_x0, pin_noise, pin_rows,
                            false, draws);
+}
+
+// Held ELEMENTS instead of pinned leading rows (HoldArgs, sd_common.h): bit j of hold_mask[b][t] set - element (b, t, j) is c0[0] known +
+// c1[0] noise on entry and c2[i] known + c3[i] noise after step i.  All three arrays must be given; J <= 32.  draws as sd_ddim_sample_draws.
+extern "C" int sd_ddim_sample_hold(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                   float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                   int max_mode, const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, void *stream) {
+    if (!hold_x0 || !hold_noise || !hold_mask) return fail(SD_E_BADARG, "sd_ddim_sample_hold: hold_x0, hold_noise and hold_mask must be given");
+    if (hold_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_hold: hold_noise must not alias x (x is overwritten by the first step)");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_hold: draws must be >= 1 and divide B");
+    if (w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_hold: one 32-bit mask word per row: J must be <= 32");
+    const HoldArgs hold{hold_x0, hold_noise, hold_mask};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, draws, &hold);
 }
 
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)

@@ -1,7 +1,7 @@
 // Closed-loop policy session: the buffer work of the receding-horizon tick (soccer_diffusion/ml/inference/ros.py:165-335) on the device.
 // Interface, ring layout and citations: include/soccerdiffusion_hip.h (sd_ring_push, sd_ring_window, sd_session_windows, sd_session_commit,
 // their *_at forms for a subset of the robots, sd_ring_push_quat, sd_session_reset, and sd_session_commit_carry(_at) / sd_session_reset_carry for a
-// session whose ticks overlap).
+// session whose ticks overlap, and sd_session_hold / sd_session_hold_mask for a session that holds chosen joints inside the rollout).
 //
 // ros.py keeps every sensor stream as a Python list of CPU tensors (append, then trim to the context length: ros.py:203,256-257,316-318)
 // and stacks + uploads every list at every tick (ros.py:265-275).  Here a stream is a ring (B, L, C) in device memory with one head word per
@@ -240,6 +240,52 @@ __global__ __launch_bounds__(THREADS) void session_reset_carry_kernel(Resets a, 
     }
 }
 
+// ---- held joints (PolicySession(holds=True): sd_ddim_sample_hold's mask and known values, kept per robot) ------------------------------
+struct HoldJoints {   // the joints of one hold / release call, by value in the kernel argument: J <= 32
+    int n;
+    int j[32];
+};
+
+// One workgroup per selected robot.  set: values[s][t][k] (radians as published; robot and row strides, 0 = broadcast) of joint j[k] go,
+// normalised - ((v + pi) - mean[j]) / std[j], the inverse of the commit's expression, every operation rounded on its own - to
+// pin_x0[b][t][j] for all T rows, and the joints' bits are set in held[b]; else the bits are cleared and pin_x0 stays.  One thread
+// moves the robot's word: no atomics.
+__global__ __launch_bounds__(THREADS) void session_hold_kernel(float *pin_x0, int32_t *held, const float *__restrict__ values, long stride_robot,
+                                                               long stride_row, HoldJoints hj, const float *__restrict__ mean,
+                                                               const float *__restrict__ stdv, const int32_t *__restrict__ robots, int B, int T,
+                                                               int J, int set) {
+    const int b = robot_of(robots, blockIdx.x, B);
+    if (b < 0) return;
+    const float pi = (float)M_PI;
+    unsigned bits = 0;
+    for (int k = 0; k < hj.n; ++k)
+        if ((unsigned)hj.j[k] < (unsigned)J) bits |= 1u << hj.j[k];
+    if (set) {
+        const float *vb = values + (long)blockIdx.x * stride_robot;
+        float *pb = pin_x0 + (long)b * T * J;
+        for (int i = threadIdx.x; i < T * hj.n; i += THREADS) {
+            const int t = i / hj.n, k = i - t * hj.n, j = hj.j[k];
+            if ((unsigned)j >= (unsigned)J) continue;
+            pb[t * J + j] = ((vb[(long)t * stride_row + k] + pi) - mean[j]) / stdv[j];
+        }
+    }
+    if (threadIdx.x == 0) held[b] = (int32_t)(set ? ((unsigned)held[b] | bits) : ((unsigned)held[b] & ~bits));
+}
+
+// The tick's mask: mask[s * draws + g][t] = held[b] | (t < pin_rows[b] ? all J bits : 0), b = robot s of the launch (robots NULL: s);
+// pin_rows NULL: a session without carried rows.  n = S * draws * T words.
+__global__ __launch_bounds__(THREADS) void session_hold_mask_kernel(int32_t *__restrict__ mask, const int32_t *__restrict__ held,
+                                                                    const int32_t *__restrict__ pin_rows, const int32_t *__restrict__ robots,
+                                                                    int n, int B, int T, int J, int draws) {
+    const int i = blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int row = i / T, t = i - row * T;
+    const int b = robot_of(robots, row / draws, B);
+    if (b < 0) return;
+    const unsigned all = J >= 32 ? 0xffffffffu : (1u << J) - 1u;
+    mask[i] = (int32_t)(((unsigned)held[b] & all) | ((pin_rows && t < pin_rows[b]) ? all : 0u));
+}
+
 }   // namespace ss
 
 static bool dims_ok(int B, int L, int C) { return B > 0 && L > 0 && C > 0 && (long)L * C <= 0x7fffffffL / 2; }   // (row * C + column stays an int)
@@ -382,6 +428,37 @@ extern "C" int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, c
     SD_LAUNCH(ss::session_reset_carry_kernel, dim3((unsigned)B, (unsigned)n_rings), dim3(ss::THREADS), 0, (hipStream_t)stream, a, mask, game_state,
               game_state_value, pin_rows);
     SD_CHECK_LAUNCH("session_reset_carry_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_hold(float *pin_x0, int32_t *held, const float *values, int64_t stride_robot, int64_t stride_row, const int32_t *joints, int n,
+                               const float *mean, const float *stdv, const int32_t *robots, int S, int B, int T, int J, int set, void *stream) {
+    if (!held || !joints || n < 1 || n > 32 || J < 1 || J > 32 || !dims_ok(B, T, J) || S < 0 || (!robots && S != B))
+        return fail(SD_E_BADARG, "sd_session_hold: held and joints must be given; 1 <= n <= 32, 1 <= J <= 32, B, T > 0, S >= 0, S = B without robots");
+    if (set && (!pin_x0 || !values || !mean || !stdv || stride_robot < 0 || stride_row < 0))
+        return fail(SD_E_BADARG, "sd_session_hold: a hold needs pin_x0, values, mean and std; strides >= 0");
+    ss::HoldJoints hj{};
+    hj.n = n;
+    for (int k = 0; k < n; ++k) {
+        if (joints[k] < 0 || joints[k] >= J) return fail(SD_E_BADARG, "sd_session_hold: joint index out of range");
+        hj.j[k] = joints[k];
+    }
+    if (S == 0) return 0;
+    SD_LAUNCH(ss::session_hold_kernel, dim3((unsigned)S), dim3(ss::THREADS), 0, (hipStream_t)stream, pin_x0, held, values, (long)stride_robot,
+              (long)stride_row, hj, mean, stdv, robots, B, T, J, set ? 1 : 0);
+    SD_CHECK_LAUNCH("session_hold_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_hold_mask(int32_t *mask, const int32_t *held, const int32_t *pin_rows, const int32_t *robots, int S, int B, int T, int J,
+                                    int draws, void *stream) {
+    if (!mask || !held || J < 1 || J > 32 || !dims_ok(B, T, J) || S < 0 || draws < 1 || (!robots && S != B) || (long)S * draws * T > 0x7fffffffL / 2)
+        return fail(SD_E_BADARG, "sd_session_hold_mask: mask and held must be given; 1 <= J <= 32, B, T > 0, S >= 0, draws >= 1, S = B without robots");
+    if (S == 0) return 0;
+    const int n = S * draws * T;
+    SD_LAUNCH(ss::session_hold_mask_kernel, dim3((unsigned)((n + ss::THREADS - 1) / ss::THREADS)), dim3(ss::THREADS), 0, (hipStream_t)stream, mask, held,
+              pin_rows, robots, n, B, T, J, draws);
+    SD_CHECK_LAUNCH("session_hold_mask_kernel");
     return 0;
 }
 

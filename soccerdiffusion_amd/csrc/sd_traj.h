@@ -1449,9 +1449,13 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // (g16 / v16 / cb of context traj / draws: a scalar quotient, once per launch or per step of the rollout loop); x, eps, the pinned rows,
 // the status word and the step block stay per trajectory.  Their pin is a runtime option (pin.rows NULL: nothing pinned), so that
 // "shared" and "shared + pinned" are one kernel.
-template <bool WIDE = false, bool PIN = false, bool ROLL = false, bool DRAWS = false>
+// PIN == 2, HOLD: the element form (HoldArgs, sd_common.h; sd_ddim_sample_hold) - the lane that stores the update of (tok, j0 .. j0 + 3) loads
+// the token's mask word once, ahead of the barrier in front of the fc_out GEMM, and takes bits j0 .. j0 + 3 of it: none set - the unpinned
+// store, x0 and noise not loaded; all four - the pinned store; else both, selected element by element.  No barrier and no LDS of its own.
+template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
-                                                 int roll_step = 0, int roll_wave = 0, int draws = 1) {
+                                                 int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{}) {
+    constexpr bool HOLD = PIN == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
@@ -1538,7 +1542,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         const Ctx &c = ROLL ? c_tail : c_step;
         float *stat = reinterpret_cast<float *>(c.smem + LDS_STAT);
         int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
-        if constexpr (PIN) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
+        if constexpr (PIN == 1) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
         float am[NTT];
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
@@ -1581,6 +1585,10 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                     if (16 * n + 4 * c.g < J) xpre[n] = *reinterpret_cast<const f32x4 *>(a.x + (traj * a.T + tok) * J + 16 * n + 4 * c.g);
             }
         }
+        unsigned hold_m = 0;   // HOLD: the mask word of this lane's token, requested beside the weight fragments
+        if constexpr (HOLD) {
+            if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) hold_m = (unsigned)hold.mask[traj * a.T + (c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6)];
+        }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
         if (c.w < NTT) {
@@ -1608,16 +1616,22 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 if (!ok || j0 >= J) continue;
                 const long at = (traj * a.T + tok) * J + j0;
                 bool pinned = false;
-                if constexpr (PIN) pinned = tok < pin_rows;
+                if constexpr (PIN == 1) pinned = tok < pin_rows;
                 if (J & 3) {   // rows of J floats are not 16-byte aligned, the last group of four is ragged: element by element
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (j0 + r >= J) continue;
                         const float e = E[n][r] * c_o + a.b_out[j0 + r];
                         if (a.eps_out) a.eps_out[at + r] = e;
-                        if constexpr (PIN) {
+                        if constexpr (PIN == 1) {
                             if (a.update_x && pinned) {
                                 a.x[at + r] = a.c2 * pin.x0[at + r] + a.c3 * pin.noise[at + r];
+                                continue;
+                            }
+                        }
+                        if constexpr (HOLD) {
+                            if (a.update_x && ((hold_m >> (j0 + r)) & 1u)) {
+                                a.x[at + r] = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
                                 continue;
                             }
                         }
@@ -1634,10 +1648,28 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 }
                 const f32x4 e = E[n] * c_o + *reinterpret_cast<const f32x4 *>(a.b_out + j0);
                 if (a.eps_out) *reinterpret_cast<f32x4 *>(a.eps_out + at) = e;
-                if constexpr (PIN) {
+                if constexpr (PIN == 1) {
                     if (a.update_x && pinned) {
                         const f32x4 k = *reinterpret_cast<const f32x4 *>(pin.x0 + at), nz = *reinterpret_cast<const f32x4 *>(pin.noise + at);
                         *reinterpret_cast<f32x4 *>(a.x + at) = a.c2 * k + a.c3 * nz;
+                        continue;
+                    }
+                }
+                if constexpr (HOLD) {
+                    const unsigned bits = (hold_m >> j0) & 15u;
+                    if (a.update_x && bits) {
+                        const f32x4 k = *reinterpret_cast<const f32x4 *>(hold.x0 + at), nz = *reinterpret_cast<const f32x4 *>(hold.noise + at);
+                        f32x4 xn = a.c2 * k + a.c3 * nz;
+                        if (bits != 15u) {   // some of the four are free: their DDIM update, as below
+                            const f32x4 xv = *reinterpret_cast<const f32x4 *>(a.x + at);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float x0 = (xv[r] - a.c1 * e[r]) / a.c0;
+                                const float u = a.c2 * x0 + a.c3 * e[r];
+                                xn[r] = ((bits >> r) & 1u) ? xn[r] : u;
+                            }
+                        }
+                        *reinterpret_cast<f32x4 *>(a.x + at) = xn;
                         continue;
                     }
                 }
@@ -1707,6 +1739,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_draws_kernel(StepArgs a
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_draws_kernel(StepArgs a, PinArgs pin, int draws) {
     TJ<NTT, true>::template step_body<true, true, false, true>(a, pin, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws);
+}
+// The hold twins (sd_ddim_sample_hold; instantiated in sd_traj_hold.hip): held ELEMENTS instead of pinned leading rows.  `draws` is a runtime
+// argument as above, so one kernel per tile count serves draws == 1 (trajectory b reads context b) and draws > 1.  Three products
+// everywhere: mode 4 has no hold twin either.
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_hold_kernel(StepArgs a, HoldArgs hold, int draws) {
+    TJ<NTT, true>::template step_body<false, 2, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_hold_kernel(StepArgs a, HoldArgs hold, int draws) {
+    TJ<NTT, true>::template step_body<true, 2, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold);
 }
 struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
     RolloutArgs ra;

@@ -1,6 +1,7 @@
 // Tuned trajectory step kernels of the sampler (modes 3 / 4: hidden_dim 256, 4 heads, horizon <= 100, <= 64 memory rows): the host side
 // of sd_traj.h - shape test, the three preparation stages, the step launch (traj_step) and the rollout launch (traj_steps_fused), each
-// for every form of the kernel: plain, pinned, shared context (the last one's instantiations compile in sd_traj_draws.hip) - and the
+// for every form of the kernel: plain, pinned, shared context, held elements (the last two's instantiations compile in sd_traj_draws.hip
+// and sd_traj_hold.hip) - and the
 // step-token kernels that only this path launches.
 // Interface towards the sampler's driver (sd_kernels.hip): sd_traj_host.h, function for function what sd_trajg.h is for the generic family.
 //
@@ -58,6 +59,9 @@ typedef void (*TrajStepDrawsFn)(tj::StepArgs, PinArgs, int);
 typedef void (*TrajRolloutDrawsFn)(tj::RolloutDrawsArgs);
 TrajStepDrawsFn traj_step_draws_fn(int ntt, int variant);
 TrajRolloutDrawsFn traj_rollout_draws_fn(int ntt, bool precise);
+// sd_traj_hold.hip: the hold instantiations (held elements: HoldArgs; the group size is a runtime argument, 1 included)
+typedef void (*TrajStepHoldFn)(tj::StepArgs, HoldArgs, int);
+TrajStepHoldFn traj_step_hold_fn(int ntt, bool wide);
 
 // zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
 __global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
@@ -342,14 +346,21 @@ static tj::StepArgs traj_step_args(const sd_denoiser_weights *w, const TrajWs &s
 static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 && r.B % r.draws == 0; }
 
 // one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
-// as a runtime option
+// as a runtime option; r.hold: the hold twin (sd_traj_hold.hip), whatever the group size
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise) {
     const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
     if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
     if (!traj_groups_ok(r)) return fail(SD_E_BADARG, "traj_step_draws_kernel: B must be a multiple of draws >= 1");
     if (r.pin && (!r.coef || variant == 0)) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
+    if (r.hold && (!r.coef || variant == 0 || r.pin))
+        return fail(SD_E_BADARG, "traj_step_hold_kernel: held elements need the DDIM coefficients and the three-product kernels, and exclude a pin");
     const tj::StepArgs a = traj_step_args(w, s, r, r.coef, nkt);
+    if (r.hold) {
+        static DevFlag hold_attr_set[2][8];   // [one key tile | wide][ntt]
+        return launch_step_kernel(traj_step_hold_fn(ntt, variant == 2), "traj_step_hold_kernel", hold_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS,
+                                  tj::LDS_BYTES, st, a, *r.hold, r.draws);
+    }
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][variant][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][variant][ntt];
     if (r.draws > 1)
@@ -368,7 +379,7 @@ int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, const StepRe
     const int ntt = (r.T + 15) / 16;
     if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_rollout_kernel: horizon out of range");
     if (n < 1 || n > tj::ROLL_MAX_STEPS || r.i < 0 || r.i + n > r.n_tok || !r.coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
-    if (!traj_groups_ok(r) || r.eps || r.per_traj || r.pin)
+    if (!traj_groups_ok(r) || r.eps || r.per_traj || r.pin || r.hold)
         return fail(SD_E_BADARG, "traj_step_rollout_kernel: B a multiple of draws; nothing returned per step, no per-trajectory tokens, no pin");
     tj::RolloutDrawsArgs da{};
     da.draws = r.draws;

@@ -816,8 +816,11 @@ struct TG {
     // PIN: the lanes that store the DDIM update store c2 * x0 + c3 * noise instead for the tokens below pin.rows[traj] (PinArgs, sd_common.h)
     // DRAWS: the shared-context instantiation (sd_ddim_sample_draws) - trajectory b reads the K / V planes of context b / draws; its pin is a
     // runtime option (pin.rows NULL: nothing pinned)
-    template <bool PIN = false, bool DRAWS = false>
-    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1) {
+    // PIN == 2, HOLD: the element form (HoldArgs, sd_common.h; sd_ddim_sample_hold) - the storing lane loads its token's mask word once,
+    // ahead of the barrier in front of the fc_out GEMM, and tests bit j per element; x0 and noise are loaded for held elements only
+    template <int PIN = 0, bool DRAWS = false>
+    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{}) {
+        constexpr bool HOLD = PIN == 2;
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -870,7 +873,7 @@ struct TG {
         {
             float *stat = reinterpret_cast<float *>(c.smem + c.oS);
             int pin_rows = 0;   // one scalar load per workgroup, two barriers ahead of its use
-            if constexpr (PIN) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
+            if constexpr (PIN == 1) pin_rows = (!DRAWS || pin.rows) ? pin.rows[traj] : 0;
             float am[NTT];
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
@@ -900,6 +903,10 @@ struct TG {
 #pragma unroll
                 for (int aa = 0; aa < NA; ++aa) store_x(c, tt, NA * c.w + aa, H[aa][tt] * s);
             }
+            unsigned hold_m = 0;   // HOLD: the mask word of this lane's token
+            if constexpr (HOLD) {
+                if (c.w < NTT && (c.w < NTT - 1 || c.okl)) hold_m = (unsigned)hold.mask[traj * a.T + (c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl)];
+            }
             __syncthreads();
             if (c.w < NTT) {
                 const char *X = c.smem;
@@ -922,15 +929,21 @@ struct TG {
                     if (!ok || j0 >= J) continue;
                     const long at = (traj * a.T + tok) * J + j0;
                     bool pinned = false;
-                    if constexpr (PIN) pinned = tok < pin_rows;
+                    if constexpr (PIN == 1) pinned = tok < pin_rows;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (j0 + r >= J) continue;
                         const float e = E[n][r] * c_o + a.b_out[j0 + r];
                         if (a.eps_out) a.eps_out[at + r] = e;
-                        if constexpr (PIN) {
+                        if constexpr (PIN == 1) {
                             if (a.update_x && pinned) {
                                 a.x[at + r] = a.c2 * pin.x0[at + r] + a.c3 * pin.noise[at + r];
+                                continue;
+                            }
+                        }
+                        if constexpr (HOLD) {
+                            if (a.update_x && ((hold_m >> (j0 + r)) & 1u)) {
+                                a.x[at + r] = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
                                 continue;
                             }
                         }
@@ -954,6 +967,11 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_pin_kernel(StepArg
 template <int D, int NTT>
 __global__ __launch_bounds__(NTHREADS) void traj_step_generic_draws_kernel(StepArgs a, PinArgs pin, int draws) {
     TG<D, NTT>::template step_body<true, true>(a, pin, draws);
+}
+// the hold twin (sd_ddim_sample_hold): held elements; `draws` at run time, 1 included - one kernel per (hidden_dim, tile count)
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_hold_kernel(StepArgs a, HoldArgs hold, int draws) {
+    TG<D, NTT>::template step_body<2, true>(a, PinArgs{}, draws, hold);
 }
 
 }   // namespace tg
@@ -1022,6 +1040,10 @@ StepFn step_fn(int d, int ntt) {
 }
 StepPinFn step_pin_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepPinFn { return tg::traj_step_generic_pin_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepHoldFn)(tg::StepArgs, HoldArgs, int);
+StepHoldFn step_hold_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepHoldFn { return tg::traj_step_generic_hold_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
@@ -1138,6 +1160,8 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     const int ntt = (T + 15) / 16;
     if (ntt < 1 || ntt > (d == 512 ? 3 : 7)) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
     if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
+    if (r.hold && (!r.coef || r.pin))
+        return fail(SD_E_BADARG, "traj_step_generic_hold_kernel: held elements need the DDIM coefficients and exclude a pin");
     tg::StepArgs a{};
     a.x = r.x;
     a.eps_out = r.eps;
@@ -1170,6 +1194,11 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     constexpr int MAX_LDS = 163840;
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.hold) {   // held elements: the hold twin, whatever the group size
+        static DevFlag hold_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_hold_fn(d, ntt), "traj_step_generic_hold_kernel", hold_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, *r.hold, r.draws);
+    }
     if (r.draws > 1)   // trajectory b reads the planes of context b / draws: the shared instantiation, pinned or not
         return launch_step_kernel(step_draws_fn(d, ntt), "traj_step_generic_draws_kernel", flag, MAX_LDS, r.B, tg::NTHREADS, lds, st, a,
                                   r.pin ? *r.pin : PinArgs{nullptr, nullptr, nullptr}, r.draws);

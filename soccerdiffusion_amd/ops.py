@@ -342,6 +342,49 @@ def _pin_req(pin, B: int, T: int, J: int, device) -> tuple:
     return known, rows
 
 
+def hold_mask(mask, B: int, T: int, J: int, device, rows=None) -> Tensor:
+    """The element mask of ``ddim_sample(hold=(known, mask))`` as the (B, T) int32 words the kernels read: bit j of word (b, t) set =
+    element (b, t, j) is held.  ``mask``: a bool tensor (B, T, J), (T, J) or (J,) - the latter two broadcast over the leading dimensions -
+    or a (B, T) int32 tensor of words, which is used as it is (on ``device``).  ``rows`` (an int or (B,) counts, as ``pin_rows``): the
+    leading rows[b] full rows are held as well - the composition of a pin with a hold.  ValueError for J > 32 (one word per row) or a
+    wrong shape.  Bit 31 (J = 32) comes out as the sign bit of the int32 word."""
+    if isinstance(J, bool) or not 1 <= int(J) <= 32:
+        raise ValueError(f"hold mask: one 32-bit word per (trajectory, row) describes at most 32 joints, got J = {J}")
+    B, T, J = int(B), int(T), int(J)
+    if not isinstance(mask, Tensor):
+        raise ValueError(f"hold mask: expected a bool tensor ({B}, {T}, {J}), ({T}, {J}) or ({J},), or ({B}, {T}) int32 words, got {type(mask).__name__}")
+    if mask.dtype == torch.int32 and tuple(mask.shape) == (B, T):
+        words = mask.to(device).contiguous()
+    elif mask.dtype == torch.bool and tuple(mask.shape) in ((B, T, J), (T, J), (J,)):
+        weights = torch.ones(J, dtype=torch.int64, device=mask.device) << torch.arange(J, dtype=torch.int64, device=mask.device)
+        w64 = (mask.expand(B, T, J).to(torch.int64) * weights).sum(-1)                  # 0 .. 2^32 - 1
+        words = torch.where(w64 >= 2 ** 31, w64 - 2 ** 32, w64).to(torch.int32).to(device).contiguous()   # the same 32 bits, signed
+    else:
+        raise ValueError(f"hold mask: expected a bool tensor ({B}, {T}, {J}), ({T}, {J}) or ({J},), or ({B}, {T}) int32 words, "
+                         f"got {tuple(mask.shape)} {mask.dtype}")
+    if rows is not None:
+        counts = pin_rows(rows, B, T, device)
+        full = -1 if J == 32 else (1 << J) - 1
+        lead = torch.arange(T, device=words.device).unsqueeze(0) < counts.unsqueeze(1)
+        words = torch.where(lead, words | full, words).to(torch.int32)
+    return words
+
+
+def _hold_req(hold, B: int, T: int, J: int, device) -> tuple:
+    """(known, mask words) of a call with held elements, validated: known (B, T, J) fp32 on the device, the mask through ``hold_mask``."""
+    try:
+        known, mask = hold
+    except (TypeError, ValueError):
+        raise ValueError("hold: expected (known, mask)") from None
+    words = hold_mask(mask, B, T, J, device)
+    if not isinstance(known, Tensor) or tuple(known.shape) != (B, T, J):
+        raise ValueError(f"hold known: expected a ({B}, {T}, {J}) tensor, got {tuple(getattr(known, 'shape', ()))}")
+    _req(known, "hold known")
+    if known.device != device:
+        raise ValueError(f"hold known: expected a tensor on {device}, got {known.device}")
+    return known, words
+
+
 def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
     """``draws`` of a sampler call, validated before any launch: an int >= 1 with ``n_ctx * draws == B`` (n_ctx None: no context rows -
     the draws then only have to divide B)."""
@@ -357,11 +400,19 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
 
 
 def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
-                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int):
+                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None):
     """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
     ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
-    ``sd_ddim_sample_pin``, launch for launch.  Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
+    ``sd_ddim_sample_pin``, launch for launch; ``hold = (known, noise, mask words)``: ``sd_ddim_sample_hold`` (never beside a pin).
+    Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
     B, T, _ = x.shape
+    if hold is not None:
+        check(_lib.load().sd_ddim_sample_hold(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                              x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1], len(coef),
+                                              _ptr(status), int(max_mode), *[_ptr(t) for t in hold], draws, _stream()),
+              "sd_ddim_sample_hold")
+        out = (x,) + tuple(t for t in (tr, et) if t is not None)
+        return out if len(out) > 1 else x
     check(_lib.load().sd_ddim_sample_draws(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
                                            x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1], len(coef),
                                            _ptr(status), int(max_mode), *[_ptr(t) for t in (pin or (None, None, None))], draws, _stream()),
@@ -378,11 +429,15 @@ class GraphedSampler:
     the range-guard word of ``sd_ddim_sample_ex``, rewritten by every replay.  ``pin=True`` captures the pinned call on static
     pin buffers (known rows, start noise, row counts): a replay copies the call's ``pin=(known, rows)`` into them, so one graph
     serves every pinning, none (rows = 0) included.  ``draws`` > 1: the context buffer holds B / draws contexts, trajectory b reads
-    context b // draws.  (One native call for all of them: ``_ddim_sample_native``.)"""
+    context b // draws.  ``hold=True`` captures the call with held elements (``sd_ddim_sample_hold``) on static known, noise and mask
+    buffers: a replay copies the call's ``hold=(known, mask)`` into them, so one graph serves every mask, the empty one included; not
+    together with ``pin`` (compose them through ``hold_mask(rows=...)``).  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
-                 draws: int = 1):
+                 draws: int = 1, hold: bool = False):
         dev = step_tokens.device
+        if pin and hold:
+            raise ValueError("GraphedSampler: pin and hold exclude each other - compose them through ops.hold_mask(rows=...)")
         self.draws = _draws_req(draws, B, None)
         self.packed, self.coef = packed, np.ascontiguousarray(coef, dtype=np.float32)
         self.tokens = step_tokens.contiguous()
@@ -393,6 +448,11 @@ class GraphedSampler:
         self.pin = None
         if pin:   # (known, noise, rows)
             self.pin = (torch.zeros_like(self.x), torch.zeros_like(self.x), torch.zeros(B, dtype=torch.int32, device=dev))
+        self.hold = None
+        if hold:   # (known, noise, mask words)
+            if packed.J > 32:
+                raise ValueError(f"hold: one 32-bit mask word per row describes at most 32 joints, got J = {packed.J}")
+            self.hold = (torch.zeros_like(self.x), torch.zeros_like(self.x), torch.zeros(B, T, dtype=torch.int32, device=dev))
         lib = _lib.load()
         self.ws = torch.empty(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, len(self.coef)),
                               dtype=torch.float32, device=dev)
@@ -407,13 +467,16 @@ class GraphedSampler:
             self._run()
 
     def _run(self):
-        _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws)
+        _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws,
+                            self.hold)
 
-    def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None) -> Tensor:
+    def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None, hold=None) -> Tensor:
         """Copies the inputs into the captured buffers, replays, and returns the captured x buffer itself
         (overwritten by the next replay)."""
         if (pin is None) != (self.pin is None):
             raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
+        if (hold is None) != (self.hold is None):
+            raise ValueError("GraphedSampler: a graph captured with hold=True takes hold=(known, mask) at every call, one without takes none")
         if self.ctx is not None and tuple(ctx.shape) != tuple(self.ctx.shape):
             raise ValueError(f"context shape mismatch: expected {tuple(self.ctx.shape)} ({self.draws} draws per context), got {tuple(ctx.shape)}")
         self.x.copy_(x_T)
@@ -424,16 +487,21 @@ class GraphedSampler:
             self.pin[0].copy_(known)
             self.pin[1].copy_(x_T)
             self.pin[2].copy_(rows)
+        if hold is not None:
+            known, words = _hold_req(hold, *self.x.shape, self.x.device)
+            self.hold[0].copy_(known)
+            self.hold[1].copy_(x_T)
+            self.hold[2].copy_(words)
         self.graph.replay()
         return self.x
 
-    def __call__(self, ctx: Optional[Tensor], x_T: Tensor, pin=None) -> Tensor:
-        return self.replay_into(ctx, x_T, pin).clone()
+    def __call__(self, ctx: Optional[Tensor], x_T: Tensor, pin=None, hold=None) -> Tensor:
+        return self.replay_into(ctx, x_T, pin, hold).clone()
 
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False, pin=None, draws: int = 1):
+                eps_trace: bool = False, pin=None, draws: int = 1, hold=None):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -448,8 +516,14 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     a private copy of it is taken first).  ``max_mode`` 4 runs the mode-3 kernels.  ``pin=None`` is the call without any of this.
     ``draws`` = G > 1: several draws per observation (``sd_ddim_sample_draws``).  ``ctx`` is (B / G, Mc, d) and trajectory b reads context
     b // G: the context is projected and folded once per context and the G draws share its planes - bit for bit the result of the call with
-    ``ctx.repeat_interleave(G, 0)``, without the G copies.  Everything else (``x_T``, the traces, ``pin``, ``status``) stays per trajectory."""
+    ``ctx.repeat_interleave(G, 0)``, without the G copies.  Everything else (``x_T``, the traces, ``pin``, ``status``) stays per trajectory.
+    ``hold = (known, mask)``: the element form of the pin (``sd_ddim_sample_hold``) - ``mask`` as ``hold_mask`` takes it: element (b, t, j)
+    is held to ``known`` iff its bit is set, with the pin's coefficients and the pin's exactness at the last step; every other element is
+    sampled to fit.  J <= 32.  ``pin`` and ``hold`` together raise ValueError: ``hold_mask(mask, ..., rows=rows)`` composes them.  The
+    trajectory routes run one hold kernel per step for any ``draws``."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
+    if pin is not None and hold is not None:
+        raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
     lib = _lib.load()
     _req(x_T, "x_T"); _req(step_tokens, "step_tokens")
     B, T, J = x_T.shape
@@ -467,13 +541,17 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         _req(status, "status", torch.int32)
     if pin is not None:
         pin = _pin_req(pin, B, T, J, x_T.device)
+    if hold is not None:
+        hold = _hold_req(hold, B, T, J, x_T.device)
     x = x_T if inplace else x_T.clone()
     tr = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if trace else None
     et = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if eps_trace else None
     ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, n_steps), x.device)
     if pin is not None:   # (known, noise, rows); the noise never x itself: the first step overwrites x
         pin = (pin[0], x_T.clone() if inplace else x_T, pin[1])
-    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws)
+    if hold is not None:   # (known, noise, mask words), the noise as the pin's
+        hold = (hold[0], x_T.clone() if inplace else x_T, hold[1])
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold)
 
 
 def default_sampler_cap() -> int:
@@ -496,22 +574,26 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
-                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1):
+                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin`` and ``draws``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context rows: correct, not shared)."""
+    ``pin``, ``hold`` and ``draws``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context rows: correct, not shared)."""
     import warnings
 
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
+    if pin is not None and hold is not None:
+        raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
     if pin is not None:   # validated and uploaded once for all repeats
         pin = _pin_req(pin, *x_T.shape, x_T.device)
+    if hold is not None:
+        hold = _hold_req(hold, *x_T.shape, x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
-    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws)
+    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold)
     word = int(status.item())
     if word == 0:
         return out
@@ -521,7 +603,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         # of the checkpoint, so later calls with these weights start there.
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
-            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws)
+            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -530,7 +612,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     if mode >= 2:
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws)
+        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
@@ -1903,6 +1985,75 @@ def session_commit_carry(x: Tensor, mean: Tensor, std: Tensor, ring: Tensor, hea
                                                      head.data_ptr(), r.data_ptr(), S, B, T, J, L, advance, carry, pin_x0.data_ptr(),
                                                      pin_rows.data_ptr(), _stream()), "sd_session_commit_carry_at")
     return out
+
+
+def hold_joints(joints, J: int) -> list:
+    """The joint indices of a hold / release, validated on the host (no device needed): a non-empty sequence of distinct ints in [0, J),
+    J <= 32."""
+    if isinstance(J, bool) or not 1 <= int(J) <= 32:
+        raise ValueError(f"hold: one 32-bit word per robot describes at most 32 joints, got J = {J}")
+    try:
+        idx = [operator.index(v) for v in joints if not isinstance(v, bool)]
+        n = len(joints)
+    except TypeError:
+        raise ValueError(f"joints: expected a sequence of joint indices, got {joints!r}") from None
+    if not idx or len(idx) != n:
+        raise ValueError(f"joints: expected a non-empty flat sequence of ints, got {joints!r}")
+    bad = [v for v in idx if not 0 <= v < J]
+    if bad:
+        raise ValueError(f"joints: index {bad[0]} is outside [0, {J})")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"joints: an index occurs twice in {idx}")
+    return idx
+
+
+def session_hold(pin_x0: Tensor, held: Tensor, joints, values: Optional[Tensor], mean: Optional[Tensor], std: Optional[Tensor],
+                 robots=None) -> None:
+    """One launch (``sd_session_hold``): ``values`` - radians as published, (n,), (S, n) or (S, T, n) fp32 on the device - of the joints
+    ``joints`` are normalised with mean and std and written into ``pin_x0[b, :, j]`` (B, T, J) for the selected robots, whose bits in
+    ``held`` (B) int32 are set; ``values`` None: the bits are cleared (a release).  ``robots`` as ``robot_index``; None: all, S = B."""
+    _req(pin_x0, "pin_x0"); _req(held, "held", torch.int32)
+    if pin_x0.dim() != 3 or tuple(held.shape) != (pin_x0.shape[0],) or held.device != pin_x0.device:
+        raise ValueError(f"pin_x0 / held: expected (B, T, J) fp32 and (B,) int32 on one device, got {tuple(pin_x0.shape)} and {tuple(held.shape)}")
+    B, T, J = pin_x0.shape
+    idx = hold_joints(joints, J)
+    n = len(idx)
+    r = None if robots is None else _robots_on(robots, B, pin_x0.device)
+    S = B if r is None else r.numel()
+    strides = (0, 0)
+    if values is not None:
+        _req(values, "values"); _req(mean, "mean"); _req(std, "std")
+        if values.device != pin_x0.device or mean.numel() != J or std.numel() != J:
+            raise ValueError(f"values: expected fp32 values on {pin_x0.device} with {J} means and stds")
+        if tuple(values.shape) == (n,):
+            strides = (0, 0)
+        elif tuple(values.shape) == (S, n):
+            strides = (n, 0)
+        elif tuple(values.shape) == (S, T, n):
+            strides = (T * n, n)
+        else:
+            raise ValueError(f"values: expected ({n},), ({S}, {n}) or ({S}, {T}, {n}), got {tuple(values.shape)}")
+    array = (C.c_int32 * n)(*idx)
+    check(_lib.load().sd_session_hold(pin_x0.data_ptr(), held.data_ptr(), _ptr(values), strides[0], strides[1], array, n, _ptr(mean), _ptr(std),
+                                      _ptr(r), S, B, T, J, 0 if values is None else 1, _stream()), "sd_session_hold")
+
+
+def session_hold_mask(mask: Tensor, held: Tensor, pin_rows: Optional[Tensor], J: int, draws: int = 1, robots=None) -> Tensor:
+    """One launch (``sd_session_hold_mask``) composes a tick's mask into ``mask`` (S * draws, T) int32: word (s * draws + g, t) =
+    held[b] | (t < pin_rows[b] ? all J bits : 0) for robot b of row s.  ``pin_rows`` None: no carried rows.  ``robots``: a (S,) int32
+    device tensor of robot indices (a session's validated subset), or None: all, S = B.  Reads device buffers only."""
+    _req(mask, "mask", torch.int32); _req(held, "held", torch.int32)
+    B = held.shape[0]
+    S = B if robots is None else robots.numel()
+    if mask.dim() != 2 or mask.shape[0] != S * draws or mask.device != held.device:
+        raise ValueError(f"mask: expected ({S * draws}, T) int32 on {held.device}, got {tuple(mask.shape)}")
+    if pin_rows is not None and (tuple(_req(pin_rows, "pin_rows", torch.int32).shape) != (B,) or pin_rows.device != held.device):
+        raise ValueError(f"pin_rows: expected ({B},) int32 on {held.device}")
+    if robots is not None:
+        _req(robots, "robots", torch.int32)
+    check(_lib.load().sd_session_hold_mask(mask.data_ptr(), held.data_ptr(), _ptr(pin_rows), _ptr(robots), S, B, mask.shape[1], int(J), int(draws),
+                                           _stream()), "sd_session_hold_mask")
+    return mask
 
 
 def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0,

@@ -32,6 +32,13 @@ chosen on the device, committed and returned instead of a single, possibly outly
     s = PolicySession(model, batch=2, draws=4, hyperparams=hp)
     traj, all_draws, index = s.step(return_draws=True)                      # (2, T, J), (2, 4, T, J), (2,): traj[b] == all_draws[b, index[b]]
 
+Held joints (``holds=True``): joints that another module owns - the head follows the ball tracker, a motor is switched off - are held at
+given angles INSIDE the rollout (``ops.ddim_sample(hold=...)``), so the free joints are sampled to fit what the robot will really do:
+
+    s = PolicySession(model, batch=3, holds=True, hyperparams=hp)
+    s.hold([0, 1], [0.3, -0.7], robots=[0, 2])                              # radians as published; until release(), through reset() too
+    traj = s.step()                                                         # traj[[0, 2]][:, :, [0, 1]] are those angles in every row
+
 There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
 
 from __future__ import annotations
@@ -80,13 +87,14 @@ class _GraphedTick:
 
     def _run(self) -> None:
         s = self.session
+        cond = s._cond()   # (holds: the mask's compose launch is part of the captured tick; it reads the session's static buffers only)
         self.ctx = s._context()
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
         if s.draws == 1:
-            self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, pin=s._pin())
+            self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond)
             return
         # G draws per robot on the shared context, and their medoid: the selection is part of the captured tick
-        self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, pin=s._pin(),
+        self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
                                    draws=s.draws)
         self.index, self.x = ops.select_medoid(self.all, s.draws)
 
@@ -98,7 +106,7 @@ class _GraphedTick:
         if int(self.status.item()) == 0:
             return self.x if s.draws == 1 else (self.x, self.all, self.index)
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
-        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, pin=s._pin(), draws=s.draws).contiguous()
+        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws).contiguous()
         if s.draws == 1:
             return x
         index, chosen = ops.select_medoid(x, s.draws)
@@ -108,7 +116,7 @@ class _GraphedTick:
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
-                 select: str = "medoid"):
+                 select: str = "medoid", holds: bool = False):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -121,11 +129,17 @@ class PolicySession:
         ``draws`` = G / ``select``: a tick samples G trajectories per robot from the once-encoded context and commits and returns the
         one ``select`` names - "medoid": the draw closest to all others (``ops.select_medoid``, on the device).  With ``carry`` all G
         draws share the seam and the carried rows come from the selected draw.  draws = 1 is the session without any of this, launch
-        for launch (no selection launch).  Not for a distilled decoder (one forward at t = 0 has no sampling to repeat)."""
+        for launch (no selection launch).  Not for a distilled decoder (one forward at t = 0 has no sampling to repeat).
+        ``holds=True``: the session can hold chosen joints of chosen robots at given angles inside the rollout (``hold`` / ``release``:
+        joints another module owns, a motor that is switched off) - the free joints are sampled to fit them.  It allocates the known-value
+        buffer, a word of held joints per robot and the tick's mask; every tick then composes the mask in one launch and runs the
+        rollout with ``ops.ddim_sample(hold=...)``, the carried rows of ``carry`` included.  Without the flag every launch is the one
+        of the session without any of this.  Not for a distilled decoder; J <= 32."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
         self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
+        self.holds = self.check_hold(holds, model.num_joints, self.distilled)                                              # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -186,6 +200,17 @@ class PolicySession:
             raise ValueError("draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
         return draws, select
 
+    @staticmethod
+    def check_hold(holds: bool = False, J: int = 1, distilled: bool = False) -> bool:
+        """``holds`` of a session with J joints, validated (no device needed): ValueError if it is set with a distilled decoder (there is
+        no rollout in which an element could be held) or with more than 32 joints (one mask word per row)."""
+        holds = bool(holds)
+        if holds and distilled:
+            raise ValueError("holds: a distilled decoder is one forward at t = 0 - there is no rollout in which a joint could be held")
+        if holds and not 1 <= int(J) <= 32:
+            raise ValueError(f"holds: one 32-bit mask word per row describes at most 32 joints, got J = {J}")
+        return holds
+
     @property
     def _carrying(self) -> bool:
         """The commit is the carrying one: anything but carry = 0 with the whole trajectory pushed."""
@@ -205,6 +230,55 @@ class PolicySession:
             known = known.unsqueeze(1).expand(S, G, self.T, self.J).reshape(S * G, self.T, self.J).contiguous()
             rows = rows.unsqueeze(1).expand(S, G).reshape(S * G).contiguous()
         return known, rows
+
+    def _hold(self, dev_idx=None):
+        """``hold`` of the tick's rollout in a session with ``holds``: ONE launch composes the mask - the robots' held joints in every row,
+        all joints in the carried rows - into the session's mask buffer (of the robots ``dev_idx``: its leading rows), and the known values
+        are the session's pin buffer: the carried rows and the held joints' values live side by side in it."""
+        G = self.draws
+        if dev_idx is None:
+            known, mask = self._pin_x0, self._mask
+        else:
+            known, mask = self._pin_x0[dev_idx.long()], self._mask[:dev_idx.numel() * G]
+        ops.session_hold_mask(mask, self._held, self._pin_rows if self.carry > 0 else None, self.J, G, robots=dev_idx)
+        if G > 1:   # every draw of a robot holds the robot's values
+            S = known.shape[0]
+            known = known.unsqueeze(1).expand(S, G, self.T, self.J).reshape(S * G, self.T, self.J).contiguous()
+        return known, mask
+
+    def _cond(self, dev_idx=None) -> dict:
+        """The conditioning arguments of the tick's rollout: ``hold=`` in a session with ``holds``, else the parent's ``pin=``."""
+        return {"hold": self._hold(dev_idx)} if self.holds else {"pin": self._pin(dev_idx)}
+
+    def hold(self, joints, values, robots=None) -> None:
+        """Holds the joints ``joints`` (indices) at ``values`` - radians as ``step`` publishes them; (n,), (S, n) or (S, T, n): the same
+        for every robot and row, per robot, or per robot and row of the horizon - for all robots or for ``robots`` (an index list).  One
+        launch normalises the values with the model's mean and std on the device, writes them into the session's known-value buffer
+        and sets the joints' bits in the robots' held words; from the next tick on the rollout holds these elements at every step and
+        returns them exactly.  A hold stays until ``release`` - through ``reset()`` too: a switched-off motor stays off.  With ``carry``
+        the values are constant over the horizon ((n,) or (S, n)): the carried rows share the buffer, and a joint that is newly held
+        between two ticks takes its new value in the carried rows as well (the seam stays exact on every other element)."""
+        if not self.holds:
+            raise RuntimeError("PolicySession.hold: the session was built without holds=True")
+        idx = ops.hold_joints(joints, self.J)
+        S, dev_idx = (self.B, None) if robots is None else self._subset(robots)[::2]
+        v = torch.as_tensor(values, dtype=torch.float32)
+        n = len(idx)
+        if tuple(v.shape) not in ((n,), (S, n), (S, self.T, n)):
+            raise ValueError(f"values: expected ({n},), ({S}, {n}) or ({S}, {self.T}, {n}) radians, got {tuple(v.shape)}")
+        if v.dim() == 3 and self.carry > 0:
+            raise ValueError("hold: with carry the held values are constant over the horizon - the carried rows overwrite the leading rows "
+                             "of the same buffer; pass (n,) or (S, n) values")
+        m = self.model
+        ops.session_hold(self._pin_x0, self._held, idx, v.to(self.device).contiguous(), m.mean, m.std, robots=dev_idx)
+
+    def release(self, joints=None, robots=None) -> None:
+        """Ends the hold of ``joints`` (None: all joints) for all robots or for ``robots``: one launch clears the bits."""
+        if not self.holds:
+            raise RuntimeError("PolicySession.release: the session was built without holds=True")
+        idx = list(range(self.J)) if joints is None else ops.hold_joints(joints, self.J)
+        dev_idx = None if robots is None else self._subset(robots)[2]
+        ops.session_hold(self._pin_x0, self._held, idx, None, None, None, robots=dev_idx)
 
     # ---- the plan: shapes from hyperparameters alone ---------------------------------------
     @staticmethod
@@ -285,8 +359,14 @@ class PolicySession:
         self._gen = torch.Generator(device=dev).manual_seed(self._seed)
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
         if self._carrying:   # the rows carried into the next tick (normalised space) and how many per robot: 0 until a tick has committed
-            self._pin_x0 = torch.zeros(B, self.T, self.J, dtype=torch.float32, device=dev)
             self._pin_rows = torch.zeros(B, dtype=torch.int32, device=dev)
+        if self.holds and getattr(self, "_held", None) is not None:
+            pass   # a hold survives reset(): the held words and the known values stay; the carried-row counts above are new
+        elif self._carrying or self.holds:
+            self._pin_x0 = torch.zeros(B, self.T, self.J, dtype=torch.float32, device=dev)
+            if self.holds:   # the held joints of every robot, and the tick's mask (one word per (trajectory, row))
+                self._held = torch.zeros(B, dtype=torch.int32, device=dev)
+                self._mask = torch.zeros(B * self.draws, self.T, dtype=torch.int32, device=dev)
         self._watched, self._graph = None, None
         self._key = self._weights_key()
         self._resettable = [(*r, None) for r in {id(r[0]): r for r in (*self._rings.values(), self._action)}.values()]
@@ -471,13 +551,14 @@ class PolicySession:
                     self._graph = _GraphedTick(self, x_T)
                 x = self._graph(x_T)
             else:
+                cond = {} if self.distilled else self._cond(dev_idx)   # (holds: the mask's compose launch opens the tick)
                 ctx = self._context(subset)
                 if self.distilled:   # one forward at t = 0 (ros.py:293-298)
                     x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
                 elif G == 1:
-                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx))
+                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond)
                 else:   # the context was encoded once per robot; its G draws share the folded planes
-                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, pin=self._pin(dev_idx), draws=G).contiguous()
+                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G).contiguous()
                     index, chosen = ops.select_medoid(every, G)
                     x = (chosen, every, index)
             if G == 1:

@@ -32,9 +32,15 @@ model, alternating blocks, medians, extremes and spread as above; no exit status
 the rollout on the pinned instantiations of the step kernels plus one entry launch, the carrying commit - against the session without
 carry, eager and with use_graph, four sessions on one model fed the same sensor rows in alternating blocks; medians, extremes and spread
 as above, the cost of the pin stated as the difference of the medians.  No exit status depends on it.
+
+--hold measures what held joints cost: PolicySession(holds=True) with two joints of every robot held - one more launch per tick that
+composes the mask, the rollout on the hold instantiations of the step kernels plus one entry launch - against the session without holds
+(the yardstick: launch for launch the tick as it was), eager and with use_graph, four sessions on one model fed the same sensor rows in
+alternating blocks; medians, extremes and spread as above, the cost stated as the difference of the medians.  No exit status depends on it.
 usage: python tools/bench_session.py [--quick] [--blocks 7] [--ticks 10] [--reset [--out profiles/session_partial_reset.jsonl]]
                                      [--raw 480x640 [--out profiles/session_raw_tick.jsonl]]
-                                     [--carry 4 [--out profiles/session_carry.jsonl]]"""
+                                     [--carry 4 [--out profiles/session_carry.jsonl]]
+                                     [--hold [--out profiles/session_hold.jsonl]]"""
 import argparse
 import json
 import os
@@ -313,6 +319,54 @@ def carry_leg(args):
             f.write("\n".join(lines) + "\n")
 
 
+HELD = ([0, 1], [0.3, -0.7])   # --hold: the head's two joints, say, at fixed angles
+
+
+def hold_leg(args):
+    """The session with two held joints against the session without holds, eager and replayed from a graph (--hold)."""
+    blocks = 3 if args.quick else args.blocks
+    lines = []
+    for name, over in CONFIGS.items():
+        params = {**BASE, **over}
+        torch.manual_seed(0)
+        model = cli.build_model(params).cuda().eval()
+        T, J = params["trajectory_prediction_length"], params["num_joints"]
+        for B in ((1, 16) if args.quick else (1, 16, 64)):
+            g = torch.Generator().manual_seed(7)
+            keys = [(graph, holds) for graph in (False, True) for holds in (False, True)]
+            sessions = {k: PolicySession(model, num_inference_steps=N_STEPS, batch=B, hyperparams=params, use_graph=k[0], holds=k[1]) for k in keys}
+            for k in keys:
+                if k[1]:
+                    sessions[k].hold(*HELD)
+            x_T = torch.randn(B, T, J, device="cuda", generator=torch.Generator(device="cuda").manual_seed(8))
+            news = [sensor_rows(params, B, g) for _ in range(args.ticks)]
+            for k in keys:                                                 # warm-up: one untimed block of every variant (and the capture)
+                block_ms(lambda new, x: session_tick(sessions[k], new, x), news, x_T)
+            times = {k: [] for k in keys}
+            for _ in range(blocks):                                        # alternating blocks: drift of the box hits all of them
+                for k in keys:
+                    times[k].append(block_ms(lambda new, x: session_tick(sessions[k], new, x), news, x_T))
+            col = lambda v: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+            spread = max(max(v) - min(v) for v in times.values())
+            med = {k: statistics.median(v) for k, v in times.items()}
+            rec = {"config": name, "B": B, "steps": N_STEPS, "new_frames_per_tick": NEW_FRAMES, "frame_size": [params["image_resolution"]] * 2,
+                   "memory_rows": PolicySession.plan(params)["memory_rows"], "blocks": blocks, "ticks_per_block": args.ticks,
+                   "held_joints": HELD[0],
+                   "eager": {"holds_off_tick_ms": col(times[(False, False)]), "holds_on_tick_ms": col(times[(False, True)]),
+                             "hold_cost_ms": round(med[(False, True)] - med[(False, False)], 3)},
+                   "use_graph": {"holds_off_tick_ms": col(times[(True, False)]), "holds_on_tick_ms": col(times[(True, True)]),
+                                 "hold_cost_ms": round(med[(True, True)] - med[(True, False)], 3)},
+                   "spread_ms": round(spread, 3)}
+            rec["hold_cost_beyond_spread"] = bool(max(abs(rec["eager"]["hold_cost_ms"]), abs(rec["use_graph"]["hold_cost_ms"])) > spread)
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+            del sessions
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="B = 1 and 16 only, fewer blocks")
@@ -323,7 +377,9 @@ def main():
                     "push_camera / push_orientation against preprocessed ones through push_image / push_rotation")
     ap.add_argument("--carry", type=int, default=None, metavar="K", help="measure PolicySession(carry=K) against the session without carry, "
                     "eager and with use_graph")
-    ap.add_argument("--out", type=str, default=None, help="--reset, --raw, --carry: also write the JSON lines to this file")
+    ap.add_argument("--hold", action="store_true", help="measure PolicySession(holds=True) with two held joints against the session without "
+                    "holds, eager and with use_graph")
+    ap.add_argument("--out", type=str, default=None, help="--reset, --raw, --carry, --hold: also write the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_session.py measures on the GPU: no device found")
@@ -333,6 +389,8 @@ def main():
         return raw_leg(args)
     if args.carry is not None:
         return carry_leg(args)
+    if args.hold:
+        return hold_leg(args)
     blocks = 3 if args.quick else args.blocks
     failed = False
     for name, over in CONFIGS.items():

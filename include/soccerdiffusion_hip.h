@@ -182,6 +182,11 @@ int sd_ddim_add_noise(const float *x0, const float *noise, const int64_t *t, con
  * sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev are the four fp32 scalars. */
 int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t, float sqrt_1m_a_t,
                  float sqrt_a_prev, float sqrt_1m_a_prev, long n, void *stream);
+/* One step of the second-order multistep solver (sd_ddim_sample_multistep) for a caller that evaluates the denoiser itself:
+ *   x0 = (x - coef4[1] eps) / coef4[0];  x_prev = coef4[2] x0 + coef4[3] eps + w * (hist - x0);  hist = x0
+ * coef4: the step's four fp32 scalars in HOST memory, in sd_ddim_step's order.  w == 0: hist is not read.  In place on x is allowed; hist
+ * (n floats, device) must alias none of the others (SD_E_BADARG). */
+int sd_multistep_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, long n, void *stream);
 
 /* Normalizer.normalize (inverse = 0: (x - mean) / std) and .denormalize (inverse = 1:
  * x * std + mean), per joint — soccer_diffusion/dataset/pytorch.py:410-414.  n = rows * J. */
@@ -292,6 +297,27 @@ int sd_ddim_sample_draws(const sd_denoiser_weights *w, const float *ctx, const f
 int sd_ddim_sample_hold(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                         float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                         const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, void *stream);
+/* sd_ddim_sample_hold with the second-order multistep solver (DPM-Solver++ 2M in its x0 form) in place of first-order DDIM: no extra
+ * denoiser evaluation, one fused multiply-add per element.
+ *   after step i: x0_i = (x - c1[i] eps) / c0[i];  x = c2[i] x0_i + c3[i] eps + msw[i] * (x0_{i-1} - x0_i);  history = x0_i
+ *   msw (n_steps floats in HOST memory; ops.multistep_weights): msw[0] must be 0 - there is no history yet - and the step to a_prev = 1
+ *   has msw = 0 as well.  All msw == 0 is the DDIM rollout.
+ *   history (B,T,J) floats in device memory, the caller's (sd_workspace_floats is unchanged).  It is read only by steps with msw[i] != 0
+ *   and written by every step, the last one included, so it needs no clearing: a replayed graph cannot see the rollout before, and a stale
+ *   NaN in it is harmless.  On return it holds the x0 of the last step.
+ *   hold_x0, hold_noise, hold_mask: all three (sd_ddim_sample_hold's meaning; J <= 32) or all NULL (nothing held, any J).  A held element
+ *   gets the hold's value; its history entry is the model's x0 all the same.  Pinned leading rows are a mask.
+ * Kernels: on the trajectory routes the multistep instantiations of the step kernels (one per family and tile count, the mask an optional
+ * pointer and `draws` a runtime argument): the lane that stores the update of (token, 4 joints) requests its history values where the
+ * hold requests its mask word, only when msw[i] != 0.  One launch per step: no fused rollout form and no mode-4 twin (max_mode = 4 runs
+ * the mode-3 kernels).  On the row-panel and chain routes each step returns eps and one elementwise launch (sd_multistep_step's kernel)
+ * updates x and the history; the hold's launch follows it.  The route is that of the pinned call of the same shape.
+ * SD_E_BADARG (nothing launched): msw or history NULL, msw[0] != 0, a partial hold triple, history aliasing x or a hold buffer,
+ * hold_noise == x, draws < 1, B % draws != 0, or a mask with J > 32. */
+int sd_ddim_sample_multistep(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                             float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                             const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw,
+                             float *history, void *stream);
 /* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
 int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
 

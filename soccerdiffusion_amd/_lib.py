@@ -137,6 +137,8 @@ SIGNATURES = {
     "sd_ddim_sample_pin": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sd_ddim_sample_draws": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_ddim_sample_hold": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_ddim_sample_multistep": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_float_p, C.c_void_p, C.c_void_p]),
+    "sd_multistep_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_float_p, C.c_float, C.c_long, C.c_void_p]),
     "sd_sampler_route_draws": (C.c_int, [C.c_int] * 9),
     "sd_select_medoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_bn_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int]),

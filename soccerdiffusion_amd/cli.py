@@ -3,10 +3,10 @@ the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [-o report.json]   (evaluation.py)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -521,6 +521,8 @@ def cmd_evaluate(args) -> int:
     split = args.val_split or recorded.get("split", "tail")
     if not args.all and fraction is None:
         raise SystemExit("evaluate: give --val-fraction F, or --all for every window (the checkpoint records no split)")
+    if args.solver != "ddim" and params.get("distilled_decoder", False):
+        raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
     model = build_model(params).to(device)
     model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
     model.eval()
@@ -528,7 +530,7 @@ def cmd_evaluate(args) -> int:
     idx = torch.arange(source.n) if args.all else holdout_split(source.n, fraction, args.seed, split)[1]
     report = evaluate(model, source, idx, steps=args.steps, draws=args.draws, grid=args.grid, seed=args.seed,
                       max_mode=3 if args.max_mode is None else args.max_mode, timesteps=_timesteps(args.timesteps) if args.timesteps else None,
-                      distilled=bool(params.get("distilled_decoder", False)))
+                      distilled=bool(params.get("distilled_decoder", False)), solver=args.solver)
     line = json.dumps(report)
     print(line)
     if args.output:
@@ -559,6 +561,8 @@ def cmd_sample(args) -> int:
     if G > 1 and params.get("distilled_decoder", False):
         raise SystemExit("--draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
     x_T = torch.randn(B * G, params["trajectory_prediction_length"], params["num_joints"], device=device, generator=gen)
+    if args.solver != "ddim" and params.get("distilled_decoder", False):
+        raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
     hold = None
     if args.hold:   # the joints held at every row of every trajectory, in the space of the file's trajectories (x * std + mean)
         if params.get("distilled_decoder", False):
@@ -579,12 +583,14 @@ def cmd_sample(args) -> int:
         if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         else:
-            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold)   # G draws for each of the B contexts, which are encoded once
+            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
             medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
     out = args.output if world == 1 else f"{args.output}.rank{rank}"
     saved = {"trajectories": traj.cpu(), "noise": x_T.cpu(), "steps": args.steps, "indices": mine}
+    if args.solver != "ddim":
+        saved["solver"] = args.solver
     if hold is not None:
         saved["hold"] = dict(args.hold)   # {joint: the value it was held at}
     if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
@@ -671,7 +677,7 @@ def cmd_rollout(args) -> int:
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
-                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold))
+                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver)
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -758,6 +764,8 @@ def build_parser() -> argparse.ArgumentParser:
     sa = sub.add_parser("sample", help="sample trajectories from a checkpoint (flags of the reference's plot.py)")
     sa.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
     sa.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
+    sa.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
+                    "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
     sa.add_argument("--num_samples", type=int, default=10, help="Number of samples to generate")
     sa.add_argument("--output", "-o", type=str, default="samples.pt", help="Where to save the sampled trajectories")
     sa.add_argument("--ema", action="store_true", help="sample from the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
@@ -789,6 +797,8 @@ def build_parser() -> argparse.ArgumentParser:
     ev = sub.add_parser("evaluate", help="held-out validation loss and sampled-trajectory errors of a checkpoint, as one JSON line")
     ev.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
     ev.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
+    ev.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
+                    "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
     ev.add_argument("--draws", type=int, default=1, metavar="G", help="draws per window (1 .. 64): rmse of the first, the medoid and the best")
     ev.add_argument("--grid", type=int, default=8, metavar="K", help="timesteps of the loss grid, t_k = (2k + 1) 1000 // (2K)")
     ev.add_argument("--timesteps", type=str, default=None, metavar="a,b,...", help="the loss grid's timesteps (0 .. 999) instead of --grid")
@@ -812,6 +822,8 @@ def build_parser() -> argparse.ArgumentParser:
     ro.add_argument("--ticks", type=int, default=10, metavar="K", help="number of control ticks")
     ro.add_argument("--output", "-o", type=str, default="rollout.pt", help="Where to save the K published trajectories")
     ro.add_argument("--steps", type=int, default=30, help="Number of denoising steps per tick")
+    ro.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
+                    "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
     ro.add_argument("--episode-ticks", type=str, default=None, metavar="E[,E...]", help="episode length in ticks, robot b's is E[b %% len(E)]: "
                     "after its last tick that robot alone is reset and goes on; the output gains 'resets' (K, N)")
     ro.add_argument("--raw", action="store_true", help="the stream carries what the sensors deliver - xyzw quaternions and uint8 camera frames - "

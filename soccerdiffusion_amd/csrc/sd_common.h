@@ -322,6 +322,15 @@ struct HoldArgs {
     const int *mask;           // [B][T] in device memory
 };
 
+// The history term of the second-order multistep solver (sd_ddim_sample_multistep): after the DDIM update of step i the storing lane adds
+// w * (hist - x0), hist = the model's x0 of step i - 1 at the same element, and leaves this step's x0 in hist.  w == 0 (step 0, and the step
+// to a_prev = 1): hist is not read - the update is DDIM's.  A struct of its own beside StepArgs and HoldArgs: their layouts do not move.
+// The multistep twins take a HoldArgs whose mask may be NULL (nothing held; x0 and noise are then never read).
+struct MultistepArgs {
+    float *hist;   // [B][T][J]: read (w != 0) and written by the lane that stores x of the same element
+    float w;
+};
+
 // One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
 // (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
 struct StepReq {
@@ -334,6 +343,7 @@ struct StepReq {
     const PinArgs *pin;  // or NULL; needs coef
     int draws;           // trajectories per context: trajectory b reads context b / draws (1: its own)
     const HoldArgs *hold = nullptr;   // or NULL; needs coef, excludes pin (one hold kernel serves every draws >= 1)
+    const MultistepArgs *ms = nullptr;   // or NULL; needs coef, excludes pin: the multistep twins (hold then optional, its mask too)
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

@@ -2513,6 +2513,21 @@ __global__ void ddim_hold_kernel(float *__restrict__ x, HoldArgs hold, float ck,
         if (((unsigned)hold.mask[row] >> j) & 1u) x[i] = ck * hold.x0[i] + cn * hold.noise[i];
     }
 }
+// One step of the second-order multistep solver (MultistepArgs, sd_common.h), element by element: the DDIM update in ddim_update's form
+// (sd_traj.h) plus w * (hist - x0), hist = the x0 of the step before; this step's x0 goes back into hist.  w == 0 - a uniform branch on the
+// kernel argument - never reads hist: the update is DDIM's and the buffer needs no clearing.  x_next may be x.  The row-panel and chain
+// routes launch it behind a step that returned eps without updating x; sd_multistep_step is the loop form's step.
+__global__ void ddim_multistep_kernel(const float *__restrict__ eps, const float *x, float *x_next, float *hist, float c0, float c1, float c2,
+                                      float c3, float w, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float e = eps[i];
+        const float x0 = __builtin_fmaf(-c1, e, x[i]) / c0;
+        float xn = __builtin_fmaf(c2, x0, c3 * e);
+        if (w != 0.f) xn = __builtin_fmaf(w, hist[i] - x0, xn);
+        x_next[i] = xn;
+        hist[i] = x0;
+    }
+}
 
 
 // ======================================================================================
@@ -2758,7 +2773,7 @@ static int f16_prepare(const sd_denoiser_weights *w, const Scratch &s, int B, in
 
 // one denoiser step + DDIM update on the fp16x3 kernels (step index i selects the step-token blocks)
 static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scratch &s, int B, int T, int Mc, int i, int n_steps,
-                             const float *coef, hipStream_t st, float *eps = nullptr, bool pinned = false) {
+                             const float *coef, hipStream_t st, float *eps = nullptr, bool pinned = false, bool no_update = false) {
     const int d = w->d, heads = w->heads, L = w->L, Mk = Mc + 1;
     const long R = (long)B * T;
     const size_t blk = (size_t)32 * d, cbstride = (size_t)B * 64;
@@ -2794,7 +2809,7 @@ static int decoder_stack_f16(const sd_denoiser_weights *w, float *x, const Scrat
         if (last) {
             fa.g.fo_w = w->out_w;
             fa.g.fo_b = w->out_b;
-            fa.g.x_io = x;
+            fa.g.x_io = no_update ? nullptr : x;   // (a multistep rollout: eps only, ddim_multistep_kernel updates x; the caller passes pinned)
             fa.g.eps = eps;
             fa.g.c0 = coef[0]; fa.g.c1 = coef[1]; fa.g.c2 = coef[2]; fa.g.c3 = coef[3];
             fa.next_head = merge && i + 1 < n_steps;
@@ -2975,11 +2990,14 @@ struct TrajCall {
     // pin: the pinned instantiations (the caller's plan is a three-product one)
     // (draws > 1: the shared-context instantiations; with per_traj the context index b / draws and the step block step_map[b] are separate)
     // hold: the hold instantiations (held elements; never beside a pin)
-    StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr) const {
-        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold};
+    // ms: the multistep instantiations (the second-order solver's history term; a hold beside it is optional, never a pin)
+    StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr,
+                const MultistepArgs *ms = nullptr) const {
+        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms};
     }
-    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) const {
-        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold);
+    int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr,
+             const MultistepArgs *ms = nullptr) const {
+        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms);
         return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
     }
     // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
@@ -3014,10 +3032,22 @@ static int ddim_hold(float *x, const HoldArgs &hold, float ck, float cn, int B, 
     return 0;
 }
 
+// x <- the multistep update of (eps, x, hist) with step i's coefficients, hist <- x0 (ddim_multistep_kernel)
+static int ddim_multistep(const float *eps, const float *x, float *x_next, float *hist, const float *coef4, float w, long n, hipStream_t st) {
+    SD_LAUNCH(ddim_multistep_kernel, dim3(grid_for(n)), dim3(256), 0, st, eps, x, x_next, hist, coef4[0], coef4[1], coef4[2], coef4[3], w, n);
+    SD_CHECK_LAUNCH("ddim_multistep_kernel");
+    return 0;
+}
+// The second-order multistep solver of a rollout (sd_ddim_sample_multistep): w[i] of step i (host) and the history array (device)
+struct MultistepCall {
+    const float *w;
+    float *hist;
+};
+
 // the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once), or - the plan's rollout_fused -
 // one launch of the rollout kernel per TRAJ_ROLLOUT_MAX_STEPS steps
 static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace, float *eps_trace,
-                        int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) {
+                        int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr, const MultistepCall *msc = nullptr) {
     const long n = (long)c.B * c.T * c.w->J;
     int rc;
     if (status && (rc = zero_async(status, sizeof(int32_t), c.st))) return rc;
@@ -3027,7 +3057,7 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     if (pin && (rc = ddim_pin(x, *pin, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
     if (hold && (rc = ddim_hold(x, *hold, coef[0], coef[1], c.B, c.T, c.w->J, c.st))) return rc;
     if (c.plan.rollout_fused) {
-        if (trace || eps_trace || pin || hold || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
+        if (trace || eps_trace || pin || hold || msc || c.generic()) return fail(SD_E_BADARG, "traj_rollout: the plan's rollout kernel returns nothing per step and has no pin");
         for (int i0 = 0; i0 < c.n_tok; i0 += TRAJ_ROLLOUT_MAX_STEPS) {
             const int nn = c.n_tok - i0 < TRAJ_ROLLOUT_MAX_STEPS ? c.n_tok - i0 : TRAJ_ROLLOUT_MAX_STEPS;
             if ((rc = c.steps_fused(x, i0, nn, coef, status))) return rc;
@@ -3037,7 +3067,8 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold))) return rc;
+        const MultistepArgs ms{msc ? msc->hist : nullptr, msc ? msc->w[i] : 0.f};   // (no fused rollout form: one launch per step, like a hold)
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
@@ -3046,7 +3077,7 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
 // the rollout on the row-panel kernels (sampler modes 0 - 2)
 static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const SamplerPlan &plan, const float *ctx, const float *step_tokens,
                          const float *coef, float *x, float *trace, float *eps_trace, int B, int T, int Mc, int n_steps, int32_t *status, hipStream_t st,
-                         const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr) {
+                         const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr, const MultistepCall *msc = nullptr) {
     const int d = w->d, R = B * T, L = w->L;
     int rc;
     // once per rollout: K/V of the context rows (placed as rows 0..Mc-1 of each trajectory's
@@ -3101,15 +3132,22 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
     for (int i = 0; i < n_steps; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
+        // Multistep: the step returns eps and leaves x alone (no fused DDIM site, and no head merged into the last layer's launch); the
+        // elementwise kernel behind it updates x and the history.  Without an eps_trace the prediction goes to the q | k | v region, which
+        // nothing reads between the last layer's self-attention and the next step's head (R * 3 d floats >= R * J).
+        if (msc && !eps_i) eps_i = s.qkv;
+        float *x_up = msc ? nullptr : x;
         // this step's token row -> row Mc of every trajectory, all layers in one launch
         if (f16) {
-            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i, pin != nullptr || hold != nullptr))) return rc;
+            if ((rc = decoder_stack_f16(w, x, s, B, T, Mc, i, n_steps, coef + 4 * i, st, eps_i, pin != nullptr || hold != nullptr || msc != nullptr,
+                                        msc != nullptr)))
+                return rc;
         } else if (fold) {
             SD_LAUNCH(fold_place_kernel, dim3(grid_for((long)B * 4 * 2 * d), L), dim3(256), 0, st, s.gvstep + (size_t)i * 4 * 2 * d,
                       s.cstep + (size_t)i * 4, (long)gvsstride, (long)cssstride, s.gv, s.cb, (long)gvstride, (long)cbstride, B, Mc,
                       2 * d);
             SD_CHECK_LAUNCH("fold_place_kernel");
-            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int) { return (const float *)nullptr; }, TailArgs{eps_i, x, coef + 4 * i}, st,
+            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int) { return (const float *)nullptr; }, TailArgs{eps_i, x_up, coef + 4 * i}, st,
                                FoldArgs{s.gv, s.cb, gvstride, cbstride});
             if (rc) return rc;
         } else {
@@ -3117,9 +3155,10 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
                       s.kv, (long)kvstride, B, Mc, Mk, 2 * d, 1);
             SD_CHECK_LAUNCH("kv_place_kernel");
             const float *kvbase = s.kv;
-            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x, coef + 4 * i}, st);
+            rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x_up, coef + 4 * i}, st);
             if (rc) return rc;
         }
+        if (msc && (rc = ddim_multistep(eps_i, x, x, msc->hist, coef + 4 * i, msc->w[i], n, st))) return rc;
         // these routes are many launches per step already: the pinned rows are one more, behind the fused DDIM sites
         if (pin && (rc = ddim_pin(x, *pin, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
         if (hold && (rc = ddim_hold(x, *hold, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
@@ -3142,7 +3181,7 @@ __global__ void ctx_expand_kernel(const float *__restrict__ src, float *__restri
 static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
                            float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode, void *stream,
                            const float *pin_x0, const float *pin_noise, const int32_t *pin_rows, bool pin_required, int draws,
-                           const HoldArgs *hold = nullptr) {
+                           const HoldArgs *hold = nullptr, const MultistepCall *msc = nullptr) {
     const int n_pin = (pin_x0 ? 1 : 0) + (pin_noise ? 1 : 0) + (pin_rows ? 1 : 0);
     if (pin_required ? n_pin != 3 : (n_pin != 0 && n_pin != 3))
         return fail(SD_E_BADARG, pin_required ? "sd_ddim_sample_pin: pin_x0, pin_noise and pin_rows must be given"
@@ -3152,7 +3191,7 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
                                               : "sd_ddim_sample_draws: pin_noise must not alias x (x is overwritten by the first step)");
     const PinArgs pin_args{pin_x0, pin_noise, pin_rows};
     const PinArgs *pin = n_pin ? &pin_args : nullptr;
-    if ((pin || hold) && max_mode == 4) max_mode = 3;
+    if ((pin || hold || msc) && max_mode == 4) max_mode = 3;
     if (Mc <= 0) draws = 1;   // no context rows: nothing to share
     int rc = check_denoiser(w);
     if (rc) return rc;
@@ -3166,9 +3205,9 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
     if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_ddim_sample: horizon exceeds positional table");
     hipStream_t st = (hipStream_t)stream;
     const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, n_steps, B);
-    const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | ((pin || hold) ? CALL_PIN : 0);   // the plan treats a hold as a pinned call
+    const int call = ((trace || eps_trace) ? CALL_TRACE : 0) | ((pin || hold || msc) ? CALL_PIN : 0);   // the plan treats a hold and a multistep call as a pinned call
     const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, call, draws);
-    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st, draws}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin, hold);
+    if (plan.traj()) return traj_rollout(TrajCall{plan, w, s, B, T, Mc, n_steps, st, draws}, ctx, step_tokens, coef, x, trace, eps_trace, status, pin, hold, msc);
     if (draws > 1) {
         // No sharing on the row-panel routes: the B / draws context rows are expanded to B in the workspace (the K | V region, which these
         // routes fill only after the context has been projected) and the kernels of old run on the copy.
@@ -3177,7 +3216,7 @@ static int ddim_sample_any(const sd_denoiser_weights *w, const float *ctx, const
         SD_CHECK_LAUNCH("ctx_expand_kernel");
         ctx = s.kv;
     }
-    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin, hold);
+    return panel_rollout(w, s, plan, ctx, step_tokens, coef, x, trace, eps_trace, B, T, Mc, n_steps, status, st, pin, hold, msc);
 }
 
 extern "C" int sd_ddim_sample_eps(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens,
@@ -3217,6 +3256,28 @@ extern "C" int sd_ddim_sample_hold(const sd_denoiser_weights *w, const float *ct
     const HoldArgs hold{hold_x0, hold_noise, hold_mask};
     return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
                            false, draws, &hold);
+}
+
+// The second-order multistep solver (DPM-Solver++ 2M in its x0 form) on every route: after step i, x gets the DDIM update plus
+// msw[i] * (x0 of step i - 1 - x0 of step i); `history` (B*T*J floats, device, the caller's) carries x0 from launch to launch and is never
+// read where msw[i] == 0, so it needs no clearing.  The hold triple: all three or none (none: nothing held, no J <= 32 limit).
+extern "C" int sd_ddim_sample_multistep(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                        float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                        int max_mode, const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws,
+                                        const float *msw, float *history, void *stream) {
+    const int n_hold = (hold_x0 ? 1 : 0) + (hold_noise ? 1 : 0) + (hold_mask ? 1 : 0);
+    if (n_hold != 0 && n_hold != 3) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: hold_x0, hold_noise and hold_mask must be given together");
+    if (!msw || !history || n_steps <= 0) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: msw (n_steps floats) and history must be given");
+    if (msw[0] != 0.f) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: msw[0] must be 0 (the first step has no history)");
+    if (history == x || (n_hold && (history == hold_x0 || history == hold_noise || (const void *)history == (const void *)hold_mask)))
+        return fail(SD_E_BADARG, "sd_ddim_sample_multistep: history must alias neither x nor the hold buffers");
+    if (n_hold && hold_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: hold_noise must not alias x (x is overwritten by the first step)");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: draws must be >= 1 and divide B");
+    if (n_hold && w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: one 32-bit mask word per row: J must be <= 32 with a mask");
+    const HoldArgs hold{hold_x0, hold_noise, hold_mask};
+    const MultistepCall msc{msw, history};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, draws, n_hold ? &hold : nullptr, &msc);
 }
 
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)
@@ -3340,6 +3401,14 @@ extern "C" int sd_ddim_add_noise(const float *x0, const float *noise, const int6
                        noise, t, acp, out, B, per_sample);
     SD_CHECK_LAUNCH("add_noise_kernel");
     return 0;
+}
+
+// One step of the second-order multistep solver on (eps, x): x_prev = the DDIM update with coef4 (host: c0, c1, c2, c3 of this step, as
+// ddim_coefficients lays them out) + w * (hist - x0); hist = x0 afterwards.  w == 0: hist is not read.  x_prev may be x.
+extern "C" int sd_multistep_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, long n, void *stream) {
+    if (!eps || !x || !x_prev || !hist || !coef4 || n <= 0) return fail(SD_E_BADARG, "sd_multistep_step: bad argument");
+    if (hist == x || hist == x_prev || hist == eps) return fail(SD_E_BADARG, "sd_multistep_step: hist must alias neither eps, x nor x_prev");
+    return ddim_multistep(eps, x, x_prev, hist, coef4, w, n, (hipStream_t)stream);
 }
 
 extern "C" int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t, float sqrt_1m_a_t,

@@ -1452,10 +1452,17 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // PIN == 2, HOLD: the element form (HoldArgs, sd_common.h; sd_ddim_sample_hold) - the lane that stores the update of (tok, j0 .. j0 + 3) loads
 // the token's mask word once, ahead of the barrier in front of the fc_out GEMM, and takes bits j0 .. j0 + 3 of it: none set - the unpinned
 // store, x0 and noise not loaded; all four - the pinned store; else both, selected element by element.  No barrier and no LDS of its own.
+// PIN == 3, MS: the second-order multistep twin (MultistepArgs, sd_common.h; sd_ddim_sample_multistep) - a hold whose mask is optional
+// (hold.mask NULL: nothing held) plus the history term: the storing lane requests its four history values where the hold requests its mask
+// word - only when ms.w != 0, a wave-uniform branch on the kernel argument - computes x0 as ddim_update does, stores
+// fma(w, hist - x0, ddim) and leaves x0 in hist (every step, the last one too).  A held element gets the hold's value; its history entry is
+// the model's x0 all the same.  The same lane reads and writes an element's history in consecutive launches: no barrier, no LDS.
 template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
-                                                 int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{}) {
+                                                 int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{},
+                                                 const MultistepArgs &ms = MultistepArgs{}) {
     constexpr bool HOLD = PIN == 2;
+    constexpr bool MS = PIN == 3;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
@@ -1589,6 +1596,18 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         if constexpr (HOLD) {
             if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) hold_m = (unsigned)hold.mask[traj * a.T + (c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6)];
         }
+        f32x4 hpre[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};   // MS: this lane's history values (w != 0, rows of whole quads)
+        if constexpr (MS) {
+            if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) {
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+                if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+                if (ms.w != 0.f && !(J & 3)) {
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        if (16 * n + 4 * c.g < J) hpre[n] = *reinterpret_cast<const f32x4 *>(ms.hist + (traj * a.T + tok) * J + 16 * n + 4 * c.g);
+                }
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
         if (c.w < NTT) {
@@ -1629,6 +1648,17 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                                 continue;
                             }
                         }
+                        if constexpr (MS) {
+                            if (a.update_x) {
+                                const float x0 = __builtin_fmaf(-a.c1, e, a.x[at + r]) / a.c0;
+                                float xn = __builtin_fmaf(a.c2, x0, a.c3 * e);
+                                if (ms.w != 0.f) xn = __builtin_fmaf(ms.w, ms.hist[at + r] - x0, xn);
+                                if ((hold_m >> (j0 + r)) & 1u) xn = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                                a.x[at + r] = xn;
+                                ms.hist[at + r] = x0;
+                            }
+                            continue;
+                        }
                         if constexpr (HOLD) {
                             if (a.update_x && ((hold_m >> (j0 + r)) & 1u)) {
                                 a.x[at + r] = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
@@ -1654,6 +1684,31 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                         *reinterpret_cast<f32x4 *>(a.x + at) = a.c2 * k + a.c3 * nz;
                         continue;
                     }
+                }
+                if constexpr (MS) {
+                    if (a.update_x) {
+                        const unsigned bits = (hold_m >> j0) & 15u;
+                        const f32x4 xv = *reinterpret_cast<const f32x4 *>(a.x + at);
+                        f32x4 x0, xn;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {   // ddim_update's form
+                            x0[r] = __builtin_fmaf(-a.c1, e[r], xv[r]) / a.c0;
+                            xn[r] = __builtin_fmaf(a.c2, x0[r], a.c3 * e[r]);
+                        }
+                        if (ms.w != 0.f) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) xn[r] = __builtin_fmaf(ms.w, hpre[n][r] - x0[r], xn[r]);
+                        }
+                        if (bits) {
+                            const f32x4 k = *reinterpret_cast<const f32x4 *>(hold.x0 + at), nz = *reinterpret_cast<const f32x4 *>(hold.noise + at);
+                            const f32x4 hv = a.c2 * k + a.c3 * nz;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) xn[r] = ((bits >> r) & 1u) ? hv[r] : xn[r];
+                        }
+                        *reinterpret_cast<f32x4 *>(a.x + at) = xn;
+                        *reinterpret_cast<f32x4 *>(ms.hist + at) = x0;
+                    }
+                    continue;
                 }
                 if constexpr (HOLD) {
                     const unsigned bits = (hold_m >> j0) & 15u;
@@ -1750,6 +1805,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_hold_kernel(StepArgs a,
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_hold_kernel(StepArgs a, HoldArgs hold, int draws) {
     TJ<NTT, true>::template step_body<true, 2, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold);
+}
+// The multistep twins (sd_ddim_sample_multistep; instantiated in sd_traj_ms.hip): the hold twins plus the history term of the second-order
+// solver.  The mask is optional (hold.mask NULL) and `draws` a runtime argument, so one kernel per tile count serves plain, pinned (a
+// leading-rows mask), held and shared-context calls.
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_ms_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, int draws) {
+    TJ<NTT, true>::template step_body<false, 3, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_ms_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, int draws) {
+    TJ<NTT, true>::template step_body<true, 3, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms);
 }
 struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
     RolloutArgs ra;

@@ -22,5 +22,6 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
 // r.pin (needs r.coef): the pinned instantiation - rows below pin->rows[b] become c2 * x0 + c3 * noise in the same launch.
 // r.draws > 1 (not per_traj): trajectory b reads the planes of context b / draws - traj_step_generic_draws_kernel, pinned or not
 // r.hold (needs r.coef, excludes r.pin): held elements (HoldArgs) - traj_step_generic_hold_kernel, whatever r.draws
+// r.ms (needs r.coef, excludes r.pin; r.hold optional): the multistep twin (MultistepArgs) - traj_step_generic_ms_kernel, whatever r.draws
 int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipStream_t st, const int *map = nullptr);
 #endif

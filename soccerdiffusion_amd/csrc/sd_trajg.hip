@@ -818,9 +818,14 @@ struct TG {
     // runtime option (pin.rows NULL: nothing pinned)
     // PIN == 2, HOLD: the element form (HoldArgs, sd_common.h; sd_ddim_sample_hold) - the storing lane loads its token's mask word once,
     // ahead of the barrier in front of the fc_out GEMM, and tests bit j per element; x0 and noise are loaded for held elements only
+    // PIN == 3, MS: the multistep twin (MultistepArgs, sd_common.h; sd_ddim_sample_multistep) - a hold whose mask is optional (NULL: nothing
+    // held) plus the history term: where ms.w != 0 (a wave-uniform branch on the kernel argument) the storing lane requests its history
+    // values beside the mask word, and stores fma(w, hist - x0, ddim); it leaves x0 in hist on every step
     template <int PIN = 0, bool DRAWS = false>
-    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{}) {
+    static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{},
+                                                     const MultistepArgs &ms = MultistepArgs{}) {
         constexpr bool HOLD = PIN == 2;
+        constexpr bool MS = PIN == 3;
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -907,6 +912,20 @@ struct TG {
             if constexpr (HOLD) {
                 if (c.w < NTT && (c.w < NTT - 1 || c.okl)) hold_m = (unsigned)hold.mask[traj * a.T + (c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl)];
             }
+            float hpre[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // MS: this lane's history values (w != 0)
+            if constexpr (MS) {
+                if (c.w < NTT && (c.w < NTT - 1 || c.okl)) {
+                    const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
+                    if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+                    if (ms.w != 0.f) {
+#pragma unroll
+                        for (int n = 0; n < 2; ++n)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (16 * n + 4 * c.g + r < J) hpre[n][r] = ms.hist[(traj * a.T + tok) * J + 16 * n + 4 * c.g + r];
+                    }
+                }
+            }
             __syncthreads();
             if (c.w < NTT) {
                 const char *X = c.smem;
@@ -941,6 +960,17 @@ struct TG {
                                 continue;
                             }
                         }
+                        if constexpr (MS) {
+                            if (a.update_x) {   // ddim_update's form (sd_traj.h), then the history term
+                                const float x0 = __builtin_fmaf(-a.c1, e, a.x[at + r]) / a.c0;
+                                float xn = __builtin_fmaf(a.c2, x0, a.c3 * e);
+                                if (ms.w != 0.f) xn = __builtin_fmaf(ms.w, hpre[n][r] - x0, xn);
+                                if ((hold_m >> (j0 + r)) & 1u) xn = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                                a.x[at + r] = xn;
+                                ms.hist[at + r] = x0;
+                            }
+                            continue;
+                        }
                         if constexpr (HOLD) {
                             if (a.update_x && ((hold_m >> (j0 + r)) & 1u)) {
                                 a.x[at + r] = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
@@ -972,6 +1002,11 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_draws_kernel(StepA
 template <int D, int NTT>
 __global__ __launch_bounds__(NTHREADS) void traj_step_generic_hold_kernel(StepArgs a, HoldArgs hold, int draws) {
     TG<D, NTT>::template step_body<2, true>(a, PinArgs{}, draws, hold);
+}
+// the multistep twin (sd_ddim_sample_multistep): the hold twin, its mask optional, plus the second-order solver's history term
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_ms_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, int draws) {
+    TG<D, NTT>::template step_body<3, true>(a, PinArgs{}, draws, hold, ms);
 }
 
 }   // namespace tg
@@ -1044,6 +1079,10 @@ StepPinFn step_pin_fn(int d, int ntt) {
 typedef void (*StepHoldFn)(tg::StepArgs, HoldArgs, int);
 StepHoldFn step_hold_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepHoldFn { return tg::traj_step_generic_hold_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepMsFn)(tg::StepArgs, HoldArgs, MultistepArgs, int);
+StepMsFn step_ms_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepMsFn { return tg::traj_step_generic_ms_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
@@ -1162,6 +1201,8 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     if (r.hold && (!r.coef || r.pin))
         return fail(SD_E_BADARG, "traj_step_generic_hold_kernel: held elements need the DDIM coefficients and exclude a pin");
+    if (r.ms && (!r.coef || r.pin || !r.ms->hist))
+        return fail(SD_E_BADARG, "traj_step_generic_ms_kernel: the multistep term needs the DDIM coefficients and a history buffer, and excludes a pin");
     tg::StepArgs a{};
     a.x = r.x;
     a.eps_out = r.eps;
@@ -1194,6 +1235,11 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     constexpr int MAX_LDS = 163840;
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.ms) {   // the multistep twin: held or not (a hold's mask may be NULL), whatever the group size
+        static DevFlag ms_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_ms_fn(d, ntt), "traj_step_generic_ms_kernel", ms_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, r.draws);
+    }
     if (r.hold) {   // held elements: the hold twin, whatever the group size
         static DevFlag hold_attr_set[3][8];   // [hidden_dim][ntt]
         return launch_step_kernel(step_hold_fn(d, ntt), "traj_step_generic_hold_kernel", hold_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,

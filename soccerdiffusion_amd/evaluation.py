@@ -71,7 +71,8 @@ def _f64(t) -> torch.Tensor:
     return torch.as_tensor(t).detach().to("cpu", torch.float64)
 
 
-def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool) -> dict:
+def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool,
+                    solver: str = "ddim") -> dict:
     """The report from the per-batch marginals, in fp64 on the host.  A part holds, for its C windows: ``err`` (C, G), ``row_err`` (C, G, T),
     ``joint_err`` (C, G, J) (mean squared errors in radians^2: ``ops.trajectory_errors``), ``best`` (C,) and ``medoid`` (C,) draw indices,
     ``spread`` (C, G) the mean squared distance of every draw to the medoid, and ``loss`` (C, K) or None (a distilled decoder predicts no
@@ -97,7 +98,7 @@ def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]]
         rmse_by_row=[math.sqrt(float(v)) for v in row[at, med].mean(0)],
         rmse_by_joint=[math.sqrt(float(v)) for v in joint[at, med].mean(0)],
         spread=math.sqrt(float(spread.mean())),
-        steps=int(steps), draws=int(draws), max_mode=int(max_mode), angular=bool(angular))
+        steps=int(steps), draws=int(draws), max_mode=int(max_mode), angular=bool(angular), solver=str(solver))
     return report
 
 
@@ -108,11 +109,13 @@ def _has_context(model) -> bool:
 
 @torch.no_grad()
 def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int = 8, batch: int = 64, seed: int = 0, max_mode: int = 3,
-             angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None) -> dict:
+             angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None, solver: str = "ddim") -> dict:
     """The report (a plain dict of Python floats, ints and lists) of ``model`` on the windows ``idx`` of ``source`` (``cli.DataSource``), in
     batches of ``batch`` windows from ``source.batch``.  The model must be in ``eval()``.  Per batch: the context is encoded once; the loss
     grid runs at ``timesteps`` (default ``default_timesteps(grid)``); ``draws`` = G trajectories per window are sampled with ``steps`` DDIM
-    steps (``model.sample(draws=G)``); ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
+    steps (``model.sample(draws=G)``; ``solver="multistep"``: with the second-order multistep solver on the same ``steps`` timesteps - the
+    instrument for "10 steps against 30" then also says what the solver buys; the report names it in its ``solver`` entry);
+    ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
     student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None.
     A model without context encoders (decoder pretraining) gets ten random context rows per window from the same generator.
     ``keep``: a list that receives, per batch, the tensors the marginals were computed from (tests).
@@ -126,6 +129,8 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     ts = check_timesteps(timesteps) if timesteps is not None else default_timesteps(grid)
     if steps < 1 or batch < 1:
         raise ValueError("evaluate: steps and batch must be positive")
+    if solver not in ("ddim", "multistep") or (distilled and solver != "ddim"):
+        raise ValueError(f"evaluate: solver must be 'ddim' or 'multistep' (a distilled decoder has no rollout: 'ddim'), got {solver!r}")
     idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
     if idx.numel() == 0:
         raise ValueError("evaluate: no windows to evaluate")
@@ -152,7 +157,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         if distilled:
             x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
         else:
-            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G)
+            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver)
         x = x.contiguous()
         part["medoid"], chosen = ops.select_medoid(x, G)
         part["err"], part["row_err"], part["joint_err"], part["best"] = ops.trajectory_errors(x, target, model.mean, model.std, draws=G, angular=angular)
@@ -162,4 +167,4 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         if keep is not None:
             keep.append({"x": x, "target": target, "medoid_x": chosen, **({} if distilled else {"eps": eps, "noise": noise}), **part})
         parts.append({k: (None if v is None else v.cpu()) for k, v in part.items()})
-    return assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular)
+    return assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular, solver=solver)

@@ -205,7 +205,7 @@ class End2EndDiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample(self, context: Sequence[torch.Tensor], x_T: torch.Tensor, num_inference_steps: int,
                return_trace: bool = False, alphas_cumprod: Optional[torch.Tensor] = None, use_graph: bool = False,
-               with_dropout: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None):
+               with_dropout: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, solver: str = "ddim"):
         """The reference's denoising loop (plot.py:122-131 / distill.py:179-189 / ros.py:301-310)
         as one native call: n x (denoiser forward + DDIM update) with the context K/V cached.
         ``use_graph`` replays the rollout from a hipGraph captured for this (B, T, M, n) shape.
@@ -222,7 +222,15 @@ class End2EndDiffusionTransformer(nn.Module):
         ``hold = (known, mask)``: the element form of ``pin`` - element (b, t, j) is held to ``known`` where ``mask`` (a bool tensor
         (B, T, J), (T, J) or (J,), or the (B, T) int32 words of ``ops.hold_mask``) is set: joints another module owns, keyframes.  A captured
         graph serves every mask and ``known``.  Not together with ``pin`` (``ops.hold_mask(rows=...)`` composes them), not with
-        ``with_dropout``."""
+        ``with_dropout``.
+        ``solver``: "ddim" (default: every call is the call without this argument) or "multistep" - the second-order multistep solver
+        (DPM-Solver++ 2M in its x0 form, ``ops.multistep_weights``) on the same timesteps: no extra denoiser evaluation, one history term
+        per element inside the step launch; meant for fewer steps.  It composes with ``pin``, ``hold``, ``draws``, ``use_graph`` and
+        ``return_trace``.  Not with ``with_dropout``."""
+        if solver not in ("ddim", "multistep"):
+            raise ValueError(f"sample: solver must be 'ddim' or 'multistep', got {solver!r}")
+        if solver != "ddim" and with_dropout:
+            raise ValueError("sample: solver is a feature of the native rollout; with_dropout steps through forward_with_context")
         if hold is not None and with_dropout:
             raise ValueError("sample: hold is a feature of the native rollout; with_dropout steps through forward_with_context")
         if hold is not None and pin is not None:
@@ -246,6 +254,7 @@ class End2EndDiffusionTransformer(nn.Module):
         ts = ops.ddim_timesteps(num_inference_steps)
         acp = ops.alphas_cumprod() if alphas_cumprod is None else alphas_cumprod
         coef = ops.ddim_coefficients(ts, acp, num_inference_steps)
+        msw = ops.multistep_weights(ts, acp, num_inference_steps) if solver == "multistep" else None
         ctx = torch.cat(list(context), dim=1).contiguous() if len(context) else None
         packed = self.diffusion_action_generator.packed()
         if use_graph and not return_trace:
@@ -254,12 +263,12 @@ class End2EndDiffusionTransformer(nn.Module):
             cap = ops.sampler_cap(packed, max_mode)   # as ops.ddim_sample_guarded
             # the weights are read through pointers at replay (their addresses are the key); the step-token table is captured by value
             token = derived.source_key(self.step_encoding.token)
-            key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(), token, cap, pin is not None, draws, hold is not None)
+            key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(), token, cap, pin is not None, draws, hold is not None, solver)
             cache = _model_cache(self, "graphs")
             if token is None or key not in cache:
                 cache.clear()  # one shape at a time: a graph pins its workspace
                 cache[key] = ops.GraphedSampler(packed, B, T, Mc, self.step_encoding.table(ts, x_T.device), coef, max_mode=cap,
-                                                pin=pin is not None, draws=draws, hold=hold is not None)
+                                                pin=pin is not None, draws=draws, hold=hold is not None, multistep=msw)
             out = cache[key](ctx, x_T, pin, hold)
             word = int(cache[key].status.item())
             if word == 0:
@@ -268,4 +277,4 @@ class End2EndDiffusionTransformer(nn.Module):
                 packed.sampler_cap = 3   # pinned before the eager rerun: it starts on mode 3, not on mode 4 again
             # range guard tripped (ops.ddim_sample_guarded): fall through to the guarded eager path
         tokens = self.step_encoding.table(ts, x_T.device)
-        return ops.ddim_sample_guarded(packed, ctx, tokens, coef, x_T.contiguous(), trace=return_trace, max_mode=max_mode, pin=pin, draws=draws, hold=hold)
+        return ops.ddim_sample_guarded(packed, ctx, tokens, coef, x_T.contiguous(), trace=return_trace, max_mode=max_mode, pin=pin, draws=draws, hold=hold, multistep=msw)

@@ -96,6 +96,72 @@ def ddim_coefficients(timesteps: Sequence[int], acp: Tensor, num_inference_steps
     return out
 
 
+def multistep_weights(timesteps: Sequence[int], acp: Tensor, num_inference_steps: int,
+                      num_train_timesteps: int = NUM_TRAIN_TIMESTEPS) -> np.ndarray:
+    """The history weights of the second-order multistep solver (DPM-Solver++ 2M in its x0 form) on the grid of ``ddim_coefficients``
+    (the same ``prev = t - ratio`` convention): after the DDIM update of step i, ``x += w[i] * (x0[i - 1] - x0[i])`` with
+    ``w[i] = sqrt(a_prev) * expm1(-h[i]) * h[i] / (2 h[i - 1])``, ``h[i] = lambda(a_prev) - lambda(a_t)``, ``lambda(a) = 0.5 log(a / (1 - a))``.
+    lambda and h are Python float64 from the fp32 ``acp`` table, the weight is rounded once to fp32.  ``w[0] = 0`` (no history yet) and
+    ``w[i] = 0`` wherever ``a_prev = 1`` (lambda is infinite there: that step is first order).  All zeros is DDIM itself.
+    ValueError unless the timesteps are the consecutive leading grid, ``t[i] == t[i - 1] - ratio``: the history term is defined only there."""
+    acp = acp.detach().cpu().float()
+    ratio = num_train_timesteps // num_inference_steps
+    ts = [int(t) for t in timesteps]
+    for i in range(1, len(ts)):
+        if ts[i] != ts[i - 1] - ratio:
+            raise ValueError(f"multistep_weights: timesteps must be the consecutive leading grid (t[i] == t[i - 1] - {ratio}); "
+                             f"got t[{i - 1}] = {ts[i - 1]}, t[{i}] = {ts[i]}")
+
+    def lam(a: float) -> float:
+        return 0.5 * math.log(a / (1.0 - a))
+
+    out = np.zeros(len(ts), dtype=np.float32)
+    h_prev = None
+    for i, t in enumerate(ts):
+        prev = t - ratio
+        if prev < 0:   # a_prev = 1
+            h_prev = None
+            continue
+        a_t, a_p = float(acp[t]), float(acp[prev])
+        h = lam(a_p) - lam(a_t)
+        if i > 0 and h_prev is not None:
+            out[i] = np.float32(math.sqrt(a_p) * math.expm1(-h) * h / (2.0 * h_prev))
+        h_prev = h
+    return out
+
+
+def _multistep_req(w, n_steps: int) -> np.ndarray:
+    """``multistep`` of a sampler call, validated before any launch: (n_steps,) finite fp32 weights with w[0] == 0."""
+    try:
+        w = np.ascontiguousarray(w, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"multistep: expected ({n_steps},) weights (ops.multistep_weights), got {w!r}") from None
+    if w.shape != (n_steps,):
+        raise ValueError(f"multistep: expected ({n_steps},) weights (ops.multistep_weights), got shape {w.shape}")
+    if not np.isfinite(w).all():
+        raise ValueError("multistep: the weights must be finite")
+    if w[0] != 0:
+        raise ValueError(f"multistep: w[0] must be 0 (the first step has no history), got {float(w[0])}")
+    return w
+
+
+def multistep_step(eps: Tensor, x: Tensor, hist: Tensor, coef4, w: float) -> Tensor:
+    """One step of the second-order multistep solver for a caller that evaluates the denoiser itself (``sd_multistep_step``):
+    returns the DDIM update of (eps, x) with ``coef4`` plus ``w * (hist - x0)`` and leaves this step's x0 in ``hist`` (updated in place;
+    not read when ``w == 0``)."""
+    lib = _lib.load()
+    _req(eps, "eps"); _req(x, "x"); _req(hist, "hist")
+    if eps.shape != x.shape or hist.shape != x.shape:
+        raise ValueError("multistep_step: eps, x and hist must have one shape")
+    out = torch.empty_like(x)
+    c = np.ascontiguousarray([float(v) for v in coef4], dtype=np.float32)
+    if c.shape != (4,):
+        raise ValueError("multistep_step: coef4 must hold 4 scalars")
+    check(lib.sd_multistep_step(eps.data_ptr(), x.data_ptr(), out.data_ptr(), hist.data_ptr(), c.ctypes.data_as(_lib.c_float_p), float(w),
+                                x.numel(), _stream()), "sd_multistep_step")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # weight descriptors
 # --------------------------------------------------------------------------------------
@@ -400,12 +466,23 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
 
 
 def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
-                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None):
+                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None, multistep=None):
     """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
     ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
     ``sd_ddim_sample_pin``, launch for launch; ``hold = (known, noise, mask words)``: ``sd_ddim_sample_hold`` (never beside a pin).
+    ``multistep = (w (n_steps,) fp32 on the host, history (B, T, J) on the device)``: ``sd_ddim_sample_multistep``, with ``hold`` or
+    without (never beside a pin: the callers fold it into a mask).
     Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
     B, T, _ = x.shape
+    if multistep is not None:
+        msw, hist = multistep
+        check(_lib.load().sd_ddim_sample_multistep(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                                   x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1],
+                                                   len(coef), _ptr(status), int(max_mode), *[_ptr(t) for t in (hold or (None, None, None))], draws,
+                                                   msw.ctypes.data_as(_lib.c_float_p), hist.data_ptr(), _stream()),
+              "sd_ddim_sample_multistep")
+        out = (x,) + tuple(t for t in (tr, et) if t is not None)
+        return out if len(out) > 1 else x
     if hold is not None:
         check(_lib.load().sd_ddim_sample_hold(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
                                               x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1], len(coef),
@@ -431,13 +508,20 @@ class GraphedSampler:
     serves every pinning, none (rows = 0) included.  ``draws`` > 1: the context buffer holds B / draws contexts, trajectory b reads
     context b // draws.  ``hold=True`` captures the call with held elements (``sd_ddim_sample_hold``) on static known, noise and mask
     buffers: a replay copies the call's ``hold=(known, mask)`` into them, so one graph serves every mask, the empty one included; not
-    together with ``pin`` (compose them through ``hold_mask(rows=...)``).  (One native call for all of them: ``_ddim_sample_native``.)"""
+    together with ``pin`` (compose them through ``hold_mask(rows=...)``).  ``multistep=w`` (``multistep_weights``) captures the
+    second-order multistep rollout (``sd_ddim_sample_multistep``) on a static history buffer, which no replay needs cleared: its first
+    step does not read it.  With ``pin=True`` the pin is folded into a mask (J <= 32): the graph is captured on hold buffers and a replay's
+    ``pin=(known, rows)`` becomes ``hold_mask(rows=rows)``.  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
-                 draws: int = 1, hold: bool = False):
+                 draws: int = 1, hold: bool = False, multistep=None):
         dev = step_tokens.device
         if pin and hold:
             raise ValueError("GraphedSampler: pin and hold exclude each other - compose them through ops.hold_mask(rows=...)")
+        self.multistep = None if multistep is None else _multistep_req(multistep, len(coef))
+        self.pin_as_hold = bool(pin) and self.multistep is not None
+        if self.pin_as_hold:
+            pin, hold = False, True
         self.draws = _draws_req(draws, B, None)
         self.packed, self.coef = packed, np.ascontiguousarray(coef, dtype=np.float32)
         self.tokens = step_tokens.contiguous()
@@ -453,6 +537,7 @@ class GraphedSampler:
             if packed.J > 32:
                 raise ValueError(f"hold: one 32-bit mask word per row describes at most 32 joints, got J = {packed.J}")
             self.hold = (torch.zeros_like(self.x), torch.zeros_like(self.x), torch.zeros(B, T, dtype=torch.int32, device=dev))
+        self.hist = torch.empty_like(self.x) if self.multistep is not None else None
         lib = _lib.load()
         self.ws = torch.empty(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, len(self.coef)),
                               dtype=torch.float32, device=dev)
@@ -468,11 +553,17 @@ class GraphedSampler:
 
     def _run(self):
         _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws,
-                            self.hold)
+                            self.hold, None if self.multistep is None else (self.multistep, self.hist))
 
     def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None, hold=None) -> Tensor:
         """Copies the inputs into the captured buffers, replays, and returns the captured x buffer itself
         (overwritten by the next replay)."""
+        if self.pin_as_hold:   # a multistep graph captured with pin=True: the pin as a mask
+            if pin is None or hold is not None:
+                raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
+            known, rows = _pin_req(pin, *self.x.shape, self.x.device)
+            B, T, J = self.x.shape
+            pin, hold = None, (known, hold_mask(torch.zeros(J, dtype=torch.bool, device=self.x.device), B, T, J, self.x.device, rows=rows))
         if (pin is None) != (self.pin is None):
             raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
         if (hold is None) != (self.hold is None):
@@ -501,7 +592,7 @@ class GraphedSampler:
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False, pin=None, draws: int = 1, hold=None):
+                eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -520,10 +611,16 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     ``hold = (known, mask)``: the element form of the pin (``sd_ddim_sample_hold``) - ``mask`` as ``hold_mask`` takes it: element (b, t, j)
     is held to ``known`` iff its bit is set, with the pin's coefficients and the pin's exactness at the last step; every other element is
     sampled to fit.  J <= 32.  ``pin`` and ``hold`` together raise ValueError: ``hold_mask(mask, ..., rows=rows)`` composes them.  The
-    trajectory routes run one hold kernel per step for any ``draws``."""
+    trajectory routes run one hold kernel per step for any ``draws``.
+    ``multistep = w`` (``multistep_weights``: (n_steps,) fp32, w[0] == 0): the second-order multistep solver (``sd_ddim_sample_multistep``) -
+    after the DDIM update of step i, ``x += w[i] * (x0[i - 1] - x0[i])``; no extra denoiser evaluation, and all zeros is DDIM.  It composes
+    with everything above; a ``pin`` is folded into ``hold_mask(rows=rows)`` for this call (J <= 32).  The trajectory routes run one
+    multistep kernel per step (no fused rollout form)."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
     if pin is not None and hold is not None:
         raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
+    if multistep is not None:   # (likewise)
+        multistep = _multistep_req(multistep, step_tokens.shape[0])
     lib = _lib.load()
     _req(x_T, "x_T"); _req(step_tokens, "step_tokens")
     B, T, J = x_T.shape
@@ -541,6 +638,8 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         _req(status, "status", torch.int32)
     if pin is not None:
         pin = _pin_req(pin, B, T, J, x_T.device)
+        if multistep is not None:   # the multistep kernels take a mask: the pin as its leading full rows
+            hold, pin = (pin[0], hold_mask(torch.zeros(J, dtype=torch.bool, device=x_T.device), B, T, J, x_T.device, rows=pin[1])), None
     if hold is not None:
         hold = _hold_req(hold, B, T, J, x_T.device)
     x = x_T if inplace else x_T.clone()
@@ -551,7 +650,9 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         pin = (pin[0], x_T.clone() if inplace else x_T, pin[1])
     if hold is not None:   # (known, noise, mask words), the noise as the pin's
         hold = (hold[0], x_T.clone() if inplace else x_T, hold[1])
-    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold)
+    if multistep is not None:   # (weights, history): the history is written before it is read - no clearing
+        multistep = (multistep, torch.empty_like(x))
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep)
 
 
 def default_sampler_cap() -> int:
@@ -574,14 +675,15 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
-                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None):
+                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, multistep=None):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin``, ``hold`` and ``draws``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context rows: correct, not shared)."""
+    ``pin``, ``hold``, ``draws`` and ``multistep``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
+    rows: correct, not shared; a repeat restarts from ``x_T``, so the multistep history needs nothing more)."""
     import warnings
 
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
@@ -591,9 +693,11 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         pin = _pin_req(pin, *x_T.shape, x_T.device)
     if hold is not None:
         hold = _hold_req(hold, *x_T.shape, x_T.device)
+    if multistep is not None:
+        multistep = _multistep_req(multistep, step_tokens.shape[0])
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
-    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold)
+    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold, multistep=multistep)
     word = int(status.item())
     if word == 0:
         return out
@@ -603,7 +707,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         # of the checkpoint, so later calls with these weights start there.
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
-            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold)
+            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold, multistep=multistep)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -612,7 +716,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     if mode >= 2:
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold)
+        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold, multistep=multistep)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")

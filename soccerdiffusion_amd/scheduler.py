@@ -62,3 +62,43 @@ class DDIMScheduler:
         t = int(timestep)
         coef = ops.ddim_coefficients([t], self.alphas_cumprod, self.num_inference_steps, self._table_len)[0]
         return SimpleNamespace(prev_sample=ops.ddim_step(model_output.contiguous(), sample.contiguous(), coef))
+
+
+class MultistepScheduler(DDIMScheduler):
+    """The second-order multistep solver (DPM-Solver++ 2M in its x0 form) for the reference's loop form: the constructor,
+    ``set_timesteps``, ``timesteps`` and ``add_noise`` of ``DDIMScheduler``; ``step(model_output, t, sample).prev_sample`` is the DDIM
+    update plus ``w * (x0 of the step before - x0 of this step)`` (``ops.multistep_weights``, ``sd_multistep_step``: one launch).  The
+    previous x0 stays on the device, in a buffer of the sample's shape; ``set_timesteps`` clears the history, so every rollout starts
+    first order, and the steps must then be taken in the order of ``timesteps``.
+
+    It runs on THIS project's leading grid (``ops.ddim_timesteps``: t - ratio, the last step to alpha = 1), not on a grid of its own, so
+    that its step counts compare with ``DDIMScheduler``'s: n steps here evaluate the denoiser at the same n timesteps.  Parity with
+    diffusers' ``DPMSolverMultistepScheduler`` is UNPINNED for the reason ``DDIMScheduler``'s is - diffusers is not available offline
+     - and that class spaces its timesteps differently by default."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._weights, self._hist, self._next = None, None, 0
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        super().set_timesteps(num_inference_steps, device)
+        self._grid = ops.ddim_timesteps(num_inference_steps, self._table_len)
+        self._weights = ops.multistep_weights(self._grid, self.alphas_cumprod, num_inference_steps, self._table_len)
+        self._hist, self._next = None, 0
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps before step")
+        t = int(timestep)
+        i = self._next
+        if i >= len(self._grid) or self._grid[i] != t:
+            if t != self._grid[0]:
+                raise ValueError(f"MultistepScheduler.step: the history term needs the steps in the order of timesteps; expected "
+                                 f"t = {self._grid[i] if i < len(self._grid) else self._grid[0]}, got {t}")
+            i = 0   # a new rollout on the same grid: no history yet
+        coef = ops.ddim_coefficients([t], self.alphas_cumprod, self.num_inference_steps, self._table_len)[0]
+        if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
+            self._hist = torch.empty_like(sample, memory_format=torch.contiguous_format)
+        out = ops.multistep_step(model_output.contiguous(), sample.contiguous(), self._hist, coef, float(self._weights[i]))
+        self._next = i + 1
+        return SimpleNamespace(prev_sample=out)

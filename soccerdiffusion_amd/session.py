@@ -72,6 +72,7 @@ class _GraphedTick:
         self.packed = m.diffusion_action_generator.packed()
         self.tokens = m.step_encoding.table(ts, dev)
         self.coef = ops.ddim_coefficients(ts, ops.alphas_cumprod(), session.n_steps)
+        self.msw = ops.multistep_weights(ts, ops.alphas_cumprod(), session.n_steps) if session.solver == "multistep" else None
         self.cap = ops.sampler_cap(self.packed, 3)
         self.noise = x_T.clone()
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -91,11 +92,12 @@ class _GraphedTick:
         self.ctx = s._context()
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
         if s.draws == 1:
-            self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond)
+            self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
+                                     multistep=self.msw)
             return
         # G draws per robot on the shared context, and their medoid: the selection is part of the captured tick
         self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
-                                   draws=s.draws)
+                                   draws=s.draws, multistep=self.msw)
         self.index, self.x = ops.select_medoid(self.all, s.draws)
 
     def __call__(self, x_T: torch.Tensor):
@@ -106,7 +108,7 @@ class _GraphedTick:
         if int(self.status.item()) == 0:
             return self.x if s.draws == 1 else (self.x, self.all, self.index)
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
-        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws).contiguous()
+        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver).contiguous()
         if s.draws == 1:
             return x
         index, chosen = ops.select_medoid(x, s.draws)
@@ -116,7 +118,7 @@ class _GraphedTick:
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
-                 select: str = "medoid", holds: bool = False):
+                 select: str = "medoid", holds: bool = False, solver: str = "ddim"):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -134,12 +136,17 @@ class PolicySession:
         joints another module owns, a motor that is switched off) - the free joints are sampled to fit them.  It allocates the known-value
         buffer, a word of held joints per robot and the tick's mask; every tick then composes the mask in one launch and runs the
         rollout with ``ops.ddim_sample(hold=...)``, the carried rows of ``carry`` included.  Without the flag every launch is the one
-        of the session without any of this.  Not for a distilled decoder; J <= 32."""
+        of the session without any of this.  Not for a distilled decoder; J <= 32.
+        ``solver``: "ddim" (default: the session without this argument, launch for launch) or "multistep" - every tick's rollout runs the
+        second-order multistep solver (``model.sample(solver="multistep")``) on the same ``num_inference_steps`` timesteps; meant for fewer
+        steps per tick.  It composes with ``carry`` (the carried rows become the mask's leading rows: the seam stays bit-exact; J <= 32),
+        ``holds``, ``draws``, ``robots=`` and ``use_graph``.  Not for a distilled decoder."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
         self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
         self.holds = self.check_hold(holds, model.num_joints, self.distilled)                                              # (likewise)
+        self.solver = self.check_solver(solver, model.num_joints, self.carry, self.distilled)                              # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -210,6 +217,18 @@ class PolicySession:
         if holds and not 1 <= int(J) <= 32:
             raise ValueError(f"holds: one 32-bit mask word per row describes at most 32 joints, got J = {J}")
         return holds
+
+    @staticmethod
+    def check_solver(solver: str = "ddim", J: int = 1, carry: int = 0, distilled: bool = False) -> str:
+        """``solver`` of a session, validated (no device needed): ValueError unless it is "ddim" or "multistep"; for "multistep" with a
+        distilled decoder (no rollout), or with ``carry`` and J > 32 (the carried rows travel as a 32-bit mask word per row)."""
+        if solver not in ("ddim", "multistep"):
+            raise ValueError(f"solver: expected 'ddim' or 'multistep', got {solver!r}")
+        if solver == "multistep" and distilled:
+            raise ValueError("solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
+        if solver == "multistep" and carry > 0 and not 1 <= int(J) <= 32:
+            raise ValueError(f"solver: with carry the multistep rollout pins rows through a 32-bit mask word per row, got J = {J}")
+        return solver
 
     @property
     def _carrying(self) -> bool:
@@ -556,9 +575,9 @@ class PolicySession:
                 if self.distilled:   # one forward at t = 0 (ros.py:293-298)
                     x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
                 elif G == 1:
-                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond)
+                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver)
                 else:   # the context was encoded once per robot; its G draws share the folded planes
-                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G).contiguous()
+                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver).contiguous()
                     index, chosen = ops.select_medoid(every, G)
                     x = (chosen, every, index)
             if G == 1:

@@ -187,6 +187,14 @@ int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t
  * coef4: the step's four fp32 scalars in HOST memory, in sd_ddim_step's order.  w == 0: hist is not read.  In place on x is allowed; hist
  * (n floats, device) must alias none of the others (SD_E_BADARG). */
 int sd_multistep_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, long n, void *stream);
+/* One step of sd_ddim_sample_limits for a caller that evaluates the denoiser itself (element i belongs to joint i % J):
+ *   x0 = (x - coef4[1] eps) / coef4[0];  x0c = x0 < lo[j] ? lo[j] : (x0 > hi[j] ? hi[j] : x0)       (compares: a NaN stays NaN)
+ *   e' = reproject && x0c != x0 ? (x - coef4[0] x0c) / coef4[1] : eps;  x_prev = coef4[2] x0c + coef4[3] e' + w * (hist - x0c);  hist = x0c
+ * hist NULL: first-order DDIM, nothing written (w must be 0).  lo, hi: 32 floats each in device memory (ops.joint_limits); coef4 in HOST
+ * memory.  In place on x is allowed.  SD_E_BADARG (nothing launched): a NULL operand, J outside 1 .. 32, n % J != 0, w != 0 without hist,
+ * hist aliasing eps, x or x_prev. */
+int sd_ddim_limit_step(const float *eps, const float *x, float *x_prev, float *hist_or_null, const float *coef4, float w, const float *lo,
+                       const float *hi, int reproject, long n, int J, void *stream);
 
 /* Normalizer.normalize (inverse = 0: (x - mean) / std) and .denormalize (inverse = 1:
  * x * std + mean), per joint — soccer_diffusion/dataset/pytorch.py:410-414.  n = rows * J. */
@@ -318,6 +326,34 @@ int sd_ddim_sample_multistep(const sd_denoiser_weights *w, const float *ctx, con
                              float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                              const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw,
                              float *history, void *stream);
+/* sd_ddim_sample_multistep with per-joint limits on the predicted clean trajectory (diffusers' clip_sample / clip_sample_range, per joint),
+ * inside the step launch.  All in normalised space; with (c0, c1, c2, c3) of step i, e the denoiser's prediction and w = msw[i] (0: DDIM):
+ *   x0  = (x - c1 e) / c0                        (fma(-c1, e, x) / c0, the multistep form)
+ *   x0c = x0 < lo[j] ? lo[j] : (x0 > hi[j] ? hi[j] : x0)
+ *   e'  = e                                      reproject == 0 (diffusers' default, use_clipped_model_output=False)
+ *       = (x0c == x0) ? e : (x - c0 x0c) / c1    reproject != 0
+ *   x   = fma(c2, x0c, c3 e') + w (history - x0c);   history = x0c
+ *   lo, hi: 32 floats each in device memory, lo[j] <= hi[j] for j < J, [J, 32) padded with -inf / +inf (ops.joint_limits); -inf / +inf: no
+ *   limit on that side.  They are read on the device at every step, so a captured graph follows a rewrite in place.  J <= 32.
+ *   The clamp is two compares and selects: a NaN x0 stays NaN (no fmin / fmax / med3, which would publish a limit for a non-finite
+ *   prediction).  The last step (c2 = 1, c3 = 0) therefore leaves every free element bitwise inside [lo[j], hi[j]]; with all limits
+ *   infinite every step is bitwise sd_ddim_sample_multistep's, with all msw == 0 besides bitwise the DDIM call's; with reproject an element
+ *   that is not clamped takes e itself.  There is no count of clamped elements: a clamped element's x0 of the next steps sits within
+ *   rounding of its limit, so two correct implementations would disagree on it - after the last step a clamped element equals its limit.
+ *   msw, history: both (sd_ddim_sample_multistep's meaning; the history holds the clamped x0), or msw NULL: first-order DDIM, and history
+ *   may be NULL too (given, it still receives the clamped x0 of every step).
+ *   hold_x0, hold_noise, hold_mask: all three or all NULL.  A held element gets the hold's value whatever the limits say; its history entry
+ *   is x0c as everything else's.  eps_trace stays the network's e for every element.
+ * Kernels: on the trajectory routes the limits instantiations of the step kernels (sd_traj_lim.hip; traj_step_generic_lim_kernel), the
+ * multistep twins plus the clamp in the lane that already holds x0: one launch per step, no fused rollout form, no mode-4 twin (max_mode = 4
+ * runs the mode-3 kernels).  On the row-panel and chain routes each step returns eps and ddim_limit_step_kernel updates x (and the history);
+ * the hold's launch follows it.  The route is that of the pinned call of the same shape.
+ * SD_E_BADARG (nothing launched): lo or hi NULL, a partial hold triple, msw without history, msw[0] != 0, history
+ * aliasing x or a hold buffer, hold_noise == x, draws < 1, B % draws != 0, J > 32. */
+int sd_ddim_sample_limits(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                          float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                          const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw, float *history,
+                          const float *lo, const float *hi, int reproject, void *stream);
 /* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
 int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
 
@@ -853,6 +889,14 @@ int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int 
  *   sd_session_hold_mask: ONE launch composes a tick's mask, mask[(s * draws + g)][t] = held[b] | (t < pin_rows[b] ? all J bits : 0) for
  *     robot b = robots[s] (NULL: s) and every draw g; mask (S * draws, T) int32; pin_rows NULL: no carried rows.  It reads device buffers
  *     only: inside a captured tick it serves every later hold, release and reset.
+ * Joint limits (a session that hands sd_ddim_sample_limits its lo / hi):
+ *   sd_session_limits: ONE launch of 64 threads writes the 32-float device arrays lo_n / hi_n from limits in radians AS PUBLISHED (lo_rad,
+ *     hi_rad: J floats each in HOST memory, read before the launch and passed by value; -inf / +inf: no limit; real numbers, no modular
+ *     arithmetic).  A bound begins as the inverse of the commit's expression, ((v + pi) - mean[j]) / std[j], and moves inward by nextafterf
+ *     (or by a quarter ulp of the commit's largest intermediate, in normalised units, where that is more; 64 tries at most) until both roundings of the commit's expression - fma(x, std, mean) - pi and
+ *     (x * std + mean) - pi - give a value inside [lo, hi]: the commit is monotonic in x (std > 0), so a trajectory sampled under
+ *     lo_n / hi_n is published inside the radians bit for bit with no clamp in the commit.  Slots [J, 32) get -inf / +inf.  A range
+ *     narrower than the commit's resolution collapses to its upper bound.  SD_E_BADARG also for lo_rad[j] > hi_rad[j] or a NaN.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
 #define SD_SESSION_MAX_RESET_RINGS 5
@@ -892,6 +936,7 @@ int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, const uint8_
                            int32_t *pin_rows, int B, void *stream);
 int sd_session_hold(float *pin_x0, int32_t *held, const float *values, int64_t stride_robot, int64_t stride_row, const int32_t *joints, int n,
                     const float *mean, const float *stdv, const int32_t *robots, int S, int B, int T, int J, int set, void *stream);
+int sd_session_limits(float *lo_n, float *hi_n, const float *lo_rad, const float *hi_rad, const float *mean, const float *stdv, int J, void *stream);
 int sd_session_hold_mask(int32_t *mask, const int32_t *held, const int32_t *pin_rows, const int32_t *robots, int S, int B, int T, int J,
                          int draws, void *stream);
 

@@ -3,10 +3,10 @@ the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [-o report.json]   (evaluation.py)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -523,6 +523,7 @@ def cmd_evaluate(args) -> int:
         raise SystemExit("evaluate: give --val-fraction F, or --all for every window (the checkpoint records no split)")
     if args.solver != "ddim" and params.get("distilled_decoder", False):
         raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
+    limits = _limits_arg(args, params)   # in the space of the target trajectories (x * std + mean), as sample --hold
     model = build_model(params).to(device)
     model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
     model.eval()
@@ -530,7 +531,8 @@ def cmd_evaluate(args) -> int:
     idx = torch.arange(source.n) if args.all else holdout_split(source.n, fraction, args.seed, split)[1]
     report = evaluate(model, source, idx, steps=args.steps, draws=args.draws, grid=args.grid, seed=args.seed,
                       max_mode=3 if args.max_mode is None else args.max_mode, timesteps=_timesteps(args.timesteps) if args.timesteps else None,
-                      distilled=bool(params.get("distilled_decoder", False)), solver=args.solver)
+                      distilled=bool(params.get("distilled_decoder", False)), solver=args.solver, limits=limits,
+                      reproject=args.reproject)
     line = json.dumps(report)
     print(line)
     if args.output:
@@ -573,6 +575,11 @@ def cmd_sample(args) -> int:
         known[:, :, joints] = (torch.tensor(values, device=device) - mean[joints]) / std[joints]
         mask[joints] = True
         hold = (known, mask)
+    limits = _limits_arg(args, params)   # in the space of the file's trajectories (x * std + mean), as --hold
+    if limits is not None:
+        from .evaluation import normalised_limits
+
+        limits = normalised_limits(limits, model.mean, model.std)
     with torch.no_grad():
         if params_need_context(params):
             batch = source.batch(mine % source.n)
@@ -583,7 +590,7 @@ def cmd_sample(args) -> int:
         if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         else:
-            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver)   # G draws for each of the B contexts, which are encoded once
+            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
             medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
@@ -593,6 +600,8 @@ def cmd_sample(args) -> int:
         saved["solver"] = args.solver
     if hold is not None:
         saved["hold"] = dict(args.hold)   # {joint: the value it was held at}
+    if limits is not None:
+        saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} or the one range of --clip, as given
     if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
         saved.update(trajectories=saved["trajectories"].view(B, G, *traj.shape[1:]), draws=G, medoid=medoid.cpu())
     torch.save(saved, out)
@@ -655,7 +664,9 @@ def cmd_rollout(args) -> int:
     --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again.
     --carry K [--advance S]: overlapping ticks - S trajectory points (default T - K) pass between two ticks, the sensor rows of S points
     arrive per tick, and the first K rows of a tick's trajectory are pinned to rows [S, S + K) of the previous one.
-    --hold J=V[,J=V...]: joint J of every robot is held at V radians (as published) inside every tick's rollout, from the first tick on."""
+    --hold J=V[,J=V...]: joint J of every robot is held at V radians (as published) inside every tick's rollout, from the first tick on.
+    --limits J=LO:HI[,J=LO:HI...] | --clip R [--reproject]: every published joint J stays inside [LO, HI] radians (as published), or every
+    joint inside [-R, R]: the limits act on the predicted clean trajectory inside every tick's rollout (PolicySession(limits=...))."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
@@ -677,7 +688,8 @@ def cmd_rollout(args) -> int:
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
-                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver)
+                                            seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver,
+                                            limits=_limits_arg(args), reproject=args.reproject)
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -710,6 +722,8 @@ def cmd_rollout(args) -> int:
         saved.update(carry=session.carry, advance=session.advance)
     if args.hold:
         saved["hold"] = dict(args.hold)   # {joint: the radians it was held at}
+    if session._limits is not None:
+        saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} radians, or the one range of --clip
     if args.draws > 1:
         saved["draws"] = session.draws   # every published trajectory is the medoid of that many draws
     if episode is not None:
@@ -744,10 +758,61 @@ def _hold(text: str) -> list:
     return pairs
 
 
+def _limits(text: str) -> list:
+    """--limits J=LO:HI[,J=LO:HI...] -> [(joint, lo, hi)]; an empty LO or HI (or -inf / inf) leaves that side open."""
+    try:
+        out = []
+        for item in text.split(","):
+            j, pair = item.split("=")
+            lo, hi = pair.split(":")
+            out.append((int(j), float(lo) if lo.strip() else -math.inf, float(hi) if hi.strip() else math.inf))
+    except ValueError:
+        out = []
+    if not out or min(j for j, _, _ in out) < 0 or len({j for j, _, _ in out}) != len(out) or any(not lo <= hi for _, lo, hi in out):
+        raise argparse.ArgumentTypeError(f"--limits takes JOINT=LO:HI[,JOINT=LO:HI...] with distinct joint indices >= 0 and LO <= HI, got {text!r}")
+    return out
+
+
+def _limits_arg(args, params: Optional[dict] = None):
+    """``limits`` of model.sample / evaluate / PolicySession from --limits / --clip: {joint: (lo, hi)}, one range, or None."""
+    if args.limits and args.clip is not None:
+        raise SystemExit("--limits and --clip exclude each other")
+    if args.reproject and not args.limits and args.clip is None:
+        raise SystemExit("--reproject is an option of --limits / --clip")
+    if args.clip is not None:
+        if not args.clip >= 0:
+            raise SystemExit("--clip takes a range R >= 0")
+        limits = float(args.clip)
+    elif args.limits:
+        limits = {j: (lo, hi) for j, lo, hi in args.limits}
+    else:
+        return None
+    if params is not None:
+        J = params["num_joints"]
+        if params.get("distilled_decoder", False):
+            raise SystemExit("--limits: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if J > 32 or (isinstance(limits, dict) and max(limits) >= J):
+            raise SystemExit(f"--limits: joint indices lie in [0, {J}) and the model has at most 32 joints")
+    return limits
+
+
+def _limits_saved(args):
+    return float(args.clip) if args.clip is not None else {j: (lo, hi) for j, lo, hi in args.limits}
+
+
 def _hold_joints(pairs: list, J: int) -> tuple:
     if J > 32 or max(j for j, _ in pairs) >= J:
         raise SystemExit(f"--hold: joint indices lie in [0, {J}) and the model has at most 32 joints")
     return [j for j, _ in pairs], [v for _, v in pairs]
+
+
+def _add_limit_flags(p) -> None:
+    p.add_argument("--limits", type=_limits, default=None, metavar="J=LO:HI[,J=LO:HI...]", help="joint J stays inside [LO, HI] (an empty side is open): "
+                   "the predicted clean trajectory is clamped at every denoising step (model.sample(limits=...)); units as --hold's in this "
+                   "subcommand (rollout: radians as published; sample / evaluate: the space of the trajectories)")
+    p.add_argument("--clip", type=float, default=None, metavar="R", help="--limits with the one range [-R, R] on every joint")
+    p.add_argument("--reproject", action="store_true", help="with --limits / --clip: a clamped element's noise prediction is recomputed from the "
+                   "clamped value (diffusers' use_clipped_model_output)")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -766,6 +831,7 @@ def build_parser() -> argparse.ArgumentParser:
     sa.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
     sa.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
                     "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
+    _add_limit_flags(sa)
     sa.add_argument("--num_samples", type=int, default=10, help="Number of samples to generate")
     sa.add_argument("--output", "-o", type=str, default="samples.pt", help="Where to save the sampled trajectories")
     sa.add_argument("--ema", action="store_true", help="sample from the checkpoint's EMA weights (train --ema-decay) instead of the last iterate")
@@ -799,6 +865,7 @@ def build_parser() -> argparse.ArgumentParser:
     ev.add_argument("--steps", type=int, default=30, help="Number of denoising steps")
     ev.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
                     "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
+    _add_limit_flags(ev)
     ev.add_argument("--draws", type=int, default=1, metavar="G", help="draws per window (1 .. 64): rmse of the first, the medoid and the best")
     ev.add_argument("--grid", type=int, default=8, metavar="K", help="timesteps of the loss grid, t_k = (2k + 1) 1000 // (2K)")
     ev.add_argument("--timesteps", type=str, default=None, metavar="a,b,...", help="the loss grid's timesteps (0 .. 999) instead of --grid")
@@ -824,6 +891,7 @@ def build_parser() -> argparse.ArgumentParser:
     ro.add_argument("--steps", type=int, default=30, help="Number of denoising steps per tick")
     ro.add_argument("--solver", choices=("ddim", "multistep"), default="ddim", help="the sampler of the rollout: first-order DDIM, or the "
                     "second-order multistep solver on the same timesteps (model.sample(solver=...)): meant for fewer --steps")
+    _add_limit_flags(ro)
     ro.add_argument("--episode-ticks", type=str, default=None, metavar="E[,E...]", help="episode length in ticks, robot b's is E[b %% len(E)]: "
                     "after its last tick that robot alone is reset and goes on; the output gains 'resets' (K, N)")
     ro.add_argument("--raw", action="store_true", help="the stream carries what the sensors deliver - xyzw quaternions and uint8 camera frames - "

@@ -331,6 +331,25 @@ struct MultistepArgs {
     float w;
 };
 
+// Per-joint limits on the predicted clean trajectory (sd_ddim_sample_limits; diffusers' clip_sample, per joint): the storing lane clamps
+// x0 = (x - c1 e) / c0 to [lo[j], hi[j]] with two compares and selects - a NaN x0 stays NaN, so no fminf / fmaxf / med3 - before the update
+// is formed from it:  x0c = x0 < lo ? lo : (x0 > hi ? hi : x0);  e' = reproject && x0c != x0 ? (x - c0 x0c) / c1 : e;
+// x = fma(c2, x0c, c3 e') + w (hist - x0c);  hist = x0c.  -inf / +inf: no limit on that side; all infinite is the multistep update bit for
+// bit.  A held element gets the hold's value whatever the limits say.  The limits twins take it beside the multistep twins' arguments;
+// their MultistepArgs.hist may be NULL (first-order DDIM: w is then 0 and no history is written).
+struct LimitArgs {
+    const float *lo, *hi;   // 32 floats each in device memory, [J, 32) padded with -inf / +inf: a lane's f32x4 load at j0 <= 28 is always legal
+    int reproject;          // != 0: a clamped element's eps is recomputed from x and x0c (diffusers' use_clipped_model_output)
+};
+// One element of the limits twins, shared by both step-kernel families and ddim_limit_step_kernel: returns fma(c2, x0c, c3 e') - the update
+// without the history term, in the multistep twins' form - and leaves the clamped x0 in x0c.  An element that is not clamped keeps e itself.
+__device__ __forceinline__ float limit_update(float x, float e, float lo, float hi, float c0, float c1, float c2, float c3, int reproject, float &x0c) {
+    const float x0 = __builtin_fmaf(-c1, e, x) / c0;
+    x0c = x0 < lo ? lo : (x0 > hi ? hi : x0);
+    if (reproject && !(x0c == x0)) e = __builtin_fmaf(-c0, x0c, x) / c1;
+    return __builtin_fmaf(c2, x0c, c3 * e);
+}
+
 // One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
 // (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
 struct StepReq {
@@ -344,6 +363,7 @@ struct StepReq {
     int draws;           // trajectories per context: trajectory b reads context b / draws (1: its own)
     const HoldArgs *hold = nullptr;   // or NULL; needs coef, excludes pin (one hold kernel serves every draws >= 1)
     const MultistepArgs *ms = nullptr;   // or NULL; needs coef, excludes pin: the multistep twins (hold then optional, its mask too)
+    const LimitArgs *lim = nullptr;      // or NULL; needs ms (whose hist may then be NULL): the limits twins
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

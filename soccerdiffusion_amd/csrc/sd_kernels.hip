@@ -2528,6 +2528,21 @@ __global__ void ddim_multistep_kernel(const float *__restrict__ eps, const float
         hist[i] = x0;
     }
 }
+// The kernel above with per-joint limits on x0 (LimitArgs, sd_common.h; joint = i % J): limit_update's clamp by compares - a NaN stays NaN -
+// and optional reprojected eps, then the history term on the clamped x0, which goes into hist.  hist NULL: first-order DDIM (w is 0), nothing
+// written.  The row-panel and chain routes of sd_ddim_sample_limits launch it where the multistep call launches the kernel above;
+// sd_ddim_limit_step is the loop form's step.
+__global__ void ddim_limit_step_kernel(const float *__restrict__ eps, const float *x, float *x_next, float *hist, float c0, float c1, float c2,
+                                       float c3, float w, LimitArgs lim, long n, int J) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(i % J);
+        float x0c;
+        float xn = limit_update(x[i], eps[i], lim.lo[j], lim.hi[j], c0, c1, c2, c3, lim.reproject, x0c);
+        if (w != 0.f) xn = __builtin_fmaf(w, hist[i] - x0c, xn);
+        x_next[i] = xn;
+        if (hist) hist[i] = x0c;
+    }
+}
 
 
 // ======================================================================================
@@ -2991,13 +3006,14 @@ struct TrajCall {
     // (draws > 1: the shared-context instantiations; with per_traj the context index b / draws and the step block step_map[b] are separate)
     // hold: the hold instantiations (held elements; never beside a pin)
     // ms: the multistep instantiations (the second-order solver's history term; a hold beside it is optional, never a pin)
+    // lim: the limits instantiations (needs ms, whose history may then be NULL: first-order DDIM)
     StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr,
-                const MultistepArgs *ms = nullptr) const {
-        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms};
+                const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr) const {
+        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms, lim};
     }
     int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr,
-             const MultistepArgs *ms = nullptr) const {
-        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms);
+             const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr) const {
+        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms, lim);
         return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
     }
     // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
@@ -3038,10 +3054,20 @@ static int ddim_multistep(const float *eps, const float *x, float *x_next, float
     SD_CHECK_LAUNCH("ddim_multistep_kernel");
     return 0;
 }
-// The second-order multistep solver of a rollout (sd_ddim_sample_multistep): w[i] of step i (host) and the history array (device)
+// x <- the same update on x0 clamped to the per-joint limits, hist <- the clamped x0 where hist is given (ddim_limit_step_kernel)
+static int ddim_limit_step(const float *eps, const float *x, float *x_next, float *hist, const float *coef4, float w, const LimitArgs &lim, long n, int J,
+                           hipStream_t st) {
+    SD_LAUNCH(ddim_limit_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, eps, x, x_next, hist, coef4[0], coef4[1], coef4[2], coef4[3], w, lim, n, J);
+    SD_CHECK_LAUNCH("ddim_limit_step_kernel");
+    return 0;
+}
+// The second-order multistep solver of a rollout (sd_ddim_sample_multistep): w[i] of step i (host) and the history array (device).
+// lim (sd_ddim_sample_limits): per-joint limits on x0; w and hist may then both be NULL - first-order DDIM under limits.
 struct MultistepCall {
     const float *w;
     float *hist;
+    const LimitArgs *lim = nullptr;
+    float weight(int i) const { return w ? w[i] : 0.f; }
 };
 
 // the rollout on the trajectory kernels: one launch per DDIM step (pin: plus the entry overwrite, once), or - the plan's rollout_fused -
@@ -3067,8 +3093,8 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
     for (int i = 0; i < c.n_tok; ++i) {
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
-        const MultistepArgs ms{msc ? msc->hist : nullptr, msc ? msc->w[i] : 0.f};   // (no fused rollout form: one launch per step, like a hold)
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr))) return rc;
+        const MultistepArgs ms{msc ? msc->hist : nullptr, msc ? msc->weight(i) : 0.f};   // (no fused rollout form: one launch per step, like a hold)
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr, msc ? msc->lim : nullptr))) return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
@@ -3158,7 +3184,9 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
             rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x_up, coef + 4 * i}, st);
             if (rc) return rc;
         }
-        if (msc && (rc = ddim_multistep(eps_i, x, x, msc->hist, coef + 4 * i, msc->w[i], n, st))) return rc;
+        if (msc && (rc = msc->lim ? ddim_limit_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, n, w->J, st)
+                                  : ddim_multistep(eps_i, x, x, msc->hist, coef + 4 * i, msc->w[i], n, st)))
+            return rc;
         // these routes are many launches per step already: the pinned rows are one more, behind the fused DDIM sites
         if (pin && (rc = ddim_pin(x, *pin, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
         if (hold && (rc = ddim_hold(x, *hold, coef[4 * i + 2], coef[4 * i + 3], B, T, w->J, st))) return rc;
@@ -3276,6 +3304,29 @@ extern "C" int sd_ddim_sample_multistep(const sd_denoiser_weights *w, const floa
     if (n_hold && w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_multistep: one 32-bit mask word per row: J must be <= 32 with a mask");
     const HoldArgs hold{hold_x0, hold_noise, hold_mask};
     const MultistepCall msc{msw, history};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, draws, n_hold ? &hold : nullptr, &msc);
+}
+
+// sd_ddim_sample_multistep with per-joint limits on the predicted x0 (LimitArgs, sd_common.h), on every route.  msw and history: both (the
+// multistep solver) or msw NULL (first-order DDIM; a history buffer, if given, still receives the clamped x0 of every step).  lo, hi: 32 floats each in device memory, padded with -inf / +inf beyond J.
+extern "C" int sd_ddim_sample_limits(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                     float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                     int max_mode, const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws,
+                                     const float *msw, float *history, const float *lo, const float *hi, int reproject, void *stream) {
+    const int n_hold = (hold_x0 ? 1 : 0) + (hold_noise ? 1 : 0) + (hold_mask ? 1 : 0);
+    if (!lo || !hi || n_steps <= 0) return fail(SD_E_BADARG, "sd_ddim_sample_limits: lo and hi (32 floats each, device) must be given");
+    if (n_hold != 0 && n_hold != 3) return fail(SD_E_BADARG, "sd_ddim_sample_limits: hold_x0, hold_noise and hold_mask must be given together");
+    if (msw && !history) return fail(SD_E_BADARG, "sd_ddim_sample_limits: msw needs a history buffer (both NULL: DDIM)");
+    if (msw && msw[0] != 0.f) return fail(SD_E_BADARG, "sd_ddim_sample_limits: msw[0] must be 0 (the first step has no history)");
+    if (history && (history == x || (n_hold && (history == hold_x0 || history == hold_noise || (const void *)history == (const void *)hold_mask))))
+        return fail(SD_E_BADARG, "sd_ddim_sample_limits: history must alias neither x nor the hold buffers");
+    if (n_hold && hold_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_limits: hold_noise must not alias x (x is overwritten by the first step)");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_limits: draws must be >= 1 and divide B");
+    if (w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_limits: lo and hi describe at most 32 joints");
+    const HoldArgs hold{hold_x0, hold_noise, hold_mask};
+    const LimitArgs lim{lo, hi, reproject ? 1 : 0};
+    const MultistepCall msc{msw, history, &lim};
     return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
                            false, draws, n_hold ? &hold : nullptr, &msc);
 }
@@ -3409,6 +3460,15 @@ extern "C" int sd_multistep_step(const float *eps, const float *x, float *x_prev
     if (!eps || !x || !x_prev || !hist || !coef4 || n <= 0) return fail(SD_E_BADARG, "sd_multistep_step: bad argument");
     if (hist == x || hist == x_prev || hist == eps) return fail(SD_E_BADARG, "sd_multistep_step: hist must alias neither eps, x nor x_prev");
     return ddim_multistep(eps, x, x_prev, hist, coef4, w, n, (hipStream_t)stream);
+}
+
+// sd_multistep_step with per-joint limits on x0 (joint = element index % J): hist may be NULL (first-order DDIM; w must then be 0).
+extern "C" int sd_ddim_limit_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, const float *lo, const float *hi,
+                                  int reproject, long n, int J, void *stream) {
+    if (!eps || !x || !x_prev || !coef4 || !lo || !hi || n <= 0 || J < 1 || J > 32 || n % J) return fail(SD_E_BADARG, "sd_ddim_limit_step: bad argument");
+    if (!hist && w != 0.f) return fail(SD_E_BADARG, "sd_ddim_limit_step: a history weight needs a history buffer");
+    if (hist && (hist == x || hist == x_prev || hist == eps)) return fail(SD_E_BADARG, "sd_ddim_limit_step: hist must alias neither eps, x nor x_prev");
+    return ddim_limit_step(eps, x, x_prev, hist, coef4, w, LimitArgs{lo, hi, reproject ? 1 : 0}, n, J, (hipStream_t)stream);
 }
 
 extern "C" int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t, float sqrt_1m_a_t,

@@ -272,6 +272,48 @@ __global__ __launch_bounds__(THREADS) void session_hold_kernel(float *pin_x0, in
     if (threadIdx.x == 0) held[b] = (int32_t)(set ? ((unsigned)held[b] | bits) : ((unsigned)held[b] & ~bits));
 }
 
+// ---- joint limits (PolicySession(limits=...): sd_ddim_sample_limits' lo / hi, from radians as published) -------------------------------
+struct SessionLimits {   // the limits of one set_limits call in radians, by value in the kernel argument: J <= 32
+    float lo[32], hi[32];
+};
+// both roundings of the commit's expression (session_commit_kernel's line, which a compiler is free to contract).  Plain operators: it is
+// this file's pragma that keeps them apart - the __fmul_rn / __fadd_rn wrappers are compiled under the header's contraction and fuse.
+static __device__ __forceinline__ float commit_fused(float x, float s, float m) { return __builtin_fmaf(x, s, m) - (float)M_PI; }
+static __device__ __forceinline__ float commit_plain(float x, float s, float m) { return (x * s + m) - (float)M_PI; }
+// One thread per slot of the 32-float arrays.  Joint j < J: the bound in normalised space begins as the inverse of the commit's expression,
+// ((v + pi) - mean[j]) / std[j], and moves inward - by nextafterf, or by a quarter ulp of the commit's largest intermediate in normalised
+// units where that is more (x near 0 has ulps far below the published value's), 64 tries at most (measured on the host: 5) - until both
+// roundings of the commit's expression give a value inside [lo, hi].  The commit is monotonic in x (std > 0), so every x0 clamped to the
+// result is published inside the radians bit for bit.  An infinite bound stays infinite.  A range narrower than the commit's resolution
+// collapses to its upper bound.  Slots >= J: -inf / +inf.
+__global__ void session_limits_kernel(float *lo_n, float *hi_n, SessionLimits rad, const float *__restrict__ mean, const float *__restrict__ stdv,
+                                      int J) {
+    const int j = threadIdx.x;
+    if (j >= 32) return;
+    float lo = -INFINITY, hi = INFINITY;
+    if (j < J) {
+        const float pi = (float)M_PI, m = mean[j], s = stdv[j];
+        const float rl = rad.lo[j], rh = rad.hi[j];
+        if (rl > -INFINITY) {
+            const float big = fmaxf(fmaxf(fabsf(rl + pi), fabsf(m)), fabsf(rl));
+            const float q = (nextafterf(big, INFINITY) - big) * 0.25f / s;
+            lo = ((rl + pi) - m) / s;
+            for (int k = 0; k < 64 && !(commit_fused(lo, s, m) >= rl && commit_plain(lo, s, m) >= rl); ++k)
+                lo = fmaxf(nextafterf(lo, INFINITY), lo + q);
+        }
+        if (rh < INFINITY) {
+            const float big = fmaxf(fmaxf(fabsf(rh + pi), fabsf(m)), fabsf(rh));
+            const float q = (nextafterf(big, INFINITY) - big) * 0.25f / s;
+            hi = ((rh + pi) - m) / s;
+            for (int k = 0; k < 64 && !(commit_fused(hi, s, m) <= rh && commit_plain(hi, s, m) <= rh); ++k)
+                hi = fminf(nextafterf(hi, -INFINITY), hi - q);
+        }
+        if (lo > hi) lo = hi;
+    }
+    lo_n[j] = lo;
+    hi_n[j] = hi;
+}
+
 // The tick's mask: mask[s * draws + g][t] = held[b] | (t < pin_rows[b] ? all J bits : 0), b = robot s of the launch (robots NULL: s);
 // pin_rows NULL: a session without carried rows.  n = S * draws * T words.
 __global__ __launch_bounds__(THREADS) void session_hold_mask_kernel(int32_t *__restrict__ mask, const int32_t *__restrict__ held,
@@ -459,6 +501,21 @@ extern "C" int sd_session_hold_mask(int32_t *mask, const int32_t *held, const in
     SD_LAUNCH(ss::session_hold_mask_kernel, dim3((unsigned)((n + ss::THREADS - 1) / ss::THREADS)), dim3(ss::THREADS), 0, (hipStream_t)stream, mask, held,
               pin_rows, robots, n, B, T, J, draws);
     SD_CHECK_LAUNCH("session_hold_mask_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_limits(float *lo_n, float *hi_n, const float *lo_rad, const float *hi_rad, const float *mean, const float *stdv, int J,
+                                 void *stream) {
+    if (!lo_n || !hi_n || !lo_rad || !hi_rad || !mean || !stdv || J < 1 || J > 32)
+        return fail(SD_E_BADARG, "sd_session_limits: lo_n, hi_n, lo_rad, hi_rad, mean and std must be given; 1 <= J <= 32");
+    ss::SessionLimits rad{};
+    for (int j = 0; j < J; ++j) {
+        if (!(lo_rad[j] <= hi_rad[j])) return fail(SD_E_BADARG, "sd_session_limits: lo[j] <= hi[j], no NaN");
+        rad.lo[j] = lo_rad[j];
+        rad.hi[j] = hi_rad[j];
+    }
+    SD_LAUNCH(ss::session_limits_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lo_n, hi_n, rad, mean, stdv, J);
+    SD_CHECK_LAUNCH("session_limits_kernel");
     return 0;
 }
 

@@ -1457,12 +1457,18 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // word - only when ms.w != 0, a wave-uniform branch on the kernel argument - computes x0 as ddim_update does, stores
 // fma(w, hist - x0, ddim) and leaves x0 in hist (every step, the last one too).  A held element gets the hold's value; its history entry is
 // the model's x0 all the same.  The same lane reads and writes an element's history in consecutive launches: no barrier, no LDS.
+// PIN == 4, LIM: the limits twin (LimitArgs, sd_common.h; sd_ddim_sample_limits) - the multistep twin with an optional history (ms.hist NULL:
+// first-order DDIM, nothing written) plus the clamp of x0 to [lo[j], hi[j]]: the storing lane requests its four lo / hi values where the
+// hold requests its mask word (32 padded floats each: always a legal f32x4), clamps with compares and selects (a NaN stays NaN), forms the
+// update from the clamped x0 (limit_update) and leaves the clamped x0 in hist.  lim.reproject is a wave-uniform branch on the kernel
+// argument.  No barrier and no LDS of its own.
 template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
                                                  int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{},
-                                                 const MultistepArgs &ms = MultistepArgs{}) {
+                                                 const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{}) {
     constexpr bool HOLD = PIN == 2;
     constexpr bool MS = PIN == 3;
+    constexpr bool LIM = PIN == 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
@@ -1608,6 +1614,20 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 }
             }
         }
+        f32x4 lo4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, hi4[2] = {lo4[0], lo4[0]};   // LIM: this lane's limits
+        if constexpr (LIM) {
+            if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) {
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+                if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                    hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                    if (ms.w != 0.f && !(J & 3) && 16 * n + 4 * c.g < J)
+                        hpre[n] = *reinterpret_cast<const f32x4 *>(ms.hist + (traj * a.T + tok) * J + 16 * n + 4 * c.g);
+                }
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
         if (c.w < NTT) {
@@ -1648,6 +1668,17 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                                 continue;
                             }
                         }
+                        if constexpr (LIM) {
+                            if (a.update_x) {
+                                float x0c;
+                                float xn = limit_update(a.x[at + r], e, lo4[n][r], hi4[n][r], a.c0, a.c1, a.c2, a.c3, lim.reproject, x0c);
+                                if (ms.w != 0.f) xn = __builtin_fmaf(ms.w, ms.hist[at + r] - x0c, xn);
+                                if ((hold_m >> (j0 + r)) & 1u) xn = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                                a.x[at + r] = xn;
+                                if (ms.hist) ms.hist[at + r] = x0c;
+                            }
+                            continue;
+                        }
                         if constexpr (MS) {
                             if (a.update_x) {
                                 const float x0 = __builtin_fmaf(-a.c1, e, a.x[at + r]) / a.c0;
@@ -1684,6 +1715,32 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                         *reinterpret_cast<f32x4 *>(a.x + at) = a.c2 * k + a.c3 * nz;
                         continue;
                     }
+                }
+                if constexpr (LIM) {
+                    if (a.update_x) {
+                        const unsigned bits = (hold_m >> j0) & 15u;
+                        const f32x4 xv = *reinterpret_cast<const f32x4 *>(a.x + at);
+                        f32x4 x0c, xn;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float q;
+                            xn[r] = limit_update(xv[r], e[r], lo4[n][r], hi4[n][r], a.c0, a.c1, a.c2, a.c3, lim.reproject, q);
+                            x0c[r] = q;
+                        }
+                        if (ms.w != 0.f) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) xn[r] = __builtin_fmaf(ms.w, hpre[n][r] - x0c[r], xn[r]);
+                        }
+                        if (bits) {
+                            const f32x4 k = *reinterpret_cast<const f32x4 *>(hold.x0 + at), nz = *reinterpret_cast<const f32x4 *>(hold.noise + at);
+                            const f32x4 hv = a.c2 * k + a.c3 * nz;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) xn[r] = ((bits >> r) & 1u) ? hv[r] : xn[r];
+                        }
+                        *reinterpret_cast<f32x4 *>(a.x + at) = xn;
+                        if (ms.hist) *reinterpret_cast<f32x4 *>(ms.hist + at) = x0c;
+                    }
+                    continue;
                 }
                 if constexpr (MS) {
                     if (a.update_x) {
@@ -1816,6 +1873,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_ms_kernel(StepArgs a, H
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_ms_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, int draws) {
     TJ<NTT, true>::template step_body<true, 3, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms);
+}
+// The limits twins (sd_ddim_sample_limits; instantiated in sd_traj_lim.hip): the multistep twins, their history optional (ms.hist NULL:
+// first-order DDIM), plus the per-joint clamp of the predicted x0 (LimitArgs).  One kernel per tile count serves DDIM and multistep,
+// plain, pinned (a leading-rows mask), held and shared-context calls.
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_lim_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, int draws) {
+    TJ<NTT, true>::template step_body<false, 4, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_lim_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, int draws) {
+    TJ<NTT, true>::template step_body<true, 4, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim);
 }
 struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
     RolloutArgs ra;

@@ -821,11 +821,15 @@ struct TG {
     // PIN == 3, MS: the multistep twin (MultistepArgs, sd_common.h; sd_ddim_sample_multistep) - a hold whose mask is optional (NULL: nothing
     // held) plus the history term: where ms.w != 0 (a wave-uniform branch on the kernel argument) the storing lane requests its history
     // values beside the mask word, and stores fma(w, hist - x0, ddim); it leaves x0 in hist on every step
+    // PIN == 4, LIM: the limits twin (LimitArgs, sd_common.h; sd_ddim_sample_limits) - the multistep twin with an optional history (ms.hist
+    // NULL: first-order DDIM) on x0 clamped to [lo[j], hi[j]] by compares and selects: the storing lane requests its four lo / hi values
+    // (32 padded floats each: always a legal f32x4) beside the mask word; lim.reproject is a wave-uniform branch on the kernel argument
     template <int PIN = 0, bool DRAWS = false>
     static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{},
-                                                     const MultistepArgs &ms = MultistepArgs{}) {
+                                                     const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{}) {
         constexpr bool HOLD = PIN == 2;
         constexpr bool MS = PIN == 3;
+        constexpr bool LIM = PIN == 4;
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -926,6 +930,23 @@ struct TG {
                     }
                 }
             }
+            f32x4 lo4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, hi4[2] = {lo4[0], lo4[0]};   // LIM: this lane's limits
+            if constexpr (LIM) {
+                if (c.w < NTT && (c.w < NTT - 1 || c.okl)) {
+                    const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
+                    if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                        hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                        if (ms.w != 0.f) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (16 * n + 4 * c.g + r < J) hpre[n][r] = ms.hist[(traj * a.T + tok) * J + 16 * n + 4 * c.g + r];
+                        }
+                    }
+                }
+            }
             __syncthreads();
             if (c.w < NTT) {
                 const char *X = c.smem;
@@ -959,6 +980,17 @@ struct TG {
                                 a.x[at + r] = a.c2 * pin.x0[at + r] + a.c3 * pin.noise[at + r];
                                 continue;
                             }
+                        }
+                        if constexpr (LIM) {
+                            if (a.update_x) {   // the multistep form on the clamped x0 (limit_update, sd_common.h)
+                                float x0c;
+                                float xn = limit_update(a.x[at + r], e, lo4[n][r], hi4[n][r], a.c0, a.c1, a.c2, a.c3, lim.reproject, x0c);
+                                if (ms.w != 0.f) xn = __builtin_fmaf(ms.w, hpre[n][r] - x0c, xn);
+                                if ((hold_m >> (j0 + r)) & 1u) xn = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                                a.x[at + r] = xn;
+                                if (ms.hist) ms.hist[at + r] = x0c;
+                            }
+                            continue;
                         }
                         if constexpr (MS) {
                             if (a.update_x) {   // ddim_update's form (sd_traj.h), then the history term
@@ -1007,6 +1039,11 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_hold_kernel(StepAr
 template <int D, int NTT>
 __global__ __launch_bounds__(NTHREADS) void traj_step_generic_ms_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, int draws) {
     TG<D, NTT>::template step_body<3, true>(a, PinArgs{}, draws, hold, ms);
+}
+// the limits twin (sd_ddim_sample_limits): the multistep twin, its history optional (ms.hist NULL: DDIM), plus the per-joint clamp of x0
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_lim_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, int draws) {
+    TG<D, NTT>::template step_body<4, true>(a, PinArgs{}, draws, hold, ms, lim);
 }
 
 }   // namespace tg
@@ -1083,6 +1120,10 @@ StepHoldFn step_hold_fn(int d, int ntt) {
 typedef void (*StepMsFn)(tg::StepArgs, HoldArgs, MultistepArgs, int);
 StepMsFn step_ms_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepMsFn { return tg::traj_step_generic_ms_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepLimFn)(tg::StepArgs, HoldArgs, MultistepArgs, LimitArgs, int);
+StepLimFn step_lim_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepLimFn { return tg::traj_step_generic_lim_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
@@ -1201,8 +1242,10 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
     if (r.hold && (!r.coef || r.pin))
         return fail(SD_E_BADARG, "traj_step_generic_hold_kernel: held elements need the DDIM coefficients and exclude a pin");
-    if (r.ms && (!r.coef || r.pin || !r.ms->hist))
+    if (r.ms && (!r.coef || r.pin || (!r.ms->hist && !r.lim)))
         return fail(SD_E_BADARG, "traj_step_generic_ms_kernel: the multistep term needs the DDIM coefficients and a history buffer, and excludes a pin");
+    if (r.lim && (!r.ms || !r.lim->lo || !r.lim->hi || (!r.ms->hist && r.ms->w != 0.f)))
+        return fail(SD_E_BADARG, "traj_step_generic_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
     tg::StepArgs a{};
     a.x = r.x;
     a.eps_out = r.eps;
@@ -1235,6 +1278,11 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     constexpr int MAX_LDS = 163840;
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.lim) {   // the limits twin: DDIM (ms->hist NULL) or multistep, held or not, whatever the group size
+        static DevFlag lim_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_lim_fn(d, ntt), "traj_step_generic_lim_kernel", lim_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, *r.lim, r.draws);
+    }
     if (r.ms) {   // the multistep twin: held or not (a hold's mask may be NULL), whatever the group size
         static DevFlag ms_attr_set[3][8];   // [hidden_dim][ntt]
         return launch_step_kernel(step_ms_fn(d, ntt), "traj_step_generic_ms_kernel", ms_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,

@@ -71,6 +71,21 @@ def _f64(t) -> torch.Tensor:
     return torch.as_tensor(t).detach().to("cpu", torch.float64)
 
 
+def normalised_limits(limits, mean: torch.Tensor, std: torch.Tensor) -> tuple:
+    """``limits`` in the space of the trajectories (x * std + mean; ``(lo, hi)``, one range or ``{joint: (lo, hi)}`` as ``ops.joint_limits``
+    takes them) as ``(lo, hi)`` (J,) fp32 host tensors in the sampler's normalised space, (v - mean) / std per joint; an infinite bound
+    stays infinite.  The normaliser's std is positive."""
+    from . import ops
+
+    mean, std = mean.detach().reshape(-1).cpu().float(), std.detach().reshape(-1).cpu().float()
+    J = mean.numel()
+    lo, hi = ops._limits_host(limits, J)
+    lo, hi = torch.from_numpy(lo[:J].copy()), torch.from_numpy(hi[:J].copy())
+    if not (std > 0).all():
+        raise ValueError("limits: the normaliser's std must be positive")
+    return (lo - mean) / std, (hi - mean) / std
+
+
 def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool,
                     solver: str = "ddim") -> dict:
     """The report from the per-batch marginals, in fp64 on the host.  A part holds, for its C windows: ``err`` (C, G), ``row_err`` (C, G, T),
@@ -109,12 +124,16 @@ def _has_context(model) -> bool:
 
 @torch.no_grad()
 def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int = 8, batch: int = 64, seed: int = 0, max_mode: int = 3,
-             angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None, solver: str = "ddim") -> dict:
+             angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None, solver: str = "ddim",
+             limits=None, reproject: bool = False) -> dict:
     """The report (a plain dict of Python floats, ints and lists) of ``model`` on the windows ``idx`` of ``source`` (``cli.DataSource``), in
     batches of ``batch`` windows from ``source.batch``.  The model must be in ``eval()``.  Per batch: the context is encoded once; the loss
     grid runs at ``timesteps`` (default ``default_timesteps(grid)``); ``draws`` = G trajectories per window are sampled with ``steps`` DDIM
     steps (``model.sample(draws=G)``; ``solver="multistep"``: with the second-order multistep solver on the same ``steps`` timesteps - the
     instrument for "10 steps against 30" then also says what the solver buys; the report names it in its ``solver`` entry);
+    ``limits`` / ``reproject``: the draws are sampled under joint limits given in the space of the target trajectories
+    (``normalised_limits``, ``model.sample(limits=...)``) - what a set of limits costs in rmse; the report then gains a ``limits`` entry,
+    ``[lo, hi]`` per joint with None for an open side, and ``reproject``;
     ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
     student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None.
     A model without context encoders (decoder pretraining) gets ten random context rows per window from the same generator.
@@ -131,6 +150,13 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         raise ValueError("evaluate: steps and batch must be positive")
     if solver not in ("ddim", "multistep") or (distilled and solver != "ddim"):
         raise ValueError(f"evaluate: solver must be 'ddim' or 'multistep' (a distilled decoder has no rollout: 'ddim'), got {solver!r}")
+    if limits is not None:
+        if distilled:
+            raise ValueError("evaluate: a distilled decoder has no rollout whose x0 could be limited")
+        J = model.mean.numel()
+        given = [[None if math.isinf(a) else a for a in pair]      # as given, per joint: [lo, hi], None for an open side
+                 for pair in zip(*(v[:J].tolist() for v in ops._limits_host(limits, J)))]
+        limits = normalised_limits(limits, model.mean, model.std)
     idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
     if idx.numel() == 0:
         raise ValueError("evaluate: no windows to evaluate")
@@ -157,7 +183,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         if distilled:
             x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
         else:
-            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver)
+            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject)
         x = x.contiguous()
         part["medoid"], chosen = ops.select_medoid(x, G)
         part["err"], part["row_err"], part["joint_err"], part["best"] = ops.trajectory_errors(x, target, model.mean, model.std, draws=G, angular=angular)
@@ -167,4 +193,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         if keep is not None:
             keep.append({"x": x, "target": target, "medoid_x": chosen, **({} if distilled else {"eps": eps, "noise": noise}), **part})
         parts.append({k: (None if v is None else v.cpu()) for k, v in part.items()})
-    return assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular, solver=solver)
+    report = assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular, solver=solver)
+    if limits is not None:
+        report.update(limits=given, reproject=bool(reproject))
+    return report

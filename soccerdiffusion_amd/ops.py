@@ -162,6 +162,100 @@ def multistep_step(eps: Tensor, x: Tensor, hist: Tensor, coef4, w: float) -> Ten
     return out
 
 
+class Limits(tuple):
+    """``(lo, hi)`` as ``joint_limits`` returns them: two (32,) fp32 device arrays, validated and padded - what the kernels read."""
+    __slots__ = ()
+    lo = property(lambda self: self[0])
+    hi = property(lambda self: self[1])
+
+
+def _limits_host(limits, J: int):
+    """``limits`` - ``(lo, hi)``, one range r or ``{joint: (lo, hi)}`` - as two (32,) fp32 host arrays padded with -inf / +inf, validated:
+    see ``joint_limits``."""
+    lo, hi = limits if isinstance(limits, tuple) and len(limits) == 2 else (limits, None)
+    if isinstance(J, bool) or not 1 <= int(J) <= 32:
+        raise ValueError(f"limits: the 32-float limit arrays describe at most 32 joints, got J = {J}")
+    J = int(J)
+    out_lo, out_hi = np.full(32, -np.inf, dtype=np.float32), np.full(32, np.inf, dtype=np.float32)
+    if isinstance(lo, Mapping) and hi is None:
+        for j, pair in lo.items():
+            if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < J:
+                raise ValueError(f"limits: joint index {j!r} out of range 0 .. {J - 1}")
+            try:
+                a, b = pair
+            except (TypeError, ValueError):
+                raise ValueError(f"limits: joint {j}: expected (lo, hi), got {pair!r}") from None
+            out_lo[int(j)], out_hi[int(j)] = a, b
+    elif hi is None:
+        try:
+            r = float(lo)
+        except (TypeError, ValueError):
+            raise ValueError(f"limits: expected (lo, hi) arrays of {J} floats, one range r, or {{joint: (lo, hi)}}; got {lo!r}") from None
+        if not r >= 0:
+            raise ValueError(f"limits: a range must be >= 0 and not NaN, got {r}")
+        out_lo[:J], out_hi[:J] = -r, r
+    else:
+        def arr(v, name):
+            v = v.detach().cpu().numpy() if isinstance(v, Tensor) else v
+            v = np.asarray(v, dtype=np.float32)
+            if v.shape != (J,):
+                raise ValueError(f"limits {name}: expected ({J},) floats, got shape {v.shape}")
+            return v
+        out_lo[:J], out_hi[:J] = arr(lo, "lo"), arr(hi, "hi")
+    if np.isnan(out_lo).any() or np.isnan(out_hi).any():
+        raise ValueError("limits: NaN is not a limit (use -inf / +inf for no limit on a side)")
+    if not (out_lo <= out_hi).all():
+        j = int(np.argmax(~(out_lo <= out_hi)))
+        raise ValueError(f"limits: lo[{j}] = {out_lo[j]} > hi[{j}] = {out_hi[j]}")
+    return out_lo, out_hi
+
+
+def joint_limits(lo, hi=None, J: Optional[int] = None, device=None) -> Limits:
+    """Per-joint limits of ``ddim_sample(limits=...)`` as the kernels read them (``sd_ddim_sample_limits``): two (32,) fp32 arrays on
+    ``device``, entries [J, 32) padded with -inf / +inf.  All in the sampler's normalised space.  ``lo``, ``hi``: (J,) floats (tensors,
+    arrays or lists) with ``lo[j] <= hi[j]``; -inf / +inf: no limit on that side.  ``joint_limits(r, J=J, device=...)``: one range,
+    (-r, r) on every joint (diffusers' ``clip_sample_range``).  ``joint_limits({joint: (lo, hi)}, J=J, device=...)``: the named joints,
+    every other unlimited.  ValueError for a wrong shape, a NaN, ``lo > hi``, a joint index outside 0 .. J - 1, or J > 32."""
+    if J is None or device is None:
+        raise ValueError("joint_limits: J and device must be given")
+    out_lo, out_hi = _limits_host(lo if hi is None else (lo, hi), J)
+    return Limits((torch.from_numpy(out_lo).to(device), torch.from_numpy(out_hi).to(device)))
+
+
+def _limits_req(limits, J: int, device) -> Limits:
+    """``limits`` of a sampler call, validated: a ``Limits`` on the device as it is; else ``(lo, hi)``, a range or a dict through
+    ``joint_limits``."""
+    if isinstance(limits, Limits):
+        for t in limits:
+            if not isinstance(t, Tensor) or tuple(t.shape) != (32,) or t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError(f"limits: expected the two (32,) fp32 arrays of ops.joint_limits on {device}")
+        if J > 32:
+            raise ValueError(f"limits: the 32-float limit arrays describe at most 32 joints, got J = {J}")
+        return limits
+    return joint_limits(limits, J=J, device=device)
+
+
+def limit_step(eps: Tensor, x: Tensor, coef4, limits: Limits, hist: Optional[Tensor] = None, w: float = 0.0, reproject: bool = False) -> Tensor:
+    """One step under per-joint limits for a caller that evaluates the denoiser itself (``sd_ddim_limit_step``): x0 of (eps, x) with
+    ``coef4`` is clamped to ``limits`` (joint = last dimension), the update is formed from the clamped x0 (``reproject``: a clamped
+    element's eps is recomputed from it) plus ``w * (hist - x0c)``; the clamped x0 is left in ``hist`` where one is given."""
+    lib = _lib.load()
+    _req(eps, "eps"); _req(x, "x")
+    if eps.shape != x.shape or (hist is not None and hist.shape != x.shape):
+        raise ValueError("limit_step: eps, x and hist must have one shape")
+    if hist is not None:
+        _req(hist, "hist")
+    limits = _limits_req(limits, x.shape[-1], x.device)
+    out = torch.empty_like(x)
+    c = np.ascontiguousarray([float(v) for v in coef4], dtype=np.float32)
+    if c.shape != (4,):
+        raise ValueError("limit_step: coef4 must hold 4 scalars")
+    check(lib.sd_ddim_limit_step(eps.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(hist), c.ctypes.data_as(_lib.c_float_p), float(w),
+                                 limits.lo.data_ptr(), limits.hi.data_ptr(), int(bool(reproject)), x.numel(), x.shape[-1], _stream()),
+          "sd_ddim_limit_step")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # weight descriptors
 # --------------------------------------------------------------------------------------
@@ -466,14 +560,27 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
 
 
 def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
-                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None, multistep=None):
+                        et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None, multistep=None,
+                        limits=None):
     """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
     ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
     ``sd_ddim_sample_pin``, launch for launch; ``hold = (known, noise, mask words)``: ``sd_ddim_sample_hold`` (never beside a pin).
     ``multistep = (w (n_steps,) fp32 on the host, history (B, T, J) on the device)``: ``sd_ddim_sample_multistep``, with ``hold`` or
     without (never beside a pin: the callers fold it into a mask).
+    ``limits = (lo, hi, reproject)`` (the (32,) device arrays of ``joint_limits``): ``sd_ddim_sample_limits``, with ``multistep`` and
+    ``hold`` or without either (never beside a pin).
     Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
     B, T, _ = x.shape
+    if limits is not None:
+        msw, hist = multistep if multistep is not None else (None, None)
+        check(_lib.load().sd_ddim_sample_limits(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                                x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1],
+                                                len(coef), _ptr(status), int(max_mode), *[_ptr(t) for t in (hold or (None, None, None))], draws,
+                                                None if msw is None else msw.ctypes.data_as(_lib.c_float_p), _ptr(hist),
+                                                limits[0].data_ptr(), limits[1].data_ptr(), int(bool(limits[2])), _stream()),
+              "sd_ddim_sample_limits")
+        out = (x,) + tuple(t for t in (tr, et) if t is not None)
+        return out if len(out) > 1 else x
     if multistep is not None:
         msw, hist = multistep
         check(_lib.load().sd_ddim_sample_multistep(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
@@ -511,15 +618,19 @@ class GraphedSampler:
     together with ``pin`` (compose them through ``hold_mask(rows=...)``).  ``multistep=w`` (``multistep_weights``) captures the
     second-order multistep rollout (``sd_ddim_sample_multistep``) on a static history buffer, which no replay needs cleared: its first
     step does not read it.  With ``pin=True`` the pin is folded into a mask (J <= 32): the graph is captured on hold buffers and a replay's
-    ``pin=(known, rows)`` becomes ``hold_mask(rows=rows)``.  (One native call for all of them: ``_ddim_sample_native``.)"""
+    ``pin=(known, rows)`` becomes ``hold_mask(rows=rows)``.  ``limits=True`` captures the call under per-joint limits
+    (``sd_ddim_sample_limits``, ``reproject`` fixed at capture) on two static (32,) arrays, ``self.limits``, which the kernels read on the
+    device at every step: they start unlimited, ``set_limits`` rewrites them in place and the captured rollout stays captured; a pin is
+    folded into a mask as under ``multistep``.  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
-                 draws: int = 1, hold: bool = False, multistep=None):
+                 draws: int = 1, hold: bool = False, multistep=None, limits: bool = False, reproject: bool = False):
         dev = step_tokens.device
         if pin and hold:
             raise ValueError("GraphedSampler: pin and hold exclude each other - compose them through ops.hold_mask(rows=...)")
         self.multistep = None if multistep is None else _multistep_req(multistep, len(coef))
-        self.pin_as_hold = bool(pin) and self.multistep is not None
+        self.limits, self.reproject = (joint_limits({}, J=packed.J, device=dev) if limits else None), bool(reproject)
+        self.pin_as_hold = bool(pin) and (self.multistep is not None or self.limits is not None)
         if self.pin_as_hold:
             pin, hold = False, True
         self.draws = _draws_req(draws, B, None)
@@ -553,12 +664,21 @@ class GraphedSampler:
 
     def _run(self):
         _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws,
-                            self.hold, None if self.multistep is None else (self.multistep, self.hist))
+                            self.hold, None if self.multistep is None else (self.multistep, self.hist),
+                            None if self.limits is None else (self.limits.lo, self.limits.hi, self.reproject))
+
+    def set_limits(self, limits) -> None:
+        """Rewrites the captured limit arrays in place (``limits`` as ``ddim_sample`` takes it): every later replay runs under them."""
+        if self.limits is None:
+            raise ValueError("GraphedSampler: set_limits needs a graph captured with limits=True")
+        new = _limits_req(limits, self.packed.J, self.x.device)
+        self.limits.lo.copy_(new.lo)
+        self.limits.hi.copy_(new.hi)
 
     def replay_into(self, ctx: Optional[Tensor], x_T: Tensor, pin=None, hold=None) -> Tensor:
         """Copies the inputs into the captured buffers, replays, and returns the captured x buffer itself
         (overwritten by the next replay)."""
-        if self.pin_as_hold:   # a multistep graph captured with pin=True: the pin as a mask
+        if self.pin_as_hold:   # a multistep or limits graph captured with pin=True: the pin as a mask
             if pin is None or hold is not None:
                 raise ValueError("GraphedSampler: a graph captured with pin=True takes pin=(known, rows) at every call, one without takes none")
             known, rows = _pin_req(pin, *self.x.shape, self.x.device)
@@ -592,7 +712,7 @@ class GraphedSampler:
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None):
+                eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None, limits=None, reproject: bool = False):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -615,7 +735,14 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     ``multistep = w`` (``multistep_weights``: (n_steps,) fp32, w[0] == 0): the second-order multistep solver (``sd_ddim_sample_multistep``) -
     after the DDIM update of step i, ``x += w[i] * (x0[i - 1] - x0[i])``; no extra denoiser evaluation, and all zeros is DDIM.  It composes
     with everything above; a ``pin`` is folded into ``hold_mask(rows=rows)`` for this call (J <= 32).  The trajectory routes run one
-    multistep kernel per step (no fused rollout form)."""
+    multistep kernel per step (no fused rollout form).
+    ``limits = (lo, hi)``, a range r, ``{joint: (lo, hi)}`` or ``joint_limits(...)``: per-joint limits in normalised space
+    (``sd_ddim_sample_limits``; diffusers' ``clip_sample``, per joint) - at every step the predicted clean trajectory x0 is clamped to
+    [lo[j], hi[j]] before the update is formed from it, in the lane that holds it, so the last step returns every free element bitwise
+    inside the limits; a NaN stays NaN.  ``reproject`` (diffusers' ``use_clipped_model_output``): a clamped element's eps is recomputed
+    from the clamped x0.  Held elements keep the hold's value whatever the limits say; ``eps_trace`` stays the network's prediction.  It
+    composes with everything above (a ``pin`` is folded into a mask: J <= 32); infinite limits are the multistep call bit for bit.  One
+    limits kernel per step on the trajectory routes (no fused rollout form)."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
     if pin is not None and hold is not None:
         raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
@@ -638,10 +765,13 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         _req(status, "status", torch.int32)
     if pin is not None:
         pin = _pin_req(pin, B, T, J, x_T.device)
-        if multistep is not None:   # the multistep kernels take a mask: the pin as its leading full rows
+        if multistep is not None or limits is not None:   # the multistep and limits kernels take a mask: the pin as its leading full rows
             hold, pin = (pin[0], hold_mask(torch.zeros(J, dtype=torch.bool, device=x_T.device), B, T, J, x_T.device, rows=pin[1])), None
     if hold is not None:
         hold = _hold_req(hold, B, T, J, x_T.device)
+    if limits is not None:
+        limits = _limits_req(limits, J, x_T.device)
+        limits = (limits.lo, limits.hi, bool(reproject))
     x = x_T if inplace else x_T.clone()
     tr = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if trace else None
     et = torch.empty(n_steps, B, T, J, dtype=torch.float32, device=x.device) if eps_trace else None
@@ -652,7 +782,7 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         hold = (hold[0], x_T.clone() if inplace else x_T, hold[1])
     if multistep is not None:   # (weights, history): the history is written before it is read - no clearing
         multistep = (multistep, torch.empty_like(x))
-    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep)
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep, limits)
 
 
 def default_sampler_cap() -> int:
@@ -675,14 +805,15 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
-                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, multistep=None):
+                        trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, multistep=None,
+                        limits=None, reproject: bool = False):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin``, ``hold``, ``draws`` and ``multistep``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
+    ``pin``, ``hold``, ``draws``, ``multistep``, ``limits`` and ``reproject``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
     rows: correct, not shared; a repeat restarts from ``x_T``, so the multistep history needs nothing more)."""
     import warnings
 
@@ -695,9 +826,12 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         hold = _hold_req(hold, *x_T.shape, x_T.device)
     if multistep is not None:
         multistep = _multistep_req(multistep, step_tokens.shape[0])
+    if limits is not None:
+        limits = _limits_req(limits, x_T.shape[2], x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
-    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold, multistep=multistep)
+    out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold, multistep=multistep,
+                      limits=limits, reproject=reproject)
     word = int(status.item())
     if word == 0:
         return out
@@ -707,7 +841,8 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         # of the checkpoint, so later calls with these weights start there.
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
-            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold, multistep=multistep)
+            out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold, multistep=multistep,
+                              limits=limits, reproject=reproject)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -716,7 +851,8 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     if mode >= 2:
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold, multistep=multistep)
+        out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold, multistep=multistep,
+                          limits=limits, reproject=reproject)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
@@ -2158,6 +2294,21 @@ def session_hold_mask(mask: Tensor, held: Tensor, pin_rows: Optional[Tensor], J:
     check(_lib.load().sd_session_hold_mask(mask.data_ptr(), held.data_ptr(), _ptr(pin_rows), _ptr(robots), S, B, mask.shape[1], int(J), int(draws),
                                            _stream()), "sd_session_hold_mask")
     return mask
+
+
+def session_limits(limits: Limits, lo_rad, hi_rad, mean: Tensor, std: Tensor, J: int) -> Limits:
+    """One launch (``sd_session_limits``) writes ``limits`` - the two (32,) device arrays a session's rollout reads - from limits in
+    radians as published (``lo_rad``, ``hi_rad``: host arrays of at least J fp32, e.g. ``PolicySession.check_limits``'s): the inverse of
+    the commit's expression, each bound moved inward until the commit's expression gives a value inside the radians."""
+    lo_rad, hi_rad = np.ascontiguousarray(lo_rad, dtype=np.float32), np.ascontiguousarray(hi_rad, dtype=np.float32)
+    if lo_rad.ndim != 1 or hi_rad.ndim != 1 or lo_rad.shape[0] < J or hi_rad.shape[0] < J:
+        raise ValueError(f"session_limits: lo_rad and hi_rad must hold at least {J} floats")
+    limits = _limits_req(limits, J, mean.device)
+    _req(mean, "mean"); _req(std, "std")
+    check(_lib.load().sd_session_limits(limits.lo.data_ptr(), limits.hi.data_ptr(), lo_rad.ctypes.data_as(_lib.c_float_p),
+                                        hi_rad.ctypes.data_as(_lib.c_float_p), mean.data_ptr(), std.data_ptr(), int(J), _stream()),
+          "sd_session_limits")
+    return limits
 
 
 def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0,

@@ -5,6 +5,9 @@ ml/inference/plot.py:71-73,124-131; ml/training/distill.py:151-152,179-189).
 Constructed exactly like the reference does — ``DDIMScheduler(beta_schedule=
 "squaredcos_cap_v2", clip_sample=False)`` — everything else is the diffusers default
 (1000 train steps, epsilon prediction, leading spacing, eta = 0, final alpha 1).
+``clip_sample=True`` (diffusers' default, which the reference switches off) is accepted as well: ``step`` clamps the predicted clean
+sample to +- ``clip_sample_range`` - or to the per-joint ``limits`` of the constructor, which diffusers has not - before it forms the
+update (``sd_ddim_limit_step``); ``step(..., use_clipped_model_output=True)`` recomputes a clamped element's model output from it.
 diffusers itself is not available offline: scheduler parity is UNPINNED."""
 
 from __future__ import annotations
@@ -18,12 +21,17 @@ from . import ops
 
 class DDIMScheduler:
     def __init__(self, num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2",
-                 clip_sample: bool = False, prediction_type: str = "epsilon"):
-        if beta_schedule != "squaredcos_cap_v2" or clip_sample or prediction_type != "epsilon":
+                 clip_sample: bool = False, prediction_type: str = "epsilon", clip_sample_range: float = 1.0, limits=None):
+        if beta_schedule != "squaredcos_cap_v2" or prediction_type != "epsilon":
             raise NotImplementedError("only the configuration the reference uses is implemented: "
-                                      "beta_schedule='squaredcos_cap_v2', clip_sample=False, epsilon prediction")
+                                      "beta_schedule='squaredcos_cap_v2', epsilon prediction")
+        if not float(clip_sample_range) >= 0:
+            raise ValueError(f"clip_sample_range must be >= 0, got {clip_sample_range}")
         self.config = {"num_train_timesteps": num_train_timesteps, "beta_schedule": beta_schedule,
-                       "clip_sample": clip_sample, "prediction_type": prediction_type}
+                       "clip_sample": bool(clip_sample), "prediction_type": prediction_type, "clip_sample_range": float(clip_sample_range)}
+        # what step clamps the predicted clean sample to: per-joint limits (ops.joint_limits' forms), else +- clip_sample_range, else nothing
+        self._limits_spec = limits if limits is not None else (float(clip_sample_range) if clip_sample else None)
+        self._limits_dev: dict = {}
         self._table_len = num_train_timesteps
         self.alphas_cumprod = ops.alphas_cumprod(num_train_timesteps)  # CPU fp32, like diffusers
         self._acp_dev: dict = {}
@@ -56,11 +64,24 @@ class DDIMScheduler:
         self.timesteps = torch.tensor(ops.ddim_timesteps(num_inference_steps, self._table_len), dtype=torch.int64,
                                       device=device)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor):
+    def _limits(self, sample: torch.Tensor):
+        """The limits as the kernel reads them, on the sample's device for its last dimension (the joints), or None: no clipping."""
+        if self._limits_spec is None:
+            return None
+        key = (sample.device, sample.shape[-1])
+        if key not in self._limits_dev:
+            self._limits_dev[key] = ops._limits_req(self._limits_spec, sample.shape[-1], sample.device)
+        return self._limits_dev[key]
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, use_clipped_model_output: bool = False):
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps before step")
         t = int(timestep)
         coef = ops.ddim_coefficients([t], self.alphas_cumprod, self.num_inference_steps, self._table_len)[0]
+        limits = self._limits(sample)
+        if limits is not None:
+            return SimpleNamespace(prev_sample=ops.limit_step(model_output.contiguous(), sample.contiguous(), coef, limits,
+                                                              reproject=use_clipped_model_output))
         return SimpleNamespace(prev_sample=ops.ddim_step(model_output.contiguous(), sample.contiguous(), coef))
 
 
@@ -69,7 +90,8 @@ class MultistepScheduler(DDIMScheduler):
     ``set_timesteps``, ``timesteps`` and ``add_noise`` of ``DDIMScheduler``; ``step(model_output, t, sample).prev_sample`` is the DDIM
     update plus ``w * (x0 of the step before - x0 of this step)`` (``ops.multistep_weights``, ``sd_multistep_step``: one launch).  The
     previous x0 stays on the device, in a buffer of the sample's shape; ``set_timesteps`` clears the history, so every rollout starts
-    first order, and the steps must then be taken in the order of ``timesteps``.
+    first order, and the steps must then be taken in the order of ``timesteps``.  ``clip_sample`` / ``clip_sample_range`` / ``limits`` as
+    ``DDIMScheduler`` takes them: the history then holds the clamped x0.
 
     It runs on THIS project's leading grid (``ops.ddim_timesteps``: t - ratio, the last step to alpha = 1), not on a grid of its own, so
     that its step counts compare with ``DDIMScheduler``'s: n steps here evaluate the denoiser at the same n timesteps.  Parity with
@@ -86,7 +108,7 @@ class MultistepScheduler(DDIMScheduler):
         self._weights = ops.multistep_weights(self._grid, self.alphas_cumprod, num_inference_steps, self._table_len)
         self._hist, self._next = None, 0
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor):
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, use_clipped_model_output: bool = False):
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps before step")
         t = int(timestep)
@@ -99,6 +121,11 @@ class MultistepScheduler(DDIMScheduler):
         coef = ops.ddim_coefficients([t], self.alphas_cumprod, self.num_inference_steps, self._table_len)[0]
         if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
             self._hist = torch.empty_like(sample, memory_format=torch.contiguous_format)
-        out = ops.multistep_step(model_output.contiguous(), sample.contiguous(), self._hist, coef, float(self._weights[i]))
+        limits = self._limits(sample)
+        if limits is not None:   # clip_sample / limits: the history holds the clamped x0
+            out = ops.limit_step(model_output.contiguous(), sample.contiguous(), coef, limits, hist=self._hist, w=float(self._weights[i]),
+                                 reproject=use_clipped_model_output)
+        else:
+            out = ops.multistep_step(model_output.contiguous(), sample.contiguous(), self._hist, coef, float(self._weights[i]))
         self._next = i + 1
         return SimpleNamespace(prev_sample=out)

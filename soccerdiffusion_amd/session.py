@@ -73,6 +73,7 @@ class _GraphedTick:
         self.tokens = m.step_encoding.table(ts, dev)
         self.coef = ops.ddim_coefficients(ts, ops.alphas_cumprod(), session.n_steps)
         self.msw = ops.multistep_weights(ts, ops.alphas_cumprod(), session.n_steps) if session.solver == "multistep" else None
+        self.lim = session._lim()   # (limits: the session's own device arrays, which set_limits rewrites in place - the capture stays)
         self.cap = ops.sampler_cap(self.packed, 3)
         self.noise = x_T.clone()
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -93,11 +94,11 @@ class _GraphedTick:
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
         if s.draws == 1:
             self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
-                                     multistep=self.msw)
+                                     multistep=self.msw, **self.lim)
             return
         # G draws per robot on the shared context, and their medoid: the selection is part of the captured tick
         self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
-                                   draws=s.draws, multistep=self.msw)
+                                   draws=s.draws, multistep=self.msw, **self.lim)
         self.index, self.x = ops.select_medoid(self.all, s.draws)
 
     def __call__(self, x_T: torch.Tensor):
@@ -108,7 +109,7 @@ class _GraphedTick:
         if int(self.status.item()) == 0:
             return self.x if s.draws == 1 else (self.x, self.all, self.index)
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
-        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver).contiguous()
+        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver, **s._lim()).contiguous()
         if s.draws == 1:
             return x
         index, chosen = ops.select_medoid(x, s.draws)
@@ -118,7 +119,7 @@ class _GraphedTick:
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
-                 select: str = "medoid", holds: bool = False, solver: str = "ddim"):
+                 select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -140,13 +141,24 @@ class PolicySession:
         ``solver``: "ddim" (default: the session without this argument, launch for launch) or "multistep" - every tick's rollout runs the
         second-order multistep solver (``model.sample(solver="multistep")``) on the same ``num_inference_steps`` timesteps; meant for fewer
         steps per tick.  It composes with ``carry`` (the carried rows become the mask's leading rows: the seam stays bit-exact; J <= 32),
-        ``holds``, ``draws``, ``robots=`` and ``use_graph``.  Not for a distilled decoder."""
+        ``holds``, ``draws``, ``robots=`` and ``use_graph``.  Not for a distilled decoder.
+        ``limits = (lo, hi)`` ((J,) floats, one range r, or ``{joint: (lo, hi)}``) / ``reproject``: joint limits in radians AS PUBLISHED
+        (after ``- pi``), as real numbers without modular arithmetic; -inf / +inf: no limit.  One launch converts them to normalised space
+        on the device, each bound moved inward until the commit's expression gives a value inside the radians (``sd_session_limits``), and
+        every tick's rollout clamps the predicted clean trajectory to them at every step (``ops.ddim_sample(limits=...)``): the published
+        trajectory of every tick lies inside the given radians bit for bit, with no clamp in the commit and no extra launch per tick.
+        ``set_limits`` rewrites the same device arrays, safe under ``use_graph``.  It composes with ``carry`` (the carried rows travel as
+        mask bits, as under ``holds``: the seam stays exact, and they were published under the limits; J <= 32), ``holds`` (a held joint
+        keeps its value whatever the limits say), ``draws``, ``robots=``, ``solver`` and ``use_graph``.  Without the argument every launch
+        is the one of the session without any of this.  Not for a distilled decoder."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
         self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
         self.holds = self.check_hold(holds, model.num_joints, self.distilled)                                              # (likewise)
         self.solver = self.check_solver(solver, model.num_joints, self.carry, self.distilled)                              # (likewise)
+        limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled)                                   # (likewise)
+        self.reproject = bool(reproject)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -177,6 +189,10 @@ class PolicySession:
                 raise ValueError("PolicySession: a model with images needs hyperparams with image_resolution (and image_context_length "
                                  "where it has no sequence encoder)")
             self.S, self.R = int(S), int(R)
+        self._limits = None   # the normalised limits the rollout reads (two (32,) device arrays): they survive reset()
+        if limits is not None:
+            self._limits = ops.joint_limits({}, J=self.J, device=self.device)
+            ops.session_limits(self._limits, *limits, model.mean, model.std, self.J)
         self.reset()
 
     @staticmethod
@@ -229,6 +245,33 @@ class PolicySession:
         if solver == "multistep" and carry > 0 and not 1 <= int(J) <= 32:
             raise ValueError(f"solver: with carry the multistep rollout pins rows through a 32-bit mask word per row, got J = {J}")
         return solver
+
+    @staticmethod
+    def check_limits(limits=None, J: int = 1, carry: int = 0, distilled: bool = False):
+        """``limits`` of a session with J joints, validated (no device needed): None, or the two (32,) fp32 host arrays in radians, padded
+        with -inf / +inf (``(lo, hi)`` of (J,) floats, one range r, or ``{joint: (lo, hi)}``, as ``ops.joint_limits`` takes them).
+        ValueError for a wrong shape, a NaN or lo > hi, with a distilled decoder (no rollout to limit), or with ``carry`` and J > 32 (the
+        carried rows travel as a 32-bit mask word per row)."""
+        if limits is None:
+            return None
+        if distilled:
+            raise ValueError("limits: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if carry > 0 and not 1 <= int(J) <= 32:
+            raise ValueError(f"limits: with carry the limited rollout pins rows through a 32-bit mask word per row, got J = {J}")
+        return ops._limits_host(limits, J)
+
+    def set_limits(self, lo, hi=None) -> None:
+        """New joint limits in radians as published (``lo``, ``hi`` as the constructor's ``limits=(lo, hi)``; ``set_limits(r)`` or
+        ``set_limits({joint: (lo, hi)})`` as there): ONE small launch rewrites the session's device arrays in place, so a captured tick
+        stays captured and the next tick runs under the new limits."""
+        if self._limits is None:
+            raise RuntimeError("PolicySession.set_limits: the session was built without limits")
+        host = self.check_limits(lo if hi is None else (lo, hi), self.J, self.carry, self.distilled)
+        ops.session_limits(self._limits, *host, self.model.mean, self.model.std, self.J)
+
+    def _lim(self) -> dict:
+        """The limit arguments of the tick's rollout: none in a session without limits."""
+        return {} if self._limits is None else {"limits": self._limits, "reproject": self.reproject}
 
     @property
     def _carrying(self) -> bool:
@@ -575,9 +618,9 @@ class PolicySession:
                 if self.distilled:   # one forward at t = 0 (ros.py:293-298)
                     x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
                 elif G == 1:
-                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver)
+                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver, **self._lim())
                 else:   # the context was encoded once per robot; its G draws share the folded planes
-                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver).contiguous()
+                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver, **self._lim()).contiguous()
                     index, chosen = ops.select_medoid(every, G)
                     x = (chosen, every, index)
             if G == 1:

@@ -196,6 +196,16 @@ int sd_multistep_step(const float *eps, const float *x, float *x_prev, float *hi
 int sd_ddim_limit_step(const float *eps, const float *x, float *x_prev, float *hist_or_null, const float *coef4, float w, const float *lo,
                        const float *hi, int reproject, long n, int J, void *stream);
 
+/* One step of sd_ddim_sample_slew for a caller that evaluates the denoiser itself: sd_ddim_limit_step with the slew scan of that call over
+ * the rows of every trajectory.  eps, x, x_prev, hist: whole (B, T, J) samples - the scan needs a trajectory's rows in order.  v: 32 floats,
+ * start: (B, 32) floats or NULL, lo / hi: 32 floats each (all in device memory).  hold_x0 (B, T, J) and hold_mask (B, T): both or neither -
+ * a held element enters the scan as hold_x0 and its x_prev is the scan's update of that value (the caller's hold overwrites it).  One
+ * thread per (trajectory, joint).  SD_E_BADARG (nothing launched): a NULL operand, J outside 1 .. 32, w != 0 without hist, hist aliasing
+ * eps, x or x_prev, one of hold_x0 / hold_mask without the other. */
+int sd_ddim_slew_step(const float *eps, const float *x, float *x_prev, float *hist_or_null, const float *coef4, float w, const float *lo,
+                      const float *hi, int reproject, const float *v, const float *start_or_null, const float *hold_x0, const int32_t *hold_mask,
+                      int B, int T, int J, void *stream);
+
 /* Normalizer.normalize (inverse = 0: (x - mean) / std) and .denormalize (inverse = 1:
  * x * std + mean), per joint — soccer_diffusion/dataset/pytorch.py:410-414.  n = rows * J. */
 int sd_normalize(const float *x, const float *mean, const float *stdv, float *out, long n, int J, int inverse,
@@ -354,6 +364,32 @@ int sd_ddim_sample_limits(const sd_denoiser_weights *w, const float *ctx, const 
                           float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                           const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw, float *history,
                           const float *lo, const float *hi, int reproject, void *stream);
+/* sd_ddim_sample_limits with per-joint slew (velocity) limits beside the box: consecutive rows of the predicted clean trajectory differ by
+ * at most v[j], at every step, before the update is formed.  With x0 of row t as in sd_ddim_sample_limits, per trajectory b and joint j:
+ *   y = start[b][j]                                        (NaN, or start NULL: row 0 is free)
+ *   for t = 0 .. T-1:
+ *     a = y - v[j];  c = y + v[j]                          (fp32, one rounding each)
+ *     z = x0[t] < a ? a : (x0[t] > c ? c : x0[t])          (compares: a NaN x0 stays NaN, a NaN y limits nothing)
+ *     z = z < lo[j] ? lo[j] : (z > hi[j] ? hi[j] : z)      (the box last: it always wins)
+ *     if bit j of hold_mask[b][t]: z = hold_x0[b][t][j]    (a held element is the scan's state as it stands)
+ *     x0c[t] = z;  y = z
+ *   e' = reproject && x0c != x0 ? (x - c0 x0c) / c1 : e;   x = fma(c2, x0c, c3 e') + w (history - x0c);   history = x0c
+ * The row order is part of the definition.  v: 32 floats in device memory, v[j] >= 0, [J, 32) padded with +inf (ops.joint_slew); +inf: no
+ * limit.  start: (B, 32) floats in device memory padded with NaN, one row per TRAJECTORY (a group of draws repeats its row), or NULL.
+ * lo / hi must be given and may all be infinite.  Both arrays are read on the device at every step.
+ * The last step therefore returns every free element bitwise inside [lo, hi] and, against a predecessor p inside the box that is not NaN,
+ * inside [fl(p - v), fl(p + v)]; a jump INTO a held element is not limited.  All v infinite and no start: every step bitwise
+ * sd_ddim_sample_limits'.
+ * Kernels: on the trajectory routes the slew instantiations of the step kernels (sd_traj_slew.hip; traj_step_generic_slew_kernel), the
+ * limits twins around the scan: the storing lanes exchange x0 through an fp32 plane in LDS behind two workgroup barriers and one lane per
+ * joint walks the rows; one launch per step, no fused rollout form, no mode-4 twin (max_mode = 4 runs the mode-3 kernels).  On the
+ * row-panel and chain routes each step returns eps and ddim_slew_step_kernel - one thread per (trajectory, joint), fetching its rows in
+ * blocks ahead of the chain - updates x (and the history); the hold's launch follows it.
+ * SD_E_BADARG: as sd_ddim_sample_limits, and for v NULL. */
+int sd_ddim_sample_slew(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                        float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                        const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw, float *history,
+                        const float *lo, const float *hi, int reproject, const float *v, const float *start_or_null, void *stream);
 /* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
 int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
 
@@ -395,6 +431,9 @@ int sd_sampler_prepare_draws(const sd_denoiser_weights *w, const float *ctx, flo
 int sd_sampler_eps_draws(const sd_denoiser_weights *w, const float *step_tokens, const float *x, float *eps, float *workspace,
                          int B, int T, int Mc, int n_tok, int32_t *status, int max_mode, int draws, void *stream);
 
+/* out[n][j] = max over t of |r[t + 1] - r[t]|, r = x std + mean (fp32, two roundings): the largest step between consecutive rows of
+ * trajectory n at joint j, in the space of the denormalised trajectories.  x (N, T, J), out (N, J); one thread per (n, j).  T == 1: 0. */
+int sd_eval_max_step(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream);
 /* ---- held-out evaluation (csrc/sd_eval.hip; soccerdiffusion_amd/evaluation.py) --------------------------------------------
  * Both kernels: fp32, contraction off, no atomics, every sum in a fixed order that depends on the shape alone (written out at the top of
  * sd_eval.hip), so two runs agree bit for bit.
@@ -897,6 +936,15 @@ int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int 
  *     (x * std + mean) - pi - give a value inside [lo, hi]: the commit is monotonic in x (std > 0), so a trajectory sampled under
  *     lo_n / hi_n is published inside the radians bit for bit with no clamp in the commit.  Slots [J, 32) get -inf / +inf.  A range
  *     narrower than the commit's resolution collapses to its upper bound.  SD_E_BADARG also for lo_rad[j] > hi_rad[j] or a NaN.
+ * Slew limits (a session that hands sd_ddim_sample_slew its v and start):
+ *   sd_session_slew: ONE launch of 64 threads writes the 32-float device array v_n from v_rad, radians per row AS PUBLISHED (J floats in
+ *     HOST memory, passed by value; +inf: no limit), and bound_rad, a finite bound on |published value| per joint (J floats, HOST):
+ *     v_n[j] = (v_rad[j] - margin) / std[j] rounded toward zero, margin = std hu(XS / std) + 2 hu(XS) + 2 hu(pi + R) + 2 hu(R) with
+ *     R = bound_rad[j], XS = R + |pi - mean[j]| and hu(z) half an fp32 ulp at z, in fp64 - what the rounding of y +- v in the scan and both roundings of the commit's expression can add to a difference of two
+ *     published values.  Consecutive published rows of a rollout sampled under v_n then differ by at most v_rad[j],
+ *     evaluated exactly, as long as |published| <= bound_rad[j].  Slots [J, 32): +inf.  SD_E_BADARG also for a negative or NaN v_rad[j].
+ *   sd_session_anchor: ONE launch copies row `row` of x (S, T, J; normalised space, as sampled) into anchor (B * draws, 32), rows
+ *     (b * draws + g) for robot b = robots[s] (NULL: s) and every draw g - the start array of the robot's next tick.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
 #define SD_SESSION_MAX_RESET_RINGS 5
@@ -937,6 +985,8 @@ int sd_session_reset_carry(const sd_ring_reset *rings, int n_rings, const uint8_
 int sd_session_hold(float *pin_x0, int32_t *held, const float *values, int64_t stride_robot, int64_t stride_row, const int32_t *joints, int n,
                     const float *mean, const float *stdv, const int32_t *robots, int S, int B, int T, int J, int set, void *stream);
 int sd_session_limits(float *lo_n, float *hi_n, const float *lo_rad, const float *hi_rad, const float *mean, const float *stdv, int J, void *stream);
+int sd_session_slew(float *v_n, const float *v_rad, const float *bound_rad, const float *mean, const float *stdv, int J, void *stream);
+int sd_session_anchor(float *anchor, const float *x, const int32_t *robots, int S, int B, int T, int J, int row, int draws, void *stream);
 int sd_session_hold_mask(int32_t *mask, const int32_t *held, const int32_t *pin_rows, const int32_t *robots, int S, int B, int T, int J,
                          int draws, void *stream);
 

@@ -141,6 +141,8 @@ SIGNATURES = {
     "sd_multistep_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_float_p, C.c_float, C.c_long, C.c_void_p]),
     "sd_ddim_sample_limits": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "sd_ddim_limit_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_float_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
+    "sd_ddim_sample_slew": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sd_ddim_slew_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_float_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_sampler_route_draws": (C.c_int, [C.c_int] * 9),
     "sd_select_medoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_bn_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int]),
@@ -251,6 +253,9 @@ SIGNATURES = {
     "sd_session_hold": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
     "sd_session_hold_mask": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "sd_session_limits": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, c_float_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_session_slew": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "sd_session_anchor": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]),
+    "sd_eval_max_step": (C.c_int, [C.c_void_p] * 4 + [C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "sd_profile_enable": (C.c_int, [C.c_int]),
     "sd_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
 }

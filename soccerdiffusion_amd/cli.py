@@ -3,10 +3,10 @@ the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [-o report.json]   (evaluation.py)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -524,6 +524,7 @@ def cmd_evaluate(args) -> int:
     if args.solver != "ddim" and params.get("distilled_decoder", False):
         raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
     limits = _limits_arg(args, params)   # in the space of the target trajectories (x * std + mean), as sample --hold
+    slew = _slew_arg(args, params)       # radians per row in the same space
     model = build_model(params).to(device)
     model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
     model.eval()
@@ -532,7 +533,7 @@ def cmd_evaluate(args) -> int:
     report = evaluate(model, source, idx, steps=args.steps, draws=args.draws, grid=args.grid, seed=args.seed,
                       max_mode=3 if args.max_mode is None else args.max_mode, timesteps=_timesteps(args.timesteps) if args.timesteps else None,
                       distilled=bool(params.get("distilled_decoder", False)), solver=args.solver, limits=limits,
-                      reproject=args.reproject)
+                      reproject=args.reproject, slew=slew)
     line = json.dumps(report)
     print(line)
     if args.output:
@@ -580,6 +581,11 @@ def cmd_sample(args) -> int:
         from .evaluation import normalised_limits
 
         limits = normalised_limits(limits, model.mean, model.std)
+    slew = _slew_arg(args, params)       # radians per row in the same space
+    if slew is not None:
+        from .evaluation import normalised_slew
+
+        slew = normalised_slew(slew, model.mean, model.std, _limits_arg(args, params))
     with torch.no_grad():
         if params_need_context(params):
             batch = source.batch(mine % source.n)
@@ -590,7 +596,7 @@ def cmd_sample(args) -> int:
         if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         else:
-            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject)   # G draws for each of the B contexts, which are encoded once
+            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject, slew=slew)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
             medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
@@ -602,6 +608,8 @@ def cmd_sample(args) -> int:
         saved["hold"] = dict(args.hold)   # {joint: the value it was held at}
     if limits is not None:
         saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} or the one range of --clip, as given
+    if slew is not None:
+        saved["slew"] = args.slew   # one number, or {joint: v}, as given
     if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
         saved.update(trajectories=saved["trajectories"].view(B, G, *traj.shape[1:]), draws=G, medoid=medoid.cpu())
     torch.save(saved, out)
@@ -666,7 +674,9 @@ def cmd_rollout(args) -> int:
     arrive per tick, and the first K rows of a tick's trajectory are pinned to rows [S, S + K) of the previous one.
     --hold J=V[,J=V...]: joint J of every robot is held at V radians (as published) inside every tick's rollout, from the first tick on.
     --limits J=LO:HI[,J=LO:HI...] | --clip R [--reproject]: every published joint J stays inside [LO, HI] radians (as published), or every
-    joint inside [-R, R]: the limits act on the predicted clean trajectory inside every tick's rollout (PolicySession(limits=...))."""
+    joint inside [-R, R]: the limits act on the predicted clean trajectory inside every tick's rollout (PolicySession(limits=...)).
+    --slew V | J=V[,J=V...]: consecutive published rows differ by at most V radians (every joint, or joint J), also across two ticks
+    (PolicySession(slew=...): V = max velocity / row rate)."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
@@ -689,7 +699,7 @@ def cmd_rollout(args) -> int:
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
                                             seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver,
-                                            limits=_limits_arg(args), reproject=args.reproject)
+                                            limits=_limits_arg(args), reproject=args.reproject, slew=_slew_arg(args))
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -722,8 +732,10 @@ def cmd_rollout(args) -> int:
         saved.update(carry=session.carry, advance=session.advance)
     if args.hold:
         saved["hold"] = dict(args.hold)   # {joint: the radians it was held at}
-    if session._limits is not None:
+    if session._limits_rad is not None:
         saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} radians, or the one range of --clip
+    if args.slew is not None:
+        saved["slew"] = args.slew   # radians per row: one number, or {joint: v}
     if args.draws > 1:
         saved["draws"] = session.draws   # every published trajectory is the medoid of that many draws
     if episode is not None:
@@ -796,6 +808,31 @@ def _limits_arg(args, params: Optional[dict] = None):
     return limits
 
 
+def _slew(text: str):
+    """--slew V | J=V[,J=V...] -> one float, or {joint: v}; radians per row, v >= 0."""
+    try:
+        out = float(text) if "=" not in text else {int(j): float(v) for j, v in (item.split("=") for item in text.split(","))}
+        ok = out >= 0 if isinstance(out, float) else (len(out) == text.count(",") + 1 and all(j >= 0 and v >= 0 for j, v in out.items()))
+    except ValueError:
+        ok = False
+    if not ok:
+        raise argparse.ArgumentTypeError(f"--slew takes V or JOINT=V[,JOINT=V...] with distinct joint indices >= 0 and V >= 0, got {text!r}")
+    return out
+
+
+def _slew_arg(args, params: Optional[dict] = None):
+    """``slew`` of model.sample / evaluate / PolicySession from --slew: one number, {joint: v}, or None."""
+    if args.slew is None:
+        return None
+    if params is not None:
+        J = params["num_joints"]
+        if params.get("distilled_decoder", False):
+            raise SystemExit("--slew: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if J > 32 or (isinstance(args.slew, dict) and max(args.slew) >= J):
+            raise SystemExit(f"--slew: joint indices lie in [0, {J}) and the model has at most 32 joints")
+    return args.slew
+
+
 def _limits_saved(args):
     return float(args.clip) if args.clip is not None else {j: (lo, hi) for j, lo, hi in args.limits}
 
@@ -811,6 +848,9 @@ def _add_limit_flags(p) -> None:
                    "the predicted clean trajectory is clamped at every denoising step (model.sample(limits=...)); units as --hold's in this "
                    "subcommand (rollout: radians as published; sample / evaluate: the space of the trajectories)")
     p.add_argument("--clip", type=float, default=None, metavar="R", help="--limits with the one range [-R, R] on every joint")
+    p.add_argument("--slew", type=_slew, default=None, metavar="V | J=V[,J=V...]", help="consecutive rows of a trajectory differ by at most V "
+                   "(every joint, or joint J): the predicted clean trajectory is slew-limited at every denoising step "
+                   "(model.sample(slew=...)); radians per row, units as --limits' in this subcommand")
     p.add_argument("--reproject", action="store_true", help="with --limits / --clip: a clamped element's noise prediction is recomputed from the "
                    "clamped value (diffusers' use_clipped_model_output)")
 

@@ -350,6 +350,29 @@ __device__ __forceinline__ float limit_update(float x, float e, float lo, float 
     return __builtin_fmaf(c2, x0c, c3 * e);
 }
 
+// Per-joint slew (velocity) limits on the predicted clean trajectory (sd_ddim_sample_slew), beside LimitArgs: consecutive rows of x0 differ
+// by at most v[j] per joint.  Unlike the box this couples neighbouring rows: x0c is a sequential scan over t = 0 .. T-1 whose state y is the
+// row before (the anchor start[b][j] for row 0; NaN: none).  The row order is part of the definition.
+struct SlewArgs {
+    const float *v;       // 32 floats in device memory, >= 0, [J, 32) padded with +inf (+inf: no limit on that joint)
+    const float *start;   // [B][32] floats, padded with NaN (NaN: row 0 of that joint is free), or NULL: no anchor at all
+};
+// One row of the scan, shared by every kernel that runs it: x0 is limited to fl(y - v) .. fl(y + v) by compares - a NaN x0 stays NaN, a NaN
+// y limits nothing - then to the box [lo, hi], which always wins; a held element is the hold's value as it stands.  The result is the
+// row's x0c and the next row's y.
+__device__ __forceinline__ float slew_row(float x0, float y, float v, float lo, float hi, bool held, float known) {
+    const float a = y - v, c = y + v;
+    float z = x0 < a ? a : (x0 > c ? c : x0);
+    z = z < lo ? lo : (z > hi ? hi : z);
+    return held ? known : z;
+}
+// The rest of a slewed element is limit_update's, on the scan's x0c: fma(c2, x0c, c3 e') with e' recomputed from x0c where reproject is set
+// and the element moved.
+__device__ __forceinline__ float slew_update(float x, float e, float x0, float x0c, float c0, float c1, float c2, float c3, int reproject) {
+    if (reproject && !(x0c == x0)) e = __builtin_fmaf(-c0, x0c, x) / c1;
+    return __builtin_fmaf(c2, x0c, c3 * e);
+}
+
 // One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
 // (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
 struct StepReq {
@@ -364,6 +387,7 @@ struct StepReq {
     const HoldArgs *hold = nullptr;   // or NULL; needs coef, excludes pin (one hold kernel serves every draws >= 1)
     const MultistepArgs *ms = nullptr;   // or NULL; needs coef, excludes pin: the multistep twins (hold then optional, its mask too)
     const LimitArgs *lim = nullptr;      // or NULL; needs ms (whose hist may then be NULL): the limits twins
+    const SlewArgs *slew = nullptr;      // or NULL; needs lim (whose bounds may all be infinite): the slew twins
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

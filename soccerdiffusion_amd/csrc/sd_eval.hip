@@ -111,7 +111,35 @@ __global__ __launch_bounds__(THREADS) void trajectory_errors_kernel(const float 
     }
 }
 
+// The largest step between consecutive rows of every trajectory, per joint: out[n][j] = max_t |r[t + 1] - r[t]| with r = x std + mean (the
+// commit's denormalisation, two roundings; a constant shift such as the published - pi changes no difference beyond its rounding).  One
+// thread per (trajectory, joint) walks the rows in order; a maximum has no order to fix.  T == 1: 0.  A NaN difference is skipped by fmaxf.
+__global__ void max_step_kernel(const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ stdv, float *__restrict__ out,
+                                long N, int T, int J) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * J) return;
+    const long n = i / J;
+    const int j = (int)(i - n * J);
+    const float sd = stdv[j], mu = mean[j];
+    const float *xn = x + n * (long)T * J + j;
+    float prev = xn[0] * sd + mu, worst = 0.f;
+    for (int t = 1; t < T; ++t) {
+        const float cur = xn[(long)t * J] * sd + mu;
+        worst = fmaxf(worst, fabsf(cur - prev));
+        prev = cur;
+    }
+    out[i] = worst;
+}
+
 }   // namespace ev
+
+extern "C" int sd_eval_max_step(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream) {
+    if (!x || !mean || !stdv || !out || N <= 0 || T < 1 || J < 1 || J > ev::MAX_J || N * J > 0x7fffffffL * 256)
+        return fail(SD_E_BADARG, "sd_eval_max_step: x, mean, std and out must be given; N > 0, T >= 1, 1 <= J <= 32");
+    SD_LAUNCH(ev::max_step_kernel, dim3((unsigned)((N * J + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, mean, stdv, out, N, T, J);
+    SD_CHECK_LAUNCH("max_step_kernel");
+    return 0;
+}
 
 extern "C" int sd_eval_sqerr_rows(const float *a, const float *b, float *out, long rows, long per, void *stream) {
     if (!a || !b || !out || rows <= 0 || rows > 0x7fffffffL || per <= 0)

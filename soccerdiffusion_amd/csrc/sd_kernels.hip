@@ -2543,6 +2543,57 @@ __global__ void ddim_limit_step_kernel(const float *__restrict__ eps, const floa
         if (hist) hist[i] = x0c;
     }
 }
+// The kernel above with per-joint slew limits beside the box (SlewArgs, sd_common.h): one thread per (trajectory b, joint j) walks the T
+// rows in order, because row t's limit is row t-1's result (slew_row: the scan's one definition).  Only the compares depend on the chain:
+// the thread fetches SLEW_BLOCK rows of eps, x, the mask words, the held values and the history at a time - every load of a block is
+// requested before the block's first compare, so a block costs one memory round trip, not one per row (x and x_next may alias: the
+// compiler cannot move a row's loads above the row before's stores by itself) - forms their x0, runs the chain in registers, then stores.
+// hold.mask / hold.x0 (both or neither): a held element enters the scan as the hold's value, and the hold's own launch behind this one
+// writes its x.  The row-panel and chain routes of sd_ddim_sample_slew launch it behind a step that returned eps and left x alone (the
+// trajectory routes run the scan inside the step kernels' slew twins); sd_ddim_slew_step is the loop form's step.
+constexpr int SLEW_BLOCK = 16;
+__global__ __launch_bounds__(64) void ddim_slew_step_kernel(const float *__restrict__ eps, const float *x, float *x_next, float *hist, float c0, float c1, float c2,
+                                      float c3, float w, LimitArgs lim, SlewArgs sl, HoldArgs hold, int B, int T, int J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J, j = i - b * J;
+    const float v = sl.v[j], lo = lim.lo[j], hi = lim.hi[j];
+    float y = sl.start ? sl.start[b * 32 + j] : __builtin_nanf("");
+    for (int t0 = 0; t0 < T; t0 += SLEW_BLOCK) {
+        float e[SLEW_BLOCK], xv[SLEW_BLOCK], kn[SLEW_BLOCK], hs[SLEW_BLOCK];
+        unsigned m[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the block's loads: none depends on y
+            const int t = t0 + k < T ? t0 + k : T - 1;   // (a ragged last block reads its last row again)
+            const long at = ((long)b * T + t) * J + j;
+            e[k] = eps[at];
+            xv[k] = x[at];
+            m[k] = hold.mask ? (((unsigned)hold.mask[(long)b * T + t] >> j) & 1u) : 0u;
+            hs[k] = w != 0.f ? hist[at] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            const int t = t0 + k < T ? t0 + k : T - 1;
+            kn[k] = m[k] ? hold.x0[((long)b * T + t) * J + j] : 0.f;
+        }
+        float x0[SLEW_BLOCK], x0c[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) x0[k] = __builtin_fmaf(-c1, e[k], xv[k]) / c0;
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the chain, in row order
+            if (t0 + k < T) y = x0c[k] = slew_row(x0[k], y, v, lo, hi, m[k] != 0u, kn[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            if (t0 + k >= T) continue;
+            const long at = ((long)b * T + t0 + k) * J + j;
+            float xn = slew_update(xv[k], e[k], x0[k], x0c[k], c0, c1, c2, c3, lim.reproject);
+            if (w != 0.f) xn = __builtin_fmaf(w, hs[k] - x0c[k], xn);
+            x_next[at] = xn;
+            if (hist) hist[at] = x0c[k];
+        }
+    }
+}
 
 
 // ======================================================================================
@@ -3007,13 +3058,14 @@ struct TrajCall {
     // hold: the hold instantiations (held elements; never beside a pin)
     // ms: the multistep instantiations (the second-order solver's history term; a hold beside it is optional, never a pin)
     // lim: the limits instantiations (needs ms, whose history may then be NULL: first-order DDIM)
+    // slew: the slew instantiations (needs lim): the limits epilogue around the scan over the rows
     StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr,
-                const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr) const {
-        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms, lim};
+                const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr, const SlewArgs *slew = nullptr) const {
+        return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms, lim, slew};
     }
     int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr,
-             const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr) const {
-        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms, lim);
+             const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr, const SlewArgs *slew = nullptr) const {
+        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms, lim, slew);
         return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
     }
     // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
@@ -3061,12 +3113,24 @@ static int ddim_limit_step(const float *eps, const float *x, float *x_next, floa
     SD_CHECK_LAUNCH("ddim_limit_step_kernel");
     return 0;
 }
+// x <- the same update on x0 under the slew scan and the box, hist <- that x0c where hist is given (ddim_slew_step_kernel)
+static int ddim_slew_step(const float *eps, const float *x, float *x_next, float *hist, const float *coef4, float w, const LimitArgs &lim,
+                          const SlewArgs &sl, const HoldArgs *hold, int B, int T, int J, hipStream_t st) {
+    const HoldArgs h = hold ? *hold : HoldArgs{nullptr, nullptr, nullptr};
+    SD_LAUNCH(ddim_slew_step_kernel, dim3((B * J + 63) / 64), dim3(64), 0, st, eps, x, x_next, hist, coef4[0], coef4[1], coef4[2], coef4[3], w, lim, sl, h,
+              B, T, J);
+    SD_CHECK_LAUNCH("ddim_slew_step_kernel");
+    return 0;
+}
 // The second-order multistep solver of a rollout (sd_ddim_sample_multistep): w[i] of step i (host) and the history array (device).
 // lim (sd_ddim_sample_limits): per-joint limits on x0; w and hist may then both be NULL - first-order DDIM under limits.
+// slew (sd_ddim_sample_slew; needs lim): per-joint slew limits beside them - the step kernels' slew twins, or ddim_slew_step_kernel behind a
+// row-panel step.
 struct MultistepCall {
     const float *w;
     float *hist;
     const LimitArgs *lim = nullptr;
+    const SlewArgs *slew = nullptr;
     float weight(int i) const { return w ? w[i] : 0.f; }
 };
 
@@ -3094,7 +3158,9 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
         // the noise prediction of this step (the very values the DDIM update consumes), when the caller asked for them
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
         const MultistepArgs ms{msc ? msc->hist : nullptr, msc ? msc->weight(i) : 0.f};   // (no fused rollout form: one launch per step, like a hold)
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr, msc ? msc->lim : nullptr))) return rc;
+        // (slew: the slew twins of the step kernels - the scan over the rows runs inside the step launch, behind an exchange of x0 through LDS)
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr, msc ? msc->lim : nullptr, msc ? msc->slew : nullptr)))
+            return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
     return status ? finite_check(x, n, status, c.st) : 0;
@@ -3184,7 +3250,9 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
             rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x_up, coef + 4 * i}, st);
             if (rc) return rc;
         }
-        if (msc && (rc = msc->lim ? ddim_limit_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, n, w->J, st)
+        if (msc && msc->slew) {
+            if ((rc = ddim_slew_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, *msc->slew, hold, B, T, w->J, st))) return rc;
+        } else if (msc && (rc = msc->lim ? ddim_limit_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, n, w->J, st)
                                   : ddim_multistep(eps_i, x, x, msc->hist, coef + 4 * i, msc->w[i], n, st)))
             return rc;
         // these routes are many launches per step already: the pinned rows are one more, behind the fused DDIM sites
@@ -3331,6 +3399,32 @@ extern "C" int sd_ddim_sample_limits(const sd_denoiser_weights *w, const float *
                            false, draws, n_hold ? &hold : nullptr, &msc);
 }
 
+// sd_ddim_sample_limits with per-joint slew limits beside the box (SlewArgs, sd_common.h), on every route.  v: 32 floats (device), start:
+// (B, 32) floats (device) or NULL.  lo / hi must be given; they may all be infinite.
+extern "C" int sd_ddim_sample_slew(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                   float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                   int max_mode, const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws,
+                                   const float *msw, float *history, const float *lo, const float *hi, int reproject, const float *v,
+                                   const float *start, void *stream) {
+    const int n_hold = (hold_x0 ? 1 : 0) + (hold_noise ? 1 : 0) + (hold_mask ? 1 : 0);
+    if (!lo || !hi || !v || n_steps <= 0) return fail(SD_E_BADARG, "sd_ddim_sample_slew: lo, hi and v (32 floats each, device) must be given");
+    if (n_hold != 0 && n_hold != 3) return fail(SD_E_BADARG, "sd_ddim_sample_slew: hold_x0, hold_noise and hold_mask must be given together");
+    if (msw && !history) return fail(SD_E_BADARG, "sd_ddim_sample_slew: msw needs a history buffer (both NULL: DDIM)");
+    if (msw && msw[0] != 0.f) return fail(SD_E_BADARG, "sd_ddim_sample_slew: msw[0] must be 0 (the first step has no history)");
+    if (history && (history == x || (n_hold && (history == hold_x0 || history == hold_noise || (const void *)history == (const void *)hold_mask))))
+        return fail(SD_E_BADARG, "sd_ddim_sample_slew: history must alias neither x nor the hold buffers");
+    if (n_hold && hold_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_slew: hold_noise must not alias x (x is overwritten by the first step)");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_slew: draws must be >= 1 and divide B");
+    if (w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_slew: lo, hi and v describe at most 32 joints");
+    if (w && (long)B * w->J > 0x7fffffffL) return fail(SD_E_BADARG, "sd_ddim_sample_slew: B * J must fit 31 bits");
+    const HoldArgs hold{hold_x0, hold_noise, hold_mask};
+    const LimitArgs lim{lo, hi, reproject ? 1 : 0};
+    const SlewArgs sl{v, start};
+    const MultistepCall msc{msw, history, &lim, &sl};
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, draws, n_hold ? &hold : nullptr, &msc);
+}
+
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)
 extern "C" int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws) {
     if (max_mode < -1 || max_mode > 4 || draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_sampler_route_draws: bad argument");
@@ -3469,6 +3563,20 @@ extern "C" int sd_ddim_limit_step(const float *eps, const float *x, float *x_pre
     if (!hist && w != 0.f) return fail(SD_E_BADARG, "sd_ddim_limit_step: a history weight needs a history buffer");
     if (hist && (hist == x || hist == x_prev || hist == eps)) return fail(SD_E_BADARG, "sd_ddim_limit_step: hist must alias neither eps, x nor x_prev");
     return ddim_limit_step(eps, x, x_prev, hist, coef4, w, LimitArgs{lo, hi, reproject ? 1 : 0}, n, J, (hipStream_t)stream);
+}
+
+// sd_ddim_limit_step with the slew scan: x is (B, T, J) whole; hold_x0 / hold_mask: both or neither (held elements enter the scan as given).
+extern "C" int sd_ddim_slew_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, const float *lo, const float *hi,
+                                 int reproject, const float *v, const float *start, const float *hold_x0, const int32_t *hold_mask, int B, int T, int J,
+                                 void *stream) {
+    if (!eps || !x || !x_prev || !coef4 || !lo || !hi || !v || B <= 0 || T <= 0 || J < 1 || J > 32 || (long)B * J > 0x7fffffffL)
+        return fail(SD_E_BADARG, "sd_ddim_slew_step: bad argument");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_ddim_slew_step: hold_x0 and hold_mask must be given together");
+    if (!hist && w != 0.f) return fail(SD_E_BADARG, "sd_ddim_slew_step: a history weight needs a history buffer");
+    if (hist && (hist == x || hist == x_prev || hist == eps)) return fail(SD_E_BADARG, "sd_ddim_slew_step: hist must alias neither eps, x nor x_prev");
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    return ddim_slew_step(eps, x, x_prev, hist, coef4, w, LimitArgs{lo, hi, reproject ? 1 : 0}, SlewArgs{v, start}, hold_mask ? &hold : nullptr, B, T, J,
+                          (hipStream_t)stream);
 }
 
 extern "C" int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t, float sqrt_1m_a_t,

@@ -314,6 +314,44 @@ __global__ void session_limits_kernel(float *lo_n, float *hi_n, SessionLimits ra
     hi_n[j] = hi;
 }
 
+// ---- slew limits (PolicySession(slew=...): sd_ddim_sample_slew's v, from radians per row as published) ---------------------------------
+struct SessionSlew {   // one set_slew call by value: v in radians per row, and the bound R[j] on |published value| of joint j
+    float v[32], r[32];
+};
+// half an ulp of the fp32 binade of z (1 + 2^-20): the most one rounding to nearest adds to a result of magnitude <= z
+__device__ __forceinline__ double half_ulp(double z) { return z > 0.0 ? ldexp(1.0, ilogb(z * (1.0 + 9.5367431640625e-07)) - 24) : 0.0; }
+// One thread per slot.  v_n = (v_rad - margin) / std, rounded toward zero, with
+//   margin = std hu(XS / std) + 2 hu(XS) + 2 hu(pi + R) + 2 hu(R),   XS = R + |pi - mean|,   hu = half_ulp
+// in fp64 (DESIGN.md 5.7.4 derives it): consecutive rows of the rollout differ by at most fl(y + v_n) - y <= v_n + hu(|x|) in normalised
+// space, |x| <= XS / std; the commit multiplies that by std and adds up to three roundings per published value in its plain form (x * std,
+// + mean, - pi: two in the fused form), each half an ulp of its result: |x std| <= XS, |x std + mean| <= R + pi, |published| <= R.  So the fp32 values the commit
+// publishes differ by at most v_rad, evaluated exactly.  A v_rad of +inf stays +inf; one not above its margin gives 0 (the host refuses
+// it before the launch).  Slots >= J: +inf.
+__global__ void session_slew_kernel(float *v_n, SessionSlew rad, const float *__restrict__ mean, const float *__restrict__ stdv, int J) {
+    const int j = threadIdx.x;
+    if (j >= 32) return;
+    float out = INFINITY;
+    if (j < J && rad.v[j] < INFINITY) {
+        const double s = (double)stdv[j], R = (double)rad.r[j], XS = R + fabs(M_PI - (double)mean[j]);
+        const double margin = s * half_ulp(XS / s) + 2.0 * half_ulp(XS) + 2.0 * half_ulp(M_PI + R) + 2.0 * half_ulp(R);
+        const double v = ((double)rad.v[j] - margin) / s;
+        out = v > 0.0 ? (float)v : 0.f;
+        if ((double)out > v) out = nextafterf(out, 0.f);
+    }
+    v_n[j] = out;
+}
+// The anchor of the next tick's scan: anchor[(b * draws + g)][j] = x[s][row][j] for robot b = robots[s] (NULL: s) and every draw g, j < J -
+// the last committed row of the robot's trajectory in normalised space, as sampled.  Slots [J, 32) keep their NaN.
+__global__ void session_anchor_kernel(float *anchor, const float *__restrict__ x, const int32_t *__restrict__ robots, int S, int B, int T, int J,
+                                      int row, int draws) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * draws * J) return;
+    const int j = i % J, g = (i / J) % draws, s = i / (J * draws);
+    const int b = robot_of(robots, s, B);
+    if (b < 0) return;
+    anchor[((long)b * draws + g) * 32 + j] = x[((long)s * T + row) * J + j];
+}
+
 // The tick's mask: mask[s * draws + g][t] = held[b] | (t < pin_rows[b] ? all J bits : 0), b = robot s of the launch (robots NULL: s);
 // pin_rows NULL: a session without carried rows.  n = S * draws * T words.
 __global__ __launch_bounds__(THREADS) void session_hold_mask_kernel(int32_t *__restrict__ mask, const int32_t *__restrict__ held,
@@ -516,6 +554,30 @@ extern "C" int sd_session_limits(float *lo_n, float *hi_n, const float *lo_rad, 
     }
     SD_LAUNCH(ss::session_limits_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lo_n, hi_n, rad, mean, stdv, J);
     SD_CHECK_LAUNCH("session_limits_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_slew(float *v_n, const float *v_rad, const float *bound_rad, const float *mean, const float *stdv, int J, void *stream) {
+    if (!v_n || !v_rad || !bound_rad || !mean || !stdv || J < 1 || J > 32)
+        return fail(SD_E_BADARG, "sd_session_slew: v_n, v_rad, bound_rad, mean and std must be given; 1 <= J <= 32");
+    ss::SessionSlew rad{};
+    for (int j = 0; j < J; ++j) {
+        if (!(v_rad[j] >= 0.f) || !(bound_rad[j] >= 0.f) || bound_rad[j] == INFINITY)
+            return fail(SD_E_BADARG, "sd_session_slew: v_rad[j] >= 0 and a finite bound_rad[j] >= 0, no NaN");
+        rad.v[j] = v_rad[j];
+        rad.r[j] = bound_rad[j];
+    }
+    SD_LAUNCH(ss::session_slew_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, v_n, rad, mean, stdv, J);
+    SD_CHECK_LAUNCH("session_slew_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_anchor(float *anchor, const float *x, const int32_t *robots, int S, int B, int T, int J, int row, int draws, void *stream) {
+    if (!anchor || !x || S < 1 || B < 1 || S > B || T < 1 || J < 1 || J > 32 || row < 0 || row >= T || draws < 1)
+        return fail(SD_E_BADARG, "sd_session_anchor: bad argument");
+    const int n = S * draws * J;
+    SD_LAUNCH(ss::session_anchor_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, anchor, x, robots, S, B, T, J, row, draws);
+    SD_CHECK_LAUNCH("session_anchor_kernel");
     return 0;
 }
 

@@ -1462,13 +1462,23 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // hold requests its mask word (32 padded floats each: always a legal f32x4), clamps with compares and selects (a NaN stays NaN), forms the
 // update from the clamped x0 (limit_update) and leaves the clamped x0 in hist.  lim.reproject is a wave-uniform branch on the kernel
 // argument.  No barrier and no LDS of its own.
+// PIN == 5, SLEW: the slew twin (SlewArgs, sd_common.h; sd_ddim_sample_slew) - the limits twin plus the exchange the scan needs, since a
+// storing lane holds the x0 of four joints of ONE row.  The epilogue runs in four phases: (1) after the fc_out MFMAs each storing lane
+// forms x0 of its elements - the hold's value where its mask bit is set - and writes it into the fp32 plane S[tok][32] and its row's mask
+// word into M[tok], both in the Q | K region, which nothing uses after the last layer's cross-attention; (2) a workgroup barrier; (3) lane
+// j < J of wave 0 runs slew_row over t = 0 .. T-1 on column j of S, in place (32 consecutive floats per row: no bank conflict; the loads
+// do not depend on the chain); (4) a second barrier, then each storing lane reads its x0c back and finishes as the limits twin does.
+// BOTH barriers stand at the top level of the epilogue, outside `if (c.w < NTT)`: all eight waves reach them.
 template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
                                                  int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{},
-                                                 const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{}) {
+                                                 const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{},
+                                                 const SlewArgs &sl = SlewArgs{}) {
     constexpr bool HOLD = PIN == 2;
     constexpr bool MS = PIN == 3;
     constexpr bool LIM = PIN == 4;
+    constexpr bool SLEW = PIN == 5;
+    static_assert(!SLEW || TMAX * 128 + TMAX * 4 <= LDS_STAT - LDS_Q, "the slew twin's S and M planes fit the Q | K region");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
@@ -1615,22 +1625,145 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
             }
         }
         f32x4 lo4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, hi4[2] = {lo4[0], lo4[0]};   // LIM: this lane's limits
-        if constexpr (LIM) {
+        if constexpr (LIM || SLEW) {
             if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) {
                 const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
                 if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
-                    lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
-                    hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                    if constexpr (LIM) {   // (the slew twin's box is applied by the scan lane, not by the storing lanes)
+                        lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                        hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                    }
                     if (ms.w != 0.f && !(J & 3) && 16 * n + 4 * c.g < J)
                         hpre[n] = *reinterpret_cast<const f32x4 *>(ms.hist + (traj * a.T + tok) * J + 16 * n + 4 * c.g);
                 }
             }
         }
+        // SLEW: the scan lane's four scalars, requested here - ahead of both barriers - so that they are no round trip on the serial part
+        float scan_v = 0.f, scan_lo = 0.f, scan_hi = 0.f, scan_y = __builtin_nanf("");
+        if constexpr (SLEW) {
+            if (c.w == 0 && c.lane < J) {
+                scan_v = sl.v[c.lane];
+                scan_lo = lim.lo[c.lane];
+                scan_hi = lim.hi[c.lane];
+                if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
-        if (c.w < NTT) {
+        if constexpr (SLEW) {
+            float *S = reinterpret_cast<float *>(c.smem + LDS_Q);
+            unsigned *M = reinterpret_cast<unsigned *>(c.smem + LDS_Q + TMAX * 128);
+            const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+            const bool ok = c.w < NTT && (c.w < NTT - 1 || c.ok6);
+            const bool vec = !(J & 3);
+            f32x4 ev[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, xv[2] = {ev[0], ev[0]}, x0v[2] = {ev[0], ev[0]};
+            // ---- phase 1: x0 of this lane's elements -> S, the row's mask word -> M
+            if (c.w < NTT) {
+                const char *X = c.smem + LDS_X;
+                f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) {
+                    const int m2lo = (ks & 1) << 1;
+                    const unsigned b0 = (c.w < NTT - 1 ? c.xa[m2lo] + (unsigned)(c.w * 16 * XROW) : c.xa6[m2lo]) + (unsigned)((ks >> 1) * 256);
+                    const unsigned b1 = (c.w < NTT - 1 ? c.xa[m2lo | 1] + (unsigned)(c.w * 16 * XROW) : c.xa6[m2lo | 1]) + (unsigned)((ks >> 1) * 256);
+                    const f16x8 bh = lds16(X + b0), bl = lds16(X + b1);
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) mma3<S_FC>(E[n], wf[n][ks][0], wf[n][ks][1], bh, bl);
+                }
+                const float *sp = stat + tok * 8;
+                const f32x4 p0 = *reinterpret_cast<const f32x4 *>(sp), p1 = *reinterpret_cast<const f32x4 *>(sp + 4);
+                const float m = fmaxf(fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p0[2], p0[3])), fmaxf(fmaxf(p1[0], p1[1]), fmaxf(p1[2], p1[3])));
+                const float c_o = 1.0f / (f16_scale_from_bits(__builtin_bit_cast(unsigned, m)) * a.sc_io[1]);
+                if (ok && c.g == 0) M[tok] = hold_m;
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int j0 = 16 * n + 4 * c.g;
+                    if (!ok || j0 >= J) continue;
+                    const long at = (traj * a.T + tok) * J + j0;
+                    if (vec) {
+                        ev[n] = E[n] * c_o + *reinterpret_cast<const f32x4 *>(a.b_out + j0);
+                        if (a.eps_out) *reinterpret_cast<f32x4 *>(a.eps_out + at) = ev[n];
+                        if (a.update_x) xv[n] = *reinterpret_cast<const f32x4 *>(a.x + at);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            ev[n][r] = E[n][r] * c_o + a.b_out[j0 + r];
+                            if (a.eps_out) a.eps_out[at + r] = ev[n][r];
+                            if (a.update_x) xv[n][r] = a.x[at + r];
+                        }
+                    }
+                    if (a.update_x) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            x0v[n][r] = __builtin_fmaf(-a.c1, ev[n][r], xv[n][r]) / a.c0;
+                            S[tok * 32 + j0 + r] = ((hold_m >> (j0 + r)) & 1u) ? hold.x0[at + r] : x0v[n][r];
+                        }
+                    }
+                }
+            }
+            // ---- phase 2: every wave of the workgroup (this barrier and the next stand outside `if (c.w < NTT)`)
+            __syncthreads();
+            // ---- phase 3: the scan, one lane per joint, rows in order
+            if (a.update_x && c.w == 0 && c.lane < J) {
+                const int j = c.lane;
+                const float v = scan_v, lo = scan_lo, hi = scan_hi;
+                float y = scan_y;
+                // 16 rows of the column and their mask words at a time, requested ahead of the chain (S is rewritten in place, so the
+                // compiler may not move row t + 1's load above row t's store by itself).  Measured no different from the row-by-row
+                // loop (profiles/slew_bench.jsonl): the scan's time is the chain itself, not its LDS reads
+                for (int t0 = 0; t0 < a.T; t0 += 16) {
+                    float q[16];
+                    unsigned mw[16];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const int t = t0 + k < a.T ? t0 + k : a.T - 1;
+                        q[k] = S[t * 32 + j];
+                        mw[k] = M[t];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        if (t0 + k >= a.T) continue;
+                        y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
+                        S[(t0 + k) * 32 + j] = y;
+                    }
+                }
+            }
+            __syncthreads();
+            // ---- phase 4: the limits twin's finish on the scan's x0c
+            if (c.w < NTT && a.update_x) {
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int j0 = 16 * n + 4 * c.g;
+                    if (!ok || j0 >= J) continue;
+                    const long at = (traj * a.T + tok) * J + j0;
+                    f32x4 x0c = f32x4{0.f, 0.f, 0.f, 0.f}, xn = x0c;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (j0 + r >= J) continue;
+                        x0c[r] = S[tok * 32 + j0 + r];
+                        xn[r] = slew_update(xv[n][r], ev[n][r], x0v[n][r], x0c[r], a.c0, a.c1, a.c2, a.c3, lim.reproject);
+                        if (ms.w != 0.f) xn[r] = __builtin_fmaf(ms.w, (vec ? hpre[n][r] : ms.hist[at + r]) - x0c[r], xn[r]);
+                        if ((hold_m >> (j0 + r)) & 1u) xn[r] = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                    }
+                    if (vec) {
+                        *reinterpret_cast<f32x4 *>(a.x + at) = xn;
+                        if (ms.hist) *reinterpret_cast<f32x4 *>(ms.hist + at) = x0c;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            a.x[at + r] = xn[r];
+                            if (ms.hist) ms.hist[at + r] = x0c[r];
+                        }
+                    }
+                }
+            }
+        }
+        if (!SLEW && c.w < NTT) {
             const char *X = c.smem + LDS_X;
             f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
             const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
@@ -1884,6 +2017,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_lim_kernel(StepArgs a, 
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_lim_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, int draws) {
     TJ<NTT, true>::template step_body<true, 4, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim);
+}
+// The slew twins (sd_ddim_sample_slew; instantiated in sd_traj_slew.hip): the limits twins plus the scan over the rows (SlewArgs), which
+// exchanges x0 through LDS behind two workgroup barriers that every wave reaches.
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_slew_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, int draws) {
+    TJ<NTT, true>::template step_body<false, 5, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, sl);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_slew_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, int draws) {
+    TJ<NTT, true>::template step_body<true, 5, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, sl);
 }
 struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
     RolloutArgs ra;

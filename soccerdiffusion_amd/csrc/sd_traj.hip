@@ -68,6 +68,9 @@ TrajStepMsFn traj_step_ms_fn(int ntt, bool wide);
 // sd_traj_lim.hip: the limits instantiations (the multistep's, its history optional, plus the per-joint clamp of x0: LimitArgs)
 typedef void (*TrajStepLimFn)(tj::StepArgs, HoldArgs, MultistepArgs, LimitArgs, int);
 TrajStepLimFn traj_step_lim_fn(int ntt, bool wide);
+// sd_traj_slew.hip: the slew instantiations (the limits', plus the scan over the rows behind two workgroup barriers: SlewArgs)
+typedef void (*TrajStepSlewFn)(tj::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, int);
+TrajStepSlewFn traj_step_slew_fn(int ntt, bool wide);
 
 // zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
 __global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
@@ -353,7 +356,7 @@ static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 &&
 
 // one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
 // as a runtime option; r.hold: the hold twin (sd_traj_hold.hip), whatever the group size; r.ms: the multistep twin (sd_traj_ms.hip);
-// r.lim: the limits twin (sd_traj_lim.hip)
+// r.lim: the limits twin (sd_traj_lim.hip); r.slew: the slew twin (sd_traj_slew.hip)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise) {
     const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
@@ -366,7 +369,14 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, h
         return fail(SD_E_BADARG, "traj_step_ms_kernel: the multistep term needs the DDIM coefficients, the three-product kernels and a history buffer, and excludes a pin");
     if (r.lim && (!r.ms || !r.lim->lo || !r.lim->hi || (!r.ms->hist && r.ms->w != 0.f)))
         return fail(SD_E_BADARG, "traj_step_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
+    if (r.slew && (!r.lim || !r.slew->v || w->J > 32))
+        return fail(SD_E_BADARG, "traj_step_slew_kernel: slew limits need v, the limits arguments (which may all be infinite) and J <= 32");
     const tj::StepArgs a = traj_step_args(w, s, r, r.coef, nkt);
+    if (r.slew) {   // the limits call plus the scan over the rows
+        static DevFlag slew_attr_set[2][8];   // [one key tile | wide][ntt]
+        return launch_step_kernel(traj_step_slew_fn(ntt, variant == 2), "traj_step_slew_kernel", slew_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS,
+                                  tj::LDS_BYTES, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, *r.lim, *r.slew, r.draws);
+    }
     if (r.lim) {   // DDIM (ms->hist NULL) or multistep, held or not, whatever the group size
         static DevFlag lim_attr_set[2][8];   // [one key tile | wide][ntt]
         return launch_step_kernel(traj_step_lim_fn(ntt, variant == 2), "traj_step_lim_kernel", lim_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS,
@@ -400,7 +410,7 @@ int traj_steps_fused(const sd_denoiser_weights *w, const TrajWs &s, const StepRe
     const int ntt = (r.T + 15) / 16;
     if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_rollout_kernel: horizon out of range");
     if (n < 1 || n > tj::ROLL_MAX_STEPS || r.i < 0 || r.i + n > r.n_tok || !r.coef) return fail(SD_E_BADARG, "traj_step_rollout_kernel: bad step range");
-    if (!traj_groups_ok(r) || r.eps || r.per_traj || r.pin || r.hold || r.ms || r.lim)
+    if (!traj_groups_ok(r) || r.eps || r.per_traj || r.pin || r.hold || r.ms || r.lim || r.slew)
         return fail(SD_E_BADARG, "traj_step_rollout_kernel: B a multiple of draws; nothing returned per step, no per-trajectory tokens, no pin");
     tj::RolloutDrawsArgs da{};
     da.draws = r.draws;

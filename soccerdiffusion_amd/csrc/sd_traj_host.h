@@ -34,6 +34,8 @@ int traj_prepare_steps(const sd_denoiser_weights *w, const TrajWs &s, const floa
 // hold's epilogue plus ms->w * (ms->hist - x0) on the DDIM update, x0 left in ms->hist; ms->hist is not read when ms->w == 0.
 // r.lim (needs r.ms, whose hist may then be NULL: first-order DDIM): the limits instantiations (sd_traj_lim.hip) - the multistep epilogue on
 // x0 clamped to [lim->lo[j], lim->hi[j]] (LimitArgs, sd_common.h).
+// r.slew (needs r.lim, whose bounds may all be infinite): the slew instantiations (sd_traj_slew.hip) - the limits epilogue on x0 after the
+// scan over the rows (SlewArgs, sd_common.h), exchanged through LDS behind two workgroup barriers.
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise);
 // DDIM steps r.i .. r.i + n - 1 of the r.n_tok prepared ones in ONE launch of the rollout kernel (the plan's rollout_fused: one key tile,
 // nothing returned per step, no pin: r.eps, r.pin NULL); n <= TRAJ_ROLLOUT_MAX_STEPS - the per-step scalars travel in the kernel

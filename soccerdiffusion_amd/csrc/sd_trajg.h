@@ -24,5 +24,6 @@ int trajg_prepare_steps(const sd_denoiser_weights *w, float *gws, const float *t
 // r.hold (needs r.coef, excludes r.pin): held elements (HoldArgs) - traj_step_generic_hold_kernel, whatever r.draws
 // r.ms (needs r.coef, excludes r.pin; r.hold optional): the multistep twin (MultistepArgs) - traj_step_generic_ms_kernel, whatever r.draws
 // r.lim (needs r.ms, whose hist may then be NULL: DDIM): the limits twin (LimitArgs) - traj_step_generic_lim_kernel, whatever r.draws
+// r.slew (needs r.lim, whose bounds may all be infinite): the slew twin (SlewArgs) - traj_step_generic_slew_kernel, whatever r.draws
 int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipStream_t st, const int *map = nullptr);
 #endif

@@ -824,12 +824,20 @@ struct TG {
     // PIN == 4, LIM: the limits twin (LimitArgs, sd_common.h; sd_ddim_sample_limits) - the multistep twin with an optional history (ms.hist
     // NULL: first-order DDIM) on x0 clamped to [lo[j], hi[j]] by compares and selects: the storing lane requests its four lo / hi values
     // (32 padded floats each: always a legal f32x4) beside the mask word; lim.reproject is a wave-uniform branch on the kernel argument
+    // PIN == 5, SLEW: the slew twin (SlewArgs, sd_common.h; sd_ddim_sample_slew) - the limits twin plus the scan over the rows, in four
+    // phases as in sd_traj.h: the storing lanes write x0 (a held element: the hold's value) into the fp32 plane S[tok][32] and their row's
+    // mask word into M[tok], both in the K / V buffer, which nothing uses after the last layer's self-attention; a workgroup barrier; lane
+    // j < J of wave 0 runs slew_row over t = 0 .. T-1 on column j of S in place; a second barrier; the storing lanes read x0c back and
+    // finish as the limits twin does.  Both barriers stand outside `if (c.w < NTT)`: every wave reaches them.
     template <int PIN = 0, bool DRAWS = false>
     static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{},
-                                                     const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{}) {
+                                                     const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{},
+                                                     const SlewArgs &sl = SlewArgs{}) {
         constexpr bool HOLD = PIN == 2;
         constexpr bool MS = PIN == 3;
         constexpr bool LIM = PIN == 4;
+        constexpr bool SLEW = PIN == 5;
+        static_assert(!SLEW || 128 + 4 <= VROW, "the slew twin's S and M planes fit the K / V buffer");
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -931,14 +939,16 @@ struct TG {
                 }
             }
             f32x4 lo4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, hi4[2] = {lo4[0], lo4[0]};   // LIM: this lane's limits
-            if constexpr (LIM) {
+            if constexpr (LIM || SLEW) {
                 if (c.w < NTT && (c.w < NTT - 1 || c.okl)) {
                     const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
                     if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
-                        lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
-                        hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                        if constexpr (LIM) {   // (the slew twin's box is applied by the scan lane, not by the storing lanes)
+                            lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                            hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                        }
                         if (ms.w != 0.f) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
@@ -947,8 +957,104 @@ struct TG {
                     }
                 }
             }
+            // SLEW: the scan lane's four scalars, requested ahead of both barriers
+            float scan_v = 0.f, scan_lo = 0.f, scan_hi = 0.f, scan_y = __builtin_nanf("");
+            if constexpr (SLEW) {
+                if (c.w == 0 && c.lane < J) {
+                    scan_v = sl.v[c.lane];
+                    scan_lo = lim.lo[c.lane];
+                    scan_hi = lim.hi[c.lane];
+                    if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+                }
+            }
             __syncthreads();
-            if (c.w < NTT) {
+            if constexpr (SLEW) {
+                float *S = reinterpret_cast<float *>(c.smem + c.oK);
+                unsigned *M = reinterpret_cast<unsigned *>(c.smem + c.oK + a.T * 128);
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
+                const bool ok = c.w < NTT && (c.w < NTT - 1 || c.okl);
+                float ev[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, xv[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}},
+                      x0v[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+                // ---- phase 1: x0 of this lane's elements -> S, the row's mask word -> M
+                if (c.w < NTT) {
+                    const char *X = c.smem;
+                    f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        const f16x8 bh = lds16(X + x_off(tok, 4 * ks + c.g)), bl = lds16(X + x_off(tok, XCH + 4 * ks + c.g));
+#pragma unroll
+                        for (int n = 0; n < 2; ++n) {
+                            const f16 *wp = a.w_out + ((long)(n * KS + ks) * 2) * 512 + c.lane * 8;
+                            mma3(E[n], glb16(wp), glb16(wp + 512), bh, bl);
+                        }
+                    }
+                    const float c_o = 1.0f / (tok_scale(tok) * a.sc_io[SC_OUT]);
+                    if (ok && c.g == 0) M[tok] = hold_m;
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const int j0 = 16 * n + 4 * c.g;
+                        if (!ok || j0 >= J) continue;
+                        const long at = (traj * a.T + tok) * J + j0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            ev[n][r] = E[n][r] * c_o + a.b_out[j0 + r];
+                            if (a.eps_out) a.eps_out[at + r] = ev[n][r];
+                            if (a.update_x) {
+                                xv[n][r] = a.x[at + r];
+                                x0v[n][r] = __builtin_fmaf(-a.c1, ev[n][r], xv[n][r]) / a.c0;
+                                S[tok * 32 + j0 + r] = ((hold_m >> (j0 + r)) & 1u) ? hold.x0[at + r] : x0v[n][r];
+                            }
+                        }
+                    }
+                }
+                // ---- phase 2: every wave of the workgroup (this barrier and the next stand outside `if (c.w < NTT)`)
+                __syncthreads();
+                // ---- phase 3: the scan, one lane per joint, rows in order
+                if (a.update_x && c.w == 0 && c.lane < J) {
+                    const int j = c.lane;
+                    const float v = scan_v, lo = scan_lo, hi = scan_hi;
+                    float y = scan_y;
+                    // 16 rows of the column and their mask words at a time, requested ahead of the chain (S is rewritten in place)
+                    for (int t0 = 0; t0 < a.T; t0 += 16) {
+                        float q[16];
+                        unsigned mw[16];
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) {
+                            const int t = t0 + k < a.T ? t0 + k : a.T - 1;
+                            q[k] = S[t * 32 + j];
+                            mw[k] = M[t];
+                        }
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) {
+                            if (t0 + k >= a.T) continue;
+                            y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
+                            S[(t0 + k) * 32 + j] = y;
+                        }
+                    }
+                }
+                __syncthreads();
+                // ---- phase 4: the limits twin's finish on the scan's x0c
+                if (c.w < NTT && a.update_x) {
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const int j0 = 16 * n + 4 * c.g;
+                        if (!ok || j0 >= J) continue;
+                        const long at = (traj * a.T + tok) * J + j0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            const float x0c = S[tok * 32 + j0 + r];
+                            float xn = slew_update(xv[n][r], ev[n][r], x0v[n][r], x0c, a.c0, a.c1, a.c2, a.c3, lim.reproject);
+                            if (ms.w != 0.f) xn = __builtin_fmaf(ms.w, hpre[n][r] - x0c, xn);
+                            if ((hold_m >> (j0 + r)) & 1u) xn = a.c2 * hold.x0[at + r] + a.c3 * hold.noise[at + r];
+                            a.x[at + r] = xn;
+                            if (ms.hist) ms.hist[at + r] = x0c;
+                        }
+                    }
+                }
+            }
+            if (!SLEW && c.w < NTT) {
                 const char *X = c.smem;
                 f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
                 const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
@@ -1046,6 +1152,12 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_lim_kernel(StepArg
     TG<D, NTT>::template step_body<4, true>(a, PinArgs{}, draws, hold, ms, lim);
 }
 
+// the slew twin (sd_ddim_sample_slew): the limits twin plus the scan over the rows (SlewArgs), x0 exchanged through LDS
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_slew_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, int draws) {
+    TG<D, NTT>::template step_body<5, true>(a, PinArgs{}, draws, hold, ms, lim, sl);
+}
+
 }   // namespace tg
 
 // ======================================================================================
@@ -1124,6 +1236,10 @@ StepMsFn step_ms_fn(int d, int ntt) {
 typedef void (*StepLimFn)(tg::StepArgs, HoldArgs, MultistepArgs, LimitArgs, int);
 StepLimFn step_lim_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepLimFn { return tg::traj_step_generic_lim_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepSlewFn)(tg::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, int);
+StepSlewFn step_slew_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepSlewFn { return tg::traj_step_generic_slew_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
@@ -1246,6 +1362,8 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
         return fail(SD_E_BADARG, "traj_step_generic_ms_kernel: the multistep term needs the DDIM coefficients and a history buffer, and excludes a pin");
     if (r.lim && (!r.ms || !r.lim->lo || !r.lim->hi || (!r.ms->hist && r.ms->w != 0.f)))
         return fail(SD_E_BADARG, "traj_step_generic_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
+    if (r.slew && (!r.lim || !r.slew->v || w->J > 32))
+        return fail(SD_E_BADARG, "traj_step_generic_slew_kernel: slew limits need v, the limits arguments (which may all be infinite) and J <= 32");
     tg::StepArgs a{};
     a.x = r.x;
     a.eps_out = r.eps;
@@ -1278,6 +1396,11 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     constexpr int MAX_LDS = 163840;
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.slew) {   // the slew twin: the limits twin plus the scan over the rows
+        static DevFlag slew_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_slew_fn(d, ntt), "traj_step_generic_slew_kernel", slew_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, *r.lim, *r.slew, r.draws);
+    }
     if (r.lim) {   // the limits twin: DDIM (ms->hist NULL) or multistep, held or not, whatever the group size
         static DevFlag lim_attr_set[3][8];   // [hidden_dim][ntt]
         return launch_step_kernel(step_lim_fn(d, ntt), "traj_step_generic_lim_kernel", lim_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,

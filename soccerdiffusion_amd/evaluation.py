@@ -17,6 +17,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 NUM_TRAIN_TIMESTEPS = 1000
@@ -86,6 +87,38 @@ def normalised_limits(limits, mean: torch.Tensor, std: torch.Tensor) -> tuple:
     return (lo - mean) / std, (hi - mean) / std
 
 
+def normalised_slew(slew, mean: torch.Tensor, std: torch.Tensor, limits=None) -> torch.Tensor:
+    """``slew`` in the space of the trajectories (x * std + mean; (J,) floats, one number or ``{joint: v}`` as ``ops.joint_slew`` takes
+    them: the largest step between consecutive rows) as a (J,) fp32 host tensor in the sampler's normalised space: (v - margin) / std per
+    joint in fp64, rounded toward zero, with ``ops.denormalised_slew_margin`` - what the scan's rounding and the denormalisation's can
+    add to the difference of two denormalised values - so that consecutive rows of the DENORMALISED trajectories differ
+    by at most v, evaluated exactly.  The margin needs a bound on |x std + mean|: max(|lo|, |hi|) of ``limits`` (the same space, as
+    ``normalised_limits`` takes them) where a joint has both, else 2 pi - joint commands lie in [0, 2 pi).  +inf stays +inf; a v not
+    above its margin raises ValueError."""
+    from . import ops
+
+    mean, std = mean.detach().reshape(-1).cpu().float().numpy(), std.detach().reshape(-1).cpu().float().numpy()
+    J = std.size
+    if not (std > 0).all():
+        raise ValueError("slew: the normaliser's std must be positive")
+    v = ops._slew_host(slew, J)[:J].astype(np.float64)
+    bound = np.full(J, 2 * math.pi)
+    if limits is not None:
+        lo, hi = (np.abs(a[:J].astype(np.float64)) for a in ops._limits_host(limits, J))
+        both = np.isfinite(lo) & np.isfinite(hi)
+        bound = np.where(both, np.maximum(lo, hi), bound)
+    margin = ops.denormalised_slew_margin(bound, mean, std)
+    finite = np.isfinite(v)
+    if (finite & ~(v > margin)).any():
+        j = int(np.argmax(finite & ~(v > margin)))
+        raise ValueError(f"slew: v[{j}] = {v[j]} is not above the margin {margin[j]:.3e} of the fp32 arithmetic")
+    exact = np.where(finite, (np.where(finite, v, 0.0) - margin) / std.astype(np.float64), np.inf)
+    out = exact.astype(np.float32)
+    over = out.astype(np.float64) > exact
+    out[over] = np.nextafter(out[over], np.float32(0))
+    return torch.from_numpy(out)
+
+
 def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool,
                     solver: str = "ddim") -> dict:
     """The report from the per-batch marginals, in fp64 on the host.  A part holds, for its C windows: ``err`` (C, G), ``row_err`` (C, G, T),
@@ -125,7 +158,7 @@ def _has_context(model) -> bool:
 @torch.no_grad()
 def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int = 8, batch: int = 64, seed: int = 0, max_mode: int = 3,
              angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None, solver: str = "ddim",
-             limits=None, reproject: bool = False) -> dict:
+             limits=None, reproject: bool = False, slew=None) -> dict:
     """The report (a plain dict of Python floats, ints and lists) of ``model`` on the windows ``idx`` of ``source`` (``cli.DataSource``), in
     batches of ``batch`` windows from ``source.batch``.  The model must be in ``eval()``.  Per batch: the context is encoded once; the loss
     grid runs at ``timesteps`` (default ``default_timesteps(grid)``); ``draws`` = G trajectories per window are sampled with ``steps`` DDIM
@@ -134,6 +167,11 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     ``limits`` / ``reproject``: the draws are sampled under joint limits given in the space of the target trajectories
     (``normalised_limits``, ``model.sample(limits=...)``) - what a set of limits costs in rmse; the report then gains a ``limits`` entry,
     ``[lo, hi]`` per joint with None for an open side, and ``reproject``;
+    ``slew``: the draws are sampled under slew limits given in the same space (``normalised_slew``, ``model.sample(slew=...)``); the report
+    then gains a ``slew`` entry, v per joint with None for none.  With or without it the report carries ``max_step_by_joint``: the
+    largest |step| between consecutive rows of the sampled trajectories, all draws, in the space of the targets (``ops.max_step``) - the
+    number from which a slew limit is chosen, and the one that shows it held: with ``--slew`` it is <= v, as long as the denormalised
+    values stay inside the bound the margin was derived for (``normalised_slew``);
     ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
     student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None.
     A model without context encoders (decoder pretraining) gets ten random context rows per window from the same generator.
@@ -150,6 +188,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         raise ValueError("evaluate: steps and batch must be positive")
     if solver not in ("ddim", "multistep") or (distilled and solver != "ddim"):
         raise ValueError(f"evaluate: solver must be 'ddim' or 'multistep' (a distilled decoder has no rollout: 'ddim'), got {solver!r}")
+    limits_given = limits
     if limits is not None:
         if distilled:
             raise ValueError("evaluate: a distilled decoder has no rollout whose x0 could be limited")
@@ -157,6 +196,11 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         given = [[None if math.isinf(a) else a for a in pair]      # as given, per joint: [lo, hi], None for an open side
                  for pair in zip(*(v[:J].tolist() for v in ops._limits_host(limits, J)))]
         limits = normalised_limits(limits, model.mean, model.std)
+    if slew is not None:
+        if distilled:
+            raise ValueError("evaluate: a distilled decoder has no rollout whose x0 could be limited")
+        slew_given = [None if math.isinf(a) else a for a in ops._slew_host(slew, model.mean.numel())[: model.mean.numel()].tolist()]
+        slew = normalised_slew(slew, model.mean, model.std, limits_given)
     idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
     if idx.numel() == 0:
         raise ValueError("evaluate: no windows to evaluate")
@@ -165,7 +209,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     t_dev = torch.tensor(ts, dtype=torch.int64, device=device)
     acp = ops.alphas_cumprod().to(device)
     K, d = len(ts), model.hidden_dim
-    parts = []
+    parts, steps_seen = [], []
     for at in range(0, idx.numel(), batch):
         data = source.batch(idx[at : at + batch])
         target = data["joint_command"].to(torch.float32).contiguous()
@@ -183,8 +227,9 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         if distilled:
             x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
         else:
-            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject)
+            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject, slew=slew)
         x = x.contiguous()
+        steps_seen.append(ops.max_step(x, model.mean, model.std).amax(0).cpu())
         part["medoid"], chosen = ops.select_medoid(x, G)
         part["err"], part["row_err"], part["joint_err"], part["best"] = ops.trajectory_errors(x, target, model.mean, model.std, draws=G, angular=angular)
         # the distance of every draw to the medoid, in radians: the same kernel against the denormalised medoid, nothing to wrap
@@ -194,6 +239,9 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
             keep.append({"x": x, "target": target, "medoid_x": chosen, **({} if distilled else {"eps": eps, "noise": noise}), **part})
         parts.append({k: (None if v is None else v.cpu()) for k, v in part.items()})
     report = assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular, solver=solver)
+    report["max_step_by_joint"] = [float(v) for v in torch.stack(steps_seen).amax(0)]
     if limits is not None:
         report.update(limits=given, reproject=bool(reproject))
+    if slew is not None:
+        report["slew"] = slew_given
     return report

@@ -206,7 +206,7 @@ class End2EndDiffusionTransformer(nn.Module):
     def sample(self, context: Sequence[torch.Tensor], x_T: torch.Tensor, num_inference_steps: int,
                return_trace: bool = False, alphas_cumprod: Optional[torch.Tensor] = None, use_graph: bool = False,
                with_dropout: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, solver: str = "ddim",
-               limits=None, reproject: bool = False):
+               limits=None, reproject: bool = False, slew=None):
         """The reference's denoising loop (plot.py:122-131 / distill.py:179-189 / ros.py:301-310)
         as one native call: n x (denoiser forward + DDIM update) with the context K/V cached.
         ``use_graph`` replays the rollout from a hipGraph captured for this (B, T, M, n) shape.
@@ -232,7 +232,12 @@ class End2EndDiffusionTransformer(nn.Module):
         predicted clean trajectory is clamped to the joints' limits at every step inside the step launch (``ops.ddim_sample``; diffusers'
         ``clip_sample``, per joint), so the returned free elements lie inside them bit for bit; ``reproject``: diffusers'
         ``use_clipped_model_output``.  It composes with ``pin``, ``hold``, ``draws``, ``solver``, ``use_graph`` (the graph reads the limits
-        on the device: one capture serves every value) and ``return_trace``.  Not with ``with_dropout``; J <= 32."""
+        on the device: one capture serves every value) and ``return_trace``.  Not with ``with_dropout``; J <= 32.
+        ``slew`` (``v`` or ``(v, start)``, ``ops.joint_slew``'s forms; normalised space): consecutive rows of the predicted clean
+        trajectory are kept within ``v[j]`` of each other at every step (row 0 against ``start`` (B, J)), then clamped to ``limits``
+        (``ops.ddim_sample(slew=...)``).  It composes with what ``limits`` composes with."""
+        if slew is not None and with_dropout:
+            raise ValueError("sample: slew is a feature of the native rollout; with_dropout steps through forward_with_context")
         if limits is not None and with_dropout:
             raise ValueError("sample: limits is a feature of the native rollout; with_dropout steps through forward_with_context")
         if solver not in ("ddim", "multistep"):
@@ -272,15 +277,19 @@ class End2EndDiffusionTransformer(nn.Module):
             # the weights are read through pointers at replay (their addresses are the key); the step-token table is captured by value
             token = derived.source_key(self.step_encoding.token)
             key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(), token, cap, pin is not None, draws, hold is not None, solver,
-                   limits is not None, bool(reproject))
+                   limits is not None, bool(reproject), slew is not None)
             cache = _model_cache(self, "graphs")
             if token is None or key not in cache:
                 cache.clear()  # one shape at a time: a graph pins its workspace
                 cache[key] = ops.GraphedSampler(packed, B, T, Mc, self.step_encoding.table(ts, x_T.device), coef, max_mode=cap,
                                                 pin=pin is not None, draws=draws, hold=hold is not None, multistep=msw, limits=limits is not None,
-                                                reproject=reproject)
+                                                reproject=reproject, slew=slew is not None)
             if limits is not None:
                 cache[key].set_limits(limits)
+            elif slew is not None:
+                cache[key].set_limits({})
+            if slew is not None:
+                cache[key].set_slew(slew)
             out = cache[key](ctx, x_T, pin, hold)
             word = int(cache[key].status.item())
             if word == 0:
@@ -290,4 +299,4 @@ class End2EndDiffusionTransformer(nn.Module):
             # range guard tripped (ops.ddim_sample_guarded): fall through to the guarded eager path
         tokens = self.step_encoding.table(ts, x_T.device)
         return ops.ddim_sample_guarded(packed, ctx, tokens, coef, x_T.contiguous(), trace=return_trace, max_mode=max_mode, pin=pin, draws=draws, hold=hold, multistep=msw,
-                                       limits=limits, reproject=reproject)
+                                       limits=limits, reproject=reproject, slew=slew)

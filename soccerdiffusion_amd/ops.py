@@ -256,6 +256,99 @@ def limit_step(eps: Tensor, x: Tensor, coef4, limits: Limits, hist: Optional[Ten
     return out
 
 
+def _slew_host(v, J: int) -> np.ndarray:
+    """``v`` - (J,) floats, one number or ``{joint: v}`` - as the (32,) fp32 host array padded with +inf, validated: see ``joint_slew``."""
+    if isinstance(J, bool) or not 1 <= int(J) <= 32:
+        raise ValueError(f"slew: the 32-float array describes at most 32 joints, got J = {J}")
+    J = int(J)
+    out = np.full(32, np.inf, dtype=np.float32)
+    if isinstance(v, Mapping):
+        for j, val in v.items():
+            if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < J:
+                raise ValueError(f"slew: joint index {j!r} out of range 0 .. {J - 1}")
+            try:
+                out[int(j)] = float(val)
+            except (TypeError, ValueError):
+                raise ValueError(f"slew: joint {j}: expected one number, got {val!r}") from None
+    else:
+        arr = v.detach().cpu().numpy() if isinstance(v, Tensor) else v
+        try:
+            arr = np.asarray(arr, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"slew: expected ({J},) floats, one number or {{joint: v}}, got {v!r}") from None
+        if arr.shape not in ((), (J,)):
+            raise ValueError(f"slew: expected ({J},) floats or one number, got shape {arr.shape}")
+        out[:J] = arr
+    if np.isnan(out).any():
+        raise ValueError("slew: NaN is not a limit (use +inf for no limit)")
+    if not (out >= 0).all():
+        j = int(np.argmax(~(out >= 0)))
+        raise ValueError(f"slew: v[{j}] = {out[j]} is negative")
+    return out
+
+
+def joint_slew(v, J: Optional[int] = None, device=None) -> Tensor:
+    """Per-joint slew limits of ``ddim_sample(slew=...)`` as the kernels read them (``sd_ddim_sample_slew``): one (32,) fp32 array on
+    ``device``, entries [J, 32) padded with +inf.  ``v[j] >= 0`` is the largest change of joint j between consecutive rows of the
+    trajectory, in the sampler's normalised space; +inf: none.  ``v``: (J,) floats, one number for every joint, or ``{joint: v}`` (every
+    other joint unlimited).  ValueError for a NaN, a negative value, a wrong shape, a joint index outside 0 .. J - 1, or J > 32."""
+    if J is None or device is None:
+        raise ValueError("joint_slew: J and device must be given")
+    return torch.from_numpy(_slew_host(v, J)).to(device)
+
+
+def _is_dev32(t, device, rows: Optional[int] = None) -> bool:
+    shape = (32,) if rows is None else (rows, 32)
+    return (isinstance(t, Tensor) and tuple(t.shape) == shape and t.dtype == torch.float32 and t.device == torch.device(device)
+            and t.is_contiguous() and t.data_ptr() % 16 == 0)
+
+
+def _slew_req(slew, B: int, J: int, device) -> tuple:
+    """``slew`` of a sampler call, validated: ``v`` or ``(v, start)`` -> (v (32,) on the device, start (B, 32) on the device or None).
+    ``v``: a (32,) fp32 array of ``joint_slew`` on the device as it is, else through ``joint_slew``.  ``start``: (B, J) or (B, 32) floats,
+    the value "before row 0" per trajectory (NaN: none); a contiguous (B, 32) fp32 device tensor is used as it is, anything else is padded
+    with NaN into a new one."""
+    pair = isinstance(slew, tuple) and len(slew) == 2 and (slew[1] is None or getattr(slew[1], "ndim", 0) >= 1)   # (v, start), not two floats
+    v, start = slew if pair else (slew, None)
+    if J > 32:
+        raise ValueError(f"slew: the 32-float array describes at most 32 joints, got J = {J}")
+    if not _is_dev32(v, device):
+        v = joint_slew(v, J=J, device=device)
+    if start is not None and not _is_dev32(start, device, B):
+        st = start.detach() if isinstance(start, Tensor) else torch.as_tensor(np.asarray(start, dtype=np.float32))
+        if st.dim() != 2 or st.shape[0] != B or st.shape[1] not in (J, 32):
+            raise ValueError(f"slew start: expected ({B}, {J}) or ({B}, 32) floats, got {tuple(st.shape)}")
+        start = torch.full((B, 32), float("nan"), dtype=torch.float32, device=device)
+        start[:, :J] = st[:, :J].to(device=device, dtype=torch.float32)
+    return v, start
+
+
+def slew_step(eps: Tensor, x: Tensor, coef4, slew, limits=None, hist: Optional[Tensor] = None, w: float = 0.0, reproject: bool = False,
+              hold=None) -> Tensor:
+    """One step under per-joint slew limits for a caller that evaluates the denoiser itself (``sd_ddim_slew_step``): ``limit_step`` with
+    the scan of ``ddim_sample(slew=...)`` over the rows of every trajectory.  ``eps``, ``x`` (and ``hist``): whole (B, T, J) samples.
+    ``slew``: ``v`` or ``(v, start)``; ``limits``: as ``limit_step`` takes them (default: none).  ``hold = (known, mask)``: held elements
+    enter the scan as ``known``; their returned value is the scan's update of it, which the caller's hold overwrites."""
+    lib = _lib.load()
+    _req(eps, "eps"); _req(x, "x")
+    if x.dim() != 3 or eps.shape != x.shape or (hist is not None and hist.shape != x.shape):
+        raise ValueError("slew_step: eps, x and hist must be whole (B, T, J) samples of one shape")
+    if hist is not None:
+        _req(hist, "hist")
+    B, T, J = x.shape
+    v, start = _slew_req(slew, B, J, x.device)
+    limits = _limits_req({} if limits is None else limits, J, x.device)
+    known, mask = (None, None) if hold is None else _hold_req(hold, B, T, J, x.device)
+    out = torch.empty_like(x)
+    c = np.ascontiguousarray([float(t) for t in coef4], dtype=np.float32)
+    if c.shape != (4,):
+        raise ValueError("slew_step: coef4 must hold 4 scalars")
+    check(lib.sd_ddim_slew_step(eps.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(hist), c.ctypes.data_as(_lib.c_float_p), float(w),
+                                limits.lo.data_ptr(), limits.hi.data_ptr(), int(bool(reproject)), v.data_ptr(), _ptr(start), _ptr(known), _ptr(mask),
+                                B, T, J, _stream()), "sd_ddim_slew_step")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # weight descriptors
 # --------------------------------------------------------------------------------------
@@ -561,7 +654,7 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
 
 def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
                         et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None, multistep=None,
-                        limits=None):
+                        limits=None, slew=None):
     """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
     ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
     ``sd_ddim_sample_pin``, launch for launch; ``hold = (known, noise, mask words)``: ``sd_ddim_sample_hold`` (never beside a pin).
@@ -569,8 +662,20 @@ def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: T
     without (never beside a pin: the callers fold it into a mask).
     ``limits = (lo, hi, reproject)`` (the (32,) device arrays of ``joint_limits``): ``sd_ddim_sample_limits``, with ``multistep`` and
     ``hold`` or without either (never beside a pin).
+    ``slew = (v, start or None)`` (needs ``limits``, which may all be infinite): ``sd_ddim_sample_slew``.
     Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
     B, T, _ = x.shape
+    if slew is not None:
+        msw, hist = multistep if multistep is not None else (None, None)
+        check(_lib.load().sd_ddim_sample_slew(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                              x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1],
+                                              len(coef), _ptr(status), int(max_mode), *[_ptr(t) for t in (hold or (None, None, None))], draws,
+                                              None if msw is None else msw.ctypes.data_as(_lib.c_float_p), _ptr(hist),
+                                              limits[0].data_ptr(), limits[1].data_ptr(), int(bool(limits[2])), slew[0].data_ptr(), _ptr(slew[1]),
+                                              _stream()),
+              "sd_ddim_sample_slew")
+        out = (x,) + tuple(t for t in (tr, et) if t is not None)
+        return out if len(out) > 1 else x
     if limits is not None:
         msw, hist = multistep if multistep is not None else (None, None)
         check(_lib.load().sd_ddim_sample_limits(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
@@ -621,15 +726,21 @@ class GraphedSampler:
     ``pin=(known, rows)`` becomes ``hold_mask(rows=rows)``.  ``limits=True`` captures the call under per-joint limits
     (``sd_ddim_sample_limits``, ``reproject`` fixed at capture) on two static (32,) arrays, ``self.limits``, which the kernels read on the
     device at every step: they start unlimited, ``set_limits`` rewrites them in place and the captured rollout stays captured; a pin is
-    folded into a mask as under ``multistep``.  (One native call for all of them: ``_ddim_sample_native``.)"""
+    folded into a mask as under ``multistep``.  ``slew=True`` captures the call under per-joint slew limits (``sd_ddim_sample_slew``) on a
+    static (32,) array ``self.slew_v`` (all +inf at first) and a static (B, 32) array ``self.slew_start`` (all NaN at first), read on the
+    device at every step: ``set_slew`` rewrites them in place.  It implies the limit arrays, which stay infinite unless ``set_limits`` is
+    called.  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
-                 draws: int = 1, hold: bool = False, multistep=None, limits: bool = False, reproject: bool = False):
+                 draws: int = 1, hold: bool = False, multistep=None, limits: bool = False, reproject: bool = False, slew: bool = False):
         dev = step_tokens.device
+        limits = bool(limits) or bool(slew)
         if pin and hold:
             raise ValueError("GraphedSampler: pin and hold exclude each other - compose them through ops.hold_mask(rows=...)")
         self.multistep = None if multistep is None else _multistep_req(multistep, len(coef))
         self.limits, self.reproject = (joint_limits({}, J=packed.J, device=dev) if limits else None), bool(reproject)
+        self.slew_v = joint_slew({}, J=packed.J, device=dev) if slew else None
+        self.slew_start = torch.full((B, 32), float("nan"), dtype=torch.float32, device=dev) if slew else None
         self.pin_as_hold = bool(pin) and (self.multistep is not None or self.limits is not None)
         if self.pin_as_hold:
             pin, hold = False, True
@@ -665,7 +776,20 @@ class GraphedSampler:
     def _run(self):
         _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws,
                             self.hold, None if self.multistep is None else (self.multistep, self.hist),
-                            None if self.limits is None else (self.limits.lo, self.limits.hi, self.reproject))
+                            None if self.limits is None else (self.limits.lo, self.limits.hi, self.reproject),
+                            None if self.slew_v is None else (self.slew_v, self.slew_start))
+
+    def set_slew(self, slew) -> None:
+        """Rewrites the captured slew arrays in place (``slew`` as ``ddim_sample`` takes it: ``v`` or ``(v, start)``; without ``start``
+        the anchors go back to NaN): every later replay runs under them."""
+        if self.slew_v is None:
+            raise ValueError("GraphedSampler: set_slew needs a graph captured with slew=True")
+        v, start = _slew_req(slew, self.x.shape[0], self.packed.J, self.x.device)
+        self.slew_v.copy_(v)
+        if start is None:
+            self.slew_start.fill_(float("nan"))
+        else:
+            self.slew_start.copy_(start)
 
     def set_limits(self, limits) -> None:
         """Rewrites the captured limit arrays in place (``limits`` as ``ddim_sample`` takes it): every later replay runs under them."""
@@ -712,7 +836,8 @@ class GraphedSampler:
 
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
-                eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None, limits=None, reproject: bool = False):
+                eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None, limits=None, reproject: bool = False,
+                slew=None):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -742,7 +867,15 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     inside the limits; a NaN stays NaN.  ``reproject`` (diffusers' ``use_clipped_model_output``): a clamped element's eps is recomputed
     from the clamped x0.  Held elements keep the hold's value whatever the limits say; ``eps_trace`` stays the network's prediction.  It
     composes with everything above (a ``pin`` is folded into a mask: J <= 32); infinite limits are the multistep call bit for bit.  One
-    limits kernel per step on the trajectory routes (no fused rollout form)."""
+    limits kernel per step on the trajectory routes (no fused rollout form).
+    ``slew = v`` or ``(v, start)`` (``joint_slew``'s forms; ``start`` (B, J) or (B, 32), NaN: none): per-joint slew limits in normalised
+    space (``sd_ddim_sample_slew``) - at every step, consecutive rows of the predicted clean trajectory are kept within ``v[j]`` of each
+    other by a scan over the rows t = 0 .. T - 1 (row 0 against ``start``), then clamped to ``limits`` (optional beside it; the box always
+    wins), before the update is formed.  A held element enters the scan as the hold's value: a jump into it is the caller's business.
+    Every free element of the result lies bitwise within ``fl(p +- v)`` of a predecessor p inside the box.  It composes with everything
+    above; infinite ``v`` without ``start`` is the ``limits=`` call bit for bit.  One slew kernel per step on the trajectory routes (the
+    limits twins around the scan, x0 exchanged through LDS; no fused rollout form); behind the row-panel routes one scan kernel, a thread
+    per trajectory and joint."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
     if pin is not None and hold is not None:
         raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
@@ -765,10 +898,13 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         _req(status, "status", torch.int32)
     if pin is not None:
         pin = _pin_req(pin, B, T, J, x_T.device)
-        if multistep is not None or limits is not None:   # the multistep and limits kernels take a mask: the pin as its leading full rows
+        if multistep is not None or limits is not None or slew is not None:   # the multistep and limits kernels take a mask: the pin as its leading full rows
             hold, pin = (pin[0], hold_mask(torch.zeros(J, dtype=torch.bool, device=x_T.device), B, T, J, x_T.device, rows=pin[1])), None
     if hold is not None:
         hold = _hold_req(hold, B, T, J, x_T.device)
+    if slew is not None:
+        slew = _slew_req(slew, B, J, x_T.device)
+        limits = {} if limits is None else limits
     if limits is not None:
         limits = _limits_req(limits, J, x_T.device)
         limits = (limits.lo, limits.hi, bool(reproject))
@@ -782,7 +918,7 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         hold = (hold[0], x_T.clone() if inplace else x_T, hold[1])
     if multistep is not None:   # (weights, history): the history is written before it is read - no clearing
         multistep = (multistep, torch.empty_like(x))
-    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep, limits)
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep, limits, slew)
 
 
 def default_sampler_cap() -> int:
@@ -806,14 +942,14 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                         trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, multistep=None,
-                        limits=None, reproject: bool = False):
+                        limits=None, reproject: bool = False, slew=None):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin``, ``hold``, ``draws``, ``multistep``, ``limits`` and ``reproject``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
+    ``pin``, ``hold``, ``draws``, ``multistep``, ``limits``, ``reproject`` and ``slew``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
     rows: correct, not shared; a repeat restarts from ``x_T``, so the multistep history needs nothing more)."""
     import warnings
 
@@ -828,10 +964,12 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         multistep = _multistep_req(multistep, step_tokens.shape[0])
     if limits is not None:
         limits = _limits_req(limits, x_T.shape[2], x_T.device)
+    if slew is not None:
+        slew = _slew_req(slew, x_T.shape[0], x_T.shape[2], x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
     out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                      limits=limits, reproject=reproject)
+                      limits=limits, reproject=reproject, slew=slew)
     word = int(status.item())
     if word == 0:
         return out
@@ -842,7 +980,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
             out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                              limits=limits, reproject=reproject)
+                              limits=limits, reproject=reproject, slew=slew)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -852,7 +990,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
         out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                          limits=limits, reproject=reproject)
+                          limits=limits, reproject=reproject, slew=slew)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
@@ -991,6 +1129,21 @@ def trajectory_errors(x: Tensor, target: Tensor, mean: Tensor, std: Tensor, draw
                                                 joint_err.data_ptr(), best.data_ptr(), Cn, draws, T, J, int(bool(angular)), _stream()),
           "sd_eval_trajectory_errors")
     return err, row_err, joint_err, best
+
+
+def max_step(x: Tensor, mean: Tensor, std: Tensor) -> Tensor:
+    """The largest step between consecutive rows of sampled trajectories, per joint (``sd_eval_max_step``, one launch): ``x`` (N, T, J) in
+    the sampler's normalised space -> (N, J) with [n, j] = max over t of |r[t + 1] - r[t]|, r = x std + mean (fp32).  The number from
+    which a slew limit is chosen, and the one that shows it held."""
+    _req(x, "x"); _req(mean, "mean"); _req(std, "std")
+    if x.dim() != 3 or x.shape[0] == 0:
+        raise ValueError(f"max_step: x must be (N, T, J), got {tuple(x.shape)}")
+    N, T, J = x.shape
+    if tuple(mean.shape) != (J,) or tuple(std.shape) != (J,) or not 1 <= J <= 32 or mean.device != x.device or std.device != x.device:
+        raise ValueError(f"max_step: mean and std must be ({J},) with J <= 32 on x's device")
+    out = torch.empty(N, J, dtype=torch.float32, device=x.device)
+    check(_lib.load().sd_eval_max_step(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), N, T, J, _stream()), "sd_eval_max_step")
+    return out
 
 
 def noise_loss_grid(model, ctx_list, x0n: Tensor, noise: Tensor, timesteps: Tensor, acp: Optional[Tensor] = None, return_eps: bool = False):
@@ -2309,6 +2462,73 @@ def session_limits(limits: Limits, lo_rad, hi_rad, mean: Tensor, std: Tensor, J:
                                         hi_rad.ctypes.data_as(_lib.c_float_p), mean.data_ptr(), std.data_ptr(), int(J), _stream()),
           "sd_session_limits")
     return limits
+
+
+SLEW_U = 2.0 ** -24   # the unit roundoff of fp32
+
+
+def _half_ulp(z) -> np.ndarray:
+    """Half an ulp of the fp32 binade of z (1 + 2^-20), in fp64: the most one rounding to nearest adds to a result of magnitude <= z."""
+    z = np.asarray(z, dtype=np.float64) * (1.0 + 2.0 ** -20)
+    return np.where(z > 0, np.ldexp(1.0, np.frexp(np.where(z > 0, z, 1.0))[1] - 1 - 24), 0.0)
+
+
+def session_slew_margin(bound_rad, mean, std) -> np.ndarray:
+    """The margin of ``sd_session_slew`` in radians, fp64, per joint: std hu(XS / std) + 2 hu(XS) + 2 hu(pi + R) + 2 hu(R) with
+    XS = R + |pi - mean| and hu half an fp32 ulp - what the rounding of y +- v in the scan and both roundings of the commit's expression
+    can add to the difference of two published values."""
+    R, s = np.asarray(bound_rad, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    XS = R + np.abs(math.pi - np.asarray(mean, dtype=np.float64))
+    return s * _half_ulp(XS / s) + 2.0 * _half_ulp(XS) + 2.0 * _half_ulp(math.pi + R) + 2.0 * _half_ulp(R)
+
+
+def denormalised_slew_margin(bound, mean, std) -> np.ndarray:
+    """``session_slew_margin`` for trajectories that are denormalised and nothing else, r = x * std + mean (``ops.normalize(inverse=True)``,
+    ``ops.max_step``, ``ops.trajectory_errors``): std hu(XS / std) + 2 hu(XS) + 2 hu(Q) with Q = ``bound`` >= |r| and XS = Q + |mean|
+    >= |x std| - the scan's rounding and the product's and the sum's of either value (the fma form has one less)."""
+    Q, s = np.asarray(bound, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    XS = Q + np.abs(np.asarray(mean, dtype=np.float64))
+    return s * _half_ulp(XS / s) + 2.0 * _half_ulp(XS) + 2.0 * _half_ulp(Q)
+
+
+def session_slew_host(v_rad, bound_rad, mean, std) -> np.ndarray:
+    """The host model of ``sd_session_slew``'s arithmetic, for J joints: fp32 v_n from fp32 v_rad, bound, mean and std."""
+    v = (np.asarray(v_rad, dtype=np.float32).astype(np.float64) - session_slew_margin(bound_rad, np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32))) / np.asarray(std, dtype=np.float32).astype(np.float64)
+    v = np.maximum(v, 0.0)
+    out = v.astype(np.float32)
+    over = out.astype(np.float64) > v
+    out[over] = np.nextafter(out[over], np.float32(0))
+    return out
+
+
+def session_slew(v_n: Tensor, v_rad, bound_rad, mean: Tensor, std: Tensor, J: int) -> Tensor:
+    """One launch (``sd_session_slew``) writes ``v_n`` - the (32,) device array a session's rollout reads - from ``v_rad``, radians per
+    row as published, and ``bound_rad``, a finite bound on the magnitude of the published values per joint (host arrays of at least J
+    fp32)."""
+    v_rad, bound_rad = np.ascontiguousarray(v_rad, dtype=np.float32), np.ascontiguousarray(bound_rad, dtype=np.float32)
+    if v_rad.ndim != 1 or bound_rad.ndim != 1 or v_rad.shape[0] < J or bound_rad.shape[0] < J:
+        raise ValueError(f"session_slew: v_rad and bound_rad must hold at least {J} floats")
+    if not _is_dev32(v_n, mean.device):
+        raise ValueError(f"session_slew: v_n is the (32,) fp32 array of ops.joint_slew on {mean.device}")
+    _req(mean, "mean"); _req(std, "std")
+    check(_lib.load().sd_session_slew(v_n.data_ptr(), v_rad.ctypes.data_as(_lib.c_float_p), bound_rad.ctypes.data_as(_lib.c_float_p),
+                                      mean.data_ptr(), std.data_ptr(), int(J), _stream()), "sd_session_slew")
+    return v_n
+
+
+def session_anchor(anchor: Tensor, x: Tensor, row: int, draws: int = 1, robots=None) -> Tensor:
+    """One launch (``sd_session_anchor``): row ``row`` of ``x`` (S, T, J; normalised space) becomes the anchor of the robots' next tick -
+    rows (b * draws + g) of ``anchor`` (B * draws, 32) for robot b = ``robots[s]`` (None: s) and every draw g."""
+    _req(x, "x")
+    S, T, J = x.shape
+    B = anchor.shape[0] // draws
+    if not _is_dev32(anchor, x.device, B * draws):
+        raise ValueError("session_anchor: anchor is a contiguous (B * draws, 32) fp32 tensor on x's device")
+    r = None if robots is None else _robots_on(robots, B, x.device)
+    if (S != B) if r is None else (r.numel() != S):
+        raise ValueError(f"session_anchor: x holds {S} robots")
+    check(_lib.load().sd_session_anchor(anchor.data_ptr(), x.data_ptr(), _ptr(r), S, B, T, J, int(row), int(draws), _stream()), "sd_session_anchor")
+    return anchor
 
 
 def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0,

@@ -46,6 +46,7 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -119,7 +120,7 @@ class _GraphedTick:
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
-                 select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False):
+                 select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False, slew=None):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -150,7 +151,17 @@ class PolicySession:
         ``set_limits`` rewrites the same device arrays, safe under ``use_graph``.  It composes with ``carry`` (the carried rows travel as
         mask bits, as under ``holds``: the seam stays exact, and they were published under the limits; J <= 32), ``holds`` (a held joint
         keeps its value whatever the limits say), ``draws``, ``robots=``, ``solver`` and ``use_graph``.  Without the argument every launch
-        is the one of the session without any of this.  Not for a distilled decoder."""
+        is the one of the session without any of this.  Not for a distilled decoder.
+        ``slew`` ((J,) floats, one number, or ``{joint: v}``): slew limits in radians PER ROW as published - ``v = max velocity / row
+        rate``, e.g. 8 rad/s at 50 Hz rows: 0.16; +inf: none.  One launch converts them to normalised space, ``v / std[j]`` moved inward by
+        a margin that covers the rounding of the scan and of the commit (``sd_session_slew``), and every tick's rollout keeps consecutive
+        rows of the predicted clean trajectory within them at every step (``ops.ddim_sample(slew=...)``): consecutive published rows of a
+        tick differ by at most ``v``, evaluated exactly, and so does a tick's first row from the robot's last committed row (row
+        ``advance - 1`` of its previous tick, kept on the device in normalised space; none after ``reset`` for the robots reset).  The
+        margin assumes published values inside ``limits`` where both sides are given, else inside [-pi, pi].  ``set_slew`` rewrites the
+        same device array, safe under ``use_graph``.  With ``carry`` row 0 is pinned: the scan starts from the carried rows (the seam
+        stays exact) and no anchor is used.  A jump into a held joint's value is not limited.  It composes with ``limits``, ``holds``,
+        ``draws``, ``robots=``, ``solver`` and ``use_graph``.  Not for a distilled decoder; a ``v`` not above its margin raises."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
@@ -159,6 +170,7 @@ class PolicySession:
         self.solver = self.check_solver(solver, model.num_joints, self.carry, self.distilled)                              # (likewise)
         limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled)                                   # (likewise)
         self.reproject = bool(reproject)
+        slew = self.check_slew(slew, model.num_joints, self.carry, self.distilled)                                         # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -193,6 +205,16 @@ class PolicySession:
         if limits is not None:
             self._limits = ops.joint_limits({}, J=self.J, device=self.device)
             ops.session_limits(self._limits, *limits, model.mean, model.std, self.J)
+        self._slew_v = self._anchor = None   # the normalised slew limits (32,) and the scan's anchors (B * draws, 32): device arrays
+        self._limits_rad = limits
+        if slew is not None:
+            if self._limits is None:   # the slew call reads a box: an infinite one
+                self._limits = ops.joint_limits({}, J=self.J, device=self.device)
+            self._slew_v = ops.joint_slew({}, J=self.J, device=self.device)
+            self._anchor = torch.full((self.B * self.draws, 32), float("nan"), dtype=torch.float32, device=self.device)
+            self._mean_host = model.mean.detach().reshape(-1).cpu().numpy().astype(np.float32)
+            self._std_host = model.std.detach().reshape(-1).cpu().numpy().astype(np.float32)
+            self._write_slew(slew)
         self.reset()
 
     @staticmethod
@@ -268,10 +290,57 @@ class PolicySession:
             raise RuntimeError("PolicySession.set_limits: the session was built without limits")
         host = self.check_limits(lo if hi is None else (lo, hi), self.J, self.carry, self.distilled)
         ops.session_limits(self._limits, *host, self.model.mean, self.model.std, self.J)
+        self._limits_rad = host
+        if self._slew_v is not None:   # the slew margin depends on the bound the limits give: one more launch
+            self._write_slew(self._slew_rad)
 
-    def _lim(self) -> dict:
-        """The limit arguments of the tick's rollout: none in a session without limits."""
-        return {} if self._limits is None else {"limits": self._limits, "reproject": self.reproject}
+    @staticmethod
+    def check_slew(slew=None, J: int = 1, carry: int = 0, distilled: bool = False):
+        """``slew`` of a session with J joints, validated (no device needed): None, or the (32,) fp32 host array in radians per row,
+        padded with +inf ((J,) floats, one number, or ``{joint: v}``, as ``ops.joint_slew`` takes them).  ValueError for a wrong shape, a
+        NaN or a negative value, J > 32, or with a distilled decoder (no rollout to limit)."""
+        if slew is None:
+            return None
+        if distilled:
+            raise ValueError("slew: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        return ops._slew_host(slew, J)
+
+    def _write_slew(self, v_rad) -> None:
+        """ONE launch: the session's (32,) device array from ``v_rad`` (``check_slew``'s array) under the current ``limits``."""
+        J = self.J
+        bound = np.full(J, math.pi, dtype=np.float32)   # |published| <= pi unless limits on both sides say otherwise
+        if self._limits_rad is not None:
+            lo, hi = (np.abs(a[:J]) for a in self._limits_rad)
+            both = np.isfinite(lo) & np.isfinite(hi)
+            one = np.where(np.isfinite(lo), lo, np.where(np.isfinite(hi), hi, 0.0))
+            bound = np.where(both, np.maximum(lo, hi), np.maximum(bound, one)).astype(np.float32)
+        margin = ops.session_slew_margin(bound, self._mean_host[:J], self._std_host[:J])
+        small = np.isfinite(v_rad[:J]) & ~(v_rad[:J].astype(np.float64) > margin)
+        if small.any():
+            j = int(np.argmax(small))
+            raise ValueError(f"slew: v[{j}] = {v_rad[j]} rad per row is not above the margin {margin[j]:.3e} of the fp32 arithmetic")
+        ops.session_slew(self._slew_v, v_rad, bound, self.model.mean, self.model.std, J)
+        self._slew_rad = v_rad
+
+    def set_slew(self, slew) -> None:
+        """New slew limits in radians per row as published (as the constructor's ``slew``): ONE small launch rewrites the session's device
+        array in place, so a captured tick stays captured and the next tick runs under the new limits."""
+        if self._slew_v is None:
+            raise RuntimeError("PolicySession.set_slew: the session was built without slew")
+        self._write_slew(self.check_slew(slew, self.J, self.carry, self.distilled))
+
+    def _lim(self, dev_idx=None) -> dict:
+        """The limit arguments of the tick's rollout (of the robots ``dev_idx``): none in a session without limits or slew."""
+        if self._limits is None:
+            return {}
+        out = {"limits": self._limits, "reproject": self.reproject}
+        if self._slew_v is not None:
+            start = None   # with carry row 0 is pinned: the scan starts from the carried rows
+            if self.carry == 0:
+                G = self.draws
+                start = self._anchor if dev_idx is None else self._anchor.view(self.B, G * 32)[dev_idx.long()].reshape(-1, 32).contiguous()
+            out["slew"] = (self._slew_v, start)
+        return out
 
     @property
     def _carrying(self) -> bool:
@@ -395,6 +464,8 @@ class PolicySession:
             mask[ops.robot_index(robots, self.B).long()] = True
             mask = mask.to(self.device)
         ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE, pin_rows=self._pin_rows if self._carrying else None)
+        if self._anchor is not None:   # no last command: the robots' next first row is free
+            self._anchor.view(self.B, -1).masked_fill_(mask.view(self.B, 1), float("nan"))
 
     def reset(self, robots=None) -> None:
         """Rings back to ``context_length`` rows of zeros (ros.py:87-106), the image ring to the token of an all-zero frame
@@ -420,6 +491,8 @@ class PolicySession:
         self._game_state = torch.full((B,), DEFAULT_GAME_STATE, dtype=torch.int64, device=dev)
         self._gen = torch.Generator(device=dev).manual_seed(self._seed)
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
+        if self._anchor is not None:   # (in place: the array is the session's for its lifetime)
+            self._anchor.fill_(float("nan"))
         if self._carrying:   # the rows carried into the next tick (normalised space) and how many per robot: 0 until a tick has committed
             self._pin_rows = torch.zeros(B, dtype=torch.int32, device=dev)
         if self.holds and getattr(self, "_held", None) is not None:
@@ -618,9 +691,9 @@ class PolicySession:
                 if self.distilled:   # one forward at t = 0 (ros.py:293-298)
                     x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
                 elif G == 1:
-                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver, **self._lim())
+                    x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver, **self._lim(dev_idx))
                 else:   # the context was encoded once per robot; its G draws share the folded planes
-                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver, **self._lim()).contiguous()
+                    every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver, **self._lim(dev_idx)).contiguous()
                     index, chosen = ops.select_medoid(every, G)
                     x = (chosen, every, index)
             if G == 1:
@@ -638,6 +711,10 @@ class PolicySession:
 
     def _commit(self, x: torch.Tensor, dev_idx) -> torch.Tensor:
         m = self.model
+        if self._anchor is not None and self.carry == 0:
+            # the next tick's scan starts from the last row this one commits (normalised space, as sampled).  One launch beside the commit,
+            # outside a captured tick like the commit itself: a replay whose range guard trips is repeated eagerly under the OLD anchor.
+            ops.session_anchor(self._anchor, x, self.advance - 1, self.draws, robots=dev_idx)
         if not self._carrying:
             return ops.session_commit(x, m.mean, m.std, *self._action, robots=dev_idx)
         return ops.session_commit_carry(x, m.mean, m.std, *self._action, self.advance, self.carry, self._pin_x0, self._pin_rows, robots=dev_idx)

@@ -729,6 +729,24 @@ int sd_adamw_ema_step(float *p, const float *g, float *m, float *v, float *ema, 
 int sd_adamw_ema_step_dev(float *p, const float *g, float *m, float *v, float *ema, long n, const float *hyper7_dev,
                           const float *ema_weight_dev, void *stream);
 
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm type 2) and the non-finite guard, on device memory so that a
+ * captured hipGraph replays them.  sd_grad_norm, two launches:
+ *   s = sum g[i]^2 in fp64 (the product of two fp32 values is exact there), in one fixed order that depends on n alone - not on
+ *       the device, the grid or g's alignment: deterministic, and 1e20 or 1e-25 gradients neither overflow nor vanish;
+ *   clip2[0] = norm = (float)sqrt(s);  clip2[1] = coef = min(1, max_norm / (norm + 1e-6f)) in fp32, or 0 where norm is not finite -
+ *       then the int32 *skipped goes up by one (plain store: the caller zeroes it once).
+ * partials_ws: sd_grad_norm_workspace_doubles() doubles of device scratch.  max_norm >= 0; +inf = norm and guard only (coef = 1).
+ * sd_adamw_clip_step / _dev: sd_adamw_step / sd_adamw_ema_step (ema != NULL; ema_weight[_dev] is read only then) and their _dev
+ * forms on g[i] * coef (one fp32 rounding; g itself is not written), bit for bit what those write for a gradient buffer that holds
+ * the products - so coef = 1 is their step exactly.  Where clip2[0] is not finite nothing is read or written: p, m, v, ema keep
+ * their bits.  SD_E_BADARG, nothing launched: a NULL operand, n <= 0, max_norm negative or NaN. */
+int sd_grad_norm_workspace_doubles(void);
+int sd_grad_norm(const float *g, long n, void *partials_ws, float *clip2, int *skipped, float max_norm, void *stream);
+int sd_adamw_clip_step(float *p, const float *g, float *m, float *v, float *ema, long n, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, long step, double ema_weight, const float *clip2, void *stream);
+int sd_adamw_clip_step_dev(float *p, const float *g, float *m, float *v, float *ema, long n, const float *hyper7_dev,
+                           const float *ema_weight_dev, const float *clip2, void *stream);
+
 /* Per-step part of the dropout mask key from DEVICE memory: when set (non-NULL), every dropout kernel adds *device_word to
  * the high half of its Philox key at run time, so a hipGraph replay of a training step draws fresh masks once the host has
  * changed the word.  Process-wide; NULL switches it off. */

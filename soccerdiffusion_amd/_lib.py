@@ -204,6 +204,10 @@ SIGNATURES = {
     "sd_adamw_hyper": (C.c_int, [C.c_double] * 5 + [C.c_long, c_float_p]),
     "sd_adamw_ema_step": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_double] * 5 + [C.c_long, C.c_double, C.c_void_p]),
     "sd_adamw_ema_step_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sd_grad_norm_workspace_doubles": (C.c_int, []),
+    "sd_grad_norm": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "sd_adamw_clip_step": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_double] * 5 + [C.c_long, C.c_double, C.c_void_p, C.c_void_p]),
+    "sd_adamw_clip_step_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sd_set_dropout_epoch": (C.c_int, [C.c_void_p]),
     "sd_train_layer_fwd_ok": (C.c_int, [C.c_int] * 4),
     "sd_train_layer_fwd": (C.c_int, [C.POINTER(TrainLayerFwdArgs), C.c_void_p]),

@@ -2,9 +2,9 @@
 the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
-    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]]
+    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]
-    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]]     (ml/training/distill.py:25-224)
+    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]     (ml/training/distill.py:25-224)
     python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [-o report.json]   (evaluation.py)
     python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]   (ml/inference/ros.py:165-335)
 
@@ -17,6 +17,8 @@ per step and `sample` shards the rollouts over the ranks; `--ema-decay` keeps an
 moving average of the weights inside the optimizer step (optim.FusedAdamW) and the checkpoint
 gains `ema_model_state_dict` and `ema`, which `--ema` / `--ema-teacher` load instead of the
 last iterate (the reference's ml/preliminary scripts kept and sampled such an average);
+`train` / `distill --clip-grad-norm X` clip the global gradient norm to X and skip a step whose gradient is not finite, inside the
+optimizer step (`inf`: the guard alone); the printed line gains `GradNorm` / `Skipped` and the checkpoint `grad_clip`;
 `train` / `distill --val-fraction F` hold the last (or a random) fraction of the windows out of training and of the normaliser fit,
 evaluate them every `--val-every` epochs (evaluation.evaluate) and record the reports in the checkpoint's `validation` entry, and
 `evaluate` prints that report for any checkpoint as one JSON line.
@@ -198,6 +200,30 @@ def _ema_checkpoint_keys(optimizer, model) -> dict:
     return {EMA_KEY: optimizer.ema_state_dict(model), "ema": optimizer.ema_state()}
 
 
+def _clip_grad_norm(text: str) -> float:
+    try:
+        value = float(text)
+    except ValueError:
+        value = float("nan")
+    if not value >= 0.0:   # (NaN fails the comparison)
+        raise argparse.ArgumentTypeError(f"--clip-grad-norm takes a norm >= 0, or inf for the non-finite guard alone, got {text!r}")
+    return value
+
+
+def _grad_clip_suffix(optimizer) -> str:
+    """What the printed iteration line gains with --clip-grad-norm (one device read, beside the loss's)."""
+    if optimizer.max_grad_norm is None:
+        return ""
+    st = optimizer.grad_stats()
+    return f", GradNorm: {st['norm']:.05f}, Skipped: {st['skipped_steps']}"
+
+
+def _grad_clip_checkpoint_keys(optimizer) -> dict:
+    if optimizer.max_grad_norm is None:
+        return {}
+    return {"grad_clip": {"max_norm": optimizer.max_grad_norm, "skipped_steps": optimizer.grad_stats()["skipped_steps"]}}
+
+
 def shard_plan(n_total: int, batch_size: int, rank: int, world: int):
     """Sample indices of this rank and the number of optimizer steps per epoch, the SAME on every rank.
 
@@ -290,10 +316,15 @@ def cmd_train(args) -> int:
     ema_decay, ema_warmup = args.ema_decay, not args.no_ema_warmup
     if ema_decay is None and checkpoint is not None and "ema" in checkpoint:   # a resumed run goes on averaging as it did
         ema_decay, ema_warmup = checkpoint["ema"]["decay"], checkpoint["ema"]["warmup"]
-    optimizer = training.FusedAdamW(model.parameters(), lr=params["lr"], ema_decay=ema_decay, ema_warmup=ema_warmup)
+    max_grad_norm = args.clip_grad_norm
+    if max_grad_norm is None and checkpoint is not None and "grad_clip" in checkpoint:   # ... and clipping as it did
+        max_grad_norm = checkpoint["grad_clip"]["max_norm"]
+    optimizer = training.FusedAdamW(model.parameters(), lr=params["lr"], ema_decay=ema_decay, ema_warmup=ema_warmup, max_grad_norm=max_grad_norm)
     if checkpoint is not None and "optimizer_state_dict" in checkpoint:
         optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
     _restore_ema(optimizer, model, checkpoint)
+    if max_grad_norm is not None and checkpoint is not None and "grad_clip" in checkpoint:
+        optimizer.set_skipped_steps(checkpoint["grad_clip"]["skipped_steps"])
     if world > 1:  # ... and rank 0's parameters, moments and buffers are what every rank starts from, whatever happened above
         training.broadcast_parameters(optimizer, model)
     bs = params["batch_size"]
@@ -322,14 +353,15 @@ def cmd_train(args) -> int:
                 loss = training.train_step(model, optimizer, lr_scheduler, scheduler, targets, input_data=inp,
                                            world_size=world, generator=dev_gen)
             if i % 20 == 0 and rank == 0:
-                print(f"Epoch {epoch}, it {i}, Loss: {float(loss):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}", flush=True)
+                print(f"Epoch {epoch}, it {i}, Loss: {float(loss):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}{_grad_clip_suffix(optimizer)}", flush=True)
         if val is not None and rank == 0:   # (the other ranks wait at the collective below)
             val.run(model, optimizer, source, epoch, params["epochs"])
         training.assert_replicas_equal(optimizer)   # one pair of tiny all-reduces per epoch
         if rank == 0:
             torch.save({"model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model), **({} if val is None else {"validation": val.entry()})},
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model), **_grad_clip_checkpoint_keys(optimizer),
+                        **({} if val is None else {"validation": val.entry()})},
                        args.output)
     if world > 1:
         import torch.distributed as dist
@@ -376,7 +408,8 @@ def cmd_distill(args) -> int:
     # the student's context encoders never see a gradient (the context comes from the teacher under
     # no_grad), so torch's AdamW leaves them untouched; the flat optimizer therefore only owns the rest
     trainable = [p for n, p in student.named_parameters() if n.startswith(("diffusion_action_generator.", "step_encoding."))]
-    optimizer = training.FusedAdamW(trainable, lr=params["lr"], ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
+    optimizer = training.FusedAdamW(trainable, lr=params["lr"], ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
+                                    max_grad_norm=args.clip_grad_norm)
     if world > 1:
         training.broadcast_parameters(optimizer, student)
 
@@ -415,14 +448,16 @@ def cmd_distill(args) -> int:
             lr_scheduler.step()
             mean_loss += float(loss)
             if i % 20 == 0 and rank == 0:
-                print(f"Epoch {epoch}, it {i}, Loss: {mean_loss / (i + 1):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}", flush=True)
+                print(f"Epoch {epoch}, it {i}, Loss: {mean_loss / (i + 1):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}{_grad_clip_suffix(optimizer)}",
+                      flush=True)
         if val is not None and rank == 0:
             val.run(student, optimizer, source, epoch, params["epochs"])
         training.assert_replicas_equal(optimizer)
         if rank == 0:
             torch.save({"model_state_dict": student.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
-                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student), **({} if val is None else {"validation": val.entry()})},
+                        "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student), **_grad_clip_checkpoint_keys(optimizer),
+                        **({} if val is None else {"validation": val.entry()})},
                        args.output)
     if world > 1:
         import torch.distributed as dist
@@ -890,6 +925,9 @@ def build_parser() -> argparse.ArgumentParser:
     for p in (tr, di):
         p.add_argument("--ema-decay", type=_ema_decay, default=None, metavar="D", help="keep an exponential moving average of the trained "
                        "weights with decay D in (0, 1), updated inside the optimizer step; the checkpoint gains ema_model_state_dict and ema")
+        p.add_argument("--clip-grad-norm", type=_clip_grad_norm, default=None, metavar="X", help="clip the global 2-norm of the gradient to X "
+                       "(>= 0; inf = the guard alone) and skip a step whose gradient holds an inf or NaN, inside the optimizer step; the "
+                       "checkpoint gains grad_clip")
         p.add_argument("--no-ema-warmup", action="store_true", help="weight 1 - D from the first update on, instead of "
                        "1 - min(D, (1 + t) / (10 + t)) after t updates")
     for p in (tr, di):

@@ -1216,6 +1216,153 @@ extern "C" int sd_adamw_ema_step_dev(float *p, const float *g, float *m, float *
     return 0;
 }
 
+// Global gradient norm (torch.nn.utils.clip_grad_norm_, norm type 2) and the non-finite guard, ahead of the update and read by it from
+// device memory.  The sum of squares is taken in fp64 - the product of two fp32 values is exact there, so gradients of
+// 1e20 or 1e-25 neither overflow nor vanish - in ONE order that depends on n alone, not on the device, the grid or the alignment:
+//   * GN_WGS workgroups of 256 threads, always; thread t of workgroup b owns the quads (four consecutive floats) b 256 + t,
+//     b 256 + t + 256 GN_WGS, ... in ascending order, x y z w within a quad, one accumulator;
+//   * the < 4 elements behind the last whole quad belong to thread 0 of workgroup 0, after its quads;
+//   * lanes by the xor butterfly (32, 16, .. 1), the four waves through LDS in wave order, one partial per workgroup (0 where a
+//     workgroup owns nothing); the finish sums the partials in index order.
+// An unaligned g takes four dword loads per quad instead of one dwordx4: same elements, same order, same bits.
+#define GN_WGS 512
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict__ g, long n, long n4, int wide, double *__restrict__ partial) {
+    __shared__ double red[4];
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0;
+    if (wide) {
+        const float4 *g4 = reinterpret_cast<const float4 *>(g);
+        for (long i = tid; i < n4; i += 256L * GN_WGS) {
+            const float4 q = g4[i];
+            s += (double)q.x * (double)q.x;
+            s += (double)q.y * (double)q.y;
+            s += (double)q.z * (double)q.z;
+            s += (double)q.w * (double)q.w;
+        }
+    } else {
+        for (long i = tid; i < n4; i += 256L * GN_WGS) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float x = g[4 * i + k];
+                s += (double)x * (double)x;
+            }
+        }
+    }
+    if (tid == 0)
+        for (long i = 4 * n4; i < n; ++i) s += (double)g[i] * (double)g[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// clip[0] = norm, clip[1] = coef = min(1, max_norm / (norm + 1e-6f)) in fp32 (torch's expression), 0 where the norm is not finite - then
+// skipped[0] goes up by one and the update kernels below return before they touch anything.
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double *__restrict__ partial, float *__restrict__ clip, int *skipped,
+                                                               float max_norm) {
+    __shared__ double part[GN_WGS];
+    for (int i = threadIdx.x; i < GN_WGS; i += 256) part[i] = partial[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < GN_WGS; ++i) s += part[i];   // index order: deterministic
+    const float norm = (float)sqrt(s);
+    const bool ok = __builtin_isfinite(norm);
+    const float coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+    clip[0] = norm;
+    clip[1] = ok ? coef : 0.0f;
+    if (!ok) skipped[0] = skipped[0] + 1;
+}
+
+extern "C" int sd_grad_norm_workspace_doubles(void) { return GN_WGS; }
+
+extern "C" int sd_grad_norm(const float *g, long n, void *partials_ws, float *clip2, int *skipped, float max_norm, void *stream) {
+    if (!g || !partials_ws || !clip2 || !skipped || n <= 0 || !(max_norm >= 0.0f))   // (a NaN fails the comparison)
+        return fail(SD_E_BADARG, "sd_grad_norm: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    SD_LAUNCH(grad_sumsq_kernel, dim3(GN_WGS), dim3(256), 0, s, g, n, n / 4, (int)(((uintptr_t)g & 15) == 0), (double *)partials_ws);
+    SD_CHECK_LAUNCH("grad_sumsq_kernel");
+    SD_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, (const double *)partials_ws, clip2, skipped, max_norm);
+    SD_CHECK_LAUNCH("grad_norm_finish_kernel");
+    return 0;
+}
+
+// The AdamW (+ EMA) update on g * coef, coef and the guard read from clip[] (sd_grad_norm) in device memory, so a captured graph
+// replays them: the bodies of the kernels above after one more rounding, contraction off as there - p, m, v, ema come out bit for bit
+// as from sd_adamw_step / sd_adamw_ema_step (and their _dev forms) on a gradient buffer that holds g[i] * coef.  A norm that is not
+// finite returns every workgroup before any load or store of p / m / v / ema.
+__device__ __forceinline__ void adamw_clip_update(float &pi, const float gi, float &mi, float &vi, float &ei, const float coef,
+                                                  const adamw_scalars &h) {
+#pragma clang fp contract(off)
+    adamw_ema_update(pi, gi * coef, mi, vi, ei, h);
+}
+
+// EMA = false: the average's line works on a register that is never stored and the compiler drops it - adamw_kernel's update.
+template <bool EMA, bool DEV>
+__global__ void adamw_clip_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                                  float *__restrict__ ema, long n, long n4, adamw_scalars hs, const float *__restrict__ hyper,
+                                  const float *__restrict__ ema_w, const float *__restrict__ clip) {
+    if (!__builtin_isfinite(clip[0])) return;
+    const float coef = clip[1];
+    adamw_scalars h = hs;
+    if (DEV) h = {hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], EMA ? ema_w[0] : 0.0f};
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v),
+           *e4 = reinterpret_cast<float4 *>(ema);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = tid; i < n4; i += nth) {
+        const float4 gq = g4[i];
+        float4 pq = p4[i], mq = m4[i], vq = v4[i], eq = EMA ? e4[i] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+        adamw_clip_update(pq.x, gq.x, mq.x, vq.x, eq.x, coef, h);
+        adamw_clip_update(pq.y, gq.y, mq.y, vq.y, eq.y, coef, h);
+        adamw_clip_update(pq.z, gq.z, mq.z, vq.z, eq.z, coef, h);
+        adamw_clip_update(pq.w, gq.w, mq.w, vq.w, eq.w, coef, h);
+        p4[i] = pq;
+        m4[i] = mq;
+        v4[i] = vq;
+        if (EMA) e4[i] = eq;
+    }
+    for (long i = 4 * n4 + tid; i < n; i += nth) {
+        float pi = p[i], mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.0f;
+        adamw_clip_update(pi, g[i], mi, vi, ei, coef, h);
+        p[i] = pi;
+        m[i] = mi;
+        v[i] = vi;
+        if (EMA) ema[i] = ei;
+    }
+}
+
+template <bool DEV>
+static int adamw_clip_launch(float *p, const float *g, float *m, float *v, float *ema, long n, const adamw_scalars &h, const float *hyper,
+                             const float *ema_w, const float *clip, hipStream_t s, const char *what) {
+    const long n4 = adamw_ema_wide(p, g, m, v, ema, n);   // (a NULL ema adds no address bits)
+    if (ema)
+        SD_LAUNCH((adamw_clip_kernel<true, DEV>), dim3(adamw_ema_grid(n, n4)), dim3(256), 0, s, p, g, m, v, ema, n, n4, h, hyper, ema_w, clip);
+    else
+        SD_LAUNCH((adamw_clip_kernel<false, DEV>), dim3(adamw_ema_grid(n, n4)), dim3(256), 0, s, p, g, m, v, ema, n, n4, h, hyper, ema_w, clip);
+    SD_CHECK_LAUNCH(what);
+    return 0;
+}
+
+extern "C" int sd_adamw_clip_step(float *p, const float *g, float *m, float *v, float *ema, long n, double lr, double beta1, double beta2,
+                                  double eps, double weight_decay, long step, double ema_weight, const float *clip2, void *stream) {
+    if (!p || !g || !m || !v || !clip2 || n <= 0 || step <= 0 || (ema && !(ema_weight >= 0.0 && ema_weight <= 1.0)))
+        return fail(SD_E_BADARG, "sd_adamw_clip_step: bad argument");
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const adamw_scalars h = {(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                             (float)(lr / bc1), (float)sqrt(bc2), (float)eps, ema ? (float)ema_weight : 0.0f};
+    return adamw_clip_launch<false>(p, g, m, v, ema, n, h, nullptr, nullptr, clip2, (hipStream_t)stream, "adamw_clip_kernel");
+}
+
+extern "C" int sd_adamw_clip_step_dev(float *p, const float *g, float *m, float *v, float *ema, long n, const float *hyper7_dev,
+                                      const float *ema_weight_dev, const float *clip2, void *stream) {
+    if (!p || !g || !m || !v || !hyper7_dev || !clip2 || n <= 0 || (ema && !ema_weight_dev))
+        return fail(SD_E_BADARG, "sd_adamw_clip_step_dev: bad argument");
+    return adamw_clip_launch<true>(p, g, m, v, ema, n, adamw_scalars{}, hyper7_dev, ema_weight_dev, clip2, (hipStream_t)stream,
+                                   "adamw_clip_dev_kernel");
+}
+
 // out[c] += sum_r src[r*row_stride + c]   (bias-like gradients over strided rows)
 __global__ void colsum_kernel(const float *__restrict__ src, long row_stride, long rows, int width, float *out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1658,6 +1658,55 @@ def adamw_ema_step_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, ema: Tensor, 
                                     ema_weight.data_ptr(), _stream()), "sd_adamw_ema_step_dev")
 
 
+def grad_norm_workspace_doubles() -> int:
+    """Doubles of device scratch ``grad_norm`` needs (a constant of the library: its fixed grid)."""
+    return int(_lib.load().sd_grad_norm_workspace_doubles())
+
+
+def grad_norm(g: Tensor, partials: Tensor, clip: Tensor, skipped: Tensor, max_norm: float) -> None:
+    """Global 2-norm of the flat gradient ``g`` in one deterministic fp64 summation -> ``clip[0]``; the clipping coefficient
+    ``min(1, max_norm / (norm + 1e-6))`` (fp32, torch's clip_grad_norm_) -> ``clip[1]``, or 0 where the norm is not finite - then the
+    int32 ``skipped[0]`` goes up by one.  Two launches, no host read: graph-capturable.  ``partials``: ``grad_norm_workspace_doubles()``
+    float64 of scratch."""
+    lib = _lib.load()
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:   # (NaN fails the comparison)
+        raise ValueError(f"max_norm must be >= 0 (inf = norm and guard only), got {max_norm!r}")
+    _req(g, "g"); _req(partials, "partials", torch.float64); _req(clip, "clip"); _req(skipped, "skipped", torch.int32)
+    if g.numel() < 1 or partials.numel() < grad_norm_workspace_doubles() or clip.numel() < 2 or skipped.numel() < 1:
+        raise ValueError("g needs >= 1 element, partials grad_norm_workspace_doubles() doubles, clip 2 floats, skipped one int32")
+    check(lib.sd_grad_norm(g.data_ptr(), g.numel(), partials.data_ptr(), clip.data_ptr(), skipped.data_ptr(), max_norm, _stream()),
+          "sd_grad_norm")
+
+
+def adamw_clip_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, ema: Optional[Tensor], clip: Tensor, lr: float, beta1: float, beta2: float,
+                    eps: float, weight_decay: float, step: int, ema_weight: float = 0.0) -> None:
+    """``adamw_step`` (``ema`` None) or ``adamw_ema_step`` on ``g * clip[1]``, skipped entirely where ``clip[0]`` is not finite
+    (``clip``: what ``grad_norm`` wrote); ``g`` is not modified."""
+    lib = _lib.load()
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (clip, "clip")) + (() if ema is None else ((ema, "ema"),)):
+        _req(t, n)
+    if clip.numel() < 2 or (ema is not None and ema.numel() != p.numel()):
+        raise ValueError("clip needs 2 floats, ema as many elements as p")
+    check(lib.sd_adamw_clip_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(ema), p.numel(), lr, beta1, beta2, eps,
+                                 weight_decay, step, ema_weight, clip.data_ptr(), _stream()), "sd_adamw_clip_step")
+
+
+def adamw_clip_step_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, ema: Optional[Tensor], clip: Tensor, hyper7: Tensor,
+                        ema_weight: Optional[Tensor] = None) -> None:
+    """``adamw_step_dev`` (``ema`` None) or ``adamw_ema_step_dev`` on ``g * clip[1]``, skipped where ``clip[0]`` is not finite."""
+    lib = _lib.load()
+    if ema is not None and ema_weight is None:
+        raise ValueError("with ema the update needs the device float ema_weight")
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (clip, "clip"), (hyper7, "hyper7")) + (
+            () if ema is None else ((ema, "ema"), (ema_weight, "ema_weight"))):
+        _req(t, n)
+    if hyper7.numel() < 7 or clip.numel() < 2 or (ema is not None and (ema_weight.numel() < 1 or ema.numel() != p.numel())):
+        raise ValueError("hyper7 needs 7 floats, clip 2, ema_weight one, ema as many elements as p")
+    check(lib.sd_adamw_clip_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(ema), p.numel(), hyper7.data_ptr(),
+                                     None if ema is None else ema_weight.data_ptr(), clip.data_ptr(), _stream()), "sd_adamw_clip_step_dev")
+
+
 # ---- image path: ResNet basic-block convolution (csrc/sd_conv.hip) -------------------------------------
 class PackedConv3x3:
     """A 3 x 3 (or 1 x 1) convolution weight (Cout, Cin, k, k) in the fragment order of ``sd_conv3x3_bn_act`` / ``sd_conv_s2_bn_act`` plus

@@ -159,13 +159,25 @@ class FusedAdamW(torch.optim.Optimizer):
     lineage took its EMA from ``ema_pytorch`` (``EMA(model, beta=0.9999)``), and neither that nor ``diffusers``' EMAModel is
     installed here to pin the warmup against - only the fixed point, ``1 - ema_decay``, is common to all of them.  ``state_dict()``
     stays torch AdamW's; the average travels as a model state dict (``ema_state_dict`` / ``load_ema_state_dict``) beside
-    ``ema_state()``.  Sampling from it in mid-training: ``with optimizer.ema_weights(): ...``."""
+    ``ema_state()``.  Sampling from it in mid-training: ``with optimizer.ema_weights(): ...``.
+
+    ``max_grad_norm`` (None = off: nothing allocated, today's launches): ``torch.nn.utils.clip_grad_norm_`` (norm type 2, over the
+    whole flat gradient) and a non-finite guard in front of the update, all on the device - eager step, graph replay and the
+    data-parallel step (after the all-reduce, so every rank computes the same coefficient) alike.  Two small launches take the norm
+    in ONE deterministic fp64 summation (``ops.grad_norm``); the update then runs on ``g * coef`` with
+    ``coef = min(1, max_grad_norm / (norm + 1e-6))``, and where the norm is inf or NaN it does not run at all: parameters, moments
+    and EMA keep their bits and a device counter goes up.  ``inf`` = guard and norm only (``coef`` = 1: bit for bit the unclipped
+    step).  A skipped step still USES UP its step number: the host is not told, so ``_step``, the bias corrections, OneCycleLR and
+    ``ema_updates`` advance as after any other step.  ``grad_stats()`` reads norm, coefficient and the count of skipped steps."""
 
     def __init__(self, params: Iterable[Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 weight_decay: float = 1e-2, ema_decay: Optional[float] = None, ema_warmup: bool = True,
+                 max_grad_norm: Optional[float] = None):
         params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:   # (NaN fails the comparison)
+            raise ValueError(f"max_grad_norm must be >= 0 (inf = guard and norm only) or None, got {max_grad_norm!r}")
         if ema_decay is not None and not 0.0 < ema_decay < 1.0:
             raise ValueError(f"ema_decay must lie in (0, 1) or be None, got {ema_decay!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -188,6 +200,12 @@ class FusedAdamW(torch.optim.Optimizer):
         self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
         self.ema_updates = 0   # completed EMA updates (its own count: an average may start in the middle of a run)
         self.flat_ema = self.flat_param.clone() if ema_decay is not None else None
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._gn_partials = self._clip = self._skipped = None
+        if self.max_grad_norm is not None:   # allocated once: their addresses sit in a captured graph
+            self._gn_partials = torch.zeros(ops.grad_norm_workspace_doubles(), dtype=torch.float64, device=dev)
+            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)   # [norm, coef] of the last step
+            self._skipped = torch.zeros(1, dtype=torch.int32, device=dev)
         self.planes = WeightPlanes(self.flat_param, params)
         self.refresh_transposes()
 
@@ -212,7 +230,13 @@ class FusedAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         g = self.param_groups[0]
         self._step += 1
-        if self.flat_ema is None:
+        if self.max_grad_norm is not None:
+            ops.grad_norm(self.flat_grad, self._gn_partials, self._clip, self._skipped, self.max_grad_norm)
+            ops.adamw_clip_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, self.flat_ema, self._clip, g["lr"], g["betas"][0],
+                                g["betas"][1], g["eps"], g["weight_decay"], self._step,
+                                0.0 if self.flat_ema is None else self.ema_weight_for_step(self.ema_updates))
+            self.ema_updates += int(self.flat_ema is not None)
+        elif self.flat_ema is None:
             ops.adamw_step(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
                            g["eps"], g["weight_decay"], self._step)
         else:
@@ -225,14 +249,34 @@ class FusedAdamW(torch.optim.Optimizer):
     def step_from_device_hyper(self, hyper7: Tensor, ema_weight: Optional[Tensor] = None) -> None:
         """The update with its scalars read from device memory (``hyper_for_step``): what a captured graph replays.
         Does NOT advance ``_step`` (nor ``ema_updates``) - the caller that fills ``hyper7`` does.  With an EMA, ``ema_weight`` is the
-        device float that holds ``ema_weight_for_step(ema_updates)`` when the update runs."""
-        if self.flat_ema is None:
+        device float that holds ``ema_weight_for_step(ema_updates)`` when the update runs.  With ``max_grad_norm`` the norm's two
+        launches come first and ``max_grad_norm`` is one of their (frozen) arguments."""
+        if self.flat_ema is not None and ema_weight is None:
+            raise ValueError("this optimizer keeps an EMA: the update needs the device word with its weight")
+        if self.max_grad_norm is not None:
+            ops.grad_norm(self.flat_grad, self._gn_partials, self._clip, self._skipped, self.max_grad_norm)
+            ops.adamw_clip_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, self.flat_ema, self._clip, hyper7, ema_weight)
+        elif self.flat_ema is None:
             ops.adamw_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, hyper7)
         else:
-            if ema_weight is None:
-                raise ValueError("this optimizer keeps an EMA: the update needs the device word with its weight")
             ops.adamw_ema_step_dev(self.flat_param, self.flat_grad, self.flat_m, self.flat_v, self.flat_ema, hyper7, ema_weight)
         self.refresh_transposes()
+
+    # ---- gradient clipping ---------------------------------------------------------------
+    def grad_stats(self) -> dict:
+        """``{"norm", "coef", "skipped_steps"}``: the gradient norm and clipping coefficient of the last step (norm 0 / coef 1 before the
+        first; coef 0 where that step was skipped) and the number of skipped steps so far.  ONE device read of three words - it waits
+        for the stream, so call it where a sync is affordable (``cli train`` does beside the printed loss), not every step."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("this optimizer does not clip (max_grad_norm=None)")
+        w = torch.cat([self._clip, self._skipped.view(torch.float32)]).cpu()
+        return {"norm": float(w[0]), "coef": float(w[1]), "skipped_steps": int(w[2:3].view(torch.int32)[0])}
+
+    def set_skipped_steps(self, count: int) -> None:
+        """Resume: the count of skipped steps a checkpoint carried."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("this optimizer does not clip (max_grad_norm=None)")
+        self._skipped.fill_(int(count))
 
     # ---- weight EMA ---------------------------------------------------------------------
     def ema_weight_for_step(self, t: int) -> float:

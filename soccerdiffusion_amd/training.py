@@ -956,7 +956,9 @@ def train_step(model, optimizer: FusedAdamW, lr_scheduler, scheduler, joint_targ
     """One iteration of the reference loop body (train.py:204-240) on already-normalised
     targets.  ``context`` given = the --decoder-pretraining path (train.py:221-224).
     Data parallel (``world_size`` > 1): the gradient all-reduce runs per decoder layer, overlapped with the rest of the
-    backward (``BucketedAllReduce``); ``bucketed=False`` = one all-reduce after it."""
+    backward (``BucketedAllReduce``); ``bucketed=False`` = one all-reduce after it.  Gradient clipping and the non-finite guard
+    (``FusedAdamW(max_grad_norm=...)``) live in ``optimizer.step()``, behind the exchange: the norm is that of the reduced gradient,
+    every rank computes the same coefficient and takes or skips the step together - no collective of their own."""
     global _BUCKETS
     B = joint_targets.shape[0]
     dev = joint_targets.device
@@ -999,6 +1001,11 @@ class GraphedTrainStep:
     step cannot sit in kernel arguments, which a graph freezes, so it comes from device memory instead:
       * AdamW's scalars (OneCycleLR's lr and cycled beta1, the bias corrections) - ``sd_adamw_step_dev``;
       * with ``FusedAdamW(ema_decay=...)`` the weight of the coming EMA update, a ninth word - ``sd_adamw_ema_step_dev``, same launch;
+      * with ``FusedAdamW(max_grad_norm=...)`` the gradient norm, the clipping coefficient and the non-finite guard: the two
+        ``sd_grad_norm`` launches write them to device words and ``sd_adamw_clip_step_dev`` reads them there, all three inside the
+        captured update (``max_grad_norm`` itself is a frozen argument: constant for a run).  A replay equals the eager step bit for
+        bit, and a step with a non-finite gradient leaves the weights as they were without the host being told
+        (``optimizer.grad_stats()`` reads the count);
       * the per-step part of the dropout key - ``sd_set_dropout_epoch`` (process-wide; reset by ``close()``);
       * timesteps and noise come from ``generator`` (registered with the graph: torch advances its Philox offset per replay).
     The first ``eager_steps`` calls run the ordinary ``train_step`` (they are real training steps and warm every lazy

@@ -2,7 +2,11 @@
 """Secondary metric: training trajectories/s (one fwd + bwd + AdamW per trajectory) at BASELINE
 config 2: decoder d=256, L=4, B=256, T=100, J=20, M=11 (decoder-pretraining path), fp32.
 N>1 under torchrun: data parallel, one flat-gradient all-reduce per step.
---ema-decay D: the same step with the weight EMA riding in the AdamW launch (FusedAdamW(ema_decay=D))."""
+--ema-decay D: the same step with the weight EMA riding in the AdamW launch (FusedAdamW(ema_decay=D)).
+--clip X: what gradient clipping costs (FusedAdamW(max_grad_norm=...)), on the replayed graph (training.GraphedTrainStep) and in ONE
+process: three legs - clipping off, the guard alone (inf) and X - from the same seed, timed in alternating blocks of --steps replays,
+--blocks times round; one JSON line per leg with the median block, the blocks' spread and the clipping coefficient after every block
+(< 1 throughout: X bound), then one line with the differences of the medians."""
 import argparse, json, os, sys, time
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +19,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--ema-decay", type=float, default=None)
+    ap.add_argument("--clip", type=float, default=None, metavar="X")
+    ap.add_argument("--blocks", type=int, default=7)
     args = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dev = torch.device("cuda", local)
@@ -32,6 +38,10 @@ def main():
                   use_images=False, image_sequence_encoder_type="transformer", image_encoder_type="resnet18",
                   num_image_sequence_encoder_layers=1, num_decoder_layers=4, distill_teacher_inference_steps=30,
                   use_gamestate=False, encoder_patch_size=10)
+    if args.clip is not None:
+        if world > 1:
+            sys.exit("--clip measures the replayed single-GPU step")
+        return clip_blocks(args, params, dev)
     torch.manual_seed(0)
     model = cli.build_model(params).to(dev).train()
     opt = training.FusedAdamW(model.parameters(), lr=1e-4, ema_decay=args.ema_decay)
@@ -65,6 +75,57 @@ def main():
                           **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_floats": opt.flat_ema.numel()})}))
     if world > 1:
         dist.destroy_process_group()
+
+
+def clip_blocks(args, params, dev):
+    import statistics
+    from soccerdiffusion_amd import cli, training
+    from soccerdiffusion_amd.scheduler import DDIMScheduler
+    B = args.batch
+    ns = DDIMScheduler(beta_schedule="squaredcos_cap_v2", clip_sample=False)
+    total = args.steps * args.blocks + args.warmup + 8
+
+    def leg(max_grad_norm):
+        torch.manual_seed(0)
+        model = cli.build_model(params).to(dev).train()
+        model.set_dropout(0.1, seed=1234)   # as bench.py --mode train
+        opt = training.FusedAdamW(model.parameters(), lr=1e-4, ema_decay=args.ema_decay, max_grad_norm=max_grad_norm)
+        sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=1e-4, total_steps=total)
+        g = torch.Generator(device=dev).manual_seed(1)
+        x0 = torch.randn(B, 100, 20, device=dev, generator=g)
+        ctx = [torch.randn(B, 10, 256, device=dev, generator=g)]
+        gs = training.GraphedTrainStep(model, opt, sched, ns, generator=g)
+        return {"opt": opt, "gs": gs, "x0": x0, "ctx": ctx, "ms": [], "coef": []}
+
+    def run(l, n):
+        for _ in range(n):
+            l["gs"](l["x0"], context=l["ctx"])
+
+    legs = {"off": leg(None), "inf": leg(float("inf")), "clip": leg(args.clip)}
+    for l in legs.values():   # the eager steps, the capture, the first replays
+        run(l, args.warmup + 3)
+    torch.cuda.synchronize()
+    for _ in range(args.blocks):
+        for l in legs.values():
+            t0 = time.perf_counter()
+            run(l, args.steps)
+            torch.cuda.synchronize()
+            l["ms"].append((time.perf_counter() - t0) / args.steps * 1e3)
+            l["coef"].append(None if l["opt"].max_grad_norm is None else l["opt"].grad_stats()["coef"])   # (outside the timed window)
+    med = {}
+    for name, l in legs.items():
+        med[name] = statistics.median(l["ms"])
+        print(json.dumps({"leg": name, "max_grad_norm": "inf" if l["opt"].max_grad_norm == float("inf") else l["opt"].max_grad_norm, "median_ms_per_step": round(med[name], 4),
+                          "min_ms": round(min(l["ms"]), 4), "max_ms": round(max(l["ms"]), 4), "blocks_ms": [round(t, 4) for t in l["ms"]],
+                          "steps_per_block": args.steps, "batch": B, "graph_replay": l["gs"].graph is not None,
+                          "coef_after_block": l["coef"], "grad_stats": None if name == "off" else l["opt"].grad_stats(), "flat_grad_floats": l["opt"].flat_grad.numel(),
+                          **({} if args.ema_decay is None else {"ema_decay": args.ema_decay})}), flush=True)
+    spread = max(max(l["ms"]) - min(l["ms"]) for l in legs.values())
+    print(json.dumps({"metric": "ms per replayed training step, clipping on minus off (medians of alternating blocks)",
+                      "inf_minus_off_ms": round(med["inf"] - med["off"], 4),
+                      "clip_minus_off_ms": round(med["clip"] - med["off"], 4), "largest_block_spread_ms": round(spread, 4)}), flush=True)
+    for l in legs.values():
+        l["gs"].close()
 
 
 if __name__ == "__main__":

@@ -399,6 +399,27 @@ int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B,
  * to the lowest index, so bitwise-equal draws tie exactly); no atomics: the result does not depend on scheduling.  1 <= G <= 64. */
 int sd_select_medoid(const float *x, int32_t *index, float *out /* or NULL */, int C, int G, int T, int J, void *stream);
 
+/* The draw that continues the previous plan (the backward-coherence criterion of Bidirectional Decoding, Liu et al. 2024): ticks that
+ * overlap by R = T - shift rows describe the same instants twice, and among the G draws of context c the one closest to what the last
+ * committed plan said about them is chosen.  Per context c, fp32 in fixed orders, the sampler's normalised space:
+ *   x (C, G, T, J), a context's draws contiguous;  prev (Cp, T, J): context c reads prev[robots ? robots[c] : c] (robots[c] in [0, Cp) is
+ *   the caller's to guarantee: the device checks nothing), a NaN element: no plan there;  w (T) row weights >= 0 in device memory, only
+ *   w[0 .. R-1] are read;  0 <= shift < T;  lam >= 0.
+ *   d = x[c,g,tau,j] - prev[.,tau+shift,j];  term = w[tau] * (d * d), SELECTED to 0.f (not multiplied by zero) where prev is NaN or
+ *   w[tau] == 0;  coh[g] = sum of term over tau < R and j, in sd_select_medoid's order: lane l of a wave adds elements l, l + 64, ... of
+ *   the R * J overlap elements in that order, then the xor butterfly 32 .. 1; one wave per draw.
+ *   med[g] = sd_select_medoid's score of draw g, same order of operations, computed only where it is needed.
+ *   Context c HAS A PLAN iff an overlap element has w[tau] > 0 and a prev that is not NaN.  With a plan cost[g] = coh[g] + lam * med[g]
+ *   (the product rounds on its own; coh[g] itself when lam == 0: G distance sums instead of G (G - 1) / 2); without one cost[g] = med[g]
+ *   and index[c] is sd_select_medoid's bit for bit.
+ *   index[c] = the lowest g among the smallest costs (compare <, from draw 0).  out (C, T, J) != NULL: out[c] = x[c, index[c]];
+ *   cost (C, G) != NULL: the costs.
+ * One workgroup per context, no atomics: the result does not depend on C, on the grid or on which rows of prev other contexts read.
+ * SD_E_BADARG before any launch: x, prev, w or index NULL; C, T, J < 1, G outside [1, 64], shift outside [0, T); lam < 0, NaN or
+ * infinite; out or cost overlapping x or prev (prev's extent is taken as C plans, one where robots is given). */
+int sd_select_coherent(const float *x, const float *prev, const int32_t *robots /* or NULL */, const float *w, int32_t *index,
+                       float *out /* or NULL */, float *cost /* or NULL */, int C, int G, int T, int J, int shift, float lam, void *stream);
+
 /* The denoiser evaluated ONE step at a time on the trajectory kernels of sampler modes 3 / 4 - the reference's own loop form,
  *   for t in scheduler.timesteps: eps = model.forward_with_context(ctx, x, t); x = scheduler.step(eps, t, x).prev_sample
  * (soccer_diffusion/ml/inference/plot.py:122-131, ml/training/distill.py:179-189, ml/inference/ros.py:301-310), whose

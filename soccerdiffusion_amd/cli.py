@@ -6,7 +6,7 @@ soccer_diffusion/ml/inference/plot.py:21-135).
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]     (ml/training/distill.py:25-224)
     python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--draws G [--select medoid|coherent [--coherence-decay R] [--contrast L]]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -702,6 +702,32 @@ def _camera_size(text: str) -> tuple:
     return h, w
 
 
+def plan_change_rms(published: torch.Tensor, shift: int, resets: Optional[torch.Tensor] = None) -> float:
+    """How far successive ticks' plans disagree about the instants both describe: the root mean square, in radians, over ticks k >= 1,
+    robots, joints and the T - shift overlapping rows of ``published[k][:, :T - shift] - published[k - 1][:, shift:]`` (``published``
+    (K, N, T, J) as ``cli rollout`` saves it; ``shift``: the rows between two ticks).  ``resets`` (K, N) bool: a robot reset after tick
+    k - 1 starts a new episode at tick k and that pair is left out.  NaN where nothing overlaps (K < 2, shift >= T, every pair reset).
+    This is the number that says whether a selector dithers between modes."""
+    K, N, T, _ = published.shape
+    if K < 2 or not 0 <= shift < T:
+        return float("nan")
+    diff = (published[1:, :, :T - shift] - published[:-1, :, shift:]).double()
+    if resets is not None:
+        diff = diff[~resets[:-1].bool()]
+    return float(diff.pow(2).mean().sqrt()) if diff.numel() else float("nan")
+
+
+def _select_arg(args, T: int) -> None:
+    """--select / --coherence-decay / --contrast against the checkpoint's horizon: PolicySession.check_select's errors as argument errors."""
+    from .session import PolicySession
+
+    try:
+        carry, advance = PolicySession.check_carry(T, args.carry, args.advance)
+        PolicySession.check_select(args.select, T, advance, args.draws, args.coherence_decay, args.contrast)
+    except ValueError as e:
+        raise SystemExit(f"rollout: {e}") from None
+
+
 def cmd_rollout(args) -> int:
     """The closed control loop (ros.py:165-335) on a synthetic sensor stream: K ticks of a PolicySession over N robots in lockstep.
     --episode-ticks: robot b's episodes last E[b % len(E)] ticks; after the last tick of one, that robot alone starts again.
@@ -711,7 +737,10 @@ def cmd_rollout(args) -> int:
     --limits J=LO:HI[,J=LO:HI...] | --clip R [--reproject]: every published joint J stays inside [LO, HI] radians (as published), or every
     joint inside [-R, R]: the limits act on the predicted clean trajectory inside every tick's rollout (PolicySession(limits=...)).
     --slew V | J=V[,J=V...]: consecutive published rows differ by at most V radians (every joint, or joint J), also across two ticks
-    (PolicySession(slew=...): V = max velocity / row rate)."""
+    (PolicySession(slew=...): V = max velocity / row rate).
+    --select medoid|coherent [--coherence-decay R] [--contrast L]: which of the --draws G draws a tick commits; "coherent" (overlapping ticks
+    only) is the draw closest to the previous tick's plan over the rows both describe (PolicySession(select="coherent")).  Whenever ticks
+    overlap the line and the file gain ``select`` and ``plan_change_rms`` (``plan_change_rms``), for either selector."""
     from .session import PolicySession
 
     if args.synthetic is None or args.synthetic < 1 or args.ticks < 1:
@@ -730,11 +759,14 @@ def cmd_rollout(args) -> int:
         if not lengths or min(lengths) < 1:
             raise SystemExit("--episode-ticks takes positive tick counts E[,E...]")
         episode = torch.tensor([lengths[b % len(lengths)] for b in range(args.synthetic)])
+    if (args.select, args.coherence_decay, args.contrast) != ("medoid", 0.5, 0.0):   # say so before anything touches the GPU
+        _select_arg(args, torch.load(args.checkpoint, map_location="cpu", weights_only=True)["hyperparams"]["trajectory_prediction_length"])
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
                                             seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver,
-                                            limits=_limits_arg(args), reproject=args.reproject, slew=_slew_arg(args))
+                                            limits=_limits_arg(args), reproject=args.reproject, slew=_slew_arg(args), select=args.select,
+                                            coherence_decay=args.coherence_decay, contrast=args.contrast)
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -772,11 +804,15 @@ def cmd_rollout(args) -> int:
     if args.slew is not None:
         saved["slew"] = args.slew   # radians per row: one number, or {joint: v}
     if args.draws > 1:
-        saved["draws"] = session.draws   # every published trajectory is the medoid of that many draws
+        saved["draws"] = session.draws   # every published trajectory is the selected one of that many draws
     if episode is not None:
         saved["resets"] = torch.stack(resets)   # (K, N): robot n was reset after tick k
+    overlap = ""
+    if session.advance < session.T:   # overlapping ticks: how far successive plans disagree about the instants both describe
+        saved.update(select=session.select, plan_change_rms=plan_change_rms(traj, session.advance, saved.get("resets")))
+        overlap = f", select {session.select}, plan_change_rms {saved['plan_change_rms']:.5f} rad"
     torch.save(saved, args.output)
-    print(f"rolled out {args.ticks} ticks of {args.synthetic} robots, trajectories of shape {tuple(traj.shape[2:])} -> {args.output}")
+    print(f"rolled out {args.ticks} ticks of {args.synthetic} robots, trajectories of shape {tuple(traj.shape[2:])}{overlap} -> {args.output}")
     return 0
 
 
@@ -984,6 +1020,12 @@ def build_parser() -> argparse.ArgumentParser:
                     "inside every tick's rollout (PolicySession(holds=True).hold)")
     ro.add_argument("--draws", type=_draws, default=1, metavar="G", help="G draws per robot and tick from the once-encoded context; their medoid is "
                     "committed and published (PolicySession(draws=G))")
+    ro.add_argument("--select", choices=("medoid", "coherent"), default="medoid", help="which of the G draws a tick commits: their medoid, or - "
+                    "overlapping ticks only - the draw that continues the previous plan (PolicySession(select='coherent'))")
+    ro.add_argument("--coherence-decay", type=float, default=0.5, metavar="R", help="--select coherent: overlap row tau weighs R ** tau, R in (0, 1] "
+                    "(0.5 is the Bidirectional Decoding paper's value, not measured on this policy)")
+    ro.add_argument("--contrast", type=float, default=0.0, metavar="L", help="--select coherent: weight >= 0, per element, of the medoid score "
+                    "beside the coherence (0: coherence alone)")
     ro.add_argument("--seed", type=int, default=0)
     return ap
 

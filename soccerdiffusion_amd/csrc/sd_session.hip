@@ -656,6 +656,135 @@ extern "C" int sd_select_medoid(const float *x, int32_t *index, float *out, int 
     return 0;
 }
 
+// ---- the draw that continues the previous plan (PolicySession(select="coherent")) -------------------------------------------------------
+// One workgroup per context, waves stride over the draws.  The overlap of the new draws with the previous plan is rows [0, R) of a draw
+// against rows [S, T) of the plan, R = T - S: both are R * J contiguous floats.  coh[g] = sum of w[tau] * (x - prev)^2 over them, a term
+// SELECTED to 0.f where prev is NaN or the row's weight is not above zero; one wave per draw, in select_medoid_kernel's order (lane l adds
+// elements l, l + 64, ..., then the xor butterfly 32 .. 1).  Every wave sees the same prev and w, so wave 0 - which always has draw 0 -
+// says whether the context has a plan at all (one contributing element).  The medoid scores are computed only where they are needed - no
+// plan, or lam != 0 - by select_medoid_kernel's statements in its order, so a context without a plan gets sd_select_medoid's index bit
+// for bit.  cost[g] = coh[g] (lam == 0) or coh[g] + lam * med[g] (the product rounds on its own: contraction is off) with a plan, med[g]
+// without one; the lowest index among the smallest costs wins.  No atomics.
+namespace ss {
+__global__ __launch_bounds__(THREADS) void select_coherent_kernel(const float *__restrict__ x, const float *__restrict__ prev,
+                                                                    const int32_t *__restrict__ robots, const float *__restrict__ w,
+                                                                    int32_t *__restrict__ index, float *__restrict__ out, float *__restrict__ cost,
+                                                                    int G, int n, int J, int shift, float lam) {
+    __shared__ float dist[MEDOID_MAX_G][MEDOID_MAX_G + 1];
+    __shared__ float score[MEDOID_MAX_G];
+    __shared__ float coh[MEDOID_MAX_G];
+    __shared__ int best, has_plan;
+    const int c = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float *xc = x + (long)c * G * n;
+    const float *pc = prev + (long)(robots ? robots[c] : c) * n + (long)shift * J;   // row S of the context's plan
+    const int m = n - shift * J;                                                       // R * J overlap elements
+    for (int g = wv; g < G; g += THREADS / 64) {
+        const float *a = xc + (long)g * n;
+        float acc = 0.f;
+        bool any = false;
+        for (int e = lane; e < m; e += 64) {
+            const float p = pc[e], wt = w[e / J];
+            const float df = a[e] - p;
+            const float term = wt * (df * df);
+            const bool counts = wt > 0.f && p == p;
+            any = any || counts;
+            acc = acc + (counts ? term : 0.f);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
+        const bool plan = __any(any);
+        if (lane == 0) {
+            coh[g] = acc;
+            if (g == 0) has_plan = plan;
+        }
+    }
+    __syncthreads();
+    const bool plan = has_plan != 0;
+    const bool medoid = !plan || lam != 0.f;   // the same in every thread of the workgroup
+    if (medoid) {
+        if ((int)threadIdx.x < G) dist[threadIdx.x][threadIdx.x] = 0.f;
+        const int pairs = G * (G - 1) / 2;
+        for (int p = wv; p < pairs; p += THREADS / 64) {
+            int i = 0, left = p;
+            while (left >= G - 1 - i) {
+                left -= G - 1 - i;
+                ++i;
+            }
+            const int k = i + 1 + left;
+            const float *a = xc + (long)i * n, *b = xc + (long)k * n;
+            float acc = 0.f;
+            for (int e = lane; e < n; e += 64) {
+                const float df = a[e] - b[e];
+                acc = acc + df * df;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
+            if (lane == 0) {
+                dist[i][k] = acc;
+                dist[k][i] = acc;
+            }
+        }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < G) {
+        float sc = coh[threadIdx.x];
+        if (medoid) {
+            float med = 0.f;
+            for (int k = 0; k < G; ++k) med = med + dist[threadIdx.x][k];
+            if (plan) {
+                const float scaled = lam * med;
+                sc = sc + scaled;
+            } else {
+                sc = med;
+            }
+        }
+        score[threadIdx.x] = sc;
+        if (cost) cost[(long)c * G + threadIdx.x] = sc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int bi = 0;
+        float bs = score[0];
+        for (int i = 1; i < G; ++i)
+            if (score[i] < bs) {
+                bs = score[i];
+                bi = i;
+            }
+        best = bi;
+        index[c] = bi;
+    }
+    __syncthreads();
+    if (out) {
+        const float *src = xc + (long)best * n;
+        float *dst = out + (long)c * n;
+        for (int e = threadIdx.x; e < n; e += THREADS) dst[e] = src[e];
+    }
+}
+
+// [a, a + na) and [b, b + nb) floats share an address
+static bool floats_overlap(const float *a, long na, const float *b, long nb) {
+    return a && b && a < b + nb && b < a + na;
+}
+}   // namespace ss
+
+extern "C" int sd_select_coherent(const float *x, const float *prev, const int32_t *robots, const float *w, int32_t *index, float *out, float *cost,
+                                  int C, int G, int T, int J, int shift, float lam, void *stream) {
+    if (!x || !prev || !w || !index)
+        return fail(SD_E_BADARG, "sd_select_coherent: x, prev, w and index must be given");
+    if (C <= 0 || G < 1 || G > ss::MEDOID_MAX_G || T <= 0 || J <= 0 || (long)T * J > (1L << 30) || shift < 0 || shift >= T)
+        return fail(SD_E_BADARG, "sd_select_coherent: C, T, J > 0, 1 <= G <= 64, 0 <= shift < T");
+    if (!(lam >= 0.f) || lam == INFINITY) return fail(SD_E_BADARG, "sd_select_coherent: lam is a finite number >= 0");
+    // the extents the call itself fixes: x holds C * G draws, prev at least C plans (one where robots names the rows), out C, cost C * G
+    const long n = (long)T * J, nx = (long)C * G * n, np = (robots ? 1 : (long)C) * n;
+    if (ss::floats_overlap(out, (long)C * n, x, nx) || ss::floats_overlap(out, (long)C * n, prev, np) ||
+        ss::floats_overlap(cost, (long)C * G, x, nx) || ss::floats_overlap(cost, (long)C * G, prev, np))
+        return fail(SD_E_BADARG, "sd_select_coherent: out and cost must not alias x or prev");
+    SD_LAUNCH(ss::select_coherent_kernel, dim3((unsigned)C), dim3(ss::THREADS), 0, (hipStream_t)stream, x, prev, robots, w, index, out, cost, G,
+              T * J, J, shift, lam);
+    SD_CHECK_LAUNCH("select_coherent_kernel");
+    return 0;
+}
+
 extern "C" int sd_session_reset(const sd_ring_reset *rings, int n_rings, const uint8_t *mask, int64_t *game_state, int64_t game_state_value, int B,
                                 void *stream) {
     if (!rings || n_rings < 1 || n_rings > SD_SESSION_MAX_RESET_RINGS || B <= 0)

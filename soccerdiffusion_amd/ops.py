@@ -8,6 +8,7 @@ CUDA(HIP) tensors and raise otherwise — there is no CPU path in this package.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import operator
 import sys
@@ -447,13 +448,19 @@ def pack_encoder(sd: Mapping[str, Tensor], device, prefix: str, heads: int = 4, 
 
 
 _ws_cache: dict = {}
+_ws_retired: list = []   # buffers outgrown while their stream was capturing: the graph under capture may hold their address
 
 
 def workspace(n_floats: int, device) -> Tensor:
-    """Grow-only scratch buffer per (device, stream)."""
+    """Grow-only scratch buffer per (device, stream).  A buffer that is outgrown DURING a stream capture stays alive: an earlier call of the
+    same capture (a context encoder, before the rollout asks for more) has put its address into the graph, and the buffer may live in the
+    private pool of an older graph that no longer exists - released here, the next capture's ``empty_cache`` would return it to the driver
+    and the graph would replay into unmapped memory."""
     key = (torch.device(device), _stream())
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < n_floats:
+        if buf is not None and torch.cuda.is_current_stream_capturing():
+            _ws_retired.append(buf)
         buf = torch.empty(int(n_floats), dtype=torch.float32, device=device)
         _ws_cache[key] = buf
     return buf
@@ -1019,6 +1026,116 @@ def select_medoid(x: Tensor, draws: int, gather: bool = True, index: Optional[Te
     check(_lib.load().sd_select_medoid(x.data_ptr(), index.data_ptr(), out.data_ptr() if gather else None, Cn, draws, T, J, _stream()),
           "sd_select_medoid")
     return index, (out if gather else None)
+
+
+def coherence_weights_host(T: int, decay: float = 0.5) -> np.ndarray:
+    """The row weights of ``select_coherent`` on the host: (T,) fp32, w[tau] = decay ** tau computed in float64 and rounded once.
+    ValueError unless 0 < decay <= 1.  (decay = 0.5 is the value of the Bidirectional Decoding paper; it has not been measured on this
+    policy.)"""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"select_coherent: T must be positive, got {T}")
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) <= 1.0:
+        raise ValueError(f"select_coherent: decay must be a number in (0, 1], got {decay!r}")
+    return np.array([float(decay) ** tau for tau in range(T)], dtype=np.float64).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=64)
+def _coherence_weights(T: int, decay: float, device: str) -> Tensor:
+    return torch.from_numpy(coherence_weights_host(T, decay)).to(device)
+
+
+def coherence_weights(T: int, decay: float = 0.5, device="cuda") -> Tensor:
+    """``coherence_weights_host`` in device memory, cached per (T, decay, device): read only."""
+    coherence_weights_host(T, decay)   # (the argument errors, every time)
+    return _coherence_weights(int(T), float(decay), str(torch.device(device)))
+
+
+def coherence_lambda(contrast: float, w, shift: int, G: int, T: int, J: int) -> float:
+    """``lam`` of ``sd_select_coherent`` for a per-element ``contrast``: the coherence of a draw sums J * sum(w[:R]) weighted squares
+    (R = T - shift), its medoid score (G - 1) * T * J squares, so lam = contrast * (J * sum(w[:R])) / ((G - 1) * T * J) weighs the two
+    means per element ``contrast`` to 1.  float64 on the host from the fp32 weights as the kernel reads them, rounded once to fp32 (the
+    value returned is that fp32 number).  G = 1: 0 (one draw has no other to be close to)."""
+    if isinstance(contrast, bool) or not isinstance(contrast, (int, float)) or not float(contrast) >= 0.0 or math.isinf(float(contrast)):
+        raise ValueError(f"select_coherent: contrast must be a finite number >= 0, got {contrast!r}")
+    if G == 1 or contrast == 0:
+        return 0.0
+    R = T - shift
+    total = np.asarray(w, dtype=np.float32)[:R].astype(np.float64).sum()
+    return float(np.float32(np.float64(contrast) * (J * total) / np.float64((G - 1) * T * J)))
+
+
+@functools.lru_cache(maxsize=256)
+def _coherence_lambda_decay(contrast: float, decay: float, shift: int, G: int, T: int, J: int) -> float:
+    return coherence_lambda(contrast, coherence_weights_host(T, decay), shift, G, T, J)
+
+
+def select_coherent(x: Tensor, draws: int, prev: Tensor, shift: int, row_weights: Optional[Tensor] = None, decay: float = 0.5,
+                    contrast: float = 0.0, robots=None, gather: bool = True, index: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                    cost=None):
+    """The draw of each context that continues the context's previous plan (``sd_select_coherent``; the backward-coherence criterion of
+    Bidirectional Decoding, Liu et al. 2024).  ``x`` (C * draws, T, J) or (C, draws, T, J) as ``select_medoid`` takes it; ``prev``
+    (Cp, T, J): the last committed plan per context in the same normalised space, NaN where there is none; ``shift`` = S in [0, T): the
+    rows that passed since, so rows [0, T - S) of a draw and rows [S, T) of the plan describe the same instants.
+    cost[c, g] = sum over those rows and the joints of w[tau] * (x - prev)^2 + lam * (the medoid score of draw g); a NaN of ``prev``
+    and a zero weight leave their elements out; a context whose plan leaves every element out falls back to the medoid
+    (``select_medoid``'s index bit for bit).  The lowest index among the smallest costs wins.
+    ``row_weights``: (T,) fp32 weights >= 0 (a device tensor is used as it is; a CPU tensor is checked and uploaded); default
+    w[tau] = ``decay`` ** tau (``coherence_weights``).  ``contrast`` >= 0, per element: ``coherence_lambda``; 0 costs G distance sums
+    and no medoid.  (With ``row_weights`` on the device and contrast > 0 the weights are read back once to compute lam.)
+    ``robots`` (see ``robot_index``; a device tensor is the int32 upload of it): context c reads ``prev[robots[c]]``; default: Cp = C
+    and context c reads ``prev[c]``.
+    Returns ``(index, chosen, cost)``: index (C,) int32; chosen (C, T, J) = x[c, index[c]] bit for bit, or None without ``gather``; cost
+    (C, G) fp32 where ``cost`` is True (a new tensor) or a buffer to write into, else None.  ``index`` / ``out``: buffers to write into.
+    One launch, no read-back."""
+    if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= 64:
+        raise ValueError(f"select_coherent: draws must be an int in [1, 64], got {draws!r}")
+    if x.dim() == 4:
+        if x.shape[1] != draws:
+            raise ValueError(f"select_coherent: x {tuple(x.shape)} does not hold {draws} draws per context")
+        Cn, _, T, J = x.shape
+    elif x.dim() == 3 and x.shape[0] % draws == 0 and x.shape[0] > 0:
+        Cn, T, J = x.shape[0] // draws, x.shape[1], x.shape[2]
+    else:
+        raise ValueError(f"select_coherent: expected (C * {draws}, T, J) or (C, {draws}, T, J), got {tuple(x.shape)}")
+    if not isinstance(prev, Tensor) or prev.dim() != 3 or tuple(prev.shape[1:]) != (T, J) or prev.shape[0] < 1:
+        raise ValueError(f"select_coherent: prev is (Cp, {T}, {J}), got {tuple(getattr(prev, 'shape', ()))}")
+    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift < T:
+        raise ValueError(f"select_coherent: shift must be an int in [0, {T}), got {shift!r}")
+    Cp = prev.shape[0]
+    if robots is None and Cp != Cn:
+        raise ValueError(f"select_coherent: prev holds {Cp} plans for {Cn} contexts and no robots= says which")
+    given = row_weights is not None
+    if given:
+        if not isinstance(row_weights, Tensor) or tuple(row_weights.shape) != (T,) or row_weights.dtype != torch.float32:
+            raise ValueError(f"select_coherent: row_weights is a ({T},) fp32 tensor, got {getattr(row_weights, 'shape', row_weights)!r}")
+        if not row_weights.is_cuda and not bool((row_weights >= 0).all() and torch.isfinite(row_weights).all()):
+            raise ValueError("select_coherent: row_weights are finite numbers >= 0")
+        lam = coherence_lambda(contrast, None, shift, 1, T, J)   # (the argument errors before anything is read back)
+        if draws > 1 and contrast != 0:
+            lam = coherence_lambda(contrast, row_weights.detach().cpu().numpy(), shift, draws, T, J)
+    else:
+        coherence_weights_host(T, decay)
+        coherence_lambda(contrast, None, shift, 1, T, J)
+        lam = _coherence_lambda_decay(float(contrast), float(decay), shift, draws, T, J)
+    r = None if robots is None else _robots_on(robots, Cp, x.device)
+    if r is not None and r.numel() != Cn:
+        raise ValueError(f"select_coherent: robots names {r.numel()} plans for {Cn} contexts")
+    _req(x, "x"); _req(prev, "prev")
+    if prev.device != x.device:
+        raise ValueError(f"select_coherent: prev is on {prev.device}, x on {x.device}")
+    w = row_weights.to(x.device).contiguous() if given else coherence_weights(T, decay, x.device)
+    if index is None:
+        index = torch.empty(Cn, dtype=torch.int32, device=x.device)
+    if gather and out is None:
+        out = torch.empty(Cn, T, J, dtype=torch.float32, device=x.device)
+    if cost is True:
+        cost = torch.empty(Cn, draws, dtype=torch.float32, device=x.device)
+    elif cost is False:
+        cost = None
+    check(_lib.load().sd_select_coherent(x.data_ptr(), prev.data_ptr(), _ptr(r), w.data_ptr(), index.data_ptr(), out.data_ptr() if gather else None,
+                                         _ptr(cost), Cn, draws, T, J, shift, lam, _stream()), "sd_select_coherent")
+    return index, (out if gather else None), cost
 
 
 PREPARE_WEIGHTS, PREPARE_CONTEXT = 1, 2   # SD_PREPARE_*

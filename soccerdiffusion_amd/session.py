@@ -32,6 +32,12 @@ chosen on the device, committed and returned instead of a single, possibly outly
     s = PolicySession(model, batch=2, draws=4, hyperparams=hp)
     traj, all_draws, index = s.step(return_draws=True)                      # (2, T, J), (2, 4, T, J), (2,): traj[b] == all_draws[b, index[b]]
 
+With overlapping ticks the draw can instead be the one that continues the previous plan (``select="coherent"``: the backward-coherence
+criterion of Bidirectional Decoding, ``ops.select_coherent``) - successive ticks of a multimodal policy then stay on one mode:
+
+    s = PolicySession(model, batch=2, draws=8, advance=5, select="coherent", hyperparams=hp)   # T = 10: five rows of overlap
+    traj = s.step(); s.selection()                                          # {"index": (2,), "cost": (2, 8)} of that tick
+
 Held joints (``holds=True``): joints that another module owns - the head follows the ball tracker, a motor is switched off - are held at
 given angles INSIDE the rollout (``ops.ddim_sample(hold=...)``), so the free joints are sampled to fit what the robot will really do:
 
@@ -43,7 +49,9 @@ There is no CPU path and no fallback: the model must be on the GPU and in eval m
 
 from __future__ import annotations
 
+import gc
 import math
+import weakref
 from typing import Optional
 
 import numpy as np
@@ -55,7 +63,7 @@ from .derived import current, version_key
 KEYS = ("joint_command_history", "rotation", "joint_state")   # the ring modalities, in encode_input_data's order
 WRAPPED = {"joint_command_history": True, "rotation": False, "joint_state": True}   # (x + 3 pi) % (2 pi): ros.py:266-273
 DEFAULT_GAME_STATE = 2   # ros.py:274
-SELECTORS = ("medoid",)   # PolicySession(select=...): which of a tick's draws is committed
+SELECTORS = ("medoid", "coherent")   # PolicySession(select=...): which of a tick's draws is committed
 
 
 class _GraphedTick:
@@ -68,7 +76,9 @@ class _GraphedTick:
 
     def __init__(self, session: "PolicySession", x_T: torch.Tensor):
         m, dev = session.model, session.device
-        self.session = session
+        # a weak reference: the session owns its tick, and with a strong one back the pair would be a cycle that only Python's collector
+        # frees - at an arbitrary allocation, possibly inside a LATER capture, where destroying a graph is not permitted and aborts
+        self.session = weakref.proxy(session)
         ts = ops.ddim_timesteps(session.n_steps)
         self.packed = m.diffusion_action_generator.packed()
         self.tokens = m.step_encoding.table(ts, dev)
@@ -85,8 +95,14 @@ class _GraphedTick:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._run()
+        collecting = gc.isenabled()
+        gc.disable()   # no collection inside the capture: a dead graph of another owner that it found would be destroyed mid-capture
+        try:
+            with torch.cuda.graph(self.graph):
+                self._run()
+        finally:
+            if collecting:
+                gc.enable()
 
     def _run(self) -> None:
         s = self.session
@@ -97,30 +113,32 @@ class _GraphedTick:
             self.x = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
                                      multistep=self.msw, **self.lim)
             return
-        # G draws per robot on the shared context, and their medoid: the selection is part of the captured tick
+        # G draws per robot on the shared context, and the selected one: the selection is part of the captured tick (select="coherent"
+        # reads the session's plan, which the commit outside the graph rewrites in place)
         self.all = ops.ddim_sample(self.packed, ctx, self.tokens, self.coef, self.noise, status=self.status, max_mode=self.cap, **cond,
                                    draws=s.draws, multistep=self.msw, **self.lim)
-        self.index, self.x = ops.select_medoid(self.all, s.draws)
+        self.index, self.x, self.cost = s._select(self.all)
 
     def __call__(self, x_T: torch.Tensor):
-        """The sample (B, T, J); with draws > 1: (the selected sample, all draws (B * G, T, J), index (B,))."""
+        """The sample (B, T, J); with draws > 1: (the selected sample, all draws (B * G, T, J), index (B,), cost (B, G) or None)."""
         self.noise.copy_(x_T)
         self.graph.replay()
         s = self.session
         if int(self.status.item()) == 0:
-            return self.x if s.draws == 1 else (self.x, self.all, self.index)
+            return self.x if s.draws == 1 else (self.x, self.all, self.index, self.cost)
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
         x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver, **s._lim()).contiguous()
         if s.draws == 1:
             return x
-        index, chosen = ops.select_medoid(x, s.draws)
-        return chosen, x, index
+        index, chosen, cost = s._select(x)
+        return chosen, x, index, cost
 
 
 class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
-                 select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False, slew=None):
+                 select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False, slew=None,
+                 coherence_decay: float = 0.5, contrast: float = 0.0):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -134,6 +152,16 @@ class PolicySession:
         one ``select`` names - "medoid": the draw closest to all others (``ops.select_medoid``, on the device).  With ``carry`` all G
         draws share the seam and the carried rows come from the selected draw.  draws = 1 is the session without any of this, launch
         for launch (no selection launch).  Not for a distilled decoder (one forward at t = 0 has no sampling to repeat).
+        ``select="coherent"`` / ``coherence_decay`` / ``contrast`` (overlapping ticks only: ``advance`` < T): the draw that continues the
+        robot's previous plan (``ops.select_coherent``; the backward-coherence criterion of Bidirectional Decoding, Liu et al. 2024).  Rows
+        [advance, T) of the last committed trajectory and rows [0, T - advance) of the new draws describe the same instants; the draw with
+        the smallest weighted squared distance over them is committed, row tau weighted ``coherence_decay`` ** tau (0.5 is the paper's
+        value and has NOT been measured on this policy), plus ``contrast`` (per element, >= 0) times the medoid score.  The session keeps
+        the last committed trajectory per robot in normalised space on the device, NaN until the robot's first tick and after its
+        ``reset``: such a robot's tick commits the medoid.  The plan is written beside the commit, outside a captured tick.  The rows
+        pinned by ``carry`` equal the plan's and contribute exactly 0.  ``selection()`` returns the last tick's indices and costs.  It
+        composes with ``carry``, ``holds``, ``limits``, ``slew``, ``solver``, ``robots=`` and ``use_graph``; ``select="medoid"`` is the
+        session without any of this, launch for launch.
         ``holds=True``: the session can hold chosen joints of chosen robots at given angles inside the rollout (``hold`` / ``release``:
         joints another module owns, a motor that is switched off) - the free joints are sampled to fit them.  It allocates the known-value
         buffer, a word of held joints per robot and the tick's mask; every tick then composes the mask in one launch and runs the
@@ -166,6 +194,8 @@ class PolicySession:
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
         self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
+        self.coherence_decay, self.contrast = self.check_select(self.select, model.trajectory_prediction_length, self.advance, self.draws,
+                                                                coherence_decay, contrast)                                # (likewise)
         self.holds = self.check_hold(holds, model.num_joints, self.distilled)                                              # (likewise)
         self.solver = self.check_solver(solver, model.num_joints, self.carry, self.distilled)                              # (likewise)
         limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled)                                   # (likewise)
@@ -207,6 +237,10 @@ class PolicySession:
             ops.session_limits(self._limits, *limits, model.mean, model.std, self.J)
         self._slew_v = self._anchor = None   # the normalised slew limits (32,) and the scan's anchors (B * draws, 32): device arrays
         self._limits_rad = limits
+        # select="coherent": the last committed trajectory per robot (normalised space; NaN: none), and the last tick's (index, cost)
+        self._plan = (torch.full((self.B, self.T, self.J), float("nan"), dtype=torch.float32, device=self.device)
+                      if self.select == "coherent" and self.draws > 1 else None)
+        self._selected = None
         if slew is not None:
             if self._limits is None:   # the slew call reads a box: an infinite one
                 self._limits = ops.joint_limits({}, J=self.J, device=self.device)
@@ -244,6 +278,24 @@ class PolicySession:
         if draws > 1 and distilled:
             raise ValueError("draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
         return draws, select
+
+    @staticmethod
+    def check_select(select: str = "medoid", T: int = 1, advance: Optional[int] = None, draws: int = 1, decay: float = 0.5,
+                     contrast: float = 0.0) -> tuple:
+        """(decay, contrast) of a session with horizon T that commits ``advance`` rows per tick, validated (no device needed): ValueError
+        for an unknown selector, a ``decay`` outside (0, 1], a ``contrast`` < 0 (or NaN), or ``select="coherent"`` with advance == T -
+        ticks that do not overlap have nothing to compare."""
+        if select not in SELECTORS:
+            raise ValueError(f"select: one of {SELECTORS}, got {select!r}")
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) <= 1.0:
+            raise ValueError(f"coherence_decay: a number in (0, 1], got {decay!r}")
+        if isinstance(contrast, bool) or not isinstance(contrast, (int, float)) or not float(contrast) >= 0.0 or math.isinf(float(contrast)):
+            raise ValueError(f"contrast: a finite number >= 0, got {contrast!r}")
+        advance = int(T) if advance is None else int(advance)
+        if select == "coherent" and advance >= int(T):
+            raise ValueError(f"select: 'coherent' compares a tick's draws with the rows of the previous plan they overlap - advance = {advance} "
+                             f"of T = {T} rows leaves no overlap (give advance < T, with or without carry)")
+        return float(decay), float(contrast)
 
     @staticmethod
     def check_hold(holds: bool = False, J: int = 1, distilled: bool = False) -> bool:
@@ -466,6 +518,8 @@ class PolicySession:
         ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE, pin_rows=self._pin_rows if self._carrying else None)
         if self._anchor is not None:   # no last command: the robots' next first row is free
             self._anchor.view(self.B, -1).masked_fill_(mask.view(self.B, 1), float("nan"))
+        if self._plan is not None:     # no plan: the robots' next tick commits the medoid of its draws
+            self._plan.masked_fill_(mask.view(self.B, 1, 1), float("nan"))
 
     def reset(self, robots=None) -> None:
         """Rings back to ``context_length`` rows of zeros (ros.py:87-106), the image ring to the token of an all-zero frame
@@ -493,6 +547,9 @@ class PolicySession:
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
         if self._anchor is not None:   # (in place: the array is the session's for its lifetime)
             self._anchor.fill_(float("nan"))
+        if self._plan is not None:
+            self._plan.fill_(float("nan"))
+        self._selected = None
         if self._carrying:   # the rows carried into the next tick (normalised space) and how many per robot: 0 until a tick has committed
             self._pin_rows = torch.zeros(B, dtype=torch.int32, device=dev)
         if self.holds and getattr(self, "_held", None) is not None:
@@ -694,20 +751,45 @@ class PolicySession:
                     x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver, **self._lim(dev_idx))
                 else:   # the context was encoded once per robot; its G draws share the folded planes
                     every = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, draws=G, solver=self.solver, **self._lim(dev_idx)).contiguous()
-                    index, chosen = ops.select_medoid(every, G)
-                    x = (chosen, every, index)
+                    index, chosen, cost = self._select(every, dev_idx)
+                    x = (chosen, every, index, cost)
             if G == 1:
                 out = self._commit(x.contiguous(), dev_idx)
                 if not return_draws:
                     return out
                 return out, out.unsqueeze(1), torch.zeros(S, dtype=torch.int32, device=self.device)
-            chosen, every, index = x
+            chosen, every, index, cost = x
             out = self._commit(chosen, dev_idx)
+            if self._plan is not None:
+                # beside the commit and outside a captured tick, like the anchor: a replay whose range guard trips is repeated eagerly and
+                # must still see the OLD plan.  Only the ticked robots' plans move.
+                if dev_idx is None:
+                    self._plan.copy_(chosen)
+                else:
+                    self._plan.index_copy_(0, dev_idx.long(), chosen)
+                self._selected = (index, cost)
             if not return_draws:
                 return out
             # the commit's expression, one rounding per operation (sd_session.hip: contraction off): (x * std + mean) - pi
             every = (every.view(S, G, self.T, self.J) * m.std + m.mean) - math.pi
             return out, every, index.clone()
+
+    def _select(self, every: torch.Tensor, dev_idx=None) -> tuple:
+        """(index (S,), chosen (S, T, J), cost (S, G) or None) of a tick's draws ``every`` (S * G, T, J): the session's selection launch."""
+        if self._plan is None:
+            return (*ops.select_medoid(every, self.draws), None)
+        return ops.select_coherent(every, self.draws, self._plan, self.advance, decay=self.coherence_decay, contrast=self.contrast,
+                                   robots=dev_idx, cost=True)
+
+    def selection(self) -> dict:
+        """The last tick's selection in a ``select="coherent"`` session: clones of ``{"index": (S,) int32, "cost": (S, G) fp32}`` - the
+        costs ``ops.select_coherent`` compared (for a robot without a plan: its draws' medoid scores)."""
+        if self._plan is None:
+            raise RuntimeError("PolicySession.selection: the session was built without select='coherent' (and draws > 1)")
+        if self._selected is None:
+            raise RuntimeError("PolicySession.selection: no tick has run since the session was built or reset")
+        index, cost = self._selected
+        return {"index": index.clone(), "cost": cost.clone()}
 
     def _commit(self, x: torch.Tensor, dev_idx) -> torch.Tensor:
         m = self.model

@@ -206,6 +206,32 @@ int sd_ddim_slew_step(const float *eps, const float *x, float *x_prev, float *hi
                       const float *hi, int reproject, const float *v, const float *start_or_null, const float *hold_x0, const int32_t *hold_mask,
                       int B, int T, int J, void *stream);
 
+/* A distilled one-step decoder (one forward at the step token of t = 0, whose output is the clean trajectory: the reference's robot node,
+ * soccer_diffusion/ml/inference/ros.py:293-298) under held elements, per-joint limits and slew limits, as sd_ddim_sample_slew defines
+ * them for the predicted x0 of a rollout - whose last step "returns the clamped x0 itself"; a one-step model is that last step alone:
+ *   raw = denoiser(ctx, step_token, x);  x0[t][j] = held(t, j) ? hold_x0[t][j] : raw[t][j];
+ *   y = start[j] (NaN: none);  for t = 0 .. T-1:  z = x0 < fl(y - v[j]) ? fl(y - v[j]) : (x0 > fl(y + v[j]) ? fl(y + v[j]) : x0);
+ *   z = z < lo[j] ? lo[j] : (z > hi[j] ? hi[j] : z);  out[t][j] = y = held(t, j) ? hold_x0[t][j] : z
+ * (compares and selects: a NaN prediction stays NaN and limits nothing after it; -0 stays -0).  x (B, T, J) is only read; out (B, T, J)
+ * receives the projection, raw_or_null (B, T, J) the unprojected prediction.  step_token: ONE row of d floats.  ctx: (B / draws, Mc, d),
+ * prepared once per context as sd_ddim_sample_draws does.  lo, hi: 32 floats each (-inf / +inf: none), v_or_null: 32 floats (NULL: no slew
+ * limit - no scan at all), start_or_null: (B, 32) floats; hold_x0 (B, T, J) and hold_mask (B, T): both or neither.  All in device memory.
+ * The route is the one host-side plan's: on a trajectory route ONE launch of a direct twin of the step kernels, on any other the eps
+ * launches and the projection kernel behind them.  max_mode as sd_ddim_sample_ex (4 is read as 3); status as sd_ddim_sample_slew
+ * (SD_STATUS_NONFINITE from out).  workspace: sd_workspace_floats(B, T, max(Mc, 1), d, L, 1).  With no mask, infinite limits and no v,
+ * out is raw bit for bit.  SD_E_BADARG (nothing launched): a NULL operand, J > 32, draws not dividing B, one of hold_x0 / hold_mask
+ * without the other, out or raw aliasing each other, x or hold_x0. */
+int sd_direct_sample(const sd_denoiser_weights *w, const float *ctx, const float *step_token, const float *x, float *out,
+                     float *raw_or_null, float *workspace, int B, int T, int Mc, int32_t *status, int max_mode,
+                     const float *hold_x0, const int32_t *hold_mask, int draws, const float *lo, const float *hi,
+                     const float *v_or_null, const float *start_or_null, void *stream);
+
+/* The projection of sd_direct_sample alone: out = project(raw; hold, limits, slew, start), one thread per (trajectory, joint).  raw, out:
+ * (B, T, J), not aliased.  An infinite prediction comes out as its limit, -0 as -0.  SD_E_BADARG: a NULL operand, J outside 1 .. 32,
+ * one of hold_x0 / hold_mask without the other, out aliasing raw or hold_x0. */
+int sd_direct_project(const float *raw, float *out, const float *hold_x0, const int32_t *hold_mask, const float *lo, const float *hi,
+                      const float *v_or_null, const float *start_or_null, int B, int T, int J, void *stream);
+
 /* Normalizer.normalize (inverse = 0: (x - mean) / std) and .denormalize (inverse = 1:
  * x * std + mean), per joint — soccer_diffusion/dataset/pytorch.py:410-414.  n = rows * J. */
 int sd_normalize(const float *x, const float *mean, const float *stdv, float *out, long n, int J, int inverse,

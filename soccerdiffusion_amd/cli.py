@@ -22,6 +22,9 @@ optimizer step (`inf`: the guard alone); the printed line gains `GradNorm` / `Sk
 `train` / `distill --val-fraction F` hold the last (or a random) fraction of the windows out of training and of the normaliser fit,
 evaluate them every `--val-every` epochs (evaluation.evaluate) and record the reports in the checkpoint's `validation` entry, and
 `evaluate` prints that report for any checkpoint as one JSON line.
+A distilled checkpoint (`distill`'s student: one forward at t = 0 whose output is the clean trajectory) takes `--limits`, `--clip`, `--slew`,
+`--hold`, `--draws`, `--select`, `--coherence-decay` and `--contrast` on `sample`, `rollout` and `evaluate` (model.sample_direct projects
+its output inside the launch); `--solver multistep`, `--carry` and `--reproject` exit with a message.
 """
 
 from __future__ import annotations
@@ -556,8 +559,7 @@ def cmd_evaluate(args) -> int:
     split = args.val_split or recorded.get("split", "tail")
     if not args.all and fraction is None:
         raise SystemExit("evaluate: give --val-fraction F, or --all for every window (the checkpoint records no split)")
-    if args.solver != "ddim" and params.get("distilled_decoder", False):
-        raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
+    _distilled_arg(args, params)
     limits = _limits_arg(args, params)   # in the space of the target trajectories (x * std + mean), as sample --hold
     slew = _slew_arg(args, params)       # radians per row in the same space
     model = build_model(params).to(device)
@@ -596,15 +598,10 @@ def cmd_sample(args) -> int:
     if B == 0:
         return 0
     G = args.draws
-    if G > 1 and params.get("distilled_decoder", False):
-        raise SystemExit("--draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
     x_T = torch.randn(B * G, params["trajectory_prediction_length"], params["num_joints"], device=device, generator=gen)
-    if args.solver != "ddim" and params.get("distilled_decoder", False):
-        raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
+    _distilled_arg(args, params)
     hold = None
     if args.hold:   # the joints held at every row of every trajectory, in the space of the file's trajectories (x * std + mean)
-        if params.get("distilled_decoder", False):
-            raise SystemExit("--hold: a distilled decoder is one forward at t = 0 - there is no rollout in which a joint could be held")
         joints, values = _hold_joints(args.hold, params["num_joints"])
         known, mask = torch.zeros_like(x_T), torch.zeros(params["num_joints"], dtype=torch.bool, device=device)
         mean, std = model.mean.reshape(-1), model.std.reshape(-1)
@@ -628,8 +625,11 @@ def cmd_sample(args) -> int:
             context = model.encode_input_data(inp)
         else:
             context = [torch.randn(B, 10, params["hidden_dim"], device=device, generator=gen)]
-        if params.get("distilled_decoder", False):  # single forward at t = 0 (plot.py:118-121)
+        distilled = params.get("distilled_decoder", False)
+        if distilled and G == 1 and hold is None and limits is None and slew is None:  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
+        elif distilled:   # the same forward on G start noises per context; its output is x0: hold, slew and limits project it in the launch
+            traj = model.sample_direct(context, x_T, hold=hold, limits=limits, slew=slew, draws=G)
         else:
             traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject, slew=slew)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
@@ -717,6 +717,21 @@ def plan_change_rms(published: torch.Tensor, shift: int, resets: Optional[torch.
     return float(diff.pow(2).mean().sqrt()) if diff.numel() else float("nan")
 
 
+def _distilled_arg(args, params: dict) -> None:
+    """What a distilled checkpoint still refuses, as argument errors: --solver multistep (one step has no history), --carry (it cannot
+    adapt its free rows to pinned ones) and --reproject (it predicts x0: there is no eps to recompute).  --limits, --clip, --slew,
+    --hold, --draws and --select are accepted: its output is the x0 they are defined on (model.sample_direct)."""
+    if not params.get("distilled_decoder", False):
+        return
+    if getattr(args, "solver", "ddim") != "ddim":
+        raise SystemExit("--solver: a distilled decoder is one forward at t = 0 - there is no rollout for a multistep solver")
+    if getattr(args, "carry", 0):
+        raise SystemExit("--carry: a distilled decoder is one forward at t = 0 - its free rows cannot adapt to pinned ones "
+                         "(--select coherent and --slew give it continuity)")
+    if getattr(args, "reproject", False):
+        raise SystemExit("--reproject: a distilled decoder predicts x0 itself - there is no eps to recompute from the clamped x0")
+
+
 def _select_arg(args, T: int) -> None:
     """--select / --coherence-decay / --contrast against the checkpoint's horizon: PolicySession.check_select's errors as argument errors."""
     from .session import PolicySession
@@ -761,12 +776,14 @@ def cmd_rollout(args) -> int:
         episode = torch.tensor([lengths[b % len(lengths)] for b in range(args.synthetic)])
     if (args.select, args.coherence_decay, args.contrast) != ("medoid", 0.5, 0.0):   # say so before anything touches the GPU
         _select_arg(args, torch.load(args.checkpoint, map_location="cpu", weights_only=True)["hyperparams"]["trajectory_prediction_length"])
+    if args.carry or args.solver != "ddim" or args.reproject:   # (likewise)
+        _distilled_arg(args, torch.load(args.checkpoint, map_location="cpu", weights_only=True)["hyperparams"])
     device = torch.device("cuda", _dist_env()[2])
     torch.cuda.set_device(device)
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
                                             seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver,
                                             limits=_limits_arg(args), reproject=args.reproject, slew=_slew_arg(args), select=args.select,
-                                            coherence_decay=args.coherence_decay, contrast=args.contrast)
+                                            coherence_decay=args.coherence_decay, contrast=args.contrast, direct=None)
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -872,8 +889,8 @@ def _limits_arg(args, params: Optional[dict] = None):
         return None
     if params is not None:
         J = params["num_joints"]
-        if params.get("distilled_decoder", False):
-            raise SystemExit("--limits: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if args.reproject and params.get("distilled_decoder", False):
+            raise SystemExit("--reproject: a distilled decoder predicts x0 itself - there is no eps to recompute from the clamped x0")
         if J > 32 or (isinstance(limits, dict) and max(limits) >= J):
             raise SystemExit(f"--limits: joint indices lie in [0, {J}) and the model has at most 32 joints")
     return limits
@@ -897,8 +914,6 @@ def _slew_arg(args, params: Optional[dict] = None):
         return None
     if params is not None:
         J = params["num_joints"]
-        if params.get("distilled_decoder", False):
-            raise SystemExit("--slew: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
         if J > 32 or (isinstance(args.slew, dict) and max(args.slew) >= J):
             raise SystemExit(f"--slew: joint indices lie in [0, {J}) and the model has at most 32 joints")
     return args.slew

@@ -373,6 +373,14 @@ __device__ __forceinline__ float slew_update(float x, float e, float x0, float x
     return __builtin_fmaf(c2, x0c, c3 * e);
 }
 
+// The direct twins of the step kernels (sd_direct_sample): the network's output IS x0 - a distilled one-step decoder (the reference's
+// robot node runs it: soccer_diffusion/ml/inference/ros.py:293-298).  No DDIM coefficient is read and no update is formed: x is only read
+// (by the embedding), the projected x0 - hold, then the slew scan, then the box, as the slew twins define them - goes to `out`, the
+// unprojected prediction to StepArgs' eps_out where that is given.  sl.v NULL: no scan, no exchange and no barrier; the storing lane clamps.
+struct DirectArgs {
+    float *out;   // [B][T][J]
+};
+
 // One step of a rollout (or one evaluation of the denoiser) on the trajectory step kernels, as the driver asks either family for it
 // (traj_step / traj_steps_fused: sd_traj_host.h; trajg_step: sd_trajg.h - each beside its own workspace).
 struct StepReq {
@@ -388,6 +396,7 @@ struct StepReq {
     const MultistepArgs *ms = nullptr;   // or NULL; needs coef, excludes pin: the multistep twins (hold then optional, its mask too)
     const LimitArgs *lim = nullptr;      // or NULL; needs ms (whose hist may then be NULL): the limits twins
     const SlewArgs *slew = nullptr;      // or NULL; needs lim (whose bounds may all be infinite): the slew twins
+    const DirectArgs *direct = nullptr;  // or NULL; excludes coef, pin and ms, needs lim; hold (mask and x0) and slew (v NULL allowed) optional: the direct twins
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

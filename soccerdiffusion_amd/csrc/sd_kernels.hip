@@ -2594,6 +2594,44 @@ __global__ __launch_bounds__(64) void ddim_slew_step_kernel(const float *__restr
         }
     }
 }
+// The projection of a one-step decoder's output alone (sd_direct_project; DirectArgs, sd_common.h): out = the prediction `raw` IS x0 -
+// under the hold, the slew scan and the box, in the kernel above's thread layout - one thread per (trajectory, joint), SLEW_BLOCK rows of
+// raw, the mask words and the held values fetched ahead of the chain, slew_row the row function.  No coefficient and no arithmetic besides
+// slew_row's own add and subtract: -0 stays -0 and an infinite prediction comes out as its limit (a DDIM step with x = 0 and coefficients
+// (1, -1, 1, 0) would give +0 and NaN).  sl.v NULL: +inf, which limits nothing.  The routes without trajectory kernels launch it behind the
+// eps launch of sd_direct_sample (the trajectory routes run it inside the step kernels' direct twins); sd_direct_project is the operation
+// on its own.  raw and out must not alias.
+__global__ __launch_bounds__(64) void direct_project_kernel(const float *__restrict__ raw, float *__restrict__ out, LimitArgs lim, SlewArgs sl, HoldArgs hold,
+                                                            int B, int T, int J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J, j = i - b * J;
+    const float v = sl.v ? sl.v[j] : __builtin_inff(), lo = lim.lo[j], hi = lim.hi[j];
+    float y = sl.start ? sl.start[b * 32 + j] : __builtin_nanf("");
+    for (int t0 = 0; t0 < T; t0 += SLEW_BLOCK) {
+        float e[SLEW_BLOCK], kn[SLEW_BLOCK], x0c[SLEW_BLOCK];
+        unsigned m[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the block's loads: none depends on y
+            const int t = t0 + k < T ? t0 + k : T - 1;   // (a ragged last block reads its last row again)
+            e[k] = raw[((long)b * T + t) * J + j];
+            m[k] = hold.mask ? (((unsigned)hold.mask[(long)b * T + t] >> j) & 1u) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            const int t = t0 + k < T ? t0 + k : T - 1;
+            kn[k] = m[k] ? hold.x0[((long)b * T + t) * J + j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the chain, in row order
+            if (t0 + k < T) y = x0c[k] = slew_row(e[k], y, v, lo, hi, m[k] != 0u, kn[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            if (t0 + k < T) out[((long)b * T + t0 + k) * J + j] = x0c[k];
+        }
+    }
+}
 
 
 // ======================================================================================
@@ -3122,6 +3160,13 @@ static int ddim_slew_step(const float *eps, const float *x, float *x_next, float
     SD_CHECK_LAUNCH("ddim_slew_step_kernel");
     return 0;
 }
+// out <- raw under the hold, the slew scan and the box (direct_project_kernel)
+static int direct_project(const float *raw, float *out, const LimitArgs &lim, const SlewArgs &sl, const HoldArgs *hold, int B, int T, int J, hipStream_t st) {
+    const HoldArgs h = hold ? *hold : HoldArgs{nullptr, nullptr, nullptr};
+    SD_LAUNCH(direct_project_kernel, dim3((B * J + 63) / 64), dim3(64), 0, st, raw, out, lim, sl, h, B, T, J);
+    SD_CHECK_LAUNCH("direct_project_kernel");
+    return 0;
+}
 // The second-order multistep solver of a rollout (sd_ddim_sample_multistep): w[i] of step i (host) and the history array (device).
 // lim (sd_ddim_sample_limits): per-joint limits on x0; w and hist may then both be NULL - first-order DDIM under limits.
 // slew (sd_ddim_sample_slew; needs lim): per-joint slew limits beside them - the step kernels' slew twins, or ddim_slew_step_kernel behind a
@@ -3131,6 +3176,7 @@ struct MultistepCall {
     float *hist;
     const LimitArgs *lim = nullptr;
     const SlewArgs *slew = nullptr;
+    bool direct = false;   // sd_direct_sample on the row-panel routes: the step returns eps and leaves x alone, and the caller projects it
     float weight(int i) const { return w ? w[i] : 0.f; }
 };
 
@@ -3250,7 +3296,9 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
             rc = decoder_stack(w, x, s, plan, B, T, Mk, [=](int l) { return kvbase + l * kvstride; }, TailArgs{eps_i, x_up, coef + 4 * i}, st);
             if (rc) return rc;
         }
-        if (msc && msc->slew) {
+        if (msc && msc->direct) {
+            // (nothing: x is only read, direct_project behind this call turns eps_i into the result)
+        } else if (msc && msc->slew) {
             if ((rc = ddim_slew_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, *msc->slew, hold, B, T, w->J, st))) return rc;
         } else if (msc && (rc = msc->lim ? ddim_limit_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, n, w->J, st)
                                   : ddim_multistep(eps_i, x, x, msc->hist, coef + 4 * i, msc->w[i], n, st)))
@@ -3423,6 +3471,75 @@ extern "C" int sd_ddim_sample_slew(const sd_denoiser_weights *w, const float *ct
     const MultistepCall msc{msw, history, &lim, &sl};
     return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
                            false, draws, n_hold ? &hold : nullptr, &msc);
+}
+
+// A distilled one-step decoder (the reference's robot node: soccer_diffusion/ml/inference/ros.py:293-298) under held elements, per-joint
+// limits and slew limits: the network's output at the one step token IS x0, so out = project(raw), raw = the denoiser on (ctx, x).  x is
+// only read.  The trajectory routes run ONE launch of a direct twin of the step kernels (DirectArgs, sd_common.h); every other route - and
+// the repeat after a tripped range guard is one - runs the eps launches of a one-step call, then direct_project_kernel.  The context is
+// prepared once per context (draws), the status word is sd_ddim_sample_slew's: zeroed first, SD_STATUS_NONFINITE from `out`.
+extern "C" int sd_direct_sample(const sd_denoiser_weights *w, const float *ctx, const float *step_token, const float *x, float *out, float *raw,
+                                float *workspace, int B, int T, int Mc, int32_t *status, int max_mode, const float *hold_x0, const int32_t *hold_mask,
+                                int draws, const float *lo, const float *hi, const float *v, const float *start, void *stream) {
+    if (!lo || !hi) return fail(SD_E_BADARG, "sd_direct_sample: lo and hi (32 floats each, device) must be given");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_direct_sample: hold_x0 and hold_mask must be given together");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_direct_sample: draws must be >= 1 and divide B");
+    if (w && w->J > 32) return fail(SD_E_BADARG, "sd_direct_sample: lo, hi and v describe at most 32 joints");
+    if (w && (long)B * w->J > 0x7fffffffL) return fail(SD_E_BADARG, "sd_direct_sample: B * J must fit 31 bits");
+    if (out && (out == x || out == raw || (raw && raw == x) || out == hold_x0 || (raw && raw == hold_x0)))
+        return fail(SD_E_BADARG, "sd_direct_sample: out and raw must alias neither each other, x nor hold_x0");
+    if (max_mode == 4) max_mode = 3;   // mode 4's two-product instantiations have no direct twin
+    if (Mc <= 0) draws = 1;            // no context rows: nothing to share
+    int rc = check_denoiser(w);
+    if (rc) return rc;
+    if (!step_token || !x || !out || !workspace || T <= 0 || Mc < 0 || (Mc > 0 && !ctx)) return fail(SD_E_BADARG, "sd_direct_sample: null pointer or empty shape");
+    if (max_mode < -1 || max_mode > 4) return fail(SD_E_BADARG, "sd_direct_sample: max_mode must be -1, 0, 1, 2, 3 or 4");
+    if (max_mode < 0) max_mode = 3;
+    if (T > w->T_max) return fail(SD_E_TOOBIG, "sd_direct_sample: horizon exceeds positional table");
+    hipStream_t st = (hipStream_t)stream;
+    const long n = (long)B * T * w->J;
+    const Scratch s = carve(workspace, (long)B * T, (long)B * (Mc + 1), w->d, w->L, 1, B);
+    const SamplerPlan plan = sampler_plan(w->d, w->heads, T, Mc, w->J, w->L, B, max_mode, CALL_PIN, draws);
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    const LimitArgs lim{lo, hi, 0};
+    const SlewArgs sl{v, start};
+    if (plan.traj()) {
+        const TrajCall c{plan, w, s, B, T, Mc, 1, st, draws};
+        if (status && (rc = zero_async(status, sizeof(int32_t), st))) return rc;
+        if ((rc = c.prepare_weights())) return rc;
+        if ((rc = c.prepare_ctx(ctx))) return rc;
+        if ((rc = c.prepare_steps(step_token, false))) return rc;
+        const DirectArgs dr{out};
+        StepReq r = c.req(const_cast<float *>(x), raw, 0, nullptr, false, status, nullptr, hold_mask ? &hold : nullptr, nullptr, &lim, &sl);
+        r.direct = &dr;
+        if ((rc = c.generic() ? trajg_step(w, s.gws, r, st, nullptr) : traj_step(w, c.ws(), r, st, plan.key_tiles, plan.precise))) return rc;
+        return status ? finite_check(out, n, status, st) : 0;
+    }
+    if (draws > 1) {   // no sharing on the row-panel routes: the context rows expanded in the workspace, as ddim_sample_any does
+        const long per = (long)Mc * w->d, nx = (long)B * per;
+        SD_LAUNCH(ctx_expand_kernel, dim3(grid_for(nx)), dim3(256), 0, st, ctx, s.kv, nx, per, draws);
+        SD_CHECK_LAUNCH("ctx_expand_kernel");
+        ctx = s.kv;
+    }
+    // one step that returns eps and leaves x alone (its coefficients are never applied), then the projection as a second launch; without a
+    // raw buffer the prediction lies in the q | k | v region, as a multistep call's does
+    static const float no_update[4] = {1.f, 0.f, 1.f, 0.f};
+    MultistepCall msc{nullptr, nullptr};
+    msc.direct = true;
+    if ((rc = panel_rollout(w, s, plan, ctx, step_token, no_update, const_cast<float *>(x), nullptr, raw, B, T, Mc, 1, status, st, nullptr, nullptr, &msc))) return rc;
+    if ((rc = direct_project(raw ? raw : s.qkv, out, lim, sl, hold_mask ? &hold : nullptr, B, T, w->J, st))) return rc;
+    return status ? finite_check(out, n, status, st) : 0;
+}
+
+// The projection of sd_direct_sample on its own: out = raw (B, T, J) under the hold, the slew scan and the box (direct_project_kernel).
+extern "C" int sd_direct_project(const float *raw, float *out, const float *hold_x0, const int32_t *hold_mask, const float *lo, const float *hi,
+                                 const float *v, const float *start, int B, int T, int J, void *stream) {
+    if (!raw || !out || raw == out || !lo || !hi || B <= 0 || T <= 0 || J < 1 || J > 32 || (long)B * J > 0x7fffffffL)
+        return fail(SD_E_BADARG, "sd_direct_project: bad argument");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_direct_project: hold_x0 and hold_mask must be given together");
+    if (out == hold_x0) return fail(SD_E_BADARG, "sd_direct_project: out must not alias hold_x0");
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    return direct_project(raw, out, LimitArgs{lo, hi, 0}, SlewArgs{v, start}, hold_mask ? &hold : nullptr, B, T, J, (hipStream_t)stream);
 }
 
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)

@@ -1469,16 +1469,23 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // j < J of wave 0 runs slew_row over t = 0 .. T-1 on column j of S, in place (32 consecutive floats per row: no bank conflict; the loads
 // do not depend on the chain); (4) a second barrier, then each storing lane reads its x0c back and finishes as the limits twin does.
 // BOTH barriers stand at the top level of the epilogue, outside `if (c.w < NTT)`: all eight waves reach them.
+// PIN == 6, DIRECT: the direct twin (DirectArgs, sd_common.h; sd_direct_sample) - the slew twin for a network whose output is x0 itself (a
+// distilled one-step decoder): x0 = e, no coefficient is read, no update is formed, x is only read (by the embedding); the unprojected
+// prediction goes to eps_out (every row, held or not) and the projected x0c to dr.out.  The epilogue is the slew twin's four phases on the
+// same S and M planes with the same two top-level barriers; sl.v NULL - a branch on the kernel argument, uniform over the workgroup -
+// skips the exchange, the scan and both barriers, and the storing lane clamps with limit_update's two compares.  hold.mask NULL: nothing
+// held, hold.x0 never read; hold.noise, lim.reproject and the multistep arguments are never read.
 template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
                                                  int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{},
                                                  const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{},
-                                                 const SlewArgs &sl = SlewArgs{}) {
+                                                 const SlewArgs &sl = SlewArgs{}, const DirectArgs &dr = DirectArgs{}) {
     constexpr bool HOLD = PIN == 2;
     constexpr bool MS = PIN == 3;
     constexpr bool LIM = PIN == 4;
     constexpr bool SLEW = PIN == 5;
-    static_assert(!SLEW || TMAX * 128 + TMAX * 4 <= LDS_STAT - LDS_Q, "the slew twin's S and M planes fit the Q | K region");
+    constexpr bool DIRECT = PIN == 6;
+    static_assert(!(SLEW || DIRECT) || TMAX * 128 + TMAX * 4 <= LDS_STAT - LDS_Q, "the slew twin's S and M planes fit the Q | K region");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx c;
     if constexpr (ROLL) c = ctx_fresh(smem, roll_wave, a.T);
@@ -1650,8 +1657,129 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
             }
         }
+        if constexpr (DIRECT) {   // the mask word; the storing lane's limits (no scan) or the scan lane's scalars, as above
+            if (c.w < NTT && (c.w < NTT - 1 || c.ok6)) {
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+                if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+                if (!sl.v) {
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                        hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                    }
+                }
+            }
+            if (sl.v && c.w == 0 && c.lane < J) {
+                scan_v = sl.v[c.lane];
+                scan_lo = lim.lo[c.lane];
+                scan_hi = lim.hi[c.lane];
+                if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         TJ_SYNC(10);
+        if constexpr (DIRECT) {
+            float *S = reinterpret_cast<float *>(c.smem + LDS_Q);
+            unsigned *M = reinterpret_cast<unsigned *>(c.smem + LDS_Q + TMAX * 128);
+            const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
+            const bool ok = c.w < NTT && (c.w < NTT - 1 || c.ok6);
+            const bool vec = !(J & 3), scan = sl.v != nullptr;
+            f32x4 zv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};   // no scan: this lane's x0c
+            // ---- phase 1: the prediction -> eps_out; x0 of this lane's elements (a held one: the hold's value) -> S, the mask word -> M
+            if (c.w < NTT) {
+                const char *X = c.smem + LDS_X;
+                f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) {
+                    const int m2lo = (ks & 1) << 1;
+                    const unsigned b0 = (c.w < NTT - 1 ? c.xa[m2lo] + (unsigned)(c.w * 16 * XROW) : c.xa6[m2lo]) + (unsigned)((ks >> 1) * 256);
+                    const unsigned b1 = (c.w < NTT - 1 ? c.xa[m2lo | 1] + (unsigned)(c.w * 16 * XROW) : c.xa6[m2lo | 1]) + (unsigned)((ks >> 1) * 256);
+                    const f16x8 bh = lds16(X + b0), bl = lds16(X + b1);
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) mma3<S_FC>(E[n], wf[n][ks][0], wf[n][ks][1], bh, bl);
+                }
+                const float *sp = stat + tok * 8;
+                const f32x4 p0 = *reinterpret_cast<const f32x4 *>(sp), p1 = *reinterpret_cast<const f32x4 *>(sp + 4);
+                const float m = fmaxf(fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p0[2], p0[3])), fmaxf(fmaxf(p1[0], p1[1]), fmaxf(p1[2], p1[3])));
+                const float c_o = 1.0f / (f16_scale_from_bits(__builtin_bit_cast(unsigned, m)) * a.sc_io[1]);
+                if (scan && ok && c.g == 0) M[tok] = hold_m;
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int j0 = 16 * n + 4 * c.g;
+                    if (!ok || j0 >= J) continue;
+                    const long at = (traj * a.T + tok) * J + j0;
+                    f32x4 e = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (vec) {
+                        e = E[n] * c_o + *reinterpret_cast<const f32x4 *>(a.b_out + j0);
+                        if (a.eps_out) *reinterpret_cast<f32x4 *>(a.eps_out + at) = e;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            e[r] = E[n][r] * c_o + a.b_out[j0 + r];
+                            if (a.eps_out) a.eps_out[at + r] = e[r];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (j0 + r >= J) continue;
+                        const bool held = ((hold_m >> (j0 + r)) & 1u) != 0u;
+                        const float x0 = held ? hold.x0[at + r] : e[r];   // x0 IS the network's output
+                        if (scan) S[tok * 32 + j0 + r] = x0;
+                        else zv[n][r] = held ? x0 : (x0 < lo4[n][r] ? lo4[n][r] : (x0 > hi4[n][r] ? hi4[n][r] : x0));
+                    }
+                }
+            }
+            if (scan) {
+                // ---- phase 2: every wave of the workgroup (this barrier and the next stand outside `if (c.w < NTT)`)
+                __syncthreads();
+                // ---- phase 3: the scan, one lane per joint, rows in order (the slew twin's, row for row)
+                if (c.w == 0 && c.lane < J) {
+                    const int j = c.lane;
+                    const float v = scan_v, lo = scan_lo, hi = scan_hi;
+                    float y = scan_y;
+                    for (int t0 = 0; t0 < a.T; t0 += 16) {
+                        float q[16];
+                        unsigned mw[16];
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) {
+                            const int t = t0 + k < a.T ? t0 + k : a.T - 1;
+                            q[k] = S[t * 32 + j];
+                            mw[k] = M[t];
+                        }
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) {
+                            if (t0 + k >= a.T) continue;
+                            y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
+                            S[(t0 + k) * 32 + j] = y;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            // ---- phase 4: x0c itself is the result
+            if (c.w < NTT) {
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int j0 = 16 * n + 4 * c.g;
+                    if (!ok || j0 >= J) continue;
+                    const long at = (traj * a.T + tok) * J + j0;
+                    f32x4 x0c = zv[n];
+                    if (scan) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (j0 + r < J) x0c[r] = S[tok * 32 + j0 + r];
+                    }
+                    if (vec) {
+                        *reinterpret_cast<f32x4 *>(dr.out + at) = x0c;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (j0 + r < J) dr.out[at + r] = x0c[r];
+                    }
+                }
+            }
+        }
         if constexpr (SLEW) {
             float *S = reinterpret_cast<float *>(c.smem + LDS_Q);
             unsigned *M = reinterpret_cast<unsigned *>(c.smem + LDS_Q + TMAX * 128);
@@ -1763,7 +1891,7 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 }
             }
         }
-        if (!SLEW && c.w < NTT) {
+        if (!SLEW && !DIRECT && c.w < NTT) {
             const char *X = c.smem + LDS_X;
             f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
             const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tok6;
@@ -2027,6 +2155,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_slew_kernel(StepArgs a,
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_slew_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, int draws) {
     TJ<NTT, true>::template step_body<true, 5, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, sl);
+}
+// The direct twins (sd_direct_sample; instantiated in sd_traj_direct.hip): the slew twins for a network whose output is x0 (DirectArgs) -
+// no coefficients, no update, no history; x is only read, the projected x0 goes to dr.out.  One kernel per tile count serves plain, held,
+// limited, slewed and shared-context calls (hold.mask, sl.v NULL; infinite limits; draws a runtime argument).
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_direct_kernel(StepArgs a, HoldArgs hold, LimitArgs lim, SlewArgs sl, DirectArgs dr, int draws) {
+    TJ<NTT, true>::template step_body<false, 6, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, MultistepArgs{}, lim, sl, dr);
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_direct_kernel(StepArgs a, HoldArgs hold, LimitArgs lim, SlewArgs sl, DirectArgs dr, int draws) {
+    TJ<NTT, true>::template step_body<true, 6, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, MultistepArgs{}, lim, sl, dr);
 }
 struct RolloutDrawsArgs {   // the kernel-argument segment of the shared rollout kernel
     RolloutArgs ra;

@@ -71,6 +71,9 @@ TrajStepLimFn traj_step_lim_fn(int ntt, bool wide);
 // sd_traj_slew.hip: the slew instantiations (the limits', plus the scan over the rows behind two workgroup barriers: SlewArgs)
 typedef void (*TrajStepSlewFn)(tj::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, int);
 TrajStepSlewFn traj_step_slew_fn(int ntt, bool wide);
+// sd_traj_direct.hip: the direct instantiations (the network's output is x0: the slew twins' epilogue without coefficients, update or history)
+typedef void (*TrajStepDirectFn)(tj::StepArgs, HoldArgs, LimitArgs, SlewArgs, DirectArgs, int);
+TrajStepDirectFn traj_step_direct_fn(int ntt, bool wide);
 
 // zeroes words [col0, col0 + ncols) of every 8-word row of the abs-max table
 __global__ void zero_word_cols_kernel(unsigned *mb, int rows, int col0, int ncols) {
@@ -356,12 +359,22 @@ static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 &&
 
 // one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
 // as a runtime option; r.hold: the hold twin (sd_traj_hold.hip), whatever the group size; r.ms: the multistep twin (sd_traj_ms.hip);
-// r.lim: the limits twin (sd_traj_lim.hip); r.slew: the slew twin (sd_traj_slew.hip)
+// r.lim: the limits twin (sd_traj_lim.hip); r.slew: the slew twin (sd_traj_slew.hip); r.direct: the direct twin (sd_traj_direct.hip)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise) {
     const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
     if (ntt < 1 || ntt > 7) return fail(SD_E_BADARG, "traj_step_kernel: horizon out of range");
     if (!traj_groups_ok(r)) return fail(SD_E_BADARG, "traj_step_draws_kernel: B must be a multiple of draws >= 1");
+    if (r.direct) {   // x0 = the network's output: hold, scan (slew->v given) and box in the epilogue, x only read
+        if (r.coef || r.pin || r.ms || variant == 0 || !r.direct->out || !r.lim || !r.lim->lo || !r.lim->hi || w->J > 32 ||
+            (r.hold && r.hold->mask && !r.hold->x0))
+            return fail(SD_E_BADARG, "traj_step_direct_kernel: the direct twins take no coefficients, pin or history; they need out, lo and hi, the three-product kernels and J <= 32");
+        const tj::StepArgs a = traj_step_args(w, s, r, nullptr, nkt);
+        static DevFlag direct_attr_set[2][8];   // [one key tile | wide][ntt]
+        return launch_step_kernel(traj_step_direct_fn(ntt, variant == 2), "traj_step_direct_kernel", direct_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B,
+                                  tj::NTHREADS, tj::LDS_BYTES, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.lim,
+                                  r.slew ? *r.slew : SlewArgs{nullptr, nullptr}, *r.direct, r.draws);
+    }
     if (r.pin && (!r.coef || variant == 0)) return fail(SD_E_BADARG, "traj_step_pin_kernel: pinned rows need the DDIM coefficients and the three-product kernels");
     if (r.hold && (!r.coef || variant == 0 || r.pin))
         return fail(SD_E_BADARG, "traj_step_hold_kernel: held elements need the DDIM coefficients and the three-product kernels, and exclude a pin");

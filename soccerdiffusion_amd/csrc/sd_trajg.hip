@@ -829,15 +829,20 @@ struct TG {
     // mask word into M[tok], both in the K / V buffer, which nothing uses after the last layer's self-attention; a workgroup barrier; lane
     // j < J of wave 0 runs slew_row over t = 0 .. T-1 on column j of S in place; a second barrier; the storing lanes read x0c back and
     // finish as the limits twin does.  Both barriers stand outside `if (c.w < NTT)`: every wave reaches them.
+    // PIN == 6, DIRECT: the direct twin (DirectArgs, sd_common.h; sd_direct_sample) - the slew twin for a network whose output is x0: no
+    // coefficient, no update, no history; x is only read, the prediction goes to eps_out and the projected x0c to dr.out.  The same four
+    // phases on the same planes; sl.v NULL (uniform over the workgroup) skips the exchange, the scan and both barriers, and the storing
+    // lane clamps.  hold.mask NULL: nothing held.
     template <int PIN = 0, bool DRAWS = false>
     static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{},
                                                      const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{},
-                                                     const SlewArgs &sl = SlewArgs{}) {
+                                                     const SlewArgs &sl = SlewArgs{}, const DirectArgs &dr = DirectArgs{}) {
         constexpr bool HOLD = PIN == 2;
         constexpr bool MS = PIN == 3;
         constexpr bool LIM = PIN == 4;
         constexpr bool SLEW = PIN == 5;
-        static_assert(!SLEW || 128 + 4 <= VROW, "the slew twin's S and M planes fit the K / V buffer");
+        constexpr bool DIRECT = PIN == 6;
+        static_assert(!(SLEW || DIRECT) || 128 + 4 <= VROW, "the slew twin's S and M planes fit the K / V buffer");
         extern __shared__ __attribute__((aligned(16))) char smem[];
         Ctx c;
         ctx_init(c, smem, a.T);
@@ -967,7 +972,107 @@ struct TG {
                     if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
                 }
             }
+            if constexpr (DIRECT) {   // the mask word; the storing lane's limits (no scan) or the scan lane's scalars, as above
+                if (c.w < NTT && (c.w < NTT - 1 || c.okl)) {
+                    const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
+                    if (hold.mask) hold_m = (unsigned)hold.mask[traj * a.T + tok];
+                    if (!sl.v) {
+#pragma unroll
+                        for (int n = 0; n < 2; ++n) {
+                            lo4[n] = *reinterpret_cast<const f32x4 *>(lim.lo + 16 * n + 4 * c.g);
+                            hi4[n] = *reinterpret_cast<const f32x4 *>(lim.hi + 16 * n + 4 * c.g);
+                        }
+                    }
+                }
+                if (sl.v && c.w == 0 && c.lane < J) {
+                    scan_v = sl.v[c.lane];
+                    scan_lo = lim.lo[c.lane];
+                    scan_hi = lim.hi[c.lane];
+                    if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+                }
+            }
             __syncthreads();
+            if constexpr (DIRECT) {
+                float *S = reinterpret_cast<float *>(c.smem + c.oK);
+                unsigned *M = reinterpret_cast<unsigned *>(c.smem + c.oK + a.T * 128);
+                const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
+                const bool ok = c.w < NTT && (c.w < NTT - 1 || c.okl);
+                const bool scan = sl.v != nullptr;
+                float zv[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // no scan: this lane's x0c
+                // ---- phase 1: the prediction -> eps_out; x0 of this lane's elements (a held one: the hold's value) -> S, the mask word -> M
+                if (c.w < NTT) {
+                    const char *X = c.smem;
+                    f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        const f16x8 bh = lds16(X + x_off(tok, 4 * ks + c.g)), bl = lds16(X + x_off(tok, XCH + 4 * ks + c.g));
+#pragma unroll
+                        for (int n = 0; n < 2; ++n) {
+                            const f16 *wp = a.w_out + ((long)(n * KS + ks) * 2) * 512 + c.lane * 8;
+                            mma3(E[n], glb16(wp), glb16(wp + 512), bh, bl);
+                        }
+                    }
+                    const float c_o = 1.0f / (tok_scale(tok) * a.sc_io[SC_OUT]);
+                    if (scan && ok && c.g == 0) M[tok] = hold_m;
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const int j0 = 16 * n + 4 * c.g;
+                        if (!ok || j0 >= J) continue;
+                        const long at = (traj * a.T + tok) * J + j0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            const float e = E[n][r] * c_o + a.b_out[j0 + r];
+                            if (a.eps_out) a.eps_out[at + r] = e;
+                            const bool held = ((hold_m >> (j0 + r)) & 1u) != 0u;
+                            const float x0 = held ? hold.x0[at + r] : e;   // x0 IS the network's output
+                            if (scan) S[tok * 32 + j0 + r] = x0;
+                            else zv[n][r] = held ? x0 : (x0 < lo4[n][r] ? lo4[n][r] : (x0 > hi4[n][r] ? hi4[n][r] : x0));
+                        }
+                    }
+                }
+                if (scan) {
+                    // ---- phase 2: every wave of the workgroup (this barrier and the next stand outside `if (c.w < NTT)`)
+                    __syncthreads();
+                    // ---- phase 3: the scan, one lane per joint, rows in order (the slew twin's, row for row)
+                    if (c.w == 0 && c.lane < J) {
+                        const int j = c.lane;
+                        const float v = scan_v, lo = scan_lo, hi = scan_hi;
+                        float y = scan_y;
+                        for (int t0 = 0; t0 < a.T; t0 += 16) {
+                            float q[16];
+                            unsigned mw[16];
+#pragma unroll
+                            for (int k = 0; k < 16; ++k) {
+                                const int t = t0 + k < a.T ? t0 + k : a.T - 1;
+                                q[k] = S[t * 32 + j];
+                                mw[k] = M[t];
+                            }
+#pragma unroll
+                            for (int k = 0; k < 16; ++k) {
+                                if (t0 + k >= a.T) continue;
+                                y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
+                                S[(t0 + k) * 32 + j] = y;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+                // ---- phase 4: x0c itself is the result
+                if (c.w < NTT) {
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const int j0 = 16 * n + 4 * c.g;
+                        if (!ok || j0 >= J) continue;
+                        const long at = (traj * a.T + tok) * J + j0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (j0 + r >= J) continue;
+                            dr.out[at + r] = scan ? S[tok * 32 + j0 + r] : zv[n][r];
+                        }
+                    }
+                }
+            }
             if constexpr (SLEW) {
                 float *S = reinterpret_cast<float *>(c.smem + c.oK);
                 unsigned *M = reinterpret_cast<unsigned *>(c.smem + c.oK + a.T * 128);
@@ -1054,7 +1159,7 @@ struct TG {
                     }
                 }
             }
-            if (!SLEW && c.w < NTT) {
+            if (!SLEW && !DIRECT && c.w < NTT) {
                 const char *X = c.smem;
                 f32x4 E[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
                 const int tok = c.w < NTT - 1 ? 16 * c.w + c.t : c.tokl;
@@ -1158,6 +1263,12 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_slew_kernel(StepAr
     TG<D, NTT>::template step_body<5, true>(a, PinArgs{}, draws, hold, ms, lim, sl);
 }
 
+// the direct twin (sd_direct_sample): the slew twin for a network whose output is x0 (DirectArgs) - x only read, the projected x0 to dr.out
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_direct_kernel(StepArgs a, HoldArgs hold, LimitArgs lim, SlewArgs sl, DirectArgs dr, int draws) {
+    TG<D, NTT>::template step_body<6, true>(a, PinArgs{}, draws, hold, MultistepArgs{}, lim, sl, dr);
+}
+
 }   // namespace tg
 
 // ======================================================================================
@@ -1240,6 +1351,10 @@ StepLimFn step_lim_fn(int d, int ntt) {
 typedef void (*StepSlewFn)(tg::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, int);
 StepSlewFn step_slew_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepSlewFn { return tg::traj_step_generic_slew_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepDirectFn)(tg::StepArgs, HoldArgs, LimitArgs, SlewArgs, DirectArgs, int);
+StepDirectFn step_direct_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDirectFn { return tg::traj_step_generic_direct_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
@@ -1355,14 +1470,16 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     if (r.draws < 1 || r.B % r.draws) return fail(SD_E_BADARG, "traj_step_generic_draws_kernel: bad group size");
     const int ntt = (T + 15) / 16;
     if (ntt < 1 || ntt > (d == 512 ? 3 : 7)) return fail(SD_E_BADARG, "traj_step_generic_kernel: horizon out of range");
+    if (r.direct && (r.coef || r.pin || r.ms || !r.direct->out || !r.lim || !r.lim->lo || !r.lim->hi || w->J > 32 || (r.hold && r.hold->mask && !r.hold->x0)))
+        return fail(SD_E_BADARG, "traj_step_generic_direct_kernel: the direct twin takes no coefficients, pin or history; it needs out, lo and hi and J <= 32");
     if (r.pin && !r.coef) return fail(SD_E_BADARG, "traj_step_generic_pin_kernel: pinned rows need the DDIM coefficients");
-    if (r.hold && (!r.coef || r.pin))
+    if (!r.direct && r.hold && (!r.coef || r.pin))
         return fail(SD_E_BADARG, "traj_step_generic_hold_kernel: held elements need the DDIM coefficients and exclude a pin");
     if (r.ms && (!r.coef || r.pin || (!r.ms->hist && !r.lim)))
         return fail(SD_E_BADARG, "traj_step_generic_ms_kernel: the multistep term needs the DDIM coefficients and a history buffer, and excludes a pin");
-    if (r.lim && (!r.ms || !r.lim->lo || !r.lim->hi || (!r.ms->hist && r.ms->w != 0.f)))
+    if (!r.direct && r.lim && (!r.ms || !r.lim->lo || !r.lim->hi || (!r.ms->hist && r.ms->w != 0.f)))
         return fail(SD_E_BADARG, "traj_step_generic_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
-    if (r.slew && (!r.lim || !r.slew->v || w->J > 32))
+    if (!r.direct && r.slew && (!r.lim || !r.slew->v || w->J > 32))
         return fail(SD_E_BADARG, "traj_step_generic_slew_kernel: slew limits need v, the limits arguments (which may all be infinite) and J <= 32");
     tg::StepArgs a{};
     a.x = r.x;
@@ -1396,6 +1513,12 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
     constexpr int MAX_LDS = 163840;
     static DevFlag attr_set[3][3][8];   // [plain | pinned | shared context][hidden_dim][ntt]
     DevFlag &flag = attr_set[r.draws > 1 ? 2 : r.pin ? 1 : 0][d == 128 ? 0 : d == 256 ? 1 : 2][ntt];
+    if (r.direct) {   // the direct twin: x0 = the network's output; hold, scan (slew->v given) and box in the epilogue, x only read
+        static DevFlag direct_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_direct_fn(d, ntt), "traj_step_generic_direct_kernel", direct_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.lim,
+                                  r.slew ? *r.slew : SlewArgs{nullptr, nullptr}, *r.direct, r.draws);
+    }
     if (r.slew) {   // the slew twin: the limits twin plus the scan over the rows
         static DevFlag slew_attr_set[3][8];   // [hidden_dim][ntt]
         return launch_step_kernel(step_slew_fn(d, ntt), "traj_step_generic_slew_kernel", slew_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,

@@ -173,7 +173,9 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     number from which a slew limit is chosen, and the one that shows it held: with ``--slew`` it is <= v, as long as the denormalised
     values stay inside the bound the margin was derived for (``normalised_slew``);
     ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
-    student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None.
+    student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None;
+    under ``limits`` / ``slew`` its output, which is x0, is projected inside the launch (``model.sample_direct``) and ``max_step_by_joint``
+    is reported as for the rollout; ``reproject`` and ``solver="multistep"`` raise for it.
     A model without context encoders (decoder pretraining) gets ten random context rows per window from the same generator.
     ``keep``: a list that receives, per batch, the tensors the marginals were computed from (tests).
     rmse_* are in radians; ``rmse_by_row`` / ``rmse_by_joint`` refer to the medoid draw; ``spread`` is the root mean squared distance, in
@@ -189,16 +191,14 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     if solver not in ("ddim", "multistep") or (distilled and solver != "ddim"):
         raise ValueError(f"evaluate: solver must be 'ddim' or 'multistep' (a distilled decoder has no rollout: 'ddim'), got {solver!r}")
     limits_given = limits
+    if reproject and distilled:
+        raise ValueError("evaluate: a distilled decoder predicts x0 itself - there is no eps to recompute (reproject)")
     if limits is not None:
-        if distilled:
-            raise ValueError("evaluate: a distilled decoder has no rollout whose x0 could be limited")
         J = model.mean.numel()
         given = [[None if math.isinf(a) else a for a in pair]      # as given, per joint: [lo, hi], None for an open side
                  for pair in zip(*(v[:J].tolist() for v in ops._limits_host(limits, J)))]
         limits = normalised_limits(limits, model.mean, model.std)
     if slew is not None:
-        if distilled:
-            raise ValueError("evaluate: a distilled decoder has no rollout whose x0 could be limited")
         slew_given = [None if math.isinf(a) else a for a in ops._slew_host(slew, model.mean.numel())[: model.mean.numel()].tolist()]
         slew = normalised_slew(slew, model.mean, model.std, limits_given)
     idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
@@ -224,8 +224,10 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
             x0n = ops.normalize(target, model.mean, model.std)
             part["loss"], eps = ops.noise_loss_grid(model, ctx, x0n, noise, t_dev, acp=acp, return_eps=True)
         x_T = torch.randn(Cn * G, T, J, device=device, generator=gen)
-        if distilled:
+        if distilled and limits is None and slew is None:
             x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
+        elif distilled:   # the student's output is x0: limits and slew project it inside the same launch (model.sample_direct)
+            x = model.sample_direct(ctx, x_T, limits=limits, slew=slew, draws=G, max_mode=max_mode)
         else:
             x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject, slew=slew)
         x = x.contiguous()

@@ -300,3 +300,20 @@ class End2EndDiffusionTransformer(nn.Module):
         tokens = self.step_encoding.table(ts, x_T.device)
         return ops.ddim_sample_guarded(packed, ctx, tokens, coef, x_T.contiguous(), trace=return_trace, max_mode=max_mode, pin=pin, draws=draws, hold=hold, multistep=msw,
                                        limits=limits, reproject=reproject, slew=slew)
+
+    @torch.no_grad()
+    def sample_direct(self, context: Sequence[torch.Tensor], x_T: torch.Tensor, hold=None, limits=None, slew=None, draws: int = 1,
+                      raw: bool = False, max_mode: Optional[int] = None):
+        """A distilled one-step decoder's tick (ros.py:293-298) under ``sample``'s guarantees: ``forward_with_context(context, x_T,
+        zeros)`` - whose output is the clean trajectory, not a noise prediction - plus the projection of ``sample``'s ``hold``, ``slew``
+        and ``limits`` (same forms, normalised space), in ONE launch on the trajectory kernels (``ops.direct_sample``).  ``draws`` = G:
+        the context tensors hold B / G observations; G start noises give G different trajectories.  ``raw=True`` also returns the
+        unprojected prediction, which is ``forward_with_context``'s value bit for bit.  With nothing set the result is that value.
+        There is no ``pin``, no ``solver`` and no ``reproject``: one step has no rows that could adapt to pinned ones, no history and
+        no eps to recompute.  The range guard is read back as in ``sample`` (``ops.direct_sample_guarded``)."""
+        ctx = torch.cat(list(context), dim=1).contiguous() if len(context) else None
+        packed = self.diffusion_action_generator.packed()
+        t0 = torch.zeros(1, dtype=torch.int64, device=x_T.device)
+        token = ops.step_token(t0, self.step_encoding._freq, self.step_encoding.token.detach()).view(1, self.hidden_dim)
+        return ops.direct_sample_guarded(packed, ctx, token, x_T.contiguous(), hold=hold, limits=limits, slew=slew, draws=draws, raw=raw,
+                                         max_mode=max_mode)

@@ -1003,6 +1003,114 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
 
 
+_NO_LIMITS: dict = {}
+
+
+def _no_limits(J: int, device) -> Limits:
+    """The infinite limit arrays of a direct call without ``limits`` (the kernels always read a box), uploaded once per (J, device): a
+    captured tick must not upload anything."""
+    key = (int(J), torch.device(device))
+    if key not in _NO_LIMITS:
+        _NO_LIMITS[key] = joint_limits({}, J=J, device=device)
+    return _NO_LIMITS[key]
+
+
+def _direct_req(x_shape, device, hold, limits, slew) -> tuple:
+    """(known, mask words, lo, hi, v, start) of a direct call, validated: ``hold``, ``limits`` and ``slew`` in ``ddim_sample``'s forms."""
+    B, T, J = x_shape
+    known, words = (None, None) if hold is None else _hold_req(hold, B, T, J, device)
+    v, start = (None, None) if slew is None else _slew_req(slew, B, J, device)
+    lim = _no_limits(J, device) if limits is None else _limits_req(limits, J, device)
+    return known, words, lim.lo, lim.hi, v, start
+
+
+def direct_sample(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Tensor, hold=None, limits=None, slew=None, draws: int = 1,
+                  raw: bool = False, status: Optional[Tensor] = None, max_mode: int = 3):
+    """A distilled one-step decoder under the guarantees of ``ddim_sample`` (``sd_direct_sample``): the network's output at the ONE step
+    token ``token`` ((d,) or (1, d): the token of t = 0, ros.py:293-298) is the clean trajectory x0 itself, so the result is that
+    prediction projected - ``hold = (known, mask)``, then the slew scan ``slew = v`` or ``(v, start)`` over the rows, then the box
+    ``limits``, each as ``ddim_sample`` takes and defines it for the predicted x0 of a rollout (whose last step returns the clamped x0
+    itself; a one-step model is that last step alone).  ``x_T`` (B, T, J), the start noise, is only read.  ``draws`` = G: ``ctx`` holds
+    B / G contexts, prepared once each; G noises give G different trajectories.  Returns the projected sample, or ``(sample, raw)`` with
+    ``raw=True``: ``raw`` is the unprojected prediction - ``forward_with_context(ctx, x_T, zeros)`` bit for bit.  With nothing set the
+    sample is ``raw`` bit for bit, -0 included; a NaN prediction stays NaN and limits nothing after it; every free element lies bitwise
+    inside ``limits`` and within ``fl(p +- v)`` of its predecessor p.  On the trajectory routes this is ONE launch of a direct twin of
+    the step kernels; on the others (``max_mode`` < 3, or a shape without trajectory kernels) the eps launches and one projection
+    launch.  ``status`` as in ``ddim_sample`` (not read here).  There is no ``pin``, no ``multistep`` and no ``reproject``: one step has
+    no free rows that could adapt to pinned ones, no history and no eps to recompute."""
+    draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
+    lib = _lib.load()
+    _req(x_T, "x_T"); _req(token, "token")
+    if x_T.dim() != 3:
+        raise ValueError("x_T: expected (B, T, J)")
+    B, T, J = x_T.shape
+    if token.numel() != packed.d:
+        raise ValueError(f"token: expected ONE step token of {packed.d} floats, got {tuple(token.shape)}")
+    Mc = 0
+    if ctx is not None:
+        _req(ctx, "context")
+        Mc = ctx.shape[1]
+        if ctx.shape[0] * draws != B or ctx.shape[2] != packed.d:
+            raise ValueError("context shape mismatch")
+    if status is not None:
+        _req(status, "status", torch.int32)
+    known, words, lo, hi, v, start = _direct_req((B, T, J), x_T.device, hold, limits, slew)
+    out = torch.empty_like(x_T)
+    pred = torch.empty_like(x_T) if raw else None
+    ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, 1), x_T.device)
+    check(lib.sd_direct_sample(C.byref(packed.struct), _ptr(ctx), token.data_ptr(), x_T.data_ptr(), out.data_ptr(), _ptr(pred), ws.data_ptr(), B, T, Mc,
+                               _ptr(status), int(max_mode), _ptr(known), _ptr(words), draws, lo.data_ptr(), hi.data_ptr(), _ptr(v), _ptr(start),
+                               _stream()), "sd_direct_sample")
+    return (out, pred) if raw else out
+
+
+def direct_sample_guarded(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Tensor, hold=None, limits=None, slew=None, draws: int = 1,
+                          raw: bool = False, max_mode: Optional[int] = None):
+    """``direct_sample`` with the range guard read back (one host synchronisation), as ``ddim_sample_guarded``: a non-finite result on
+    the split-fp16 kernels is repeated on the exact-fp32 MFMA kernels (``max_mode`` 1: the eps launches, then the projection launch),
+    with the same ``hold``, ``limits``, ``slew`` and ``draws``; FloatingPointError if that is not finite either.  ``max_mode`` None: the
+    default cap (mode 4 has no direct twin and runs as 3)."""
+    import warnings
+
+    draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
+    B, T, J = x_T.shape
+    if hold is not None:   # validated and uploaded once for both runs
+        hold = _hold_req(hold, B, T, J, x_T.device)
+    if limits is not None:
+        limits = _limits_req(limits, J, x_T.device)
+    if slew is not None:
+        slew = _slew_req(slew, B, J, x_T.device)
+    status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
+    cap = min(sampler_cap(packed, max_mode), 3)
+    out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=cap)
+    if int(status.item()) == 0:
+        return out
+    if cap >= 2:
+        warnings.warn("sd_direct_sample: the split-fp16 kernels left their operand range (non-finite sample); "
+                      "repeating the call on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
+        out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=1)
+        if int(status.item()) == 0:
+            return out
+    raise FloatingPointError("sd_direct_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
+
+
+def direct_project(raw: Tensor, hold=None, limits=None, slew=None) -> Tensor:
+    """The projection of ``direct_sample`` on its own (``sd_direct_project``): ``raw`` (B, T, J) - a predicted clean trajectory from
+    anywhere - under ``hold = (known, mask)``, the slew scan ``slew = v`` or ``(v, start)`` and the box ``limits``, in ``ddim_sample``'s
+    forms; a new tensor.  Compares and selects, one fp32 add and one subtract per row: -0 stays -0, a NaN stays NaN and limits nothing
+    after it, an infinite prediction comes out as its limit."""
+    lib = _lib.load()
+    _req(raw, "raw")
+    if raw.dim() != 3:
+        raise ValueError("direct_project: raw must be a whole (B, T, J) sample")
+    B, T, J = raw.shape
+    known, words, lo, hi, v, start = _direct_req((B, T, J), raw.device, hold, limits, slew)
+    out = torch.empty_like(raw)
+    check(lib.sd_direct_project(raw.data_ptr(), out.data_ptr(), _ptr(known), _ptr(words), lo.data_ptr(), hi.data_ptr(), _ptr(v), _ptr(start), B, T, J,
+                                _stream()), "sd_direct_project")
+    return out
+
+
 def select_medoid(x: Tensor, draws: int, gather: bool = True, index: Optional[Tensor] = None, out: Optional[Tensor] = None):
     """The representative of each context's draws (``sd_select_medoid``): ``x`` (C * draws, T, J) - the draws of a context contiguous, as
     ``ddim_sample(draws=...)`` returns them - or (C, draws, T, J).  Returns ``(index, chosen)``: index (C,) int32 with

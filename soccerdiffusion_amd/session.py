@@ -45,6 +45,12 @@ given angles INSIDE the rollout (``ops.ddim_sample(hold=...)``), so the free joi
     s.hold([0, 1], [0.3, -0.7], robots=[0, 2])                              # radians as published; until release(), through reset() too
     traj = s.step()                                                         # traj[[0, 2]][:, :, [0, 1]] are those angles in every row
 
+A distilled decoder (``cli distill``'s student, the checkpoint ros.py:47 loads: one forward at t = 0 whose output is the clean trajectory)
+takes the same ``limits``, ``slew``, ``holds``, ``draws`` / ``select`` and ``use_graph`` with ``direct=True`` - its output is the x0 they are defined on, projected
+inside the one launch (``model.sample_direct``); it refuses ``carry``, ``solver="multistep"`` and ``reproject``:
+
+    s = PolicySession.from_checkpoint("student.pth", batch=1, direct=True, limits=(lo, hi), slew=0.16, draws=8, advance=5, select="coherent", use_graph=True)
+
 There is no CPU path and no fallback: the model must be on the GPU and in eval mode."""
 
 from __future__ import annotations
@@ -64,6 +70,8 @@ KEYS = ("joint_command_history", "rotation", "joint_state")   # the ring modalit
 WRAPPED = {"joint_command_history": True, "rotation": False, "joint_state": True}   # (x + 3 pi) % (2 pi): ros.py:266-273
 DEFAULT_GAME_STATE = 2   # ros.py:274
 SELECTORS = ("medoid", "coherent")   # PolicySession(select=...): which of a tick's draws is committed
+# what a distilled session without direct=True says when it refuses limits, slew, holds, draws or use_graph
+_DIRECT_HINT = "pass direct=True: its output is x0, which is then projected inside the one launch (model.sample_direct)"
 
 
 class _GraphedTick:
@@ -72,7 +80,9 @@ class _GraphedTick:
     session's state alone.  A call copies the noise into the captured buffer, replays, reads the range-guard word back as the eager
     route does (``ops.ddim_sample_guarded``) and returns the captured sample buffer, which the next call overwrites.  A session with
     carry captures the pinned rollout on the session's own pin buffers, which the commit outside the graph rewrites: the same graph
-    serves a first tick (no rows pinned), every later one and the ticks after a partial reset."""
+    serves a first tick (no rows pinned), every later one and the ticks after a partial reset.  For a distilled decoder the captured
+    tick is windows, context encoders, the ONE direct launch (``ops.direct_sample``: the forward at t = 0 and the projection of its output)
+    and the selection; its step token is computed inside the tick from the session's device zeros."""
 
     def __init__(self, session: "PolicySession", x_T: torch.Tensor):
         m, dev = session.model, session.device
@@ -81,10 +91,12 @@ class _GraphedTick:
         self.session = weakref.proxy(session)
         ts = ops.ddim_timesteps(session.n_steps)
         self.packed = m.diffusion_action_generator.packed()
-        self.tokens = m.step_encoding.table(ts, dev)
-        self.coef = ops.ddim_coefficients(ts, ops.alphas_cumprod(), session.n_steps)
+        if not session.distilled:   # (a distilled decoder has no schedule: its one step token is computed inside the tick)
+            self.tokens = m.step_encoding.table(ts, dev)
+            self.coef = ops.ddim_coefficients(ts, ops.alphas_cumprod(), session.n_steps)
         self.msw = ops.multistep_weights(ts, ops.alphas_cumprod(), session.n_steps) if session.solver == "multistep" else None
-        self.lim = session._lim()   # (limits: the session's own device arrays, which set_limits rewrites in place - the capture stays)
+        # (limits: the session's own device arrays, which set_limits rewrites in place - the capture stays)
+        self.lim = session._direct_lim() if session.distilled else session._lim()
         self.cap = ops.sampler_cap(self.packed, 3)
         self.noise = x_T.clone()
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -106,6 +118,18 @@ class _GraphedTick:
 
     def _run(self) -> None:
         s = self.session
+        if s.distilled:   # windows, context encoders, ONE direct launch (ops.direct_sample) and the selection
+            cond = s._direct_cond()
+            self.ctx = s._context()
+            ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
+            m = s.model
+            token = ops.step_token(s._t0[:1], m.step_encoding._freq, m.step_encoding.token.detach()).view(1, m.hidden_dim)
+            self.all = ops.direct_sample(self.packed, ctx, token, self.noise, status=self.status, max_mode=self.cap, draws=s.draws, **cond, **self.lim)
+            if s.draws == 1:
+                self.x = self.all
+            else:
+                self.index, self.x, self.cost = s._select(self.all)
+            return
         cond = s._cond()   # (holds: the mask's compose launch is part of the captured tick; it reads the session's static buffers only)
         self.ctx = s._context()
         ctx = torch.cat(self.ctx, dim=1).contiguous() if self.ctx else None
@@ -127,7 +151,10 @@ class _GraphedTick:
         if int(self.status.item()) == 0:
             return self.x if s.draws == 1 else (self.x, self.all, self.index, self.cost)
         # the range guard tripped: model.sample's guarded eager route on the context the replay has just encoded
-        x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver, **s._lim()).contiguous()
+        if s.distilled:
+            x = s.model.sample_direct(self.ctx, x_T, draws=s.draws, max_mode=3, **s._direct_cond(), **s._direct_lim()).contiguous()
+        else:
+            x = s.model.sample(self.ctx, x_T, s.n_steps, max_mode=3, **s._cond(), draws=s.draws, solver=s.solver, **s._lim()).contiguous()
         if s.draws == 1:
             return x
         index, chosen, cost = s._select(x)
@@ -138,12 +165,20 @@ class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
                  select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False, slew=None,
-                 coherence_decay: float = 0.5, contrast: float = 0.0):
+                 coherence_decay: float = 0.5, contrast: float = 0.0, direct: bool = False):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
         also read for ``distilled_decoder`` unless ``distilled`` says it.  ``use_graph``: windows, context encoders and rollout of
-        ``step`` are replayed from one captured hipGraph (not for a distilled decoder).
+        ``step`` are replayed from one captured hipGraph (a distilled decoder: windows, encoders, the one direct launch and the selection).
+        ``direct=True`` (a DISTILLED decoder only - one forward at t = 0 whose output is the clean trajectory: ros.py:293-298): the session
+        takes ``limits``, ``slew``, ``holds``, ``draws`` / ``select`` and ``use_graph`` through ``model.sample_direct``: the network's
+        output is x0, on which all of them are defined - a one-step model is the last step of a limited rollout alone.  Without the flag
+        a distilled session refuses these options as it always did (nothing that ran before runs differently), and the message names it.  G start noises give G different trajectories,
+        so the selectors mean what they mean for the rollout.  It refuses ``carry`` (one step cannot adapt its free rows to pinned ones:
+        ``select="coherent"`` plus ``slew`` from the last committed row is its continuity), ``solver="multistep"`` (no history) and
+        ``reproject`` (no eps to recompute), with or without the flag.  Built with none of the options it makes the calls it always made:
+        ``forward_with_context``.
         ``carry`` / ``advance`` (overlapping ticks): a tick pushes the first ``advance`` rows of its trajectory into the action history
         (default: T - carry) and pins the first ``carry`` rows of the next tick to its rows [advance, advance + carry), in normalised
         space as sampled, at every denoising step.  ``advance`` is the number of trajectory points between two ticks.  carry = 0 with
@@ -151,7 +186,7 @@ class PolicySession:
         ``draws`` = G / ``select``: a tick samples G trajectories per robot from the once-encoded context and commits and returns the
         one ``select`` names - "medoid": the draw closest to all others (``ops.select_medoid``, on the device).  With ``carry`` all G
         draws share the seam and the carried rows come from the selected draw.  draws = 1 is the session without any of this, launch
-        for launch (no selection launch).  Not for a distilled decoder (one forward at t = 0 has no sampling to repeat).
+        for launch (no selection launch).
         ``select="coherent"`` / ``coherence_decay`` / ``contrast`` (overlapping ticks only: ``advance`` < T): the draw that continues the
         robot's previous plan (``ops.select_coherent``; the backward-coherence criterion of Bidirectional Decoding, Liu et al. 2024).  Rows
         [advance, T) of the last committed trajectory and rows [0, T - advance) of the new draws describe the same instants; the draw with
@@ -166,7 +201,7 @@ class PolicySession:
         joints another module owns, a motor that is switched off) - the free joints are sampled to fit them.  It allocates the known-value
         buffer, a word of held joints per robot and the tick's mask; every tick then composes the mask in one launch and runs the
         rollout with ``ops.ddim_sample(hold=...)``, the carried rows of ``carry`` included.  Without the flag every launch is the one
-        of the session without any of this.  Not for a distilled decoder; J <= 32.
+        of the session without any of this.  J <= 32.
         ``solver``: "ddim" (default: the session without this argument, launch for launch) or "multistep" - every tick's rollout runs the
         second-order multistep solver (``model.sample(solver="multistep")``) on the same ``num_inference_steps`` timesteps; meant for fewer
         steps per tick.  It composes with ``carry`` (the carried rows become the mask's leading rows: the seam stays bit-exact; J <= 32),
@@ -179,7 +214,7 @@ class PolicySession:
         ``set_limits`` rewrites the same device arrays, safe under ``use_graph``.  It composes with ``carry`` (the carried rows travel as
         mask bits, as under ``holds``: the seam stays exact, and they were published under the limits; J <= 32), ``holds`` (a held joint
         keeps its value whatever the limits say), ``draws``, ``robots=``, ``solver`` and ``use_graph``.  Without the argument every launch
-        is the one of the session without any of this.  Not for a distilled decoder.
+        is the one of the session without any of this.
         ``slew`` ((J,) floats, one number, or ``{joint: v}``): slew limits in radians PER ROW as published - ``v = max velocity / row
         rate``, e.g. 8 rad/s at 50 Hz rows: 0.16; +inf: none.  One launch converts them to normalised space, ``v / std[j]`` moved inward by
         a margin that covers the rounding of the scan and of the commit (``sd_session_slew``), and every tick's rollout keeps consecutive
@@ -189,18 +224,19 @@ class PolicySession:
         margin assumes published values inside ``limits`` where both sides are given, else inside [-pi, pi].  ``set_slew`` rewrites the
         same device array, safe under ``use_graph``.  With ``carry`` row 0 is pinned: the scan starts from the carried rows (the seam
         stays exact) and no anchor is used.  A jump into a held joint's value is not limited.  It composes with ``limits``, ``holds``,
-        ``draws``, ``robots=``, ``solver`` and ``use_graph``.  Not for a distilled decoder; a ``v`` not above its margin raises."""
+        ``draws``, ``robots=``, ``solver`` and ``use_graph``.  A ``v`` not above its margin raises."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
-        self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (needs no device)
-        self.draws, self.select = self.check_draws(draws, select, self.distilled)                                          # (likewise)
+        self.direct = self.check_direct(direct, self.distilled)                                                            # (needs no device)
+        self.carry, self.advance = self.check_carry(model.trajectory_prediction_length, carry, advance, self.distilled)   # (likewise)
+        self.draws, self.select = self.check_draws(draws, select, self.distilled, self.direct)                             # (likewise)
         self.coherence_decay, self.contrast = self.check_select(self.select, model.trajectory_prediction_length, self.advance, self.draws,
                                                                 coherence_decay, contrast)                                # (likewise)
-        self.holds = self.check_hold(holds, model.num_joints, self.distilled)                                              # (likewise)
+        self.holds = self.check_hold(holds, model.num_joints, self.distilled, self.direct)                                            # (likewise)
         self.solver = self.check_solver(solver, model.num_joints, self.carry, self.distilled)                              # (likewise)
-        limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled)                                   # (likewise)
-        self.reproject = bool(reproject)
-        slew = self.check_slew(slew, model.num_joints, self.carry, self.distilled)                                         # (likewise)
+        limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled, self.direct)                                 # (likewise)
+        self.reproject = self.check_reproject(reproject, self.distilled)
+        slew = self.check_slew(slew, model.num_joints, self.carry, self.distilled, self.direct)                                       # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -214,8 +250,10 @@ class PolicySession:
         self.T, self.J = model.trajectory_prediction_length, model.num_joints
         self._seed, self._watched = int(seed), None
         self.use_graph = bool(use_graph)
-        if self.use_graph and self.distilled:
-            raise ValueError("PolicySession: use_graph replays the rollout; a distilled decoder has none")
+        if self.use_graph and self.distilled and not self.direct:
+            raise ValueError("PolicySession: use_graph replays the rollout; a distilled decoder has none - " + _DIRECT_HINT)
+        # a distilled session with any of the options runs the direct launch (model.sample_direct); with none, forward_with_context as ever
+        self._direct = self.direct and (self.use_graph or self.draws > 1 or self.holds or limits is not None or slew is not None)
         encoders = {"joint_command_history": model.action_history_encoder, "rotation": model.imu_encoder,
                     "joint_state": model.joint_states_encoder}
         self._encoders = {k: e for k, e in encoders.items() if e is not None}
@@ -268,15 +306,15 @@ class PolicySession:
         return carry, advance
 
     @staticmethod
-    def check_draws(draws: int = 1, select: str = "medoid", distilled: bool = False) -> tuple:
+    def check_draws(draws: int = 1, select: str = "medoid", distilled: bool = False, direct: bool = False) -> tuple:
         """(draws, select) of a session, validated (no device needed): ValueError unless draws is an int in [1, 64] and select a known
-        selector, or if draws > 1 with a distilled decoder."""
+        selector, or if draws > 1 with a distilled decoder without ``direct`` (with it, G start noises are G draws of the one-step map)."""
         if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= 64:
             raise ValueError(f"draws: the number of trajectories sampled per robot and tick is an int in [1, 64], got {draws!r}")
         if select not in SELECTORS:
             raise ValueError(f"select: one of {SELECTORS}, got {select!r}")
-        if draws > 1 and distilled:
-            raise ValueError("draws: a distilled decoder is one forward at t = 0 - there is no sampling to repeat")
+        if draws > 1 and distilled and not direct:
+            raise ValueError("draws: a distilled decoder is one forward at t = 0 - " + _DIRECT_HINT)
         return draws, select
 
     @staticmethod
@@ -298,12 +336,12 @@ class PolicySession:
         return float(decay), float(contrast)
 
     @staticmethod
-    def check_hold(holds: bool = False, J: int = 1, distilled: bool = False) -> bool:
-        """``holds`` of a session with J joints, validated (no device needed): ValueError if it is set with a distilled decoder (there is
-        no rollout in which an element could be held) or with more than 32 joints (one mask word per row)."""
+    def check_hold(holds: bool = False, J: int = 1, distilled: bool = False, direct: bool = False) -> bool:
+        """``holds`` of a session with J joints, validated (no device needed): ValueError if it is set with a distilled decoder without
+        ``direct`` (with it, an element is held in the decoder's output, which is x0) or with more than 32 joints (one mask word per row)."""
         holds = bool(holds)
-        if holds and distilled:
-            raise ValueError("holds: a distilled decoder is one forward at t = 0 - there is no rollout in which a joint could be held")
+        if holds and distilled and not direct:
+            raise ValueError("holds: a distilled decoder is one forward at t = 0 - " + _DIRECT_HINT)
         if holds and not 1 <= int(J) <= 32:
             raise ValueError(f"holds: one 32-bit mask word per row describes at most 32 joints, got J = {J}")
         return holds
@@ -321,18 +359,34 @@ class PolicySession:
         return solver
 
     @staticmethod
-    def check_limits(limits=None, J: int = 1, carry: int = 0, distilled: bool = False):
+    def check_limits(limits=None, J: int = 1, carry: int = 0, distilled: bool = False, direct: bool = False):
         """``limits`` of a session with J joints, validated (no device needed): None, or the two (32,) fp32 host arrays in radians, padded
         with -inf / +inf (``(lo, hi)`` of (J,) floats, one range r, or ``{joint: (lo, hi)}``, as ``ops.joint_limits`` takes them).
-        ValueError for a wrong shape, a NaN or lo > hi, with a distilled decoder (no rollout to limit), or with ``carry`` and J > 32 (the
-        carried rows travel as a 32-bit mask word per row)."""
+        ValueError for a wrong shape, a NaN or lo > hi, with a distilled decoder without ``direct`` (with it, the decoder's output is the
+        x0 that is limited), or with ``carry`` and J > 32 (the carried rows travel as a 32-bit mask word per row)."""
         if limits is None:
             return None
-        if distilled:
-            raise ValueError("limits: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if distilled and not direct:
+            raise ValueError("limits: a distilled decoder is one forward at t = 0 - " + _DIRECT_HINT)
         if carry > 0 and not 1 <= int(J) <= 32:
             raise ValueError(f"limits: with carry the limited rollout pins rows through a 32-bit mask word per row, got J = {J}")
         return ops._limits_host(limits, J)
+
+    @staticmethod
+    def check_direct(direct: bool = False, distilled: bool = False) -> bool:
+        """``direct`` of a session, validated (no device needed): ValueError if it is set without a distilled decoder - a model that
+        predicts noise has a rollout, and its output is not x0."""
+        if direct and not distilled:
+            raise ValueError("direct: the projection of a one-step output is a distilled decoder's route - this model predicts noise and has a rollout")
+        return bool(direct)
+
+    @staticmethod
+    def check_reproject(reproject: bool = False, distilled: bool = False) -> bool:
+        """``reproject`` of a session, validated (no device needed): ValueError if it is set with a distilled decoder - its output is x0,
+        there is no eps that could be recomputed from a clamped one."""
+        if reproject and distilled:
+            raise ValueError("reproject: a distilled decoder predicts x0 itself - there is no eps to recompute from the clamped x0")
+        return bool(reproject)
 
     def set_limits(self, lo, hi=None) -> None:
         """New joint limits in radians as published (``lo``, ``hi`` as the constructor's ``limits=(lo, hi)``; ``set_limits(r)`` or
@@ -340,21 +394,21 @@ class PolicySession:
         stays captured and the next tick runs under the new limits."""
         if self._limits is None:
             raise RuntimeError("PolicySession.set_limits: the session was built without limits")
-        host = self.check_limits(lo if hi is None else (lo, hi), self.J, self.carry, self.distilled)
+        host = self.check_limits(lo if hi is None else (lo, hi), self.J, self.carry, self.distilled, self.direct)
         ops.session_limits(self._limits, *host, self.model.mean, self.model.std, self.J)
         self._limits_rad = host
         if self._slew_v is not None:   # the slew margin depends on the bound the limits give: one more launch
             self._write_slew(self._slew_rad)
 
     @staticmethod
-    def check_slew(slew=None, J: int = 1, carry: int = 0, distilled: bool = False):
+    def check_slew(slew=None, J: int = 1, carry: int = 0, distilled: bool = False, direct: bool = False):
         """``slew`` of a session with J joints, validated (no device needed): None, or the (32,) fp32 host array in radians per row,
         padded with +inf ((J,) floats, one number, or ``{joint: v}``, as ``ops.joint_slew`` takes them).  ValueError for a wrong shape, a
-        NaN or a negative value, J > 32, or with a distilled decoder (no rollout to limit)."""
+        NaN or a negative value, J > 32, or with a distilled decoder without ``direct`` (with it, the scan runs on the decoder's output)."""
         if slew is None:
             return None
-        if distilled:
-            raise ValueError("slew: a distilled decoder is one forward at t = 0 - there is no rollout whose x0 could be limited")
+        if distilled and not direct:
+            raise ValueError("slew: a distilled decoder is one forward at t = 0 - " + _DIRECT_HINT)
         return ops._slew_host(slew, J)
 
     def _write_slew(self, v_rad) -> None:
@@ -379,7 +433,7 @@ class PolicySession:
         array in place, so a captured tick stays captured and the next tick runs under the new limits."""
         if self._slew_v is None:
             raise RuntimeError("PolicySession.set_slew: the session was built without slew")
-        self._write_slew(self.check_slew(slew, self.J, self.carry, self.distilled))
+        self._write_slew(self.check_slew(slew, self.J, self.carry, self.distilled, self.direct))
 
     def _lim(self, dev_idx=None) -> dict:
         """The limit arguments of the tick's rollout (of the robots ``dev_idx``): none in a session without limits or slew."""
@@ -393,6 +447,16 @@ class PolicySession:
                 start = self._anchor if dev_idx is None else self._anchor.view(self.B, G * 32)[dev_idx.long()].reshape(-1, 32).contiguous()
             out["slew"] = (self._slew_v, start)
         return out
+
+    def _direct_lim(self, dev_idx=None) -> dict:
+        """``_lim`` for the direct launch of a distilled decoder: the same device arrays and anchors, without ``reproject``."""
+        out = self._lim(dev_idx)
+        out.pop("reproject", None)
+        return out
+
+    def _direct_cond(self, dev_idx=None) -> dict:
+        """The conditioning of a distilled tick: ``hold=`` in a session with ``holds`` (the mask's compose launch), else nothing."""
+        return {"hold": self._hold(dev_idx)} if self.holds else {}
 
     @property
     def _carrying(self) -> bool:
@@ -743,10 +807,17 @@ class PolicySession:
                     self._graph = _GraphedTick(self, x_T)
                 x = self._graph(x_T)
             else:
-                cond = {} if self.distilled else self._cond(dev_idx)   # (holds: the mask's compose launch opens the tick)
+                cond = self._direct_cond(dev_idx) if self.distilled else self._cond(dev_idx)   # (holds: the mask's compose launch opens the tick)
                 ctx = self._context(subset)
-                if self.distilled:   # one forward at t = 0 (ros.py:293-298)
+                if self.distilled and not self._direct:   # one forward at t = 0 (ros.py:293-298)
                     x = m.forward_with_context(ctx, x_T.contiguous(), self._t0[:S])
+                elif self.distilled:   # the same forward and the projection of its output - hold, slew, limits - in one launch
+                    every = m.sample_direct(ctx, x_T, draws=G, max_mode=3, **cond, **self._direct_lim(dev_idx)).contiguous()
+                    if G == 1:
+                        x = every
+                    else:
+                        index, chosen, cost = self._select(every, dev_idx)
+                        x = (chosen, every, index, cost)
                 elif G == 1:
                     x = m.sample(ctx, x_T, self.n_steps, max_mode=3, **cond, solver=self.solver, **self._lim(dev_idx))
                 else:   # the context was encoded once per robot; its G draws share the folded planes
@@ -804,7 +875,8 @@ class PolicySession:
     @classmethod
     def from_checkpoint(cls, path: str, device=None, ema: bool = False, **kwargs) -> "PolicySession":
         """A session on the model of a checkpoint written by ``cli train`` / ``cli distill`` (or by the reference).  ``ema=True``: on the
-        checkpoint's ``ema_model_state_dict`` (``cli train --ema-decay``) instead of the last iterate; ValueError if it holds none."""
+        checkpoint's ``ema_model_state_dict`` (``cli train --ema-decay``) instead of the last iterate; ValueError if it holds none.
+        ``direct=None``: as the checkpoint says - True for a distilled one (``cli rollout``)."""
         from .cli import build_model
 
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
@@ -813,4 +885,6 @@ class PolicySession:
             raise ValueError(f"checkpoint {path} has no '{key}' (ema=True needs one trained with --ema-decay)")
         model = build_model(ckpt["hyperparams"]).to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
         model.load_state_dict(ckpt[key])
+        if "direct" in kwargs and kwargs["direct"] is None:
+            kwargs["direct"] = bool(ckpt["hyperparams"].get("distilled_decoder", False))
         return cls(model.eval(), hyperparams=ckpt["hyperparams"], **kwargs)

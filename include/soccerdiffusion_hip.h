@@ -232,6 +232,12 @@ int sd_direct_sample(const sd_denoiser_weights *w, const float *ctx, const float
 int sd_direct_project(const float *raw, float *out, const float *hold_x0, const int32_t *hold_mask, const float *lo, const float *hi,
                       const float *v_or_null, const float *start_or_null, int B, int T, int J, void *stream);
 
+/* sd_ddim_slew_step with the acceleration scan of sd_ddim_sample_accel: a 32 floats, start2 (B, 32) floats or NULL (device memory); v must
+ * be given and may be all +inf.  One thread per (trajectory, joint).  SD_E_BADARG as sd_ddim_slew_step, and for a NULL. */
+int sd_ddim_accel_step(const float *eps, const float *x, float *x_prev, float *hist_or_null, const float *coef4, float w, const float *lo,
+                       const float *hi, int reproject, const float *v, const float *start_or_null, const float *a, const float *start2_or_null,
+                       const float *hold_x0, const int32_t *hold_mask, int B, int T, int J, void *stream);
+
 /* Normalizer.normalize (inverse = 0: (x - mean) / std) and .denormalize (inverse = 1:
  * x * std + mean), per joint — soccer_diffusion/dataset/pytorch.py:410-414.  n = rows * J. */
 int sd_normalize(const float *x, const float *mean, const float *stdv, float *out, long n, int J, int inverse,
@@ -416,6 +422,42 @@ int sd_ddim_sample_slew(const sd_denoiser_weights *w, const float *ctx, const fl
                         float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
                         const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw, float *history,
                         const float *lo, const float *hi, int reproject, const float *v, const float *start_or_null, void *stream);
+/* sd_ddim_sample_slew with per-joint acceleration limits beside the slew limits and the box: the second difference of consecutive rows of
+ * the predicted clean trajectory is at most a[j], at every step, before the update is formed.  Per trajectory b and joint j the scan's
+ * state is y1 (the row before; row -1: start[b][j]) and y2 (the row before that; row -2: start2[b][j]); NaN: no such row.
+ *   for t = 0 .. T-1:
+ *     d = y1 - y2;  p = y1 + d                             (fp32, one rounding each: the constant-velocity continuation)
+ *     al = p - a[j];  ah = p + a[j]                        (one rounding each)
+ *     z = x0[t] < al ? al : (x0[t] > ah ? ah : x0[t])      (compares: a NaN x0 stays NaN, a NaN p limits nothing)
+ *     z = the slew interval around y1, then the box, then the hold, as sd_ddim_sample_slew applies them to z
+ *     x0c[t] = z;  y2 = y1;  y1 = z
+ * and the update is sd_ddim_sample_slew's on x0c.  Priority: box, then slew, then acceleration.  The row order is part of the definition.
+ * a: 32 floats in device memory, a[j] >= 0, [J, 32) padded with +inf; +inf: no limit.  start2: (B, 32) floats in device memory padded with
+ * NaN, one row per TRAJECTORY, or NULL.  lo / hi and v must be given and may all be infinite.  There is no braking ahead of the box: where
+ * the box or the slew interval wins, the second difference at that row can exceed a; without a box or a slew limit the velocity can
+ * accumulate and the scan can run away from the prediction.  All a infinite and no start2: every step bitwise sd_ddim_sample_slew's.
+ * Kernels: on the trajectory routes the acceleration instantiations of the step kernels (sd_traj_acc.hip; traj_step_generic_accel_kernel),
+ * the slew twins with two rows of state in the scan; one launch per step, no fused rollout form, no mode-4 twin (max_mode = 4 runs the
+ * mode-3 kernels).  On the row-panel and chain routes each step returns eps and ddim_accel_step_kernel updates x (and the history).
+ * SD_E_BADARG: as sd_ddim_sample_slew, and for a NULL. */
+int sd_ddim_sample_accel(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x, float *trace,
+                         float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status, int max_mode,
+                         const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws, const float *msw, float *history,
+                         const float *lo, const float *hi, int reproject, const float *v, const float *start_or_null, const float *a,
+                         const float *start2_or_null, void *stream);
+/* The projection of a one-step decoder's output under acceleration limits: sd_direct_project with the scan above (direct_project_accel_kernel).
+ * A one-step call under acceleration limits is two launches: sd_direct_sample with nothing set, which returns raw, then this.  v NULL: no
+ * slew limit. */
+int sd_direct_project_accel(const float *raw, float *out, const float *hold_x0, const int32_t *hold_mask, const float *lo, const float *hi,
+                            const float *v_or_null, const float *start_or_null, const float *a, const float *start2_or_null, int B, int T, int J,
+                            void *stream);
+/* sd_direct_sample under acceleration limits in one call: the plain direct launch (no hold, no scan), which returns the unprojected
+ * prediction in raw - it must be given - then sd_direct_project_accel from raw to out.  Arguments as sd_direct_sample's, plus a and
+ * start2.  The status word tells of out.  SD_E_BADARG as sd_direct_sample, and for raw or a NULL. */
+int sd_direct_sample_accel(const sd_denoiser_weights *w, const float *ctx, const float *step_token, const float *x, float *out, float *raw,
+                           float *workspace, int B, int T, int Mc, int32_t *status, int max_mode, const float *hold_x0,
+                           const int32_t *hold_mask, int draws, const float *lo, const float *hi, const float *v_or_null,
+                           const float *start_or_null, const float *a, const float *start2_or_null, void *stream);
 /* sd_sampler_route (plain route numbers only) of a sd_ddim_sample_draws call of B trajectories. */
 int sd_sampler_route_draws(int d, int heads, int T, int Mc, int J, int L, int B, int max_mode, int draws);
 
@@ -481,6 +523,10 @@ int sd_sampler_eps_draws(const sd_denoiser_weights *w, const float *step_tokens,
 /* out[n][j] = max over t of |r[t + 1] - r[t]|, r = x std + mean (fp32, two roundings): the largest step between consecutive rows of
  * trajectory n at joint j, in the space of the denormalised trajectories.  x (N, T, J), out (N, J); one thread per (n, j).  T == 1: 0. */
 int sd_eval_max_step(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream);
+/* out[n][j] = max over t of |(r[t + 1] - r[t]) - (r[t] - r[t - 1])|, r as above (fp32, one rounding per operation, in that order): the largest
+ * second difference of trajectory n at joint j - the number an acceleration limit is chosen from.  One thread per (n, j); two runs agree
+ * bit for bit.  T <= 2: 0. */
+int sd_max_accel(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream);
 /* ---- held-out evaluation (csrc/sd_eval.hip; soccerdiffusion_amd/evaluation.py) --------------------------------------------
  * Both kernels: fp32, contraction off, no atomics, every sum in a fixed order that depends on the shape alone (written out at the top of
  * sd_eval.hip), so two runs agree bit for bit.
@@ -1010,6 +1056,12 @@ int sd_camera_intake(const uint8_t *frames, int64_t n_frames, int H, int W, int 
  *     evaluated exactly, as long as |published| <= bound_rad[j].  Slots [J, 32): +inf.  SD_E_BADARG also for a negative or NaN v_rad[j].
  *   sd_session_anchor: ONE launch copies row `row` of x (S, T, J; normalised space, as sampled) into anchor (B * draws, 32), rows
  *     (b * draws + g) for robot b = robots[s] (NULL: s) and every draw g - the start array of the robot's next tick.
+ * Acceleration limits (a session that hands sd_ddim_sample_accel its a, start and start2):
+ *   sd_session_accel: sd_session_slew for a_rad, radians per row^2 AS PUBLISHED: a_n[j] = (a_rad[j] - margin) / std[j] rounded toward zero,
+ *     margin = 4 std hu(3 XS / std) + 4 hu(XS) + 4 hu(pi + R) + 4 hu(R) - the four roundings of the scan's row function at magnitudes up to
+ *     3 XS / std and both roundings of the commit's expression at three published values with weights 1, 2 and 1.
+ *   sd_session_anchor2: sd_session_anchor with a second destination, in ONE launch: anchor2 <- row >= 1 ? row (row - 1) of x : the old
+ *     anchor, then anchor <- row `row` of x (row = advance - 1).  anchor and anchor2: (B * draws, 32) each, not the same array.
  * SD_E_BADARG on null pointers or non-positive sizes, before any launch. */
 #define SD_SESSION_MAX_RINGS 3
 #define SD_SESSION_MAX_RESET_RINGS 5
@@ -1052,6 +1104,9 @@ int sd_session_hold(float *pin_x0, int32_t *held, const float *values, int64_t s
 int sd_session_limits(float *lo_n, float *hi_n, const float *lo_rad, const float *hi_rad, const float *mean, const float *stdv, int J, void *stream);
 int sd_session_slew(float *v_n, const float *v_rad, const float *bound_rad, const float *mean, const float *stdv, int J, void *stream);
 int sd_session_anchor(float *anchor, const float *x, const int32_t *robots, int S, int B, int T, int J, int row, int draws, void *stream);
+int sd_session_accel(float *a_n, const float *a_rad, const float *bound_rad, const float *mean, const float *stdv, int J, void *stream);
+int sd_session_anchor2(float *anchor, float *anchor2, const float *x, const int32_t *robots, int S, int B, int T, int J, int row, int draws,
+                       void *stream);
 int sd_session_hold_mask(int32_t *mask, const int32_t *held, const int32_t *pin_rows, const int32_t *robots, int S, int B, int T, int J,
                          int draws, void *stream);
 

@@ -18,7 +18,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SRC = [os.path.join(CSRC, u + ".hip") for u in ("sd_kernels", "sd_traj", "sd_train", "sd_train_chain", "sd_conv", "sd_train_traj", "sd_trajg",
                                                 "sd_conv_train", "sd_swin", "sd_frames", "sd_head", "sd_session", "sd_traj_draws", "sd_eval", "sd_traj_hold",
-                                                "sd_traj_ms", "sd_traj_lim", "sd_traj_slew", "sd_traj_direct")]
+                                                "sd_traj_ms", "sd_traj_lim", "sd_traj_slew", "sd_traj_direct", "sd_traj_acc")]
 # The sampler's translation units are compiled WITHOUT packed fp32 vector instructions (v_pk_fma/mul/add_f32): they do not overlap with
 # MFMAs - neither a wave's own nor its SIMD partner's - while plain fp32 instructions do (tools/exp/coissue3.hip; NOTEBOOK.md 5.11), and
 # the trajectory kernel lives on that overlap: + 1.5 % sampler throughput.  The training units lose 0.6 % with the same flag: packed.
@@ -28,11 +28,11 @@ SRC = [os.path.join(CSRC, u + ".hip") for u in ("sd_kernels", "sd_traj", "sd_tra
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"sd_traj.hip": NO_PACKED_FP32, "sd_trajg.hip": NO_PACKED_FP32, "sd_traj_draws.hip": NO_PACKED_FP32, "sd_traj_hold.hip": NO_PACKED_FP32,
                "sd_traj_ms.hip": NO_PACKED_FP32, "sd_traj_lim.hip": NO_PACKED_FP32, "sd_traj_slew.hip": NO_PACKED_FP32,
-               "sd_traj_direct.hip": NO_PACKED_FP32, "sd_kernels.hip": NO_PACKED_FP32}   # the row-panel sampler (modes 0 - 2) was tuned with the flag as well
+               "sd_traj_direct.hip": NO_PACKED_FP32, "sd_traj_acc.hip": NO_PACKED_FP32, "sd_kernels.hip": NO_PACKED_FP32}   # the row-panel sampler (modes 0 - 2) was tuned with the flag as well
 # The units that own trajectory step kernels (traj_step*): build() checks their objects - no v_pk_{fma,mul,add}_f32 in a step kernel.
 STEP_KERNEL_UNITS = ("sd_traj.hip", "sd_trajg.hip", "sd_traj_draws.hip", "sd_traj_hold.hip",   # (_draws / _hold / _ms / _lim: sd_traj.h's shared-context /
                      "sd_traj_ms.hip", "sd_traj_lim.hip", "sd_traj_slew.hip",             # hold / multistep / limits / slew instantiations;
-                     "sd_traj_direct.hip")                                                # _direct: the direct twins of a one-step decoder)
+                     "sd_traj_direct.hip", "sd_traj_acc.hip")                             # _direct: a one-step decoder's twins; _acc: acceleration)
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libsoccerdiffusion_hip.so")
 ARCH = "gfx950"

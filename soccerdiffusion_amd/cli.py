@@ -3,10 +3,10 @@ the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
     python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]
-    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]]
+    python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]]
     python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]     (ml/training/distill.py:25-224)
-    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [-o report.json]   (evaluation.py)
-    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--draws G [--select medoid|coherent [--coherence-decay R] [--contrast L]]]   (ml/inference/ros.py:165-335)
+    python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]] [-o report.json]   (evaluation.py)
+    python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]] [--draws G [--select medoid|coherent [--coherence-decay R] [--contrast L]]]   (ml/inference/ros.py:165-335)
 
 Differences, all additive: data comes from the reference's SQLite database (`--db file`,
 read once into HBM by soccerdiffusion_amd/dataset.py, image frames included), from a tensor
@@ -562,6 +562,7 @@ def cmd_evaluate(args) -> int:
     _distilled_arg(args, params)
     limits = _limits_arg(args, params)   # in the space of the target trajectories (x * std + mean), as sample --hold
     slew = _slew_arg(args, params)       # radians per row in the same space
+    accel = _accel_arg(args, params)     # radians per row^2 in the same space
     model = build_model(params).to(device)
     model.load_state_dict(ema_model_state(checkpoint, "--ema", args.checkpoint) if args.ema else checkpoint["model_state_dict"])
     model.eval()
@@ -570,7 +571,7 @@ def cmd_evaluate(args) -> int:
     report = evaluate(model, source, idx, steps=args.steps, draws=args.draws, grid=args.grid, seed=args.seed,
                       max_mode=3 if args.max_mode is None else args.max_mode, timesteps=_timesteps(args.timesteps) if args.timesteps else None,
                       distilled=bool(params.get("distilled_decoder", False)), solver=args.solver, limits=limits,
-                      reproject=args.reproject, slew=slew)
+                      reproject=args.reproject, slew=slew, accel=accel)
     line = json.dumps(report)
     print(line)
     if args.output:
@@ -618,6 +619,11 @@ def cmd_sample(args) -> int:
         from .evaluation import normalised_slew
 
         slew = normalised_slew(slew, model.mean, model.std, _limits_arg(args, params))
+    accel = _accel_arg(args, params)     # radians per row^2 in the same space
+    if accel is not None:
+        from .evaluation import normalised_accel
+
+        accel = normalised_accel(accel, model.mean, model.std, _limits_arg(args, params))
     with torch.no_grad():
         if params_need_context(params):
             batch = source.batch(mine % source.n)
@@ -626,12 +632,13 @@ def cmd_sample(args) -> int:
         else:
             context = [torch.randn(B, 10, params["hidden_dim"], device=device, generator=gen)]
         distilled = params.get("distilled_decoder", False)
-        if distilled and G == 1 and hold is None and limits is None and slew is None:  # single forward at t = 0 (plot.py:118-121)
+        if distilled and G == 1 and hold is None and limits is None and slew is None and accel is None:  # single forward at t = 0 (plot.py:118-121)
             traj = model.forward_with_context(context, x_T, torch.zeros(B, device=device))
         elif distilled:   # the same forward on G start noises per context; its output is x0: hold, slew and limits project it in the launch
-            traj = model.sample_direct(context, x_T, hold=hold, limits=limits, slew=slew, draws=G)
+            traj = model.sample_direct(context, x_T, hold=hold, limits=limits, slew=slew, draws=G, accel=accel)
         else:
-            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject, slew=slew)   # G draws for each of the B contexts, which are encoded once
+            traj = model.sample(context, x_T, args.steps, draws=G, hold=hold, solver=args.solver, limits=limits, reproject=args.reproject, slew=slew,
+                                accel=accel)   # G draws for each of the B contexts, which are encoded once
         if G > 1:
             medoid = ops.select_medoid(traj.contiguous(), G, gather=False)[0]
         traj = ops.normalize(traj.contiguous(), model.mean, model.std, inverse=True)
@@ -645,6 +652,8 @@ def cmd_sample(args) -> int:
         saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} or the one range of --clip, as given
     if slew is not None:
         saved["slew"] = args.slew   # one number, or {joint: v}, as given
+    if accel is not None:
+        saved["accel"] = args.accel   # one number, or {joint: a}, as given
     if G > 1:   # (n, G, T, J): the draws of a context side by side; medoid (n,): the representative draw of each (ops.select_medoid)
         saved.update(trajectories=saved["trajectories"].view(B, G, *traj.shape[1:]), draws=G, medoid=medoid.cpu())
     torch.save(saved, out)
@@ -753,6 +762,9 @@ def cmd_rollout(args) -> int:
     joint inside [-R, R]: the limits act on the predicted clean trajectory inside every tick's rollout (PolicySession(limits=...)).
     --slew V | J=V[,J=V...]: consecutive published rows differ by at most V radians (every joint, or joint J), also across two ticks
     (PolicySession(slew=...): V = max velocity / row rate).
+    --accel A | J=A[,J=A...]: the second difference of three consecutive published rows is at most A radians (every joint, or joint J), also
+    across two ticks, wherever neither the box nor the slew limit wins (PolicySession(accel=...): A = max acceleration / row rate^2); it
+    needs --limits or --clip finite on both sides for every such joint.
     --select medoid|coherent [--coherence-decay R] [--contrast L]: which of the --draws G draws a tick commits; "coherent" (overlapping ticks
     only) is the draw closest to the previous tick's plan over the rows both describe (PolicySession(select="coherent")).  Whenever ticks
     overlap the line and the file gain ``select`` and ``plan_change_rms`` (``plan_change_rms``), for either selector."""
@@ -783,7 +795,7 @@ def cmd_rollout(args) -> int:
     session = PolicySession.from_checkpoint(args.checkpoint, device, ema=args.ema, num_inference_steps=args.steps, batch=args.synthetic,
                                             seed=args.seed, carry=args.carry, advance=args.advance, draws=args.draws, holds=bool(args.hold), solver=args.solver,
                                             limits=_limits_arg(args), reproject=args.reproject, slew=_slew_arg(args), select=args.select,
-                                            coherence_decay=args.coherence_decay, contrast=args.contrast, direct=None)
+                                            coherence_decay=args.coherence_decay, contrast=args.contrast, direct=None, accel=_accel_arg(args))
     params = session.hyperparams
     if args.hold:
         session.hold(*_hold_joints(args.hold, params["num_joints"]))
@@ -820,6 +832,8 @@ def cmd_rollout(args) -> int:
         saved["limits"] = _limits_saved(args)   # {joint: (lo, hi)} radians, or the one range of --clip
     if args.slew is not None:
         saved["slew"] = args.slew   # radians per row: one number, or {joint: v}
+    if args.accel is not None:
+        saved["accel"] = args.accel   # radians per row^2: one number, or {joint: a}
     if args.draws > 1:
         saved["draws"] = session.draws   # every published trajectory is the selected one of that many draws
     if episode is not None:
@@ -919,6 +933,29 @@ def _slew_arg(args, params: Optional[dict] = None):
     return args.slew
 
 
+def _accel(text: str):
+    """--accel A | J=A[,J=A...] -> one float, or {joint: a}; radians per row^2, a >= 0."""
+    try:
+        out = float(text) if "=" not in text else {int(j): float(v) for j, v in (item.split("=") for item in text.split(","))}
+        ok = out >= 0 if isinstance(out, float) else (len(out) == text.count(",") + 1 and all(j >= 0 and v >= 0 for j, v in out.items()))
+    except ValueError:
+        ok = False
+    if not ok:
+        raise argparse.ArgumentTypeError(f"--accel takes A or JOINT=A[,JOINT=A...] with distinct joint indices >= 0 and A >= 0, got {text!r}")
+    return out
+
+
+def _accel_arg(args, params: Optional[dict] = None):
+    """``accel`` of model.sample / evaluate / PolicySession from --accel: one number, {joint: a}, or None."""
+    if args.accel is None:
+        return None
+    if params is not None:
+        J = params["num_joints"]
+        if J > 32 or (isinstance(args.accel, dict) and max(args.accel) >= J):
+            raise SystemExit(f"--accel: joint indices lie in [0, {J}) and the model has at most 32 joints")
+    return args.accel
+
+
 def _limits_saved(args):
     return float(args.clip) if args.clip is not None else {j: (lo, hi) for j, lo, hi in args.limits}
 
@@ -937,6 +974,10 @@ def _add_limit_flags(p) -> None:
     p.add_argument("--slew", type=_slew, default=None, metavar="V | J=V[,J=V...]", help="consecutive rows of a trajectory differ by at most V "
                    "(every joint, or joint J): the predicted clean trajectory is slew-limited at every denoising step "
                    "(model.sample(slew=...)); radians per row, units as --limits' in this subcommand")
+    p.add_argument("--accel", type=_accel, default=None, metavar="A | J=A[,J=A...]", help="the second difference of three consecutive rows of a "
+                   "trajectory is at most A (every joint, or joint J): the predicted clean trajectory is acceleration-limited at every denoising "
+                   "step, ahead of --slew and --limits, which win (model.sample(accel=...)); radians per row^2, units as --limits' in this "
+                   "subcommand; rollout needs --limits / --clip finite on both sides for every such joint")
     p.add_argument("--reproject", action="store_true", help="with --limits / --clip: a clamped element's noise prediction is recomputed from the "
                    "clamped value (diffusers' use_clipped_model_output)")
 

@@ -373,6 +373,49 @@ __device__ __forceinline__ float slew_update(float x, float e, float x0, float x
     return __builtin_fmaf(c2, x0c, c3 * e);
 }
 
+// Per-joint acceleration limits on the predicted clean trajectory (sd_ddim_sample_accel), beside SlewArgs, whose layout does not move: the
+// second difference of consecutive rows of x0 is at most a[j] per joint.  The scan's state is two rows, y1 (the row before; row -1 is
+// SlewArgs.start) and y2 (the row before that; row -2 is start2); NaN: no such row.  An acceleration call always carries a SlewArgs, whose
+// v may all be +inf, as a slew call carries a LimitArgs.
+struct AccelArgs {
+    const float *a;        // 32 floats in device memory, >= 0, [J, 32) padded with +inf (+inf: no limit on that joint)
+    const float *start2;   // [B][32] floats, padded with NaN (NaN: no row -2 for that joint), or NULL: none at all
+};
+// Where the scan lane of an acceleration twin keeps its two extra scalars: elements of lo4[0], the storing lanes' box of the limits twin,
+// which a slew twin declares and never uses (its box is the scan lane's) - any new declaration in the shared step body moved two
+// instructions of three slew instantiations (profiles/accel_isa.txt).  lo4[0][ACC_A] is a[j], lo4[0][ACC_Y2] the row before y1.
+constexpr int ACC_A = 0, ACC_Y2 = 1;
+// The step bodies take their SlewArgs by reference and keep their signature: an acceleration twin hands them this pair, and only its own
+// code (if constexpr) reads the second half - so that the other twins' code does not change.
+struct SlewAccelArgs : SlewArgs {
+    AccelArgs ac;
+};
+__device__ __forceinline__ const AccelArgs &accel_of(const SlewArgs &sl) { return static_cast<const SlewAccelArgs &>(sl).ac; }
+// One row of the acceleration scan, shared by every kernel that runs it: x0 is limited to fl(p - a) .. fl(p + a) around the constant-velocity
+// continuation p = fl(y1 + fl(y1 - y2)) by compares - a NaN x0 stays NaN, a NaN p (either predecessor missing) limits nothing - and then
+// goes through slew_row as it stands: the slew interval, the box, the hold.  Priority: box, then slew, then acceleration.  The result is the
+// row's x0c; the caller moves y2 <- y1, y1 <- result.
+__device__ __forceinline__ float accel_row(float x0, float y1, float y2, float a, float v, float lo, float hi, bool held, float known) {
+    const float d = y1 - y2;
+    const float p = y1 + d;
+    const float al = p - a, ah = p + a;
+    const float z = x0 < al ? al : (x0 > ah ? ah : x0);
+    return slew_row(z, y1, v, lo, hi, held, known);
+}
+
+// The acceleration twins' embedding scale of one token (x_row: its J values): 1 while max |x| < 2^15 - the embedding is then the other
+// twins', bit for bit - else the power of two that brings max |x| into [2^14, 2^15).  The scan of these twins can run away from the
+// prediction (no box, no slew limit), and the step kernels split x into fp16 parts as it stands: |x| >= 65 504 would come out as NaN.
+// Returns the scale; *inv: its reciprocal, both exact.  A NaN is skipped by fmaxf; an infinite x stays infinite.
+__device__ __forceinline__ float x_token_scale(const float *x_row, int J, float *inv) {
+    float m = 0.f;
+    for (int j = 0; j < J; ++j) m = fmaxf(m, fabsf(x_row[j]));
+    const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u) - 127;
+    const bool big = e >= 15;
+    *inv = big ? __builtin_bit_cast(float, (unsigned)(127 - 14 + e) << 23) : 1.0f;
+    return big ? __builtin_bit_cast(float, (unsigned)(127 + 14 - e) << 23) : 1.0f;
+}
+
 // The direct twins of the step kernels (sd_direct_sample): the network's output IS x0 - a distilled one-step decoder (the reference's
 // robot node runs it: soccer_diffusion/ml/inference/ros.py:293-298).  No DDIM coefficient is read and no update is formed: x is only read
 // (by the embedding), the projected x0 - hold, then the slew scan, then the box, as the slew twins define them - goes to `out`, the
@@ -397,6 +440,7 @@ struct StepReq {
     const LimitArgs *lim = nullptr;      // or NULL; needs ms (whose hist may then be NULL): the limits twins
     const SlewArgs *slew = nullptr;      // or NULL; needs lim (whose bounds may all be infinite): the slew twins
     const DirectArgs *direct = nullptr;  // or NULL; excludes coef, pin and ms, needs lim; hold (mask and x0) and slew (v NULL allowed) optional: the direct twins
+    const AccelArgs *accel = nullptr;    // or NULL; needs slew (whose v may all be infinite), excludes direct: the acceleration twins
 };
 
 // A runtime token-tile count as a compile-time one: f(std::integral_constant<int, N>{}) for ntt = N in 1 .. MAX, nullptr for any other.

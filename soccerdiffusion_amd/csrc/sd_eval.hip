@@ -131,7 +131,39 @@ __global__ void max_step_kernel(const float *__restrict__ x, const float *__rest
     out[i] = worst;
 }
 
+// The largest second difference of consecutive rows of every trajectory, per joint: out[n][j] = max_t |(r[t + 1] - r[t]) - (r[t] - r[t - 1])|
+// with r = x std + mean as in max_step_kernel - three subtractions in fp32, one rounding each, in that order.  One thread per (trajectory,
+// joint) walks the rows in order; a maximum has no order to fix, so two runs agree bit for bit.  T <= 2: 0.  A NaN is skipped by fmaxf.
+__global__ void max_accel_kernel(const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ stdv, float *__restrict__ out,
+                                 long N, int T, int J) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * J) return;
+    const long n = i / J;
+    const int j = (int)(i - n * J);
+    const float sd = stdv[j], mu = mean[j];
+    const float *xn = x + n * (long)T * J + j;
+    float worst = 0.f;
+    if (T >= 3) {
+        float p2 = xn[0] * sd + mu, p1 = xn[J] * sd + mu;
+        for (int t = 2; t < T; ++t) {
+            const float cur = xn[(long)t * J] * sd + mu;
+            worst = fmaxf(worst, fabsf((cur - p1) - (p1 - p2)));
+            p2 = p1;
+            p1 = cur;
+        }
+    }
+    out[i] = worst;
+}
+
 }   // namespace ev
+
+extern "C" int sd_max_accel(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream) {
+    if (!x || !mean || !stdv || !out || N <= 0 || T < 1 || J < 1 || J > ev::MAX_J || N * J > 0x7fffffffL * 256)
+        return fail(SD_E_BADARG, "sd_max_accel: x, mean, std and out must be given; N > 0, T >= 1, 1 <= J <= 32");
+    SD_LAUNCH(ev::max_accel_kernel, dim3((unsigned)((N * J + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, mean, stdv, out, N, T, J);
+    SD_CHECK_LAUNCH("max_accel_kernel");
+    return 0;
+}
 
 extern "C" int sd_eval_max_step(const float *x, const float *mean, const float *stdv, float *out, long N, int T, int J, void *stream) {
     if (!x || !mean || !stdv || !out || N <= 0 || T < 1 || J < 1 || J > ev::MAX_J || N * J > 0x7fffffffL * 256)

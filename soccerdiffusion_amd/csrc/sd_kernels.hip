@@ -2632,6 +2632,97 @@ __global__ __launch_bounds__(64) void direct_project_kernel(const float *__restr
         }
     }
 }
+// ddim_slew_step_kernel with per-joint acceleration limits beside the slew limits and the box (AccelArgs, sd_common.h): the same thread
+// layout and the same blocked fetch ahead of the chain; the chain's state is two rows - y (row t-1; row -1: sl.start) and y2 (row t-2;
+// row -2: ac.start2) - and its row function is accel_row, the scan's one definition.  The row-panel and chain routes of
+// sd_ddim_sample_accel launch it behind a step that returned eps and left x alone (the trajectory routes run the scan inside the step
+// kernels' acceleration twins); sd_ddim_accel_step is the loop form's step.
+__global__ __launch_bounds__(64) void ddim_accel_step_kernel(const float *__restrict__ eps, const float *x, float *x_next, float *hist, float c0, float c1, float c2,
+                                       float c3, float w, LimitArgs lim, SlewArgs sl, AccelArgs ac, HoldArgs hold, int B, int T, int J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J, j = i - b * J;
+    const float a = ac.a[j], v = sl.v[j], lo = lim.lo[j], hi = lim.hi[j];
+    float y = sl.start ? sl.start[b * 32 + j] : __builtin_nanf("");
+    float y2 = ac.start2 ? ac.start2[b * 32 + j] : __builtin_nanf("");
+    for (int t0 = 0; t0 < T; t0 += SLEW_BLOCK) {
+        float e[SLEW_BLOCK], xv[SLEW_BLOCK], kn[SLEW_BLOCK], hs[SLEW_BLOCK];
+        unsigned m[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the block's loads: none depends on the chain
+            const int t = t0 + k < T ? t0 + k : T - 1;   // (a ragged last block reads its last row again)
+            const long at = ((long)b * T + t) * J + j;
+            e[k] = eps[at];
+            xv[k] = x[at];
+            m[k] = hold.mask ? (((unsigned)hold.mask[(long)b * T + t] >> j) & 1u) : 0u;
+            hs[k] = w != 0.f ? hist[at] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            const int t = t0 + k < T ? t0 + k : T - 1;
+            kn[k] = m[k] ? hold.x0[((long)b * T + t) * J + j] : 0.f;
+        }
+        float x0[SLEW_BLOCK], x0c[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) x0[k] = __builtin_fmaf(-c1, e[k], xv[k]) / c0;
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the chain, in row order
+            if (t0 + k < T) {
+                x0c[k] = accel_row(x0[k], y, y2, a, v, lo, hi, m[k] != 0u, kn[k]);
+                y2 = y;
+                y = x0c[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            if (t0 + k >= T) continue;
+            const long at = ((long)b * T + t0 + k) * J + j;
+            float xn = slew_update(xv[k], e[k], x0[k], x0c[k], c0, c1, c2, c3, lim.reproject);
+            if (w != 0.f) xn = __builtin_fmaf(w, hs[k] - x0c[k], xn);
+            x_next[at] = xn;
+            if (hist) hist[at] = x0c[k];
+        }
+    }
+}
+// direct_project_kernel with the acceleration scan (sd_direct_project_accel): out = raw under the hold, the acceleration and slew limits
+// and the box, accel_row the row function.  sl.v NULL: +inf.  The second launch of a one-step decoder's call under acceleration limits
+// (the first is the plain direct launch, which returns raw).  raw and out must not alias.
+__global__ __launch_bounds__(64) void direct_project_accel_kernel(const float *__restrict__ raw, float *__restrict__ out, LimitArgs lim, SlewArgs sl,
+                                                                  AccelArgs ac, HoldArgs hold, int B, int T, int J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J, j = i - b * J;
+    const float a = ac.a[j], v = sl.v ? sl.v[j] : __builtin_inff(), lo = lim.lo[j], hi = lim.hi[j];
+    float y = sl.start ? sl.start[b * 32 + j] : __builtin_nanf("");
+    float y2 = ac.start2 ? ac.start2[b * 32 + j] : __builtin_nanf("");
+    for (int t0 = 0; t0 < T; t0 += SLEW_BLOCK) {
+        float e[SLEW_BLOCK], kn[SLEW_BLOCK], x0c[SLEW_BLOCK];
+        unsigned m[SLEW_BLOCK];
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the block's loads: none depends on the chain
+            const int t = t0 + k < T ? t0 + k : T - 1;   // (a ragged last block reads its last row again)
+            e[k] = raw[((long)b * T + t) * J + j];
+            m[k] = hold.mask ? (((unsigned)hold.mask[(long)b * T + t] >> j) & 1u) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            const int t = t0 + k < T ? t0 + k : T - 1;
+            kn[k] = m[k] ? hold.x0[((long)b * T + t) * J + j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {   // the chain, in row order
+            if (t0 + k < T) {
+                x0c[k] = accel_row(e[k], y, y2, a, v, lo, hi, m[k] != 0u, kn[k]);
+                y2 = y;
+                y = x0c[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SLEW_BLOCK; ++k) {
+            if (t0 + k < T) out[((long)b * T + t0 + k) * J + j] = x0c[k];
+        }
+    }
+}
 
 
 // ======================================================================================
@@ -3097,13 +3188,15 @@ struct TrajCall {
     // ms: the multistep instantiations (the second-order solver's history term; a hold beside it is optional, never a pin)
     // lim: the limits instantiations (needs ms, whose history may then be NULL: first-order DDIM)
     // slew: the slew instantiations (needs lim): the limits epilogue around the scan over the rows
+    // accel: the acceleration instantiations (needs slew): the slew twins with two rows of state in the scan
     StepReq req(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin, const HoldArgs *hold = nullptr,
                 const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr, const SlewArgs *slew = nullptr) const {
         return StepReq{x, eps, B, T, Mc, i, n_tok, coef, per_traj, plan.precise ? nullptr : status, pin, draws, hold, ms, lim, slew};
     }
     int step(float *x, float *eps, int i, const float *coef, bool per_traj, int32_t *status, const PinArgs *pin = nullptr, const HoldArgs *hold = nullptr,
-             const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr, const SlewArgs *slew = nullptr) const {
-        const StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms, lim, slew);
+             const MultistepArgs *ms = nullptr, const LimitArgs *lim = nullptr, const SlewArgs *slew = nullptr, const AccelArgs *accel = nullptr) const {
+        StepReq r = req(x, eps, i, coef, per_traj, status, pin, hold, ms, lim, slew);
+        r.accel = accel;
         return generic() ? trajg_step(w, s.gws, r, st, per_traj ? s.stepmap : nullptr) : traj_step(w, ws(), r, st, plan.key_tiles, plan.precise);
     }
     // steps i0 .. i0 + n - 1 in one launch of the tuned family's rollout kernel; coef: the rollout's whole table
@@ -3160,6 +3253,23 @@ static int ddim_slew_step(const float *eps, const float *x, float *x_next, float
     SD_CHECK_LAUNCH("ddim_slew_step_kernel");
     return 0;
 }
+// x <- the same update on x0 under the acceleration scan (ddim_accel_step_kernel)
+static int ddim_accel_step(const float *eps, const float *x, float *x_next, float *hist, const float *coef4, float w, const LimitArgs &lim,
+                           const SlewArgs &sl, const AccelArgs &ac, const HoldArgs *hold, int B, int T, int J, hipStream_t st) {
+    const HoldArgs h = hold ? *hold : HoldArgs{nullptr, nullptr, nullptr};
+    SD_LAUNCH(ddim_accel_step_kernel, dim3((B * J + 63) / 64), dim3(64), 0, st, eps, x, x_next, hist, coef4[0], coef4[1], coef4[2], coef4[3], w, lim, sl, ac,
+              h, B, T, J);
+    SD_CHECK_LAUNCH("ddim_accel_step_kernel");
+    return 0;
+}
+// out <- raw under the hold, the acceleration scan and the box (direct_project_accel_kernel)
+static int direct_project_accel(const float *raw, float *out, const LimitArgs &lim, const SlewArgs &sl, const AccelArgs &ac, const HoldArgs *hold, int B,
+                                int T, int J, hipStream_t st) {
+    const HoldArgs h = hold ? *hold : HoldArgs{nullptr, nullptr, nullptr};
+    SD_LAUNCH(direct_project_accel_kernel, dim3((B * J + 63) / 64), dim3(64), 0, st, raw, out, lim, sl, ac, h, B, T, J);
+    SD_CHECK_LAUNCH("direct_project_accel_kernel");
+    return 0;
+}
 // out <- raw under the hold, the slew scan and the box (direct_project_kernel)
 static int direct_project(const float *raw, float *out, const LimitArgs &lim, const SlewArgs &sl, const HoldArgs *hold, int B, int T, int J, hipStream_t st) {
     const HoldArgs h = hold ? *hold : HoldArgs{nullptr, nullptr, nullptr};
@@ -3171,12 +3281,14 @@ static int direct_project(const float *raw, float *out, const LimitArgs &lim, co
 // lim (sd_ddim_sample_limits): per-joint limits on x0; w and hist may then both be NULL - first-order DDIM under limits.
 // slew (sd_ddim_sample_slew; needs lim): per-joint slew limits beside them - the step kernels' slew twins, or ddim_slew_step_kernel behind a
 // row-panel step.
+// accel (sd_ddim_sample_accel; needs slew): per-joint acceleration limits beside them - the acceleration twins, or ddim_accel_step_kernel.
 struct MultistepCall {
     const float *w;
     float *hist;
     const LimitArgs *lim = nullptr;
     const SlewArgs *slew = nullptr;
     bool direct = false;   // sd_direct_sample on the row-panel routes: the step returns eps and leaves x alone, and the caller projects it
+    const AccelArgs *accel = nullptr;
     float weight(int i) const { return w ? w[i] : 0.f; }
 };
 
@@ -3205,7 +3317,8 @@ static int traj_rollout(const TrajCall &c, const float *ctx, const float *step_t
         float *eps_i = eps_trace ? eps_trace + (size_t)i * n : nullptr;
         const MultistepArgs ms{msc ? msc->hist : nullptr, msc ? msc->weight(i) : 0.f};   // (no fused rollout form: one launch per step, like a hold)
         // (slew: the slew twins of the step kernels - the scan over the rows runs inside the step launch, behind an exchange of x0 through LDS)
-        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr, msc ? msc->lim : nullptr, msc ? msc->slew : nullptr)))
+        if ((rc = c.step(x, eps_i, i, coef + 4 * i, false, status, pin, hold, msc ? &ms : nullptr, msc ? msc->lim : nullptr, msc ? msc->slew : nullptr,
+                         msc ? msc->accel : nullptr)))
             return rc;
         if (trace && (rc = trace_copy(x, trace, i, n, c.st))) return rc;
     }
@@ -3298,6 +3411,8 @@ static int panel_rollout(const sd_denoiser_weights *w, const Scratch &s, const S
         }
         if (msc && msc->direct) {
             // (nothing: x is only read, direct_project behind this call turns eps_i into the result)
+        } else if (msc && msc->accel) {
+            if ((rc = ddim_accel_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, *msc->slew, *msc->accel, hold, B, T, w->J, st))) return rc;
         } else if (msc && msc->slew) {
             if ((rc = ddim_slew_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, *msc->slew, hold, B, T, w->J, st))) return rc;
         } else if (msc && (rc = msc->lim ? ddim_limit_step(eps_i, x, x, msc->hist, coef + 4 * i, msc->weight(i), *msc->lim, n, w->J, st)
@@ -3473,6 +3588,34 @@ extern "C" int sd_ddim_sample_slew(const sd_denoiser_weights *w, const float *ct
                            false, draws, n_hold ? &hold : nullptr, &msc);
 }
 
+// sd_ddim_sample_slew with per-joint acceleration limits beside the slew limits and the box (AccelArgs, sd_common.h), on every route.
+// a: 32 floats (device), start2: (B, 32) floats (device) or NULL.  lo / hi and v must be given; they may all be infinite.
+extern "C" int sd_ddim_sample_accel(const sd_denoiser_weights *w, const float *ctx, const float *step_tokens, const float *coef, float *x,
+                                    float *trace, float *eps_trace, float *workspace, int B, int T, int Mc, int n_steps, int32_t *status,
+                                    int max_mode, const float *hold_x0, const float *hold_noise, const int32_t *hold_mask, int draws,
+                                    const float *msw, float *history, const float *lo, const float *hi, int reproject, const float *v,
+                                    const float *start, const float *a, const float *start2, void *stream) {
+    const int n_hold = (hold_x0 ? 1 : 0) + (hold_noise ? 1 : 0) + (hold_mask ? 1 : 0);
+    if (!lo || !hi || !v || !a || n_steps <= 0) return fail(SD_E_BADARG, "sd_ddim_sample_accel: lo, hi, v and a (32 floats each, device) must be given");
+    if (n_hold != 0 && n_hold != 3) return fail(SD_E_BADARG, "sd_ddim_sample_accel: hold_x0, hold_noise and hold_mask must be given together");
+    if (msw && !history) return fail(SD_E_BADARG, "sd_ddim_sample_accel: msw needs a history buffer (both NULL: DDIM)");
+    if (msw && msw[0] != 0.f) return fail(SD_E_BADARG, "sd_ddim_sample_accel: msw[0] must be 0 (the first step has no history)");
+    if (history && (history == x || (n_hold && (history == hold_x0 || history == hold_noise || (const void *)history == (const void *)hold_mask))))
+        return fail(SD_E_BADARG, "sd_ddim_sample_accel: history must alias neither x nor the hold buffers");
+    if (n_hold && hold_noise == x) return fail(SD_E_BADARG, "sd_ddim_sample_accel: hold_noise must not alias x (x is overwritten by the first step)");
+    if (draws < 1 || B <= 0 || B % draws) return fail(SD_E_BADARG, "sd_ddim_sample_accel: draws must be >= 1 and divide B");
+    if (w && w->J > 32) return fail(SD_E_BADARG, "sd_ddim_sample_accel: lo, hi, v and a describe at most 32 joints");
+    if (w && (long)B * w->J > 0x7fffffffL) return fail(SD_E_BADARG, "sd_ddim_sample_accel: B * J must fit 31 bits");
+    const HoldArgs hold{hold_x0, hold_noise, hold_mask};
+    const LimitArgs lim{lo, hi, reproject ? 1 : 0};
+    const SlewArgs sl{v, start};
+    const AccelArgs ac{a, start2};
+    MultistepCall msc{msw, history, &lim, &sl};
+    msc.accel = &ac;
+    return ddim_sample_any(w, ctx, step_tokens, coef, x, trace, eps_trace, workspace, B, T, Mc, n_steps, status, max_mode, stream, nullptr, nullptr, nullptr,
+                           false, draws, n_hold ? &hold : nullptr, &msc);
+}
+
 // A distilled one-step decoder (the reference's robot node: soccer_diffusion/ml/inference/ros.py:293-298) under held elements, per-joint
 // limits and slew limits: the network's output at the one step token IS x0, so out = project(raw), raw = the denoiser on (ctx, x).  x is
 // only read.  The trajectory routes run ONE launch of a direct twin of the step kernels (DirectArgs, sd_common.h); every other route - and
@@ -3540,6 +3683,40 @@ extern "C" int sd_direct_project(const float *raw, float *out, const float *hold
     if (out == hold_x0) return fail(SD_E_BADARG, "sd_direct_project: out must not alias hold_x0");
     const HoldArgs hold{hold_x0, nullptr, hold_mask};
     return direct_project(raw, out, LimitArgs{lo, hi, 0}, SlewArgs{v, start}, hold_mask ? &hold : nullptr, B, T, J, (hipStream_t)stream);
+}
+
+// sd_direct_project with the acceleration scan (direct_project_accel_kernel): the second launch of a one-step decoder's call under
+// acceleration limits, behind the plain direct launch that returned raw.  v NULL: no slew limit.
+extern "C" int sd_direct_project_accel(const float *raw, float *out, const float *hold_x0, const int32_t *hold_mask, const float *lo, const float *hi,
+                                       const float *v, const float *start, const float *a, const float *start2, int B, int T, int J, void *stream) {
+    if (!raw || !out || raw == out || !lo || !hi || !a || B <= 0 || T <= 0 || J < 1 || J > 32 || (long)B * J > 0x7fffffffL)
+        return fail(SD_E_BADARG, "sd_direct_project_accel: bad argument");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_direct_project_accel: hold_x0 and hold_mask must be given together");
+    if (out == hold_x0) return fail(SD_E_BADARG, "sd_direct_project_accel: out must not alias hold_x0");
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    return direct_project_accel(raw, out, LimitArgs{lo, hi, 0}, SlewArgs{v, start}, AccelArgs{a, start2}, hold_mask ? &hold : nullptr, B, T, J,
+                                (hipStream_t)stream);
+}
+
+// sd_direct_sample under acceleration limits, in one call: the plain direct launch of sd_direct_sample - no hold, no scan; it returns the
+// unprojected prediction in `raw`, which must be given, and what it leaves in `out` is overwritten - then direct_project_accel_kernel
+// from raw to out.  Two launches on every route (no fused direct-accel twin).  The status word is zeroed first and tells of `out`.
+extern "C" int sd_direct_sample_accel(const sd_denoiser_weights *w, const float *ctx, const float *step_token, const float *x, float *out, float *raw,
+                                      float *workspace, int B, int T, int Mc, int32_t *status, int max_mode, const float *hold_x0,
+                                      const int32_t *hold_mask, int draws, const float *lo, const float *hi, const float *v, const float *start,
+                                      const float *a, const float *start2, void *stream) {
+    if (!raw || !a) return fail(SD_E_BADARG, "sd_direct_sample_accel: raw (B, T, J) and a (32 floats, device) must be given");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_direct_sample_accel: hold_x0 and hold_mask must be given together");
+    if (out && (out == hold_x0 || raw == hold_x0)) return fail(SD_E_BADARG, "sd_direct_sample_accel: out and raw must not alias hold_x0");
+    int rc = sd_direct_sample(w, ctx, step_token, x, out, raw, workspace, B, T, Mc, status, max_mode, nullptr, nullptr, draws, lo, hi, nullptr, nullptr, stream);
+    if (rc) return rc;
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = direct_project_accel(raw, out, LimitArgs{lo, hi, 0}, SlewArgs{v, start}, AccelArgs{a, start2}, hold_mask ? &hold : nullptr, B, T, w->J, st)))
+        return rc;
+    if (!status) return 0;
+    if ((rc = zero_async(status, sizeof(int32_t), st))) return rc;
+    return finite_check(out, (long)B * T * w->J, status, st);
 }
 
 // sd_sampler_route for a shared-context call: the tuned kernels' size limit counts contexts (B / draws)
@@ -3694,6 +3871,20 @@ extern "C" int sd_ddim_slew_step(const float *eps, const float *x, float *x_prev
     const HoldArgs hold{hold_x0, nullptr, hold_mask};
     return ddim_slew_step(eps, x, x_prev, hist, coef4, w, LimitArgs{lo, hi, reproject ? 1 : 0}, SlewArgs{v, start}, hold_mask ? &hold : nullptr, B, T, J,
                           (hipStream_t)stream);
+}
+
+// sd_ddim_slew_step with the acceleration scan (ddim_accel_step_kernel): a 32 floats, start2 (B, 32) floats or NULL.
+extern "C" int sd_ddim_accel_step(const float *eps, const float *x, float *x_prev, float *hist, const float *coef4, float w, const float *lo, const float *hi,
+                                  int reproject, const float *v, const float *start, const float *a, const float *start2, const float *hold_x0,
+                                  const int32_t *hold_mask, int B, int T, int J, void *stream) {
+    if (!eps || !x || !x_prev || !coef4 || !lo || !hi || !v || !a || B <= 0 || T <= 0 || J < 1 || J > 32 || (long)B * J > 0x7fffffffL)
+        return fail(SD_E_BADARG, "sd_ddim_accel_step: bad argument");
+    if ((hold_x0 == nullptr) != (hold_mask == nullptr)) return fail(SD_E_BADARG, "sd_ddim_accel_step: hold_x0 and hold_mask must be given together");
+    if (!hist && w != 0.f) return fail(SD_E_BADARG, "sd_ddim_accel_step: a history weight needs a history buffer");
+    if (hist && (hist == x || hist == x_prev || hist == eps)) return fail(SD_E_BADARG, "sd_ddim_accel_step: hist must alias neither eps, x nor x_prev");
+    const HoldArgs hold{hold_x0, nullptr, hold_mask};
+    return ddim_accel_step(eps, x, x_prev, hist, coef4, w, LimitArgs{lo, hi, reproject ? 1 : 0}, SlewArgs{v, start}, AccelArgs{a, start2},
+                           hold_mask ? &hold : nullptr, B, T, J, (hipStream_t)stream);
 }
 
 extern "C" int sd_ddim_step(const float *eps, const float *x, float *x_prev, float sqrt_a_t, float sqrt_1m_a_t,

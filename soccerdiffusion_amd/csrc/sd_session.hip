@@ -352,6 +352,44 @@ __global__ void session_anchor_kernel(float *anchor, const float *__restrict__ x
     anchor[((long)b * draws + g) * 32 + j] = x[((long)s * T + row) * J + j];
 }
 
+// ---- acceleration limits (sd_ddim_sample_accel's a, from radians per row^2 as published) ----------------------------------------------
+// One thread per slot.  a_n = (a_rad - margin) / std, rounded toward zero, with
+//   margin = 4 std hu(3 XS / std) + 4 hu(XS) + 4 hu(pi + R) + 4 hu(R),   XS = R + |pi - mean|,   hu = half_ulp
+// in fp64 (DESIGN.md 5.7.6 derives it): a row of the scan lies within a_n of 2 y1 - y2 up to the four roundings of accel_row (d, p,
+// p - a, p + a), each half an ulp of a result of magnitude <= 3 XS / std, since |x| <= XS / std inside the box; the commit multiplies by
+// std and adds up to three roundings per published value (x * std, + mean, - pi; |x std| <= XS, |x std + mean| <= R + pi,
+// |published| <= R), and a second difference takes three published values with weights 1, 2 and 1.  So the second difference of the
+// fp32 values the commit publishes is at most a_rad, evaluated exactly.  +inf stays +inf; an a_rad not above its margin gives 0 (the
+// host refuses it before the launch).  Slots >= J: +inf.
+__global__ void session_accel_kernel(float *a_n, SessionSlew rad, const float *__restrict__ mean, const float *__restrict__ stdv, int J) {
+    const int j = threadIdx.x;
+    if (j >= 32) return;
+    float out = INFINITY;
+    if (j < J && rad.v[j] < INFINITY) {
+        const double s = (double)stdv[j], R = (double)rad.r[j], XS = R + fabs(M_PI - (double)mean[j]);
+        const double margin = 4.0 * s * half_ulp(3.0 * XS / s) + 4.0 * half_ulp(XS) + 4.0 * half_ulp(M_PI + R) + 4.0 * half_ulp(R);
+        const double a = ((double)rad.v[j] - margin) / s;
+        out = a > 0.0 ? (float)a : 0.f;
+        if ((double)out > a) out = nextafterf(out, 0.f);
+    }
+    a_n[j] = out;
+}
+// session_anchor_kernel with a second destination, for a scan whose state is two rows: per robot b = robots[s] (NULL: s), draw g and
+// joint j < J,  anchor2 <- row >= 1 ? x[s][row - 1][j] : the old anchor;  anchor <- x[s][row][j]  (row = advance - 1).  One thread reads
+// the old anchor before it writes either destination, and no other thread touches its two slots.  Slots [J, 32) keep their NaN.
+__global__ void session_anchor2_kernel(float *anchor, float *anchor2, const float *__restrict__ x, const int32_t *__restrict__ robots, int S, int B, int T,
+                                       int J, int row, int draws) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * draws * J) return;
+    const int j = i % J, g = (i / J) % draws, s = i / (J * draws);
+    const int b = robot_of(robots, s, B);
+    if (b < 0) return;
+    const long at = ((long)b * draws + g) * 32 + j;
+    const float old = anchor[at];
+    anchor2[at] = row >= 1 ? x[((long)s * T + row - 1) * J + j] : old;
+    anchor[at] = x[((long)s * T + row) * J + j];
+}
+
 // The tick's mask: mask[s * draws + g][t] = held[b] | (t < pin_rows[b] ? all J bits : 0), b = robot s of the launch (robots NULL: s);
 // pin_rows NULL: a session without carried rows.  n = S * draws * T words.
 __global__ __launch_bounds__(THREADS) void session_hold_mask_kernel(int32_t *__restrict__ mask, const int32_t *__restrict__ held,
@@ -578,6 +616,31 @@ extern "C" int sd_session_anchor(float *anchor, const float *x, const int32_t *r
     const int n = S * draws * J;
     SD_LAUNCH(ss::session_anchor_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, anchor, x, robots, S, B, T, J, row, draws);
     SD_CHECK_LAUNCH("session_anchor_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_accel(float *a_n, const float *a_rad, const float *bound_rad, const float *mean, const float *stdv, int J, void *stream) {
+    if (!a_n || !a_rad || !bound_rad || !mean || !stdv || J < 1 || J > 32)
+        return fail(SD_E_BADARG, "sd_session_accel: a_n, a_rad, bound_rad, mean and std must be given; 1 <= J <= 32");
+    ss::SessionSlew rad{};
+    for (int j = 0; j < J; ++j) {
+        if (!(a_rad[j] >= 0.f) || !(bound_rad[j] >= 0.f) || bound_rad[j] == INFINITY)
+            return fail(SD_E_BADARG, "sd_session_accel: a_rad[j] >= 0 and a finite bound_rad[j] >= 0, no NaN");
+        rad.v[j] = a_rad[j];
+        rad.r[j] = bound_rad[j];
+    }
+    SD_LAUNCH(ss::session_accel_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a_n, rad, mean, stdv, J);
+    SD_CHECK_LAUNCH("session_accel_kernel");
+    return 0;
+}
+
+extern "C" int sd_session_anchor2(float *anchor, float *anchor2, const float *x, const int32_t *robots, int S, int B, int T, int J, int row, int draws,
+                                  void *stream) {
+    if (!anchor || !anchor2 || anchor == anchor2 || !x || S < 1 || B < 1 || S > B || T < 1 || J < 1 || J > 32 || row < 0 || row >= T || draws < 1)
+        return fail(SD_E_BADARG, "sd_session_anchor2: bad argument");
+    const int n = S * draws * J;
+    SD_LAUNCH(ss::session_anchor2_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, anchor, anchor2, x, robots, S, B, T, J, row, draws);
+    SD_CHECK_LAUNCH("session_anchor2_kernel");
     return 0;
 }
 

@@ -1475,6 +1475,8 @@ static __device__ __forceinline__ float ddim_update(float x, float e, const f32x
 // same S and M planes with the same two top-level barriers; sl.v NULL - a branch on the kernel argument, uniform over the workgroup -
 // skips the exchange, the scan and both barriers, and the storing lane clamps with limit_update's two compares.  hold.mask NULL: nothing
 // held, hold.x0 never read; hold.noise, lim.reproject and the multistep arguments are never read.
+// PIN == 7, ACCEL: the acceleration twin (AccelArgs, sd_common.h; sd_ddim_sample_accel) - the slew twin, phase for phase, whose scan lane
+// carries two rows of state and calls accel_row; it requests a[j] and start2[b][j] beside its other four scalars, ahead of both barriers.
 template <bool WIDE = false, int PIN = 0, bool ROLL = false, bool DRAWS = false>
 static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, f32x4 roll_coef = f32x4{0.f, 0.f, 0.f, 0.f},
                                                  int roll_step = 0, int roll_wave = 0, int draws = 1, const HoldArgs &hold = HoldArgs{},
@@ -1483,7 +1485,8 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
     constexpr bool HOLD = PIN == 2;
     constexpr bool MS = PIN == 3;
     constexpr bool LIM = PIN == 4;
-    constexpr bool SLEW = PIN == 5;
+    constexpr bool ACCEL = PIN == 7;           // the acceleration twin: the slew twin with accel_row in phase 3
+    constexpr bool SLEW = PIN == 5 || ACCEL;
     constexpr bool DIRECT = PIN == 6;
     static_assert(!(SLEW || DIRECT) || TMAX * 128 + TMAX * 4 <= LDS_STAT - LDS_Q, "the slew twin's S and M planes fit the Q | K region");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1514,12 +1517,30 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
         __builtin_amdgcn_sched_barrier(0);
         const float *xr = a.x + traj * (long)a.T * J;
         const int tid = ROLL ? 64 * c.w + c.lane : (int)threadIdx.x;   // (rollout: the thread index is not kept around the step loop)
+        if constexpr (ACCEL) {   // one thread per token: its row's scale (x_token_scale: 1 in range) and the reciprocal -> the X panel, which is
+            float *xs = reinterpret_cast<float *>(c.smem + LDS_X);   // dead here: floats [TMAX, TMAX + T) and [0, T); one barrier for all waves
+            for (int tok = tid; tok < a.T; tok += NTHREADS) xs[TMAX + tok] = x_token_scale(xr + tok * J, J, xs + tok);
+            __syncthreads();
+        }
         if (J & 3) {
             // any joint count <= 32 (the reference's database has 22: soccer_diffusion/dataset/models.py:222-247): one thread per (token,
             // 8-joint chunk), scalar loads (rows are not 16-byte aligned), joints >= J zero
             for (int i = tid; i < a.T * 4; i += NTHREADS) {
                 const int tok = i >> 2, chunk = i & 3;
                 f16x8 h8, l8;
+                if constexpr (ACCEL) {   // the row times its token's scale
+                    const float xs = reinterpret_cast<const float *>(c.smem + LDS_X)[TMAX + tok];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = 8 * chunk + e;
+                        const float v = j < J ? xr[tok * J + j] * XSC * xs : 0.f;
+                        h8[e] = (f16)v;
+                        l8[e] = (f16)(v - (float)h8[e]);
+                    }
+                    *reinterpret_cast<f16x8 *>(Qb + q_off(tok, chunk)) = h8;
+                    *reinterpret_cast<f16x8 *>(Qb + q_off(tok, chunk | 4)) = l8;
+                    continue;
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int j = 8 * chunk + e;
@@ -1536,7 +1557,12 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
             const f32x4 v = *reinterpret_cast<const f32x4 *>(xr + 4 * i) * XSC;
             const int tok = (4 * i) / J, j0 = 4 * i - tok * J;     // 4 consecutive joints of one token
             const int chunk = j0 >> 3;
-            split_store(Qb + q_off(tok, chunk) + 2 * (j0 & 7), Qb + q_off(tok, chunk | 4) + 2 * (j0 & 7), v);
+            if constexpr (ACCEL) {   // the row times its token's scale
+                const float xs = reinterpret_cast<const float *>(c.smem + LDS_X)[TMAX + tok];
+                split_store(Qb + q_off(tok, chunk) + 2 * (j0 & 7), Qb + q_off(tok, chunk | 4) + 2 * (j0 & 7), v * xs);
+            } else {
+                split_store(Qb + q_off(tok, chunk) + 2 * (j0 & 7), Qb + q_off(tok, chunk | 4) + 2 * (j0 & 7), v);
+            }
             if (j0 + 4 >= J) {   // this thread also zeroes k = J .. 31 of its token (the weights there are zero; LDS garbage might be NaN)
                 const f16x4 z4 = {0, 0, 0, 0};
                 for (int k = J; k < 32; k += 4) {
@@ -1554,6 +1580,10 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
             for (int tt = 0; tt < NTT; ++tt) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 mma3<S_EMB>(acc, ah, al, lds16(Qb + q_at(c, tt, 0, 0)), lds16(Qb + q_at(c, tt, 1, 0)));
+                if constexpr (ACCEL) {   // the token's scale taken back (a power of two: exact; 1 in range)
+                    H[n][tt] = acc * (c_e * reinterpret_cast<const float *>(c.smem + LDS_X)[tok_of(c, tt)]) + (be[n] + pe4[n][tt]);
+                    continue;
+                }
                 H[n][tt] = acc * c_e + (be[n] + pe4[n][tt]);
             }
         }
@@ -1655,6 +1685,16 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
                 scan_lo = lim.lo[c.lane];
                 scan_hi = lim.hi[c.lane];
                 if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+            }
+        }
+        // ACCEL: the scan lane's other two scalars, requested where it requests those four.  They live in lo4[0][ACC_A] (a[j]) and lo4[0][ACC_Y2] (row
+        // -2, then the row before y), which no slew twin uses - the box is the scan lane's - so that no other twin's code gains a declaration
+        if constexpr (ACCEL) {
+            lo4[0][ACC_Y2] = __builtin_nanf("");
+            if (c.w == 0 && c.lane < J) {
+                const AccelArgs &ac = accel_of(sl);   // (ACCEL: sl is the SlewAccelArgs of the kernel below)
+                lo4[0][ACC_A] = ac.a[c.lane];
+                if (ac.start2) lo4[0][ACC_Y2] = ac.start2[traj * 32 + c.lane];
             }
         }
         if constexpr (DIRECT) {   // the mask word; the storing lane's limits (no scan) or the scan lane's scalars, as above
@@ -1855,6 +1895,12 @@ static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArg
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
                         if (t0 + k >= a.T) continue;
+                        if constexpr (ACCEL) {   // two rows of state: y is y1, lo4[0][ACC_Y2] is y2 (sd_common.h: ACC_A, ACC_Y2)
+                            const float z = accel_row(q[k], y, lo4[0][ACC_Y2], lo4[0][ACC_A], v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);
+                            lo4[0][ACC_Y2] = y;
+                            S[(t0 + k) * 32 + j] = y = z;
+                            continue;
+                        }
                         y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
                         S[(t0 + k) * 32 + j] = y;
                     }
@@ -2155,6 +2201,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void traj_step_slew_kernel(StepArgs a,
 template <int NTT>
 __global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_slew_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, int draws) {
     TJ<NTT, true>::template step_body<true, 5, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, sl);
+}
+// The acceleration twins (sd_ddim_sample_accel; instantiated in sd_traj_acc.hip): the slew twins with accel_row (AccelArgs, sd_common.h) in
+// the scan - a state of two rows instead of one.  The S and M planes, both barriers and LDS_BYTES are the slew twins'.
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_accel_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl, AccelArgs ac,
+                                                                      int draws) {
+    TJ<NTT, true>::template step_body<false, 7, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, SlewAccelArgs{sl, ac});
+}
+template <int NTT>
+__global__ __launch_bounds__(NTHREADS, 2) void traj_step_wide_accel_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl,
+                                                                           AccelArgs ac, int draws) {
+    TJ<NTT, true>::template step_body<true, 7, false, true>(a, PinArgs{}, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, draws, hold, ms, lim, SlewAccelArgs{sl, ac});
 }
 // The direct twins (sd_direct_sample; instantiated in sd_traj_direct.hip): the slew twins for a network whose output is x0 (DirectArgs) -
 // no coefficients, no update, no history; x is only read, the projected x0 goes to dr.out.  One kernel per tile count serves plain, held,

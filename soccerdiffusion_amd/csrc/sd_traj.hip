@@ -71,6 +71,9 @@ TrajStepLimFn traj_step_lim_fn(int ntt, bool wide);
 // sd_traj_slew.hip: the slew instantiations (the limits', plus the scan over the rows behind two workgroup barriers: SlewArgs)
 typedef void (*TrajStepSlewFn)(tj::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, int);
 TrajStepSlewFn traj_step_slew_fn(int ntt, bool wide);
+// sd_traj_acc.hip: the acceleration instantiations (the slew twins with accel_row in the scan: AccelArgs)
+typedef void (*TrajStepAccelFn)(tj::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, AccelArgs, int);
+TrajStepAccelFn traj_step_accel_fn(int ntt, bool wide);
 // sd_traj_direct.hip: the direct instantiations (the network's output is x0: the slew twins' epilogue without coefficients, update or history)
 typedef void (*TrajStepDirectFn)(tj::StepArgs, HoldArgs, LimitArgs, SlewArgs, DirectArgs, int);
 TrajStepDirectFn traj_step_direct_fn(int ntt, bool wide);
@@ -359,7 +362,8 @@ static bool traj_groups_ok(const StepReq &r) { return r.draws >= 1 && r.B > 0 &&
 
 // one denoiser step + DDIM update in ONE launch: the plain kernel, its pinned twin, or - draws > 1 - the shared-context one, which takes the pin
 // as a runtime option; r.hold: the hold twin (sd_traj_hold.hip), whatever the group size; r.ms: the multistep twin (sd_traj_ms.hip);
-// r.lim: the limits twin (sd_traj_lim.hip); r.slew: the slew twin (sd_traj_slew.hip); r.direct: the direct twin (sd_traj_direct.hip)
+// r.lim: the limits twin (sd_traj_lim.hip); r.slew: the slew twin (sd_traj_slew.hip); r.direct: the direct twin (sd_traj_direct.hip);
+// r.accel: the acceleration twin (sd_traj_acc.hip)
 int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, hipStream_t st, int nkt, bool precise) {
     const int ntt = (r.T + 15) / 16;
     const int variant = nkt > 1 ? 2 : (precise ? 1 : 0);
@@ -384,7 +388,15 @@ int traj_step(const sd_denoiser_weights *w, const TrajWs &s, const StepReq &r, h
         return fail(SD_E_BADARG, "traj_step_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
     if (r.slew && (!r.lim || !r.slew->v || w->J > 32))
         return fail(SD_E_BADARG, "traj_step_slew_kernel: slew limits need v, the limits arguments (which may all be infinite) and J <= 32");
+    if (r.accel && (!r.slew || !r.accel->a))
+        return fail(SD_E_BADARG, "traj_step_accel_kernel: acceleration limits need a and the slew arguments (whose v may all be infinite)");
     const tj::StepArgs a = traj_step_args(w, s, r, r.coef, nkt);
+    if (r.accel) {   // the slew call with two rows of state in the scan
+        static DevFlag accel_attr_set[2][8];   // [one key tile | wide][ntt]
+        return launch_step_kernel(traj_step_accel_fn(ntt, variant == 2), "traj_step_accel_kernel", accel_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B,
+                                  tj::NTHREADS, tj::LDS_BYTES, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, *r.lim, *r.slew, *r.accel,
+                                  r.draws);
+    }
     if (r.slew) {   // the limits call plus the scan over the rows
         static DevFlag slew_attr_set[2][8];   // [one key tile | wide][ntt]
         return launch_step_kernel(traj_step_slew_fn(ntt, variant == 2), "traj_step_slew_kernel", slew_attr_set[variant == 2][ntt], tj::LDS_BYTES, r.B, tj::NTHREADS,

@@ -833,6 +833,8 @@ struct TG {
     // coefficient, no update, no history; x is only read, the prediction goes to eps_out and the projected x0c to dr.out.  The same four
     // phases on the same planes; sl.v NULL (uniform over the workgroup) skips the exchange, the scan and both barriers, and the storing
     // lane clamps.  hold.mask NULL: nothing held.
+    // PIN == 7, ACCEL: the acceleration twin (AccelArgs, sd_common.h; sd_ddim_sample_accel) - the slew twin, phase for phase, whose scan
+    // lane carries two rows of state and calls accel_row; a[j] and start2[b][j] are requested beside its other four scalars.
     template <int PIN = 0, bool DRAWS = false>
     static __device__ __forceinline__ void step_body(const StepArgs &a, const PinArgs &pin = PinArgs{}, int draws = 1, const HoldArgs &hold = HoldArgs{},
                                                      const MultistepArgs &ms = MultistepArgs{}, const LimitArgs &lim = LimitArgs{},
@@ -840,7 +842,8 @@ struct TG {
         constexpr bool HOLD = PIN == 2;
         constexpr bool MS = PIN == 3;
         constexpr bool LIM = PIN == 4;
-        constexpr bool SLEW = PIN == 5;
+        constexpr bool ACCEL = PIN == 7;           // the acceleration twin: the slew twin with accel_row in phase 3
+        constexpr bool SLEW = PIN == 5 || ACCEL;
         constexpr bool DIRECT = PIN == 6;
         static_assert(!(SLEW || DIRECT) || 128 + 4 <= VROW, "the slew twin's S and M planes fit the K / V buffer");
         extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -854,9 +857,27 @@ struct TG {
         {
             char *Eb = c.smem + c.oK;
             const float *xr = a.x + traj * (long)a.T * J;
+            if constexpr (ACCEL) {   // one thread per token: its row's scale (x_token_scale: 1 in range) and the reciprocal -> the X panel, which
+                float *xs = reinterpret_cast<float *>(c.smem);   // is dead here: floats [T, 2 T) and [0, T); one barrier for all waves
+                for (int tok = threadIdx.x; tok < a.T; tok += NTHREADS) xs[a.T + tok] = x_token_scale(xr + tok * J, J, xs + tok);
+                __syncthreads();
+            }
             for (int i = threadIdx.x; i < a.T * 4; i += NTHREADS) {
                 const int tok = i >> 2, chunk = i & 3;
                 f16x8 h8, l8;
+                if constexpr (ACCEL) {   // the row times its token's scale
+                    const float xs = reinterpret_cast<const float *>(c.smem)[a.T + tok];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = 8 * chunk + e;
+                        const float v = j < J ? xr[tok * J + j] * xs : 0.f;
+                        h8[e] = (f16)v;
+                        l8[e] = (f16)(v - (float)h8[e]);
+                    }
+                    *reinterpret_cast<f16x8 *>(Eb + e_off(tok, chunk)) = h8;
+                    *reinterpret_cast<f16x8 *>(Eb + e_off(tok, chunk | 4)) = l8;
+                    continue;
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int j = 8 * chunk + e;
@@ -880,6 +901,10 @@ struct TG {
                     const int tok = tok_of(c, tt);
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                     mma3(acc, ah, al, lds16(Eb + e_off(tok, c.g)), lds16(Eb + e_off(tok, 4 | c.g)));
+                    if constexpr (ACCEL) {   // the token's scale taken back (a power of two: exact; 1 in range)
+                        H[aa][tt] = acc * (c_e * reinterpret_cast<const float *>(c.smem)[tok]) + (be + *reinterpret_cast<const f32x4 *>(a.pe + (long)tok * D + 16 * nt + 4 * c.g));
+                        continue;
+                    }
                     H[aa][tt] = acc * c_e + (be + *reinterpret_cast<const f32x4 *>(a.pe + (long)tok * D + 16 * nt + 4 * c.g));
                 }
             }
@@ -970,6 +995,16 @@ struct TG {
                     scan_lo = lim.lo[c.lane];
                     scan_hi = lim.hi[c.lane];
                     if (sl.start) scan_y = sl.start[traj * 32 + c.lane];
+                }
+            }
+            // ACCEL: the scan lane's other two scalars, requested where it requests those four.  They live in lo4[0][ACC_A] (a[j]) and lo4[0][ACC_Y2] (row
+            // -2, then the row before y), which no slew twin uses - the box is the scan lane's - so that no other twin's code gains a declaration
+            if constexpr (ACCEL) {
+                lo4[0][ACC_Y2] = __builtin_nanf("");
+                if (c.w == 0 && c.lane < J) {
+                    const AccelArgs &ac = accel_of(sl);   // (ACCEL: sl is the SlewAccelArgs of the kernel below)
+                    lo4[0][ACC_A] = ac.a[c.lane];
+                    if (ac.start2) lo4[0][ACC_Y2] = ac.start2[traj * 32 + c.lane];
                 }
             }
             if constexpr (DIRECT) {   // the mask word; the storing lane's limits (no scan) or the scan lane's scalars, as above
@@ -1133,6 +1168,12 @@ struct TG {
 #pragma unroll
                         for (int k = 0; k < 16; ++k) {
                             if (t0 + k >= a.T) continue;
+                            if constexpr (ACCEL) {   // two rows of state: y is y1, lo4[0][ACC_Y2] is y2 (sd_common.h: ACC_A, ACC_Y2)
+                                const float z = accel_row(q[k], y, lo4[0][ACC_Y2], lo4[0][ACC_A], v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);
+                                lo4[0][ACC_Y2] = y;
+                                S[(t0 + k) * 32 + j] = y = z;
+                                continue;
+                            }
                             y = slew_row(q[k], y, v, lo, hi, ((mw[k] >> j) & 1u) != 0u, q[k]);   // (a held element's S entry is the hold's value already)
                             S[(t0 + k) * 32 + j] = y;
                         }
@@ -1269,6 +1310,13 @@ __global__ __launch_bounds__(NTHREADS) void traj_step_generic_direct_kernel(Step
     TG<D, NTT>::template step_body<6, true>(a, PinArgs{}, draws, hold, MultistepArgs{}, lim, sl, dr);
 }
 
+// the acceleration twin (sd_ddim_sample_accel): the slew twin with accel_row in the scan (AccelArgs) - two rows of state instead of one
+template <int D, int NTT>
+__global__ __launch_bounds__(NTHREADS) void traj_step_generic_accel_kernel(StepArgs a, HoldArgs hold, MultistepArgs ms, LimitArgs lim, SlewArgs sl,
+                                                                           AccelArgs ac, int draws) {
+    TG<D, NTT>::template step_body<7, true>(a, PinArgs{}, draws, hold, ms, lim, SlewAccelArgs{sl, ac});
+}
+
 }   // namespace tg
 
 // ======================================================================================
@@ -1358,6 +1406,10 @@ StepDirectFn step_direct_fn(int d, int ntt) {
 }
 StepDrawsFn step_draws_fn(int d, int ntt) {
     return by_d_ntt(d, ntt, [](auto D, auto n) -> StepDrawsFn { return tg::traj_step_generic_draws_kernel<decltype(D)::value, decltype(n)::value>; });
+}
+typedef void (*StepAccelFn)(tg::StepArgs, HoldArgs, MultistepArgs, LimitArgs, SlewArgs, AccelArgs, int);
+StepAccelFn step_accel_fn(int d, int ntt) {
+    return by_d_ntt(d, ntt, [](auto D, auto n) -> StepAccelFn { return tg::traj_step_generic_accel_kernel<decltype(D)::value, decltype(n)::value>; });
 }
 
 }   // namespace
@@ -1481,6 +1533,8 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
         return fail(SD_E_BADARG, "traj_step_generic_lim_kernel: limits need lo and hi and the multistep arguments (a history buffer wherever w != 0)");
     if (!r.direct && r.slew && (!r.lim || !r.slew->v || w->J > 32))
         return fail(SD_E_BADARG, "traj_step_generic_slew_kernel: slew limits need v, the limits arguments (which may all be infinite) and J <= 32");
+    if (r.accel && (r.direct || !r.slew || !r.accel->a))
+        return fail(SD_E_BADARG, "traj_step_generic_accel_kernel: acceleration limits need a and the slew arguments (whose v may all be infinite), and exclude the direct twin");
     tg::StepArgs a{};
     a.x = r.x;
     a.eps_out = r.eps;
@@ -1518,6 +1572,11 @@ int trajg_step(const sd_denoiser_weights *w, float *gws, const StepReq &r, hipSt
         return launch_step_kernel(step_direct_fn(d, ntt), "traj_step_generic_direct_kernel", direct_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
                                   tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.lim,
                                   r.slew ? *r.slew : SlewArgs{nullptr, nullptr}, *r.direct, r.draws);
+    }
+    if (r.accel) {   // the acceleration twin: the slew twin with two rows of state in the scan
+        static DevFlag accel_attr_set[3][8];   // [hidden_dim][ntt]
+        return launch_step_kernel(step_accel_fn(d, ntt), "traj_step_generic_accel_kernel", accel_attr_set[d == 128 ? 0 : d == 256 ? 1 : 2][ntt], MAX_LDS, r.B,
+                                  tg::NTHREADS, lds, st, a, r.hold ? *r.hold : HoldArgs{nullptr, nullptr, nullptr}, *r.ms, *r.lim, *r.slew, *r.accel, r.draws);
     }
     if (r.slew) {   // the slew twin: the limits twin plus the scan over the rows
         static DevFlag slew_attr_set[3][8];   // [hidden_dim][ntt]

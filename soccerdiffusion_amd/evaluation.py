@@ -119,6 +119,37 @@ def normalised_slew(slew, mean: torch.Tensor, std: torch.Tensor, limits=None) ->
     return torch.from_numpy(out)
 
 
+def normalised_accel(accel, mean: torch.Tensor, std: torch.Tensor, limits=None) -> torch.Tensor:
+    """``accel`` in the space of the trajectories (x * std + mean; (J,) floats, one number or ``{joint: a}`` as ``ops.joint_accel`` takes
+    them: the largest second difference over three consecutive rows) as a (J,) fp32 host tensor in the sampler's normalised space:
+    (a - margin) / std per joint in fp64, rounded toward zero, with ``ops.denormalised_accel_margin``, so that the second
+    difference of the DENORMALISED trajectories is at most a, evaluated exactly, wherever the acceleration limit is the one that binds.
+    The margin needs a bound on |x std + mean|, as ``normalised_slew``'s does, and takes it the same way.  +inf stays +inf; an a not
+    above its margin raises ValueError."""
+    from . import ops
+
+    mean, std = mean.detach().reshape(-1).cpu().float().numpy(), std.detach().reshape(-1).cpu().float().numpy()
+    J = std.size
+    if not (std > 0).all():
+        raise ValueError("accel: the normaliser's std must be positive")
+    a = ops._accel_host(accel, J)[:J].astype(np.float64)
+    bound = np.full(J, 2 * math.pi)
+    if limits is not None:
+        lo, hi = (np.abs(b[:J].astype(np.float64)) for b in ops._limits_host(limits, J))
+        both = np.isfinite(lo) & np.isfinite(hi)
+        bound = np.where(both, np.maximum(lo, hi), bound)
+    margin = ops.denormalised_accel_margin(bound, mean, std)
+    finite = np.isfinite(a)
+    if (finite & ~(a > margin)).any():
+        j = int(np.argmax(finite & ~(a > margin)))
+        raise ValueError(f"accel: a[{j}] = {a[j]} is not above the margin {margin[j]:.3e} of the fp32 arithmetic")
+    exact = np.where(finite, (np.where(finite, a, 0.0) - margin) / std.astype(np.float64), np.inf)
+    out = exact.astype(np.float32)
+    over = out.astype(np.float64) > exact
+    out[over] = np.nextafter(out[over], np.float32(0))
+    return torch.from_numpy(out)
+
+
 def assemble_report(parts: Sequence[dict], *, timesteps: Optional[Sequence[int]], steps: int, draws: int, max_mode: int, angular: bool,
                     solver: str = "ddim") -> dict:
     """The report from the per-batch marginals, in fp64 on the host.  A part holds, for its C windows: ``err`` (C, G), ``row_err`` (C, G, T),
@@ -158,7 +189,7 @@ def _has_context(model) -> bool:
 @torch.no_grad()
 def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int = 8, batch: int = 64, seed: int = 0, max_mode: int = 3,
              angular: bool = True, timesteps: Optional[Sequence[int]] = None, distilled: bool = False, keep: Optional[list] = None, solver: str = "ddim",
-             limits=None, reproject: bool = False, slew=None) -> dict:
+             limits=None, reproject: bool = False, slew=None, accel=None) -> dict:
     """The report (a plain dict of Python floats, ints and lists) of ``model`` on the windows ``idx`` of ``source`` (``cli.DataSource``), in
     batches of ``batch`` windows from ``source.batch``.  The model must be in ``eval()``.  Per batch: the context is encoded once; the loss
     grid runs at ``timesteps`` (default ``default_timesteps(grid)``); ``draws`` = G trajectories per window are sampled with ``steps`` DDIM
@@ -172,6 +203,11 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     largest |step| between consecutive rows of the sampled trajectories, all draws, in the space of the targets (``ops.max_step``) - the
     number from which a slew limit is chosen, and the one that shows it held: with ``--slew`` it is <= v, as long as the denormalised
     values stay inside the bound the margin was derived for (``normalised_slew``);
+    ``accel``: the draws are sampled under acceleration limits given in the same space (``normalised_accel``, ``model.sample(accel=...)``);
+    the report then gains an ``accel`` entry.  With or without it the report carries ``max_accel_by_joint``: the largest second
+    difference over three consecutive rows of the sampled trajectories, all draws, in the space of the targets (``ops.max_accel``) - the
+    number from which an acceleration limit is chosen (where the box or the slew limit wins at a row it can exceed ``accel``: there is
+    no braking ahead of the box);
     ``ops.select_medoid`` and ``ops.trajectory_errors`` follow.  ``distilled``: the model is a one-step
     student - one forward at t = 0 on G start noises through the shared loop form; it predicts no noise, so its ``val_loss*`` are None;
     under ``limits`` / ``slew`` its output, which is x0, is projected inside the launch (``model.sample_direct``) and ``max_step_by_joint``
@@ -201,6 +237,9 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     if slew is not None:
         slew_given = [None if math.isinf(a) else a for a in ops._slew_host(slew, model.mean.numel())[: model.mean.numel()].tolist()]
         slew = normalised_slew(slew, model.mean, model.std, limits_given)
+    if accel is not None:
+        accel_given = [None if math.isinf(a) else a for a in ops._accel_host(accel, model.mean.numel())[: model.mean.numel()].tolist()]
+        accel = normalised_accel(accel, model.mean, model.std, limits_given)
     idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
     if idx.numel() == 0:
         raise ValueError("evaluate: no windows to evaluate")
@@ -209,7 +248,7 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
     t_dev = torch.tensor(ts, dtype=torch.int64, device=device)
     acp = ops.alphas_cumprod().to(device)
     K, d = len(ts), model.hidden_dim
-    parts, steps_seen = [], []
+    parts, steps_seen, accels_seen = [], [], []
     for at in range(0, idx.numel(), batch):
         data = source.batch(idx[at : at + batch])
         target = data["joint_command"].to(torch.float32).contiguous()
@@ -224,14 +263,15 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
             x0n = ops.normalize(target, model.mean, model.std)
             part["loss"], eps = ops.noise_loss_grid(model, ctx, x0n, noise, t_dev, acp=acp, return_eps=True)
         x_T = torch.randn(Cn * G, T, J, device=device, generator=gen)
-        if distilled and limits is None and slew is None:
+        if distilled and limits is None and slew is None and accel is None:
             x = model.forward_with_context(ctx, x_T, torch.zeros(Cn * G, device=device), draws=G)
         elif distilled:   # the student's output is x0: limits and slew project it inside the same launch (model.sample_direct)
-            x = model.sample_direct(ctx, x_T, limits=limits, slew=slew, draws=G, max_mode=max_mode)
+            x = model.sample_direct(ctx, x_T, limits=limits, slew=slew, draws=G, max_mode=max_mode, accel=accel)
         else:
-            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject, slew=slew)
+            x = model.sample(ctx, x_T, steps, max_mode=max_mode, draws=G, solver=solver, limits=limits, reproject=reproject, slew=slew, accel=accel)
         x = x.contiguous()
         steps_seen.append(ops.max_step(x, model.mean, model.std).amax(0).cpu())
+        accels_seen.append(ops.max_accel(x, model.mean, model.std).amax(0).cpu())
         part["medoid"], chosen = ops.select_medoid(x, G)
         part["err"], part["row_err"], part["joint_err"], part["best"] = ops.trajectory_errors(x, target, model.mean, model.std, draws=G, angular=angular)
         # the distance of every draw to the medoid, in radians: the same kernel against the denormalised medoid, nothing to wrap
@@ -242,8 +282,11 @@ def evaluate(model, source, idx, *, steps: int = 30, draws: int = 1, grid: int =
         parts.append({k: (None if v is None else v.cpu()) for k, v in part.items()})
     report = assemble_report(parts, timesteps=ts, steps=steps, draws=G, max_mode=max_mode, angular=angular, solver=solver)
     report["max_step_by_joint"] = [float(v) for v in torch.stack(steps_seen).amax(0)]
+    report["max_accel_by_joint"] = [float(v) for v in torch.stack(accels_seen).amax(0)]
     if limits is not None:
         report.update(limits=given, reproject=bool(reproject))
     if slew is not None:
         report["slew"] = slew_given
+    if accel is not None:
+        report["accel"] = accel_given
     return report

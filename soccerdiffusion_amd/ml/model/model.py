@@ -206,7 +206,7 @@ class End2EndDiffusionTransformer(nn.Module):
     def sample(self, context: Sequence[torch.Tensor], x_T: torch.Tensor, num_inference_steps: int,
                return_trace: bool = False, alphas_cumprod: Optional[torch.Tensor] = None, use_graph: bool = False,
                with_dropout: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, solver: str = "ddim",
-               limits=None, reproject: bool = False, slew=None):
+               limits=None, reproject: bool = False, slew=None, accel=None):
         """The reference's denoising loop (plot.py:122-131 / distill.py:179-189 / ros.py:301-310)
         as one native call: n x (denoiser forward + DDIM update) with the context K/V cached.
         ``use_graph`` replays the rollout from a hipGraph captured for this (B, T, M, n) shape.
@@ -235,7 +235,13 @@ class End2EndDiffusionTransformer(nn.Module):
         on the device: one capture serves every value) and ``return_trace``.  Not with ``with_dropout``; J <= 32.
         ``slew`` (``v`` or ``(v, start)``, ``ops.joint_slew``'s forms; normalised space): consecutive rows of the predicted clean
         trajectory are kept within ``v[j]`` of each other at every step (row 0 against ``start`` (B, J)), then clamped to ``limits``
-        (``ops.ddim_sample(slew=...)``).  It composes with what ``limits`` composes with."""
+        (``ops.ddim_sample(slew=...)``).  It composes with what ``limits`` composes with.
+        ``accel`` (``a`` or ``(a, start2)``, ``ops.joint_accel``'s forms; normalised space): the second difference of consecutive rows of
+        the predicted clean trajectory is kept within ``a[j]`` at every step (rows -1 and -2: ``slew``'s ``start`` and ``start2``), ahead
+        of the slew interval and the box (``ops.ddim_sample(accel=...)``, which states what this is not: no braking ahead of the box).  It
+        composes with what ``slew`` composes with."""
+        if accel is not None and with_dropout:
+            raise ValueError("sample: accel is a feature of the native rollout; with_dropout steps through forward_with_context")
         if slew is not None and with_dropout:
             raise ValueError("sample: slew is a feature of the native rollout; with_dropout steps through forward_with_context")
         if limits is not None and with_dropout:
@@ -277,19 +283,23 @@ class End2EndDiffusionTransformer(nn.Module):
             # the weights are read through pointers at replay (their addresses are the key); the step-token table is captured by value
             token = derived.source_key(self.step_encoding.token)
             key = (B, T, Mc, num_inference_steps, x_T.device, self.diffusion_action_generator._signature(), token, cap, pin is not None, draws, hold is not None, solver,
-                   limits is not None, bool(reproject), slew is not None)
+                   limits is not None, bool(reproject), slew is not None, accel is not None)
             cache = _model_cache(self, "graphs")
             if token is None or key not in cache:
                 cache.clear()  # one shape at a time: a graph pins its workspace
                 cache[key] = ops.GraphedSampler(packed, B, T, Mc, self.step_encoding.table(ts, x_T.device), coef, max_mode=cap,
                                                 pin=pin is not None, draws=draws, hold=hold is not None, multistep=msw, limits=limits is not None,
-                                                reproject=reproject, slew=slew is not None)
+                                                reproject=reproject, slew=slew is not None, accel=accel is not None)
             if limits is not None:
                 cache[key].set_limits(limits)
-            elif slew is not None:
+            elif slew is not None or accel is not None:
                 cache[key].set_limits({})
             if slew is not None:
                 cache[key].set_slew(slew)
+            elif accel is not None:
+                cache[key].set_slew({})
+            if accel is not None:
+                cache[key].set_accel(accel)
             out = cache[key](ctx, x_T, pin, hold)
             word = int(cache[key].status.item())
             if word == 0:
@@ -299,21 +309,22 @@ class End2EndDiffusionTransformer(nn.Module):
             # range guard tripped (ops.ddim_sample_guarded): fall through to the guarded eager path
         tokens = self.step_encoding.table(ts, x_T.device)
         return ops.ddim_sample_guarded(packed, ctx, tokens, coef, x_T.contiguous(), trace=return_trace, max_mode=max_mode, pin=pin, draws=draws, hold=hold, multistep=msw,
-                                       limits=limits, reproject=reproject, slew=slew)
+                                       limits=limits, reproject=reproject, slew=slew, accel=accel)
 
     @torch.no_grad()
     def sample_direct(self, context: Sequence[torch.Tensor], x_T: torch.Tensor, hold=None, limits=None, slew=None, draws: int = 1,
-                      raw: bool = False, max_mode: Optional[int] = None):
+                      raw: bool = False, max_mode: Optional[int] = None, accel=None):
         """A distilled one-step decoder's tick (ros.py:293-298) under ``sample``'s guarantees: ``forward_with_context(context, x_T,
         zeros)`` - whose output is the clean trajectory, not a noise prediction - plus the projection of ``sample``'s ``hold``, ``slew``
         and ``limits`` (same forms, normalised space), in ONE launch on the trajectory kernels (``ops.direct_sample``).  ``draws`` = G:
         the context tensors hold B / G observations; G start noises give G different trajectories.  ``raw=True`` also returns the
         unprojected prediction, which is ``forward_with_context``'s value bit for bit.  With nothing set the result is that value.
         There is no ``pin``, no ``solver`` and no ``reproject``: one step has no rows that could adapt to pinned ones, no history and
-        no eps to recompute.  The range guard is read back as in ``sample`` (``ops.direct_sample_guarded``)."""
+        no eps to recompute.  The range guard is read back as in ``sample`` (``ops.direct_sample_guarded``).  ``accel``: ``sample``'s
+        acceleration limits - then two launches, the plain direct launch and the projection (``ops.direct_sample``)."""
         ctx = torch.cat(list(context), dim=1).contiguous() if len(context) else None
         packed = self.diffusion_action_generator.packed()
         t0 = torch.zeros(1, dtype=torch.int64, device=x_T.device)
         token = ops.step_token(t0, self.step_encoding._freq, self.step_encoding.token.detach()).view(1, self.hidden_dim)
         return ops.direct_sample_guarded(packed, ctx, token, x_T.contiguous(), hold=hold, limits=limits, slew=slew, draws=draws, raw=raw,
-                                         max_mode=max_mode)
+                                         max_mode=max_mode, accel=accel)

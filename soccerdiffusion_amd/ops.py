@@ -350,6 +350,70 @@ def slew_step(eps: Tensor, x: Tensor, coef4, slew, limits=None, hist: Optional[T
     return out
 
 
+def _accel_host(a, J: int) -> np.ndarray:
+    """``a`` - (J,) floats, one number or ``{joint: a}`` - as the (32,) fp32 host array padded with +inf, validated as ``joint_slew``
+    validates ``v``: see ``joint_accel``."""
+    try:
+        return _slew_host(a, J)
+    except ValueError as e:
+        raise ValueError(str(e).replace("slew:", "accel:").replace("v[", "a[")) from None
+
+
+def joint_accel(a, J: Optional[int] = None, device=None) -> Tensor:
+    """Per-joint acceleration limits of ``ddim_sample(accel=...)`` as the kernels read them (``sd_ddim_sample_accel``): one (32,) fp32
+    array on ``device``, entries [J, 32) padded with +inf.  ``a[j] >= 0`` is the largest second difference of joint j over three
+    consecutive rows of the trajectory, in the sampler's normalised space; +inf: none.  ``a``: (J,) floats, one number for every joint, or
+    ``{joint: a}`` (every other joint unlimited).  ValueError for a NaN, a negative value, a wrong shape, a joint index outside
+    0 .. J - 1, or J > 32."""
+    if J is None or device is None:
+        raise ValueError("joint_accel: J and device must be given")
+    return torch.from_numpy(_accel_host(a, J)).to(device)
+
+
+def _accel_req(accel, B: int, J: int, device) -> tuple:
+    """``accel`` of a sampler call, validated: ``a`` or ``(a, start2)`` -> (a (32,) on the device, start2 (B, 32) on the device or None),
+    as ``_slew_req`` does it for ``(v, start)``; ``start2`` is the value two rows "before row 0" per trajectory (NaN: none)."""
+    pair = isinstance(accel, tuple) and len(accel) == 2 and (accel[1] is None or getattr(accel[1], "ndim", 0) >= 1)   # (a, start2), not two floats
+    a, start2 = accel if pair else (accel, None)
+    if J > 32:
+        raise ValueError(f"accel: the 32-float array describes at most 32 joints, got J = {J}")
+    if not _is_dev32(a, device):
+        a = joint_accel(a, J=J, device=device)
+    if start2 is not None and not _is_dev32(start2, device, B):
+        st = start2.detach() if isinstance(start2, Tensor) else torch.as_tensor(np.asarray(start2, dtype=np.float32))
+        if st.dim() != 2 or st.shape[0] != B or st.shape[1] not in (J, 32):
+            raise ValueError(f"accel start2: expected ({B}, {J}) or ({B}, 32) floats, got {tuple(st.shape)}")
+        start2 = torch.full((B, 32), float("nan"), dtype=torch.float32, device=device)
+        start2[:, :J] = st[:, :J].to(device=device, dtype=torch.float32)
+    return a, start2
+
+
+def accel_step(eps: Tensor, x: Tensor, coef4, accel, slew=None, limits=None, hist: Optional[Tensor] = None, w: float = 0.0,
+               reproject: bool = False, hold=None) -> Tensor:
+    """One step under per-joint acceleration limits for a caller that evaluates the denoiser itself (``sd_ddim_accel_step``):
+    ``slew_step`` with the scan of ``ddim_sample(accel=...)`` over the rows of every trajectory.  ``accel``: ``a`` or ``(a, start2)``;
+    ``slew`` (default: no slew limit and no anchor) and everything else as ``slew_step`` takes them."""
+    lib = _lib.load()
+    _req(eps, "eps"); _req(x, "x")
+    if x.dim() != 3 or eps.shape != x.shape or (hist is not None and hist.shape != x.shape):
+        raise ValueError("accel_step: eps, x and hist must be whole (B, T, J) samples of one shape")
+    if hist is not None:
+        _req(hist, "hist")
+    B, T, J = x.shape
+    a, start2 = _accel_req(accel, B, J, x.device)
+    v, start = _slew_req({} if slew is None else slew, B, J, x.device)
+    limits = _limits_req({} if limits is None else limits, J, x.device)
+    known, mask = (None, None) if hold is None else _hold_req(hold, B, T, J, x.device)
+    out = torch.empty_like(x)
+    c = np.ascontiguousarray([float(t) for t in coef4], dtype=np.float32)
+    if c.shape != (4,):
+        raise ValueError("accel_step: coef4 must hold 4 scalars")
+    check(lib.sd_ddim_accel_step(eps.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(hist), c.ctypes.data_as(_lib.c_float_p), float(w),
+                                 limits.lo.data_ptr(), limits.hi.data_ptr(), int(bool(reproject)), v.data_ptr(), _ptr(start), a.data_ptr(),
+                                 _ptr(start2), _ptr(known), _ptr(mask), B, T, J, _stream()), "sd_ddim_accel_step")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # weight descriptors
 # --------------------------------------------------------------------------------------
@@ -661,7 +725,7 @@ def _draws_req(draws, B: int, n_ctx: Optional[int]) -> int:
 
 def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x: Tensor, tr: Optional[Tensor],
                         et: Optional[Tensor], ws: Tensor, status: Optional[Tensor], max_mode: int, pin, draws: int, hold=None, multistep=None,
-                        limits=None, slew=None):
+                        limits=None, slew=None, accel=None):
     """The native rollout of ``ddim_sample`` and ``GraphedSampler`` on validated operands, x updated in place: always
     ``sd_ddim_sample_draws`` - with ``draws`` = 1 and NULL pin pointers it is ``sd_ddim_sample_eps``, with ``pin = (known, noise, rows)``
     ``sd_ddim_sample_pin``, launch for launch; ``hold = (known, noise, mask words)``: ``sd_ddim_sample_hold`` (never beside a pin).
@@ -670,8 +734,20 @@ def _ddim_sample_native(packed: "_Packed", ctx: Optional[Tensor], step_tokens: T
     ``limits = (lo, hi, reproject)`` (the (32,) device arrays of ``joint_limits``): ``sd_ddim_sample_limits``, with ``multistep`` and
     ``hold`` or without either (never beside a pin).
     ``slew = (v, start or None)`` (needs ``limits``, which may all be infinite): ``sd_ddim_sample_slew``.
+    ``accel = (a, start2 or None)`` (needs ``slew``, whose ``v`` may all be infinite): ``sd_ddim_sample_accel``.
     Returns x, or (x, trace?, eps_trace?) where those buffers were given."""
     B, T, _ = x.shape
+    if accel is not None:
+        msw, hist = multistep if multistep is not None else (None, None)
+        check(_lib.load().sd_ddim_sample_accel(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
+                                               x.data_ptr(), _ptr(tr), _ptr(et), ws.data_ptr(), B, T, 0 if ctx is None else ctx.shape[1],
+                                               len(coef), _ptr(status), int(max_mode), *[_ptr(t) for t in (hold or (None, None, None))], draws,
+                                               None if msw is None else msw.ctypes.data_as(_lib.c_float_p), _ptr(hist),
+                                               limits[0].data_ptr(), limits[1].data_ptr(), int(bool(limits[2])), slew[0].data_ptr(), _ptr(slew[1]),
+                                               accel[0].data_ptr(), _ptr(accel[1]), _stream()),
+              "sd_ddim_sample_accel")
+        out = (x,) + tuple(t for t in (tr, et) if t is not None)
+        return out if len(out) > 1 else x
     if slew is not None:
         msw, hist = multistep if multistep is not None else (None, None)
         check(_lib.load().sd_ddim_sample_slew(C.byref(packed.struct), _ptr(ctx), step_tokens.data_ptr(), coef.ctypes.data_as(_lib.c_float_p),
@@ -736,11 +812,15 @@ class GraphedSampler:
     folded into a mask as under ``multistep``.  ``slew=True`` captures the call under per-joint slew limits (``sd_ddim_sample_slew``) on a
     static (32,) array ``self.slew_v`` (all +inf at first) and a static (B, 32) array ``self.slew_start`` (all NaN at first), read on the
     device at every step: ``set_slew`` rewrites them in place.  It implies the limit arrays, which stay infinite unless ``set_limits`` is
-    called.  (One native call for all of them: ``_ddim_sample_native``.)"""
+    called.  ``accel=True`` captures the call under per-joint acceleration limits (``sd_ddim_sample_accel``) on a static (32,) array
+    ``self.accel_a`` (all +inf at first) and a static (B, 32) array ``self.accel_start2`` (all NaN at first): ``set_accel`` rewrites them
+    in place and keeps the capture.  It implies the slew and limit arrays.  (One native call for all of them: ``_ddim_sample_native``.)"""
 
     def __init__(self, packed: _Packed, B: int, T: int, Mc: int, step_tokens: Tensor, coef: np.ndarray, max_mode: int = -1, pin: bool = False,
-                 draws: int = 1, hold: bool = False, multistep=None, limits: bool = False, reproject: bool = False, slew: bool = False):
+                 draws: int = 1, hold: bool = False, multistep=None, limits: bool = False, reproject: bool = False, slew: bool = False,
+                 accel: bool = False):
         dev = step_tokens.device
+        slew = bool(slew) or bool(accel)
         limits = bool(limits) or bool(slew)
         if pin and hold:
             raise ValueError("GraphedSampler: pin and hold exclude each other - compose them through ops.hold_mask(rows=...)")
@@ -748,6 +828,8 @@ class GraphedSampler:
         self.limits, self.reproject = (joint_limits({}, J=packed.J, device=dev) if limits else None), bool(reproject)
         self.slew_v = joint_slew({}, J=packed.J, device=dev) if slew else None
         self.slew_start = torch.full((B, 32), float("nan"), dtype=torch.float32, device=dev) if slew else None
+        self.accel_a = joint_accel({}, J=packed.J, device=dev) if accel else None
+        self.accel_start2 = torch.full((B, 32), float("nan"), dtype=torch.float32, device=dev) if accel else None
         self.pin_as_hold = bool(pin) and (self.multistep is not None or self.limits is not None)
         if self.pin_as_hold:
             pin, hold = False, True
@@ -784,7 +866,20 @@ class GraphedSampler:
         _ddim_sample_native(self.packed, self.ctx, self.tokens, self.coef, self.x, None, None, self.ws, self.status, self.max_mode, self.pin, self.draws,
                             self.hold, None if self.multistep is None else (self.multistep, self.hist),
                             None if self.limits is None else (self.limits.lo, self.limits.hi, self.reproject),
-                            None if self.slew_v is None else (self.slew_v, self.slew_start))
+                            None if self.slew_v is None else (self.slew_v, self.slew_start),
+                            None if self.accel_a is None else (self.accel_a, self.accel_start2))
+
+    def set_accel(self, accel) -> None:
+        """Rewrites the captured acceleration arrays in place (``accel`` as ``ddim_sample`` takes it: ``a`` or ``(a, start2)``; without
+        ``start2`` the second anchors go back to NaN): every later replay runs under them."""
+        if self.accel_a is None:
+            raise ValueError("GraphedSampler: set_accel needs a graph captured with accel=True")
+        a, start2 = _accel_req(accel, self.x.shape[0], self.packed.J, self.x.device)
+        self.accel_a.copy_(a)
+        if start2 is None:
+            self.accel_start2.fill_(float("nan"))
+        else:
+            self.accel_start2.copy_(start2)
 
     def set_slew(self, slew) -> None:
         """Rewrites the captured slew arrays in place (``slew`` as ``ddim_sample`` takes it: ``v`` or ``(v, start)``; without ``start``
@@ -844,7 +939,7 @@ class GraphedSampler:
 def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                 trace: bool = False, inplace: bool = False, status: Optional[Tensor] = None, max_mode: int = -1,
                 eps_trace: bool = False, pin=None, draws: int = 1, hold=None, multistep=None, limits=None, reproject: bool = False,
-                slew=None):
+                slew=None, accel=None):
     """The reference's sampling loop (ml/inference/plot.py:122-131, ml/training/distill.py:179-189)
     as ONE native call.  Returns the sample, or (sample, per-step trace) when ``trace``; with ``eps_trace`` the
     noise prediction of every step (n_steps, B, T, J) - the value of ``forward_with_context`` inside the loop - is
@@ -882,7 +977,15 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
     Every free element of the result lies bitwise within ``fl(p +- v)`` of a predecessor p inside the box.  It composes with everything
     above; infinite ``v`` without ``start`` is the ``limits=`` call bit for bit.  One slew kernel per step on the trajectory routes (the
     limits twins around the scan, x0 exchanged through LDS; no fused rollout form); behind the row-panel routes one scan kernel, a thread
-    per trajectory and joint."""
+    per trajectory and joint.
+    ``accel = a`` or ``(a, start2)`` (``joint_accel``'s forms; ``start2`` (B, J) or (B, 32), NaN: none): per-joint acceleration limits in
+    normalised space (``sd_ddim_sample_accel``) - the scan carries the two rows before (row -1 is ``slew``'s ``start``, row -2 is
+    ``start2``) and keeps row t within ``a[j]`` of their constant-velocity continuation ``fl(y1 + fl(y1 - y2))``, then applies the slew
+    interval, the box and the hold as above: the box wins over the slew limit, which wins over the acceleration limit.  A missing or NaN
+    predecessor limits nothing.  ``slew`` and ``limits`` are optional beside it.  There is no braking ahead of the box - where the box or
+    the slew interval wins, the second difference at that row can exceed ``a`` - and without a box or a slew limit the velocity can
+    accumulate and the scan can run away from the prediction.  Infinite ``a`` without ``start2`` is the ``slew=`` call bit for bit.  One
+    acceleration kernel per step on the trajectory routes (the slew twins with two rows of state); ``max_mode`` 4 runs the mode-3 kernels."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])   # (shapes only: before anything touches a device)
     if pin is not None and hold is not None:
         raise ValueError("pin and hold exclude each other: compose them through ops.hold_mask(mask, B, T, J, device, rows=rows)")
@@ -905,10 +1008,13 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         _req(status, "status", torch.int32)
     if pin is not None:
         pin = _pin_req(pin, B, T, J, x_T.device)
-        if multistep is not None or limits is not None or slew is not None:   # the multistep and limits kernels take a mask: the pin as its leading full rows
+        if multistep is not None or limits is not None or slew is not None or accel is not None:   # these kernels take a mask: the pin as its leading full rows
             hold, pin = (pin[0], hold_mask(torch.zeros(J, dtype=torch.bool, device=x_T.device), B, T, J, x_T.device, rows=pin[1])), None
     if hold is not None:
         hold = _hold_req(hold, B, T, J, x_T.device)
+    if accel is not None:
+        accel = _accel_req(accel, B, J, x_T.device)
+        slew = {} if slew is None else slew
     if slew is not None:
         slew = _slew_req(slew, B, J, x_T.device)
         limits = {} if limits is None else limits
@@ -925,7 +1031,7 @@ def ddim_sample(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coe
         hold = (hold[0], x_T.clone() if inplace else x_T, hold[1])
     if multistep is not None:   # (weights, history): the history is written before it is read - no clearing
         multistep = (multistep, torch.empty_like(x))
-    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep, limits, slew)
+    return _ddim_sample_native(packed, ctx, step_tokens, coef, x, tr, et, ws, status, max_mode, pin, draws, hold, multistep, limits, slew, accel)
 
 
 def default_sampler_cap() -> int:
@@ -949,14 +1055,14 @@ def sampler_cap(packed: _Packed, max_mode: Optional[int] = None) -> int:
 
 def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Tensor, coef: np.ndarray, x_T: Tensor,
                         trace: bool = False, max_mode: Optional[int] = None, pin=None, draws: int = 1, hold=None, multistep=None,
-                        limits=None, reproject: bool = False, slew=None):
+                        limits=None, reproject: bool = False, slew=None, accel=None):
     """``ddim_sample`` with the range guard read back (one host synchronisation): when the split-fp16 kernels of
     sampler modes 2 .. 4 were driven out of their operand range (|8 v| >= 65520 for a LayerNorm / attention / GELU output -
     e.g. a checkpoint with LayerNorm weights in the thousands), the rollout is repeated on the exact-fp32 MFMA kernels
     (``max_mode`` 1), which have no such limit.  Raises if that result is not finite either (non-finite inputs).
     ``max_mode``: None = ``default_sampler_cap()`` (3).  With 4, mode 4's own guard (SD_STATUS_SHARP_LOGITS: a self-attention logit
     beyond the range its two-product Q | K | V site is validated on) repeats the rollout on mode 3 and pins ``packed.sampler_cap`` there.
-    ``pin``, ``hold``, ``draws``, ``multistep``, ``limits``, ``reproject`` and ``slew``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
+    ``pin``, ``hold``, ``draws``, ``multistep``, ``limits``, ``reproject``, ``slew`` and ``accel``: as in ``ddim_sample``; every repeat carries them (the rerun at ``max_mode`` 1 expands the context
     rows: correct, not shared; a repeat restarts from ``x_T``, so the multistep history needs nothing more)."""
     import warnings
 
@@ -973,10 +1079,12 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         limits = _limits_req(limits, x_T.shape[2], x_T.device)
     if slew is not None:
         slew = _slew_req(slew, x_T.shape[0], x_T.shape[2], x_T.device)
+    if accel is not None:
+        accel = _accel_req(accel, x_T.shape[0], x_T.shape[2], x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = sampler_cap(packed, max_mode)
     out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=cap, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                      limits=limits, reproject=reproject, slew=slew)
+                      limits=limits, reproject=reproject, slew=slew, accel=accel)
     word = int(status.item())
     if word == 0:
         return out
@@ -987,7 +1095,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         packed.sampler_cap = 3
         if not word & STATUS_NONFINITE:
             out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=3, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                              limits=limits, reproject=reproject, slew=slew)
+                              limits=limits, reproject=reproject, slew=slew, accel=accel)
             if int(status.item()) == 0:
                 return out
     mode = _lib.load().sd_sampler_mode(packed.d, packed.heads, x_T.shape[1], 0 if ctx is None else ctx.shape[1], packed.J)
@@ -997,7 +1105,7 @@ def ddim_sample_guarded(packed: _Packed, ctx: Optional[Tensor], step_tokens: Ten
         warnings.warn("sd_ddim_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the rollout on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
         out = ddim_sample(packed, ctx, step_tokens, coef, x_T, trace=trace, status=status, max_mode=1, pin=pin, draws=draws, hold=hold, multistep=multistep,
-                          limits=limits, reproject=reproject, slew=slew)
+                          limits=limits, reproject=reproject, slew=slew, accel=accel)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_ddim_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
@@ -1025,7 +1133,7 @@ def _direct_req(x_shape, device, hold, limits, slew) -> tuple:
 
 
 def direct_sample(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Tensor, hold=None, limits=None, slew=None, draws: int = 1,
-                  raw: bool = False, status: Optional[Tensor] = None, max_mode: int = 3):
+                  raw: bool = False, status: Optional[Tensor] = None, max_mode: int = 3, accel=None):
     """A distilled one-step decoder under the guarantees of ``ddim_sample`` (``sd_direct_sample``): the network's output at the ONE step
     token ``token`` ((d,) or (1, d): the token of t = 0, ros.py:293-298) is the clean trajectory x0 itself, so the result is that
     prediction projected - ``hold = (known, mask)``, then the slew scan ``slew = v`` or ``(v, start)`` over the rows, then the box
@@ -1037,7 +1145,11 @@ def direct_sample(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Te
     inside ``limits`` and within ``fl(p +- v)`` of its predecessor p.  On the trajectory routes this is ONE launch of a direct twin of
     the step kernels; on the others (``max_mode`` < 3, or a shape without trajectory kernels) the eps launches and one projection
     launch.  ``status`` as in ``ddim_sample`` (not read here).  There is no ``pin``, no ``multistep`` and no ``reproject``: one step has
-    no free rows that could adapt to pinned ones, no history and no eps to recompute."""
+    no free rows that could adapt to pinned ones, no history and no eps to recompute.
+    ``accel = a`` or ``(a, start2)``: acceleration limits as ``ddim_sample`` defines them.  The call is then TWO launches on every route:
+    the plain direct launch with nothing set, which returns ``raw``, then ``direct_project(raw, ..., accel=)`` (there is no fused
+    direct twin: the fused launch measured no faster than launch + projection at the robot's T = 10, profiles/direct_bench.jsonl), in one
+    native call (``sd_direct_sample_accel``).  The status word tells of the projected sample."""
     draws = _draws_req(draws, x_T.shape[0], None if ctx is None else ctx.shape[0])
     lib = _lib.load()
     _req(x_T, "x_T"); _req(token, "token")
@@ -1055,6 +1167,14 @@ def direct_sample(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Te
     if status is not None:
         _req(status, "status", torch.int32)
     known, words, lo, hi, v, start = _direct_req((B, T, J), x_T.device, hold, limits, slew)
+    if accel is not None:   # sd_direct_sample_accel: the plain launch, which returns raw, then the projection
+        a, start2 = _accel_req(accel, B, J, x_T.device)
+        out, pred = torch.empty_like(x_T), torch.empty_like(x_T)
+        ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, 1), x_T.device)
+        check(lib.sd_direct_sample_accel(C.byref(packed.struct), _ptr(ctx), token.data_ptr(), x_T.data_ptr(), out.data_ptr(), pred.data_ptr(), ws.data_ptr(),
+                                         B, T, Mc, _ptr(status), int(max_mode), _ptr(known), _ptr(words), draws, lo.data_ptr(), hi.data_ptr(), _ptr(v),
+                                         _ptr(start), a.data_ptr(), _ptr(start2), _stream()), "sd_direct_sample_accel")
+        return (out, pred) if raw else out
     out = torch.empty_like(x_T)
     pred = torch.empty_like(x_T) if raw else None
     ws = workspace(lib.sd_workspace_floats(B, T, max(Mc, 1), packed.d, packed.L, 1), x_T.device)
@@ -1065,7 +1185,7 @@ def direct_sample(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Te
 
 
 def direct_sample_guarded(packed: _Packed, ctx: Optional[Tensor], token: Tensor, x_T: Tensor, hold=None, limits=None, slew=None, draws: int = 1,
-                          raw: bool = False, max_mode: Optional[int] = None):
+                          raw: bool = False, max_mode: Optional[int] = None, accel=None):
     """``direct_sample`` with the range guard read back (one host synchronisation), as ``ddim_sample_guarded``: a non-finite result on
     the split-fp16 kernels is repeated on the exact-fp32 MFMA kernels (``max_mode`` 1: the eps launches, then the projection launch),
     with the same ``hold``, ``limits``, ``slew`` and ``draws``; FloatingPointError if that is not finite either.  ``max_mode`` None: the
@@ -1080,25 +1200,28 @@ def direct_sample_guarded(packed: _Packed, ctx: Optional[Tensor], token: Tensor,
         limits = _limits_req(limits, J, x_T.device)
     if slew is not None:
         slew = _slew_req(slew, B, J, x_T.device)
+    if accel is not None:
+        accel = _accel_req(accel, B, J, x_T.device)
     status = torch.zeros(1, dtype=torch.int32, device=x_T.device)
     cap = min(sampler_cap(packed, max_mode), 3)
-    out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=cap)
+    out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=cap, accel=accel)
     if int(status.item()) == 0:
         return out
     if cap >= 2:
         warnings.warn("sd_direct_sample: the split-fp16 kernels left their operand range (non-finite sample); "
                       "repeating the call on the fp32-MFMA kernels", RuntimeWarning, stacklevel=2)
-        out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=1)
+        out = direct_sample(packed, ctx, token, x_T, hold=hold, limits=limits, slew=slew, draws=draws, raw=raw, status=status, max_mode=1, accel=accel)
         if int(status.item()) == 0:
             return out
     raise FloatingPointError("sd_direct_sample produced non-finite values on the fp32 kernels too: the inputs or the weights are not finite")
 
 
-def direct_project(raw: Tensor, hold=None, limits=None, slew=None) -> Tensor:
+def direct_project(raw: Tensor, hold=None, limits=None, slew=None, accel=None) -> Tensor:
     """The projection of ``direct_sample`` on its own (``sd_direct_project``): ``raw`` (B, T, J) - a predicted clean trajectory from
     anywhere - under ``hold = (known, mask)``, the slew scan ``slew = v`` or ``(v, start)`` and the box ``limits``, in ``ddim_sample``'s
     forms; a new tensor.  Compares and selects, one fp32 add and one subtract per row: -0 stays -0, a NaN stays NaN and limits nothing
-    after it, an infinite prediction comes out as its limit."""
+    after it, an infinite prediction comes out as its limit.  ``accel = a`` or ``(a, start2)``: the acceleration scan of
+    ``ddim_sample(accel=...)`` ahead of the slew interval (``sd_direct_project_accel``)."""
     lib = _lib.load()
     _req(raw, "raw")
     if raw.dim() != 3:
@@ -1106,6 +1229,11 @@ def direct_project(raw: Tensor, hold=None, limits=None, slew=None) -> Tensor:
     B, T, J = raw.shape
     known, words, lo, hi, v, start = _direct_req((B, T, J), raw.device, hold, limits, slew)
     out = torch.empty_like(raw)
+    if accel is not None:
+        a, start2 = _accel_req(accel, B, J, raw.device)
+        check(lib.sd_direct_project_accel(raw.data_ptr(), out.data_ptr(), _ptr(known), _ptr(words), lo.data_ptr(), hi.data_ptr(), _ptr(v), _ptr(start),
+                                          a.data_ptr(), _ptr(start2), B, T, J, _stream()), "sd_direct_project_accel")
+        return out
     check(lib.sd_direct_project(raw.data_ptr(), out.data_ptr(), _ptr(known), _ptr(words), lo.data_ptr(), hi.data_ptr(), _ptr(v), _ptr(start), B, T, J,
                                 _stream()), "sd_direct_project")
     return out
@@ -1368,6 +1496,21 @@ def max_step(x: Tensor, mean: Tensor, std: Tensor) -> Tensor:
         raise ValueError(f"max_step: mean and std must be ({J},) with J <= 32 on x's device")
     out = torch.empty(N, J, dtype=torch.float32, device=x.device)
     check(_lib.load().sd_eval_max_step(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), N, T, J, _stream()), "sd_eval_max_step")
+    return out
+
+
+def max_accel(x: Tensor, mean: Tensor, std: Tensor) -> Tensor:
+    """The largest second difference of sampled trajectories, per joint (``sd_max_accel``, one launch): ``x`` (N, T, J) in the sampler's
+    normalised space -> (N, J) with [n, j] = max over t of |(r[t + 1] - r[t]) - (r[t] - r[t - 1])|, r = x std + mean (fp32, one rounding per
+    operation).  The number from which an acceleration limit is chosen.  T <= 2: 0."""
+    _req(x, "x"); _req(mean, "mean"); _req(std, "std")
+    if x.dim() != 3 or x.shape[0] == 0:
+        raise ValueError(f"max_accel: x must be (N, T, J), got {tuple(x.shape)}")
+    N, T, J = x.shape
+    if tuple(mean.shape) != (J,) or tuple(std.shape) != (J,) or not 1 <= J <= 32 or mean.device != x.device or std.device != x.device:
+        raise ValueError(f"max_accel: mean and std must be ({J},) with J <= 32 on x's device")
+    out = torch.empty(N, J, dtype=torch.float32, device=x.device)
+    check(_lib.load().sd_max_accel(x.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), N, T, J, _stream()), "sd_max_accel")
     return out
 
 
@@ -2803,6 +2946,71 @@ def session_anchor(anchor: Tensor, x: Tensor, row: int, draws: int = 1, robots=N
         raise ValueError(f"session_anchor: x holds {S} robots")
     check(_lib.load().sd_session_anchor(anchor.data_ptr(), x.data_ptr(), _ptr(r), S, B, T, J, int(row), int(draws), _stream()), "sd_session_anchor")
     return anchor
+
+
+def session_accel_margin(bound_rad, mean, std) -> np.ndarray:
+    """The margin of ``sd_session_accel`` in radians, fp64, per joint: 4 std hu(3 XS / std) + 4 hu(XS) + 4 hu(pi + R) + 4 hu(R) with
+    XS = R + |pi - mean| and hu half an fp32 ulp - what the four roundings of the scan's row function (d, p, p - a, p + a, at magnitudes
+    up to 3 XS / std) and the roundings of the commit's expression at three published values with weights 1, 2 and 1 can add to a
+    published second difference."""
+    R, s = np.asarray(bound_rad, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    XS = R + np.abs(math.pi - np.asarray(mean, dtype=np.float64))
+    return 4.0 * s * _half_ulp(3.0 * XS / s) + 4.0 * _half_ulp(XS) + 4.0 * _half_ulp(math.pi + R) + 4.0 * _half_ulp(R)
+
+
+def denormalised_accel_margin(bound, mean, std) -> np.ndarray:
+    """``session_accel_margin`` for trajectories that are denormalised and nothing else, r = x * std + mean (``ops.max_accel``):
+    4 std hu(3 XS / std) + 4 hu(XS) + 4 hu(Q) with Q = ``bound`` >= |r| and XS = Q + |mean| >= |x std| - the scan's four roundings and the
+    product's and the sum's of three values with weights 1, 2 and 1."""
+    Q, s = np.asarray(bound, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    XS = Q + np.abs(np.asarray(mean, dtype=np.float64))
+    return 4.0 * s * _half_ulp(3.0 * XS / s) + 4.0 * _half_ulp(XS) + 4.0 * _half_ulp(Q)
+
+
+def session_accel_host(a_rad, bound_rad, mean, std) -> np.ndarray:
+    """The host model of ``sd_session_accel``'s arithmetic, for J joints: fp32 a_n from fp32 a_rad, bound, mean and std."""
+    s32 = np.asarray(std, dtype=np.float32)
+    a = (np.asarray(a_rad, dtype=np.float32).astype(np.float64) - session_accel_margin(bound_rad, np.asarray(mean, dtype=np.float32), s32)) / s32.astype(np.float64)
+    a = np.maximum(a, 0.0)
+    out = a.astype(np.float32)
+    over = out.astype(np.float64) > a
+    out[over] = np.nextafter(out[over], np.float32(0))
+    return out
+
+
+def session_accel(a_n: Tensor, a_rad, bound_rad, mean: Tensor, std: Tensor, J: int) -> Tensor:
+    """One launch (``sd_session_accel``) writes ``a_n`` - the (32,) device array a rollout under ``accel=`` reads - from ``a_rad``, radians
+    per row^2 as published, and ``bound_rad``, a finite bound on the magnitude of the published values per joint (host arrays of at least
+    J fp32).  ValueError for an ``a_rad`` that is not above its margin (``session_accel_margin``)."""
+    a_rad, bound_rad = np.ascontiguousarray(a_rad, dtype=np.float32), np.ascontiguousarray(bound_rad, dtype=np.float32)
+    if a_rad.ndim != 1 or bound_rad.ndim != 1 or a_rad.shape[0] < J or bound_rad.shape[0] < J:
+        raise ValueError(f"session_accel: a_rad and bound_rad must hold at least {J} floats")
+    if not _is_dev32(a_n, mean.device):
+        raise ValueError(f"session_accel: a_n is the (32,) fp32 array of ops.joint_accel on {mean.device}")
+    _req(mean, "mean"); _req(std, "std")
+    margin = session_accel_margin(bound_rad[:J], mean.detach().cpu().numpy(), std.detach().cpu().numpy())
+    finite = np.isfinite(a_rad[:J])
+    if (a_rad[:J][finite].astype(np.float64) <= margin[finite]).any():
+        j = int(np.argmax(finite & (a_rad[:J].astype(np.float64) <= margin)))
+        raise ValueError(f"session_accel: a_rad[{j}] = {a_rad[j]} is not above its margin {margin[j]:.3g}")
+    check(_lib.load().sd_session_accel(a_n.data_ptr(), a_rad.ctypes.data_as(_lib.c_float_p), bound_rad.ctypes.data_as(_lib.c_float_p),
+                                       mean.data_ptr(), std.data_ptr(), int(J), _stream()), "sd_session_accel")
+    return a_n
+
+
+def session_anchor2(anchor: Tensor, anchor2: Tensor, x: Tensor, row: int, draws: int = 1, robots=None) -> None:
+    """One launch (``sd_session_anchor2``): ``session_anchor`` with a second destination, for a scan whose state is two rows -
+    ``anchor2`` <- row ``row - 1`` of ``x`` (``row`` == 0: the old ``anchor``), ``anchor`` <- row ``row`` of ``x``."""
+    _req(x, "x")
+    S, T, J = x.shape
+    B = anchor.shape[0] // draws
+    if not _is_dev32(anchor, x.device, B * draws) or not _is_dev32(anchor2, x.device, B * draws) or anchor.data_ptr() == anchor2.data_ptr():
+        raise ValueError("session_anchor2: anchor and anchor2 are two contiguous (B * draws, 32) fp32 tensors on x's device")
+    r = None if robots is None else _robots_on(robots, B, x.device)
+    if (S != B) if r is None else (r.numel() != S):
+        raise ValueError(f"session_anchor2: x holds {S} robots")
+    check(_lib.load().sd_session_anchor2(anchor.data_ptr(), anchor2.data_ptr(), x.data_ptr(), _ptr(r), S, B, T, J, int(row), int(draws), _stream()),
+          "sd_session_anchor2")
 
 
 def session_reset(rings: Sequence[tuple], mask: Optional[Tensor] = None, game_state: Optional[Tensor] = None, game_state_value: int = 0,

@@ -11,6 +11,8 @@ update (``sd_ddim_limit_step``); ``step(..., use_clipped_model_output=True)`` re
 ``slew=v`` or ``(v, start)`` (``ops.joint_slew``'s forms; diffusers has nothing like it): ``step`` also keeps consecutive rows of the
 predicted clean sample within ``v[j]`` of each other (``sd_ddim_slew_step``, the scan of ``ops.ddim_sample(slew=...)``); the samples are
 then whole (B, T, J) trajectories, since the scan walks a trajectory's rows in order.
+``accel=a`` or ``(a, start2)`` (``ops.joint_accel``'s forms): ``step`` also keeps the second difference of consecutive rows within
+``a[j]`` (``sd_ddim_accel_step``, the scan of ``ops.ddim_sample(accel=...)``), ahead of the slew interval and the box.
 diffusers itself is not available offline: scheduler parity is UNPINNED."""
 
 from __future__ import annotations
@@ -24,7 +26,8 @@ from . import ops
 
 class DDIMScheduler:
     def __init__(self, num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2",
-                 clip_sample: bool = False, prediction_type: str = "epsilon", clip_sample_range: float = 1.0, limits=None, slew=None):
+                 clip_sample: bool = False, prediction_type: str = "epsilon", clip_sample_range: float = 1.0, limits=None, slew=None,
+                 accel=None):
         if beta_schedule != "squaredcos_cap_v2" or prediction_type != "epsilon":
             raise NotImplementedError("only the configuration the reference uses is implemented: "
                                       "beta_schedule='squaredcos_cap_v2', epsilon prediction")
@@ -37,6 +40,10 @@ class DDIMScheduler:
         self._limits_dev: dict = {}
         self._slew_spec = slew   # v or (v, start): step runs the slew scan over the rows of every (B, T, J) sample
         self._slew_dev: dict = {}
+        self._accel_spec = accel   # a or (a, start2): the scan's state is two rows
+        self._accel_dev: dict = {}
+        if accel is not None and slew is None:
+            self._slew_spec = {}   # an acceleration step always carries the slew arrays: no limit, no anchor
         self._table_len = num_train_timesteps
         self.alphas_cumprod = ops.alphas_cumprod(num_train_timesteps)  # CPU fp32, like diffusers
         self._acp_dev: dict = {}
@@ -89,13 +96,28 @@ class DDIMScheduler:
             self._slew_dev[key] = ops._slew_req(self._slew_spec, sample.shape[0], sample.shape[-1], sample.device)
         return self._slew_dev[key]
 
+    def _accel(self, sample: torch.Tensor):
+        """(a, start2) as the kernel reads them, on the sample's device for its (B, T, J) shape, or None: no acceleration limits."""
+        if self._accel_spec is None:
+            return None
+        if sample.dim() != 3:
+            raise ValueError(f"accel: the scan walks the rows of whole (B, T, J) samples, got {tuple(sample.shape)}")
+        key = (sample.device, sample.shape[0], sample.shape[-1])
+        if key not in self._accel_dev:
+            self._accel_dev[key] = ops._accel_req(self._accel_spec, sample.shape[0], sample.shape[-1], sample.device)
+        return self._accel_dev[key]
+
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, use_clipped_model_output: bool = False):
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps before step")
         t = int(timestep)
         coef = ops.ddim_coefficients([t], self.alphas_cumprod, self.num_inference_steps, self._table_len)[0]
         limits = self._limits(sample)
+        accel = self._accel(sample)
         slew = self._slew(sample)
+        if accel is not None:
+            return SimpleNamespace(prev_sample=ops.accel_step(model_output.contiguous(), sample.contiguous(), coef, accel, slew=slew, limits=limits,
+                                                              reproject=use_clipped_model_output))
         if slew is not None:
             return SimpleNamespace(prev_sample=ops.slew_step(model_output.contiguous(), sample.contiguous(), coef, slew, limits=limits,
                                                              reproject=use_clipped_model_output))
@@ -111,7 +133,7 @@ class MultistepScheduler(DDIMScheduler):
     update plus ``w * (x0 of the step before - x0 of this step)`` (``ops.multistep_weights``, ``sd_multistep_step``: one launch).  The
     previous x0 stays on the device, in a buffer of the sample's shape; ``set_timesteps`` clears the history, so every rollout starts
     first order, and the steps must then be taken in the order of ``timesteps``.  ``clip_sample`` / ``clip_sample_range`` / ``limits`` as
-    ``DDIMScheduler`` takes them, ``slew`` too: the history then holds the clamped x0.
+    ``DDIMScheduler`` takes them, ``slew`` and ``accel`` too: the history then holds the clamped x0.
 
     It runs on THIS project's leading grid (``ops.ddim_timesteps``: t - ratio, the last step to alpha = 1), not on a grid of its own, so
     that its step counts compare with ``DDIMScheduler``'s: n steps here evaluate the denoiser at the same n timesteps.  Parity with
@@ -142,8 +164,12 @@ class MultistepScheduler(DDIMScheduler):
         if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
             self._hist = torch.empty_like(sample, memory_format=torch.contiguous_format)
         limits = self._limits(sample)
+        accel = self._accel(sample)
         slew = self._slew(sample)
-        if slew is not None:   # the history holds the slewed and clamped x0
+        if accel is not None:   # the history holds the x0 the acceleration scan returned
+            out = ops.accel_step(model_output.contiguous(), sample.contiguous(), coef, accel, slew=slew, limits=limits, hist=self._hist,
+                                 w=float(self._weights[i]), reproject=use_clipped_model_output)
+        elif slew is not None:   # the history holds the slewed and clamped x0
             out = ops.slew_step(model_output.contiguous(), sample.contiguous(), coef, slew, limits=limits, hist=self._hist,
                                 w=float(self._weights[i]), reproject=use_clipped_model_output)
         elif limits is not None:   # clip_sample / limits: the history holds the clamped x0

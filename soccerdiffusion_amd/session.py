@@ -165,7 +165,7 @@ class PolicySession:
     def __init__(self, model, num_inference_steps: int = 30, batch: int = 1, distilled: Optional[bool] = None, seed: int = 0,
                  hyperparams: Optional[dict] = None, use_graph: bool = False, carry: int = 0, advance: Optional[int] = None, draws: int = 1,
                  select: str = "medoid", holds: bool = False, solver: str = "ddim", limits=None, reproject: bool = False, slew=None,
-                 coherence_decay: float = 0.5, contrast: float = 0.0, direct: bool = False):
+                 coherence_decay: float = 0.5, contrast: float = 0.0, direct: bool = False, accel=None):
         """``model``: an End2EndDiffusionTransformer in eval mode on a GPU.  ``hyperparams``: the checkpoint's dictionary (default: the
         model's ``hyperparams`` attribute where it has one).  REQUIRED for a model with images: the model does not keep its
         ``image_resolution`` (the size of the all-zero start frames), nor ``image_context_length`` where it has no sequence encoder;
@@ -224,7 +224,20 @@ class PolicySession:
         margin assumes published values inside ``limits`` where both sides are given, else inside [-pi, pi].  ``set_slew`` rewrites the
         same device array, safe under ``use_graph``.  With ``carry`` row 0 is pinned: the scan starts from the carried rows (the seam
         stays exact) and no anchor is used.  A jump into a held joint's value is not limited.  It composes with ``limits``, ``holds``,
-        ``draws``, ``robots=``, ``solver`` and ``use_graph``.  A ``v`` not above its margin raises."""
+        ``draws``, ``robots=``, ``solver`` and ``use_graph``.  A ``v`` not above its margin raises.
+        ``accel`` ((J,) floats, one number, or ``{joint: a}``): acceleration limits in radians PER ROW^2 as published - ``a = max
+        acceleration / row rate^2``; +inf: none.  One launch converts them to normalised space, ``a / std[j]`` moved inward by a derived
+        margin (``sd_session_accel``, ``ops.session_accel_margin``: the four roundings of the scan's row function and the commit's
+        roundings at three published values), and every tick's rollout limits the second difference of consecutive rows of the predicted
+        clean trajectory at every step (``ops.ddim_sample(accel=...)``), a tick's first two rows against the robot's last two committed
+        rows (rows ``advance - 2`` and ``advance - 1`` of its previous tick, kept on the device; none after ``reset`` for the robots
+        reset).  Every published triple then has a second difference of at most ``a``, evaluated exactly, unless the box or the slew
+        limit won at its last row: there is NO braking ahead of the box.  It REQUIRES ``limits`` that are finite on both sides for every
+        joint with a finite ``a`` (ValueError otherwise): without a bound the velocity can accumulate and the scan can run away from the
+        prediction, and the margin is derived from that bound.  ``set_accel`` rewrites the same device array, safe under ``use_graph``.
+        With ``carry`` no anchor is used, as for ``slew``: the pinned rows are the state, and ``carry >= 2`` is what gives continuity of
+        acceleration across the seam.  It composes with ``limits``, ``slew``, ``holds``, ``draws``, ``select``, ``robots=``, ``solver``,
+        ``use_graph`` and ``direct=True``.  An ``a`` not above its margin raises."""
         hp = dict(hyperparams if hyperparams is not None else (getattr(model, "hyperparams", None) or {}))
         self.distilled = bool(hp.get("distilled_decoder", False)) if distilled is None else bool(distilled)
         self.direct = self.check_direct(direct, self.distilled)                                                            # (needs no device)
@@ -237,6 +250,7 @@ class PolicySession:
         limits = self.check_limits(limits, model.num_joints, self.carry, self.distilled, self.direct)                                 # (likewise)
         self.reproject = self.check_reproject(reproject, self.distilled)
         slew = self.check_slew(slew, model.num_joints, self.carry, self.distilled, self.direct)                                       # (likewise)
+        accel = self.check_accel(accel, model.num_joints, self.carry, self.distilled, self.direct, limits)                            # (likewise)
         params = [p for p in model.parameters()]
         if model.training:
             raise RuntimeError("PolicySession: the model is in train() mode; cached image tokens are exact in eval mode only - call model.eval()")
@@ -253,7 +267,8 @@ class PolicySession:
         if self.use_graph and self.distilled and not self.direct:
             raise ValueError("PolicySession: use_graph replays the rollout; a distilled decoder has none - " + _DIRECT_HINT)
         # a distilled session with any of the options runs the direct launch (model.sample_direct); with none, forward_with_context as ever
-        self._direct = self.direct and (self.use_graph or self.draws > 1 or self.holds or limits is not None or slew is not None)
+        self._direct = self.direct and (self.use_graph or self.draws > 1 or self.holds or limits is not None or slew is not None
+                                        or accel is not None)
         encoders = {"joint_command_history": model.action_history_encoder, "rotation": model.imu_encoder,
                     "joint_state": model.joint_states_encoder}
         self._encoders = {k: e for k, e in encoders.items() if e is not None}
@@ -274,6 +289,7 @@ class PolicySession:
             self._limits = ops.joint_limits({}, J=self.J, device=self.device)
             ops.session_limits(self._limits, *limits, model.mean, model.std, self.J)
         self._slew_v = self._anchor = None   # the normalised slew limits (32,) and the scan's anchors (B * draws, 32): device arrays
+        self._accel_a = self._anchor2 = None   # the normalised acceleration limits (32,) and the rows before the anchors (B * draws, 32)
         self._limits_rad = limits
         # select="coherent": the last committed trajectory per robot (normalised space; NaN: none), and the last tick's (index, cost)
         self._plan = (torch.full((self.B, self.T, self.J), float("nan"), dtype=torch.float32, device=self.device)
@@ -287,6 +303,16 @@ class PolicySession:
             self._mean_host = model.mean.detach().reshape(-1).cpu().numpy().astype(np.float32)
             self._std_host = model.std.detach().reshape(-1).cpu().numpy().astype(np.float32)
             self._write_slew(slew)
+        if accel is not None:   # (limits are given: check_accel; the acceleration call reads the slew arrays: infinite ones without slew)
+            if self._slew_v is None:
+                self._slew_v = ops.joint_slew({}, J=self.J, device=self.device)
+                self._anchor = torch.full((self.B * self.draws, 32), float("nan"), dtype=torch.float32, device=self.device)
+                self._mean_host = model.mean.detach().reshape(-1).cpu().numpy().astype(np.float32)
+                self._std_host = model.std.detach().reshape(-1).cpu().numpy().astype(np.float32)
+                self._slew_rad = None
+            self._accel_a = ops.joint_accel({}, J=self.J, device=self.device)
+            self._anchor2 = torch.full((self.B * self.draws, 32), float("nan"), dtype=torch.float32, device=self.device)
+            self._write_accel(accel)
         self.reset()
 
     @staticmethod
@@ -395,10 +421,14 @@ class PolicySession:
         if self._limits is None:
             raise RuntimeError("PolicySession.set_limits: the session was built without limits")
         host = self.check_limits(lo if hi is None else (lo, hi), self.J, self.carry, self.distilled, self.direct)
+        if self._accel_a is not None:   # (before anything is written: the new box must still bound every joint with a finite a)
+            self._accel_box(self._accel_rad, self.J, host)
         ops.session_limits(self._limits, *host, self.model.mean, self.model.std, self.J)
         self._limits_rad = host
-        if self._slew_v is not None:   # the slew margin depends on the bound the limits give: one more launch
+        if self._slew_v is not None and self._slew_rad is not None:   # the slew margin depends on the bound the limits give: one more launch
             self._write_slew(self._slew_rad)
+        if self._accel_a is not None:   # likewise
+            self._write_accel(self._accel_rad)
 
     @staticmethod
     def check_slew(slew=None, J: int = 1, carry: int = 0, distilled: bool = False, direct: bool = False):
@@ -435,6 +465,52 @@ class PolicySession:
             raise RuntimeError("PolicySession.set_slew: the session was built without slew")
         self._write_slew(self.check_slew(slew, self.J, self.carry, self.distilled, self.direct))
 
+    @staticmethod
+    def check_accel(accel=None, J: int = 1, carry: int = 0, distilled: bool = False, direct: bool = False, limits=None):
+        """``accel`` of a session with J joints, validated (no device needed): None, or the (32,) fp32 host array in radians per row^2,
+        padded with +inf ((J,) floats, one number, or ``{joint: a}``, as ``ops.joint_accel`` takes them).  ``limits``: the session's, as
+        ``check_limits`` returns them.  ValueError for a wrong shape, a NaN or a negative value, J > 32, with a distilled decoder without
+        ``direct``, or for a joint with a finite ``a`` whose limits are not finite on both sides - without a bound the scan can run away
+        from the prediction, and the margin of the conversion is derived from that bound."""
+        if accel is None:
+            return None
+        if distilled and not direct:
+            raise ValueError("accel: a distilled decoder is one forward at t = 0 - " + _DIRECT_HINT)
+        return PolicySession._accel_box(ops._accel_host(accel, J), J, limits)
+
+    @staticmethod
+    def _accel_box(a, J: int, limits):
+        """``a`` (``check_accel``'s array) if ``limits`` (``check_limits``' arrays, or None) are finite on both sides for every joint with
+        a finite ``a[j]``; ValueError otherwise."""
+        lo, hi = (np.full(32, -np.inf), np.full(32, np.inf)) if limits is None else limits
+        open_ = np.isfinite(a[:J]) & ~(np.isfinite(lo[:J]) & np.isfinite(hi[:J]))
+        if open_.any():
+            j = int(np.argmax(open_))
+            raise ValueError(f"accel: joint {j} has a finite acceleration limit but no finite box - give limits that are finite on both sides "
+                             f"for every such joint (without a bound the scan can run away from the prediction)")
+        return a
+
+    def _write_accel(self, a_rad) -> None:
+        """ONE launch: the session's (32,) device array from ``a_rad`` (``check_accel``'s array) under the current ``limits``."""
+        J = self.J
+        lo, hi = (np.abs(b[:J]) for b in self._limits_rad)
+        bound = np.where(np.isfinite(a_rad[:J]), np.maximum(lo, hi), math.pi).astype(np.float32)   # (an unlimited joint's bound is not read)
+        bound = np.where(np.isfinite(bound), bound, math.pi).astype(np.float32)
+        margin = ops.session_accel_margin(bound, self._mean_host[:J], self._std_host[:J])
+        small = np.isfinite(a_rad[:J]) & ~(a_rad[:J].astype(np.float64) > margin)
+        if small.any():
+            j = int(np.argmax(small))
+            raise ValueError(f"accel: a[{j}] = {a_rad[j]} rad per row^2 is not above the margin {margin[j]:.3e} of the fp32 arithmetic")
+        ops.session_accel(self._accel_a, a_rad, bound, self.model.mean, self.model.std, J)
+        self._accel_rad = a_rad
+
+    def set_accel(self, accel) -> None:
+        """New acceleration limits in radians per row^2 as published (as the constructor's ``accel``): ONE small launch rewrites the
+        session's device array in place, so a captured tick stays captured and the next tick runs under the new limits."""
+        if self._accel_a is None:
+            raise RuntimeError("PolicySession.set_accel: the session was built without accel")
+        self._write_accel(self.check_accel(accel, self.J, self.carry, self.distilled, self.direct, self._limits_rad))
+
     def _lim(self, dev_idx=None) -> dict:
         """The limit arguments of the tick's rollout (of the robots ``dev_idx``): none in a session without limits or slew."""
         if self._limits is None:
@@ -446,6 +522,12 @@ class PolicySession:
                 G = self.draws
                 start = self._anchor if dev_idx is None else self._anchor.view(self.B, G * 32)[dev_idx.long()].reshape(-1, 32).contiguous()
             out["slew"] = (self._slew_v, start)
+            if self._accel_a is not None:
+                start2 = None   # (with carry the pinned rows are the state)
+                if self.carry == 0:
+                    G = self.draws
+                    start2 = self._anchor2 if dev_idx is None else self._anchor2.view(self.B, G * 32)[dev_idx.long()].reshape(-1, 32).contiguous()
+                out["accel"] = (self._accel_a, start2)
         return out
 
     def _direct_lim(self, dev_idx=None) -> dict:
@@ -582,6 +664,8 @@ class PolicySession:
         ops.session_reset(self._resettable, mask, self._game_state, DEFAULT_GAME_STATE, pin_rows=self._pin_rows if self._carrying else None)
         if self._anchor is not None:   # no last command: the robots' next first row is free
             self._anchor.view(self.B, -1).masked_fill_(mask.view(self.B, 1), float("nan"))
+        if self._anchor2 is not None:   # ... and its next two rows are free of the acceleration limit
+            self._anchor2.view(self.B, -1).masked_fill_(mask.view(self.B, 1), float("nan"))
         if self._plan is not None:     # no plan: the robots' next tick commits the medoid of its draws
             self._plan.masked_fill_(mask.view(self.B, 1, 1), float("nan"))
 
@@ -611,6 +695,8 @@ class PolicySession:
         self._t0 = torch.zeros(B, dtype=torch.int64, device=dev)
         if self._anchor is not None:   # (in place: the array is the session's for its lifetime)
             self._anchor.fill_(float("nan"))
+        if self._anchor2 is not None:
+            self._anchor2.fill_(float("nan"))
         if self._plan is not None:
             self._plan.fill_(float("nan"))
         self._selected = None
@@ -867,7 +953,10 @@ class PolicySession:
         if self._anchor is not None and self.carry == 0:
             # the next tick's scan starts from the last row this one commits (normalised space, as sampled).  One launch beside the commit,
             # outside a captured tick like the commit itself: a replay whose range guard trips is repeated eagerly under the OLD anchor.
-            ops.session_anchor(self._anchor, x, self.advance - 1, self.draws, robots=dev_idx)
+            if self._anchor2 is not None:   # both rows of the acceleration scan's state, in the same one launch
+                ops.session_anchor2(self._anchor, self._anchor2, x, self.advance - 1, self.draws, robots=dev_idx)
+            else:
+                ops.session_anchor(self._anchor, x, self.advance - 1, self.draws, robots=dev_idx)
         if not self._carrying:
             return ops.session_commit(x, m.mean, m.std, *self._action, robots=dev_idx)
         return ops.session_commit_carry(x, m.mean, m.std, *self._action, self.advance, self.carry, self._pin_x0, self._pin_rows, robots=dev_idx)

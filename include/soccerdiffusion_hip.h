@@ -601,7 +601,14 @@ int sd_op_attention(const float *q, int ldq, const float *k, const float *v, int
                     const float *k_extra, const float *v_extra, float *out, int ldo,
                     int B, int Tq, int S, int d, int heads, void *stream);
 
-/* out (B,S/p,d) = Conv1d(k=s=p)(x (B,S,C)) + bias + pe[:S/p]; p = 1 is nn.Linear + PE. */
+/* Host-only, reporting: the kernel the attention core launches for a call that does not take the split-fp16 kernel above -
+ * 1 = attention_pipe_kernel (a workgroup per sample walking its heads: Tq <= 128, no extra row, no dropout, B >= 64),
+ * 0 = attention_kernel (a workgroup per (sample, head)).  has_extra: an extra key/value row is passed; dropout: p > 0.
+ * The function the launch itself asks.  SD_E_BADARG on an empty shape. */
+int sd_attention_route(int B, int Tq, int S, int has_extra, int dropout);
+
+/* out (B,S/p,d) = Conv1d(k=s=p)(x (B,S,C)) + bias + pe[:S/p]; p = 1 is nn.Linear + PE.  Any C*p: up to 319 the patches and a column
+ * chunk of W^T are staged whole in LDS, beyond that (the image tokens of a hidden_dim-512 model) 128 values of k at a time. */
 int sd_op_patch_embed(const float *x, const float *w, const float *b, const float *pe,
                       float *out, int B, int S, int C, int p, int d, void *stream);
 

@@ -150,6 +150,7 @@ SIGNATURES = {
     "sd_direct_sample_accel": (C.c_int, [C.POINTER(DenoiserWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sd_direct_project_accel": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p]),
     "sd_sampler_route_draws": (C.c_int, [C.c_int] * 9),
+    "sd_attention_route": (C.c_int, [C.c_int] * 5),
     "sd_select_medoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_select_coherent": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "sd_bn_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int]),
@@ -291,6 +292,16 @@ def sampler_route_draws(d: int, heads: int, T: int, Mc: int, J: int, L: int, B: 
     rc = load().sd_sampler_route_draws(d, heads, T, Mc, J, L, B, max_mode, draws)
     check(min(rc, 0), "sd_sampler_route_draws")
     return ROUTES[rc]
+
+
+ATTENTION_ROUTES = ("attention_kernel", "attention_pipe_kernel")
+
+
+def attention_route(B: int, Tq: int, S: int, has_extra: bool = False, dropout: bool = False) -> str:
+    """The kernel the attention core launches for this call (sd_attention_route: the predicate the launch itself asks; reporting only)."""
+    rc = load().sd_attention_route(B, Tq, S, int(bool(has_extra)), int(bool(dropout)))
+    check(min(rc, 0), "sd_attention_route")
+    return ATTENTION_ROUTES[rc]
 
 
 ROLLOUTS = ("PER_STEP", "FUSED")   # SD_ROLLOUT_*

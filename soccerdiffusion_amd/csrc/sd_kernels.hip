@@ -453,6 +453,15 @@ __device__ __forceinline__ void chain_zero(f32x16 (&acc)[PanelCfg<D>::TM][PanelC
 }
 
 template <int D>
+__device__ __forceinline__ void chain_add(f32x16 (&acc)[PanelCfg<D>::TM][PanelCfg<D>::TN], const f32x16 (&u)[PanelCfg<D>::TM][PanelCfg<D>::TN]) {
+    using C = PanelCfg<D>;
+#pragma unroll
+    for (int tm = 0; tm < C::TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < C::TN; ++tn) acc[tm][tn] += u[tm][tn];
+}
+
+template <int D>
 __device__ __forceinline__ void chain_acc_to_lds(float *sA, const f32x16 (&acc)[PanelCfg<D>::TM][PanelCfg<D>::TN],
                                                  const ChainPos<D> &p) {
     using C = PanelCfg<D>;
@@ -607,8 +616,12 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void chain_b_kernel(ChainB
     chain_load_acc<D>(H, g.h, p);
     chain_load_panel<D>(sA, g.a, p);
     __syncthreads();
-    chain_gemm<D>(H, aBase, g.wo + wOff);          // h += a Wo^T
-    chain_bias_act<D, 0>(H, g.bo, p);
+    // Both out-projections run in U and meet the residual in ONE addition: accumulated in H, each of their D / 2 MFMAs would round at
+    // the magnitude of the residual stream
+    chain_zero<D>(U);
+    chain_gemm<D>(U, aBase, g.wo + wOff);          // h += a Wo^T + bo
+    chain_bias_act<D, 0>(U, g.bo, p);
+    chain_add<D>(H, U);
     __syncthreads();
     chain_acc_to_lds<D>(sA, H, p);
     __syncthreads();
@@ -619,8 +632,10 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void chain_b_kernel(ChainB
     __syncthreads();
     chain_gelu_to_lds<D>(sA, U, g.b1, p);
     __syncthreads();
-    chain_gemm<D>(H, aBase, g.w2 + wOff);          // h += u W2^T + b2
-    chain_bias_act<D, 0>(H, g.b2, p);
+    chain_zero<D>(U);
+    chain_gemm<D>(U, aBase, g.w2 + wOff);          // h += u W2^T + b2
+    chain_bias_act<D, 0>(U, g.b2, p);
+    chain_add<D>(H, U);
     chain_store_acc<D>(g.h, D, 0, H, p);
     if (g.nln_w == nullptr) return;
     __syncthreads();
@@ -1974,6 +1989,14 @@ __global__ __launch_bounds__(256, (HD <= 64 ? 2 : 1)) void attention_pipe_kernel
     }
 }
 
+// The kernel attention() launches: 1 = attention_pipe_kernel (one workgroup per sample walking its heads), 0 = attention_kernel.
+static int attention_route(int B, int Tq, int S, bool has_extra, bool dropout) {
+    // small batches (the robot: B = 1): one workgroup per (sample, head) instead of one per sample walking its heads
+    // in sequence - the rollout there is a chain of kernel latencies (robot shape: 11.6 -> 9.4 ms per rollout)
+    constexpr int pipe_min_b = 64;
+    return Tq <= 128 && !has_extra && S > 0 && B >= pipe_min_b && !dropout;
+}
+
 static int attention(const float *q, int ldq, const float *k, const float *v, int ldkv, const float *k_extra,
                      const float *v_extra, float *out, int ldo, int B, int Tq, int S, int d, int heads,
                      hipStream_t s, float *lse2 = nullptr, const DropoutArgs &da = DropoutArgs{}) {
@@ -1986,10 +2009,7 @@ static int attention(const float *q, int ldq, const float *k, const float *v, in
     ProfScope prof(SD_KCLASS_ATTENTION, s);
     const float sl2e = (1.0f / sqrtf((float)hd)) * 1.44269504088896340736f;
     dim3 grid(B * heads), block(256);
-    // small batches (the robot: B = 1): one workgroup per (sample, head) instead of one per sample walking its heads
-    // in sequence - the rollout there is a chain of kernel latencies (robot shape: 11.6 -> 9.4 ms per rollout)
-    constexpr int pipe_min_b = 64;
-    if (Tq <= 128 && !k_extra && S > 0 && B >= pipe_min_b && !da.thresh) {
+    if (attention_route(B, Tq, S, k_extra != nullptr, da.thresh != 0)) {
         dim3 gridp(B);
 #define SD_ATTNP(HD_)                                                                                            \
     do {                                                                                                         \
@@ -2113,6 +2133,78 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float *__restric
     }
 }
 
+// K = C*p beyond what patch_embed_kernel stages whole (K > 319: the image tokens of a hidden_dim-512 model, K = 512): the same 16 rows
+// and the same ascending-k fma chain per output, with the patches and W^T staged PE_KC values of k at a time; a thread keeps its
+// PE_RB * PE_DC / 256 = 4 outputs in registers across the chunks.  out[r][c] = sum_k x[r][k] w[c][k] + bias[c] + pe[r % n][c].
+// The 16 patch rows are staged again for every 64-column chunk (d / 64 times) on purpose: the column loop outside keeps the accumulators
+// at 4 registers for any d, and the shapes that come here are a few hundred rows of image tokens - no speed is claimed for it.
+constexpr int PE_RB = 16, PE_DC = 64, PE_KC = 128;
+__global__ __launch_bounds__(256) void patch_embed_bigk_kernel(const float *__restrict__ x, const float *__restrict__ w,
+                                                                const float *__restrict__ bias,
+                                                                const float *__restrict__ pe, float *__restrict__ out,
+                                                                long rows, int n_per_sample, int S, int C, int p, int d) {
+    __shared__ float sX[PE_RB * (PE_KC + 1)];   // [row][k + 1]
+    __shared__ float sW[PE_KC * PE_DC];         // [k][column]
+    const int K = C * p;
+    const int tid = threadIdx.x;
+    const long r0 = (long)blockIdx.x * PE_RB;
+    constexpr int PER = PE_RB * PE_DC / 256;
+    for (int c0 = 0; c0 < d; c0 += PE_DC) {
+        float acc[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) acc[j] = 0.f;
+        for (int k0 = 0; k0 < K; k0 += PE_KC) {
+            const int kn = min(PE_KC, K - k0);
+            __syncthreads();
+            for (int i = tid; i < PE_RB * PE_KC; i += 256) {
+                const int row = i / PE_KC, kc = i - row * PE_KC;
+                const long r = r0 + row;
+                float v = 0.f;
+                if (r < rows && kc < kn) {
+                    const long bidx = r / n_per_sample;
+                    const int n = (int)(r - bidx * n_per_sample);
+                    const int kk = k0 + kc;
+                    const int c = kk / p, t = kk - c * p;  // w is (d, C, p): kk = c*p + t
+                    v = x[((bidx * S) + (long)n * p + t) * C + c];
+                }
+                sX[row * (PE_KC + 1) + kc] = v;
+            }
+            for (int i = tid; i < PE_DC * PE_KC; i += 256) {
+                const int cc = i / PE_KC, kc = i - cc * PE_KC;
+                sW[kc * PE_DC + cc] = (c0 + cc < d && kc < kn) ? w[(long)(c0 + cc) * K + k0 + kc] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int i = tid + 256 * j;
+                const int row = i / PE_DC, cc = i - row * PE_DC;
+                float a = acc[j];
+                for (int kc = 0; kc < kn; ++kc) a = fmaf(sX[row * (PE_KC + 1) + kc], sW[kc * PE_DC + cc], a);
+                acc[j] = a;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / PE_DC, cc = i - row * PE_DC;
+            const long r = r0 + row;
+            const int c = c0 + cc;
+            if (r >= rows || c >= d) continue;
+            const int n = (int)(r % n_per_sample);
+            out[r * d + c] = acc[j] + bias[c] + pe[(long)n * d + c];
+        }
+    }
+}
+
+// The staging of patch_embed_kernel for K = C*p: rows per workgroup and the column chunk of W^T (0 = K does not fit: the K-chunked kernel)
+static void patch_embed_plan(int K, int d, int *RB, int *DC) {
+    *RB = (K <= 64) ? 64 : 16;
+    const long budget = 15360 - (long)*RB * (K + 1);  // floats (60 KB total)
+    long dc = budget > 0 ? (budget / K) / 32 * 32 : 0;
+    if (dc > d) dc = (d + 31) / 32 * 32;
+    *DC = dc < 32 ? 0 : (int)dc;
+}
+
 static int patch_embed(const float *x, const float *w, const float *b, const float *pe, float *out, int B, int S,
                        int C, int p, int d, hipStream_t s) {
     if (!x || !w || !b || !pe || !out || B <= 0 || S <= 0 || C <= 0 || p <= 0 || d <= 0)
@@ -2121,15 +2213,18 @@ static int patch_embed(const float *x, const float *w, const float *b, const flo
     if (n <= 0) return fail(SD_E_BADARG, "patch_embed: sequence shorter than one patch");
     const long rows = (long)B * n;
     const int K = C * p;
-    const int RB = (K <= 64) ? 64 : 16;
-    const long budget = 15360 - (long)RB * (K + 1);  // floats (60 KB total)
-    long DC = budget > 0 ? (budget / K) / 32 * 32 : 0;
-    if (DC > d) DC = (d + 31) / 32 * 32;
-    if (DC < 32) return fail(SD_E_TOOBIG, "patch_embed: C*p too large for LDS staging");
-    const size_t lds = ((size_t)RB * (K + 1) + (size_t)K * DC) * sizeof(float);
+    int RB, DC;
+    patch_embed_plan(K, d, &RB, &DC);
     ProfScope prof(SD_KCLASS_PATCH_EMBED, s);
+    if (!DC) {
+        SD_LAUNCH(patch_embed_bigk_kernel, dim3((unsigned)((rows + PE_RB - 1) / PE_RB)), dim3(256), 0, s, x, w, b, pe, out,
+                           rows, n, S, C, p, d);
+        SD_CHECK_LAUNCH("patch_embed_bigk_kernel");
+        return 0;
+    }
+    const size_t lds = ((size_t)RB * (K + 1) + (size_t)K * DC) * sizeof(float);
     SD_LAUNCH(patch_embed_kernel, dim3((unsigned)((rows + RB - 1) / RB)), dim3(256), lds, s, x, w, b, pe, out,
-                       rows, n, S, C, p, d, RB, (int)DC);
+                       rows, n, S, C, p, d, RB, DC);
     SD_CHECK_LAUNCH("patch_embed_kernel");
     return 0;
 }
@@ -3946,6 +4041,11 @@ extern "C" int sd_op_attention(const float *q, int ldq, const float *k, const fl
     if (!k_extra && !v_extra && att_op_f16(q, ldq, k, v, ldkv, ldo, B, Tq, S, d, heads, out))
         return attention_f16(q, out, B, Tq, d, heads, (hipStream_t)stream, false);
     return attention(q, ldq, k, v, ldkv, k_extra, v_extra, out, ldo, B, Tq, S, d, heads, (hipStream_t)stream);
+}
+
+extern "C" int sd_attention_route(int B, int Tq, int S, int has_extra, int dropout) {
+    if (B <= 0 || Tq <= 0 || S < 0 || S + (has_extra ? 1 : 0) <= 0) return fail(SD_E_BADARG, "sd_attention_route: empty shape");
+    return attention_route(B, Tq, S, has_extra != 0, dropout != 0);
 }
 
 extern "C" int sd_op_patch_embed(const float *x, const float *w, const float *b, const float *pe, float *out, int B,

@@ -484,6 +484,17 @@ __device__ __forceinline__ void f16_scores_prime(F16Scores &f, const F16LayerArg
     }
 }
 
+// a * b as ONE fp32 value in front of f16_split4.  Left to contraction, the compiler folds the product into the two conversions separately:
+// the hi plane from v_mul_f32 + v_cvt_pk_f16_f32 (two roundings), the lo plane from v_fma_mix (a, b, -RN16(exact a b)) - and where the exact
+// product and its fp32 rounding lie on either side of an fp16 tie the planes no longer add up: one fp16 ulp of hi, 2^-11 of that value
+// (one probability in ~10^4, 25 x the fp32 oracle's error on its row: tests/test_gpu_panel_grade.py).  A power-of-two scale cannot do this.
+// (`#pragma clang fp contract(off)` does not stop it: the fold is made on the conversion.  The empty asm makes the product a register value.)
+__device__ __forceinline__ float f16_mul_once(float a, float b) {
+    float v = a * b;
+    asm("" : "+v"(v));
+    return v;
+}
+
 // S^T of head `wave` on the fp16 pipe, softmax, P -> split planes (columns k = tl*64 + head*16 + slot, and the step
 // token's probability of head h at column 128 + h; columns 132..143 zero)
 template <int D>
@@ -560,7 +571,8 @@ __device__ __forceinline__ void f16_scores(float *sA, F16Scores &f, const F16Lay
         float pstep = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x4 t = {sc[tq][4 * q] * inv, sc[tq][4 * q + 1] * inv, sc[tq][4 * q + 2] * inv, sc[tq][4 * q + 3] * inv};
+            const f32x4 t = {f16_mul_once(sc[tq][4 * q], inv), f16_mul_once(sc[tq][4 * q + 1], inv), f16_mul_once(sc[tq][4 * q + 2], inv),
+                             f16_mul_once(sc[tq][4 * q + 3], inv)};
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if ((q & 1) * 8 + 4 * p.half + i == Mc && (q >> 1) * 16 == key_lo) pstep = t[i];

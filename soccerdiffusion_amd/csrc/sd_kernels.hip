@@ -575,12 +575,15 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void chain_a_kernel(ChainA
     extern __shared__ __attribute__((aligned(16))) float sA[];
     const ChainPos<D> p(g.R);
     const float *aBase = sA + (p.wm * C::WM + p.l31) * C::LDA + 4 * p.half;
-    f32x16 H[C::TM][C::TN];
+    f32x16 H[C::TM][C::TN], U[C::TM][C::TN];
     chain_load_acc<D>(H, g.h, p);   // issued first: in flight while the panel lands
     chain_load_panel<D>(sA, g.a, p);
     __syncthreads();
-    chain_gemm<D>(H, aBase, g.wo + (long)(p.wn * C::WN + p.l31) * D + 4 * p.half);
-    chain_bias_act<D, 0>(H, g.bo, p);
+    // the out-projection runs in U and meets the residual in ONE addition (see chain_b_kernel)
+    chain_zero<D>(U);
+    chain_gemm<D>(U, aBase, g.wo + (long)(p.wn * C::WN + p.l31) * D + 4 * p.half);
+    chain_bias_act<D, 0>(U, g.bo, p);
+    chain_add<D>(H, U);
     chain_store_acc<D>(g.h, D, 0, H, p);
     __syncthreads();  // every wave is done reading the panel
     chain_acc_to_lds<D>(sA, H, p);
@@ -1094,12 +1097,16 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_layer_kernel(
     chain_load_panel<D>(sA, g.a.a, p);
     __syncthreads();
     SD_STAMP(g.slot, 1);
-    chain_gemm_primed<D>(H, aBase, g.a.wo + wOff, ring);   // h += a Wo^T + bo   (self-attention out)
+    // The three out-projections of the layer (Wo, Woc or P V', W2) run in U - idle at each of them - and meet the residual in ONE addition:
+    // accumulated in H, every one of their MFMAs would round at the magnitude of the residual stream (see chain_b_kernel)
+    chain_zero<D>(U);
+    chain_gemm_primed<D>(U, aBase, g.a.wo + wOff, ring);   // h += a Wo^T + bo   (self-attention out)
     SD_STAMP(g.slot, 2);
     if constexpr (FOLD) {
         FoldState<D> fs;
         fold_prime<D>(fs, g, p);          // G rows + score bias in flight behind the epilogue and LN2
-        chain_bias_act<D, 0>(H, g.a.bo, p);
+        chain_bias_act<D, 0>(U, g.a.bo, p);
+        chain_add<D>(H, U);
         __syncthreads();
         chain_acc_to_lds<D>(sA, H, p);
         __syncthreads();
@@ -1111,11 +1118,13 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_layer_kernel(
         panel_folded_scores<D>(sA, fs, g, p, vr, voff);
         __syncthreads();
         SD_STAMP(g.slot, 5);
-        panel_folded_pv<D>(H, aBase, fs.gbase, voff, fs.n_traj, vr);   // h += P V' + boc
+        chain_zero<D>(U);
+        panel_folded_pv<D>(U, aBase, fs.gbase, voff, fs.n_traj, vr);   // h += P V' + boc
         SD_STAMP(g.slot, 6);
     } else {
         chain_prime<D>(ring, g.a.wq + wOff);
-        chain_bias_act<D, 0>(H, g.a.bo, p);
+        chain_bias_act<D, 0>(U, g.a.bo, p);
+        chain_add<D>(H, U);
         __syncthreads();
         chain_acc_to_lds<D>(sA, H, p);
         __syncthreads();
@@ -1134,10 +1143,12 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_layer_kernel(
         }
         chain_prime<D>(ring, g.b.wo + wOff);   // primed after the attention: its 24 registers are needed there
         __syncthreads();
-        chain_gemm_primed<D>(H, aBase, g.b.wo + wOff, ring);   // h += a_c Woc^T + boc
+        chain_zero<D>(U);
+        chain_gemm_primed<D>(U, aBase, g.b.wo + wOff, ring);   // h += a_c Woc^T + boc
     }
     chain_prime<D>(ring, g.b.w1 + wOff);
-    chain_bias_act<D, 0>(H, g.b.bo, p);
+    chain_bias_act<D, 0>(U, g.b.bo, p);
+    chain_add<D>(H, U);
     __syncthreads();
     chain_acc_to_lds<D>(sA, H, p);
     __syncthreads();
@@ -1152,10 +1163,12 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_layer_kernel(
     chain_gelu_to_lds<D>(sA, U, g.b.b1, p);
     __syncthreads();
     SD_STAMP(g.slot, 9);
-    chain_gemm_primed<D>(H, aBase, g.b.w2 + wOff, ring);   // h += u W2^T + b2
+    chain_zero<D>(U);                    // (its GELU tile went to the panel above)
+    chain_gemm_primed<D>(U, aBase, g.b.w2 + wOff, ring);   // h += u W2^T + b2
     SD_STAMP(g.slot, 10);
     if constexpr (TAIL) {
-        chain_bias_act<D, 0>(H, g.b.b2, p);
+        chain_bias_act<D, 0>(U, g.b.b2, p);
+        chain_add<D>(H, U);
         __syncthreads();                 // last layer: eps = h Wout^T + b (+ DDIM update of x) right here
         chain_acc_to_lds<D>(sA, H, p);
         __syncthreads();
@@ -1166,7 +1179,8 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void decoder_layer_kernel(
     }
     const bool has_next = g.b.nln_w != nullptr;            // workgroup-uniform
     if (has_next) chain_prime<D>(ring, g.b.wqkv + wOff);
-    chain_bias_act<D, 0>(H, g.b.b2, p);
+    chain_bias_act<D, 0>(U, g.b.b2, p);
+    chain_add<D>(H, U);
     chain_store_acc<D>(g.a.h, D, 0, H, p);
     if (!has_next) return;
     SD_STAMP(g.slot, 11);

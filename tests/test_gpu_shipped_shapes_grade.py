@@ -6,7 +6,6 @@ cross-attention softmax, and operands 2^k away from what the fixed activation sc
 The yardstick is always the fp32 CPU oracle's own error against the fp64 oracle on the same inputs.  Every gated tensor prints one
 line (python -m pytest -s; profiles/shipped_shapes_parity.txt is that output)."""
 
-import functools
 import math
 
 import pytest
@@ -14,12 +13,12 @@ import torch
 
 from oracle import ddim_ref
 from oracle import denoiser_ref as ref
+from panel_cases import LAYER, N_SCHEDULE, N_STEPS, PAIRS, RESCALE_SHAPES
+from panel_cases import gpu_tokens as _gpu_tokens, oracle_rollout as _oracle_rollout, rescale_base as _rescale_base
+from panel_cases import rescaled as _rescaled, schedule as _schedule
 from parity import Errors, assert_fp32_grade, errors, report
 
 gpu = pytest.mark.gpu
-LAYER = "diffusion_action_generator.transformer_decoder.layers.{}."
-N_SCHEDULE = 50   # the first steps of the 50-step schedule: t = 980, 960, 940, 920 (|x| stays at its t ~ T level, as in a rollout's start)
-N_STEPS = 4
 
 SHIPPED = [
     # d, T, Mc, J, L, B
@@ -85,28 +84,6 @@ def _factor(shape):
 
 def _case_id(v):
     return "-".join(str(i) for i in v) if isinstance(v, tuple) else None
-
-
-def _schedule():
-    acp = ddim_ref.alphas_cumprod()
-    ts = ddim_ref.timesteps(N_SCHEDULE).tolist()
-    return acp, ts
-
-
-def _oracle_rollout(sd, ctx, x_T, dtype, n_steps):
-    """The reference's loop (ddim_ref.sample's body) over the first n_steps of the 50-step schedule: x after every step and every noise
-    prediction, in `dtype`."""
-    acp, ts = _schedule()
-    B = x_T.shape[0]
-    x = x_T.to(dtype)
-    xs, eps = [], []
-    for t in ts[:n_steps]:
-        e = ref.forward_with_context(sd, [ctx] if ctx is not None else [], x, torch.full((B,), t, dtype=torch.int64), dtype=dtype)
-        x = ddim_ref.step(e, t, x, N_SCHEDULE, acp)
-        assert x.dtype == dtype
-        eps.append(e)
-        xs.append(x)
-    return xs, eps
 
 
 def _mode3(ops, sd, ctx, toks, coef, x, T):
@@ -297,59 +274,9 @@ def test_sharp_ordered_memory_through_the_streamed_softmax(shape, A, gain, least
 # ------------------------------------------------------------------------------------------------------------------------------------
 # 4. function-preserving rescaling by powers of two
 # ------------------------------------------------------------------------------------------------------------------------------------
-RESCALE_SHAPES = [(256, 100, 10, 20, 2, 2), (128, 10, 40, 20, 2, 2)]   # tuned (folded) and generic
-PAIRS = ["norm1", "norm2", "norm3", "self_v", "cross_v", "memory"]
+# RESCALE_SHAPES (tuned, folded; generic), PAIRS and the construction itself: tests/panel_cases.py, shared with the row-panel suite
 GRADE_K = [-4, 4]
 RANGE_K = [-12, -8, 8]
-
-
-@functools.lru_cache(maxsize=None)
-def _rescale_base(shape):
-    """Unscaled weights, inputs, the memory (context rows and the oracle's own step token at t = 980) and both oracles' outputs."""
-    d, T, Mc, J, L, B = shape
-    sd = ref.synthetic_state_dict(d, J, L, seed=53 + d)
-    g = torch.Generator().manual_seed(d + T)
-    x = torch.randn(B, T, J, generator=g)
-    ctx = torch.randn(B, Mc, d, generator=g)
-    tok = ref.step_token(torch.tensor([980]), sd["step_encoding.token"].float(), d)           # (1, 1, d)
-    mem = torch.cat([ctx, tok.expand(B, 1, d)], 1)
-    want64 = ref.denoiser_forward(sd, x, mem, dtype=torch.float64)
-    want32 = ref.denoiser_forward(sd, x, mem)
-    return sd, x, ctx, tok, want64, want32
-
-
-def _rescaled(shape, pairs, k):
-    """Producer x 2^-k, consumer x 2^k for every pair named: the same function, bit for bit in fp32, on operands 2^k away from where
-    the kernels' fixed activation scales expect them.  'memory' scales every memory row - the context and the step token handed to the
-    sampler - against the K | V rows of the cross-attention's in_proj_weight."""
-    sd0, x, ctx, tok, _, _ = _rescale_base(shape)
-    d, L = shape[0], shape[4]
-    sd = {key: v.clone() for key, v in sd0.items()}
-    down, up = 2.0 ** -k, 2.0 ** k
-    for l in range(L):
-        pre = LAYER.format(l)
-        for p in pairs:
-            if p in ("norm1", "norm2", "norm3"):
-                sd[pre + p + ".weight"] *= down
-                sd[pre + p + ".bias"] *= down
-                if p == "norm1":
-                    sd[pre + "self_attn.in_proj_weight"] *= up
-                elif p == "norm2":
-                    sd[pre + "multihead_attn.in_proj_weight"][:d] *= up
-                else:
-                    sd[pre + "linear1.weight"] *= up
-            elif p in ("self_v", "cross_v"):
-                att = "self_attn" if p == "self_v" else "multihead_attn"
-                sd[pre + att + ".in_proj_weight"][2 * d:] *= down
-                sd[pre + att + ".in_proj_bias"][2 * d:] *= down
-                sd[pre + att + ".out_proj.weight"] *= up
-            elif p == "memory":
-                sd[pre + "multihead_attn.in_proj_weight"][d:] *= up
-            else:
-                raise KeyError(p)
-    if "memory" in pairs:
-        ctx, tok = ctx * down, tok * down
-    return sd, x, ctx, tok
 
 
 RESCALE_CASES = [(s, (p,), k) for s in RESCALE_SHAPES for p in PAIRS for k in GRADE_K + RANGE_K] + \

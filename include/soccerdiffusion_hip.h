@@ -897,6 +897,30 @@ int sd_bn_relu_pool_fwd(const float *y, const float *gamma, const float *beta, f
                         void *stream);
 int sd_bn_relu_pool_bwd(const float *dp, const uint32_t *idx, const float *y, const float *mean, const float *rstd, const float *gamma, float *dy,
                         float *dgamma, float *dbeta, double *acc, float *scratch, uint32_t *dy_amax, int N, int Hc, int Wc, int C, void *stream);
+/* BatchNorm on FROZEN statistics inside a training backbone (bn.eval(): fine-tuning on the running statistics, which are never written).
+ *   sd_bn_frozen_fold: rstd = 1 / sqrt(running_var + eps), s = gamma rstd, t = beta - running_mean s (C floats each, formed in double); runs on
+ *     the device with every forward, so a captured training step folds what the optimizer last wrote.
+ *   sd_bn_frozen_fwd: z = relu?(y s + t (+ res)) and the abs-max word of z - the forward of a unit whose affine pair is TRAINED (y is kept for
+ *     dgamma).  Where the pair needs no gradient the forward is the inference launch (sd_conv3x3_bn_act / sd_conv_s2_bn_act with s, t) and y
+ *     is never written.
+ *   sd_bn_frozen_bwd: g = dz behind the ReLU mask, dres (or NULL) = g, dy = g s, dy_amax = the bits of max |dy|.  dgamma NULL (with dbeta, y, t,
+ *     running_mean, rstd, acc, scratch unused): ONE element-wise launch, the mask is z > 0.  Otherwise dbeta = sum g, dgamma = sum g (y -
+ *     running_mean) rstd from the same single pass over the tensors (partial sums in scratch, added up in double in a fixed order into acc: no
+ *     atomics, two runs agree bit for bit); z NULL with relu and no residual operand: the mask is recomputed from y, s, t.
+ *   sd_bn_frozen_relu_pool_fwd / _bwd: the stem, max_pool(relu(y s + t), 3, 2, 1) with the window scan, tie rule and index bytes of
+ *     sd_bn_relu_pool_fwd; the backward in one pass (dy = g s; dgamma / dbeta as above, or both NULL); scratch: sd_bn_scratch_floats(N Hc Wc, C). */
+int sd_bn_frozen_fold(const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int C, float *s, float *t,
+                      float *rstd, void *stream);
+int sd_bn_frozen_fwd(const float *y, const float *s, const float *t, const float *res, float *z, uint32_t *z_amax, int64_t npix, int C, int relu,
+                     void *stream);
+int sd_bn_frozen_bwd(const float *dz, const float *z, const float *y, const float *s, const float *t, const float *running_mean, const float *rstd,
+                     float *dy, float *dres, float *dgamma, float *dbeta, double *acc, float *scratch, uint32_t *dy_amax, int64_t npix, int C, int relu,
+                     void *stream);
+int sd_bn_frozen_relu_pool_fwd(const float *y, const float *s, const float *t, float *p, uint32_t *idx, uint32_t *p_amax, int N, int Hc, int Wc, int C,
+                               void *stream);
+int sd_bn_frozen_relu_pool_bwd(const float *dp, const uint32_t *idx, const float *y, const float *s, const float *running_mean, const float *rstd,
+                               float *dy, float *dgamma, float *dbeta, double *acc, float *scratch, uint32_t *dy_amax, int N, int Hc, int Wc, int C,
+                               void *stream);
 /* The stem in training: sd_stem_conv_raw = the bare 7 x 7 / stride-2 / padding-3 convolution of sd_stem_conv_bn_relu_pool (same packed planes,
  * same kernel) -> y_raw (N, Hc, Wc, 64) NHWC, Hc = (H - 1) / 2 + 1; sd_stem_wgrad: its weight gradient dw (64, 3, 7, 7) from dy (N, Hc, Wc, 64)
  * and the frames x (N, 3, H, W), both with their abs-max words; scratch: sd_stem_wgrad_scratch_floats(N, H, W) floats.  (The frames need no gradient.) */

@@ -160,6 +160,11 @@ SIGNATURES = {
     "sd_bn_relu_pool_fwd": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "sd_bn_relu_pool_bwd": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sd_bn_train_bwd": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "sd_bn_frozen_fold": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int] + [C.c_void_p] * 4),
+    "sd_bn_frozen_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "sd_bn_frozen_bwd": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "sd_bn_frozen_relu_pool_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "sd_bn_frozen_relu_pool_bwd": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 4 + [C.c_void_p]),
     "sd_conv_wgrad": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
     "sd_conv_wgrad_scratch_floats": (C.c_size_t, [C.c_int] * 7),
     "sd_stem_conv_raw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),

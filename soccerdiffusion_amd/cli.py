@@ -2,9 +2,9 @@
 the reference's scripts (soccer_diffusion/ml/training/train.py:26-253,
 soccer_diffusion/ml/inference/plot.py:21-135).
 
-    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]
+    python -m soccerdiffusion_amd.cli train -c cfg.yaml [-p ckpt] [-o out] [--decoder-pretraining] [--pretrained-decoder p] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X] [--freeze-bn stats|all] [--pretrained-backbone FILE]
     python -m soccerdiffusion_amd.cli sample ckpt [--steps 30] [--solver ddim|multistep] [--num_samples 10] [--ema] [--draws G] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]]
-    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X]     (ml/training/distill.py:25-224)
+    python -m soccerdiffusion_amd.cli distill cfg.yaml teacher_ckpt [-o out] [--ema-teacher] [--ema-decay D [--no-ema-warmup]] [--clip-grad-norm X] [--freeze-bn stats|all]     (ml/training/distill.py:25-224)
     python -m soccerdiffusion_amd.cli evaluate ckpt --synthetic N [--val-fraction F | --all] [--steps 30] [--solver ddim|multistep] [--draws G] [--grid K | --timesteps a,b,..] [--ema] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]] [-o report.json]   (evaluation.py)
     python -m soccerdiffusion_amd.cli rollout ckpt --synthetic N --ticks K [-o out.pt] [--steps 30] [--solver ddim|multistep] [--seed S] [--raw [--camera HxW]] [--ema] [--carry K [--advance S]] [--hold J=V[,J=V...]] [--limits J=LO:HI[,J=LO:HI...] | --clip R] [--reproject] [--slew V | J=V[,J=V...]] [--accel A | J=A[,J=A...]] [--draws G [--select medoid|coherent [--coherence-decay R] [--contrast L]]]   (ml/inference/ros.py:165-335)
 
@@ -227,6 +227,63 @@ def _grad_clip_checkpoint_keys(optimizer) -> dict:
     return {"grad_clip": {"max_norm": optimizer.max_grad_norm, "skipped_steps": optimizer.grad_stats()["skipped_steps"]}}
 
 
+FREEZE_BN_MODES = ("stats", "all")
+
+
+def validate_freeze_bn(mode: Optional[str], params: dict) -> Optional[str]:
+    """``--freeze-bn`` against the run's hyperparameters: the mode, or the end of the command where there is no ResNet image encoder to freeze."""
+    if mode is None:
+        return None
+    if mode not in FREEZE_BN_MODES:
+        raise SystemExit(f"--freeze-bn takes one of {', '.join(FREEZE_BN_MODES)}, got {mode!r}")
+    if not params.get("use_images"):
+        raise SystemExit("--freeze-bn: this configuration has no image encoder (use_images is false)")
+    if params.get("image_encoder_type") not in ("resnet18", "resnet50"):
+        raise SystemExit(f"--freeze-bn: image_encoder_type {params.get('image_encoder_type')!r} has no BatchNorm layers (resnet18 / resnet50 only)")
+    return mode
+
+
+def apply_freeze_bn(model, mode: Optional[str]) -> None:
+    """stats: every BatchNorm2d of the image encoder normalises with its running statistics and stops updating them; all: its weight and bias
+    are frozen too (the optimizer is built afterwards and owns only what requires a gradient)."""
+    if mode is not None:
+        from .ml.model.encoder.image import freeze_batchnorm
+
+        freeze_batchnorm(model.image_sequence_encoder, affine=mode == "all")
+
+
+def _freeze_bn_checkpoint_keys(mode: Optional[str]) -> dict:
+    return {} if mode is None else {"freeze_bn": mode}
+
+
+def load_pretrained_backbone(model, path: str) -> tuple:
+    """Loads a state dict with torchvision's ResNet keys (a torchvision checkpoint, or ``backbone.state_dict()`` of this package) into the
+    image encoder's backbone: every tensor whose name and shape match, except the classifier ``fc.*`` (the encoder has its own head).
+    -> (loaded names, skipped names); the skipped ones are logged."""
+    from .ml.model.encoder.image import _ResNet
+
+    enc = getattr(model, "image_sequence_encoder", None)
+    backbone = None if enc is None else next((m for m in enc.modules() if isinstance(m, _ResNet)), None)
+    if backbone is None:
+        raise SystemExit("--pretrained-backbone: this configuration has no ResNet image encoder")
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    own = backbone.state_dict()
+    loaded, skipped = [], []
+    for name, value in state.items():
+        if not name.startswith("fc.") and name in own and tuple(own[name].shape) == tuple(value.shape):
+            loaded.append(name)
+        else:
+            skipped.append(name)
+    backbone.load_state_dict({k: state[k] for k in loaded}, strict=False)
+    missing = [k for k in own if k not in loaded and not k.startswith("fc.")]
+    logger.info("--pretrained-backbone: loaded %d tensors from %s", len(loaded), path)
+    if skipped:
+        logger.warning("--pretrained-backbone: not loaded from the file (fc.*, unknown name or other shape): %s", ", ".join(skipped))
+    if missing:
+        logger.warning("--pretrained-backbone: not in the file, left as initialised: %s", ", ".join(missing))
+    return loaded, skipped
+
+
 def shard_plan(n_total: int, batch_size: int, rank: int, world: int):
     """Sample indices of this rank and the number of optimizer steps per epoch, the SAME on every rank.
 
@@ -290,6 +347,8 @@ def cmd_train(args) -> int:
         params = dict(config_params)
     if params["train_denoising_timesteps"] != 1000:
         raise SystemExit("train_denoising_timesteps must be 1000 (the scheduler table length; see scheduler.py)")
+    # a resumed run goes on with its BatchNorm layers as they were
+    freeze_bn = validate_freeze_bn(args.freeze_bn if args.freeze_bn is not None or checkpoint is None else checkpoint.get("freeze_bn"), params)
 
     gen = torch.Generator().manual_seed(args.seed + rank)
     source = data_source(args, params, device)
@@ -313,6 +372,9 @@ def cmd_train(args) -> int:
     if args.pretrained_decoder is not None:
         pre = torch.load(args.pretrained_decoder, map_location="cpu", weights_only=True)
         model.load_state_dict(pre["model_state_dict"], strict=False)
+    if args.pretrained_backbone is not None:
+        load_pretrained_backbone(model, args.pretrained_backbone)
+    apply_freeze_bn(model, freeze_bn)   # (before the optimizer: it owns the parameters that require a gradient)
     model.train()
     model.set_dropout(args.dropout, seed=args.seed + 7919 * rank)   # every rank its own mask stream
 
@@ -364,6 +426,7 @@ def cmd_train(args) -> int:
             torch.save({"model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
                         "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model), **_grad_clip_checkpoint_keys(optimizer),
+                        **_freeze_bn_checkpoint_keys(freeze_bn),
                         **({} if val is None else {"validation": val.entry()})},
                        args.output)
     if world > 1:
@@ -396,16 +459,19 @@ def cmd_distill(args) -> int:
         elif value != teacher_params[key]:
             logger.warning("parameter %s differs from the teacher checkpoint: %r != %r", key, teacher_params[key], value)
     params["distilled_decoder"] = True  # flags the student (distill.py:62)
+    freeze_bn = validate_freeze_bn(args.freeze_bn if args.freeze_bn is not None else checkpoint.get("freeze_bn"), params)
 
     teacher = build_model(params).to(device)
     teacher.load_state_dict(ema_model_state(checkpoint, "--ema-teacher", args.checkpoint) if args.ema_teacher else checkpoint["model_state_dict"])
     # distill.py:127-131 never calls teacher_model.eval(): the reference's teacher rollout (and its context encoders) run
     # with dropout 0.1 live.  --teacher-dropout reproduces that (a Python loop over the training kernels); the default
     # is the clean teacher on the native sampler.
+    apply_freeze_bn(teacher, freeze_bn)   # (with --teacher-dropout the teacher's backbone is in train mode: its statistics stay as trained)
     teacher.train(args.teacher_dropout)
     teacher.set_dropout(args.dropout if args.teacher_dropout else 0.0, seed=args.seed + 104729 + 7919 * rank)
     student = build_model(params).to(device)
     student.load_state_dict(checkpoint["model_state_dict"])
+    apply_freeze_bn(student, freeze_bn)
     student.train()
     student.set_dropout(args.dropout, seed=args.seed + 7919 * rank)
     # the student's context encoders never see a gradient (the context comes from the teacher under
@@ -460,6 +526,7 @@ def cmd_distill(args) -> int:
             torch.save({"model_state_dict": student.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
                         "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, student), **_grad_clip_checkpoint_keys(optimizer),
+                        **_freeze_bn_checkpoint_keys(freeze_bn),
                         **({} if val is None else {"validation": val.entry()})},
                        args.output)
     if world > 1:
@@ -1014,7 +1081,12 @@ def build_parser() -> argparse.ArgumentParser:
     di.add_argument("--teacher-dropout", action="store_true", help="leave the teacher in train mode during its rollout, as the "
                     "reference's distill.py does (it never calls teacher_model.eval())")
     di.add_argument("--ema-teacher", action="store_true", help="build the teacher from the checkpoint's EMA weights (train --ema-decay)")
+    tr.add_argument("--pretrained-backbone", type=str, default=None, metavar="FILE", help="state dict with torchvision's ResNet keys: every tensor "
+                    "whose name and shape match is loaded into the image encoder's backbone, except fc.* (what --freeze-bn is for)")
     for p in (tr, di):
+        p.add_argument("--freeze-bn", choices=FREEZE_BN_MODES, default=None, help="fine-tune on frozen BatchNorm statistics: every BatchNorm2d of "
+                       "the ResNet image encoder normalises with its running statistics and leaves them alone (stats); all: its weight and bias "
+                       "are frozen too; the checkpoint gains freeze_bn and a resumed run continues as it did")
         p.add_argument("--ema-decay", type=_ema_decay, default=None, metavar="D", help="keep an exponential moving average of the trained "
                        "weights with decay D in (0, 1), updated inside the optimizer step; the checkpoint gains ema_model_state_dict and ema")
         p.add_argument("--clip-grad-norm", type=_clip_grad_norm, default=None, metavar="X", help="clip the global 2-norm of the gradient to X "

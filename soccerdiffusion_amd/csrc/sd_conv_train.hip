@@ -16,6 +16,7 @@
 // output parity class, sd_convt1x1_s2), no zero-dilated dY (host side: soccerdiffusion_amd/conv_training.py).
 #include "../../include/soccerdiffusion_hip.h"
 #include "sd_common.h"
+#include <initializer_list>
 #include <stdlib.h>
 
 namespace cvt {
@@ -391,6 +392,177 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const float *__r
         const unsigned b = __builtin_bit_cast(unsigned, mx);
         if ((threadIdx.x & 63) == 0 && b > __atomic_load_n(amax, __ATOMIC_RELAXED)) atomicMax(amax, b);
     }
+}
+
+// ---- BatchNorm on FROZEN statistics (bn.eval() inside a training backbone: fine-tuning on the running statistics, which are not written).
+// Per channel rstd = 1 / sqrt(running_var + eps), s = gamma rstd, t = beta - running_mean s; z = relu?(y s + t (+ res)).  There is no
+// statistics pass and no mean term in dy: g = dz behind the ReLU mask, dres = g, dy = g s, dbeta = sum g, dgamma = sum g (y - running_mean) rstd.
+// The fold runs on the device with every forward (a captured training step replays it after the optimizer's in-place updates).
+__global__ void bn_frozen_fold_kernel(const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ running_mean,
+                                      const float *__restrict__ running_var, float eps, int C, float *s, float *t, float *rstd) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double r = 1.0 / sqrt((double)running_var[c] + (double)eps);
+    const float sf = (float)((double)gamma[c] * r);
+    s[c] = sf;
+    rstd[c] = (float)r;
+    t[c] = (float)((double)beta[c] - (double)running_mean[c] * (double)sf);   // (with the ROUNDED s: y s + t = (y - running_mean) s + beta)
+}
+// one expression (explicit fmas) for the forward and for the backward's recomputed ReLU mask: the same bits
+__device__ __forceinline__ f32x4 bn_frozen_affine(const f32x4 &y, const float *s, const float *t, int c0) {
+    const f32x4 sv = *reinterpret_cast<const f32x4 *>(s + c0), tv = *reinterpret_cast<const f32x4 *>(t + c0);
+    return f32x4{__builtin_fmaf(y[0], sv[0], tv[0]), __builtin_fmaf(y[1], sv[1], tv[1]), __builtin_fmaf(y[2], sv[2], tv[2]), __builtin_fmaf(y[3], sv[3], tv[3])};
+}
+__device__ __forceinline__ void amax_word_max(float mx, unsigned *amax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const unsigned b = __builtin_bit_cast(unsigned, mx);
+    if ((threadIdx.x & 63) == 0 && b > __atomic_load_n(amax, __ATOMIC_RELAXED)) atomicMax(amax, b);
+}
+__device__ __forceinline__ float absmax4(const f32x4 &v) { return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))); }
+// z = relu?(y s + t (+ res)); abs-max of z -> word  (the forward of a unit whose affine pair is trained: y is kept for dgamma)
+__global__ __launch_bounds__(256) void bn_frozen_apply_kernel(const float *__restrict__ y, const float *__restrict__ s, const float *__restrict__ t,
+                                                              const float *__restrict__ res, float *__restrict__ z, long n4, int C, int relu,
+                                                              unsigned *amax) {
+    float mx = 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const int c0 = (int)((4 * i) % C);
+        f32x4 v = bn_frozen_affine(*reinterpret_cast<const f32x4 *>(y + 4 * i), s, t, c0);
+        if (res) v = v + *reinterpret_cast<const f32x4 *>(res + 4 * i);
+        if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+        *reinterpret_cast<f32x4 *>(z + 4 * i) = v;
+        mx = fmaxf(mx, absmax4(v));
+    }
+    if (amax) amax_word_max(mx, amax);
+}
+// the whole backward of a unit whose affine pair needs no gradient: g = dz [z > 0] -> dres (if asked), dy = g s, abs-max of dy -> word
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ z, const float *__restrict__ s,
+                                                            float *__restrict__ dy, float *__restrict__ dres, long n4, int C, int relu, unsigned *amax) {
+    float mx = 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const int c0 = (int)((4 * i) % C);
+        f32x4 g = *reinterpret_cast<const f32x4 *>(dz + 4 * i);
+        if (relu) {
+            const f32x4 zz = *reinterpret_cast<const f32x4 *>(z + 4 * i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = zz[e] > 0.f ? g[e] : 0.f;
+        }
+        if (dres) *reinterpret_cast<f32x4 *>(dres + 4 * i) = g;
+        const f32x4 v = g * *reinterpret_cast<const f32x4 *>(s + c0);
+        *reinterpret_cast<f32x4 *>(dy + 4 * i) = v;
+        mx = fmaxf(mx, absmax4(v));
+    }
+    if (amax) amax_word_max(mx, amax);
+}
+// ... and with a trained affine pair: the same element-wise work inside the per-channel reduction's ONE pass over dz / y (/ z) - dy does not
+// depend on the sums - leaving the workgroups' partial (sum g, sum g (y - running_mean) rstd) for partial_sum_kernel.  z NULL with relu: the
+// mask is recomputed from y (a unit without residual operand).
+struct BnFrozenLoad { f32x4 g, z, y; long at; };
+__global__ __launch_bounds__(256) void bn_frozen_bwd_sums_kernel(const float *__restrict__ dz, const float *__restrict__ z, const float *__restrict__ y,
+                                                                 const float *__restrict__ s, const float *__restrict__ t,
+                                                                 const float *__restrict__ running_mean, const float *__restrict__ rstd,
+                                                                 float *__restrict__ dy, float *__restrict__ dres, long npix, int C, int relu, float *part,
+                                                                 unsigned *amax) {
+    float mx = 0.f;
+    channel_reduce<BnFrozenLoad>(
+        npix, C, part,
+        [&](long p, int c0) {
+            BnFrozenLoad v;
+            v.at = p * C + c0;
+            v.g = *reinterpret_cast<const f32x4 *>(dz + v.at);
+            v.y = *reinterpret_cast<const f32x4 *>(y + v.at);
+            v.z = (relu && z) ? *reinterpret_cast<const f32x4 *>(z + v.at) : f32x4{1.f, 1.f, 1.f, 1.f};
+            return v;
+        },
+        [&](const BnFrozenLoad &v, int c0, f32x4 &sum, f32x4 &q) {
+            f32x4 g = v.g;
+            const f32x4 zz = (relu && !z) ? bn_frozen_affine(v.y, s, t, c0) : v.z;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = zz[e] > 0.f ? g[e] : 0.f;
+            if (dres) *reinterpret_cast<f32x4 *>(dres + v.at) = g;
+            const f32x4 d = g * *reinterpret_cast<const f32x4 *>(s + c0);
+            *reinterpret_cast<f32x4 *>(dy + v.at) = d;
+            mx = fmaxf(mx, absmax4(d));
+            sum = sum + g;
+            q = q + g * ((v.y - *reinterpret_cast<const f32x4 *>(running_mean + c0)) * *reinterpret_cast<const f32x4 *>(rstd + c0));
+        });
+    if (amax) amax_word_max(mx, amax);
+}
+__global__ void bn_frozen_dparams_kernel(const double *__restrict__ acc, int C, float *dgamma, float *dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    dgamma[c] = (float)acc[2 * c + 1];
+    dbeta[c] = (float)acc[2 * c];
+}
+// the stem on frozen statistics: bn_relu_pool_fwd_kernel's pass (same window scan, same tie rule, same index bytes) with the folded affine ...
+__global__ __launch_bounds__(256) void bn_frozen_relu_pool_fwd_kernel(const float *__restrict__ y, const float *__restrict__ s, const float *__restrict__ t,
+                                                                      float *__restrict__ p, unsigned *__restrict__ idx, int N, int Hc, int Wc, int Hp,
+                                                                      int Wp, int C, unsigned *amax) {
+    const unsigned cg = C / 4;
+    const unsigned n4 = (unsigned)N * Hp * Wp * cg;
+    float mx = 0.f;
+    for (unsigned e = xcd_band_id() * blockDim.x + threadIdx.x; e < n4; e += gridDim.x * blockDim.x) {
+        const int c0 = (int)(e % cg) * 4;
+        unsigned u = e / cg;
+        const int j = (int)(u % (unsigned)Wp); u /= (unsigned)Wp;
+        const int i = (int)(u % (unsigned)Hp);
+        const int n = (int)(u / (unsigned)Hp);
+        f32x4 m = {0.f, 0.f, 0.f, 0.f};
+        unsigned k[4] = {9u, 9u, 9u, 9u};
+        f32x4 yv[9];   // (all nine loads first, from clamped coordinates: as bn_relu_pool_fwd_kernel)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int r = 2 * i - 1 + ky, rc = r < 0 ? 0 : (r >= Hc ? Hc - 1 : r);
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int c = 2 * j - 1 + kx, cc = c < 0 ? 0 : (c >= Wc ? Wc - 1 : c);
+                yv[ky * 3 + kx] = *reinterpret_cast<const f32x4 *>(y + (((long)n * Hc + rc) * Wc + cc) * C + c0);
+            }
+        }
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int r = 2 * i - 1 + ky;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int c = 2 * j - 1 + kx;
+                const bool in = r >= 0 && r < Hc && c >= 0 && c < Wc;
+                const f32x4 v = bn_frozen_affine(yv[ky * 3 + kx], s, t, c0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (in && v[q] > m[q]) {
+                        m[q] = v[q];
+                        k[q] = (unsigned)(ky * 3 + kx);
+                    }
+            }
+        }
+        *reinterpret_cast<f32x4 *>(p + 4l * e) = m;
+        idx[e] = k[0] | (k[1] << 8) | (k[2] << 16) | (k[3] << 24);
+        mx = fmaxf(mx, fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
+    }
+    if (amax) amax_word_max(mx, amax);
+}
+// ... and its backward in ONE pass over the 2 x 2 blocks of convolution pixels (pool_block): dy = g s, and the partial sums for dgamma / dbeta
+__global__ __launch_bounds__(256) void bn_frozen_pool_bwd_kernel(const float *__restrict__ dp, const unsigned *__restrict__ idx, const float *__restrict__ y,
+                                                                 const float *__restrict__ s, const float *__restrict__ running_mean,
+                                                                 const float *__restrict__ rstd, float *__restrict__ dy, long nitems, PoolGeom G, float *part,
+                                                                 unsigned *amax) {
+    float mx = 0.f;
+    channel_reduce<PoolBlock, 1>(
+        nitems, G.C, part, [&](long p, int c0) { return pool_block(dp, idx, y, G, (unsigned)p, c0); },
+        [&](const PoolBlock &v, int c0, f32x4 &sum, f32x4 &q) {
+            const f32x4 mu = *reinterpret_cast<const f32x4 *>(running_mean + c0), rs = *reinterpret_cast<const f32x4 *>(rstd + c0);
+            const f32x4 sv = *reinterpret_cast<const f32x4 *>(s + c0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!v.in[k]) continue;
+                const f32x4 d = v.g[k] * sv;
+                *reinterpret_cast<f32x4 *>(dy + v.at[k]) = d;
+                mx = fmaxf(mx, absmax4(d));
+                sum = sum + v.g[k];
+                q = q + v.g[k] * ((v.y[k] - mu) * rs);
+            }
+        });
+    if (amax) amax_word_max(mx, amax);
 }
 
 // ---- convolution weight gradient.  One WAVE owns a 64 (co) x 64 (ci) tile of dW for ONE tap and a group of `rows_per_item` output image
@@ -1039,6 +1211,92 @@ extern "C" int sd_bn_relu_pool_bwd(const float *dp, const uint32_t *idx, const f
     SD_LAUNCH(cvt::bn_pool_bwd_apply_kernel, dim3(blocks_for(nitems * C / 4, 512, 4096)), dim3(256), 0, st, dp, idx, y, mean, rstd, gamma, acc, dy, dgamma, dbeta,
               npix, nitems, G, dy_amax);
     SD_CHECK_LAUNCH("bn_pool_bwd_apply_kernel");
+    return 0;
+}
+
+// ---- BatchNorm on frozen statistics (the kernels' comment above has the formulas)
+static bool misaligned16(std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15) != 0;
+}
+extern "C" int sd_bn_frozen_fold(const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps, int C, float *s,
+                                 float *t, float *rstd, void *stream) {
+    if (!gamma || !beta || !running_mean || !running_var || !s || !t || !rstd || !bn_shape_ok(1, C))
+        return fail(SD_E_BADARG, "sd_bn_frozen_fold: null pointer or bad shape");
+    SD_LAUNCH(cvt::bn_frozen_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta, running_mean, running_var, eps, C, s, t, rstd);
+    SD_CHECK_LAUNCH("bn_frozen_fold_kernel");
+    return 0;
+}
+extern "C" int sd_bn_frozen_fwd(const float *y, const float *s, const float *t, const float *res, float *z, uint32_t *z_amax, int64_t npix, int C, int relu,
+                                void *stream) {
+    if (!y || !s || !t || !z || !bn_shape_ok(npix, C)) return fail(SD_E_BADARG, "sd_bn_frozen_fwd: null pointer or bad shape");
+    if (misaligned16({y, s, t, res, z})) return fail(SD_E_BADARG, "sd_bn_frozen_fwd: tensors must be 16-byte aligned");
+    const long n4 = npix * C / 4;
+    SD_LAUNCH(cvt::bn_frozen_apply_kernel, dim3(blocks_for(n4, 1024, 4096)), dim3(256), 0, (hipStream_t)stream, y, s, t, res, z, n4, C, relu, z_amax);
+    SD_CHECK_LAUNCH("bn_frozen_apply_kernel");
+    return 0;
+}
+extern "C" int sd_bn_frozen_bwd(const float *dz, const float *z, const float *y, const float *s, const float *t, const float *running_mean,
+                                const float *rstd, float *dy, float *dres, float *dgamma, float *dbeta, double *acc, float *scratch, uint32_t *dy_amax,
+                                int64_t npix, int C, int relu, void *stream) {
+    if (!dz || !s || !dy || !bn_shape_ok(npix, C)) return fail(SD_E_BADARG, "sd_bn_frozen_bwd: null pointer or bad shape");
+    if (misaligned16({dz, z, y, s, t, running_mean, rstd, dy, dres})) return fail(SD_E_BADARG, "sd_bn_frozen_bwd: tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (!dgamma) {   // the affine pair needs no gradient: one launch, y was never written
+        if (dbeta) return fail(SD_E_BADARG, "sd_bn_frozen_bwd: dbeta without dgamma");
+        if (relu && !z) return fail(SD_E_BADARG, "sd_bn_frozen_bwd: without y the ReLU mask needs z");
+        const long n4 = npix * C / 4;
+        SD_LAUNCH(cvt::bn_frozen_bwd_kernel, dim3(blocks_for(n4, 1024, 4096)), dim3(256), 0, st, dz, z, s, dy, dres, n4, C, relu, dy_amax);
+        SD_CHECK_LAUNCH("bn_frozen_bwd_kernel");
+        return 0;
+    }
+    if (!dbeta || !y || !running_mean || !rstd || !acc || !scratch || (relu && !z && !t))
+        return fail(SD_E_BADARG, "sd_bn_frozen_bwd: dgamma / dbeta need y, running_mean, rstd, acc, scratch (and t for a recomputed mask)");
+    if (relu && !z && dres) return fail(SD_E_BADARG, "sd_bn_frozen_bwd: a unit with a residual operand needs z for its ReLU mask");
+    const unsigned nb = reduce_blocks(npix, C);
+    SD_LAUNCH(cvt::bn_frozen_bwd_sums_kernel, dim3(nb), dim3(256), 0, st, dz, z, y, s, t, running_mean, rstd, dy, dres, (long)npix, C, relu, scratch, dy_amax);
+    SD_CHECK_LAUNCH("bn_frozen_bwd_sums_kernel");
+    SD_LAUNCH(cvt::partial_sum_kernel, dim3(2 * C / 32), dim3(256), 0, st, scratch, (int)nb, 2 * C, acc);
+    SD_CHECK_LAUNCH("partial_sum_kernel");
+    SD_LAUNCH(cvt::bn_frozen_dparams_kernel, dim3((C + 255) / 256), dim3(256), 0, st, acc, C, dgamma, dbeta);
+    SD_CHECK_LAUNCH("bn_frozen_dparams_kernel");
+    return 0;
+}
+extern "C" int sd_bn_frozen_relu_pool_fwd(const float *y, const float *s, const float *t, float *p, uint32_t *idx, uint32_t *p_amax, int N, int Hc, int Wc,
+                                          int C, void *stream) {
+    const long npix = (long)N * Hc * Wc;
+    if (!y || !s || !t || !p || !idx || N <= 0 || Hc <= 0 || Wc <= 0 || !bn_shape_ok(npix, C))
+        return fail(SD_E_BADARG, "sd_bn_frozen_relu_pool_fwd: null pointer or bad shape");
+    if (npix * (C / 4) >= (1l << 31)) return fail(SD_E_TOOBIG, "sd_bn_frozen_relu_pool_fwd: 2^31 or more 16-byte elements");
+    if (misaligned16({y, s, t, p})) return fail(SD_E_BADARG, "sd_bn_frozen_relu_pool_fwd: tensors must be 16-byte aligned");
+    const int Hp = (Hc - 1) / 2 + 1, Wp = (Wc - 1) / 2 + 1;
+    SD_LAUNCH(cvt::bn_frozen_relu_pool_fwd_kernel, dim3(blocks_for((long)N * Hp * Wp * (C / 4), 512, 8192)), dim3(256), 0, (hipStream_t)stream, y, s, t, p, idx,
+              N, Hc, Wc, Hp, Wp, C, p_amax);
+    SD_CHECK_LAUNCH("bn_frozen_relu_pool_fwd_kernel");
+    return 0;
+}
+extern "C" int sd_bn_frozen_relu_pool_bwd(const float *dp, const uint32_t *idx, const float *y, const float *s, const float *running_mean, const float *rstd,
+                                          float *dy, float *dgamma, float *dbeta, double *acc, float *scratch, uint32_t *dy_amax, int N, int Hc, int Wc,
+                                          int C, void *stream) {
+    const long npix = (long)N * Hc * Wc;
+    if (!dp || !idx || !y || !s || !running_mean || !rstd || !dy || !scratch || (dgamma && (!dbeta || !acc)) || (!dgamma && dbeta) || N <= 0 || Hc <= 0 ||
+        Wc <= 0 || !bn_shape_ok(npix, C))
+        return fail(SD_E_BADARG, "sd_bn_frozen_relu_pool_bwd: null pointer or bad shape");
+    if (npix * (C / 4) >= (1l << 31)) return fail(SD_E_TOOBIG, "sd_bn_frozen_relu_pool_bwd: 2^31 or more 16-byte elements");
+    if (misaligned16({dp, y, s, running_mean, rstd, dy})) return fail(SD_E_BADARG, "sd_bn_frozen_relu_pool_bwd: tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const cvt::PoolGeom G{Hc, Wc, (Hc - 1) / 2 + 1, (Wc - 1) / 2 + 1, C, (Hc + 1) / 2, (Wc + 1) / 2};
+    const long nitems = (long)N * G.Hb * G.Wb;
+    const unsigned nb = reduce_blocks(npix, C);    // (what sd_bn_scratch_floats sized the scratch for)
+    SD_LAUNCH(cvt::bn_frozen_pool_bwd_kernel, dim3(nb), dim3(256), 0, st, dp, idx, y, s, running_mean, rstd, dy, nitems, G, scratch, dy_amax);
+    SD_CHECK_LAUNCH("bn_frozen_pool_bwd_kernel");
+    if (dgamma) {
+        SD_LAUNCH(cvt::partial_sum_kernel, dim3(2 * C / 32), dim3(256), 0, st, scratch, (int)nb, 2 * C, acc);
+        SD_CHECK_LAUNCH("partial_sum_kernel");
+        SD_LAUNCH(cvt::bn_frozen_dparams_kernel, dim3((C + 255) / 256), dim3(256), 0, st, acc, C, dgamma, dbeta);
+        SD_CHECK_LAUNCH("bn_frozen_dparams_kernel");
+    }
     return 0;
 }
 

@@ -77,6 +77,11 @@ class _BasicBlock(nn.Module):
         if stride != 1 or cin != planes:
             self.downsample = nn.Sequential(_conv(cin, planes, 1, stride), nn.BatchNorm2d(planes))
 
+    def train(self, mode: bool = True):   # (BatchNorm layers marked by freeze_batchnorm stay in eval())
+        super().train(mode)
+        _keep_frozen(self)
+        return self
+
     def forward(self, x):
         idt = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
@@ -146,6 +151,11 @@ class _Bottleneck(nn.Module):
         if stride != 1 or cin != planes * 4:
             self.downsample = nn.Sequential(_conv(cin, planes * 4, 1, stride), nn.BatchNorm2d(planes * 4))
 
+    def train(self, mode: bool = True):   # (BatchNorm layers marked by freeze_batchnorm stay in eval())
+        super().train(mode)
+        _keep_frozen(self)
+        return self
+
     def forward(self, x):
         idt = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
@@ -206,15 +216,32 @@ class _ResNet(nn.Module):
                 and not torch.is_grad_enabled() and os.environ.get("SD_CONV", "hip") != "torch")
 
     def _hip_training(self, x: torch.Tensor) -> bool:
-        """train() mode (BatchNorm on batch statistics) on fp32 CUDA tensors: the blocks run conv_training.ConvBNUnit.  (eval() mode WITH a tape -
-        fine-tuning on frozen statistics - keeps torch.nn, as does SD_CONV=torch.)"""
+        """train() mode on fp32 CUDA tensors: the blocks run conv_training's units - ConvBNUnit where the BatchNorm2d is in training mode (batch
+        statistics), FrozenConvBNUnit where it is in eval() (fine-tuning on frozen running statistics: ``freeze_batchnorm``), unit by unit.
+        (eval() of the WHOLE backbone with a tape keeps torch.nn, as does SD_CONV=torch, and a backbone with a BatchNorm2d that
+        conv_training.bn_route sends to "torch".)"""
         if not (x.is_cuda and x.dtype == torch.float32 and self.conv1.weight.dtype == torch.float32 and self.training
                 and os.environ.get("SD_CONV", "hip") != "torch"):
             return False
         slot = cache(self, "train")
         if "ok" not in slot:
             slot["ok"] = all(_train_ok(b) for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer)
-        return slot["ok"]
+            slot["bns"] = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        if not slot["ok"]:
+            return False
+        # the BatchNorm layers' part of the decision, kept until a mode or a requires_grad flag flips
+        from .... import conv_training as ct
+
+        facts = [tuple(ct.bn_facts(m).values()) for m in slot["bns"]]
+        if slot.get("bn_facts") != facts:
+            slot["bn_facts"], slot["bn_ok"] = facts, all(ct.bn_route(**ct.bn_facts(m)) != "torch" for m in slot["bns"])
+        return slot["bn_ok"]
+
+    def train(self, mode: bool = True):
+        """nn.Module.train, except that BatchNorm layers marked by ``freeze_batchnorm`` stay in eval()."""
+        super().train(mode)
+        _keep_frozen(self)
+        return self
 
     def _hip_head(self, h: torch.Tensor):
         """(conv or None, fc) when the head is exactly AdaptiveAvgPool2d((1, 1)) or Conv2d(C, 32, 1, bias=True), then an nn.Linear (with bias)
@@ -281,6 +308,47 @@ class _ResNet(nn.Module):
         else:
             x = self.layer4(self.layer3(self.layer2(self.layer1(self.maxpool(self.relu(self.bn1(self.conv1(x))))))))
         return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
+# ---- fine-tuning on frozen BatchNorm statistics -------------------------------------------------------
+_FROZEN = "_sd_bn_frozen"   # on a frozen BatchNorm2d: the (weight, bias) requires_grad flags from before the freeze
+
+
+def _keep_frozen(module: nn.Module) -> None:
+    for m in module.modules():
+        if isinstance(m, nn.BatchNorm2d) and hasattr(m, _FROZEN):
+            nn.Module.train(m, False)
+
+
+def freeze_batchnorm(module: nn.Module, affine: bool = False) -> nn.Module:
+    """Puts every BatchNorm2d under ``module`` into eval() - normalisation with the running statistics, which are no longer updated: the usual
+    recipe for fine-tuning a pretrained backbone at a small per-GPU batch - and keeps it there across later ``.train()`` calls of a ``_ResNet``
+    above or below ``module`` (a bare ``bn.train()`` still wins).  ``affine=True`` also clears ``requires_grad`` on weight and bias; build the
+    optimizer afterwards, from the parameters that require a gradient.  A train() ``_ResNet`` runs such layers on conv_training's frozen units."""
+    for m in module.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            if not hasattr(m, _FROZEN):
+                setattr(m, _FROZEN, tuple(p is not None and p.requires_grad for p in (m.weight, m.bias)))
+            nn.Module.train(m, False)
+            if affine:
+                for p in (m.weight, m.bias):
+                    if p is not None:
+                        p.requires_grad_(False)
+    return module
+
+
+def unfreeze_batchnorm(module: nn.Module) -> nn.Module:
+    """Undoes ``freeze_batchnorm``: the layers follow their parent's mode again (and take it now), ``requires_grad`` as before the freeze."""
+    for parent in [None, *module.modules()]:   # (None: ``module`` itself, whose parent is not known - it keeps its mode)
+        for m in ([module] if parent is None else parent.children()):
+            if isinstance(m, nn.BatchNorm2d) and hasattr(m, _FROZEN):
+                for p, flag in zip((m.weight, m.bias), getattr(m, _FROZEN)):
+                    if p is not None:
+                        p.requires_grad_(flag)
+                delattr(m, _FROZEN)
+                if parent is not None:
+                    nn.Module.train(m, parent.training)
+    return module
 
 
 # ---- torchvision.models.swin_transformer (V1), attribute for attribute ------------------------------

@@ -783,6 +783,24 @@ int sd_op_attention_bwd_dropout(const float *q, int ldq, const float *k, const f
                                 float *dv, int lddkv, int B, int Tq, int S, int d, int heads, float p, uint64_t seed,
                                 uint64_t site, void *stream);
 
+/* Cross-attention of C * K trajectories over C shared contexts (training with several noise draws per window): trajectory b's keys are the
+ * Mc rows of context b / K followed by its own token row at key index Mc - the order of cat(context, token).  q, out (C*K, T, d);
+ * kv_ctx (C, Mc, 2d) and kv_tok (C*K, 1, 2d): packed K | V rows; lse2 (C*K, heads, T) as sd_op_attention_lse.  Dropout on the
+ * probabilities uses sd_op_attention_lse_dropout's mask index for (b, head, t, key) with S = Mc + 1: the call equals that one on the
+ * expanded K | V under the same (p, seed, site).  The backward returns dq, dkv_tok and dkv_ctx (C, Mc, 2d), the sum over the K draws of a
+ * context and their T rows: one workgroup per (context, head) adds them in draw order without atomics, so two runs give the same bits.
+ * Head dims 16, 32, 64; 1 <= T <= 100; Mc >= 1; any K (sd_train_xattn_shared_ok); anything else: SD_E_UNSUPPORTED, nothing launched. */
+int sd_train_xattn_shared_ok(int d, int heads, int T, int Mc);
+int sd_train_xattn_shared_fwd(const float *q, const float *kv_ctx, const float *kv_tok, float *out, float *lse2, int C, int K,
+                              int T, int Mc, int d, int heads, float p, uint64_t seed, uint64_t site, void *stream);
+int sd_train_xattn_shared_bwd(const float *q, const float *kv_ctx, const float *kv_tok, const float *o, const float *dO,
+                              const float *lse2, float *dq, float *dkv_ctx, float *dkv_tok, int C, int K, int T, int Mc, int d,
+                              int heads, float p, uint64_t seed, uint64_t site, void *stream);
+/* out[b] = in[b / K] for C * K rows of `row` floats (a multiple of 4, 16-byte aligned), and its backward din[c] = sum over the K rows
+ * of a group of dout, added in draw order (deterministic): where the shared kernels do not apply the context is expanded. */
+int sd_train_expand_rows(const float *in, float *out, long C, int K, long row, void *stream);
+int sd_train_expand_rows_bwd(const float *dout, float *din, long C, int K, long row, void *stream);
+
 /* dW[N,K] += dY[R,N]^T X[R,K];  db[N] += column sums of dY (db may be NULL).  Accumulates
  * with fp32 atomics: zero dW/db first (summation order is not fixed). */
 int sd_op_gemm_tn(const float *dY, int ldy, const float *X, int ldx, float *dW, int ldw, float *db, long R,

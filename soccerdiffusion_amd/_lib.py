@@ -204,6 +204,11 @@ SIGNATURES = {
     "sd_op_attention_bwd_dropout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 5 +
                                     [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "sd_train_xattn_shared_ok": (C.c_int, [C.c_int] * 4),
+    "sd_train_xattn_shared_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "sd_train_xattn_shared_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "sd_train_expand_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_void_p]),
+    "sd_train_expand_rows_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_void_p]),
     "sd_op_gemm_tn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "sd_op_layernorm_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_long, C.c_int, C.c_void_p]),
     "sd_op_layernorm_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_long, C.c_int, C.c_void_p]),

@@ -18,7 +18,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SRC = [os.path.join(CSRC, u + ".hip") for u in ("sd_kernels", "sd_traj", "sd_train", "sd_train_chain", "sd_conv", "sd_train_traj", "sd_trajg",
                                                 "sd_conv_train", "sd_swin", "sd_frames", "sd_head", "sd_session", "sd_traj_draws", "sd_eval", "sd_traj_hold",
-                                                "sd_traj_ms", "sd_traj_lim", "sd_traj_slew", "sd_traj_direct", "sd_traj_acc")]
+                                                "sd_traj_ms", "sd_traj_lim", "sd_traj_slew", "sd_traj_direct", "sd_traj_acc", "sd_train_shared")]
 # The sampler's translation units are compiled WITHOUT packed fp32 vector instructions (v_pk_fma/mul/add_f32): they do not overlap with
 # MFMAs - neither a wave's own nor its SIMD partner's - while plain fp32 instructions do (tools/exp/coissue3.hip; NOTEBOOK.md 5.11), and
 # the trajectory kernel lives on that overlap: + 1.5 % sampler throughput.  The training units lose 0.6 % with the same flag: packed.

@@ -349,6 +349,10 @@ def cmd_train(args) -> int:
         raise SystemExit("train_denoising_timesteps must be 1000 (the scheduler table length; see scheduler.py)")
     # a resumed run goes on with its BatchNorm layers as they were
     freeze_bn = validate_freeze_bn(args.freeze_bn if args.freeze_bn is not None or checkpoint is None else checkpoint.get("freeze_bn"), params)
+    noise_draws = noise_draws_of(args.noise_draws, checkpoint)   # a resumed run goes on with its draws per window
+    if noise_draws > 1 and params.get("use_images") and str(params.get("image_encoder_type", "")).startswith("swin_transformer"):
+        raise SystemExit("--noise-draws: not with a Swin image encoder (its training runs on torch's own modules; see README)")
+    draws_kw = {} if noise_draws == 1 else {"draws": noise_draws}
 
     gen = torch.Generator().manual_seed(args.seed + rank)
     source = data_source(args, params, device)
@@ -412,11 +416,11 @@ def cmd_train(args) -> int:
             if args.decoder_pretraining:
                 ctx = [torch.randn((len(idx), 10, params["hidden_dim"]), device=device, generator=dev_gen)]
                 loss = training.train_step(model, optimizer, lr_scheduler, scheduler, targets, context=ctx,
-                                           world_size=world, generator=dev_gen)
+                                           world_size=world, generator=dev_gen, **draws_kw)
             else:
                 inp = {k: batch[k].contiguous() for k in CONTEXT_KEYS if k in batch}
                 loss = training.train_step(model, optimizer, lr_scheduler, scheduler, targets, input_data=inp,
-                                           world_size=world, generator=dev_gen)
+                                           world_size=world, generator=dev_gen, **draws_kw)
             if i % 20 == 0 and rank == 0:
                 print(f"Epoch {epoch}, it {i}, Loss: {float(loss):.05f}, LR: {lr_scheduler.get_last_lr()[0]:0.7f}{_grad_clip_suffix(optimizer)}", flush=True)
         if val is not None and rank == 0:   # (the other ranks wait at the collective below)
@@ -426,7 +430,7 @@ def cmd_train(args) -> int:
             torch.save({"model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                         "lr_scheduler_state_dict": lr_scheduler.state_dict(), "hyperparams": params,
                         "current_epoch": epoch, **_ema_checkpoint_keys(optimizer, model), **_grad_clip_checkpoint_keys(optimizer),
-                        **_freeze_bn_checkpoint_keys(freeze_bn),
+                        **_freeze_bn_checkpoint_keys(freeze_bn), **({} if noise_draws == 1 else {"noise_draws": noise_draws}),
                         **({} if val is None else {"validation": val.entry()})},
                        args.output)
     if world > 1:
@@ -928,6 +932,23 @@ def _draws(text: str) -> int:
     return g
 
 
+def _noise_draws(text: str) -> int:
+    try:
+        k = int(text)
+    except ValueError:
+        k = 0
+    if not 1 <= k <= 64:
+        raise argparse.ArgumentTypeError(f"--noise-draws takes a number of (timestep, noise) pairs per window in [1, 64], got {text!r}")
+    return k
+
+
+def noise_draws_of(arg: Optional[int], checkpoint: Optional[dict]) -> int:
+    """--noise-draws, else what the resumed checkpoint trained with (``noise_draws``), else 1."""
+    if arg is not None:
+        return arg
+    return int(checkpoint.get("noise_draws", 1)) if checkpoint is not None else 1
+
+
 def _hold(text: str) -> list:
     """--hold J=V[,J=V...] -> [(joint, value)]; the joints are checked against the model's joint count where it is known."""
     try:
@@ -1060,6 +1081,9 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--pretrained-decoder", type=str, default=None, help="Checkpoint whose decoder weights are loaded (strict=False)")
     tr.add_argument("--dropout", type=float, default=0.1, help="dropout probability of the transformer layers in training "
                     "(the reference never sets it: torch's default 0.1, decoder.py:26-33); 0 = the parity path")
+    tr.add_argument("--noise-draws", type=_noise_draws, default=None, metavar="K", help="K (timestep, noise) pairs per window on ONE encoded "
+                    "observation (train_step(draws=K)): K x the denoising supervision per encoder pass; steps per epoch and the learning-rate "
+                    "schedule still count windows; the checkpoint gains noise_draws and a resumed run (-p) continues with it")
     sa = sub.add_parser("sample", help="sample trajectories from a checkpoint (flags of the reference's plot.py)")
     sa.add_argument("checkpoint", type=str, help="Path to the checkpoint to load")
     sa.add_argument("--steps", type=int, default=30, help="Number of denoising steps")

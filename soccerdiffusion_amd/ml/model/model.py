@@ -88,8 +88,12 @@ class End2EndDiffusionTransformer(nn.Module):
         return [enc(input_data[key]) for enc, key in pairs if enc is not None]
 
     def forward(self, input_data: dict[str, torch.Tensor], noisy_action_predictions: torch.Tensor,
-                step: torch.Tensor) -> torch.Tensor:
-        return self.forward_with_context(self.encode_input_data(input_data), noisy_action_predictions, step)
+                step: torch.Tensor, draws: int = 1) -> torch.Tensor:
+        """``draws`` = K > 1 (not in the reference): ``input_data`` holds C windows, encoded once; ``noisy_action_predictions`` C K
+        trajectories, trajectory b of window b // K (``forward_with_context``)."""
+        if draws != 1:   # (validated before any encoder runs)
+            ops._draws_req(draws, noisy_action_predictions.shape[0], None)
+        return self.forward_with_context(self.encode_input_data(input_data), noisy_action_predictions, step, draws)
 
     def forward_with_context(self, context: Sequence[torch.Tensor], noisy_action_predictions: torch.Tensor,
                              step: torch.Tensor, draws: int = 1) -> torch.Tensor:
@@ -97,7 +101,9 @@ class End2EndDiffusionTransformer(nn.Module):
         LAST memory row (model.py:176).  ``step`` is int64 or float, shape (B,) (or (1,) at B=1).
         ``draws`` = G > 1 (not in the reference): the context tensors hold C rows, ``x`` C * G trajectories, trajectory b reads context
         b // G.  On the trajectory kernels the context is folded once per row (``ops.LoopSampler(draws=G)``); elsewhere the rows are
-        expanded and the call is the one with ``draws`` = 1 - the same result, only not shared."""
+        expanded and the call is the one with ``draws`` = 1 - the same result, only not shared.  With a tape (training) the context is
+        projected to K | V once per row and layer where ``training.denoiser_forward_autograd`` takes the shared route, and its gradient
+        is the sum over the G draws in a fixed order."""
         x = noisy_action_predictions
         B = x.shape[0]
         if draws != 1:
@@ -111,6 +117,17 @@ class End2EndDiffusionTransformer(nn.Module):
         if eps is not None:
             return eps
         if draws != 1:
+            dag = self.diffusion_action_generator
+            tape = torch.is_grad_enabled() and (any(c.requires_grad for c in context) or any(p.requires_grad for p in dag.parameters())
+                                                or self.step_encoding.token.requires_grad)
+            if len(context) and (tape or (self.training and dag.dropout.p > 0.0)):
+                # training (train_step(draws=)): the context stays C rows - projected once per context where the shared
+                # cross-attention applies, expanded by a node with a fixed-order backward where it does not
+                from ...training import denoiser_forward_autograd, step_token_autograd
+
+                tokens = step_token_autograd(self.step_encoding, step if step.shape[0] == B else step.expand(B), fixed_order=True)
+                ctx = context[0] if len(context) == 1 else torch.cat(list(context), dim=1)
+                return denoiser_forward_autograd(dag, x, ctx, draws=draws, tokens=tokens)
             return self.forward_with_context([c.repeat_interleave(draws, 0) for c in context], x, step)
         if step.shape[0] != B:
             step = step.expand(B)

@@ -1869,6 +1869,74 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, dO: Tensor, lse: T
                                           B, Tq, S, d, heads, p, seed, site, _stream()), "sd_op_attention_bwd")
 
 
+def train_xattn_shared_ok(d: int, heads: int, T: int, Mc: int) -> bool:
+    """The shared cross-attention kernels take this shape (head dim 16 / 32 / 64, 1 <= T <= 100, Mc >= 1)."""
+    return bool(_lib.load().sd_train_xattn_shared_ok(int(d), int(heads), int(T), int(Mc)))
+
+
+def _xattn_shared_shapes(q: Tensor, kv_ctx: Tensor, kv_tok: Tensor, draws: int):
+    for t, name in ((q, "q"), (kv_ctx, "kv_ctx"), (kv_tok, "kv_tok")):
+        _req(t, name)
+    B, T, d = q.shape
+    C_, Mc = kv_ctx.shape[0], kv_ctx.shape[1]
+    _draws_req(draws, B, C_)
+    if tuple(kv_ctx.shape) != (C_, Mc, 2 * d) or tuple(kv_tok.shape) != (B, 1, 2 * d):
+        raise ValueError(f"shared cross-attention: expected kv_ctx (C, Mc, {2 * d}) and kv_tok ({B}, 1, {2 * d}), got {tuple(kv_ctx.shape)} and "
+                         f"{tuple(kv_tok.shape)}")
+    return C_, T, Mc, d
+
+
+def train_xattn_shared_fwd(q: Tensor, kv_ctx: Tensor, kv_tok: Tensor, heads: int, draws: int, drop=None):
+    """Cross-attention of C * draws trajectories over C shared contexts: q (C * draws, T, d), kv_ctx (C, Mc, 2d), kv_tok (C * draws, 1, 2d);
+    trajectory b's keys are context b // draws's rows, then its own token row.  Returns (out, lse2) as ``attention_lse`` on the expanded
+    K | V does - the same dropout mask under the same ``drop``.  A shape the kernels decline raises ``Unsupported``-coded RuntimeError."""
+    lib = _lib.load()
+    C_, T, Mc, d = _xattn_shared_shapes(q, kv_ctx, kv_tok, draws)
+    out = torch.empty_like(q)
+    lse = torch.empty(q.shape[0], heads, T, dtype=torch.float32, device=q.device)
+    p, seed, site = _drop(drop)
+    check(lib.sd_train_xattn_shared_fwd(q.data_ptr(), kv_ctx.data_ptr(), kv_tok.data_ptr(), out.data_ptr(), lse.data_ptr(), C_, draws, T, Mc, d,
+                                        heads, p, seed, site, _stream()), "sd_train_xattn_shared_fwd")
+    return out, lse
+
+
+def train_xattn_shared_bwd(q: Tensor, kv_ctx: Tensor, kv_tok: Tensor, o: Tensor, dO: Tensor, lse: Tensor, heads: int, draws: int, drop=None):
+    """(dq, dkv_ctx, dkv_tok) of ``train_xattn_shared_fwd``; dkv_ctx is summed over the draws in a fixed order (bitwise repeatable)."""
+    lib = _lib.load()
+    C_, T, Mc, d = _xattn_shared_shapes(q, kv_ctx, kv_tok, draws)
+    _req(o, "o"); _req(dO, "dO"); _req(lse, "lse")
+    if o.shape != q.shape or dO.shape != q.shape or tuple(lse.shape) != (q.shape[0], heads, T):
+        raise ValueError("shared cross-attention backward: o / dO / lse do not match q")
+    dq, dkv_ctx, dkv_tok = torch.empty_like(q), torch.empty_like(kv_ctx), torch.empty_like(kv_tok)
+    p, seed, site = _drop(drop)
+    check(lib.sd_train_xattn_shared_bwd(q.data_ptr(), kv_ctx.data_ptr(), kv_tok.data_ptr(), o.data_ptr(), dO.data_ptr(), lse.data_ptr(),
+                                        dq.data_ptr(), dkv_ctx.data_ptr(), dkv_tok.data_ptr(), C_, draws, T, Mc, d, heads, p, seed, site,
+                                        _stream()), "sd_train_xattn_shared_bwd")
+    return dq, dkv_ctx, dkv_tok
+
+
+def expand_rows(x: Tensor, draws: int) -> Tensor:
+    """x (C, ...) -> (C * draws, ...), row b = x[b // draws] (``repeat_interleave(draws, 0)``)."""
+    _req(x, "x")
+    _draws_req(draws, 0, None)
+    C_ = x.shape[0]
+    row = x.numel() // C_
+    out = torch.empty(C_ * draws, *x.shape[1:], dtype=torch.float32, device=x.device)
+    check(_lib.load().sd_train_expand_rows(x.data_ptr(), out.data_ptr(), C_, draws, row, _stream()), "sd_train_expand_rows")
+    return out
+
+
+def expand_rows_bwd(dout: Tensor, draws: int) -> Tensor:
+    """The gradient of ``expand_rows``: the sum over each group of ``draws`` rows, in draw order."""
+    _req(dout, "dout")
+    _draws_req(draws, dout.shape[0], None)
+    C_ = dout.shape[0] // draws
+    row = dout.numel() // dout.shape[0]
+    din = torch.empty(C_, *dout.shape[1:], dtype=torch.float32, device=dout.device)
+    check(_lib.load().sd_train_expand_rows_bwd(dout.data_ptr(), din.data_ptr(), C_, draws, row, _stream()), "sd_train_expand_rows_bwd")
+    return din
+
+
 def gemm_tn(dY: Tensor, X: Tensor, dW: Tensor, db: Optional[Tensor] = None) -> None:
     """dW[N,K] += dY[R,N]^T X[R,K]; db[N] += colsum(dY).  dY / X may be column slices."""
     lib = _lib.load()

@@ -377,8 +377,9 @@ class _FcOut(Function):
 
 class _StepTokenFn(Function):
     @staticmethod
-    def forward(ctx, steps, freq, token):
+    def forward(ctx, steps, freq, token, fixed_order: bool = False):
         ctx.half = token.shape[-1]
+        ctx.fixed_order = fixed_order
         ctx.save_for_backward(token)
         return ops.step_token(steps, freq, token)
 
@@ -386,8 +387,18 @@ class _StepTokenFn(Function):
     def backward(ctx, dtok):
         (token,) = ctx.saved_tensors
         (dtoken,), (rtoken,) = _grad_targets(token)
-        ops.colsum(dtok.contiguous()[:, 0, ctx.half :], dtoken.view(-1))  # the learned half is expanded over the batch
-        return None, None, rtoken
+        learned = dtok.contiguous()[:, 0, ctx.half :]   # the learned half is expanded over the batch
+        if ctx.fixed_order and ctx.half % 4 == 0:
+            # several draws per window: the rows are added in a fixed order first (colsum's atomics take more than two rows in any
+            # order) - level by level, groups of up to 32 consecutive rows at a time, so that no thread walks thousands of rows alone;
+            # the grouping is a function of the row count only
+            learned = learned.contiguous()
+            while learned.shape[0] > 1:
+                rows = learned.shape[0]
+                f = next((f for f in range(min(32, rows), 1, -1) if rows % f == 0), rows)
+                learned = ops.expand_rows_bwd(learned, f)
+        ops.colsum(learned, dtoken.view(-1))
+        return None, None, rtoken, None
 
 
 class _MSELoss(Function):
@@ -409,11 +420,11 @@ def mse_loss(pred: Tensor, target: Tensor) -> Tensor:
     return _MSELoss.apply(pred, target)
 
 
-def step_token_autograd(step_module, steps: Tensor) -> Tensor:
+def step_token_autograd(step_module, steps: Tensor, fixed_order: bool = False) -> Tensor:
     steps = steps.contiguous()
     if steps.dtype not in (torch.int64, torch.float32):
         steps = steps.to(torch.float32 if steps.is_floating_point() else torch.int64)
-    return _StepTokenFn.apply(steps, step_module._freq, step_module.token)
+    return _StepTokenFn.apply(steps, step_module._freq, step_module.token, fixed_order)
 
 
 def _layer(lp, h, heads, memory=None, ffn_norm=None, dc=None, li: int = 0):
@@ -529,8 +540,9 @@ def _traj_slices(layers, route: TrainRoute) -> dict:
 # the per-tensor scales of the grouped weight-gradient GEMM
 AMAX_WORDS = 64   # SD_AMAX_WORDS: the producers spread their atomics over this many words per tensor
 (_AX_N1, _AX_ASA, _AX_N2, _AX_ACA, _AX_NF, _AX_U, _AX_DY2, _AX_DPRE, _AX_DYC, _AX_DQ, _AX_DYS, _AX_DQKV, _AX_DKV, _AX_OUT, _AX_SCR,
- _AX_MEM, _AX_DX, _AX_SCR2) = range(18)   # _AX_OUT / _AX_DX: the layer's output / its input gradient (for fc_out / the embedding,
-_AX_SLOTS = 20                             # with a scratch slot each for their small operand); _AX_MEM: the memory (row 0)
+ _AX_MEM, _AX_DX, _AX_SCR2, _AX_TOK, _AX_DKT) = range(20)   # _AX_OUT / _AX_DX: the layer's output / its input gradient (for fc_out / the
+_AX_SLOTS = 20                             # embedding, with a scratch slot each for their small operand); _AX_MEM: the memory (row 0);
+                                           # shared draws: _AX_TOK the step tokens (row 0), _AX_DKT the gradient of their K | V
 
 
 def _ax(amax: Tensor, layer: int, slot: int) -> int:
@@ -539,10 +551,11 @@ def _ax(amax: Tensor, layer: int, slot: int) -> int:
 
 
 class _FusedCfg:
-    __slots__ = ("heads", "dc", "li", "decoder", "next_ln", "next_w", "next_b", "amax", "tw")
+    __slots__ = ("heads", "dc", "li", "decoder", "next_ln", "next_w", "next_b", "amax", "tw", "draws")
 
-    def __init__(self, heads, dc, li, decoder, nxt, amax, tw=None):
+    def __init__(self, heads, dc, li, decoder, nxt, amax, tw=None, draws: int = 1):
         self.heads, self.dc, self.li, self.decoder, self.amax = heads, dc, li, decoder, amax
+        self.draws = draws   # > 1: `memory` holds B / draws contexts, the step tokens come beside it (the shared cross-attention)
         self.tw = tw   # the plane addresses of sd_train_layer_fwd (train_route's traj_layers), else None: attention + row chains
         if nxt is not None:
             self.next_ln = (nxt.norm1.weight.detach(), nxt.norm1.bias.detach())
@@ -594,7 +607,7 @@ class _FusedLayer(Function):
     (h, LN1(h), qkv = LN1(h) Wqkv^T + b); returns (h', LN1'(h'), qkv') for the next layer (empty tensors after the last)."""
 
     @staticmethod
-    def forward(ctx, h, n1, qkv, memory, cfg: _FusedCfg, *P):
+    def forward(ctx, h, n1, qkv, memory, tok, cfg: _FusedCfg, *P):
         B, T, d = h.shape
         R = B * T
         dec, last = cfg.decoder, cfg.next_w is None
@@ -606,11 +619,15 @@ class _FusedLayer(Function):
         h = h.contiguous()
         if dec:   # the memory's K/V projection beside the self-attention and chain A
             M = memory.shape[1]
-            kv = _new(B, M, 2 * d, like=h)
+            Bm = memory.shape[0]   # B, or the B / draws contexts the draws share (tok: their step tokens (B, 1, d); M then counts context rows)
+            kv = _new(Bm, M, 2 * d, like=h)
+            kvt = _new(B, 1, 2 * d, like=h) if tok is not None else None
             side = _mem_side(h.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                ops.linear_packed(memory.reshape(B * M, d), _packed_weight(Wc, 1), 2 * d, bc[d:], out=kv.view(B * M, 2 * d))
+                ops.linear_packed(memory.reshape(Bm * M, d), _packed_weight(Wc, 1), 2 * d, bc[d:], out=kv.view(Bm * M, 2 * d))
+                if tok is not None:
+                    ops.linear_packed(tok.reshape(B, d), _packed_weight(Wc, 1), 2 * d, bc[d:], out=kvt.view(B, 2 * d))
             h1, n2, q = _new(B, T, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
         h2, nf, pre, u, h3 = _new(B, T, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(R, d, like=h), _new(B, T, d, like=h)
         nn1, qkv2 = (_new(0, like=h), _new(0, like=h)) if last else (_new(R, d, like=h), _new(B, T, 3 * d, like=h))
@@ -635,7 +652,10 @@ class _FusedLayer(Function):
                                     wn=_packed_weight(Wc), bn=bc, y_out=q, n_next=1, p=p, seed=seed, sites=(cfg.site(SITE_SA_OUT), 0, 0),
                                     amax=(cfg.ax(_AX_ASA), None, None, cfg.ax(_AX_N2)))
                 torch.cuda.current_stream().wait_stream(side)
-                a_ca, lse_ca = ops.attention_lse(q, kv[..., :d], kv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
+                if tok is not None:
+                    a_ca, lse_ca = ops.train_xattn_shared_fwd(q, kv, kvt, heads, cfg.draws, cfg.drop(SITE_CA_PROBS))
+                else:
+                    a_ca, lse_ca = ops.attention_lse(q, kv[..., :d], kv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
                 a_in, w_in, b_in, h_res, site_out, ax_a = a_ca, Woc, boc, h1, cfg.site(SITE_CA_OUT), _AX_ACA
             else:
                 a_in, w_in, b_in, h_res, site_out, ax_a = a_sa, Wo, bo, h, cfg.site(SITE_SA_OUT), _AX_ASA
@@ -648,7 +668,7 @@ class _FusedLayer(Function):
             _amax_register(h3, cfg.amax, ax_out, cfg.ax(_AX_SCR))
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)   # LN1'(h') and qkv' carry no gradient: autograd would hand zeros of their size to backward
-        ctx.save_for_backward(h, n1, qkv, memory if dec else None, a_sa, lse_sa, h2, nf, pre, u, *((h1, n2, q, kv, a_ca, lse_ca) if dec else ()), *P)
+        ctx.save_for_backward(h, n1, qkv, memory if dec else None, a_sa, lse_sa, h2, nf, pre, u, *((h1, n2, q, kv, a_ca, lse_ca, tok, kvt) if dec else ()), *P)
         ctx.mark_non_differentiable(nn1, qkv2)
         return h3, nn1, qkv2
 
@@ -658,13 +678,13 @@ class _FusedLayer(Function):
         dec, heads, p, seed = cfg.decoder, cfg.heads, cfg.p, cfg.seed
         sv = ctx.saved_tensors
         h, n1, qkv, memory, a_sa, lse_sa, h2, nf, pre, u = sv[:10]
-        n_c = 6 if dec else 0   # the cross-attention's tensors
+        n_c = 8 if dec else 0   # the cross-attention's tensors
         saved_c, P = sv[10 : 10 + n_c], sv[10 + n_c :]
         B, T, d = h.shape
         R = B * T
         if dec:
             (n1w, n1b, Wqkv, bqkv, Wo, bo, n2w, n2b, Wc, bc, Woc, boc, nfw, nfb, W1, b1, W2, b2) = P
-            h1, n2, q, kv, a_ca, lse_ca = saved_c
+            h1, n2, q, kv, a_ca, lse_ca, tok, kvt = saved_c
         else:
             (n1w, n1b, Wqkv, bqkv, Wo, bo, nfw, nfb, W1, b1, W2, b2) = P
         G, back = _grad_targets(*P)
@@ -686,7 +706,7 @@ class _FusedLayer(Function):
         dws = [(dym, u, g["linear2.weight"], g["linear2.bias"], cfg.ax(_AX_DY2), cfg.ax(_AX_U)),
                (dpre, nf, g["linear1.weight"], g["linear1.bias"], cfg.ax(_AX_DPRE), cfg.ax(_AX_NF))]
 
-        dmem = None
+        dmem = dtok = None
         if dec:
             # cross-attention block
             dym, da = (_new(R, d, like=h) if p > 0 else dh2.view(R, d)), _new(B, T, d, like=h)
@@ -694,9 +714,12 @@ class _FusedLayer(Function):
                                 amax=(cfg.ax(_AX_DYC), None))
             dws.append((dym, a_ca.view(R, d), g["multihead_attn.out_proj.weight"], g["multihead_attn.out_proj.bias"], cfg.ax(_AX_DYC),
                         cfg.ax(_AX_ACA)))
-            dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-            ops.attention_bwd(q, kv[..., :d], kv[..., d:], a_ca, da, lse_ca, dq, dkv[..., :d], dkv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
-            M = memory.shape[1]
+            if tok is not None:   # dkv: summed over the draws of a context, in draw order
+                dq, dkv, dkvt = ops.train_xattn_shared_bwd(q, kv, kvt, a_ca, da, lse_ca, heads, cfg.draws, cfg.drop(SITE_CA_PROBS))
+            else:
+                dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+                ops.attention_bwd(q, kv[..., :d], kv[..., d:], a_ca, da, lse_ca, dq, dkv[..., :d], dkv[..., d:], heads, cfg.drop(SITE_CA_PROBS))
+            M, Bm = memory.shape[1], memory.shape[0]
             gWc, gbc = g["multihead_attn.in_proj_weight"], g["multihead_attn.in_proj_bias"]
             if ctx.needs_input_grad[3]:   # (the learned half of the step token sits in the memory)
                 dmem = _new(*memory.shape, like=h)
@@ -704,12 +727,21 @@ class _FusedLayer(Function):
             mside.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(mside):
                 if grouped:
-                    ops.absmax(dkv.view(B * M, 2 * d), cfg.ax(_AX_DKV))
-                    dws.append((dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:], cfg.ax(_AX_DKV), _ax(cfg.amax, 0, _AX_MEM)))
+                    ops.absmax(dkv.view(Bm * M, 2 * d), cfg.ax(_AX_DKV))
+                    dws.append((dkv.view(Bm * M, 2 * d), memory.reshape(Bm * M, d), gWc[d:], gbc[d:], cfg.ax(_AX_DKV), _ax(cfg.amax, 0, _AX_MEM)))
                 else:
-                    ops.gemm_tn(dkv.view(B * M, 2 * d), memory.reshape(B * M, d), gWc[d:], gbc[d:])
+                    ops.gemm_tn(dkv.view(Bm * M, 2 * d), memory.reshape(Bm * M, d), gWc[d:], gbc[d:])
                 if dmem is not None:   # both column passes in one launch
-                    ops.train_bwd_chain(B * M, d, dkv.view(B * M, 2 * d), wT(Wc, 1), dmem.view(B * M, d), passes=2)
+                    ops.train_bwd_chain(Bm * M, d, dkv.view(Bm * M, 2 * d), wT(Wc, 1), dmem.view(Bm * M, d), passes=2)
+                if tok is not None:   # the second key segment: the same weight block's gradient from the B token rows
+                    if grouped:
+                        ops.absmax(dkvt.view(B, 2 * d), cfg.ax(_AX_DKT))
+                        dws.append((dkvt.view(B, 2 * d), tok.reshape(B, d), gWc[d:], gbc[d:], cfg.ax(_AX_DKT), _ax(cfg.amax, 0, _AX_TOK)))
+                    else:
+                        ops.gemm_tn(dkvt.view(B, 2 * d), tok.reshape(B, d), gWc[d:], gbc[d:])
+                    if ctx.needs_input_grad[4]:
+                        dtok = _new(B, 1, d, like=h)
+                        ops.train_bwd_chain(B, d, dkvt.view(B, 2 * d), wT(Wc, 1), dtok.view(B, d), passes=2)
             dh1 = _new(B, T, d, like=h)
             ops.train_bwd_chain(R, d, dq.view(R, d), wT(Wc), dh1, x=h1, ln_w=n2w, dres=dh2, dg=g["norm2.weight"], db=g["norm2.bias"],
                                 amax=(cfg.ax(_AX_DQ), None))
@@ -739,15 +771,18 @@ class _FusedLayer(Function):
         else:
             for dY, X, dW, db, _, _ in dws:
                 ops.gemm_tn(dY, X, dW, db)
-        return (dh, None, None, dmem, None) + tuple(back)
+        return (dh, None, None, dmem, dtok, None) + tuple(back)
 
 
 FUSED_STACKS = [0]   # how many layer stacks went through the fused path (tests assert that it is the path that ran)
 
 
-def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, route: TrainRoute, store=None, embed=None) -> Tensor:
+def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, route: TrainRoute, store=None, embed=None, tokens=None,
+                 draws: int = 1) -> Tensor:
     """``embed`` = (x, gen) with route.embed_head: the stack starts from the raw trajectory - embedding, LayerNorm 1 and the Q | K | V
-    projection of layer 0 in one trajectory-owning launch (_EmbedHead) - instead of from an embedded ``h``."""
+    projection of layer 0 in one trajectory-owning launch (_EmbedHead) - instead of from an embedded ``h``.
+    ``tokens`` (B, 1, d) with ``draws`` > 1: ``memory`` holds the B / draws contexts WITHOUT the step tokens; every layer projects both
+    segments and runs the shared cross-attention (csrc/sd_train_shared.hip)."""
     FUSED_STACKS[0] += 1
     lp0, L = layers[0], len(layers)
     dev = embed[0].device if embed is not None else h.device
@@ -755,6 +790,8 @@ def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, 
     amax = torch.zeros(L + 1, _AX_SLOTS, AMAX_WORDS, dtype=torch.int32, device=dev)
     if memory is not None and d % 128 == 0:
         ops.absmax(memory.reshape(-1, d), _ax(amax, 0, _AX_MEM))
+        if tokens is not None:
+            ops.absmax(tokens.reshape(-1, d), _ax(amax, 0, _AX_TOK))
     # the trajectory launches' planes: every slice of the stack in one request, so no address is resolved before a later registration grows the buffer
     slices = _traj_slices(layers, route)
     tw = dict(zip(slices, store.traj_planes(slices.values()))) if slices else {}
@@ -777,13 +814,38 @@ def _fused_stack(layers, h, heads: int, memory, dc, decoder: bool, hooks: bool, 
             _layer_input_hook(h, li)
         # traj_layers is a property of the stack: every layer passes the same shape test, and "chains" already required planes for every layer
         lw = {k: tw.get((li, k)) for k in ("w_o", "w_q", "w_oc", "w_1", "w_2", "w_n")} if route.traj_layers else None
-        cfg = _FusedCfg(heads, dc, li, decoder, layers[li + 1] if li + 1 < L else None, amax, lw)
-        h, n1, qkv = _FusedLayer.apply(h, n1, qkv, memory, cfg, *_layer_params(lp, decoder))
+        cfg = _FusedCfg(heads, dc, li, decoder, layers[li + 1] if li + 1 < L else None, amax, lw, draws)
+        h, n1, qkv = _FusedLayer.apply(h, n1, qkv, memory, tokens, cfg, *_layer_params(lp, decoder))
     return h
 
 
-def denoiser_forward_autograd(gen, x: Tensor, memory: Tensor) -> Tensor:
-    """Differentiable DiffusionActionGenerator.forward (reference ml/model/decoder.py:38-54)."""
+class _ExpandRows(Function):
+    """c (C, ...) -> (C K, ...), row b = c[b // K]; the backward sums each group of K rows in draw order (one small kernel each way)."""
+
+    @staticmethod
+    def forward(ctx, c, draws: int):
+        ctx.draws = draws
+        return ops.expand_rows(c.contiguous(), draws)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.expand_rows_bwd(dy.contiguous(), ctx.draws), None
+
+
+def expand_context(c: Tensor, draws: int) -> Tensor:
+    return _ExpandRows.apply(c, draws)
+
+
+SHARED_STACKS = [0]       # decoder stacks (draws > 1) whose draws shared the projected context: the shared cross-attention kernels ran
+EXPANDED_CONTEXTS = [0]   # decoder stacks (draws > 1) whose context was expanded to one copy per draw: the existing path ran
+
+
+def denoiser_forward_autograd(gen, x: Tensor, memory: Tensor, draws: int = 1, tokens: Optional[Tensor] = None) -> Tensor:
+    """Differentiable DiffusionActionGenerator.forward (reference ml/model/decoder.py:38-54).
+    ``draws`` = K > 1 (training with several noise draws per window): ``x`` holds C K trajectories, ``memory`` the C contexts (C, Mc, d)
+    without their step tokens and ``tokens`` (C K, 1, d) those; trajectory b reads context b // K and token b.  Where the stack runs as
+    row chains and the shared cross-attention takes the shape, K | V of the context are projected once per context (SHARED_STACKS);
+    anywhere else the context is expanded by ``expand_context`` and the call is the one with ``draws`` = 1 (EXPANDED_CONTEXTS)."""
     T = x.shape[1]
     pe = gen.positional_encoding.pe[0, :T].contiguous()
     memory = memory.contiguous()
@@ -791,12 +853,23 @@ def denoiser_forward_autograd(gen, x: Tensor, memory: Tensor) -> Tensor:
     layers = list(gen.transformer_decoder.layers)
     W = gen.embedding.weight
     params_ok, ffn_is_d, block_planes, store = _stack_facts(layers, W.shape[0], decoder=True)
-    route = train_route(decoder=True, d=W.shape[0], heads=gen.num_heads, T=T, M=memory.shape[1], J=x.shape[-1], ffn_is_d=ffn_is_d, params_ok=params_ok,
+    M = memory.shape[1] + (1 if draws > 1 else 0)
+    route = train_route(decoder=True, d=W.shape[0], heads=gen.num_heads, T=T, M=M, J=x.shape[-1], ffn_is_d=ffn_is_d, params_ok=params_ok,
                         block_planes=block_planes, traj_planes=store is not None and x.is_cuda and W.dim() == 2, x_differentiable=x.requires_grad)
+    if draws > 1:
+        tokens = tokens.contiguous()
+        # (SD_TRAIN_SHARED=0, A/B runs: the expanding route everywhere - read here and nowhere else)
+        if (route.stack == "chains" and os.environ.get("SD_TRAIN_SHARED", "1") != "0"
+                and ops.train_xattn_shared_ok(W.shape[0], gen.num_heads, T, memory.shape[1])):
+            SHARED_STACKS[0] += 1
+            route = route._replace(traj_layers=False)   # (a layer launch owns one trajectory AND its memory)
+        else:
+            EXPANDED_CONTEXTS[0] += 1
+            memory, tokens, draws = torch.cat([expand_context(memory, draws), tokens], dim=1), None, 1
     h = None if route.embed_head else _PatchEmbed.apply(x, W, gen.embedding.bias, pe)
     if route.stack == "chains":
         h = _fused_stack(layers, h, gen.num_heads, memory, dc, decoder=True, hooks=True, route=route, store=store,
-                         embed=(x, gen) if route.embed_head else None)
+                         embed=(x, gen) if route.embed_head else None, tokens=tokens, draws=draws)
     else:
         for li, lp in enumerate(layers):
             _layer_input_hook(h, li)
@@ -950,24 +1023,39 @@ def _layer_input_hook(h: Tensor, layer: int) -> None:
         h.register_hook(lambda g, l=layer: (_BUCKETS.ready(l) if _BUCKETS is not None else None, None)[1])
 
 
+def noise_draws(draws) -> int:
+    """``draws`` of a training call, validated as the samplers validate theirs (``ops._draws_req``): an int >= 1."""
+    return ops._draws_req(draws, 0, None)
+
+
 def train_step(model, optimizer: FusedAdamW, lr_scheduler, scheduler, joint_targets: Tensor, context=None,
                input_data=None, noise: Optional[Tensor] = None, timesteps: Optional[Tensor] = None,
-               world_size: int = 1, generator: Optional[torch.Generator] = None, bucketed: bool = True) -> Tensor:
+               world_size: int = 1, generator: Optional[torch.Generator] = None, bucketed: bool = True, draws: int = 1) -> Tensor:
     """One iteration of the reference loop body (train.py:204-240) on already-normalised
     targets.  ``context`` given = the --decoder-pretraining path (train.py:221-224).
+    ``draws`` = K > 1 (not in the reference): K (timestep, noise) pairs per window on ONE encoded observation - ``joint_targets`` (C, T, J)
+    and the context / ``input_data`` hold C windows, ``noise`` (C K, T, J) and ``timesteps`` (C K,) (drawn from ``generator`` when not
+    given) one entry per trajectory, trajectory b belongs to window b // K; the loss is the MSE over all C K trajectories.  Every
+    context encoder runs once per window; the result is the step on the K times repeated context.  ``draws`` = 1 is the call without it.
     Data parallel (``world_size`` > 1): the gradient all-reduce runs per decoder layer, overlapped with the rest of the
     backward (``BucketedAllReduce``); ``bucketed=False`` = one all-reduce after it.  Gradient clipping and the non-finite guard
     (``FusedAdamW(max_grad_norm=...)``) live in ``optimizer.step()``, behind the exchange: the norm is that of the reduced gradient,
     every rank computes the same coefficient and takes or skips the step together - no collective of their own."""
     global _BUCKETS
-    B = joint_targets.shape[0]
+    draws = noise_draws(draws)
+    B = joint_targets.shape[0] * draws
     dev = joint_targets.device
+    if draws > 1 and timesteps is not None and tuple(timesteps.shape) != (B,):
+        raise ValueError(f"timesteps: expected ({B},) = windows x draws entries, got {tuple(timesteps.shape)}")
+    if draws > 1 and noise is not None and tuple(noise.shape) != (B,) + tuple(joint_targets.shape[1:]):
+        raise ValueError(f"noise: expected {(B,) + tuple(joint_targets.shape[1:])} = (windows x draws, T, J), got {tuple(noise.shape)}")
     optimizer.zero_grad()
     if timesteps is None:
         timesteps = torch.randint(0, scheduler.config["num_train_timesteps"], (B,), device=dev, generator=generator).long()
     if noise is None:
-        noise = torch.randn(joint_targets.shape, device=dev, generator=generator)
-    noisy = scheduler.add_noise(joint_targets, noise, timesteps)
+        noise = torch.randn(joint_targets.shape if draws == 1 else (B,) + tuple(joint_targets.shape[1:]), device=dev, generator=generator)
+    noisy = scheduler.add_noise(joint_targets if draws == 1 else joint_targets.repeat_interleave(draws, 0), noise, timesteps)
+    kw = {} if draws == 1 else {"draws": draws}
     buckets = None
     if world_size > 1 and bucketed:
         buckets = getattr(optimizer, "_buckets", None)
@@ -976,9 +1064,9 @@ def train_step(model, optimizer: FusedAdamW, lr_scheduler, scheduler, joint_targ
     _BUCKETS = buckets            # the forward registers one hook per decoder layer while this is set
     try:
         if context is not None:
-            pred = model.forward_with_context(context, noisy, timesteps)
+            pred = model.forward_with_context(context, noisy, timesteps, **kw)
         else:
-            pred = model(input_data, noisy, timesteps)
+            pred = model(input_data, noisy, timesteps, **kw)
         loss = mse_loss(pred, noise)
         loss.backward()
         if buckets is not None:
@@ -1019,8 +1107,9 @@ class GraphedTrainStep:
     backward, then ONE flat all-reduce and the update) for A/B runs and its parity test."""
 
     def __init__(self, model, optimizer: FusedAdamW, lr_scheduler, scheduler, world_size: int = 1,
-                 generator: Optional[torch.Generator] = None, eager_steps: int = 2, split_update: Optional[bool] = None):
+                 generator: Optional[torch.Generator] = None, eager_steps: int = 2, split_update: Optional[bool] = None, draws: int = 1):
         self.model, self.opt, self.lr_sched, self.sched = model, optimizer, lr_scheduler, scheduler
+        self.draws = noise_draws(draws)   # (timestep, noise) pairs per window (train_step): the captured shapes are (windows x draws, T, J)
         self.world, self.gen, self.eager_left = world_size, generator, eager_steps
         # data parallel: the eager bucketed step (see the class comment) unless split_update is forced
         self.split = False if split_update is None else bool(split_update)
@@ -1071,16 +1160,18 @@ class GraphedTrainStep:
 
     def _body(self):
         st = self._static
-        B = st["targets"].shape[0]
+        K = self.draws
+        B = st["targets"].shape[0] * K
         dev = st["targets"].device
         self.opt.zero_grad()
         t = torch.randint(0, self.sched.config["num_train_timesteps"], (B,), device=dev, generator=self.gen).long()
-        noise = torch.randn(st["targets"].shape, device=dev, generator=self.gen)
-        noisy = self.sched.add_noise(st["targets"], noise, t)
+        noise = torch.randn((B,) + tuple(st["targets"].shape[1:]), device=dev, generator=self.gen)
+        noisy = self.sched.add_noise(st["targets"] if K == 1 else st["targets"].repeat_interleave(K, 0), noise, t)
+        kw = {} if K == 1 else {"draws": K}
         if st["context"] is not None:
-            pred = self.model.forward_with_context(st["context"], noisy, t)
+            pred = self.model.forward_with_context(st["context"], noisy, t, **kw)
         else:
-            pred = self.model(st["input"], noisy, t)
+            pred = self.model(st["input"], noisy, t, **kw)
         loss = mse_loss(pred, noise)
         loss.backward()
         if not self.split:
@@ -1094,7 +1185,7 @@ class GraphedTrainStep:
         if self.eager_left > 0 or self.eager_dp:
             self.eager_left = max(self.eager_left - 1, 0)
             return train_step(self.model, self.opt, self.lr_sched, self.sched, joint_targets, context=context,
-                              input_data=input_data, world_size=self.world, generator=self.gen)
+                              input_data=input_data, world_size=self.world, generator=self.gen, draws=self.draws)
         self._stage(joint_targets, context, input_data)
         if self.graph is None:
             ops.set_dropout_epoch(self.hyper[7:8])
